@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path's headline benchmark on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--dump-outputs DIR]
 
 A *step* is one pass of the hot path over one batch: MaskCBAM forward + backward at P3, P4 and P5 (YOLOv8n channel
 widths, 640x640 input -> 80/40/20 px feature maps, batch 32 per GPU, fp32, random masks = BASELINE.json configs[1]),
@@ -79,7 +79,13 @@ def parse():
     ap.add_argument("--no-harness", action="store_true", help="skip the train-step harness (tools/harness.py, extra key train_harness)")
     ap.add_argument("--harness-steps", type=int, default=8)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only for rehearsing the multi-rank code path on one GPU)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (per level y, gx, gmask and the parameter gradients) "
+                         "as DIR/<name>.npy in float32, for output-for-output comparison of two builds (rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def relaunch_distributed(args):
@@ -259,6 +265,43 @@ def slice_step(workload, device, steps=100, warmup=10, dtype_name="f32"):
                 note="mask heads + MaskCBAM + seg loss + Kendall, fwd + bwd, one hipGraph; dL/d(refined) and det_loss are given")
 
 
+DUMP_MAX_ELEMS = 1 << 20        # per array: a larger output is written as a fixed sample of this many elements (4 MB in float32)
+DUMP_SEED = 1234
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(plan, out_dir):
+    """Write what the timed path left in the plan's output buffers after its last step, as `out_dir/<name>.npy` (float32): per level l
+    `y_l<l>`, `gx_l<l>`, `gmask_l<l>` and the parameter gradients `gw1_l<l>` ... `gbeta_l<l>` (N > 1: after the exchange, i.e. averaged
+    over the ranks).  The backward overwrites every output, so the last step's values do not depend on --steps.  An array of more than
+    DUMP_MAX_ELEMS elements is written as a sample: the flat indices are drawn without replacement from a generator seeded by
+    (DUMP_SEED, size) and sorted, so the same arguments give the same positions in every run.  Returns (arrays, bytes) written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for l in range(plan.n):
+        arrays[f"y_l{l}"], arrays[f"gx_l{l}"] = plan.y[l], plan.gx[l]
+        if plan.gmask[l] is not None:
+            arrays[f"gmask_l{l}"] = plan.gmask[l]
+        for name, g in plan.named_param_grads(l).items():
+            arrays[f"{name}_l{l}"] = g
+    torch.cuda.synchronize(plan.device)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:                                    # 1-D sample; smaller arrays keep their shape
+            idx = np.sort(np.random.default_rng([DUMP_SEED, n]).choice(n, DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB for this workload")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return len(arrays), total
+
+
 def host_cpu_info():
     model = "unknown"
     try:
@@ -434,6 +477,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:          # before time_kernels: it reissues the step's launches one stage at a time
+        n_arrays, n_bytes = dump_outputs(plan, args.dump_outputs)
+        dumped = dict(dir=os.path.abspath(args.dump_outputs), arrays=n_arrays, bytes=n_bytes, sample_max_elems=DUMP_MAX_ELEMS)
 
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * batch * args.steps / elapsed
@@ -515,7 +562,7 @@ def main():
                                 handoff_kernels=bool(plan.fuse_forward)),
                     roofline=roofline, step_roofline=step_roof, kernels=kernels, cpu_baseline=cpu,
                     eager_module_ms_per_step=eager_ms, eager_module_ms_per_step_engine_inline=eager_inline_ms, layer_loop_slice=slice_res,
-                    train_harness=harness_res,
+                    train_harness=harness_res, dump_outputs=dumped,
                     eager_module_note="the unchanged reference layer loop's path: three MaskCBAM modules through autograd, one library call per level each way, launches issued from Python (no PyramidPlan / hipGraph), gradients reset to None every step as the trainer does; engine_inline = autograd engine on the calling thread (the blocks' marginal cost inside a whole-model backward, which pays the engine's worker-thread wake-up once for all layers)",
                     lib=_lib.load().mgacbam_build_info().decode())
         print(json.dumps(line))
