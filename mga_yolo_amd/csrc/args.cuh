@@ -86,7 +86,8 @@ struct BwdArgs {
   int bflag0;   // first backward hand-off flag in c.sync (ints): [B][nflag], one per k_bwd_reduce1 tile
   int cflag0;   // first flag of the folded transposed-conv tiles in c.sync: [nconv], generation counters like the tile flags
   int wflag0;   // ... of the dWsa tile roles when they ride in the merged launch: [nwsa]
-  int sflag0;   // ... of k_bwd_reduce2's sweep workgroups in the merged launch: [B][C] (a sample's channel groups are its first ncg entries)
+  int sflag0;   // ... of k_bwd_reduce2's sweep workgroups in the merged launch: [B][C], one counter per CHANNEL (a sweep reads its first
+                // channel's, bumps all of its own): the channel grouping depends on the call's other levels, the counts do not
   int mbflag0, mcflag0;   // the merged launch's own tile / conv-tile flags (the host puts them into bflag0 / cflag0 for that launch)
   int merged;   // 1: k_bwd_reduce1 tiles, transposed-conv tiles, dWsa tiles and k_bwd_reduce2 sweeps are ONE launch (k_bwd_r12)
   unsigned spin_limit;

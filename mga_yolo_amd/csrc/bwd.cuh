@@ -403,12 +403,16 @@ __device__ __forceinline__ void bwd_reduce2_body(const BwdArgs& A, const int bid
   __amdgpu_buffer_rsrc_t gprs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gp0), 0, 2 * g.HW * 4, 0x00020000);
   if (COH) {
     // this sample's transposed-conv tiles (lower workgroup ids of this launch) publish g_planes; they in turn waited for the sample's
-    // k_bwd_reduce1 tiles, so the tile partials read below are out as well.  Own generation counter, bounded wait, NaN on time-out.
-    int* own = A.c.sync + A.sflag0 + static_cast<size_t>(b) * g.C + cg;
+    // k_bwd_reduce1 tiles, so the tile partials read below are out as well.  Bounded wait, NaN on time-out.
+    // The generation is counted per CHANNEL, not per channel group: CPB (group_cpt) depends on the other levels of the call, but every
+    // merged launch covers each channel of the sample exactly once, so every counter equals the number of merged launches this ctx has
+    // seen under any call composition.  The group reads its first channel's counter and bumps all of its channels'.
+    int* own = A.c.sync + A.sflag0 + static_cast<size_t>(b) * g.C + cg * CPB;
     const int gen = static_cast<int>(static_cast<unsigned>(ld_agent(own)) + 1u);
     const int cps = A.nconv / g.B;                                // conv tiles per sample (sample-major ids)
     bad = handoff_wait(A.c.sync + A.cflag0, b * cps, b * cps + cps - 1, gen, A.c.sync + static_cast<size_t>(g.B) * A.nflag, A.spin_limit);
-    if (tid == 0) __hip_atomic_fetch_add(own, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int nch = min(CPB, g.C - cg * CPB);                     // (handoff_wait ends in a barrier: every lane has read gen by now)
+    for (int c = tid; c < nch; c += kBlock) __hip_atomic_fetch_add(own + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 
   constexpr int PF = MGACBAM_POOL_PF;                         // positions per lane per memory round (see k_pool)
@@ -546,6 +550,8 @@ __global__ __launch_bounds__(kBlock) BWD_OCC void k_bwd_reduce2(const Group<BwdA
 //   start while the last tiles still stream.  All four bodies fit 64 VGPRs (occupancy 7-8): k_bwd_apply (104) stays a launch of its own
 //   -- capped at its 4 waves per SIMD these two kernels lose 9 us at config 2.
 //   The merged launch has generation counters of its own for every class (args.cuh): the fold form may run on the same ctx in between.
+//   The sweeps' channel groups (cpt = group_cpt over ALL levels of the call) change with the call's composition; their counters are per
+//   channel (bwd_reduce2_body), so a ctx may be reused under any composition.
 // ---------------------------------------------------------------------------------------------
 struct R12Group {
   Group<BwdArgs> g;

@@ -80,7 +80,7 @@ static void ctx_layout(int B, int C, int H, int W, int hidden, mgacbam_ctx_layou
   L->sa = take(static_cast<size_t>(B) * HW);
   L->proj = take(hidden <= MGACBAM_PROJ_MAX_HIDDEN ? static_cast<size_t>(B) * hidden * HW : 0);
   // hand-off state: [B][nflag] k_gate tile flags, 4 status words, [B] ca flags, [B][nflag] k_bwd_reduce1 tile flags, [B][nflag] folded
-  // conv-tile flags; merged backward launch (k_bwd_r12): [B][nflag] tile, [B][nflag] conv-tile, [B][nflag] dWsa-tile and [B][C] sweep flags
+  // conv-tile flags; merged backward launch (k_bwd_r12): [B][nflag] tile, [B][nflag] conv-tile, [B][nflag] dWsa-tile and [B][C] per-channel sweep flags
   // (the merged launch has tile / conv-tile flags of its OWN beside its dWsa-tile and sweep flags: every class of generation counters is
   //  bumped exactly once per launch of its kind, so the two launch forms can alternate on one ctx without their counters drifting apart)
   L->sync = take(6 * static_cast<size_t>(B) * sync_flags(HW) + 4 + B + static_cast<size_t>(B) * C);

@@ -227,8 +227,9 @@ class _PyramidFn(torch.autograd.Function):
             y = torch.empty_like(xc)
             # FWD_FUSE / BWD_FOLD contract: the hand-off flags at the end of ctx were zero-filled once (by the pool, at creation)
             # (the flags count calls PER TILE, so a buffer is only reused under the tiling it was used with.  The library derives every
-            #  tiling from the level alone -- shape, element type, conv size k, knobs; never from the other levels of the call -- and
-            #  exactly those are in the key)
+            #  flagged tiling from the level alone -- shape, element type, conv size k, knobs; never from the other levels of the call --
+            #  and exactly those are in the key.  The merged backward's sweeps, whose channel groups do depend on the call, count per
+            #  channel instead: tests/test_gpu_composition.py)
             key = (dev.index, stream, B, Cc, H, W, cfg.hidden, x.dtype, _lib.ENV_EPOCH, cfg.k)
             lease = _Lease(key, _POOL.take(key, _lib.ctx_bytes(B, Cc, H, W, cfg.hidden), _lib.ctx_layout(B, Cc, H, W, cfg.hidden)["sync"], dev))
             cbuf = lease.buf
