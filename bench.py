@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path's headline benchmark on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path over one batch: MaskCBAM forward + backward at P3, P4 and P5 (YOLOv8n channel
 widths, 640x640 input -> 80/40/20 px feature maps, batch 32 per GPU, fp32, random masks = BASELINE.json configs[1]),
@@ -12,8 +12,12 @@ starts.  For N > 1 the driver starts one process per GPU with torch.distributed.
 MASTER_* are read from the environment.  Rank 0 prints ONE JSON line:
 
   value        images/s over all N GPUs = N * batch / step time (max over ranks)             "scaling": "weak"
+
+A plain run does only what that line needs: set up, W warm-up steps, the K timed steps, --dump-outputs if given.  With --full the
+line also carries what takes work of its own after the timed steps (all of it absent from a plain run):
   roofline     the dominant kernel: algorithmic bytes per launch / its mean duration (events on the launch stream)
   kernels      the same for every HBM-bound kernel, plus the whole step against SURVEY 8d's 8*E*4 bytes
+  eager_module_ms_per_step / layer_loop_slice / train_harness   the module path, the layer-loop slice, the train-step harness
   cpu_baseline the oracle's eager-op form (same op sequence as the reference's PyTorch-CPU path) timed on this
                box's host cores on a bounded sample (rank 0, N = 1 only)
 """
@@ -68,6 +72,10 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="issue every launch from Python instead of replaying hipGraphs")
     ap.add_argument("--steps-per-graph", type=int, default=1,
                     help="N = 1 only: steps recorded per hipGraph (diagnostic of the launch gap; the headline uses 1 = one replay per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: per-kernel durations and roofline, the eager "
+                         "module path, the layer-loop slice, the train-step harness and the CPU baseline (the --no-* / --kernel-reps / "
+                         "--cpu-seconds / --harness-steps options below shape these and do nothing without --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-eager", action="store_true", help="skip the eager-module (unchanged-trainer) timing")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the bounded CPU-baseline sample (>= 50 iterations at config 2 need ~15 s)")
@@ -485,67 +493,74 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * batch * args.steps / elapsed
 
-    # ---- per-kernel durations on this GPU, isolated launches on the same stream -------------------------------
-    kt = time_kernels(plan, args.kernel_reps)
-    E = plan.elements()
-    w = 4 if args.dtype == "f32" else 2
-    kernels = {}
-    event_pad = kt.pop("_event_pad_us")
-    fast75 = kt.pop("_fast75")
-    symbols = dict(KERNEL_SYMBOL, **(KERNEL_SYMBOL_FOLD if kt.pop("_folded") else {}))   # (bwd.r12 has its own entry)
-    for name, us in kt.items():
-        side, k = name.split(".")
-        mult = (FWD_KERNEL_E if side == "fwd" else BWD_KERNEL_E).get(k)
-        ent = dict(us=round(us, 2), us_fastest75=round(fast75[name], 2), launches=1, symbol=symbols[name])
-        if mult:
-            ent["alg_bytes"] = mult * E * w
-            ent["GBps"] = round(mult * E * w / us / 1e3, 1)
-        kernels[name] = ent
-    dom = max((n for n in kernels if "alg_bytes" in kernels[n]), key=lambda n: kernels[n]["us"])
-    # roofline.traffic = HBM bytes per launch from the PMC counters: they need rocprofv3 passes of their own (FETCH_SIZE / WRITE_SIZE,
-    # MI355X_MICROARCH.md), so the figure is NOT measured in this run -- it is read from the committed summary of the last
-    # profiling run and tagged with where it came from
-    traffic, traffic_source = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            traffic = tj.get(args.workload if args.dtype == "f32" else f"{args.workload}_{args.dtype}", {}).get(symbols[dom])
-            src = tj.get("_source")
-            traffic_source = src.get(args.workload) if isinstance(src, dict) else src
-        except Exception:
-            traffic = None
-    roofline = dict(bound="hbm", kernel=symbols[dom], stage=dom, achieved=kernels[dom]["GBps"], peak=HBM_PEAK_GBPS, unit="GB/s",
-                    frac=round(kernels[dom]["GBps"] / HBM_PEAK_GBPS, 4), traffic=traffic, traffic_source=traffic_source,
-                    alg_bytes_per_launch=kernels[dom]["alg_bytes"], us=kernels[dom]["us"],
-                    note="one launch covers P3+P4+P5; duration = plain mean over the repetitions of the elapsed time between an event recorded before and one after the launch, on the launch stream, with the step issued in order")
-    step_alg = 8 * E * w                                           # forward 3*E*w + backward 5*E*w
-    step_roof = dict(alg_bytes=step_alg, GBps=round(step_alg / (ms_per_step * 1e-3) / 1e9, 1),
-                     frac=round(step_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                     sum_kernel_us=round(sum(kt.values()), 1), event_pad_us=round(event_pad, 2))
+    extra = {}                   # what --full adds to the line; a plain run measures nothing after the timed steps
+    if args.full:
+        # ---- per-kernel durations on this GPU, isolated launches on the same stream -------------------------------
+        kt = time_kernels(plan, args.kernel_reps)
+        E = plan.elements()
+        w = 4 if args.dtype == "f32" else 2
+        kernels = {}
+        event_pad = kt.pop("_event_pad_us")
+        fast75 = kt.pop("_fast75")
+        symbols = dict(KERNEL_SYMBOL, **(KERNEL_SYMBOL_FOLD if kt.pop("_folded") else {}))   # (bwd.r12 has its own entry)
+        for name, us in kt.items():
+            side, k = name.split(".")
+            mult = (FWD_KERNEL_E if side == "fwd" else BWD_KERNEL_E).get(k)
+            ent = dict(us=round(us, 2), us_fastest75=round(fast75[name], 2), launches=1, symbol=symbols[name])
+            if mult:
+                ent["alg_bytes"] = mult * E * w
+                ent["GBps"] = round(mult * E * w / us / 1e3, 1)
+            kernels[name] = ent
+        dom = max((n for n in kernels if "alg_bytes" in kernels[n]), key=lambda n: kernels[n]["us"])
+        # roofline.traffic = HBM bytes per launch from the PMC counters: they need profiler passes of their own (FETCH_SIZE and
+        # WRITE_SIZE do not fit one pass), so the figure is NOT measured in this run -- it is read from the committed summary of the
+        # last profiling run and tagged with where it came from
+        traffic, traffic_source = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                traffic = tj.get(args.workload if args.dtype == "f32" else f"{args.workload}_{args.dtype}", {}).get(symbols[dom])
+                src = tj.get("_source")
+                traffic_source = src.get(args.workload) if isinstance(src, dict) else src
+            except Exception:
+                traffic = None
+        roofline = dict(bound="hbm", kernel=symbols[dom], stage=dom, achieved=kernels[dom]["GBps"], peak=HBM_PEAK_GBPS, unit="GB/s",
+                        frac=round(kernels[dom]["GBps"] / HBM_PEAK_GBPS, 4), traffic=traffic, traffic_source=traffic_source,
+                        alg_bytes_per_launch=kernels[dom]["alg_bytes"], us=kernels[dom]["us"],
+                        note="one launch covers P3+P4+P5; duration = plain mean over the repetitions of the elapsed time between an event recorded before and one after the launch, on the launch stream, with the step issued in order")
+        step_alg = 8 * E * w                                           # forward 3*E*w + backward 5*E*w
+        step_roof = dict(alg_bytes=step_alg, GBps=round(step_alg / (ms_per_step * 1e-3) / 1e9, 1),
+                         frac=round(step_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                         sum_kernel_us=round(sum(kt.values()), 1), event_pad_us=round(event_pad, 2))
 
-    eager_ms = eager_inline_ms = None
-    if rank == 0 and world == 1 and not args.no_eager:
-        eager_ms = round(eager_module_step(args.workload, device, args.dtype), 4)
-        eager_inline_ms = round(eager_module_step(args.workload, device, args.dtype, engine_inline=True), 4)
-        from mga_yolo_amd import handoff_report
-        handoff_report()
-    slice_res = None
-    if rank == 0 and world == 1 and not args.no_eager:
-        slice_res = slice_step(args.workload, device, dtype_name=args.dtype)
-    # SURVEY 8d images/s definition (2): the train-step harness, under DDP when N > 1 (every rank takes part)
-    harness_res = None
-    if not args.no_harness and not args.no_eager:
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import harness
-            harness_res = harness.run(MODEL_SCALE.get(args.workload, "n"), batch=batch, size=1280 if args.workload == "cfg4" else 640,
-                                      steps=args.harness_steps, warmup=3, device=device, world=world, rank=rank)
-        except Exception as e:                                    # the harness is an extra key: its failure must not cost the headline line
-            harness_res = dict(error=f"{type(e).__name__}: {e}"[:300])
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(args.workload, args.cpu_seconds)
+        eager_ms = eager_inline_ms = None
+        if rank == 0 and world == 1 and not args.no_eager:
+            eager_ms = round(eager_module_step(args.workload, device, args.dtype), 4)
+            eager_inline_ms = round(eager_module_step(args.workload, device, args.dtype, engine_inline=True), 4)
+            from mga_yolo_amd import handoff_report
+            handoff_report()
+        slice_res = None
+        if rank == 0 and world == 1 and not args.no_eager:
+            slice_res = slice_step(args.workload, device, dtype_name=args.dtype)
+        # SURVEY 8d images/s definition (2): the train-step harness, under DDP when N > 1 (every rank takes part)
+        harness_res = None
+        if not args.no_harness and not args.no_eager:
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                import harness
+                harness_res = harness.run(MODEL_SCALE.get(args.workload, "n"), batch=batch, size=1280 if args.workload == "cfg4" else 640,
+                                          steps=args.harness_steps, warmup=3, device=device, world=world, rank=rank)
+            except Exception as e:                                    # the harness is an extra key: its failure must not cost the headline line
+                harness_res = dict(error=f"{type(e).__name__}: {e}"[:300])
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(args.workload, args.cpu_seconds)
+
+        extra = dict(roofline=roofline, step_roofline=step_roof, kernels=kernels, cpu_baseline=cpu,
+                     eager_module_ms_per_step=eager_ms, eager_module_ms_per_step_engine_inline=eager_inline_ms, layer_loop_slice=slice_res,
+                     train_harness=harness_res,
+                     eager_module_note="the unchanged reference layer loop's path: three MaskCBAM modules through autograd, one library call per level each way, launches issued from Python (no PyramidPlan / hipGraph), gradients reset to None every step as the trainer does; engine_inline = autograd engine on the calling thread (the blocks' marginal cost inside a whole-model backward, which pays the engine's worker-thread wake-up once for all layers)")
 
     if rank == 0:
         line = dict(metric="images/s (MaskCBAM fwd+bwd step at P3/P4/P5, YOLOv8n 640x640)", value=round(value, 1), unit="images/s",
@@ -560,11 +575,7 @@ def main():
                                     total_bytes=exchange.nbytes(),
                                     placement="started after the backward that produces the gradients, overlapped with the next step's parameter-free k_pool, joined before the first kernel that reads a parameter (the DDP contract); the payload stands for the out-of-scope layers' gradients, whose own backward -- absent here -- is what hides most of it in a whole-model step (see train_harness)"),
                                 handoff_kernels=bool(plan.fuse_forward)),
-                    roofline=roofline, step_roofline=step_roof, kernels=kernels, cpu_baseline=cpu,
-                    eager_module_ms_per_step=eager_ms, eager_module_ms_per_step_engine_inline=eager_inline_ms, layer_loop_slice=slice_res,
-                    train_harness=harness_res, dump_outputs=dumped,
-                    eager_module_note="the unchanged reference layer loop's path: three MaskCBAM modules through autograd, one library call per level each way, launches issued from Python (no PyramidPlan / hipGraph), gradients reset to None every step as the trainer does; engine_inline = autograd engine on the calling thread (the blocks' marginal cost inside a whole-model backward, which pays the engine's worker-thread wake-up once for all layers)",
-                    lib=_lib.load().mgacbam_build_info().decode())
+                    full=args.full, **extra, dump_outputs=dumped, lib=_lib.load().mgacbam_build_info().decode())
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

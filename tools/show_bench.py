@@ -9,7 +9,9 @@ for f in sys.argv[1:]:
         if not l.startswith("{"):
             continue
         d = json.loads(l)
-        print(f"  value {d['value']} img/s   ms/step {d['ms_per_step']}   step: {d['step_roofline']}")
+        print(f"  value {d['value']} img/s   ms/step {d['ms_per_step']}   step: {d.get('step_roofline')}")
+        if "kernels" not in d:                    # a plain run's line: per-kernel figures come with bench.py --full
+            continue
         r = d["roofline"]
         print(f"  dominant {r['kernel']} {r['achieved']} GB/s frac {r['frac']} ({r['us']} us)")
         print("  " + "  ".join(f"{k.split('.')[0][0]}.{k.split('.')[1]}={v['us']}us" + (f"({v['GBps']:.0f}GB/s)" if 'GBps' in v else "") for k, v in d["kernels"].items()))

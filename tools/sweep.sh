@@ -5,7 +5,7 @@
 # MGACBAM_CHAN_MINTX, MGACBAM_LEVEL_ORDER, MGACBAM_NT, MGACBAM_HALF_VEC) or MGACBAM_LIB=<path> for an A/B build made with
 # mga_yolo_amd.build.build(defines=[...], out=...).  Differences below ~2 % are run-to-run / box-to-box noise.
 WL=${1:-cfg2}
-run() { echo "## $*"; env "$@" python bench.py --workload $WL --steps 100 --warmup 10 --no-cpu-baseline --kernel-reps 20 2>/dev/null | python tools/show_bench.py /dev/stdin | grep -E "value|f.pool"; }
+run() { echo "## $*"; env "$@" python bench.py --full --workload $WL --steps 100 --warmup 10 --no-cpu-baseline --kernel-reps 20 2>/dev/null | python tools/show_bench.py /dev/stdin | grep -E "value|f.pool"; }
 run BASE=1
 for tx in 16 32 64; do run MGACBAM_CHAN_TX=$tx; done
 for cpt in 1 2 4; do run MGACBAM_POOL_CPT=$cpt; done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # launch-geometry sweep at a workload (default cfg4): one bench line per variant, per-kernel table printed by tools/show_bench.py
 WL=${1:-cfg4}; OUT=gpurun_out/${2:-sweep4}; mkdir -p $OUT
-run() { tag=$1; shift; env "$@" python bench.py --workload $WL --steps 50 --warmup 5 --no-cpu-baseline --no-eager --kernel-reps 20 > $OUT/$tag.json 2> $OUT/$tag.err || echo "$tag failed"; }
+run() { tag=$1; shift; env "$@" python bench.py --full --workload $WL --steps 50 --warmup 5 --no-cpu-baseline --no-eager --kernel-reps 20 > $OUT/$tag.json 2> $OUT/$tag.err || echo "$tag failed"; }
 run base X=1
 run cpt1 MGACBAM_POOL_CPT=1
 run cpt4 MGACBAM_POOL_CPT=4
