@@ -131,7 +131,7 @@ typedef struct mgacbam_ctx_layout {
   int64_t sa;       /* (B,HW)   spatial gate                              masked_cbam.py:147 */
   int64_t proj;     /* (B,hid,HW) W1-projection of x, only when hid <= MGACBAM_PROJ_MAX_HIDDEN (else empty)  */
   int64_t sync;     /* int32 hand-off state, generation counters that are never reset: (B, ceil(HW/16)+1) tile flags of MGACBAM_FWD_FUSE
-                       (see there), 4 status words ([0] time-out, [1] [2] arrival counters of the dWsa tail roles: 0 between calls), (B) ca
+                       (see there), 4 status words ([0] time-out, [1] .. [3] reserved, left as zero-filled), (B) ca
                        flags, 2 x (B, ceil(HW/16)+1) MGACBAM_BWD_FOLD tile / conv-tile flags; the merged backward launch's own 3 x (B, ceil(HW/16)+1)
                        tile / conv-tile / dWsa-tile flags and (B, C) per-channel sweep flags */
   int64_t total;    /* == mgacbam_ctx_bytes()                                                 */
@@ -206,11 +206,7 @@ enum {
                                  sweeps of a sample wait for its conv tiles inside the launch; generation counters of its own in ctx.sync,
                                  so both launch forms may alternate on one ctx.  Every counter counts launches per tile or per channel,
                                  never per channel group, so a ctx may also be reused under any call composition (alone or with
-                                 other levels, gmask requested or not), although the sweeps' channel grouping depends on the call.  The backward is then 2 launches (4 per step).
-                                 Knob MGACBAM_WSA_TAIL=1 (opt-in, measured slower at BASELINE configs[1]): with WSA + PARAMGRAD + APPLY +
-                                 FUSE in the same call the flag also moves the dWsa tile partials from the front of the REDUCE2 launch
-                                 to the END of the APPLY launch, followed by the workgroups that sum them in the fixed order (bitwise
-                                 reproducible) once an arrival counter (status words 1, 2 of ctx.sync, 0 between calls) says so      */
+                                 other levels, gmask requested or not), although the sweeps' channel grouping depends on the call.  The backward is then 2 launches (4 per step). */
 };
 int mgacbam_forward_stages(const mgacbam_fwd_level_t* levels, int n_levels, int stages, void* stream);
 int mgacbam_backward_stages(const mgacbam_bwd_level_t* levels, int n_levels, int stages, void* stream);

@@ -12,7 +12,7 @@ static int backward_args(const mgacbam_bwd_level_t& L, BwdArgs& A, Sig& sig) {
   if (int e = check_params(L.p)) return e;
   if (int e = check_shape(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k)) return e;
   if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "backward: dtype %d", L.dtype);
-  const int VEC = vec_of(L.H, L.W, L.dtype);
+  const int VEC = vec_of(L.H, L.W);
   const size_t need = VEC * elem_size(L.dtype);
   if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
       !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 16)))
@@ -22,8 +22,8 @@ static int backward_args(const mgacbam_bwd_level_t& L, BwdArgs& A, Sig& sig) {
   A.c = ctx_ptrs(const_cast<void*>(L.ctx), L.B, L.C, L.H, L.W, L.p.hidden);
   A.p = make_params(L.p);
   A.g = make_geo(L.B, L.C, L.H, L.W, L.p);
-  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k, L.dtype);
-  const ScratchLayout SL = scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k, L.dtype);
+  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k);
+  const ScratchLayout SL = scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k);
   {
     mgacbam_ctx_layout_t CL;
     ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, &CL);
@@ -40,8 +40,6 @@ static int backward_args(const mgacbam_bwd_level_t& L, BwdArgs& A, Sig& sig) {
   A.nt = chan_tiles(A.t, A.g.H, A.g.W, VEC);
   A.nconv = A.g.B * conv_tiles(A.t, A.g.H, A.g.W);
   A.nwsa = A.g.B * wsa_tiles(A.t, A.g.H, A.g.W);
-  A.nrole = A.nwsa;
-  A.wsa_tail = 0;
   A.npg = params_blocks(A.g);
   A.ncg = 0;
   A.nflag = static_cast<int>(sync_flags(static_cast<size_t>(L.H) * L.W));
@@ -63,8 +61,8 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
   G.n = n;
   // k_bwd_reduce2 re-reads three planes (g_planes x 2, cidx) per channel group: 4 channels per row halve that share of its loads
   // (config 4: 88 -> 80 us) whenever the grid still fills the chip; k_pool (one mask plane per group) measured slower with 4
-  const int r2max = knobs().r2_cpt == 1 || knobs().r2_cpt == 2 || knobs().r2_cpt == 4 ? knobs().r2_cpt : 4;
-  const int cpt = group_cpt(lv, n, r2max);
+  constexpr int kReduce2MaxCpt = 4;
+  const int cpt = group_cpt(lv, n, kReduce2MaxCpt);
   for (int l = 0; l < n; ++l) {
     lv[l].t.pool_cpt = cpt;
     const int cpb = (kBlock / lv[l].t.pool_tx) * cpt;
@@ -77,25 +75,22 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
   // least one image row and at least kSyncPx pixels -- one flag per tile in ctx.sync -- and few tiles per conv window)
   // (the conv tiles are the LAST workgroups of the launch and wait only for lower-numbered producers, which never wait themselves:
   //  progress does not depend on residency; the span bound is a speed heuristic)
-  bool fold = (stages & MGACBAM_BWD_FOLD) && (stages & MGACBAM_BWD_REDUCE1) && (stages & MGACBAM_BWD_CONVT) && knobs().bwd_fold;
+  bool fold = (stages & MGACBAM_BWD_FOLD) && (stages & MGACBAM_BWD_REDUCE1) && (stages & MGACBAM_BWD_CONVT);
   for (int l = 0; l < n && fold; ++l) {
     const int TP = lv[l].t.chan_tx * sig.vec;
     fold = TP >= kSyncPx && TP >= lv[l].g.W && 8 * (((lv[l].t.conv_th + lv[l].g.k) * lv[l].g.W + TP - 1) / TP + 1) <= 512 &&
            lv[l].nconv <= lv[l].g.B * lv[l].nflag;                 // one flag per conv tile fits the region reserved in ctx.sync
   }
   // k_bwd_r12: the folded launch AND k_bwd_reduce2 with its dWsa roles as one launch (bwd.cuh), when both stages are in this call
-  const bool fuse_early = (stages & MGACBAM_BWD_FUSE) != 0;
-  const bool tail_early = fuse_early && (stages & MGACBAM_BWD_APPLY) && (stages & MGACBAM_BWD_PARAMGRAD) && (stages & MGACBAM_BWD_WSA) && sig.k == 7 &&
-                          knobs().wsa_tail;
-  bool merge = fold && fuse_early && (stages & MGACBAM_BWD_REDUCE2) && (stages & MGACBAM_BWD_WSA) && sig.k == 7 && !tail_early && knobs().bwd_merge &&
-               !knobs().wsa_fat;
+  const bool fuse = (stages & MGACBAM_BWD_FUSE) != 0;
+  bool merge = fold && fuse && (stages & MGACBAM_BWD_REDUCE2) && (stages & MGACBAM_BWD_WSA) && sig.k == 7 && knobs().bwd_merge;
   for (int l = 0; l < n && merge; ++l) merge = lv[l].nwsa <= lv[l].g.B * lv[l].nflag && lv[l].ncg <= lv[l].g.C && lv[l].nconv % lv[l].g.B == 0;
   if (merge) {
     R12Group R;
     R.g.n = n;
     size_t smem = 0;
     for (int l = 0; l < n; ++l) {
-      lv[l].merged = 1; lv[l].bflag0 = lv[l].mbflag0; lv[l].cflag0 = lv[l].mcflag0; lv[l].nrole = lv[l].nwsa;
+      lv[l].merged = 1; lv[l].bflag0 = lv[l].mbflag0; lv[l].cflag0 = lv[l].mcflag0;
       R.g.lv[l] = lv[l];
       smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec), convT_smem(lv[l].t, sig.k), wsa_smem(lv[l].t, sig.k),
                        (64 + static_cast<size_t>(std::max(kPghLds, kBlock / lv[l].t.pool_tx))) * sizeof(float)});
@@ -147,45 +142,15 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
     }
     if (int e = launch_status("k_bwd_convT")) return e;
   }
-  const bool fuse = (stages & MGACBAM_BWD_FUSE) != 0;
   const bool fuse_pg = fuse && (stages & MGACBAM_BWD_APPLY) && (stages & MGACBAM_BWD_PARAMGRAD);
-  // dWsa tile partials: leading roles of k_bwd_reduce2; or (opt-in knob MGACBAM_WSA_TAIL, measured slower: bwd.cuh) the LAST workgroups
-  // of the k_bwd_apply launch when ctx.sync is the zero-filled hand-off state (MGACBAM_BWD_FOLD's contract: the arrival counters live there)
-  // (a staged caller asks for it by passing MGACBAM_BWD_WSA with the APPLY call instead of the REDUCE2 call: bench.py's per-kernel timing)
-  const bool wsa_tail = fuse_pg && (stages & MGACBAM_BWD_FOLD) && (stages & MGACBAM_BWD_WSA) && sig.k == 7 && knobs().wsa_tail;
-  const bool fuse_wsa = fuse && (stages & MGACBAM_BWD_REDUCE2) && (stages & MGACBAM_BWD_WSA) && sig.k == 7 && !wsa_tail;
-  if (wsa_tail) for (int l = 0; l < n; ++l) { lv[l].wsa_tail = 1; G.lv[l].wsa_tail = 1; }
+  const bool fuse_wsa = fuse && (stages & MGACBAM_BWD_REDUCE2) && (stages & MGACBAM_BWD_WSA) && sig.k == 7;   // dWsa tile partials: leading roles of k_bwd_reduce2
   if ((stages & MGACBAM_BWD_REDUCE2) && !merge) {  // 3. rest of g_ca (needs g_planes), g_z [+ dWsa partials as role workgroups]
     size_t smem = 0;
     for (int l = 0; l < n; ++l) {
       smem = std::max(smem, (64 + static_cast<size_t>(std::max(kPghLds, kBlock / lv[l].t.pool_tx))) * sizeof(float));
       if (fuse_wsa) smem = std::max(smem, wsa_smem(lv[l].t, sig.k));
     }
-    if (fuse_wsa && knobs().wsa_fat) {
-      // experiment (MGACBAM_WSA_FAT=1, off by default): as many dWsa roles as the streaming workgroups leave slots idle (config 2: 1792 of
-      // 2048), each working through several tiles, instead of one thin role per tile.  Measured at configs 2 and 3: no change (26.9-27.2 us
-      // either way) -- what the roles add to the launch (5.5 us over the role-free kernel) is not slot displacement
-      int slots = 0;
-#define RES_R22(CPTV) slots = resident_workgroups(k_bwd_reduce2<TT, VV, CPTV, true>, smem)
-#define RES_R2(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, RES_R22); }
-      DISPATCH_T_VEC(sig.dtype, sig.vec, RES_R2);
-#undef RES_R2
-#undef RES_R22
-      long long streaming = 0, tiles = 0;
-      for (int l = 0; l < n; ++l) {
-        const int cpb = (kBlock / lv[l].t.pool_tx) * cpt;
-        streaming += static_cast<long long>(lv[l].g.B) * ((lv[l].g.C + cpb - 1) / cpb);
-        tiles += lv[l].nwsa;
-      }
-      const long long idle = slots - streaming;
-      if (idle >= 32 && idle < tiles) {
-        for (int l = 0; l < n; ++l) {
-          lv[l].nrole = static_cast<int>(std::max(1ll, std::min<long long>(lv[l].nwsa, idle * lv[l].nwsa / tiles)));
-          G.lv[l].nrole = lv[l].nrole;
-        }
-      }
-    }
-    const int grid = fill([&](const BwdArgs& a) { return (fuse_wsa ? pad8(a.nrole) : 0) + sweep_blocks(a, a.t.pool_tx, cpt); });
+    const int grid = fill([&](const BwdArgs& a) { return (fuse_wsa ? pad8(a.nwsa) : 0) + sweep_blocks(a, a.t.pool_tx, cpt); });
 #define CALL_R22(CPTV) if (fuse_wsa) LAUNCH((k_bwd_reduce2<TT, VV, CPTV, true>), grid, smem, st, G); else LAUNCH((k_bwd_reduce2<TT, VV, CPTV, false>), grid, smem, st, G)
 #define CALL_R2(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_R22); }
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R2);
@@ -193,7 +158,7 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
 #undef CALL_R22
     if (int e = launch_status("k_bwd_reduce2")) return e;
   }
-  if ((stages & MGACBAM_BWD_WSA) && !fuse_wsa && !wsa_tail && !merge) {  // 4. dWsa tile partials (depends on stage 1 only)
+  if ((stages & MGACBAM_BWD_WSA) && !fuse_wsa && !merge) {  // 4. dWsa tile partials (depends on stage 1 only)
     size_t smem = 0;
     for (int l = 0; l < n; ++l) smem = std::max(smem, wsa_smem(lv[l].t, sig.k));
     const int grid = fill([&](const BwdArgs& a) { return a.nwsa; });
@@ -217,9 +182,8 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
     for (int l = 0; l < n; ++l) {
       smem = std::max(smem, bwd_apply_smem(lv[l].g, sig.vec));
       if (fuse_pg) smem = std::max(smem, params_smem(lv[l].g));
-      if (wsa_tail) smem = std::max(smem, wsa_smem(lv[l].t, sig.k));
     }
-    const int grid = fill([&](const BwdArgs& a) { return (fuse_pg ? pad8(a.npg) : 0) + xcd_grid(a.g.B, a.nt) + (wsa_tail ? a.nwsa + (3 * a.g.k * a.g.k + 3) / 4 : 0); });
+    const int grid = fill([&](const BwdArgs& a) { return (fuse_pg ? pad8(a.npg) : 0) + xcd_grid(a.g.B, a.nt); });
 #define CALL_AP2(GM) if (fuse_pg) LAUNCH((k_bwd_apply<TT, VV, GM, true>), grid, smem, st, G); else LAUNCH((k_bwd_apply<TT, VV, GM, false>), grid, smem, st, G)
 #define CALL_AP(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; if (sig.gmask) { CALL_AP2(true); } else { CALL_AP2(false); } }
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_AP);

@@ -78,7 +78,7 @@ extern "C" int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_
     if (int e = eca_check_params(L.p)) return e;
     if (int e = check_shape(L.B, L.C, L.H, L.W, 1, L.p.k)) return e;
     if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "eca forward: dtype %d", L.dtype);
-    const int VEC = vec_of(L.H, L.W, L.dtype);
+    const int VEC = vec_of(L.H, L.W);
     const size_t need = VEC * elem_size(L.dtype);
     if (!aligned_to(L.x, need) || !aligned_to(L.y, need) || !aligned_to(L.ctx, 16) || (L.mask && !aligned_to(L.mask, 16)))
       return fail(MGACBAM_E_ALIGN, "eca forward: x/y must be %zu-byte aligned, ctx and mask 16-byte", need);
@@ -88,7 +88,7 @@ extern "C" int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_
     A.c = eca_ctx_ptrs(L.ctx, L.B, L.C, L.H, L.W);
     A.w1d = L.p.w; A.beta = L.p.beta;
     A.g = eca_geo(L.B, L.C, L.H, L.W, L.p);
-    A.t = choose_tune(L.B, L.C, L.H, L.W, 7, L.dtype);
+    A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
     sigs[l] = Sig{L.dtype, VEC, L.mask != nullptr, 0, 0, 0};
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -136,7 +136,7 @@ extern "C" int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n
     if (int e = eca_check_params(L.p)) return e;
     if (int e = check_shape(L.B, L.C, L.H, L.W, 1, L.p.k)) return e;
     if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "eca backward: dtype %d", L.dtype);
-    const int VEC = vec_of(L.H, L.W, L.dtype);
+    const int VEC = vec_of(L.H, L.W);
     const size_t need = VEC * elem_size(L.dtype);
     if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
         !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 16)))
@@ -149,7 +149,7 @@ extern "C" int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n
     A.w1d = L.p.w; A.beta = L.p.beta;
     A.s.gg = static_cast<float*>(L.scratch);
     A.g = eca_geo(L.B, L.C, L.H, L.W, L.p);
-    A.t = choose_tune(L.B, L.C, L.H, L.W, 7, L.dtype);
+    A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
     A.nt = chan_tiles(A.t, L.H, L.W, VEC);
     sigs[l] = Sig{L.dtype, VEC, L.mask != nullptr, 0, L.gmask != nullptr, 0};
   }

@@ -10,7 +10,7 @@ static int forward_args(const mgacbam_fwd_level_t& L, FwdArgs& A, Sig& sig) {
   if (int e = check_params(L.p)) return e;
   if (int e = check_shape(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k)) return e;
   if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "forward: dtype %d", L.dtype);
-  const int VEC = vec_of(L.H, L.W, L.dtype);
+  const int VEC = vec_of(L.H, L.W);
   const size_t need = VEC * elem_size(L.dtype);
   if (!aligned_to(L.x, need) || !aligned_to(L.y, need) || !aligned_to(L.ctx, 16) || (L.mask && !aligned_to(L.mask, 16)))
     return fail(MGACBAM_E_ALIGN, "forward: x/y must be %zu-byte aligned, ctx 16-byte, mask %d-byte", need, VEC * 4);
@@ -25,14 +25,14 @@ static int forward_args(const mgacbam_fwd_level_t& L, FwdArgs& A, Sig& sig) {
   A.c = ctx_ptrs(L.ctx, L.B, L.C, L.H, L.W, L.p.hidden);
   A.p = make_params(L.p);
   A.g = make_geo(L.B, L.C, L.H, L.W, L.p);
-  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k, L.dtype);
+  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k);
   const int proj = (L.flags & MGACBAM_FWD_SAVE_PROJ) && L.mask != nullptr;
   A.g.proj_h = (proj && L.p.hidden <= MGACBAM_PROJ_MAX_HIDDEN) ? L.p.hidden : 0;
   sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, 0, proj};
   // fp16 / bf16: k_gate reads 16 bytes per lane (8 elements, kept packed in the registers) whatever vector width the other kernels
   // use -- twice the pixels per tile, half the workgroups: at YOLOv8n sizes the grid then runs as ONE resident round
   sig.gvec = VEC;
-  if (L.dtype != MGACBAM_F32 && VEC == 4 && knobs().gate_h8 && (static_cast<long long>(L.H) * L.W) % 8 == 0) {
+  if (L.dtype != MGACBAM_F32 && VEC == 4 && (static_cast<long long>(L.H) * L.W) % 8 == 0) {
     Tune t8 = A.t;
     gate_geometry(L.C, L.H, L.W, L.p.k, 8, t8);
     if (t8.gate_tx > 0) { sig.gvec = 8; A.t = t8; }
@@ -49,7 +49,7 @@ static int forward_group(FwdArgs* lv, int n, const Sig& sig, int stages, hipStre
 
   // MGACBAM_FWD_FUSE: stages 2 + 3 become ONE x-resident launch (k_gate) when every level of the group is eligible
   const int gvec = sig.gvec;                   // per level (forward_args), uniform over the group by construction
-  bool gate = (stages & MGACBAM_FWD_FUSE) && (stages & MGACBAM_FWD_CHAN) && (stages & MGACBAM_FWD_APPLY) && !sig.proj && sig.vec <= 4 && gvec > 0;
+  bool gate = (stages & MGACBAM_FWD_FUSE) && (stages & MGACBAM_FWD_CHAN) && (stages & MGACBAM_FWD_APPLY) && !sig.proj && gvec > 0;
   for (int l = 0; l < n && gate; ++l) gate = lv[l].t.gate_tx > 0;
   size_t gsmem = 0;
   if (gate) {
@@ -59,7 +59,7 @@ static int forward_group(FwdArgs* lv, int n, const Sig& sig, int stages, hipStre
     for (int l = 0; l < n; ++l) { gsmem = std::max(gsmem, gate_smem(lv[l].g, lv[l].t, gvec)); span = std::max(span, lv[l].t.gate_span); }
     int resident = 0;
 #define RES_GATE(Tt, Vv) resident = (sig.k == 7) ? resident_workgroups(k_gate<Tt, Vv, 7>, gsmem) : resident_workgroups(k_gate<Tt, Vv, 0>, gsmem)
-    DISPATCH_T_VEC(sig.dtype, gvec, RES_GATE);
+    DISPATCH_T_GVEC(sig.dtype, gvec, RES_GATE);
 #undef RES_GATE
     gate = 2 * (8 * span + 1) <= resident;
   }
@@ -84,7 +84,7 @@ static int forward_group(FwdArgs* lv, int n, const Sig& sig, int stages, hipStre
     GG.rstart[n] = GG.nrole;
     const int grid = GG.nrole + tiles;
 #define CALL_GATE(Tt, Vv) if (sig.k == 7) LAUNCH((k_gate<Tt, Vv, 7>), grid, smem, st, GG); else LAUNCH((k_gate<Tt, Vv, 0>), grid, smem, st, GG)
-    DISPATCH_T_VEC(sig.dtype, gvec, CALL_GATE);
+    DISPATCH_T_GVEC(sig.dtype, gvec, CALL_GATE);
 #undef CALL_GATE
     return launch_status("k_gate");
   }
@@ -92,7 +92,6 @@ static int forward_group(FwdArgs* lv, int n, const Sig& sig, int stages, hipStre
     // With C*hidden large the MLP prologue keeps every k_chan workgroup from streaming for 15-20 us; one tiny launch per step is cheaper
     bool split_mlp = false;
     for (int l = 0; l < n; ++l) split_mlp |= static_cast<long long>(lv[l].g.C) * lv[l].g.hidden >= 8192;
-    { const int f = knobs().split_mlp; if (f == 0) split_mlp = false; else if (f == 1) split_mlp = true; }
     if (split_mlp) {
       size_t msmem = 0;
       for (int l = 0; l < n; ++l) msmem = std::max(msmem, (3 * static_cast<size_t>(lv[l].g.C) + 2 * lv[l].g.hidden) * sizeof(float));
@@ -102,7 +101,7 @@ static int forward_group(FwdArgs* lv, int n, const Sig& sig, int stages, hipStre
     }
     size_t smem = 0;
     for (int l = 0; l < n; ++l) smem = std::max(smem, chan_smem(lv[l].g, sig.vec, sig.proj));
-    const int grid = fill([&](const FwdArgs& a) { return xcd_grid(a.g.B, (a.g.HW / sig.vec + a.t.chanf_tx - 1) / a.t.chanf_tx); });
+    const int grid = fill([&](const FwdArgs& a) { return xcd_grid(a.g.B, chan_tiles(a.t, a.g.H, a.g.W, sig.vec)); });
 #define CALL_CHAN(Tt, Vv)                                                                                         \
     if (split_mlp) { if (sig.proj) LAUNCH((k_chan<Tt, Vv, true, true>), grid, smem, st, G); else LAUNCH((k_chan<Tt, Vv, false, true>), grid, smem, st, G); } \
     else { if (sig.proj) LAUNCH((k_chan<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_chan<Tt, Vv, false>), grid, smem, st, G); }

@@ -58,9 +58,12 @@ static HeadTiling head_tiling(int B, int C, int H, int W, int hidden) {
   t.nshare = static_cast<int>(std::max(32ll, std::min(256ll, ns)));
   t.gw2 = (t.vec == 4 && t.hidp <= 64) ? 1 : 0;                     // k_head_bwd_gw2 (operands through LDS): a share = every nshare-th 64-pixel chunk
   if (t.gw2) {
+    // 64-pixel chunks per workgroup (pixel shares = chunks / this).  5: the YOLOv8n pyramid's 1,008 workgroups are one resident round
+    // at the kernel's 108 VGPRs (4 per CU): slice 0.3886 -> 0.3852 ms; 3, 6, 8 and config 3: no difference
+    constexpr int kHeadGwDiv = 5;
     const long long chunks64 = static_cast<long long>(B) * ((HW + kHeadGwPx - 1) / kHeadGwPx);
     const long long cap = std::max(1ll, std::min(512ll, (4ll << 20) / per_share));
-    t.nshare = static_cast<int>(std::max(1ll, std::min(cap, chunks64 / std::max(1, knobs().head_gw_div))));   // (measured: 2-4 chunks per workgroup and 512-2048 shares all within 1 %; 6+ chunks, one resident round: +12 %)
+    t.nshare = static_cast<int>(std::max(1ll, std::min(cap, chunks64 / kHeadGwDiv)));   // (measured: 2-4 chunks per workgroup and 512-2048 shares all within 1 %; 6+ chunks, one resident round: +12 %)
   }
   return t;
 }

@@ -13,10 +13,7 @@ struct Geo {
   int proj_h;      // > 0: W1-projection planes of x are saved (forward) / available (backward); = hidden (<= kProjMax)
 };
 constexpr int kProjMax = 4;   // MGACBAM_PROJ_MAX_HIDDEN
-#ifndef MGACBAM_GATE_R
-#define MGACBAM_GATE_R 16
-#endif
-constexpr int kGateR = MGACBAM_GATE_R;   // channels a thread of the x-resident kernels keeps in registers (x VEC pixels each)
+constexpr int kGateR = 16;   // channels a thread of the x-resident kernels keeps in registers (x VEC pixels each)
 constexpr int kSyncPx = 16;   // a hand-off tile is at least this many pixels: ctx.sync holds ceil(HW/kSyncPx)+1 flags per sample
 
 // saved statistics (device pointers into the caller's ctx buffer) -- see mgacbam_ctx_layout_t
@@ -38,12 +35,10 @@ struct Tune {
   int pool_tx;     // sweep kernels (k_pool, k_bwd_reduce2, k_eca_*): rows of TX lanes sweep H*W, TY = 256/TX rows x CPT channels
   int pool_cpt;
   int chan_tx;     // tile kernels (k_chan, k_apply, k_bwd_reduce1, k_bwd_apply, k_eca_bwd): one H*W vector per lane, TY = 256/TX channel slices
-  int chanf_tx;    // k_chan alone (its tiles are independent of every other kernel's): TX lanes along H*W
   int conv_twq;    // backward conv tiles: TWQ quads (4 px) wide, TH rows
   int conv_th;
   int wsa_th;      // k_bwd_wsa tiles: fewer rows so 4 staged planes stay under ~16 KB of LDS (role workgroups)
   int apply_rows;  // k_apply: upper bound of the plane rows (tile rows + halo) staged per workgroup
-  int nt_stores;   // 1: y / gx are written with non-temporal stores
   int gate_rows;   // k_gate: upper bound of the plane rows (tile rows + halo) staged per workgroup
   int gate_tx;     // k_gate (x-resident chan+apply): TX lanes along H*W, TY = 256/TX slices of kGateR channels each; 0 = not eligible
   int gate_span;   // k_gate: tiles a k x k window reaches on either side (a tile waits for workgroups up to 8*span ids away)
@@ -79,7 +74,6 @@ struct BwdArgs {
   int nt;       // hw tiles of k_bwd_reduce1
   int nconv;    // k_bwd_convT tiles of this level (B * tiles_y * tiles_x)
   int nwsa;     // k_bwd_wsa tiles of this level: one dWsa partial each
-  int nrole;    // role workgroups of k_bwd_reduce2 that work through those tiles (<= nwsa)
   int npg;      // parameter-gradient workgroups of this level (k_bwd_params roles)
   int ncg;      // channel groups per sample of k_bwd_reduce2
   int nflag;    // flags per sample in c.sync
@@ -92,8 +86,6 @@ struct BwdArgs {
   int merged;   // 1: k_bwd_reduce1 tiles, transposed-conv tiles, dWsa tiles and k_bwd_reduce2 sweeps are ONE launch (k_bwd_r12)
   unsigned spin_limit;
   int vec;      // elements per lane of the tile kernels (TP = chan_tx * vec pixels per tile)
-  int wsa_tail; // 1: the dWsa tile partials and their sums are the LAST workgroups of the k_bwd_apply launch (arrival counters = status
-                // words 1, 2 of c.sync, 0 between calls); 0: k_bwd_reduce2 roles / own launch
   long long* trace;   // MGACBAM_TRACE builds only (tools/trace_gate.py), else nullptr
 };
 

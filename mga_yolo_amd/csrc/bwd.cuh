@@ -25,28 +25,9 @@
 #include "common.cuh"
 #include "tile.cuh"   // ConvTile / stage_window
 
-// tuning hooks (A/B builds): unroll 1/2/4/8 and prefetch 1/2 of k_bwd_apply all measure within noise (54.5-57.7 us)
-#ifndef MGACBAM_BAPPLY_UNROLL
-#define MGACBAM_BAPPLY_UNROLL 4
-#endif
-constexpr int kPghLds = 2048;   // floats of LDS for k_bwd_reduce2's hidden-gradient partials (rows x hidden chunk)
-
-#ifndef MGACBAM_EARLY_H
-#define MGACBAM_EARLY_H 8    // hidden sizes up to this issue k_bwd_apply's second-phase prologue loads early
-#endif
-#ifndef MGACBAM_BAPPLY_UN
-#define MGACBAM_BAPPLY_UN 2
-#endif
-
-// A/B hook: occupancy cap of the two read-only backward kernels (-DMGACBAM_BWD_WAVES=4: what they would get inside one launch with
-// k_bwd_apply, whose 104 VGPRs allow 4 waves per SIMD)
-#ifdef MGACBAM_BWD_WAVES
-#define BWD_OCC __attribute__((amdgpu_waves_per_eu(MGACBAM_BWD_WAVES, MGACBAM_BWD_WAVES)))
-#else
-#define BWD_OCC
-#endif
-
 namespace mgacbam {
+
+constexpr int kPghLds = 2048;   // floats of LDS for k_bwd_reduce2's hidden-gradient partials (rows x hidden chunk)
 
 // ---------------------------------------------------------------------------------------------
 // k_bwd_reduce1     (thread layout of k_chan: one H*W vector per lane, rows take channel slices; TX <= 64)
@@ -240,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_convT(const Group<BwdArgs> G) {
 // latency-bound conv overlaps the streaming tail and one launch boundary disappears.  Flags: one generation counter per k_bwd_reduce1
 // tile and per conv tile in ctx.sync (zero-filled by the caller once, never reset: see bwd_convT_body).
 template <typename T, int VEC, int K>
-__global__ __launch_bounds__(kBlock) BWD_OCC void k_bwd_reduce1_fold(const Group<BwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_bwd_reduce1_fold(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
@@ -262,8 +243,8 @@ __global__ __launch_bounds__(kBlock) BWD_OCC void k_bwd_reduce1_fold(const Group
 //   through LDS.  K == 0 (any odd k): one thread per output.
 //   LDS: [g_pre tile][3 plane tiles][items * k partial sums]
 // ---------------------------------------------------------------------------------------------
-template <int K, bool AGENT = false, bool COH = false>   // AGENT: the partials are summed inside the same launch (k_bwd_apply's tail roles): written through
-__device__ __forceinline__ void bwd_wsa_body(const BwdArgs& A, const int local, float* smem) {   // COH: g_pre is published inside this launch (k_bwd_r12)
+template <int K, bool COH = false>   // COH: g_pre is published inside this launch (k_bwd_r12)
+__device__ __forceinline__ void bwd_wsa_body(const BwdArgs& A, const int local, float* smem) {
   const Geo& g = A.g;
   const int k = K ? K : g.k;
   const ConvTile c = conv_tile(g, A.t, k, local, A.t.wsa_th);
@@ -322,8 +303,7 @@ __device__ __forceinline__ void bwd_wsa_body(const BwdArgs& A, const int local, 
       float sum = 0.f;
       for (int r = 0; r < c.TH; ++r) sum += accs[(pi * c.TH + r) * KK + j];
       if (COH && bad) sum = __builtin_nanf("");
-      if (AGENT) st_agent(A.s.gwsa_part + static_cast<size_t>(o) * A.nwsa + local, sum);
-      else A.s.gwsa_part[static_cast<size_t>(o) * A.nwsa + local] = sum;
+      A.s.gwsa_part[static_cast<size_t>(o) * A.nwsa + local] = sum;
     }
   } else {
     for (int o = tid; o < nout; o += kBlock) {
@@ -334,8 +314,7 @@ __device__ __forceinline__ void bwd_wsa_body(const BwdArgs& A, const int local, 
       float sum = 0.f;
       for (int yy = 0; yy < c.TH; ++yy)
         for (int xx = 0; xx < c.TW; ++xx) sum += gg[yy * c.PW + xx] * pp[yy * c.PW + xx];
-      if (AGENT) st_agent(A.s.gwsa_part + static_cast<size_t>(o) * A.nwsa + local, sum);
-      else A.s.gwsa_part[static_cast<size_t>(o) * A.nwsa + local] = sum;
+      A.s.gwsa_part[static_cast<size_t>(o) * A.nwsa + local] = sum;
     }
   }
 }
@@ -415,7 +394,7 @@ __device__ __forceinline__ void bwd_reduce2_body(const BwdArgs& A, const int bid
     for (int c = tid; c < nch; c += kBlock) __hip_atomic_fetch_add(own + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 
-  constexpr int PF = MGACBAM_POOL_PF;                         // positions per lane per memory round (see k_pool)
+  constexpr int PF = kSweepPF;                                // positions per lane per memory round (see k_pool)
   for (int i0 = tx; i0 < nv; i0 += TX * PF) {
     float g0[PF][VEC], g1[PF][VEC], xv[PF][CPT][VEC];
     int ci[PF][VEC];
@@ -507,24 +486,24 @@ __device__ __forceinline__ void bwd_reduce2_body(const BwdArgs& A, const int bid
 // ROLES: the level's grid is [nwsa dWsa-partial workgroups (k = 7)][streaming workgroups]: the LDS/VALU-bound role
 // workgroups are dispatched first and overlap with the HBM-bound ones instead of costing a launch on the critical path.
 template <typename T, int VEC, int CPT, bool ROLES>
-__global__ __launch_bounds__(kBlock) BWD_OCC void k_bwd_reduce2(const Group<BwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_bwd_reduce2(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];                // [64 reduction scratch][TY * hidden] | wsa tiles
   int local;
   const int l = find_level(G, blockIdx.x, local);
   const BwdArgs& A = G.lv[l];
   if (ROLES) {
-    // A.nrole role workgroups share the level's A.nwsa dWsa tiles (tile t -> role t % nrole, one after the other): the host sizes nrole to
-    // the slots the streaming workgroups leave idle, so that the roles displace nothing and finish inside the streaming time
-    const int npad = (A.nrole + 7) & ~7;                        // keeps the streaming ids' id % 8 <-> sample alignment
+    // one role workgroup per dWsa tile of the level
+    const int npad = (A.nwsa + 7) & ~7;                         // keeps the streaming ids' id % 8 <-> sample alignment
     // (tools/trace_r2.py, config 2: the 800 one-tile roles live 8.6 us each and hold 800 of the 1792 slots first, so the last streaming
     // workgroups start at 15 us and a 19 us stream ends at 24.6.  Interleaving roles and streaming workgroups in dispatch order was
     // measured: +2 us -- the roles first is the better of the two orders; the fix is fewer slot-microseconds of role work.)
     if (local < npad) {
-      if (local < A.nrole) {
+      if (local < A.nwsa) {
         TRACE_MARK(A.trace, blockIdx.x, 0);
-        for (int t = local; t < A.nwsa; t += A.nrole) { bwd_wsa_body<7>(A, t, smem); __syncthreads(); }
+        bwd_wsa_body<7>(A, local, smem);
 #ifdef MGACBAM_TRACE
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
         TRACE_MARK(A.trace, blockIdx.x, 5);
 #endif
       }
@@ -558,7 +537,7 @@ struct R12Group {
   int seg[4][kGroupMax + 1];     // seg[p][l]: first workgroup id of level l in phase p; seg[p][n]: end of phase p
 };
 template <typename T, int VEC, int CPT>
-__global__ __launch_bounds__(kBlock) BWD_OCC void k_bwd_r12(const R12Group R) {
+__global__ __launch_bounds__(kBlock) void k_bwd_r12(const R12Group R) {
   extern __shared__ __align__(16) float smem[];
   const int bid = blockIdx.x;
   int p = 0;
@@ -577,7 +556,7 @@ __global__ __launch_bounds__(kBlock) BWD_OCC void k_bwd_r12(const R12Group R) {
 #endif
   if (p == 0) bwd_reduce1_body<T, VEC, true>(A, local, smem);
   else if (p == 1) { if (local < A.nconv) bwd_convT_body<7, true>(A, local, smem); }
-  else if (p == 2) { if (local < A.nwsa) bwd_wsa_body<7, false, true>(A, local, smem); }
+  else if (p == 2) { if (local < A.nwsa) bwd_wsa_body<7, true>(A, local, smem); }
   else bwd_reduce2_body<T, VEC, CPT, true>(A, local, smem);
 #ifdef MGACBAM_TRACE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -666,7 +645,6 @@ __device__ __forceinline__ void bwd_params_body(const BwdArgs& A, const int loca
     return;
   }
   if (local < h + nb2 + nb_wsa) {                                // dWsa: lanes stride the tile partials
-    if (A.wsa_tail) return;                                      // (summed by the last-arriving tail role of this launch instead)
     const int o = (local - h - nb2) * 4 + wave;
     if (o >= kk3) return;
     const float* part = A.s.gwsa_part + static_cast<size_t>(o) * A.nwsa;
@@ -704,7 +682,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_params(const Group<BwdArgs> G) {
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, bool GMASK>
 __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, float* smem, float* red) {
-  constexpr int UN = MGACBAM_BAPPLY_UN;
+  constexpr int UN = 2;   // channels a thread requests before the prologue (1 or 2, and unroll 1/2/4/8 of the channel loop: within noise, 54.5-57.7 us)
   const Geo& g = A.g;
   const int tid = threadIdx.x;
   const int TX = A.t.chan_tx, lt = ilog2(TX);
@@ -769,7 +747,7 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
   float kpart = 0.f;
   // common sizes (one channel per thread, hidden <= 16): the per-channel operands of the second prologue phase do not depend
   // on the first, so they are requested now; 20 registers, live only until the main loop starts
-  constexpr int kEarlyH = MGACBAM_EARLY_H;
+  constexpr int kEarlyH = 8;                                   // hidden sizes up to this issue the second-phase prologue loads early
   const bool early = g.C <= kBlock && h <= kEarlyH;
   float rw1[kEarlyH], rca = 0.f, rmavg = 0.f;
   int rvalid = 0, ramax = 0;
@@ -855,14 +833,14 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
       ov[e] = r;
       if (GMASK) { if (need_x) accp[e] += q.y * xv[e]; }
     }
-    if (active) store_vec_stream<T, VEC>(op + static_cast<size_t>(c) * g.HW, ov, A.t.nt_stores);
+    if (active) store_vec<T, VEC>(op + static_cast<size_t>(c) * g.HW, ov);
   };
 #pragma unroll
   for (int u = 0; u < UN; ++u) {
     const int c = ty + u * TY;
     if (c < g.C) emit(g0v[u], x0v[u], c);
   }
-#pragma unroll MGACBAM_BAPPLY_UNROLL
+#pragma unroll 4
   for (int c = ty + UN * TY; c < g.C; c += TY) {
     float gv[VEC], xv[VEC];
     load_vec<T, VEC>(gp + static_cast<size_t>(c) * g.HW, gv);
@@ -914,54 +892,6 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
 // (amdgpu_waves_per_eu(5) -- 94 instead of 104 VGPRs, 5 instead of 4 workgroups per CU -- was measured: config 2 fp32 57.9 -> 55.8 us,
 //  bf16 37.3 -> 38.5, config 4 200 -> 225 us; not adopted.  tools/trace_gate.py bwd shows the launch as two rounds of
 //  ~5 us prologue + ~19 us streaming per workgroup with HBM saturated during the streaming.)
-// dWsa as TAIL roles of the k_bwd_apply launch (A.wsa_tail): the level's grid is [params roles][streaming][nwsa tile partials][nsum sums].
-// As leading roles of k_bwd_reduce2 the 800 one-tile workgroups (8.6 us each at config 2) held 800 of its 1792 slots first and cost that
-// launch 5.5-7 us (tools/trace_r2.py).  Dispatched behind the last streaming workgroup of the step's LONGEST launch they start when its
-// last resident round does and run in the slots that round leaves free.  dWsa needs g_pre and the forward planes only (complete since
-// k_bwd_reduce1).  Hand-off: every tile role adds to an arrival counter (status word 1 of ctx.sync) once its partials are out; the sum
-// roles (4 outputs each, the fixed order of k_bwd_params: bitwise reproducible) are the very last workgroups, wait for nwsa arrivals --
-// every producer has a lower id and never waits, so progress does not depend on residency; the wait is bounded like every other -- and
-// the last of them to finish (word 2) hands both words back as 0.
-// MEASURED (config 2, round 3) and therefore OPT-IN (MGACBAM_WSA_TAIL=1): k_bwd_reduce2 27.1 -> 22.2 us, k_bwd_apply 58.8 -> 74.3 us,
-// step 200.5 -> 207.2 us.  The 800 tile roles are ~6,900 slot-microseconds of latency-bound work wherever they run: the last resident
-// round of k_bwd_apply leaves 224 of 1024 slots free, not enough to absorb them.  (ONE last-arriving workgroup summing all partials was
-// measured first: 470 KB through one CU, +31 us.)
-__device__ __forceinline__ void bwd_wsa_tail(const BwdArgs& A, const int t, float* smem) {
-  bwd_wsa_body<7, true>(A, t, smem);
-  int* cnt = A.c.sync + static_cast<size_t>(A.g.B) * A.nflag + 1;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this workgroup's partials are out (every wave waits before the barrier)
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void bwd_wsa_sum(const BwdArgs& A, const int s, const int nsum) {
-  int* words = A.c.sync + static_cast<size_t>(A.g.B) * A.nflag;  // [0] time-out status, [1] arrivals, [2] finished sum roles
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kk3 = 3 * A.g.k * A.g.k;
-  int timed_out = 0;
-  if (threadIdx.x == 0) {
-    unsigned spins = 0;
-    while (ld_agent(words + 1) < A.nwsa) {
-      __builtin_amdgcn_s_sleep(16);
-      if (++spins > A.spin_limit) { st_agent(words, 1); timed_out = 1; break; }
-    }
-  }
-  const bool bad = __syncthreads_or(timed_out) != 0;
-  const int o = s * (kBlock / kWave) + wave;
-  if (o < kk3) {
-    const float* part = A.s.gwsa_part + static_cast<size_t>(o) * A.nwsa;
-    float acc = 0.f;
-#pragma unroll 4
-    for (int i = lane; i < A.nwsa; i += kWave) acc += ld_agent(part + i);
-    acc = wave_group_sum(acc, kWave);
-    if (lane == 0) A.gwsa[o] = bad ? __builtin_nanf("") : acc;   // NaN: a hand-off that timed out must be loud
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0 && __hip_atomic_fetch_add(words + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsum - 1) {
-    st_agent(words + 1, 0);                                      // every sum role has seen the full count: the next call starts from 0
-    st_agent(words + 2, 0);
-  }
-}
-
 template <typename T, int VEC, bool GMASK, bool ROLES>
 __global__ __launch_bounds__(kBlock) void k_bwd_apply(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
@@ -984,15 +914,6 @@ __global__ __launch_bounds__(kBlock) void k_bwd_apply(const Group<BwdArgs> G) {
       return;
     }
     local -= npad;
-    if (A.wsa_tail) {
-      const int tiles = ((A.g.B + 7) / 8) * 8 * A.nt;
-      if (local >= tiles) {
-        const int nsum = (3 * A.g.k * A.g.k + 3) / 4;
-        if (local - tiles < A.nwsa) bwd_wsa_tail(A, local - tiles, smem);
-        else if (local - tiles - A.nwsa < nsum) bwd_wsa_sum(A, local - tiles - A.nwsa, nsum);
-        return;
-      }
-    }
   }
   bwd_apply_body<T, VEC, GMASK>(A, local, smem, red);
 }

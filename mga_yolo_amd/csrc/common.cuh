@@ -8,13 +8,10 @@
 
 #include "args.cuh"
 
-#ifndef MGACBAM_POOL_PF
-#define MGACBAM_POOL_PF 1   // H*W positions per lane per memory round in the sweep kernels (k_pool, k_bwd_reduce2)
-#endif
-
 namespace mgacbam {
 
 constexpr int kBlock = 256;        // every kernel uses 256-thread workgroups = 4 waves
+constexpr int kSweepPF = 1;        // H*W positions per lane per memory round in the sweep kernels (k_pool, k_bwd_reduce2)
 constexpr int kWave = 64;
 using bf16_t = __hip_bfloat16;
 
@@ -47,26 +44,24 @@ __device__ __forceinline__ void store_vec(T* __restrict__ p, const float (&in)[V
   for (int e = 0; e < VEC; ++e) r.v[e] = from_f32<T>(in[e]);
   *reinterpret_cast<Pack<T, VEC>*>(p) = r;
 }
-// write-once streams (y, gx): non-temporal, so they do not displace x / gy (re-read by later kernels) from L2 / Infinity Cache
+// write-once streams: non-temporal, so they do not displace data later kernels re-read from L2 / Infinity Cache (the mask head's gx).
+// (Not taken by the MaskCBAM / MaskECA y and gx stores: behind a run-time flag the compiler had merged the non-temporal and the plain
+//  store into one plain store, so those kernels have always stored plainly; making them non-temporal is a tuning change of its own.)
 template <typename T, int VEC>
-__device__ __forceinline__ void store_vec_stream(T* __restrict__ p, const float (&in)[VEC], bool nt) {
+__device__ __forceinline__ void store_vec_stream(T* __restrict__ p, const float (&in)[VEC]) {
   Pack<T, VEC> r;
 #pragma unroll
   for (int e = 0; e < VEC; ++e) r.v[e] = from_f32<T>(in[e]);
-  if (nt) {
-    if constexpr (sizeof(T) * VEC == 16) {
-      typedef float v4f __attribute__((ext_vector_type(4)));
-      __builtin_nontemporal_store(*reinterpret_cast<v4f*>(&r), reinterpret_cast<v4f*>(p));
-    } else if constexpr (sizeof(T) * VEC == 8) {
-      typedef float v2f __attribute__((ext_vector_type(2)));
-      __builtin_nontemporal_store(*reinterpret_cast<v2f*>(&r), reinterpret_cast<v2f*>(p));
-    } else if constexpr (sizeof(T) * VEC == 4) {
-      __builtin_nontemporal_store(*reinterpret_cast<float*>(&r), reinterpret_cast<float*>(p));
-    } else {
-      __builtin_nontemporal_store(*reinterpret_cast<unsigned short*>(&r), reinterpret_cast<unsigned short*>(p));
-    }
+  if constexpr (sizeof(T) * VEC == 16) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    __builtin_nontemporal_store(*reinterpret_cast<v4f*>(&r), reinterpret_cast<v4f*>(p));
+  } else if constexpr (sizeof(T) * VEC == 8) {
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    __builtin_nontemporal_store(*reinterpret_cast<v2f*>(&r), reinterpret_cast<v2f*>(p));
+  } else if constexpr (sizeof(T) * VEC == 4) {
+    __builtin_nontemporal_store(*reinterpret_cast<float*>(&r), reinterpret_cast<float*>(p));
   } else {
-    *reinterpret_cast<Pack<T, VEC>*>(p) = r;
+    __builtin_nontemporal_store(*reinterpret_cast<unsigned short*>(&r), reinterpret_cast<unsigned short*>(p));
   }
 }
 template <int VEC>

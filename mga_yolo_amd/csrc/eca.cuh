@@ -166,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void k_eca_apply(const Group<EcaFwdArgs> G)
       float yv[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) yv[e] = xv[j][e] * gate[j];
-      if (live[j]) store_vec_stream<T, VEC>(yr[j] + static_cast<size_t>(i) * VEC, yv, A.t.nt_stores);
+      if (live[j]) store_vec<T, VEC>(yr[j] + static_cast<size_t>(i) * VEC, yv);
     }
   }
 }
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(kBlock) void k_eca_bwd(const Group<EcaBwdArgs> G) {
       ov[e] = gv[e] * q.x + q.y * wA[e];
       if (GMASK) accp[e] += q.y * xv[e];
     }
-    if (active) store_vec_stream<T, VEC>(op + static_cast<size_t>(c) * g.HW, ov, A.t.nt_stores);
+    if (active) store_vec<T, VEC>(op + static_cast<size_t>(c) * g.HW, ov);
   };
 #pragma unroll
   for (int u = 0; u < UN; ++u) {

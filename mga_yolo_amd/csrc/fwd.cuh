@@ -70,7 +70,7 @@ __device__ __forceinline__ void pool_body(const FwdArgs& A, const int bid, float
 
   // PF positions per lane are requested per round: a lane's sweep is a chain of dependent memory rounds (each ~2.5 us
   // under load), so the kernel cannot finish before rounds x latency -- fewer, fatter rounds (profiles/ notes, membw).
-  constexpr int PF = MGACBAM_POOL_PF;
+  constexpr int PF = kSweepPF;
   // (A staggered start -- every workgroup beginning its sweep at a different round, to spread concurrent requests over the memory
   //  channels -- was measured at configs 2, 3, 4: no gain, k_bwd_reduce2 10 % slower from the extra index arithmetic; not kept.)
   for (int i0 = tx; i0 < nv; i0 += TX * PF) {
@@ -235,7 +235,7 @@ __device__ __forceinline__ void chan_body(const FwdArgs& A, const int bid, float
   constexpr int HP = kProjMax;
   const Geo& g = A.g;
   const int tid = threadIdx.x;
-  const int TX = A.t.chanf_tx, lt = ilog2(TX);
+  const int TX = A.t.chan_tx, lt = ilog2(TX);
   const int tx = tid & (TX - 1), ty = tid >> lt, TY = kBlock >> lt;
   const int nv = g.HW / VEC;
   const int ntile = (nv + TX - 1) / TX;
@@ -469,7 +469,7 @@ __device__ __forceinline__ void apply_body(const FwdArgs& A, const int bid, floa
       const float v = u * sav[e];                               // masked_cbam.py:148
       yv[e] = xv[e] + a * (v - xv[e]);                          // masked_cbam.py:171
     }
-    if (active) store_vec_stream<T, VEC>(yp + static_cast<size_t>(c) * g.HW, yv, A.t.nt_stores);
+    if (active) store_vec<T, VEC>(yp + static_cast<size_t>(c) * g.HW, yv);
   };
 #pragma unroll
   for (int u = 0; u < UN; ++u) {
@@ -703,7 +703,7 @@ __device__ __forceinline__ void gate_body(const FwdArgs& A, const int bid, float
         const float u = xe * cac;                               // masked_cbam.py:130
         yv[e] = xe + a * (u * sav[e] - xe);                     // masked_cbam.py:148,171
       }
-      if (active) store_vec_stream<T, VEC>(yp + static_cast<size_t>(c) * g.HW, yv, A.t.nt_stores);
+      if (active) store_vec<T, VEC>(yp + static_cast<size_t>(c) * g.HW, yv);
     }
   }
 #ifdef MGACBAM_TRACE
@@ -882,13 +882,8 @@ struct GateGroup {
 };
 
 
-#ifdef MGACBAM_GATE_WAVES
-#define GATE_OCC __attribute__((amdgpu_waves_per_eu(MGACBAM_GATE_WAVES)))
-#else
-#define GATE_OCC
-#endif
 template <typename T, int VEC, int K>
-__global__ __launch_bounds__(kBlock) GATE_OCC void k_gate(const GateGroup GG) {
+__global__ __launch_bounds__(kBlock) void k_gate(const GateGroup GG) {
   extern __shared__ __align__(16) float smem[];
   const int bid = blockIdx.x;
   if (bid < GG.nrole) {

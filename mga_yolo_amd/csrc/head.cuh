@@ -34,11 +34,8 @@ typedef __bf16 v4bf16 __attribute__((ext_vector_type(4)));
 // four channel rows), so the operands are the fp32 values the loads produced, packed pairwise (v_cvt_pk_*): feature values are half
 // already (exact), the fp32 weights and g_z are rounded to the feature type (2^-11 / 2^-8 relative, inside the half-precision bars).
 template <typename T> struct HalfMma { static constexpr bool on = false; };
-#ifndef MGAHEAD_HALF_MMA
-#define MGAHEAD_HALF_MMA 1      // A/B builds: 0 = half features through the fp32 MFMA (round 2's path)
-#endif
 template <> struct HalfMma<__half> {
-  static constexpr bool on = MGAHEAD_HALF_MMA != 0;
+  static constexpr bool on = true;
   __device__ static __forceinline__ v4f32 mma(float a0, float a1, float a2, float a3, float b0, float b1, float b2, float b3, v4f32 c) {
     const v4f16 a = {static_cast<_Float16>(a0), static_cast<_Float16>(a1), static_cast<_Float16>(a2), static_cast<_Float16>(a3)};
     const v4f16 b = {static_cast<_Float16>(b0), static_cast<_Float16>(b1), static_cast<_Float16>(b2), static_cast<_Float16>(b3)};
@@ -46,7 +43,7 @@ template <> struct HalfMma<__half> {
   }
 };
 template <> struct HalfMma<bf16_t> {
-  static constexpr bool on = MGAHEAD_HALF_MMA != 0;
+  static constexpr bool on = true;
   __device__ static __forceinline__ v4f32 mma(float a0, float a1, float a2, float a3, float b0, float b1, float b2, float b3, v4f32 c) {
     const v4bf16 a = {static_cast<__bf16>(a0), static_cast<__bf16>(a1), static_cast<__bf16>(a2), static_cast<__bf16>(a3)};
     const v4bf16 b = {static_cast<__bf16>(b0), static_cast<__bf16>(b1), static_cast<__bf16>(b2), static_cast<__bf16>(b3)};
@@ -360,7 +357,7 @@ __device__ __forceinline__ void head_gemm_body(const HeadArgs& A, const int wg, 
 #pragma unroll
                 for (int r = 0; r < VEC; ++r) ov[r] += oldv[GX ? t : 0][GX ? v : 0][r];
               }
-              store_vec_stream<T, VEC>(gp, ov, true);
+              store_vec_stream<T, VEC>(gp, ov);
             }
             else store_vec<float, VEC>(A.c.z + (static_cast<size_t>(b) * g.hid + out) * g.HW + px, ov);
           }

@@ -116,12 +116,9 @@ static int env_int(const char* name, int dflt) {
 // Tuning / test knobs come from the environment ONCE (first call) -- not per call: the eager path makes ~50 look-ups per step
 // otherwise.  mgacbam_reload_env() re-reads them (tests and tuning sweeps that change the environment in-process).
 struct Knobs {
-  int head_gw_div;         // MGAHEAD_GW_DIV (default 5): 64-pixel chunks per k_head_bwd_gw2 workgroup (pixel shares = chunks / this).  5: the YOLOv8n pyramid's 1,008
-                           // workgroups are one resident round at the kernel's 108 VGPRs (4 per CU): slice 0.3886 -> 0.3852 ms; 3, 6, 8 and config 3: no difference
   int bwd_merge;           // MGACBAM_BWD_MERGE (default 1): k_bwd_reduce1 + conv + dWsa tiles + k_bwd_reduce2 as one launch (k_bwd_r12)
-  int wsa_tail;            // MGACBAM_WSA_TAIL (default 0, opt-in): dWsa tile partials + sums as the last workgroups of the k_bwd_apply launch
   int gate_narrow;         // MGACBAM_GATE_NARROW (default 0): k_gate also for tiles narrower than an image row
-  int gate, chan_mintx, pool_tx, pool_cpt, r2_cpt, wsa_fat, chan_tx, chanf_tx, split_mlp, nt, half_vec, gate_h8, level_order, bwd_fold;
+  int pool_tx, pool_cpt, chan_tx;   // MGACBAM_POOL_TX / _POOL_CPT / _CHAN_TX: launch-geometry overrides (choose_tune, group_cpt)
   int resident_wgs;        // MGACBAM_RESIDENT_WGS: override of the co-resident workgroup budget the hand-off eligibility is sized from
   int fault;               // MGACBAM_FAULT: fault injection for tests (args.cuh)
   unsigned spin_limit;     // MGACBAM_SPIN_LIMIT
@@ -130,14 +127,8 @@ struct Knobs {
 static Knobs read_knobs() {
   Knobs k;
   k.bwd_merge = env_int("MGACBAM_BWD_MERGE", 1);
-  k.head_gw_div = env_int("MGAHEAD_GW_DIV", 5);
-  k.wsa_tail = env_int("MGACBAM_WSA_TAIL", 0);
   k.gate_narrow = env_int("MGACBAM_GATE_NARROW", 0);
-  k.gate = env_int("MGACBAM_GATE", 1); k.chan_mintx = env_int("MGACBAM_CHAN_MINTX", 16);
   k.pool_tx = env_int("MGACBAM_POOL_TX", 0); k.pool_cpt = env_int("MGACBAM_POOL_CPT", 0); k.chan_tx = env_int("MGACBAM_CHAN_TX", 0);
-  k.nt = env_int("MGACBAM_NT", 1); k.half_vec = env_int("MGACBAM_HALF_VEC", 4); k.gate_h8 = env_int("MGACBAM_GATE_H8", 1);
-  k.level_order = env_int("MGACBAM_LEVEL_ORDER", 1); k.bwd_fold = env_int("MGACBAM_BWD_FOLD", 1);
-  k.r2_cpt = env_int("MGACBAM_R2_CPT", 0); k.wsa_fat = env_int("MGACBAM_WSA_FAT", 0); k.chanf_tx = env_int("MGACBAM_CHANF_TX", 0); k.split_mlp = env_int("MGACBAM_SPLIT_MLP", -1);
   k.resident_wgs = env_int("MGACBAM_RESIDENT_WGS", 0); k.fault = env_int("MGACBAM_FAULT", 0);
   const int sl = env_int("MGACBAM_SPIN_LIMIT", 0);
   k.spin_limit = sl > 0 ? static_cast<unsigned>(sl) : (1u << 20);
@@ -196,14 +187,10 @@ static int resident_workgroups(K kernel, size_t smem) {
 }
 static bool is_pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && (v & (v - 1)) == 0; }
 
-// elements per lane per access: 4 (16 B fp32, 8 B fp16/bf16) when the row length allows, else scalar.  8-element (16 B)
-// half vectors exist (MGACBAM_HALF_VEC=8) but halve the tile count, which starves the small levels (P5: 128 workgroups;
-// k_chan 19 -> 33 us at YOLOv8n sizes), so they are opt-in for large feature maps only
-static int vec_of(int H, int W, int dtype = MGACBAM_F32) {
-  const long long hw = static_cast<long long>(H) * W;
-  if (dtype != MGACBAM_F32 && hw % 8 == 0 && knobs().half_vec == 8) return 8;
-  return hw % 4 == 0 ? 4 : 1;
-}
+// elements per lane per access: 4 (16 B fp32, 8 B fp16/bf16) when the row length allows, else scalar.  8-element (16 B) half
+// vectors halve the tile count, which starves the small levels (P5: 128 workgroups; k_chan 19 -> 33 us at YOLOv8n sizes): only
+// k_gate reads them (forward_args: gvec)
+static int vec_of(int H, int W) { return (static_cast<long long>(H) * W) % 4 == 0 ? 4 : 1; }
 
 // k_gate (x-resident chan+apply): every thread keeps kGateR channels, so TY = ceil(C / kGateR) slices (power of two) and the
 // rest of the 256 threads go along H*W.  Eligible when a tile is >= kSyncPx pixels (ctx.sync has one flag per kSyncPx) and >= one
@@ -212,7 +199,7 @@ static int vec_of(int H, int W, int dtype = MGACBAM_F32) {
 static void gate_geometry(int C, int H, int W, int k, int VEC, Tune& t) {
   t.gate_tx = 0; t.gate_rows = 0; t.gate_span = 0;
   const int gty = pow2_ceil((C + kGateR - 1) / kGateR);
-  if (gty > kBlock || !knobs().gate) return;
+  if (gty > kBlock) return;
   const int gtx = kBlock / gty, TP = gtx * VEC;
   int grows = (TP - 1) / W + 2;
   if (grows > H) grows = H;
@@ -229,8 +216,8 @@ static void gate_geometry(int C, int H, int W, int k, int VEC, Tune& t) {
   if (TP >= kSyncPx && (TP >= W || knobs().gate_narrow) && lds <= 48 * 1024) { t.gate_tx = gtx; t.gate_rows = grows; t.gate_span = span; }
 }
 
-static Tune choose_tune(int B, int C, int H, int W, int k, int dtype = MGACBAM_F32) {
-  const int HW = H * W, VEC = vec_of(H, W, dtype), nv = HW / VEC;
+static Tune choose_tune(int B, int C, int H, int W, int k) {
+  const int HW = H * W, VEC = vec_of(H, W), nv = HW / VEC;
   const Knobs kn = knobs();
   Tune t;
   // rows of TX lanes sweep H*W: aim for >= 4 sweeps per lane, then shrink channels/row until the grid fills the chip
@@ -241,8 +228,8 @@ static Tune choose_tune(int B, int C, int H, int W, int k, int dtype = MGACBAM_F
   t.pool_tx = tx; t.pool_cpt = cpt;
   // one H*W vector per lane, TY channel slices: TX <= 64 so row reductions are pure wave shuffles
   int ctx = pow2_ceil(nv) < 64 ? pow2_ceil(nv) : 64;
-  const int min_tx = kn.chan_mintx;
-  while (ctx > min_tx && static_cast<long long>(B) * ((nv + ctx - 1) / ctx) < 768) ctx /= 2;
+  constexpr int kChanMinTx = 16;
+  while (ctx > kChanMinTx && static_cast<long long>(B) * ((nv + ctx - 1) / ctx) < 768) ctx /= 2;
   while (ctx < 64 && (256 / ctx) * 4 > C) ctx *= 2;       // keep >= 4 channels per row
   t.chan_tx = ctx;
   // conv tiles: full rows when W <= 128, otherwise equal column strips; 4 px per thread
@@ -266,13 +253,10 @@ static Tune choose_tune(int B, int C, int H, int W, int k, int dtype = MGACBAM_F
   if (is_pow2_in(v = kn.pool_tx, 1, 256)) t.pool_tx = v;
   if ((v = kn.pool_cpt) == 1 || v == 2 || v == 4) t.pool_cpt = v;
   if (is_pow2_in(v = kn.chan_tx, 1, 64)) t.chan_tx = v;
-  t.chanf_tx = t.chan_tx;
-  if (is_pow2_in(v = kn.chanf_tx, 1, 64)) t.chanf_tx = v;
   // k_apply stages every image row its TX*VEC-pixel tile touches, plus the k-1 halo rows
   int rows = (t.chan_tx * VEC - 1) / W + 2;
   if (rows > H) rows = H;
   t.apply_rows = rows + k - 1;
-  t.nt_stores = kn.nt ? 1 : 0;
   // k_gate (x-resident chan+apply): every thread keeps kGateR channels, so TY = ceil(C / kGateR) slices (power of two) and the
   // rest of the 256 threads go along H*W.  Eligible when a tile is >= kSyncPx pixels (ctx.sync has one flag per kSyncPx) and >= one image row,
   // the tiles a k x k window reaches are few (their workgroups must be co-resident: 8 ids apart per tile, common.cuh) and
@@ -295,11 +279,11 @@ static int chan_tiles(const Tune& t, int H, int W, int vec) {
 }
 
 struct ScratchLayout { size_t A_part, gpre, gplanes, gwsa_part, gz, gbq, gh_avg, gh_mx, pgh, total; };
-static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int k, int dtype) {
-  // the tile counts follow the launch geometry, which follows the element type (vector width) and the knobs: the layout is per dtype
-  const Tune t = choose_tune(B, C, H, W, k, dtype);
+static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int k) {
+  // the tile counts follow the launch geometry, which follows the knobs
+  const Tune t = choose_tune(B, C, H, W, k);
   const size_t HW = static_cast<size_t>(H) * W, BC = static_cast<size_t>(B) * C;
-  const size_t nt = chan_tiles(t, H, W, vec_of(H, W, dtype)), nconv = static_cast<size_t>(B) * wsa_tiles(t, H, W);
+  const size_t nt = chan_tiles(t, H, W, vec_of(H, W)), nconv = static_cast<size_t>(B) * wsa_tiles(t, H, W);
   ScratchLayout L;
   size_t o = 0;
   auto take = [&](size_t n_elems) { size_t at = o; o = align16(o + n_elems * 4); return at; };
@@ -330,10 +314,17 @@ static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintp
 
 #define LAUNCH(kernel, grid, smem, stream, args) launch(kernel, static_cast<unsigned>(grid), smem, stream, args)
 
-// T x VEC
-#define DISPATCH_T_VEC(dtype, VECV, CALL)                                                         \
-  do {                                                                                            \
-    if ((dtype) == MGACBAM_F32) { if ((VECV) == 4) { CALL(float, 4); } else { CALL(float, 1); } }  \
+// T x VEC (vec_of: 1 or 4)
+#define DISPATCH_T_VEC(dtype, VECV, CALL)                                                                \
+  do {                                                                                                   \
+    if ((dtype) == MGACBAM_F32) { if ((VECV) == 4) { CALL(float, 4); } else { CALL(float, 1); } }         \
+    else if ((dtype) == MGACBAM_F16) { if ((VECV) == 4) { CALL(__half, 4); } else { CALL(__half, 1); } }  \
+    else { if ((VECV) == 4) { CALL(bf16_t, 4); } else { CALL(bf16_t, 1); } }                              \
+  } while (0)
+// T x VEC of k_gate alone (Sig::gvec): fp16 / bf16 also 8
+#define DISPATCH_T_GVEC(dtype, VECV, CALL)                                                                                          \
+  do {                                                                                                                              \
+    if ((dtype) == MGACBAM_F32) { if ((VECV) == 4) { CALL(float, 4); } else { CALL(float, 1); } }                                    \
     else if ((dtype) == MGACBAM_F16) { if ((VECV) == 8) { CALL(__half, 8); } else if ((VECV) == 4) { CALL(__half, 4); } else { CALL(__half, 1); } } \
     else { if ((VECV) == 8) { CALL(bf16_t, 8); } else if ((VECV) == 4) { CALL(bf16_t, 4); } else { CALL(bf16_t, 1); } }          \
   } while (0)
@@ -434,10 +425,7 @@ static int for_each_group(Args* args, const Sig* sigs, int n, Run run) {
     int m = 0;
     for (int j = l; j < n && m < kGroupMax; ++j)
       if (!done[j] && sigs[j] == sigs[l]) { grp[m++] = args[j]; done[j] = true; }
-    if (knobs().level_order)
-      std::stable_sort(grp, grp + m, [](const Args& a, const Args& b) {
-        return level_weight(a, 0) > level_weight(b, 0);
-      });
+    std::stable_sort(grp, grp + m, [](const Args& a, const Args& b) { return level_weight(a, 0) > level_weight(b, 0); });
     if (int e = run(grp, m, sigs[l])) return e;
   }
   return 0;

@@ -58,7 +58,6 @@ class _on_device:
     def __exit__(self, *a):
         if self.guard is not None:
             self.guard.__exit__(*a)
-_USE_PROJ = bool(int(os.environ.get("MGACBAM_PROJ", "0")))
 # k_chan + k_apply as ONE x-resident launch (k_gate, MGACBAM_FWD_FUSE); MGACBAM_FUSE_FWD=0 restores the three-launch forward
 _FUSE_FWD = bool(int(os.environ.get("MGACBAM_FUSE_FWD", "1")))
 # transposed conv folded into the k_bwd_reduce1 launch (MGACBAM_BWD_FOLD); needs the zero-filled ctx tail the fused forward sets up
@@ -239,13 +238,11 @@ class _PyramidFn(torch.autograd.Function):
             L.ctx_bytes = cbuf.numel()
             L.p = _params_struct(pc, cfg)
             L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[x.dtype]
-            # opt-in (MGACBAM_PROJ=1): the backward of this call will want dL/dmask, let the forward save the W1-projection
-            # planes for it.  Off by default: at YOLOv8n sizes what k_bwd_apply saves (x of P3) k_chan pays back
-            proj = _USE_PROJ and mask is not None and mask.requires_grad and torch.is_grad_enabled()
-            L.flags = _lib.FWD_SAVE_PROJ if proj else 0
+            # (L.flags stays 0: the W1-projection planes are not saved here -- at YOLOv8n sizes what k_bwd_apply saves (x of P3) k_chan
+            #  pays back; PyramidPlan(use_proj=True) and forward_with_ctx still drive that path)
             keep += [xc, m32, *pc]
             outs.append(y)
-            meta.append(((None if mask is None else (mask.dtype, tuple(mask.shape))), proj))
+            meta.append(None if mask is None else (mask.dtype, tuple(mask.shape)))
         with _on_device(dev):
             rc = lib.mgacbam_forward_stages(levels, n, _FWD_STAGES, stream)
         if rc:
@@ -286,7 +283,6 @@ class _PyramidFn(torch.autograd.Function):
             L.gw1, L.gb1, L.gw2, L.gb2, L.gwsa, L.gbeta = (t.data_ptr() for t in pg)
             L.p = _params_struct(pc, cfg)
             L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[xc.dtype]
-            L.flags = _lib.BWD_HAVE_PROJ if ctx.meta[l][1] else 0
             hold += [gy, scratch]
             grads += [gx, gmask, *pg]
         with _on_device(dev):
@@ -297,7 +293,7 @@ class _PyramidFn(torch.autograd.Function):
         for l in range(n):                                         # dL/dmask in the mask's own shape / element type -- AFTER the launch that
             gm = grads[1 + l * SLOTS + 1]                          # writes it (a cast enqueued before it would read unwritten memory: that
             if gm is not None:                                     # was the case for half-precision masks until the AMP test of round 3)
-                mdtype, mshape = ctx.meta[l][0]
+                mdtype, mshape = ctx.meta[l]
                 grads[1 + l * SLOTS + 1] = gm.reshape(mshape).to(mdtype)
         if _CHECK_HANDOFF:
             _check_status([(ls.buf, ls.key[2:7]) for ls in ctx.leases], "mask_cbam backward")

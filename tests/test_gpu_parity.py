@@ -871,45 +871,6 @@ def test_half_precision_mask_gets_its_gradient_in_its_own_dtype(F, mdtype, tol):
     assert md.grad.dtype == mdtype and rel_err(md.grad.float(), mh.grad) < tol and rel_err(xd.grad, xh.grad) < TOL
 
 
-def test_dwsa_tail_roles_give_the_same_bits(F, monkeypatch):
-    """MGACBAM_WSA_TAIL=1 (opt-in): the dWsa tile partials and their fixed-order sums ride at the END of the k_bwd_apply launch behind an
-    arrival counter instead of at the front of k_bwd_reduce2 -- every gradient must equal the default placement bit for bit, over
-    repeated calls and graph replays (the counters return to 0 each call), and the hand-off status must stay clear."""
-    from mga_yolo_amd import _lib
-    from mga_yolo_amd.plan import PyramidPlan
-    shapes = [(8, 64, 40, 40), (8, 128, 20, 20), (5, 256, 10, 10)]
-    params, cfgs, data = [], [], []
-    for l, (B, C, H, W) in enumerate(shapes):
-        p = O.Params.default_init(C, seed=l)
-        p.beta.fill_(0.2)
-        params.append((p.w1, p.b1, p.w2, p.b2, p.wsa, p.beta))
-        cfgs.append(F.BlockConfig(hidden=p.w1.shape[0]))
-        data.append(synth(B, C, H, W, seed=60 + l, mask_kind="mixed"))
-
-    def run():
-        plan = PyramidPlan(shapes, params, cfgs)
-        for l, (x, mask, gy) in enumerate(data):
-            plan.x[l].copy_(x); plan.mask[l].copy_(mask); plan.gy[l].copy_(gy)
-        for _ in range(3):
-            plan.forward(); plan.backward()
-        g = plan.capture(lambda: (plan.forward(), plan.backward()))
-        g.replay(); g.replay()
-        plan.check_handoff()
-        words = [plan.ctx_view(l)["sync"][B * ((H * W + 15) // 16 + 1):][:4].clone() for l, (B, C, H, W) in enumerate(shapes)]
-        return plan.grad_bucket.clone(), [t.clone() for t in plan.gx], words
-
-    base = run()
-    monkeypatch.setenv("MGACBAM_WSA_TAIL", "1")
-    _lib.reload_env()
-    try:
-        tail = run()
-    finally:
-        monkeypatch.undo()
-        _lib.reload_env()
-    assert torch.equal(base[0], tail[0]) and all(torch.equal(a, b) for a, b in zip(base[1], tail[1]))
-    assert all(int(w.abs().sum()) == 0 for w in tail[2]), "arrival counters must be back at 0 between calls"
-
-
 def test_rccl_branch_of_the_gradient_exchange_runs_on_this_gpu(F):
     """`GradExchange`'s "nccl" (= RCCL) branch -- ReduceOp.AVG inside the collective, launched on a side stream behind an event, joined
     back into the compute stream -- on hardware.  A one-GPU box cannot host two RCCL ranks, so this is a ONE-rank group with the
