@@ -13,7 +13,7 @@
  *     frees, copies to the host or synchronises, so every call may be captured in a hipGraph.
  *   - re-entrant: no mutable globals except a thread-local error string.
  *   - return value: 0 = ok, <0 = argument error (MGACBAM_E_*), >0 = hipError_t from a launch.
- *   - tensors are dense NCHW; `dtype` selects the element type of x / y / gy / gx (mask, parameters,
+ *   - tensors are dense NCHW, or dense NHWC (channels_last) for MaskCBAM levels flagged MGACBAM_LAYOUT_NHWC; `dtype` selects the element type of x / y / gy / gx (mask, parameters,
  *     every accumulator and every saved statistic are fp32).
  *
  * Entry-point families: mgacbam_*  MaskCBAM (the hot path) + mgacbam_eca_* MaskECA + mgacbam_resize_nearest;
@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MGACBAM_ABI_VERSION 14
+#define MGACBAM_ABI_VERSION 15
 #define MGACBAM_MAX_LEVELS 8          /* P3/P4/P5 need 3 */
 
 enum { MGACBAM_F32 = 0, MGACBAM_F16 = 1, MGACBAM_BF16 = 2 };
@@ -43,6 +43,13 @@ enum { MGACBAM_F32 = 0, MGACBAM_F16 = 1, MGACBAM_BF16 = 2 };
 #define MGACBAM_PROJ_MAX_HIDDEN 4
 enum { MGACBAM_FWD_SAVE_PROJ = 1 };
 enum { MGACBAM_BWD_HAVE_PROJ = 1 };
+/* Layout flag of a forward or backward level (ABI 15): x, y, gy and gx are dense (B,H,W,C) -- torch's channels_last -- instead of
+ * (B,C,H,W); mask and gmask stay (B,1,H,W) and ctx keeps its layout, so both layouts save the same statistics.  NHWC levels run kernels
+ * of their own (5 launches forward, 7 backward for all NHWC levels of a call), ignore SAVE_PROJ / HAVE_PROJ and MGACBAM_FWD_FUSE /
+ * MGACBAM_BWD_FUSE / MGACBAM_BWD_FOLD, need the forward workspace `ws` (mgacbam_fwd_ws_bytes) and size their backward scratch with
+ * mgacbam_bwd_scratch_bytes_flags.  x / y / gy / gx must be aligned to the element size times the lane width along C: 8 for fp16 /
+ * bf16 with C % 8 == 0, else 4 when C % 4 == 0, else 1 (MGACBAM_E_ALIGN).  NHWC and NCHW levels of one call go to separate launch groups. */
+enum { MGACBAM_LAYOUT_NHWC = 2 };
 
 enum {
   MGACBAM_E_NULL = -1,        /* required pointer is NULL */
@@ -87,7 +94,10 @@ typedef struct mgacbam_fwd_level {
   mgacbam_params_t p;
   int32_t B, C, H, W;
   int32_t dtype;
-  int32_t flags;             /* MGACBAM_FWD_* */
+  int32_t flags;             /* MGACBAM_FWD_SAVE_PROJ | MGACBAM_LAYOUT_NHWC */
+  void* ws;                  /* MGACBAM_LAYOUT_NHWC levels: mgacbam_fwd_ws_bytes(), per-chunk pooling partials, contents undefined
+                                (NULL allowed for NCHW levels) */
+  size_t ws_bytes;           /* capacity of ws (checked: MGACBAM_E_SIZE) */
 } mgacbam_fwd_level_t;
 
 /* One pyramid level of a backward call: replaces what autograd derives for the block. */
@@ -110,7 +120,7 @@ typedef struct mgacbam_bwd_level {
   mgacbam_params_t p;
   int32_t B, C, H, W;
   int32_t dtype;
-  int32_t flags;             /* MGACBAM_BWD_HAVE_PROJ */
+  int32_t flags;             /* MGACBAM_BWD_HAVE_PROJ | MGACBAM_LAYOUT_NHWC */
 } mgacbam_bwd_level_t;
 
 /* Named regions inside ctx (byte offsets), for stage-wise tests and tooling.  All fp32 unless noted. */
@@ -150,6 +160,11 @@ const char* mgacbam_build_info(void);      /* "gfx950 hipcc-x.y ..." */
 size_t mgacbam_ctx_bytes(int B, int C, int H, int W, int hidden);
 size_t mgacbam_bwd_scratch_bytes(int B, int C, int H, int W, int hidden, int k);
 int mgacbam_ctx_layout(int B, int C, int H, int W, int hidden, mgacbam_ctx_layout_t* out);
+/* Layout-aware size queries (ABI 15), `flags` = the level's flags.  Forward workspace: 0 for NCHW levels, > 0 for MGACBAM_LAYOUT_NHWC
+ * levels (enough for every element type).  Backward scratch: mgacbam_bwd_scratch_bytes() for NCHW levels, the NHWC requirement otherwise.
+ * 0 also means a bad shape. */
+size_t mgacbam_fwd_ws_bytes(int B, int C, int H, int W, int hidden, int flags);
+size_t mgacbam_bwd_scratch_bytes_flags(int B, int C, int H, int W, int hidden, int k, int flags);
 
 /* Forward / backward over n_levels independent pyramid levels (P3/P4/P5 = 3) enqueued on `stream`. */
 int mgacbam_forward(const mgacbam_fwd_level_t* levels, int n_levels, void* stream);

@@ -8,7 +8,7 @@ import threading
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGACBAM_LIB") or os.path.join(_PKG, "libmgacbam.so")   # MGACBAM_LIB: A/B builds in tuning sweeps
-ABI_VERSION = 14
+ABI_VERSION = 15
 MAX_LEVELS = 8
 F32, F16, BF16 = 0, 1, 2
 E_NULL, E_SHAPE, E_DTYPE, E_ALIGN, E_LEVELS, E_SIZE = -1, -2, -3, -4, -5, -6
@@ -17,6 +17,7 @@ FWD_STAGES = dict(pool=1, chan=2, apply=4)
 BWD_STAGES = dict(reduce1=1, convT=2, reduce2=4, wsa=8, params=16, apply=32)
 BWD_FUSE = 64
 FWD_SAVE_PROJ, BWD_HAVE_PROJ, PROJ_MAX_HIDDEN = 1, 1, 4
+LAYOUT_NHWC = 2   # level flag (forward and backward): x, y, gy, gx are (B,H,W,C) -- torch's channels_last
 FWD_ALL, BWD_PARAMS, BWD_INPUTS, BWD_ALL = 7, 31, 32, 127
 BWD_FOLD = 128   # with BWD_ALL: transposed conv folded into the k_bwd_reduce1 launch (ctx.sync zero-filled once by the caller)
 FWD_FUSE = 8   # with FWD_ALL: one launch, in-launch hand-off through ctx.sync (caller zero-fills it once)
@@ -34,7 +35,7 @@ class Params(C.Structure):                       # mgacbam_params_t
 class FwdLevel(C.Structure):                     # mgacbam_fwd_level_t
     _fields_ = [("x", C.c_void_p), ("mask", C.c_void_p), ("y", C.c_void_p), ("ctx", C.c_void_p), ("ctx_bytes", C.c_size_t),
                 ("p", Params), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
-                ("dtype", C.c_int32), ("flags", C.c_int32)]
+                ("dtype", C.c_int32), ("flags", C.c_int32), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
 class BwdLevel(C.Structure):                     # mgacbam_bwd_level_t
@@ -120,6 +121,8 @@ SYMBOLS = {
     "mgacbam_ctx_bytes": (C.c_size_t, [C.c_int] * 5),
     "mgacbam_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 6),
     "mgacbam_ctx_layout": (C.c_int, [C.c_int] * 5 + [C.POINTER(CtxLayout)]),
+    "mgacbam_fwd_ws_bytes": (C.c_size_t, [C.c_int] * 6),
+    "mgacbam_bwd_scratch_bytes_flags": (C.c_size_t, [C.c_int] * 7),
     "mgacbam_forward": (C.c_int, [C.POINTER(FwdLevel), C.c_int, C.c_void_p]),
     "mgacbam_backward": (C.c_int, [C.POINTER(BwdLevel), C.c_int, C.c_void_p]),
     "mgacbam_forward_stages": (C.c_int, [C.POINTER(FwdLevel), C.c_int, C.c_int, C.c_void_p]),
@@ -217,13 +220,30 @@ def ctx_bytes(B, Cc, H, W, hidden) -> int:
     return n
 
 
-def scratch_bytes(B, Cc, H, W, hidden, k) -> int:
-    key = ("scratch", B, Cc, H, W, hidden, k)
+def scratch_bytes(B, Cc, H, W, hidden, k, flags: int = 0) -> int:
+    key = ("scratch", B, Cc, H, W, hidden, k, flags & LAYOUT_NHWC)
     n = _size_cache.get(key)
     if n is None:
-        n = load().mgacbam_bwd_scratch_bytes(B, Cc, H, W, hidden, k)
+        if flags & LAYOUT_NHWC:
+            n = load().mgacbam_bwd_scratch_bytes_flags(B, Cc, H, W, hidden, k, LAYOUT_NHWC)
+        else:
+            n = load().mgacbam_bwd_scratch_bytes(B, Cc, H, W, hidden, k)
         if n == 0:
             check(-2, "mgacbam_bwd_scratch_bytes")
+        _size_cache[key] = n
+    return n
+
+
+def fwd_ws_bytes(B, Cc, H, W, hidden, flags: int) -> int:
+    """Forward workspace of a level: 0 for NCHW levels, the per-chunk pooling partials for LAYOUT_NHWC levels."""
+    if not flags & LAYOUT_NHWC:
+        return 0
+    key = ("ws", B, Cc, H, W, hidden)
+    n = _size_cache.get(key)
+    if n is None:
+        n = load().mgacbam_fwd_ws_bytes(B, Cc, H, W, hidden, LAYOUT_NHWC)
+        if n == 0:
+            check(-2, "mgacbam_fwd_ws_bytes")
         _size_cache[key] = n
     return n
 

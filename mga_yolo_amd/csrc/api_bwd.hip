@@ -1,6 +1,7 @@
 // libmgacbam.so, C ABI (include/mgacbam.h): MaskCBAM backward (mgacbam_backward[_stages])
 #include "host.cuh"
 #include "bwd.cuh"
+#include "nhwc_bwd.cuh"
 
 // ------------------------------------------------------------------------------------------------
 // backward
@@ -194,15 +195,152 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward of channels-last levels (nhwc.cuh): k_bwd_reduce1_nhwc, k_bwd_convT, k_bwd_reduce2_nhwc + k_bwd_fold_nhwc, k_bwd_wsa,
+// k_bwd_params, k_bwd_apply_nhwc -- the layout-free kernels are the NCHW path's own
+// ------------------------------------------------------------------------------------------------
+namespace mgacbam {
+inline int level_weight(const NhwcBwdArgs& a, int) { return a.a.g.C; }   // (found by for_each_group through ADL)
+}
+
+static int nhwc_backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig) {
+  if (!L.x || !L.gy || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "backward: x / gy / ctx / scratch / gx is NULL");
+  if (!L.gw1 || !L.gb1 || !L.gw2 || !L.gb2 || !L.gwsa || !L.gbeta) return fail(MGACBAM_E_NULL, "backward: NULL parameter-gradient pointer");
+  if (L.gmask && !L.mask) return fail(MGACBAM_E_NULL, "backward: gmask requested but mask is NULL");
+  if (int e = check_params(L.p)) return e;
+  if (int e = check_shape(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k)) return e;
+  if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "backward: dtype %d", L.dtype);
+  const int VEC = nhwc_vec(L.C, L.dtype);
+  const size_t need = VEC * elem_size(L.dtype);
+  if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
+      !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 4)) || (L.mask && !aligned_to(L.mask, 4)))
+    return fail(MGACBAM_E_ALIGN, "backward (NHWC): x/gy/gx must be %zu-byte aligned, ctx/scratch 16-byte", need);
+  const ScratchLayout SL = nhwc_scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k, VEC);
+  {
+    mgacbam_ctx_layout_t CL;
+    ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, &CL);
+    if (int e = check_capacity("backward", "ctx", static_cast<size_t>(CL.total), L.ctx_bytes)) return e;
+    if (int e = check_capacity("backward", "scratch", SL.total, L.scratch_bytes)) return e;
+  }
+  BwdArgs& A = N.a;
+  A.x = L.x; A.mask = L.mask; A.gy = L.gy; A.gx = L.gx; A.gmask = L.gmask;
+  A.gw1 = L.gw1; A.gb1 = L.gb1; A.gw2 = L.gw2; A.gb2 = L.gb2; A.gwsa = L.gwsa; A.gbeta = L.gbeta;
+  A.c = ctx_ptrs(const_cast<void*>(L.ctx), L.B, L.C, L.H, L.W, L.p.hidden);
+  A.p = make_params(L.p);
+  A.g = make_geo(L.B, L.C, L.H, L.W, L.p);
+  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k);
+  char* sp = static_cast<char*>(L.scratch);
+  A.s.A_part = reinterpret_cast<float*>(sp + SL.A_part);
+  A.s.gpre = reinterpret_cast<float*>(sp + SL.gpre); A.s.gplanes = reinterpret_cast<float*>(sp + SL.gplanes);
+  A.s.gwsa_part = reinterpret_cast<float*>(sp + SL.gwsa_part);
+  A.s.gz = reinterpret_cast<float*>(sp + SL.gz); A.s.gbq = reinterpret_cast<float*>(sp + SL.gbq);
+  A.s.gh_avg = reinterpret_cast<float*>(sp + SL.gh_avg); A.s.gh_mx = reinterpret_cast<float*>(sp + SL.gh_mx);
+  A.s.pgh = reinterpret_cast<float*>(sp + SL.pgh);
+  N.n = nhwc_geo(L.C, L.H, L.W, VEC);
+  N.ncb = (L.C + kNhwcFoldC - 1) / kNhwcFoldC;
+  A.nt = N.n.nchunk;
+  A.nconv = A.g.B * conv_tiles(A.t, A.g.H, A.g.W);
+  A.nwsa = A.g.B * wsa_tiles(A.t, A.g.H, A.g.W);
+  A.npg = params_blocks(A.g);
+  A.ncg = N.ncb;
+  A.nflag = static_cast<int>(sync_flags(static_cast<size_t>(L.H) * L.W));
+  A.bflag0 = A.cflag0 = A.mbflag0 = A.mcflag0 = A.wflag0 = A.sflag0 = 0;   // (no in-launch hand-off on this path)
+  A.merged = 0;
+  A.vec = VEC;
+  { const Knobs kn = knobs(); A.trace = kn.trace; A.spin_limit = kn.spin_limit; }
+  A.g.proj_h = 0;                                               // (HAVE_PROJ is ignored: the NHWC apply reads x for dL/dmask)
+  sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, L.gmask != nullptr, 0};
+  sig.nhwc = 1;
+  return 0;
+}
+
+static int backward_group_nhwc(NhwcBwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
+  Group<NhwcBwdArgs> G;
+  Group<BwdArgs> GB;                                            // the layout-free kernels take the plain level arguments
+  G.n = GB.n = n;
+  for (int l = 0; l < n; ++l) { G.lv[l] = lv[l]; GB.lv[l] = lv[l].a; }
+  auto fill = [&](auto blocks_of) { int tot = 0; for (int l = 0; l < n; ++l) { G.start[l] = tot; tot += blocks_of(lv[l]); } G.start[n] = tot; return tot; };
+  auto fillb = [&](auto blocks_of) { int tot = 0; for (int l = 0; l < n; ++l) { GB.start[l] = tot; tot += blocks_of(lv[l].a); } GB.start[n] = tot; return tot; };
+  auto chunks = [&]() { return fill([&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }); };
+  if (stages & MGACBAM_BWD_REDUCE1) {  // 1. chunk partials of A and D, g_pre
+    size_t smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, (3 * ((static_cast<size_t>(lv[l].a.g.C) + 3) & ~static_cast<size_t>(3)) + 2 * kBlock * sig.vec) * sizeof(float));
+    const int grid = chunks();
+#define CALL_NR1(Tt, Vv) LAUNCH((k_bwd_reduce1_nhwc<Tt, Vv>), grid, smem, st, G)
+    DISPATCH_T_NVEC(sig.dtype, sig.vec, CALL_NR1);
+#undef CALL_NR1
+    if (int e = launch_status("k_bwd_reduce1_nhwc")) return e;
+  }
+  if (stages & MGACBAM_BWD_CONVT) {  // 2. transposed conv
+    size_t smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, convT_smem(lv[l].a.t, sig.k));
+    const int grid = fillb([&](const BwdArgs& a) { return a.nconv; });
+    switch (sig.k) {
+      case 3: LAUNCH(k_bwd_convT<3>, grid, smem, st, GB); break;
+      case 5: LAUNCH(k_bwd_convT<5>, grid, smem, st, GB); break;
+      case 7: LAUNCH(k_bwd_convT<7>, grid, smem, st, GB); break;
+      default: LAUNCH(k_bwd_convT<0>, grid, smem, st, GB); break;
+    }
+    if (int e = launch_status("k_bwd_convT")) return e;
+  }
+  if (stages & MGACBAM_BWD_REDUCE2) {  // 3. chunk partials of the g_planes term, then their fold: g_z, D, hidden-gradient partials
+    size_t smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, static_cast<size_t>(lv[l].a.g.C) * sizeof(float));
+    const int grid = chunks();
+#define CALL_NR2(Tt, Vv) LAUNCH((k_bwd_reduce2_nhwc<Tt, Vv>), grid, smem, st, G)
+    DISPATCH_T_NVEC(sig.dtype, sig.vec, CALL_NR2);
+#undef CALL_NR2
+    if (int e = launch_status("k_bwd_reduce2_nhwc")) return e;
+    const int fgrid = fill([&](const NhwcBwdArgs& a) { return a.a.g.B * a.ncb; });
+    LAUNCH(k_bwd_fold_nhwc, fgrid, 0, st, G);
+    if (int e = launch_status("k_bwd_fold_nhwc")) return e;
+  }
+  if (stages & MGACBAM_BWD_WSA) {  // 4. dWsa tile partials
+    size_t smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, wsa_smem(lv[l].a.t, sig.k));
+    const int grid = fillb([&](const BwdArgs& a) { return a.nwsa; });
+    switch (sig.k) {
+      case 3: LAUNCH(k_bwd_wsa<3>, grid, smem, st, GB); break;
+      case 5: LAUNCH(k_bwd_wsa<5>, grid, smem, st, GB); break;
+      case 7: LAUNCH(k_bwd_wsa<7>, grid, smem, st, GB); break;
+      default: LAUNCH(k_bwd_wsa<0>, grid, smem, st, GB); break;
+    }
+    if (int e = launch_status("k_bwd_wsa")) return e;
+  }
+  if (stages & MGACBAM_BWD_PARAMGRAD) {  // 5. every parameter gradient
+    size_t smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, params_smem(lv[l].a.g));
+    const int grid = fillb([&](const BwdArgs& a) { return a.npg; });
+    LAUNCH(k_bwd_params, grid, smem, st, GB);
+    if (int e = launch_status("k_bwd_params")) return e;
+  }
+  if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask)
+    size_t smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, (5 * static_cast<size_t>(lv[l].a.g.C) + 2 * lv[l].a.g.hidden) * sizeof(float));
+    const int grid = fill([&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); });
+#define CALL_NAP(Tt, Vv) if (sig.gmask) LAUNCH((k_bwd_apply_nhwc<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_bwd_apply_nhwc<Tt, Vv, false>), grid, smem, st, G)
+    DISPATCH_T_NVEC(sig.dtype, sig.vec, CALL_NAP);
+#undef CALL_NAP
+    if (int e = launch_status("k_bwd_apply_nhwc")) return e;
+  }
+  return 0;
+}
+
 extern "C" int mgacbam_backward_stages(const mgacbam_bwd_level_t* levels, int n_levels, int stages, void* stream) {
   if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
   if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
   hipStream_t st = static_cast<hipStream_t>(stream);
   BwdArgs args[MGACBAM_MAX_LEVELS];
   Sig sigs[MGACBAM_MAX_LEVELS];
-  for (int l = 0; l < n_levels; ++l)
-    if (int e = backward_args(levels[l], args[l], sigs[l])) return e;
-  if (int e = for_each_group(args, sigs, n_levels, [&](BwdArgs* g, int m, const Sig& s) { return backward_group(g, m, s, stages, st); })) return e;
+  NhwcBwdArgs nargs[MGACBAM_MAX_LEVELS];
+  Sig nsigs[MGACBAM_MAX_LEVELS];
+  int nc = 0, nn = 0;                                           // NCHW levels, NHWC levels (every level is checked before any launch)
+  for (int l = 0; l < n_levels; ++l) {
+    if (levels[l].flags & MGACBAM_LAYOUT_NHWC) { if (int e = nhwc_backward_args(levels[l], nargs[nn], nsigs[nn])) return e; ++nn; }
+    else { if (int e = backward_args(levels[l], args[nc], sigs[nc])) return e; ++nc; }
+  }
+  if (nc) if (int e = for_each_group(args, sigs, nc, [&](BwdArgs* g, int m, const Sig& s) { return backward_group(g, m, s, stages, st); })) return e;
+  if (nn) if (int e = for_each_group(nargs, nsigs, nn, [&](NhwcBwdArgs* g, int m, const Sig& s) { return backward_group_nhwc(g, m, s, stages, st); })) return e;
   g_err[0] = 0;
   return 0;
 }

@@ -89,6 +89,19 @@ struct BwdArgs {
   long long* trace;   // MGACBAM_TRACE builds only (tools/trace_gate.py), else nullptr
 };
 
+// channels-last levels (nhwc.cuh): chunk geometry, a function of the level alone (host: nhwc_geo)
+struct NhwcGeo {
+  int cs, lcs;     // lanes per pixel (power of two <= 64) and its log2
+  int ng;          // channel groups of VEC channels: ceil(C / VEC)
+  int ch;          // pixels per TILE = (256 / cs) * pixels per thread (8; 4 with 8-element lanes)
+  int ntile;       // tiles per sample: the per-pixel kernels (k_chan_nhwc, k_apply_nhwc, k_bwd_apply_nhwc) take one tile per workgroup
+  int rp;          // tiles per CHUNK: the per-channel kernels (k_pool_nhwc, k_bwd_reduce1_nhwc, k_bwd_reduce2_nhwc) sweep rp tiles per
+                   // workgroup and write one partial per chunk, so a sample has at most kNhwcMaxChunks partials to fold
+  int nchunk;      // chunks per sample = ceil(ntile / rp)
+};
+constexpr int kNhwcMaxChunks = 64;
+constexpr int kNhwcFoldC = 64;   // channels per workgroup of the NHWC fold kernels (x 4 chunk groups = 256 threads)
+
 static inline size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
 
 // One launch covers up to kGroupMax pyramid levels: workgroup ids [start[l], start[l+1]) belong to level l.

@@ -298,6 +298,52 @@ static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int 
   return L;
 }
 
+// ------------------------------------------------------------------------------------------------
+// channels-last levels (MGACBAM_LAYOUT_NHWC, nhwc.cuh): chunk geometry and work buffers, functions of the level alone
+// ------------------------------------------------------------------------------------------------
+// elements per lane along C: 16 B when C allows it (fp32: 4, fp16 / bf16: 8), else 4 or scalar
+static int nhwc_vec(int C, int dtype) { return (dtype != MGACBAM_F32 && C % 8 == 0) ? 8 : (C % 4 == 0 ? 4 : 1); }
+static NhwcGeo nhwc_geo(int C, int H, int W, int vec) {
+  NhwcGeo n;
+  n.ng = (C + vec - 1) / vec;
+  n.cs = std::max(4, std::min(pow2_ceil(n.ng), 64));         // >= 4 lanes: a tile is at most 512 pixels (k_apply_nhwc stages its rows)
+  n.lcs = 0;
+  while ((1 << n.lcs) < n.cs) ++n.lcs;
+  n.ch = (kBlock / n.cs) * (vec == 8 ? 4 : 8);                // pixels per thread: nhwc.cuh NhwcNpx
+  n.ntile = static_cast<int>((static_cast<long long>(H) * W + n.ch - 1) / n.ch);
+  n.rp = (n.ntile + kNhwcMaxChunks - 1) / kNhwcMaxChunks;     // H*W-dependent chunking: at most kNhwcMaxChunks partials per sample
+  n.nchunk = (n.ntile + n.rp - 1) / n.rp;
+  return n;
+}
+static size_t nhwc_ws_bytes(int B, int C, int H, int W, int vec) {
+  return static_cast<size_t>(B) * nhwc_geo(C, H, W, vec).nchunk * (4 * static_cast<size_t>(C) + 4) * sizeof(float);
+}
+static ScratchLayout nhwc_scratch_layout(int B, int C, int H, int W, int hidden, int k, int vec) {
+  const Tune t = choose_tune(B, C, H, W, k);                  // (only its conv tiling, which does not depend on B, is used)
+  const NhwcGeo n = nhwc_geo(C, H, W, vec);
+  const size_t HW = static_cast<size_t>(H) * W, BC = static_cast<size_t>(B) * C;
+  const size_t nwsa = static_cast<size_t>(B) * wsa_tiles(t, H, W), ncb = (C + kNhwcFoldC - 1) / kNhwcFoldC;
+  ScratchLayout L;
+  size_t o = 0;
+  auto take = [&](size_t n_elems) { size_t at = o; o = align16(o + n_elems * 4); return at; };
+  L.A_part = take(3 * BC * n.nchunk);                          // (B, nchunk, 3, C): A, D, sum x*wgt
+  L.gpre = take(B * HW); L.gplanes = take(static_cast<size_t>(B) * 3 * HW);
+  L.gwsa_part = take(nwsa * 3 * k * k);
+  L.gz = take(BC); L.gbq = take(BC);
+  L.gh_avg = take(static_cast<size_t>(B) * hidden); L.gh_mx = take(static_cast<size_t>(B) * hidden);
+  L.pgh = take(static_cast<size_t>(B) * ncb * hidden);
+  L.total = o;
+  return L;
+}
+// the size queries take no element type: the answer covers every one
+static size_t nhwc_ws_bytes_any(int B, int C, int H, int W) {
+  return std::max(nhwc_ws_bytes(B, C, H, W, nhwc_vec(C, MGACBAM_F32)), nhwc_ws_bytes(B, C, H, W, nhwc_vec(C, MGACBAM_F16)));
+}
+static size_t nhwc_scratch_bytes_any(int B, int C, int H, int W, int hidden, int k) {
+  return std::max(nhwc_scratch_layout(B, C, H, W, hidden, k, nhwc_vec(C, MGACBAM_F32)).total,
+                  nhwc_scratch_layout(B, C, H, W, hidden, k, nhwc_vec(C, MGACBAM_F16)).total);
+}
+
 // ABI 14: every work buffer travels with its capacity; the requirement is recomputed under the CURRENT knobs at every call
 static int check_capacity(const char* what, const char* buf, size_t want, size_t got) {
   if (got < want)
@@ -329,6 +375,9 @@ static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintp
     else { if ((VECV) == 8) { CALL(bf16_t, 8); } else if ((VECV) == 4) { CALL(bf16_t, 4); } else { CALL(bf16_t, 1); } }          \
   } while (0)
 
+// T x VEC of the NHWC kernels (nhwc_vec): fp16 / bf16 also 8
+#define DISPATCH_T_NVEC(dtype, VECV, CALL) DISPATCH_T_GVEC(dtype, VECV, CALL)
+
 #define DISPATCH_CPT(CPTV, CALL2)                                              \
   do { if ((CPTV) == 4) { CALL2(4); } else if ((CPTV) == 2) { CALL2(2); } else { CALL2(1); } } while (0)
 
@@ -350,11 +399,12 @@ static int check_params(const mgacbam_params_t& p) {
 struct Sig {
   int dtype, vec, has_mask, k, gmask, proj;
   int lf32 = 0;   // mask head only: logits / g_logits are fp32 whatever dtype is (MGAHEAD_LOGITS_F32)
+  int nhwc = 0;   // MGACBAM_LAYOUT_NHWC level: kernels of nhwc.cuh (vec = its lanes' width along C)
   int gvec = 0;   // forward only: elements per lane of k_gate for this level -- a function of the LEVEL alone (dtype, shape, k, knobs), never of
                   // the levels it happens to be called with: the hand-off flags in ctx.sync count calls per TILE, so a ctx must see the same
                   // tiling in every call whatever the group composition (levels of different gvec go to different launches)
   bool operator==(const Sig& o) const {
-    return dtype == o.dtype && vec == o.vec && has_mask == o.has_mask && k == o.k && gmask == o.gmask && proj == o.proj && gvec == o.gvec && lf32 == o.lf32;
+    return dtype == o.dtype && vec == o.vec && has_mask == o.has_mask && k == o.k && gmask == o.gmask && proj == o.proj && gvec == o.gvec && lf32 == o.lf32 && nhwc == o.nhwc;
   }
 };
 

@@ -1,0 +1,352 @@
+// Forward kernels of channels-last (MGACBAM_LAYOUT_NHWC) levels: thread layout and data flow in nhwc.cuh.
+#pragma once
+#include "fwd.cuh"    // kSelLogit, mlp_gate_to_lds
+#include "nhwc.cuh"
+#include "tile.cuh"
+
+namespace mgacbam {
+
+// ---------------------------------------------------------------------------------------------
+// k_pool_nhwc: workgroup = (sample, chunk of rp tiles).  Per tile and channel group the rows' sums meet in LDS in row order; the
+// channel's owner thread adds them, tile by tile, to the chunk's running sums in LDS; the chunk's partials then go to ws.
+//   LDS: [256*VEC x 3 row sums][256*VEC row arg-max (int)] static ; [C sum x*s][C sum x][C max][C arg-max (int)] dynamic
+// ---------------------------------------------------------------------------------------------
+template <typename T, int VEC, bool HAS_MASK>
+__global__ __launch_bounds__(kBlock) void k_pool_nhwc(const Group<NhwcFwdArgs> G) {
+  __shared__ __align__(16) float red[3 * kBlock * VEC];
+  __shared__ __align__(16) int redi[kBlock * VEC];
+  extern __shared__ __align__(16) float s_acc[];
+  int local;
+  const int l = find_level(G, blockIdx.x, local);
+  const NhwcFwdArgs& N = G.lv[l];
+  const FwdArgs& A = N.a;
+  const Geo& g = A.g;
+  int b, chunk;
+  if (!xcd_sample_part(local, g.B, N.n.nchunk, b, chunk)) return;
+  constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
+  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
+  float* part = N.ws + (static_cast<size_t>(b) * N.n.nchunk + chunk) * (4 * static_cast<size_t>(g.C) + 4);
+  int* s_idx = reinterpret_cast<int*>(s_acc + 3 * g.C);
+  for (int c = tid; c < g.C; c += kBlock) { s_acc[c] = 0.f; s_acc[g.C + c] = 0.f; s_acc[2 * g.C + c] = -FLT_MAX; s_idx[c] = INT_MAX; }
+  float ssum = 0.f;
+  const int nj = (N.n.ng + CS - 1) / CS, CV = CS * VEC;
+  const int t_end = min((chunk + 1) * N.n.rp, N.n.ntile);
+  for (int tile = chunk * N.n.rp; tile < t_end; ++tile) {
+    const int p0 = tile * N.n.ch;
+    float s[kNhwcNpx];
+    bool sel[kNhwcNpx], okp[kNhwcNpx];
+#pragma unroll
+    for (int k = 0; k < kNhwcNpx; ++k) {
+      const int p = p0 + k * PR + row;
+      okp[k] = p < g.HW;
+      s[k] = 0.f; sel[k] = okp[k];
+      if (HAS_MASK && okp[k]) {
+        const float m = A.mask[static_cast<size_t>(b) * g.HW + p];
+        s[k] = g.use_sigmoid ? sigmoid_fast(m) : m;                       // masked_cbam.py:93-94
+        sel[k] = g.use_sigmoid ? m > kSelLogit : s[k] > 0.5f;             // masked_cbam.py:116 (fwd.cuh: kSelLogit)
+        ssum += s[k];
+      }
+    }
+    for (int j = 0; j < nj; ++j) {
+      const int cgi = lane + j * CS;
+      const bool okc = cgi < N.n.ng;
+      const int c0 = min(cgi, N.n.ng - 1) * VEC;
+      float acc[3][VEC];                                                  // [sum x*s][sum x][max]
+      int im[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; acc[2][e] = -FLT_MAX; im[e] = INT_MAX; }
+      float xv[kNhwcNpx][VEC];
+#pragma unroll
+      for (int k = 0; k < kNhwcNpx; ++k) {
+        const int p = okp[k] ? p0 + k * PR + row : 0;
+        load_vec<T, VEC>(xb + static_cast<size_t>(p) * g.C + c0, xv[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < kNhwcNpx; ++k) {
+        if (!okp[k] || !okc) continue;
+        const int p = p0 + k * PR + row;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          const float v = xv[k][e];
+          acc[1][e] += v;
+          if (HAS_MASK) acc[0][e] += v * s[k];
+          if (sel[k] && v > acc[2][e]) { acc[2][e] = v; im[e] = p; }      // pixels ascend along k: strict > keeps the first
+        }
+      }
+      nhwc_rows_sum<3, VEC>(acc, red, tid);
+      // (the arg-max pixel travels as an int: red's barrier pair above also orders these stores against the reads below)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) redi[tid * VEC + e] = im[e];
+      __syncthreads();
+      for (int t = tid; t < CV; t += kBlock) {                            // (CV = 512 with 8-element lanes)
+        const int c = j * CV + t;
+        if (c < g.C) {
+          float sxs = 0.f, sx = 0.f, vm = -FLT_MAX;
+          int ix = INT_MAX;
+          for (int r = 0; r < PR; ++r) {
+            const int o = r * CV + t;                                     // element (row r, lane t / VEC, e = t % VEC)
+            sxs += red[o]; sx += red[kBlock * VEC + o];
+            argmax_combine(vm, ix, red[2 * kBlock * VEC + o], redi[o]);
+          }
+          s_acc[c] += sxs; s_acc[g.C + c] += sx;                          // (channel c has ONE owner thread: fixed order over the tiles)
+          float cm = s_acc[2 * g.C + c];
+          int ci = s_idx[c];
+          argmax_combine(cm, ci, vm, ix);
+          s_acc[2 * g.C + c] = cm; s_idx[c] = ci;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < g.C; c += kBlock) {
+    part[c] = s_acc[c]; part[g.C + c] = s_acc[g.C + c]; part[2 * g.C + c] = s_acc[2 * g.C + c];
+    reinterpret_cast<int*>(part)[3 * g.C + c] = s_idx[c];
+  }
+  // sum of s over the chunk: rows in order
+  if (HAS_MASK) {
+    if (lane == 0) red[row] = ssum;
+    __syncthreads();
+    if (tid == 0) { float t = 0.f; for (int r = 0; r < PR; ++r) t += red[r]; part[4 * g.C] = t; }
+  } else if (tid == 0) {
+    part[4 * g.C] = 0.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_pool_fin: workgroup = (sample, block of kNhwcFoldC channels); its 4 waves fold the chunk partials of a channel with a stride of
+// 4 chunks, the 4 results are combined in wave order (fixed order; ties of the max go to the lower pixel: the first arg-max).  Writes the
+// pooled statistics exactly as k_pool defines them; the shared MLP follows as k_mlp.
+// ---------------------------------------------------------------------------------------------
+template <bool HAS_MASK>
+__global__ __launch_bounds__(kBlock) void k_pool_fin(const Group<NhwcFwdArgs> G) {
+  __shared__ float s_part[3][kBlock];
+  __shared__ int s_pidx[kBlock];
+  int local;
+  const int l = find_level(G, blockIdx.x, local);
+  const NhwcFwdArgs& N = G.lv[l];
+  const FwdArgs& A = N.a;
+  const Geo& g = A.g;
+  const int ncb = (g.C + kNhwcFoldC - 1) / kNhwcFoldC;
+  const int b = local / ncb, cb = local - b * ncb;
+  const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, nch = N.n.nchunk;
+  const size_t stride = 4 * static_cast<size_t>(g.C) + 4;
+  const float* wb = N.ws + static_cast<size_t>(b) * nch * stride;
+  float S = 0.f;                                                        // every workgroup of the sample forms S the same way
+  if (HAS_MASK) {
+    for (int q = lane; q < nch; q += 64) S += wb[q * stride + 4 * g.C];
+    S = wave_group_sum(S, 64);
+  }
+  const int c = cb * kNhwcFoldC + lane;
+  const int cc = min(c, g.C - 1);
+  float sxs = 0.f, sx = 0.f, vm = -FLT_MAX;
+  int im = INT_MAX;
+#pragma unroll 4
+  for (int q = grp; q < nch; q += 4) {
+    const float* pq = wb + q * stride;
+    sxs += pq[cc]; sx += pq[g.C + cc];
+    argmax_combine(vm, im, pq[2 * g.C + cc], reinterpret_cast<const int*>(pq)[3 * g.C + cc]);
+  }
+  s_part[0][tid] = sxs; s_part[1][tid] = sx; s_part[2][tid] = vm; s_pidx[tid] = im;
+  __syncthreads();
+  if (grp != 0 || c >= g.C) return;
+  for (int r = 1; r < 4; ++r) {
+    sxs += s_part[0][r * 64 + lane]; sx += s_part[1][r * 64 + lane];
+    argmax_combine(vm, im, s_part[2][r * 64 + lane], s_pidx[r * 64 + lane]);
+  }
+  if (im == INT_MAX) im = 0;                                            // nothing selected: k_pool leaves index 0
+  const float Nf = static_cast<float>(g.HW);
+  const float use = (S / Nf >= g.thr) ? 1.f : 0.f;                      // masked_cbam.py:97-98
+  const float den = fmaxf(S, g.eps);                                    // masked_cbam.py:99
+  const size_t o = static_cast<size_t>(b) * g.C + c;
+  const float gap = sx / Nf;                                            // masked_cbam.py:101
+  float avg, mavg, mxo;
+  int valid;
+  if (HAS_MASK) {
+    mavg = sxs / den;                                                   // masked_cbam.py:100
+    avg = mavg * use + gap * (1.f - use);                               // masked_cbam.py:102
+    valid = isclosef_(vm, -FLT_MAX) ? 0 : 1;                            // masked_cbam.py:120
+    mxo = valid ? vm : gap;                                             // masked_cbam.py:121
+  } else {
+    mavg = gap; avg = gap; valid = 1; mxo = vm;                         // masked_cbam.py:90-91, 107-108
+  }
+  A.c.avg[o] = avg; A.c.mavg[o] = mavg; A.c.mx[o] = mxo;
+  A.c.valid[o] = valid; A.c.amax[o] = im;
+  if (cb == 0 && lane == 0) {
+    A.c.S[b] = HAS_MASK ? S : 0.f;
+    A.c.use[b] = HAS_MASK ? use : 0.f;
+    A.c.den[b] = HAS_MASK ? den : 1.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_chan_nhwc: per pixel max_c u (+ first arg-max channel), mean_c u, sigma(mask)           masked_cbam.py:130,135-138,146
+//   LDS: [C ca]
+// ---------------------------------------------------------------------------------------------
+template <typename T, int VEC, bool HAS_MASK>
+__global__ __launch_bounds__(kBlock) void k_chan_nhwc(const Group<NhwcFwdArgs> G) {
+  extern __shared__ __align__(16) float smem[];
+  int local;
+  const int l = find_level(G, blockIdx.x, local);
+  const NhwcFwdArgs& N = G.lv[l];
+  const FwdArgs& A = N.a;
+  const Geo& g = A.g;
+  int b, chunk;
+  if (!xcd_sample_part(local, g.B, N.n.ntile, b, chunk)) return;
+  constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
+  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const int p0 = chunk * N.n.ch;
+  const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
+  float* s_ca = smem;
+  for (int c = tid; c < g.C; c += kBlock) s_ca[c] = A.c.ca[static_cast<size_t>(b) * g.C + c];
+  __syncthreads();
+  bool okp[kNhwcNpx];
+  float vmax[kNhwcNpx], vsum[kNhwcNpx];
+  int vidx[kNhwcNpx];
+#pragma unroll
+  for (int k = 0; k < kNhwcNpx; ++k) {
+    okp[k] = row < PR && p0 + k * PR + row < g.HW;
+    vmax[k] = -INFINITY; vsum[k] = 0.f; vidx[k] = lane * VEC;
+  }
+  const int nj = (N.n.ng + CS - 1) / CS;
+  for (int j = 0; j < nj; ++j) {
+    const int cgi = lane + j * CS;
+    if (cgi >= N.n.ng) break;
+    const int c0 = cgi * VEC;
+    float xv[kNhwcNpx][VEC];
+#pragma unroll
+    for (int k = 0; k < kNhwcNpx; ++k) {
+      const int p = okp[k] ? p0 + k * PR + row : 0;
+      load_vec<T, VEC>(xb + static_cast<size_t>(p) * g.C + c0, xv[k]);
+    }
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const int c = c0 + e;
+      if (c >= g.C) break;
+      const float cac = s_ca[c];
+#pragma unroll
+      for (int k = 0; k < kNhwcNpx; ++k) {
+        const float u = xv[k][e] * cac;                                  // masked_cbam.py:130
+        vsum[k] += u;
+        if (u > vmax[k]) { vmax[k] = u; vidx[k] = c; }                   // channels ascend within a lane: strict > keeps the first
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kNhwcNpx; ++k) {
+    vsum[k] = wave_group_sum(vsum[k], CS);
+    wave_group_argmax(vmax[k], vidx[k], CS);                             // ties -> the lower channel
+    if (lane == 0 && okp[k]) {
+      const int p = p0 + k * PR + row;
+      float* pl = A.c.planes + static_cast<size_t>(b) * 3 * g.HW + p;
+      pl[0] = vmax[k];
+      pl[g.HW] = vsum[k] / static_cast<float>(g.C);                      // masked_cbam.py:136
+      float s = 0.f;
+      if (HAS_MASK) { const float m = A.mask[static_cast<size_t>(b) * g.HW + p]; s = g.use_sigmoid ? sigmoid_fast(m) : m; }
+      pl[2 * g.HW] = s;                                                  // masked_cbam.py:138,146 (zero plane without a mask)
+      A.c.cidx[static_cast<size_t>(b) * g.HW + p] = vidx[k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_apply_nhwc: prologue = k x k conv + sigmoid for the chunk's pixels (plane window staged in LDS, as k_apply); body = y
+//   LDS: [3*k*k weights][3 * rows * (W+k-1) planes][CH sa][C ca]
+// ---------------------------------------------------------------------------------------------
+template <typename T, int VEC, int K>
+__global__ __launch_bounds__(kBlock) void k_apply_nhwc(const Group<NhwcFwdArgs> G) {
+  extern __shared__ __align__(16) float smem[];
+  int local;
+  const int l = find_level(G, blockIdx.x, local);
+  const NhwcFwdArgs& N = G.lv[l];
+  const FwdArgs& A = N.a;
+  const Geo& g = A.g;
+  int b, chunk;
+  if (!xcd_sample_part(local, g.B, N.n.ntile, b, chunk)) return;
+  constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
+  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const int CH = N.n.ch;
+  const int p0 = chunk * CH, p1 = min(p0 + CH, g.HW) - 1;
+  const int k = K ? K : g.k, pad = k / 2;
+  const int r0 = p0 / g.W, r1 = p1 / g.W;
+  const int PW = g.W + k - 1, PH = (r1 - r0 + 1) + k - 1;
+  float* wts = smem;
+  float* planes = smem + ((3 * k * k + 3) & ~3);
+  float* s_sa = planes + 3 * A.t.apply_rows * PW;                        // apply_rows >= PH (host bound for this chunk size)
+  float* s_ca = s_sa + CH;
+  for (int t = tid; t < 3 * k * k; t += kBlock) wts[t] = A.p.wsa[t];
+  for (int c = tid; c < g.C; c += kBlock) s_ca[c] = A.c.ca[static_cast<size_t>(b) * g.C + c];
+  const float* pl = A.c.planes + static_cast<size_t>(b) * 3 * g.HW;
+  stage_window<12>(planes, 3, PH, PW, r0 - pad, -pad, g, [&](int p, int off) { return pl[static_cast<size_t>(p) * g.HW + off]; });
+  __syncthreads();
+  for (int tp = tid; tp < CH; tp += kBlock) {
+    if (p0 + tp >= g.HW) break;
+    const int p = p0 + tp;
+    const int py = p / g.W, px = p - py * g.W;
+    const float* origin = planes + (py - r0) * PW + px;
+    float acc = 0.f;
+    if (K) {
+      constexpr int KK = K ? K : 1;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+#pragma unroll
+        for (int ti = 0; ti < KK; ++ti) {
+          const float* rw = origin + q * PH * PW + ti * PW;
+          const float* wr = wts + (q * KK + ti) * KK;
+#pragma unroll
+          for (int tj = 0; tj < KK; ++tj) acc += wr[tj] * rw[tj];
+        }
+      }
+    } else {
+      for (int q = 0; q < 3; ++q)
+        for (int ti = 0; ti < k; ++ti) {
+          const float* rw = origin + q * PH * PW + ti * PW;
+          const float* wr = wts + (q * k + ti) * k;
+          for (int tj = 0; tj < k; ++tj) acc += wr[tj] * rw[tj];
+        }
+    }
+    const float sa = sigmoidf_(acc);                                     // masked_cbam.py:147
+    s_sa[tp] = sa;
+    A.c.sa[static_cast<size_t>(b) * g.HW + p] = sa;
+  }
+  __syncthreads();
+  const float a = softplusf_(*A.p.beta);                                 // masked_cbam.py:150-152
+  const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
+  T* yb = static_cast<T*>(A.y) + static_cast<size_t>(b) * g.HW * g.C;
+  bool okp[kNhwcNpx];
+  float sav[kNhwcNpx];
+#pragma unroll
+  for (int k2 = 0; k2 < kNhwcNpx; ++k2) {
+    const int tp = k2 * PR + row;
+    okp[k2] = row < PR && p0 + tp < g.HW;
+    sav[k2] = okp[k2] ? s_sa[tp] : 0.f;
+  }
+  const int nj = (N.n.ng + CS - 1) / CS;
+  for (int j = 0; j < nj; ++j) {
+    const int cgi = lane + j * CS;
+    if (cgi >= N.n.ng) break;
+    const int c0 = cgi * VEC;
+    float cav[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) cav[e] = s_ca[min(c0 + e, g.C - 1)];
+    float xv[kNhwcNpx][VEC];
+#pragma unroll
+    for (int k2 = 0; k2 < kNhwcNpx; ++k2) {
+      const int p = okp[k2] ? p0 + k2 * PR + row : 0;
+      load_vec<T, VEC>(xb + static_cast<size_t>(p) * g.C + c0, xv[k2]);
+    }
+#pragma unroll
+    for (int k2 = 0; k2 < kNhwcNpx; ++k2) {
+      float yv[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float u = xv[k2][e] * cav[e];                             // masked_cbam.py:130
+        const float v = u * sav[k2];                                     // masked_cbam.py:148
+        yv[e] = xv[k2][e] + a * (v - xv[k2][e]);                         // masked_cbam.py:171
+      }
+      if (okp[k2]) store_vec<T, VEC>(yb + static_cast<size_t>(p0 + k2 * PR + row) * g.C + c0, yv);
+    }
+  }
+}
+
+}  // namespace mgacbam

@@ -165,6 +165,19 @@ def _ready(t: torch.Tensor) -> torch.Tensor:
     return _aligned(t.detach())
 
 
+def _is_nhwc(x: torch.Tensor) -> bool:
+    """A level takes the channels-last kernels when x is channels_last-contiguous and NOT also NCHW-contiguous (C == 1 or H = W = 1 are
+    both: those, and every other stride pattern, keep the NCHW path)."""
+    return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+
+
+def _ready_nhwc(t: torch.Tensor) -> torch.Tensor:
+    """Detached, channels_last-contiguous, 16-byte aligned view/copy of t (one conversion at most)."""
+    if t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0:
+        return t
+    return t.detach().clone(memory_format=torch.channels_last)
+
+
 def _mask32(mask: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
     m = mask
     if m.dim() == 3:
@@ -208,7 +221,7 @@ class _PyramidFn(torch.autograd.Function):
         lib = _lib.load()
         levels = (_lib.FwdLevel * n)()
         keep: List[Optional[torch.Tensor]] = []
-        outs, meta, leases = [], [], []
+        outs, meta, leases, layouts, hold = [], [], [], [], []
         dev = flat[0].device
         if not flat[0].is_cuda:
             raise RuntimeError("mask_cbam: device tensors only (host tensors take the module's host path)")
@@ -220,7 +233,9 @@ class _PyramidFn(torch.autograd.Function):
                 raise RuntimeError("mask_cbam: all features must live on the same GPU")
             _check_level(x, mask, params, cfg)
             B, Cc, H, W = x.shape
-            xc = _ready(x)
+            nhwc = _is_nhwc(x)                                  # the layout decides the kernels, per level; y keeps it
+            flags = _lib.LAYOUT_NHWC if nhwc else 0
+            xc = _ready_nhwc(x) if nhwc else _ready(x)
             m32 = None if mask is None else _mask32(mask, B, H, W)
             pc = [_ready(p) for p in params]
             y = torch.empty_like(xc)
@@ -229,7 +244,7 @@ class _PyramidFn(torch.autograd.Function):
             #  flagged tiling from the level alone -- shape, element type, conv size k, knobs; never from the other levels of the call --
             #  and exactly those are in the key.  The merged backward's sweeps, whose channel groups do depend on the call, count per
             #  channel instead: tests/test_gpu_composition.py)
-            key = (dev.index, stream, B, Cc, H, W, cfg.hidden, x.dtype, _lib.ENV_EPOCH, cfg.k)
+            key = (dev.index, stream, B, Cc, H, W, cfg.hidden, x.dtype, _lib.ENV_EPOCH, cfg.k) + ((flags,) if flags else ())
             lease = _Lease(key, _POOL.take(key, _lib.ctx_bytes(B, Cc, H, W, cfg.hidden), _lib.ctx_layout(B, Cc, H, W, cfg.hidden)["sync"], dev))
             cbuf = lease.buf
             leases.append(lease)
@@ -238,19 +253,25 @@ class _PyramidFn(torch.autograd.Function):
             L.ctx_bytes = cbuf.numel()
             L.p = _params_struct(pc, cfg)
             L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[x.dtype]
-            # (L.flags stays 0: the W1-projection planes are not saved here -- at YOLOv8n sizes what k_bwd_apply saves (x of P3) k_chan
+            if nhwc:                                            # per-chunk pooling partials, consumed inside this call
+                ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, flags), dtype=torch.uint8, device=dev)
+                L.ws, L.ws_bytes, L.flags = ws.data_ptr(), ws.numel(), flags
+                hold.append(ws)
+            # (L.flags has no SAVE_PROJ: the W1-projection planes are not saved here -- at YOLOv8n sizes what k_bwd_apply saves (x of P3) k_chan
             #  pays back; PyramidPlan(use_proj=True) and forward_with_ctx still drive that path)
             keep += [xc, m32, *pc]
             outs.append(y)
+            layouts.append(flags)
             meta.append(None if mask is None else (mask.dtype, tuple(mask.shape)))
         with _on_device(dev):
             rc = lib.mgacbam_forward_stages(levels, n, _FWD_STAGES, stream)
         if rc:
             _lib.check(rc, "mgacbam_forward_stages")
+        del hold
         if _CHECK_HANDOFF:
             _check_status([(ls.buf, ls.key[2:7]) for ls in leases], "mask_cbam forward")
         ctx.save_for_backward(*keep)
-        ctx.cfgs, ctx.meta, ctx.leases = cfgs, meta, leases
+        ctx.cfgs, ctx.meta, ctx.leases, ctx.layouts = cfgs, meta, leases, layouts
         return tuple(outs)
 
     @staticmethod
@@ -268,13 +289,19 @@ class _PyramidFn(torch.autograd.Function):
             cbuf = ctx.leases[l].buf
             cfg = cfgs[l]
             B, Cc, H, W = xc.shape
+            flags = ctx.layouts[l]
             gy = gys[l]
-            gy = torch.zeros_like(xc) if gy is None else _aligned(gy.to(xc.dtype))
+            if gy is None:
+                gy = torch.zeros_like(xc)
+            elif flags & _lib.LAYOUT_NHWC:                         # a gy of any other layout is converted once
+                gy = _ready_nhwc(gy.to(xc.dtype))
+            else:
+                gy = _aligned(gy.to(xc.dtype))
             want_gmask = m32 is not None and ctx.needs_input_grad[1 + l * SLOTS + 1]
-            gx = torch.empty_like(xc)
+            gx = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
             gmask = torch.empty_like(m32) if want_gmask else None
             pg = [torch.empty_like(p) for p in pc]
-            scratch = torch.empty(_lib.scratch_bytes(B, Cc, H, W, cfg.hidden, cfg.k), dtype=torch.uint8, device=dev)
+            scratch = torch.empty(_lib.scratch_bytes(B, Cc, H, W, cfg.hidden, cfg.k, flags), dtype=torch.uint8, device=dev)
             L = levels[l]
             L.x, L.mask, L.gy, L.ctx, L.scratch = (xc.data_ptr(), None if m32 is None else m32.data_ptr(), gy.data_ptr(),
                                                    cbuf.data_ptr(), scratch.data_ptr())
@@ -282,7 +309,7 @@ class _PyramidFn(torch.autograd.Function):
             L.gx, L.gmask = gx.data_ptr(), (None if gmask is None else gmask.data_ptr())
             L.gw1, L.gb1, L.gw2, L.gb2, L.gwsa, L.gbeta = (t.data_ptr() for t in pg)
             L.p = _params_struct(pc, cfg)
-            L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[xc.dtype]
+            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[xc.dtype], flags
             hold += [gy, scratch]
             grads += [gx, gmask, *pg]
         with _on_device(dev):
@@ -318,11 +345,13 @@ def mask_cbam(x: torch.Tensor, mask: Optional[torch.Tensor], w1, b1, w2, b2, wsa
 # inspection helpers (tests / tooling): run the forward library call and view the saved statistics by name
 # ---------------------------------------------------------------------------------------------------------
 def forward_with_ctx(x, mask, params, cfg: BlockConfig, save_proj: bool = True):
-    """-> (y, {name: tensor view into ctx}) without autograd; names follow mgacbam_ctx_layout_t."""
+    """-> (y, {name: tensor view into ctx}) without autograd; names follow mgacbam_ctx_layout_t.  A channels_last x runs the
+    channels-last kernels (y comes back channels_last); the ctx views are the same for both layouts."""
     lib = _lib.load()
     _check_level(x, mask, params, cfg)
     B, Cc, H, W = x.shape
-    xc = _aligned(x.detach())
+    nhwc = _is_nhwc(x)
+    xc = _ready_nhwc(x.detach()) if nhwc else _aligned(x.detach())
     m32 = None if mask is None else _aligned(mask.detach().reshape(B, 1, H, W).float())
     pc = [_aligned(p.detach()) for p in params]
     y = torch.empty_like(xc)
@@ -334,6 +363,10 @@ def forward_with_ctx(x, mask, params, cfg: BlockConfig, save_proj: bool = True):
     L.p = _params_struct(pc, cfg)
     L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[x.dtype]
     L.flags = _lib.FWD_SAVE_PROJ if (save_proj and mask is not None) else 0
+    ws = None
+    if nhwc:
+        ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, _lib.LAYOUT_NHWC), dtype=torch.uint8, device=x.device)
+        L.ws, L.ws_bytes, L.flags = ws.data_ptr(), ws.numel(), L.flags | _lib.LAYOUT_NHWC
     with torch.cuda.device(x.device):
         _lib.check(lib.mgacbam_forward(lv, 1, torch.cuda.current_stream(x.device).cuda_stream), "mgacbam_forward")
     return y, ctx_views(cbuf, B, Cc, H, W, cfg.hidden)

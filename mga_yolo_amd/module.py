@@ -7,6 +7,8 @@ list input, ``alpha`` property, ``extra_repr``, plain-tensor output (forward hoo
 state on the instance -- EMA deep-copies the module, U/utils/torch_utils.py:722).
 
 Device tensors run the hand-written HIP kernels through ``functional.mask_cbam`` (one library call forward, one backward).
+A ``channels_last`` feature (``model.to(memory_format=torch.channels_last)``) runs the channels-last kernels without a layout copy, and
+its output and input gradient come back ``channels_last``; any other layout takes the NCHW kernels.
 Host (CPU) tensors -- the 256x256 stride probe ``parse_model`` runs at build time (U/nn/tasks.py:413-429) and BASELINE
 config 0 (``device='cpu'``) -- run ``_host_forward``, a plain-PyTorch statement of the same mathematics; it is never
 used for a device tensor, and a device tensor with the library missing raises.

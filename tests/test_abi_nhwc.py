@@ -1,0 +1,144 @@
+"""CPU-side checks of the channels-last (MGACBAM_LAYOUT_NHWC) part of the C ABI (ABI 15) and of the Python layout decision.
+No kernel is launched here: every call below must fail its argument checks before anything touches a device."""
+import os
+import re
+
+import pytest
+import torch
+
+from conftest import ROOT
+
+HEADER = os.path.join(ROOT, "include", "mgacbam.h")
+
+
+def _header():
+    return open(HEADER).read()
+
+
+def test_layout_flag_matches_header_and_binding(built_lib):
+    from mga_yolo_amd import _lib
+    m = re.search(r"MGACBAM_LAYOUT_NHWC\s*=\s*(\d+)", _header())
+    assert m and int(m.group(1)) == _lib.LAYOUT_NHWC == 2
+    assert _lib.LAYOUT_NHWC & _lib.FWD_SAVE_PROJ == 0 and _lib.LAYOUT_NHWC & _lib.BWD_HAVE_PROJ == 0   # bit 0 keeps its meaning
+    assert int(re.search(r"#define MGACBAM_ABI_VERSION (\d+)", _header()).group(1)) == 15 == _lib.ABI_VERSION
+
+
+def test_forward_level_carries_the_workspace_last(built_lib):
+    from mga_yolo_amd import _lib
+    names = [f[0] for f in _lib.FwdLevel._fields_]
+    assert names[-3:] == ["flags", "ws", "ws_bytes"]
+    body = re.search(r"typedef struct mgacbam_fwd_level \{(.*?)\} mgacbam_fwd_level_t;", _header(), re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    assert re.search(r"void\s*\*\s*ws;\s*size_t\s+ws_bytes;\s*$", body.strip() + "\n", re.M)
+
+
+def test_size_queries_are_declared_bound_and_layout_aware(built_lib):
+    from mga_yolo_amd import _lib
+    lib = _lib.load()
+    for name in ("mgacbam_fwd_ws_bytes", "mgacbam_bwd_scratch_bytes_flags"):
+        assert name in _lib.SYMBOLS and re.search(r"\b" + name + r"\s*\(", _header())
+    for B, Cc, H, W, hid, k in [(2, 64, 16, 16, 4, 7), (32, 64, 80, 80, 4, 7), (1, 48, 17, 17, 3, 3), (3, 5, 7, 9, 1, 5), (2, 1024, 10, 10, 64, 7)]:
+        assert lib.mgacbam_fwd_ws_bytes(B, Cc, H, W, hid, 0) == 0
+        assert lib.mgacbam_fwd_ws_bytes(B, Cc, H, W, hid, _lib.FWD_SAVE_PROJ) == 0
+        ws = lib.mgacbam_fwd_ws_bytes(B, Cc, H, W, hid, _lib.LAYOUT_NHWC)
+        assert ws > 0 and ws % 16 == 0
+        assert ws >= B * (4 * Cc + 4) * 4                          # at least one chunk of partials per sample
+        assert lib.mgacbam_bwd_scratch_bytes_flags(B, Cc, H, W, hid, k, 0) == lib.mgacbam_bwd_scratch_bytes(B, Cc, H, W, hid, k)
+        assert lib.mgacbam_bwd_scratch_bytes_flags(B, Cc, H, W, hid, k, _lib.LAYOUT_NHWC) > 0
+        assert _lib.scratch_bytes(B, Cc, H, W, hid, k, _lib.LAYOUT_NHWC) == lib.mgacbam_bwd_scratch_bytes_flags(B, Cc, H, W, hid, k, _lib.LAYOUT_NHWC)
+        assert _lib.fwd_ws_bytes(B, Cc, H, W, hid, _lib.LAYOUT_NHWC) == ws and _lib.fwd_ws_bytes(B, Cc, H, W, hid, 0) == 0
+    assert lib.mgacbam_fwd_ws_bytes(0, 64, 8, 8, 4, _lib.LAYOUT_NHWC) == 0        # bad shape
+    assert lib.mgacbam_bwd_scratch_bytes_flags(2, 64, 8, 8, 4, 4, _lib.LAYOUT_NHWC) == 0   # even k
+
+
+def _fake(addr=0x10000):
+    return addr          # a non-NULL, 16-byte aligned "pointer": the calls below must fail before anything dereferences it
+
+
+def _levels(_lib, B, Cc, H, W, hid, k, dtype):
+    P = _lib.Params(*([_fake()] * 6), hid, k, 1, 1e-4, 1e-6)
+    fl = (_lib.FwdLevel * 1)()
+    F = fl[0]
+    F.x = F.mask = F.y = F.ctx = F.ws = _fake()
+    F.p, F.B, F.C, F.H, F.W, F.dtype, F.flags = P, B, Cc, H, W, dtype, _lib.LAYOUT_NHWC
+    F.ctx_bytes = _lib.ctx_bytes(B, Cc, H, W, hid)
+    F.ws_bytes = _lib.fwd_ws_bytes(B, Cc, H, W, hid, _lib.LAYOUT_NHWC)
+    bl = (_lib.BwdLevel * 1)()
+    Bw = bl[0]
+    for f in ("x", "mask", "gy", "ctx", "scratch", "gx", "gmask", "gw1", "gb1", "gw2", "gb2", "gwsa", "gbeta"):
+        setattr(Bw, f, _fake())
+    Bw.p, Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype, Bw.flags = P, B, Cc, H, W, dtype, _lib.LAYOUT_NHWC
+    Bw.ctx_bytes = _lib.ctx_bytes(B, Cc, H, W, hid)
+    Bw.scratch_bytes = _lib.scratch_bytes(B, Cc, H, W, hid, k, _lib.LAYOUT_NHWC)
+    return fl, bl
+
+
+@pytest.mark.parametrize("dtype", [0, 1, 2])
+def test_undersized_nhwc_work_buffers_are_an_error_not_a_launch(built_lib, dtype):
+    from mga_yolo_amd import _lib
+    lib = _lib.load()
+    B, Cc, H, W, hid, k = 2, 64, 16, 16, 4, 7
+    fl, bl = _levels(_lib, B, Cc, H, W, hid, k, dtype)
+    need_ws = fl[0].ws_bytes
+    fl[0].ws_bytes = 0
+    assert lib.mgacbam_forward(fl, 1, None) == _lib.E_SIZE
+    msg = lib.mgacbam_last_error().decode()
+    assert "ws" in msg and "holds 0 bytes" in msg
+    fl[0].ws_bytes = need_ws
+    fl[0].ws = None
+    assert lib.mgacbam_forward(fl, 1, None) == _lib.E_NULL
+    fl[0].ws = _fake()
+    fl[0].ctx_bytes -= 16
+    assert lib.mgacbam_forward(fl, 1, None) == _lib.E_SIZE and b"ctx" in lib.mgacbam_last_error()
+    bl[0].scratch_bytes = 16
+    assert lib.mgacbam_backward(bl, 1, None) == _lib.E_SIZE and b"scratch" in lib.mgacbam_last_error()
+    # the NCHW requirement is not the NHWC one: a scratch sized by the NCHW query for this shape is refused when it is smaller
+    nchw = lib.mgacbam_bwd_scratch_bytes(B, Cc, H, W, hid, k)
+    nhwc = _lib.scratch_bytes(B, Cc, H, W, hid, k, _lib.LAYOUT_NHWC)
+    if nchw < nhwc:
+        bl[0].scratch_bytes = nchw
+        assert lib.mgacbam_backward(bl, 1, None) == _lib.E_SIZE
+
+
+def test_misaligned_nhwc_features_are_refused(built_lib):
+    from mga_yolo_amd import _lib
+    lib = _lib.load()
+    fl, bl = _levels(_lib, 2, 64, 16, 16, 4, 7, _lib.F32)
+    fl[0].x = _fake() + 4                                          # fp32 with C % 4 == 0: 16-byte lanes
+    assert lib.mgacbam_forward(fl, 1, None) == _lib.E_ALIGN
+    fl[0].x = _fake()
+    fl[0].y = _fake() + 8
+    assert lib.mgacbam_forward(fl, 1, None) == _lib.E_ALIGN
+    for f in ("x", "gy", "gx"):
+        setattr(bl[0], f, _fake() + 4)
+        assert lib.mgacbam_backward(bl, 1, None) == _lib.E_ALIGN, f
+        setattr(bl[0], f, _fake())
+    fl2, _ = _levels(_lib, 2, 64, 16, 16, 4, 7, _lib.BF16)        # bf16 with C % 8 == 0: 16-byte lanes as well
+    fl2[0].x = _fake() + 8
+    assert lib.mgacbam_forward(fl2, 1, None) == _lib.E_ALIGN
+
+
+def test_ws_query_covers_every_element_type(built_lib):
+    """The queries take no element type: the answer must cover the largest requirement (fp32 and fp16 chunk differently)."""
+    from mga_yolo_amd import _lib
+    lib = _lib.load()
+    for Cc in (8, 64, 256, 512, 1024, 2048, 48, 5):
+        for dtype in (0, 1, 2):
+            fl, bl = _levels(_lib, 3, Cc, 9, 11, 4, 5, dtype)
+            fl[0].ctx_bytes -= 16                                  # stop at the ctx check, which follows the ws check
+            fl[0].ws_bytes = lib.mgacbam_fwd_ws_bytes(3, Cc, 9, 11, 4, _lib.LAYOUT_NHWC)
+            assert lib.mgacbam_forward(fl, 1, None) == _lib.E_SIZE and b"ctx" in lib.mgacbam_last_error(), (Cc, dtype)
+
+
+def test_layout_decision():
+    from mga_yolo_amd.functional import _is_nhwc
+    x = torch.randn(2, 8, 5, 6)
+    assert not _is_nhwc(x)                                                          # NCHW
+    assert _is_nhwc(x.to(memory_format=torch.channels_last))                        # channels_last
+    for shape in [(2, 1, 5, 6), (2, 8, 1, 1)]:                                      # ambiguous: both contiguities hold -> NCHW path
+        t = torch.randn(*shape).to(memory_format=torch.channels_last)
+        assert t.is_contiguous() and not _is_nhwc(t)
+    assert not _is_nhwc(x[:, :, :, ::2])                                            # arbitrary strides: NCHW path (copied)
+    assert not _is_nhwc(x.to(memory_format=torch.channels_last)[:, :4])
+    assert not _is_nhwc(x.permute(0, 1, 3, 2))
+    assert not _is_nhwc(torch.randn(8, 5, 6))
