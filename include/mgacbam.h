@@ -333,14 +333,14 @@ typedef struct mgahead_params {
 } mgahead_params_t;
 
 typedef struct mgahead_fwd_level {
-  const void* x;               /* (B,C,H,W) feature of `dtype`                                 */
+  const void* x;               /* (B,C,H,W) feature of `dtype` ((B,H,W,C) with MGAHEAD_LAYOUT_NHWC) */
   void* logits;                /* (B,1,H,W) mask logits of `dtype` (fp32 with MGAHEAD_LOGITS_F32) */
   void* ctx;                   /* mgahead_ctx_bytes(): z, batch statistics (kept for backward) */
   size_t ctx_bytes;            /* capacity of ctx (checked: MGACBAM_E_SIZE)                    */
   mgahead_params_t p;
   int32_t B, C, H, W;
   int32_t dtype;
-  int32_t flags;               /* MGAHEAD_LOGITS_F32                                           */
+  int32_t flags;               /* MGAHEAD_LOGITS_F32 | MGAHEAD_LAYOUT_NHWC                     */
 } mgahead_fwd_level_t;
 
 typedef struct mgahead_bwd_level {
@@ -352,7 +352,7 @@ typedef struct mgahead_bwd_level {
   void* scratch;               /* mgahead_bwd_scratch_bytes(), contents undefined              */
   size_t ctx_bytes;            /* capacities of ctx / scratch (checked: MGACBAM_E_SIZE)        */
   size_t scratch_bytes;
-  void* gx;                    /* (B,C,H,W) dL/dx of `dtype`                                   */
+  void* gx;                    /* (B,C,H,W) dL/dx of `dtype` ((B,H,W,C) with MGAHEAD_LAYOUT_NHWC) */
   float* gw1;                  /* parameter gradients, shapes of the parameters, OVERWRITTEN   */
   float* gbn_weight;
   float* gbn_bias;
@@ -367,12 +367,25 @@ typedef struct mgahead_bwd_level {
 } mgahead_bwd_level_t;
 enum {
   MGAHEAD_BWD_ACCUM_GX = 1,
-  MGAHEAD_LOGITS_F32 = 2       /* forward: logits, backward: g_logits are fp32 whatever `dtype` is -- half-precision features with the mask
+  MGAHEAD_LOGITS_F32 = 2,      /* forward: logits, backward: g_logits are fp32 whatever `dtype` is -- half-precision features with the mask
                                   logits handed to MaskCBAM (whose mask input is fp32) and to the loss without a conversion pass        */
+  MGAHEAD_LAYOUT_NHWC = 4      /* forward and backward (ABI 15): x and gx are dense (B,H,W,C) -- torch's channels_last -- instead of (B,C,H,W)
+                                  (with ACCUM_GX the call adds into a channels_last gx); logits, g_logits and g_logits2 stay (B,1,H,W), the
+                                  same memory in both layouts.  Combines with ACCUM_GX and LOGITS_F32.  z keeps its (B,hidden,H,W) layout in
+                                  the ctx, so only the 1x1-conv GEMM and its two backward products run kernels of their own (head_nhwc.cuh):
+                                  still 3 (4) launches forward and 5 backward; NHWC and NCHW levels of one call go to separate launches.
+                                  The ctx `part` and scratch `gwpart` regions follow the NHWC tiling: size ctx and scratch with
+                                  mgahead_ctx_bytes_flags / mgahead_bwd_scratch_bytes_flags (MGACBAM_E_SIZE otherwise).  x / gx must be
+                                  aligned to the element size times the lane width along C, the MaskCBAM NHWC rule: 8 for fp16 / bf16 with
+                                  C % 8 == 0, else 4 when C % 4 == 0, else 1 (MGACBAM_E_ALIGN).                                           */
 };
 
 size_t mgahead_ctx_bytes(int B, int C, int H, int W, int hidden);
 size_t mgahead_bwd_scratch_bytes(int B, int C, int H, int W, int hidden);
+/* Layout-aware size queries (ABI 15), `flags` = the level's flags: with MGAHEAD_LAYOUT_NHWC clear they return exactly mgahead_ctx_bytes /
+ * mgahead_bwd_scratch_bytes, with it set the NHWC requirement (any element type).  0 means a bad shape. */
+size_t mgahead_ctx_bytes_flags(int B, int C, int H, int W, int hidden, int flags);
+size_t mgahead_bwd_scratch_bytes_flags(int B, int C, int H, int W, int hidden, int flags);
 int mgahead_forward(const mgahead_fwd_level_t* levels, int n_levels, void* stream);     /* 3 launches for all levels at hidden <= 128 (GEMM, statistics, output); 4 when levels with hidden > 128 are present (their GEMM is a launch of its own) */
 int mgahead_backward(const mgahead_bwd_level_t* levels, int n_levels, void* stream);    /* 5 launches for all levels */
 

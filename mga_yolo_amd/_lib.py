@@ -107,6 +107,7 @@ class HeadBwdLevel(C.Structure):                 # mgahead_bwd_level_t
 
 
 HEAD_BWD_ACCUM_GX, HEAD_LOGITS_F32 = 1, 2
+HEAD_LAYOUT_NHWC = 4   # mask head level flag (forward and backward): x, gx are (B,H,W,C) -- torch's channels_last
 
 
 class PmgCfg(C.Structure):                       # mgapmg_cfg_t
@@ -137,6 +138,8 @@ SYMBOLS = {
     "mgaseg_backward": (C.c_int, [C.POINTER(SegLevel), C.c_int, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mgahead_ctx_bytes": (C.c_size_t, [C.c_int] * 5),
     "mgahead_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
+    "mgahead_ctx_bytes_flags": (C.c_size_t, [C.c_int] * 6),
+    "mgahead_bwd_scratch_bytes_flags": (C.c_size_t, [C.c_int] * 6),
     "mgahead_forward": (C.c_int, [C.POINTER(HeadFwdLevel), C.c_int, C.c_void_p]),
     "mgahead_backward": (C.c_int, [C.POINTER(HeadBwdLevel), C.c_int, C.c_void_p]),
     "mgakendall_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,6 @@
 // libmgacbam.so, C ABI (include/mgacbam.h): MGAMaskHead
 #include "host.cuh"
-#include "head.cuh"
+#include "head_nhwc.cuh"
 
 // ------------------------------------------------------------------------------------------------
 // MGAMaskHead
@@ -29,7 +29,7 @@ static void head_waves(int mtiles, int mtw, int K, int& pw, int& kw) {
   kw = K >= 128 ? rest : 1;
   pw = rest / kw;
 }
-static HeadTiling head_tiling(int B, int C, int H, int W, int hidden) {
+static HeadTiling head_tiling(int B, int C, int H, int W, int hidden, bool nhwc = false) {
   HeadTiling t;
   const int HW = H * W;
   t.vec = (HW % 4 == 0) ? 4 : 1;
@@ -65,11 +65,26 @@ static HeadTiling head_tiling(int B, int C, int H, int W, int hidden) {
     const long long cap = std::max(1ll, std::min(512ll, (4ll << 20) / per_share));
     t.nshare = static_cast<int>(std::max(1ll, std::min(cap, chunks64 / kHeadGwDiv)));   // (measured: 2-4 chunks per workgroup and 512-2048 shares all within 1 %; 6+ chunks, one resident round: +12 %)
   }
+  if (nhwc) {
+    // MGAHEAD_LAYOUT_NHWC (head_nhwc.cuh): 64 pixels per wave along N, no K split; dW1 always takes the LDS-staged form, shares as k_head_bwd_gw2's
+    auto waves_px = [](int mtiles, int mtw) { int mw = std::min(4, (mtiles + mtw - 1) / mtw); if (mw == 3) mw = 4; return 4 / mw; };
+    t.fw_kw = t.gx_kw = 1;
+    t.tile_px = waves_px(t.hidp / 16, t.fw_mtw) * kHeadNhwcPx;
+    t.tps = (HW + t.tile_px - 1) / t.tile_px;
+    t.nwg = B * t.tps;
+    t.gx_tile_px = waves_px(t.cp / 16, t.gx_mtw) * kHeadNhwcPx;
+    t.gx_tps = (HW + t.gx_tile_px - 1) / t.gx_tile_px;
+    constexpr int kHeadGwDiv = 5;
+    const long long chunks64 = static_cast<long long>(B) * ((HW + kHeadGwPx - 1) / kHeadGwPx);
+    const long long cap = std::max(1ll, std::min(512ll, (4ll << 20) / per_share));
+    t.nshare = static_cast<int>(std::max(1ll, std::min(cap, chunks64 / kHeadGwDiv)));
+    t.gw2 = 0;
+  }
   return t;
 }
 struct HeadCtxLayout { size_t z, mean, rstd, par, part, total; };
-static HeadCtxLayout head_ctx_layout(int B, int C, int H, int W, int hidden) {
-  const HeadTiling t = head_tiling(B, C, H, W, hidden);
+static HeadCtxLayout head_ctx_layout(int B, int C, int H, int W, int hidden, bool nhwc = false) {
+  const HeadTiling t = head_tiling(B, C, H, W, hidden, nhwc);
   HeadCtxLayout L;
   size_t o = 0;
   auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
@@ -81,8 +96,8 @@ static HeadCtxLayout head_ctx_layout(int B, int C, int H, int W, int hidden) {
   return L;
 }
 struct HeadScratchLayout { size_t ga, part1, kst, gwpart, total; };
-static HeadScratchLayout head_scratch_layout(int B, int C, int H, int W, int hidden) {
-  const HeadTiling t = head_tiling(B, C, H, W, hidden);
+static HeadScratchLayout head_scratch_layout(int B, int C, int H, int W, int hidden, bool nhwc = false) {
+  const HeadTiling t = head_tiling(B, C, H, W, hidden, nhwc);
   HeadScratchLayout L;
   size_t o = 0;
   auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
@@ -101,18 +116,26 @@ extern "C" size_t mgahead_bwd_scratch_bytes(int B, int C, int H, int W, int hidd
   if (head_check_shape(B, C, H, W, hidden)) return 0;
   return head_scratch_layout(B, C, H, W, hidden).total;
 }
-static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, int dtype, void* ctx, HeadArgs& A, Sig& sig) {
+extern "C" size_t mgahead_ctx_bytes_flags(int B, int C, int H, int W, int hidden, int flags) {
+  if (head_check_shape(B, C, H, W, hidden)) return 0;
+  return head_ctx_layout(B, C, H, W, hidden, (flags & MGAHEAD_LAYOUT_NHWC) != 0).total;
+}
+extern "C" size_t mgahead_bwd_scratch_bytes_flags(int B, int C, int H, int W, int hidden, int flags) {
+  if (head_check_shape(B, C, H, W, hidden)) return 0;
+  return head_scratch_layout(B, C, H, W, hidden, (flags & MGAHEAD_LAYOUT_NHWC) != 0).total;
+}
+static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, int dtype, bool nhwc, void* ctx, HeadArgs& A, Sig& sig) {
   if (!P.w1 || !P.bn_weight || !P.bn_bias || !P.running_mean || !P.running_var || !P.wh || !P.bh)
     return fail(MGACBAM_E_NULL, "mask head: NULL parameter pointer");
   if (int e = head_check_shape(B, C, H, W, P.hidden)) return e;
   if (dtype < MGACBAM_F32 || dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "mask head: dtype %d", dtype);
   if (!(P.eps > 0.f) || !(P.momentum >= 0.f && P.momentum <= 1.f)) return fail(MGACBAM_E_SHAPE, "mask head: eps=%g momentum=%g", P.eps, P.momentum);
-  const HeadTiling t = head_tiling(B, C, H, W, P.hidden);
+  const HeadTiling t = head_tiling(B, C, H, W, P.hidden, nhwc);
   memset(&A, 0, sizeof(A));
   A.p = HeadPtrs{P.w1, P.bn_weight, P.bn_bias, P.running_mean, P.running_var, reinterpret_cast<long long*>(P.num_batches_tracked), P.wh, P.bh};
   A.g.B = B; A.g.C = C; A.g.hid = P.hidden; A.g.H = H; A.g.W = W; A.g.HW = H * W; A.g.hidp = t.hidp; A.g.cp = t.cp;
   A.g.eps = P.eps; A.g.momentum = P.momentum; A.g.training = P.training ? 1 : 0;
-  const HeadCtxLayout L = head_ctx_layout(B, C, H, W, P.hidden);
+  const HeadCtxLayout L = head_ctx_layout(B, C, H, W, P.hidden, nhwc);
   char* cp = static_cast<char*>(ctx);
   A.c = HeadCtx{reinterpret_cast<float*>(cp + L.z), reinterpret_cast<float*>(cp + L.mean), reinterpret_cast<float*>(cp + L.rstd),
                 reinterpret_cast<float*>(cp + L.par), reinterpret_cast<float*>(cp + L.part)};
@@ -121,11 +144,17 @@ static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, in
   A.trace = knobs().trace; A.trace_base = 0;
   A.nwg_out = t.nwg_out; A.out_ppt = t.out_ppt; A.out_px = t.out_px; A.out_per = t.out_per; A.nwg1 = t.nwg1; A.act_ppt = t.act_ppt; A.act_hl_max = t.act_hl; A.ncb = t.ncb; A.nshare = t.nshare; A.gw2 = t.gw2;
   sig = Sig{dtype, t.vec, 0, 0, 0, 0};
+  if (nhwc) { sig.nhwc = 1; sig.cvec = C % 4 == 0 ? 4 : 1; }
   return 0;
 }
 static size_t head_gemm_smem(const HeadArgs* lv, int n) {
   size_t m = 0;
   for (int l = 0; l < n; ++l) m = std::max(m, (static_cast<size_t>(kHeadLdsX) + 8 * lv[l].g.hidp) * sizeof(float));
+  return m;
+}
+static int max_hidp(const HeadArgs* lv, int n) {
+  int m = 0;
+  for (int l = 0; l < n; ++l) m = std::max(m, lv[l].g.hidp);
   return m;
 }
 template <typename Fn>
@@ -155,6 +184,16 @@ static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t s
       if (!Gm.n) continue;
       Gm.start[Gm.n] = grid;
       for (int l = 0; l < Gm.n; ++l) Gm.lv[l].trace_base = pass * 8192;
+      if (sig.nhwc) {                                             // channels-last features: head_nhwc.cuh (the level's MTW is its own fw_mtw)
+        const size_t nsmem = static_cast<size_t>(8) * max_hidp(lv, n) * sizeof(float);
+#define CALL_HN3(Tt, Cv) { if (mtw <= 2) { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 2>), grid, nsmem, st, Gm); } else { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 4>), grid, nsmem, st, Gm); } }
+#define CALL_HN(Tt) { if (sig.cvec == 4) { CALL_HN3(Tt, 4); } else { CALL_HN3(Tt, 1); } }
+        if (sig.dtype == MGACBAM_F32) { CALL_HN(float); } else if (sig.dtype == MGACBAM_F16) { CALL_HN(__half); } else { CALL_HN(bf16_t); }
+#undef CALL_HN
+#undef CALL_HN3
+        if (int e = launch_status("k_head_gemm_nhwc")) return e;
+        continue;
+      }
       for (int l = 0; l < Gm.n; ++l) {                            // the wave arrangement follows the template the level runs under
         int pw;
         head_waves(Gm.lv[l].g.hidp / 16, mtw, Gm.lv[l].g.C, pw, Gm.lv[l].fw_kw);
@@ -197,9 +236,10 @@ extern "C" int mgahead_forward(const mgahead_fwd_level_t* levels, int n_levels, 
   for (int l = 0; l < n_levels; ++l) {
     const mgahead_fwd_level_t& L = levels[l];
     if (!L.x || !L.logits || !L.ctx) return fail(MGACBAM_E_NULL, "mask head forward: x / logits / ctx is NULL");
-    if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, L.ctx, args[l], sigs[l])) return e;
-    if (int e = check_capacity("mask head forward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden).total, L.ctx_bytes)) return e;
-    const size_t need = sigs[l].vec * elem_size(L.dtype);
+    const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
+    if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, nhwc, L.ctx, args[l], sigs[l])) return e;
+    if (int e = check_capacity("mask head forward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc).total, L.ctx_bytes)) return e;
+    const size_t need = (nhwc ? nhwc_vec(L.C, L.dtype) : sigs[l].vec) * elem_size(L.dtype);
     if (!aligned_to(L.x, need) || !aligned_to(L.ctx, 16)) return fail(MGACBAM_E_ALIGN, "mask head forward: x must be %zu-byte aligned, ctx 16-byte", need);
     args[l].x = L.x; args[l].logits = L.logits;
     sigs[l].lf32 = (L.flags & MGAHEAD_LOGITS_F32) ? 1 : 0;
@@ -231,6 +271,25 @@ static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t 
     LAUNCH(k_head_bwd_fin, grid, 0, st, G);
     if (int e = launch_status("k_head_bwd_fin")) return e;
   }
+  if (sig.nhwc) {                                                 // channels-last features: head_nhwc.cuh
+    const size_t hp = static_cast<size_t>(max_hidp(lv, n));
+    {
+      const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
+      const size_t smem = 5 * hp * sizeof(float);
+#define CALL_HX(Tt) { if (sig.cvec == 4) { LAUNCH((k_head_gx_nhwc<Tt, 4>), grid, smem, st, G); } else { LAUNCH((k_head_gx_nhwc<Tt, 1>), grid, smem, st, G); } }
+      if (sig.dtype == MGACBAM_F32) { CALL_HX(float); } else if (sig.dtype == MGACBAM_F16) { CALL_HX(__half); } else { CALL_HX(bf16_t); }
+#undef CALL_HX
+      if (int e = launch_status("k_head_gx_nhwc")) return e;
+    }
+    {
+      const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.ncb * a.nshare; });
+      const size_t smem = (5 * hp + 2 * static_cast<size_t>(kHeadGwPx) * kHeadGwPitch) * sizeof(float);
+#define CALL_HW(Tt) { if (sig.cvec == 4) { LAUNCH((k_head_gw_nhwc<Tt, 4>), grid, smem, st, G); } else { LAUNCH((k_head_gw_nhwc<Tt, 1>), grid, smem, st, G); } }
+      if (sig.dtype == MGACBAM_F32) { CALL_HW(float); } else if (sig.dtype == MGACBAM_F16) { CALL_HW(__half); } else { CALL_HW(bf16_t); }
+#undef CALL_HW
+      if (int e = launch_status("k_head_gw_nhwc")) return e;
+    }
+  } else {
   {
     for (int l = 0; l < n; ++l) G.lv[l].trace_base = 16384;
     const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
@@ -273,6 +332,7 @@ static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t 
       if (int e = launch_status("k_head_bwd_gw")) return e;
     }
   }
+  }
   {
     const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return (a.g.hid * a.g.C + kHeadGwfOut - 1) / kHeadGwfOut; });
     LAUNCH(k_head_bwd_gwf, grid, 0, st, G);
@@ -289,8 +349,9 @@ extern "C" int mgahead_backward(const mgahead_bwd_level_t* levels, int n_levels,
     const mgahead_bwd_level_t& L = levels[l];
     if (!L.x || !L.g_logits || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "mask head backward: x / g_logits / ctx / scratch / gx is NULL");
     if (!L.gw1 || !L.gbn_weight || !L.gbn_bias || !L.gwh || !L.gbh) return fail(MGACBAM_E_NULL, "mask head backward: NULL parameter-gradient pointer");
-    if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, const_cast<void*>(L.ctx), args[l], sigs[l])) return e;
-    const size_t need = sigs[l].vec * elem_size(L.dtype);
+    const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
+    if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, nhwc, const_cast<void*>(L.ctx), args[l], sigs[l])) return e;
+    const size_t need = (nhwc ? nhwc_vec(L.C, L.dtype) : sigs[l].vec) * elem_size(L.dtype);
     if (!aligned_to(L.x, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) || !aligned_to(L.scratch, 16))
       return fail(MGACBAM_E_ALIGN, "mask head backward: x/gx must be %zu-byte aligned, ctx/scratch 16-byte", need);
     HeadArgs& A = args[l];
@@ -299,8 +360,8 @@ extern "C" int mgahead_backward(const mgahead_bwd_level_t* levels, int n_levels,
     A.accum_gx = (L.flags & MGAHEAD_BWD_ACCUM_GX) ? 1 : 0;
     sigs[l].lf32 = (L.flags & MGAHEAD_LOGITS_F32) ? 1 : 0;
     A.gl2 = L.g_logits2;
-    const HeadScratchLayout SL = head_scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden);
-    if (int e = check_capacity("mask head backward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden).total, L.ctx_bytes)) return e;
+    const HeadScratchLayout SL = head_scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc);
+    if (int e = check_capacity("mask head backward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc).total, L.ctx_bytes)) return e;
     if (int e = check_capacity("mask head backward", "scratch", SL.total, L.scratch_bytes)) return e;
     char* sp = static_cast<char*>(L.scratch);
     A.s = HeadScratch{reinterpret_cast<float*>(sp + SL.ga), reinterpret_cast<float*>(sp + SL.part1), reinterpret_cast<float*>(sp + SL.kst),

@@ -561,7 +561,8 @@ def prob_mask_gate(p: torch.Tensor, u1: torch.Tensor, u2: torch.Tensor, tau: flo
 
 
 # ---------------------------------------------------------------------------------------------------------
-# MGAMaskHead: Conv1x1 -> BatchNorm2d -> SiLU -> Conv3x3 as 3 launches forward, 5 backward (csrc/head.cuh)
+# MGAMaskHead: Conv1x1 -> BatchNorm2d -> SiLU -> Conv3x3 as 3 launches forward, 5 backward (csrc/head.cuh); a channels_last
+# feature takes the NHWC forms of the GEMM kernels (csrc/head_nhwc.cuh) without a copy, and its gx comes back channels_last
 # ---------------------------------------------------------------------------------------------------------
 def _head_params(w1, gamma, beta, rmean, rvar, nbt, wh, bh, hidden, eps, momentum, training) -> "_lib.HeadParams":
     return _lib.HeadParams(w1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(),
@@ -593,20 +594,22 @@ class _HeadFn(torch.autograd.Function):
                 raise ValueError(f"mask_head: parameter shapes do not match C={Cc}, hidden={hid} (out_channels must be 1)")
             if training and B * H * W == 1:                     # torch.nn.functional.batch_norm refuses this too (no variance from one value)
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
-            xc = _ready(x)
+            nhwc = _is_nhwc(x)                                  # the layout decides the GEMM kernels, per level (MaskCBAM's rule)
+            fl = _lib.HEAD_LAYOUT_NHWC if nhwc else 0
+            xc = _ready_nhwc(x) if nhwc else _ready(x)
             pc = [_ready(t.float() if t.dtype != torch.float32 else t) for t in (w1, gamma, beta, wh, bh)]
             for t in (rmean, rvar):
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
                     raise ValueError("mask_head: running statistics must be contiguous fp32 tensors on the feature's device")
             logits = torch.empty(B, 1, H, W, dtype=x.dtype, device=dev)
-            cbuf = torch.empty(lib.mgahead_ctx_bytes(B, Cc, H, W, hid), dtype=torch.uint8, device=dev)
+            cbuf = torch.empty(lib.mgahead_ctx_bytes_flags(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
             L = levels[l]
             L.x, L.logits, L.ctx, L.ctx_bytes = xc.data_ptr(), logits.data_ptr(), cbuf.data_ptr(), cbuf.numel()
             L.p = _head_params(*pc[:3], rmean, rvar, nbt, *pc[3:], hid, float(eps), float(momentum), training)
-            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[x.dtype], 0
+            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[x.dtype], fl
             keep += [xc, cbuf, *pc, rmean, rvar]
             outs.append(logits)
-            meta.append((hid, float(eps), float(momentum), bool(training), tuple(w1.shape)))
+            meta.append((hid, float(eps), float(momentum), bool(training), tuple(w1.shape), fl))
         with torch.cuda.device(dev):
             _lib.check(lib.mgahead_forward(levels, n, torch.cuda.current_stream(dev).cuda_stream), "mgahead_forward")
         ctx.save_for_backward(*keep)
@@ -624,19 +627,19 @@ class _HeadFn(torch.autograd.Function):
         dev = saved[0].device
         for l in range(n):
             xc, cbuf, w1, gamma, beta, wh, bh, rmean, rvar = saved[9 * l:9 * l + 9]
-            hid, eps, momentum, training, w1_shape = ctx.meta[l]
+            hid, eps, momentum, training, w1_shape, fl = ctx.meta[l]
             B, Cc, H, W = xc.shape
             gl = gls[l]
             gl = torch.zeros(B, 1, H, W, dtype=xc.dtype, device=dev) if gl is None else _aligned(gl.to(xc.dtype))
-            gx = torch.empty_like(xc)
+            gx = torch.empty_like(xc, memory_format=torch.channels_last if fl else torch.contiguous_format)
             pg = [torch.empty_like(t) for t in (w1, gamma, beta, wh, bh)]
-            scratch = torch.empty(lib.mgahead_bwd_scratch_bytes(B, Cc, H, W, hid), dtype=torch.uint8, device=dev)
+            scratch = torch.empty(lib.mgahead_bwd_scratch_bytes_flags(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
             L = levels[l]
             L.x, L.g_logits, L.g_logits2, L.ctx, L.scratch, L.gx = xc.data_ptr(), gl.data_ptr(), None, cbuf.data_ptr(), scratch.data_ptr(), gx.data_ptr()
             L.ctx_bytes, L.scratch_bytes = cbuf.numel(), scratch.numel()
             L.gw1, L.gbn_weight, L.gbn_bias, L.gwh, L.gbh = (t.data_ptr() for t in pg)
             L.p = _head_params(w1, gamma, beta, rmean, rvar, None, wh, bh, hid, eps, momentum, training)
-            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[xc.dtype], 0
+            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[xc.dtype], fl
             hold += [gl, scratch]
             pg[0] = pg[0].view(w1_shape)
             grads += [gx, *pg]
@@ -655,7 +658,8 @@ def mask_head(x: torch.Tensor, w1, bn_weight, bn_bias, running_mean, running_var
 
 def mask_head_pyramid(levels):
     """levels: [(x, w1, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, wh, bh, eps, momentum, training), ...]
-    -> tuple of logits; ONE library call each way for all levels (the three heads read different features: they are independent)."""
+    -> tuple of logits; ONE library call each way for all levels (the three heads read different features: they are independent).
+    Levels may mix layouts: each channels_last feature runs the NHWC kernels, the others the NCHW ones."""
     state, flat = [], []
     for x, w1, g_, b_, rm, rv, nbt, wh, bh, eps, mom, tr in levels:
         state.append((rm, rv, nbt, eps, mom, tr))

@@ -303,8 +303,9 @@ class MGAMaskHead(nn.Module):
     ``head.{weight,bias}``), same initialisation order (kaiming_normal fan_out for the convs, BatchNorm ones / zeros), ``cfg`` and
     ``extra_repr``.  The containers hold the parameters; for device tensors in the configuration every reference YAML uses
     (norm="bn", act=SiLU, dropout=0, out_channels=1) the math runs in the HIP kernels (the 1x1 conv and its backward products on the
-    matrix cores), BatchNorm's running statistics updated in place as torch does.  Host tensors and other constructor variants run
-    the containers' own torch ops."""
+    matrix cores), BatchNorm's running statistics updated in place as torch does.  A ``channels_last`` feature runs the channels-last
+    forms of the 1x1-conv kernels without a layout copy, and its input gradient comes back ``channels_last``; the logits are (B,1,H,W)
+    in either layout.  Host tensors and other constructor variants run the containers' own torch ops."""
 
     def __init__(self, in_channels: int, hidden_channels: int, out_channels: int = 1, norm: Optional[str] = "bn",
                  act: type = nn.SiLU, dropout: float = 0.0) -> None:
