@@ -2,7 +2,11 @@
 their own -- exercises the launch-group partition (levels with different compile-time signatures go to different launches), the
 longest-first level ordering and the XCD-aligned grids.  Every level is checked against the oracle.  After each grouped call a random
 subset of its levels runs again as single-level calls (mask_cbam) with fresh inputs on the same pooled ctxs: the call composition
-changes under one ctx (batches up to 32 make the launch group's channels per thread differ between the two forms).
+changes under one ctx (batches up to 32 make the launch group's channels per thread differ between the two forms).  Every call, and
+every single-level re-run, runs once more with a layout drawn per level (NCHW or channels_last, at least one channels_last), against the
+same oracle results: mixed-layout launch groups, and pooled ctxs that see both layouts.  Some calls run again with a level of the
+channels-last tiling's larger shapes added (several tiles per chunk, scalar lanes with C > 64).  What those runs draw comes from a
+second generator seeded by the call index: the NCHW calls are those of the original stream.
     python tests/fuzz/fuzz_pyramid.py [n_calls] [seed]"""
 import os, random, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,9 +25,16 @@ ties = 0            # samples with a channel arg-max near-tie (their gy is zeroe
 tie_levels = 0      # levels with at least one such sample
 
 
-def run_call(it, spec, seed0=7000, tag=""):
-    global bad, ties, tie_levels
-    lv, ref = [], []
+CL = torch.channels_last
+# channels-last level shapes past the pool's: more than 64 tiles per sample (rp >= 2, ragged last chunk), scalar lanes with C > 64
+CL_EXTRA = [(2, 130, 48, 47), (1, 16, 190, 190), (2, 256, 40, 52), (1, 72, 140, 120), (3, 130, 23, 17), (1, 68, 101, 99)]
+
+
+def run_call(it, spec, seed0=7000, tag="", layouts=(None,)):
+    """Oracle once per level of spec, then the device call once per entry of layouts (None: every level NCHW, else a memory format per
+    level)."""
+    global ties, tie_levels
+    ref = []
     for l, (B, C, H, W, k, kind, dt, mask_grad) in enumerate(spec):
         x, mask, gy = synth(B, C, H, W, seed=seed0 + 10 * it + l, mask_kind=kind)
         x, gy = x.to(dt).float(), gy.to(dt).float()
@@ -39,15 +50,27 @@ def run_call(it, spec, seed0=7000, tag=""):
             ties += int(tied.sum())
             tie_levels += int(bool(tied.any()))
         g_o = O.backward(gy, x, mask, p, O.Config(), c)
-        xd = x.cuda().to(dt).requires_grad_(True)
+        ref.append((y_o, g_o, gy, dt, (B, C, H, W, k, kind), (x, mask, p, mask_grad)))
+    for fmts in layouts:
+        device_call(it, ref, tag if fmts is None else tag + " layouts " + "".join("C" if f is CL else "N" for f in fmts),
+                    fmts or [torch.contiguous_format] * len(ref))
+
+
+def device_call(it, ref, tag, fmts):
+    global bad
+    lv = []
+    for (y_o, g_o, gy, dt, (B, C, H, W, k, kind), (x, mask, p, mask_grad)), fmt in zip(ref, fmts):
+        xd = x.cuda().to(dt).to(memory_format=fmt).requires_grad_(True)
         md = None if mask is None else mask.cuda().requires_grad_(mask_grad)
         ps = [t.cuda().requires_grad_(True) for t in (p.w1, p.b1, p.w2, p.b2, p.wsa, p.beta)]
         lv.append((xd, md, ps, F.BlockConfig(hidden=p.w1.shape[0], k=k)))
-        ref.append((y_o, g_o, gy, dt, (B, C, H, W, k, kind)))
     try:
         ys = F.mask_cbam_pyramid(lv) if len(lv) > 1 else (F.mask_cbam(lv[0][0], lv[0][1], *lv[0][2], lv[0][3]),)
-        torch.autograd.backward(list(ys), [r[2].cuda().to(r[3]) for r in ref])
-        for l, ((xd, md, ps, _), (y_o, g_o, gy, dt, desc)) in enumerate(zip(lv, ref)):
+        torch.autograd.backward(list(ys), [r[2].cuda().to(r[3]).to(memory_format=f) for r, f in zip(ref, fmts)])
+        for l, ((xd, md, ps, _), (y_o, g_o, gy, dt, desc, _), fmt) in enumerate(zip(lv, ref, fmts)):
+            if fmt is CL and desc[1] > 1 and desc[2] * desc[3] > 1 and not (ys[l].is_contiguous(memory_format=CL) and xd.grad.is_contiguous(memory_format=CL)):
+                bad += 1
+                print(f"FAIL call {it}{tag} level {l} {desc} {dt}: y / gx came back in another layout", flush=True)
             tol = {torch.float32: 1e-4, torch.float16: 4e-3, torch.bfloat16: 3e-2}[dt]
             floor = 1e-7 * float(gy.norm() * xd.detach().float().norm().cpu())   # absolute: fp32 rounding of a cancelling sum's terms
             checks = dict(y=(ys[l].float(), y_o), gx=(xd.grad.float(), g_o["gx"]), gw1=(ps[0].grad, g_o["gw1"]), gwsa=(ps[4].grad, g_o["gwsa"]),
@@ -68,9 +91,16 @@ def run_call(it, spec, seed0=7000, tag=""):
         print(f"ERROR call {it}{tag}: {[r[4] for r in ref]}: {type(ex).__name__}: {ex}", flush=True)
 
 
+def draw_layouts(rng2, nl):
+    fmts = [rng2.choice([CL, torch.contiguous_format]) for _ in range(nl)]
+    fmts[rng2.randrange(nl)] = CL
+    return fmts
+
+
 BUDGET = 16 << 20   # feature elements per call: the oracle runs on the CPU
 
 for it in range(n):
+    rng2 = random.Random(1_000_003 * (it + 1))
     nl = rng.randint(2, 5)
     spec = []
     for l in range(nl):
@@ -87,10 +117,20 @@ for it in range(n):
     alone = [l for l in range(nl) if rng.random() < 0.5]                    # levels that run again on their own after the grouped call
     if only and it not in only:
         continue
+    mixed = draw_layouts(rng2, nl)
+    alone_fmt = {l: draw_layouts(rng2, 1) for l in alone}
+    extra = None
+    if rng2.random() < 0.25:                      # + a level of the channels-last tiling's larger shapes, after the call's first levels
+        B, C, H, W = rng2.choice(CL_EXTRA)
+        extra = spec[:rng2.randint(1, nl)] + [(B, C, H, W, rng2.choice([7, 3, 5, 9]), rng2.choice(["randn", "sparse", "none"]),
+                                                rng2.choice([torch.float32, torch.float16, torch.bfloat16]), True)]
+        extra = (extra, draw_layouts(rng2, len(extra)))
     for _ in range(repeat):
-        run_call(it, spec)
+        run_call(it, spec, layouts=(None, mixed))
         for l in alone:
-            run_call(it, [spec[l]], seed0=1000000 * (l + 1), tag=f" (level {l} alone)")
+            run_call(it, [spec[l]], seed0=1000000 * (l + 1), tag=f" (level {l} alone)", layouts=(None, alone_fmt[l]))
+        if extra is not None:
+            run_call(it, extra[0], tag=" (+ a larger level)", layouts=(extra[1],))
     if only:
         print(f"call {it}: {[(s_[:6], str(s_[6]).replace('torch.', ''), s_[7]) for s_ in spec]}", flush=True)
 print(f"pyramid fuzz: {n} calls, {bad} failures ({ties} samples in {tie_levels} levels with a channel arg-max near-tie: gy zeroed there, "

@@ -142,3 +142,58 @@ def test_layout_decision():
     assert not _is_nhwc(x.to(memory_format=torch.channels_last)[:, :4])
     assert not _is_nhwc(x.permute(0, 1, 3, 2))
     assert not _is_nhwc(torch.randn(8, 5, 6))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# coverage of tests/test_gpu_channels_last_edges.py: its rows are checked against a copy of host.cuh's nhwc_vec / nhwc_geo, and that copy
+# against the library's own size query, so a change of the tiling fails here instead of silently thinning what the GPU rows reach
+# ---------------------------------------------------------------------------------------------------------------------------
+def _nhwc_vec(C, dtype):
+    return 8 if (dtype != "f32" and C % 8 == 0) else (4 if C % 4 == 0 else 1)
+
+
+def _nhwc_geo(C, H, W, vec):
+    ng = -(-C // vec)
+    cs = max(4, min(1 << (ng - 1).bit_length(), 64))
+    ch = (256 // cs) * (4 if vec == 8 else 8)
+    ntile = -(-(H * W) // ch)
+    rp = -(-ntile // 64)
+    nchunk = -(-ntile // rp)
+    return dict(vec=vec, ng=ng, cs=cs, nj=-(-ng // cs), ch=ch, ntile=ntile, rp=rp, nchunk=nchunk, ragged=ntile % rp != 0,
+                ncb=-(-C // 64), fold_partial=C > 64 and C % 64 != 0)
+
+
+def test_channels_last_edge_rows_reach_every_tiling_branch(built_lib):
+    from mga_yolo_amd import _lib
+    from test_gpu_channels_last_edges import EDGE_ROWS
+    lib = _lib.load()
+    rows = []
+    for name, dt, B, C, H, W, k, kind, mask3d, mask_grad in EDGE_ROWS:
+        nchunk = max(_nhwc_geo(C, H, W, _nhwc_vec(C, d))["nchunk"] for d in ("f32", "f16"))
+        assert lib.mgacbam_fwd_ws_bytes(B, C, H, W, 4, _lib.LAYOUT_NHWC) == B * nchunk * (4 * C + 4) * 4, name
+        rows.append(dict(_nhwc_geo(C, H, W, _nhwc_vec(C, dt)), name=name, dt=dt, B=B, C=C, H=H, W=W, k=k, kind=kind, mask3d=mask3d,
+                         mask_grad=mask_grad))
+    branches = {
+        "vec 1, nj 3, partial fold block": lambda r: r["vec"] == 1 and r["nj"] >= 3 and r["fold_partial"],
+        "vec 1, rp 2, ragged": lambda r: r["vec"] == 1 and r["rp"] >= 2 and r["ragged"],
+        "vec 4, cs 4, rp 2, ragged": lambda r: r["vec"] == 4 and r["cs"] == 4 and r["rp"] >= 2 and r["ragged"],
+        "vec 4, cs 64, rp 2, ragged": lambda r: r["vec"] == 4 and r["cs"] == 64 and r["rp"] >= 2 and r["ragged"],
+        "vec 4 in half precision, nj 2": lambda r: r["vec"] == 4 and r["dt"] != "f32" and r["nj"] >= 2,
+        "vec 8, nj 2, partial fold block": lambda r: r["vec"] == 8 and r["nj"] >= 2 and r["fold_partial"],
+        "vec 8, rp 5, ragged": lambda r: r["vec"] == 8 and r["rp"] >= 5 and r["ragged"],
+        "vec 1 in half precision": lambda r: r["vec"] == 1 and r["dt"] != "f32",
+        "W = 1": lambda r: r["W"] == 1,
+        "a tile spans many image rows": lambda r: r["cs"] == 4 and r["W"] == 3 and r["ch"] // r["W"] >= 100 and r["ntile"] >= 2,
+        "a tile inside one image row": lambda r: r["W"] > r["ch"],
+        "fp16": lambda r: r["dt"] == "f16",
+        "bf16": lambda r: r["dt"] == "bf16",
+        "3-D mask": lambda r: r["mask3d"],
+        "mask without grad": lambda r: r["kind"] != "none" and not r["mask_grad"],
+        "raw-probability mask": lambda r: r["kind"] == "prob",
+        "B = 1": lambda r: r["B"] == 1,
+        "B > 1, not a multiple of 8": lambda r: r["B"] > 1 and r["B"] % 8 != 0,
+    }
+    missed = [b for b, hit in branches.items() if not any(hit(r) for r in rows)]
+    assert not missed, missed
+    assert {1, 3, 5, 9, 15} <= {r["k"] for r in rows}
+    assert {"randn", "sparse", "none", "tiny", "all_negative", "prob", "mixed"} <= {r["kind"] for r in rows}

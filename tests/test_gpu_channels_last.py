@@ -5,7 +5,8 @@ import torch
 
 from conftest import checksum, elem_err, golden_case_names, load_golden, rel_err, synth
 from oracle import maskcbam_oracle as O
-from test_gpu_parity import CONFIG_LEVELS, GRADS, TOL, _cfg, _params_dev
+from test_gpu_parity import (CONFIG5_SHAPES, CONFIG_LEVELS, FULL_SIZE_SHAPES, FUZZER_REGRESSIONS, GENERIC_KS, GRADS, TOL, _cfg,
+                              _params_dev)
 
 pytestmark = pytest.mark.gpu
 CL = torch.channels_last
@@ -299,3 +300,106 @@ def test_amp_channels_last_model_matches_nchw(F):
         assert rel_err(g1[n], g0[n]) < 4 * tol, n
     for n in p0:
         assert rel_err(p1[n], p0[n]) < tol, n
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# channels_last counterparts of test_gpu_parity's oracle tests: the same shapes, inputs and bars, features channels_last.  The
+# full-size rows (1, 256, 160, 160), (8, 512, 80, 80) and (32, 128, 80, 80) have several tiles per chunk (nhwc_geo's rp >= 2) and a
+# ragged last chunk: element-wise checks of that tiling.  test_gpu_channels_last_edges.py holds the geometry-corner matrix.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _run_cl(F, x, mask, gy, p, k=7, use_sig=True, dtype=torch.float32):
+    """x / gy channels_last on the device -> (y, grads); asserts y and gx come back channels_last (ambiguous layouts excepted)."""
+    xd = x.cuda().to(dtype).to(memory_format=CL).requires_grad_(True)
+    md = None if mask is None else mask.cuda().requires_grad_(True)
+    ps = [t.cuda().requires_grad_(True) for t in (p.w1, p.b1, p.w2, p.b2, p.wsa, p.beta)]
+    y = F.mask_cbam(xd, md, *ps, F.BlockConfig(hidden=p.w1.shape[0], k=k, use_sigmoid_mask=use_sig))
+    y.backward(gy.cuda().to(dtype).to(memory_format=CL))
+    torch.cuda.synchronize()
+    B, C, H, W = x.shape
+    if C > 1 and H * W > 1:
+        assert _is_cl(y) and _is_cl(xd.grad), "y / gx came back in another layout"
+    g = dict(gx=xd.grad, gmask=None if md is None else md.grad, gw1=ps[0].grad, gb1=ps[1].grad, gw2=ps[2].grad, gb2=ps[3].grad,
+             gwsa=ps[4].grad, gbeta=ps[5].grad)
+    return y.detach(), g
+
+
+@pytest.mark.parametrize("shape,mask_kind", FULL_SIZE_SHAPES)
+def test_full_size_vs_oracle_live_channels_last(F, shape, mask_kind):
+    B, C, H, W = shape
+    if mask_kind == "mixed" and B < 2:
+        mask_kind = "randn"
+    x, mask, gy = synth(B, C, H, W, seed=77, mask_kind=mask_kind)
+    p = O.Params.default_init(C, seed=3)
+    p.beta.fill_(0.3)
+    y_o, ctx = O.forward(x, mask, p)
+    g_o = O.backward(gy, x, mask, p, O.Config(), ctx)
+    y, g = _run_cl(F, x, mask, gy, p)
+    report = []
+    if not rel_err(y, y_o) < TOL:
+        report.append(f"y {rel_err(y, y_o):.3e}")
+    for k in GRADS:
+        if g_o[k] is None:
+            continue
+        e = rel_err(g[k], g_o[k])
+        if not e < TOL:
+            report.append(f"{k} {e:.3e}")
+    for k, got, want in (("y", y, y_o), ("gx", g["gx"], g_o["gx"]), ("gmask", g["gmask"], g_o["gmask"])):
+        if want is not None and not elem_err(got, want) < 1e-3:
+            report.append(f"{k} element-wise {elem_err(got, want):.3e}")
+    assert not report, "; ".join(report)
+
+
+@pytest.mark.parametrize("k", GENERIC_KS)
+def test_generic_spatial_kernel_sizes_channels_last(F, k):
+    """Run-time k (k_apply_nhwc<..., 0>) and k = 1 on channels_last features."""
+    B, C, H, W = 3, 32, 12, 20
+    x, mask, gy = synth(B, C, H, W, seed=k, mask_kind="mixed")
+    p = O.Params.default_init(C, k=k, seed=2)
+    with torch.no_grad():
+        p.wsa.mul_(3.0)
+    y_o, c = O.forward(x, mask, p)
+    g_o = O.backward(gy, x, mask, p, O.Config(), c)
+    y, g = _run_cl(F, x, mask, gy, p, k=k)
+    assert rel_err(y, y_o) < TOL
+    for name in GRADS:
+        assert rel_err(g[name], g_o[name]) < TOL, name
+
+
+@pytest.mark.parametrize("B,C,H,W,k,r,kind", FUZZER_REGRESSIONS)
+def test_regressions_found_by_the_fuzzer_channels_last(F, B, C, H, W, k, r, kind):
+    x, mask, gy = synth(B, C, H, W, seed=5, mask_kind=kind)
+    p = O.Params.default_init(C, r=r, k=k, seed=1)
+    cfg = O.Config(use_sigmoid_mask=kind != "prob")
+    y_o, c = O.forward(x, mask, p, cfg)
+    g_o = O.backward(gy, x, mask, p, cfg, c)
+    y, g = _run_cl(F, x, mask, gy, p, k=k, use_sig=kind != "prob")
+    assert rel_err(y, y_o) < TOL
+    floor = 1e-6 * float(gy.norm() * x.norm())
+    for name in GRADS:
+        tol = TOL * float(g_o[name].abs().max()) + (floor if name not in ("gx",) else 0.0)
+        assert float((g[name].detach().cpu().double() - g_o[name].double()).abs().max()) <= tol, name
+
+
+@pytest.mark.parametrize("shape,dtype,tol", CONFIG5_SHAPES)
+def test_config5_shapes_low_precision_channels_last(F, shape, dtype, tol):
+    B, C, H, W = shape
+    x, mask, gy = synth(B, C, H, W, seed=91, mask_kind="sparse")
+    x, gy = x.to(dtype).float(), gy.to(dtype).float()
+    p = O.Params.default_init(C, seed=5)
+    y_o, ctx = O.forward(x, mask, p)
+    g_o = O.backward(gy, x, mask, p, O.Config(), ctx)
+    y, g = _run_cl(F, x, mask, gy, p, dtype=dtype)
+    assert y.dtype == dtype and g["gx"].dtype == dtype
+    assert rel_err(y.float(), y_o) < tol and rel_err(g["gx"].float(), g_o["gx"]) < tol and rel_err(g["gmask"], g_o["gmask"]) < tol
+    for k in ("gw1", "gb1", "gw2", "gb2", "gwsa", "gbeta"):
+        assert rel_err(g[k], g_o[k]) < tol, k
+
+
+def test_backward_is_linear_in_gy_channels_last(F):
+    B, C, H, W = 32, 64, 80, 80
+    x, mask, gy = synth(B, C, H, W, seed=9, mask_kind="sparse")
+    p = O.Params.default_init(C)
+    _, g1 = _run_cl(F, x, mask, gy, p)
+    _, g2 = _run_cl(F, x, mask, -2.5 * gy, p)
+    for k in GRADS:
+        assert rel_err(g2[k], -2.5 * g1[k]) < 1e-5, k

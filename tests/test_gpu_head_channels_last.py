@@ -100,7 +100,10 @@ def _perturbed_head(Cc, hid, seed):
                                           (3, 36, 8, 9, 11),      # C % 8 != 0 (4-channel lanes), H*W % 4 != 0
                                           (2, 6, 8, 7, 5),        # C % 4 != 0: per-element lanes along C
                                           (2, 768, 192, 6, 10),   # hidden 192: the hidden > 128 forward template, dW1 in 3 passes
-                                          (1, 20, 40, 2, 500)])   # the widest row (W = 500)
+                                          (1, 20, 40, 2, 500),    # the widest row (W = 500)
+                                          (1, 130, 200, 12, 20),  # hidden 200 / 256 / 384: more 16-row M tiles; at 384 more than
+                                          (2, 64, 256, 8, 8),     # 4 waves x 4 tiles per wave, and dW1 in 4 / 6 passes of 64
+                                          (2, 96, 384, 9, 13)])
 def test_channels_last_vs_live_oracle(built_lib, dtype, tol, B, Cc, hid, H, W):
     """fp32 / fp16 / bf16 channels_last features against the fp32 oracle on the rounded inputs (4e-3 / 3e-2 for half precision)."""
     m = _perturbed_head(Cc, hid, 21)
@@ -119,6 +122,32 @@ def test_channels_last_vs_live_oracle(built_lib, dtype, tol, B, Cc, hid, H, W):
     assert rel_err(y.float(), lo) < tol and rel_err(xd.grad.float(), go["gx"]) < tol
     assert rel_err(m.proj[0].weight.grad.reshape(hid, Cc), go["gw1"]) < tol and rel_err(m.head.weight.grad, go["gwh"]) < tol
     assert rel_err(m.proj[1].weight.grad, go["ggamma"]) < tol and rel_err(m.proj[1].bias.grad, go["gbeta"]) < tol
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float16, 4e-3), (torch.bfloat16, 3e-2), (torch.float32, TOL)])
+@pytest.mark.parametrize("B,Cc,hid,H,W", [(3, 36, 8, 9, 11), (2, 6, 8, 7, 5), (1, 130, 200, 12, 20), (2, 96, 384, 9, 13)])
+def test_channels_last_eval_mode_vs_live_oracle(built_lib, dtype, tol, B, Cc, hid, H, W):
+    """Eval mode (running statistics, perturbed) on channels_last features, every element type, against the fp32 oracle."""
+    m = _perturbed_head(Cc, hid, 31)
+    g = torch.Generator().manual_seed(32)
+    with torch.no_grad():
+        m.proj[1].running_mean.add_(0.2 * torch.randn(hid, generator=g))
+        m.proj[1].running_var.mul_(0.5 + torch.rand(hid, generator=g))
+    m.eval()
+    x = torch.randn(B, Cc, H, W, generator=g).to(dtype)
+    gl = torch.randn(B, 1, H, W, generator=g).to(dtype)
+    p = HO.HeadParams.from_state_dict({k: v.detach().clone() for k, v in m.state_dict().items()})
+    lo, c = HO.forward(x.float(), p, False)
+    go = HO.backward(gl.float(), x.float(), p, c, False)
+    m.cuda()
+    xd = x.cuda().to(memory_format=CL).requires_grad_(True)
+    y = m(xd)
+    y.backward(gl.cuda())
+    assert xd.grad.dtype == dtype and _is_cl(xd.grad)
+    assert rel_err(y.float(), lo) < tol and rel_err(xd.grad.float(), go["gx"]) < tol
+    assert rel_err(m.proj[0].weight.grad.reshape(hid, Cc), go["gw1"]) < tol and rel_err(m.head.weight.grad, go["gwh"]) < tol
+    assert rel_err(m.proj[1].weight.grad, go["ggamma"]) < tol and rel_err(m.proj[1].bias.grad, go["gbeta"]) < tol
+    assert torch.equal(m.proj[1].running_mean.cpu(), p.running_mean) and torch.equal(m.proj[1].running_var.cpu(), p.running_var)
 
 
 def test_gradient_comes_back_channels_last(built_lib):

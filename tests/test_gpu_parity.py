@@ -137,15 +137,18 @@ def test_full_size_checksums_vs_reference(F, checksums, name):
     assert not report, f"{name}: " + "; ".join(report)
 
 
-@pytest.mark.parametrize("shape,mask_kind", [((32, 64, 80, 80), "sparse"), ((32, 128, 40, 40), "randn"), ((32, 256, 20, 20), "sparse"),
-                                             ((4, 192, 40, 40), "mixed"), ((2, 384, 20, 20), "randn"), ((3, 48, 17, 17), "mixed"),
-                                             ((1, 256, 160, 160), "sparse"), ((2, 512, 40, 40), "randn"), ((1, 768, 20, 20), "mixed"),
-                                             ((5, 64, 24, 40), "mixed"), ((9, 32, 6, 10), "randn"), ((1, 1, 1, 1), "randn"),
-                                             ((2, 3, 2, 3), "randn"), ((1, 16, 1, 37), "sparse"), ((11, 24, 13, 4), "mixed"),
-                                             # BASELINE configs[2] (YOLOv8s, 32 images per GPU) at FULL batch and configs[3]'s P4 (8 x 512 x 80 x 80):
-                                             # twice config 2's workgroups per launch; a wrong tile or halo shows here element by element
-                                             ((32, 128, 80, 80), "sparse"), ((32, 256, 40, 40), "randn"), ((32, 512, 20, 20), "sparse"),
-                                             ((8, 512, 80, 80), "sparse")])
+FULL_SIZE_SHAPES = [((32, 64, 80, 80), "sparse"), ((32, 128, 40, 40), "randn"), ((32, 256, 20, 20), "sparse"),
+                    ((4, 192, 40, 40), "mixed"), ((2, 384, 20, 20), "randn"), ((3, 48, 17, 17), "mixed"),
+                    ((1, 256, 160, 160), "sparse"), ((2, 512, 40, 40), "randn"), ((1, 768, 20, 20), "mixed"),
+                    ((5, 64, 24, 40), "mixed"), ((9, 32, 6, 10), "randn"), ((1, 1, 1, 1), "randn"),
+                    ((2, 3, 2, 3), "randn"), ((1, 16, 1, 37), "sparse"), ((11, 24, 13, 4), "mixed"),
+                    # BASELINE configs[2] (YOLOv8s, 32 images per GPU) at FULL batch and configs[3]'s P4 (8 x 512 x 80 x 80):
+                    # twice config 2's workgroups per launch; a wrong tile or halo shows here element by element
+                    ((32, 128, 80, 80), "sparse"), ((32, 256, 40, 40), "randn"), ((32, 512, 20, 20), "sparse"),
+                    ((8, 512, 80, 80), "sparse")]
+
+
+@pytest.mark.parametrize("shape,mask_kind", FULL_SIZE_SHAPES)
 def test_full_size_vs_oracle_live(F, shape, mask_kind):
     """Same seeded inputs through the oracle (CPU) and the HIP path, element-wise, at config-2 / config-3 sizes and the odd shapes."""
     B, C, H, W = shape
@@ -495,7 +498,10 @@ def test_fused_forward_generation_flags_wrap_around(F):
     assert int(plans[1].ctx_view(0)["sync"][0]) == want
 
 
-@pytest.mark.parametrize("k", [1, 9, 11, 15])
+GENERIC_KS = [1, 9, 11, 15]
+
+
+@pytest.mark.parametrize("k", GENERIC_KS)
 def test_generic_spatial_kernel_sizes(F, k):
     """spatial_k other than 3/5/7 takes the run-time-k code paths of the conv prologue, transposed conv and dWsa kernels."""
     B, C, H, W = 3, 32, 12, 20
@@ -514,8 +520,11 @@ def test_generic_spatial_kernel_sizes(F, k):
         assert rel_err(g[name], g_o[name]) < TOL, name
 
 
-@pytest.mark.parametrize("shape,dtype,tol", [((2, 256, 160, 160), torch.bfloat16, 3e-2), ((2, 512, 40, 40), torch.float16, 4e-3),
-                                             ((2, 512, 20, 20), torch.bfloat16, 3e-2), ((1, 768, 40, 40), torch.float32, 1e-4)])
+CONFIG5_SHAPES = [((2, 256, 160, 160), torch.bfloat16, 3e-2), ((2, 512, 40, 40), torch.float16, 4e-3),
+                  ((2, 512, 20, 20), torch.bfloat16, 3e-2), ((1, 768, 40, 40), torch.float32, 1e-4)]
+
+
+@pytest.mark.parametrize("shape,dtype,tol", CONFIG5_SHAPES)
 def test_config5_shapes_low_precision(F, shape, dtype, tol):
     """BASELINE.json configs[4] (YOLOv8l widths, 640/1280 inputs, bf16) and the x-scale width: large C / hidden (32, 48) takes
     the general MLP paths; half-precision I/O with fp32 statistics, against the fp32 oracle on the rounded inputs."""
@@ -572,14 +581,17 @@ def test_reentrant_from_two_threads_on_two_streams(F):
             assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("B,C,H,W,k,r,kind", [
+FUZZER_REGRESSIONS = [
     (3, 64, 14, 27, 1, 16, "mixed"),      # k = 1, H*W odd: the conv prologue stages a 1-row window (divide-by-one index magic)
     (16, 130, 23, 1, 1, 16, "sparse"),    # W = 1: 1-column windows
     (9, 256, 28, 1, 7, 1, "randn"),       # r = 1: hidden = C = 256 with one lane per row (LDS chunking of the hidden partials)
     (2, 320, 2, 12, 3, 1, "randn"),
     (8, 320, 8, 3, 9, 1, "prob"),
     (5, 3, 23, 17, 1, 1, "mixed"),
-])
+]
+
+
+@pytest.mark.parametrize("B,C,H,W,k,r,kind", FUZZER_REGRESSIONS)
 def test_regressions_found_by_the_fuzzer(F, B, C, H, W, k, r, kind):
     """Shapes that tests/fuzz/fuzz_parity.py (randomised parity fuzz, 1000 cases on MI355X) once broke."""
     x, mask, gy = synth(B, C, H, W, seed=5, mask_kind=kind)
