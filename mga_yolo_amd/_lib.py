@@ -251,6 +251,31 @@ def fwd_ws_bytes(B, Cc, H, W, hidden, flags: int) -> int:
     return n
 
 
+def sync_regions(B, Cc, H, W) -> dict:
+    """The hand-off state at ctx_layout()["sync"], in int32 words from its start: name -> (offset, length).  Every word is a generation
+    counter the caller zero-fills once.  This is the one Python copy of csrc/host.cuh's sync_layout (tests/test_abi.py pins the two
+    against each other): gate = (B, nflag) k_gate tile flags, status = [time-out, 3 spare], ca = (B) per-sample flags, tiles / conv_tiles =
+    (B, nflag) flags of the folded backward launch, merged_* / wsa_tiles = the same and the dWsa-tile flags of the merged launch
+    (k_bwd_r12), sweeps = its (B, C) per-channel flags."""
+    nf = B * ((H * W + 15) // 16 + 1)              # nflag per sample: one per 16 pixels (kSyncPx) + 1
+    out, o = {}, 0
+    for name, n in (("gate", nf), ("status", 4), ("ca", B), ("tiles", nf), ("conv_tiles", nf), ("merged_tiles", nf),
+                    ("merged_conv_tiles", nf), ("wsa_tiles", nf), ("sweeps", B * Cc)):
+        out[name] = (o, n)
+        o += n
+    return out
+
+
+def sync_len(B, Cc, H, W) -> int:
+    o, n = sync_regions(B, Cc, H, W)["sweeps"]
+    return o + n
+
+
+def sync_slices(B, Cc, H, W) -> dict:
+    """sync_regions as slice objects: ctx_views(...)["sync"][sync_slices(...)["status"]]"""
+    return {name: slice(o, o + n) for name, (o, n) in sync_regions(B, Cc, H, W).items()}
+
+
 def ctx_layout(B, Cc, H, W, hidden) -> dict:
     key = ("layout", B, Cc, H, W, hidden)
     lay = _size_cache.get(key)

@@ -6,55 +6,90 @@
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
-static int backward_args(const mgacbam_bwd_level_t& L, BwdArgs& A, Sig& sig) {
+// One level of either layout: validated (NULL, parameters, shape, dtype, alignment, capacity), then its kernel arguments.  N.a is the
+// whole result for an NCHW level; a channels-last level (sig.nhwc) also gets its chunk geometry and has no in-launch hand-off.
+static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig) {
+  const bool nhwc = (L.flags & MGACBAM_LAYOUT_NHWC) != 0;
   if (!L.x || !L.gy || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "backward: x / gy / ctx / scratch / gx is NULL");
   if (!L.gw1 || !L.gb1 || !L.gw2 || !L.gb2 || !L.gwsa || !L.gbeta) return fail(MGACBAM_E_NULL, "backward: NULL parameter-gradient pointer");
   if (L.gmask && !L.mask) return fail(MGACBAM_E_NULL, "backward: gmask requested but mask is NULL");
-  if (int e = check_params(L.p)) return e;
-  if (int e = check_shape(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k)) return e;
-  if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "backward: dtype %d", L.dtype);
-  const int VEC = vec_of(L.H, L.W);
+  if (int e = check_level("backward", L)) return e;
+  const int VEC = level_vec(nhwc, L.C, L.H, L.W, L.dtype);
   const size_t need = VEC * elem_size(L.dtype);
   if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
-      !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 16)))
-    return fail(MGACBAM_E_ALIGN, "backward: x/gy/gx must be %zu-byte aligned, ctx/scratch 16-byte", need);
+      !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, nhwc ? 4 : 16)) || (nhwc && L.mask && !aligned_to(L.mask, 4)))
+    return fail(MGACBAM_E_ALIGN, "backward%s: x/gy/gx must be %zu-byte aligned, ctx/scratch 16-byte", nhwc ? " (NHWC)" : "", need);
+  const ScratchLayout SL = scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k, nhwc, VEC);
+  if (int e = check_ctx_capacity("backward", L)) return e;
+  if (int e = check_capacity("backward", "scratch", SL.total, L.scratch_bytes)) return e;
+  BwdArgs& A = N.a;
   A.x = L.x; A.mask = L.mask; A.gy = L.gy; A.gx = L.gx; A.gmask = L.gmask;
   A.gw1 = L.gw1; A.gb1 = L.gb1; A.gw2 = L.gw2; A.gb2 = L.gb2; A.gwsa = L.gwsa; A.gbeta = L.gbeta;
-  A.c = ctx_ptrs(const_cast<void*>(L.ctx), L.B, L.C, L.H, L.W, L.p.hidden);
-  A.p = make_params(L.p);
-  A.g = make_geo(L.B, L.C, L.H, L.W, L.p);
-  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k);
-  const ScratchLayout SL = scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k);
-  {
-    mgacbam_ctx_layout_t CL;
-    ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, &CL);
-    if (int e = check_capacity("backward", "ctx", static_cast<size_t>(CL.total), L.ctx_bytes)) return e;
-    if (int e = check_capacity("backward", "scratch", SL.total, L.scratch_bytes)) return e;
-  }
-  char* sp = static_cast<char*>(L.scratch);
-  A.s.A_part = reinterpret_cast<float*>(sp + SL.A_part);
-  A.s.gpre = reinterpret_cast<float*>(sp + SL.gpre); A.s.gplanes = reinterpret_cast<float*>(sp + SL.gplanes);
-  A.s.gwsa_part = reinterpret_cast<float*>(sp + SL.gwsa_part);
-  A.s.gz = reinterpret_cast<float*>(sp + SL.gz); A.s.gbq = reinterpret_cast<float*>(sp + SL.gbq);
-  A.s.gh_avg = reinterpret_cast<float*>(sp + SL.gh_avg); A.s.gh_mx = reinterpret_cast<float*>(sp + SL.gh_mx);
-  A.s.pgh = reinterpret_cast<float*>(sp + SL.pgh);
-  A.nt = chan_tiles(A.t, A.g.H, A.g.W, VEC);
+  level_setup(L, A);
+  A.s = scratch_ptrs(L.scratch, SL);
   A.nconv = A.g.B * conv_tiles(A.t, A.g.H, A.g.W);
   A.nwsa = A.g.B * wsa_tiles(A.t, A.g.H, A.g.W);
   A.npg = params_blocks(A.g);
-  A.ncg = 0;
-  A.nflag = static_cast<int>(sync_flags(static_cast<size_t>(L.H) * L.W));
-  A.bflag0 = L.B * A.nflag + 4 + L.B;
-  A.cflag0 = A.bflag0 + L.B * A.nflag;
-  A.mbflag0 = A.cflag0 + L.B * A.nflag; A.mcflag0 = A.mbflag0 + L.B * A.nflag;
-  A.wflag0 = A.mcflag0 + L.B * A.nflag; A.sflag0 = A.wflag0 + L.B * A.nflag;
   A.merged = 0;
   A.vec = VEC;
-  { const Knobs kn = knobs(); A.trace = kn.trace; A.spin_limit = kn.spin_limit; }
-  const int proj = (L.flags & MGACBAM_BWD_HAVE_PROJ) && L.gmask != nullptr;
-  A.g.proj_h = (proj && L.p.hidden <= MGACBAM_PROJ_MAX_HIDDEN) ? L.p.hidden : 0;
-  sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, L.gmask != nullptr, proj};
+  sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, L.gmask != nullptr, 0};
+  if (nhwc) {
+    N.n = nhwc_geo(L.C, L.H, L.W, VEC);
+    N.ncb = (L.C + kNhwcFoldC - 1) / kNhwcFoldC;
+    A.nt = N.n.nchunk;
+    A.ncg = N.ncb;
+    A.bflag0 = A.cflag0 = A.mbflag0 = A.mcflag0 = A.wflag0 = A.sflag0 = 0;   // (no in-launch hand-off on this path)
+    sig.nhwc = 1;                                                 // (HAVE_PROJ is ignored: the NHWC apply reads x for dL/dmask)
+    sig.weight = L.C;
+    return 0;
+  }
+  A.nt = chan_tiles(A.t, A.g.H, A.g.W, VEC);
+  A.ncg = 0;                                                      // (set per group: backward_group)
+  const SyncLayout S = sync_layout(L.B, L.C, static_cast<size_t>(L.H) * L.W);
+  A.bflag0 = static_cast<int>(S.bflag); A.cflag0 = static_cast<int>(S.cflag);
+  A.mbflag0 = static_cast<int>(S.mbflag); A.mcflag0 = static_cast<int>(S.mcflag);
+  A.wflag0 = static_cast<int>(S.wflag); A.sflag0 = static_cast<int>(S.sflag);
+  sig.weight = L.C * A.t.chan_tx;
+  sig.proj = (L.flags & MGACBAM_BWD_HAVE_PROJ) && L.gmask != nullptr;
+  A.g.proj_h = (sig.proj && L.p.hidden <= MGACBAM_PROJ_MAX_HIDDEN) ? L.p.hidden : 0;
   return 0;
+}
+
+// The layout-free kernels take the plain level arguments: each launch computes its own grid and LDS size from the group
+template <typename SmemOf>
+static size_t group_smem(const Group<BwdArgs>& G, SmemOf smem_of) {
+  size_t smem = 0;
+  for (int l = 0; l < G.n; ++l) smem = std::max(smem, smem_of(G.lv[l]));
+  return smem;
+}
+static size_t reduce2_smem(const Tune& t) { return (64 + static_cast<size_t>(std::max(kPghLds, kBlock / t.pool_tx))) * sizeof(float); }
+static int launch_convT(Group<BwdArgs>& G, int k, hipStream_t st) {
+  const size_t smem = group_smem(G, [&](const BwdArgs& a) { return convT_smem(a.t, k); });
+  const int grid = fill_starts(G, G.lv, G.n, [](const BwdArgs& a) { return a.nconv; });
+  switch (k) {
+    case 3: LAUNCH(k_bwd_convT<3>, grid, smem, st, G); break;
+    case 5: LAUNCH(k_bwd_convT<5>, grid, smem, st, G); break;
+    case 7: LAUNCH(k_bwd_convT<7>, grid, smem, st, G); break;
+    default: LAUNCH(k_bwd_convT<0>, grid, smem, st, G); break;
+  }
+  return launch_status("k_bwd_convT");
+}
+static int launch_wsa(Group<BwdArgs>& G, int k, hipStream_t st) {
+  const size_t smem = group_smem(G, [&](const BwdArgs& a) { return wsa_smem(a.t, k); });
+  const int grid = fill_starts(G, G.lv, G.n, [](const BwdArgs& a) { return a.nwsa; });
+  switch (k) {
+    case 3: LAUNCH(k_bwd_wsa<3>, grid, smem, st, G); break;
+    case 5: LAUNCH(k_bwd_wsa<5>, grid, smem, st, G); break;
+    case 7: LAUNCH(k_bwd_wsa<7>, grid, smem, st, G); break;
+    default: LAUNCH(k_bwd_wsa<0>, grid, smem, st, G); break;
+  }
+  return launch_status("k_bwd_wsa");
+}
+static int launch_params(Group<BwdArgs>& G, hipStream_t st) {
+  const size_t smem = group_smem(G, [](const BwdArgs& a) { return params_smem(a.g); });
+  const int grid = fill_starts(G, G.lv, G.n, [](const BwdArgs& a) { return a.npg; });
+  LAUNCH(k_bwd_params, grid, smem, st, G);
+  return launch_status("k_bwd_params");
 }
 
 static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
@@ -70,7 +105,6 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
     lv[l].ncg = (lv[l].g.C + cpb - 1) / cpb;
     G.lv[l] = lv[l];
   }
-  auto fill = [&](auto blocks_of) { int tot = 0; for (int l = 0; l < n; ++l) { G.start[l] = tot; tot += blocks_of(lv[l]); } G.start[n] = tot; return tot; };
 
   // MGACBAM_BWD_FOLD: transposed conv as trailing role workgroups of the k_bwd_reduce1 launch (whole backward in this call, a tile at
   // least one image row and at least kSyncPx pixels -- one flag per tile in ctx.sync -- and few tiles per conv window)
@@ -94,7 +128,7 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
       lv[l].merged = 1; lv[l].bflag0 = lv[l].mbflag0; lv[l].cflag0 = lv[l].mcflag0;
       R.g.lv[l] = lv[l];
       smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec), convT_smem(lv[l].t, sig.k), wsa_smem(lv[l].t, sig.k),
-                       (64 + static_cast<size_t>(std::max(kPghLds, kBlock / lv[l].t.pool_tx))) * sizeof(float)});
+                       reduce2_smem(lv[l].t)});
     }
     int tot = 0;
     for (int p = 0; p < 4; ++p) {
@@ -116,7 +150,7 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
   if (fold && !merge) {
     size_t smem = 0;
     for (int l = 0; l < n; ++l) smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec), convT_smem(lv[l].t, sig.k)});
-    const int grid = fill([&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt) + pad8(a.nconv); });
+    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt) + pad8(a.nconv); });
 #define CALL_R1F(Tt, Vv) if (sig.k == 7) LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 7>), grid, smem, st, G); else LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 0>), grid, smem, st, G)
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R1F);
 #undef CALL_R1F
@@ -125,33 +159,23 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
   if ((stages & MGACBAM_BWD_REDUCE1) && !fold) {  // 1. per-(b,c) and per-pixel reductions of gy*x
     size_t smem = 0;
     for (int l = 0; l < n; ++l) smem = std::max(smem, reduce1_smem(lv[l].g, sig.vec));
-    const int grid = fill([&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt); });
+    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt); });
 #define CALL_R1(Tt, Vv) LAUNCH((k_bwd_reduce1<Tt, Vv>), grid, smem, st, G)
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R1);
 #undef CALL_R1
     if (int e = launch_status("k_bwd_reduce1")) return e;
   }
-  if ((stages & MGACBAM_BWD_CONVT) && !fold) {  // 2. transposed conv
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, convT_smem(lv[l].t, sig.k));
-    const int grid = fill([&](const BwdArgs& a) { return a.nconv; });
-    switch (sig.k) {
-      case 3: LAUNCH(k_bwd_convT<3>, grid, smem, st, G); break;
-      case 5: LAUNCH(k_bwd_convT<5>, grid, smem, st, G); break;
-      case 7: LAUNCH(k_bwd_convT<7>, grid, smem, st, G); break;
-      default: LAUNCH(k_bwd_convT<0>, grid, smem, st, G); break;
-    }
-    if (int e = launch_status("k_bwd_convT")) return e;
-  }
+  if ((stages & MGACBAM_BWD_CONVT) && !fold)  // 2. transposed conv
+    if (int e = launch_convT(G, sig.k, st)) return e;
   const bool fuse_pg = fuse && (stages & MGACBAM_BWD_APPLY) && (stages & MGACBAM_BWD_PARAMGRAD);
   const bool fuse_wsa = fuse && (stages & MGACBAM_BWD_REDUCE2) && (stages & MGACBAM_BWD_WSA) && sig.k == 7;   // dWsa tile partials: leading roles of k_bwd_reduce2
   if ((stages & MGACBAM_BWD_REDUCE2) && !merge) {  // 3. rest of g_ca (needs g_planes), g_z [+ dWsa partials as role workgroups]
     size_t smem = 0;
     for (int l = 0; l < n; ++l) {
-      smem = std::max(smem, (64 + static_cast<size_t>(std::max(kPghLds, kBlock / lv[l].t.pool_tx))) * sizeof(float));
+      smem = std::max(smem, reduce2_smem(lv[l].t));
       if (fuse_wsa) smem = std::max(smem, wsa_smem(lv[l].t, sig.k));
     }
-    const int grid = fill([&](const BwdArgs& a) { return (fuse_wsa ? pad8(a.nwsa) : 0) + sweep_blocks(a, a.t.pool_tx, cpt); });
+    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return (fuse_wsa ? pad8(a.nwsa) : 0) + sweep_blocks(a, a.t.pool_tx, cpt); });
 #define CALL_R22(CPTV) if (fuse_wsa) LAUNCH((k_bwd_reduce2<TT, VV, CPTV, true>), grid, smem, st, G); else LAUNCH((k_bwd_reduce2<TT, VV, CPTV, false>), grid, smem, st, G)
 #define CALL_R2(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_R22); }
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R2);
@@ -159,32 +183,17 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
 #undef CALL_R22
     if (int e = launch_status("k_bwd_reduce2")) return e;
   }
-  if ((stages & MGACBAM_BWD_WSA) && !fuse_wsa && !merge) {  // 4. dWsa tile partials (depends on stage 1 only)
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, wsa_smem(lv[l].t, sig.k));
-    const int grid = fill([&](const BwdArgs& a) { return a.nwsa; });
-    switch (sig.k) {
-      case 3: LAUNCH(k_bwd_wsa<3>, grid, smem, st, G); break;
-      case 5: LAUNCH(k_bwd_wsa<5>, grid, smem, st, G); break;
-      case 7: LAUNCH(k_bwd_wsa<7>, grid, smem, st, G); break;
-      default: LAUNCH(k_bwd_wsa<0>, grid, smem, st, G); break;
-    }
-    if (int e = launch_status("k_bwd_wsa")) return e;
-  }
-  if ((stages & MGACBAM_BWD_PARAMGRAD) && !fuse_pg) {  // 5. every parameter gradient
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, params_smem(lv[l].g));
-    const int grid = fill([&](const BwdArgs& a) { return a.npg; });
-    LAUNCH(k_bwd_params, grid, smem, st, G);
-    if (int e = launch_status("k_bwd_params")) return e;
-  }
+  if ((stages & MGACBAM_BWD_WSA) && !fuse_wsa && !merge)  // 4. dWsa tile partials (depends on stage 1 only)
+    if (int e = launch_wsa(G, sig.k, st)) return e;
+  if ((stages & MGACBAM_BWD_PARAMGRAD) && !fuse_pg)  // 5. every parameter gradient
+    if (int e = launch_params(G, st)) return e;
   if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask) [+ parameter gradients as role workgroups]
     size_t smem = 0;
     for (int l = 0; l < n; ++l) {
       smem = std::max(smem, bwd_apply_smem(lv[l].g, sig.vec));
       if (fuse_pg) smem = std::max(smem, params_smem(lv[l].g));
     }
-    const int grid = fill([&](const BwdArgs& a) { return (fuse_pg ? pad8(a.npg) : 0) + xcd_grid(a.g.B, a.nt); });
+    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return (fuse_pg ? pad8(a.npg) : 0) + xcd_grid(a.g.B, a.nt); });
 #define CALL_AP2(GM) if (fuse_pg) LAUNCH((k_bwd_apply<TT, VV, GM, true>), grid, smem, st, G); else LAUNCH((k_bwd_apply<TT, VV, GM, false>), grid, smem, st, G)
 #define CALL_AP(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; if (sig.gmask) { CALL_AP2(true); } else { CALL_AP2(false); } }
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_AP);
@@ -199,127 +208,45 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
 // backward of channels-last levels (nhwc.cuh): k_bwd_reduce1_nhwc, k_bwd_convT, k_bwd_reduce2_nhwc + k_bwd_fold_nhwc, k_bwd_wsa,
 // k_bwd_params, k_bwd_apply_nhwc -- the layout-free kernels are the NCHW path's own
 // ------------------------------------------------------------------------------------------------
-namespace mgacbam {
-inline int level_weight(const NhwcBwdArgs& a, int) { return a.a.g.C; }   // (found by for_each_group through ADL)
-}
-
-static int nhwc_backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig) {
-  if (!L.x || !L.gy || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "backward: x / gy / ctx / scratch / gx is NULL");
-  if (!L.gw1 || !L.gb1 || !L.gw2 || !L.gb2 || !L.gwsa || !L.gbeta) return fail(MGACBAM_E_NULL, "backward: NULL parameter-gradient pointer");
-  if (L.gmask && !L.mask) return fail(MGACBAM_E_NULL, "backward: gmask requested but mask is NULL");
-  if (int e = check_params(L.p)) return e;
-  if (int e = check_shape(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k)) return e;
-  if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "backward: dtype %d", L.dtype);
-  const int VEC = nhwc_vec(L.C, L.dtype);
-  const size_t need = VEC * elem_size(L.dtype);
-  if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
-      !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 4)) || (L.mask && !aligned_to(L.mask, 4)))
-    return fail(MGACBAM_E_ALIGN, "backward (NHWC): x/gy/gx must be %zu-byte aligned, ctx/scratch 16-byte", need);
-  const ScratchLayout SL = nhwc_scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k, VEC);
-  {
-    mgacbam_ctx_layout_t CL;
-    ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, &CL);
-    if (int e = check_capacity("backward", "ctx", static_cast<size_t>(CL.total), L.ctx_bytes)) return e;
-    if (int e = check_capacity("backward", "scratch", SL.total, L.scratch_bytes)) return e;
-  }
-  BwdArgs& A = N.a;
-  A.x = L.x; A.mask = L.mask; A.gy = L.gy; A.gx = L.gx; A.gmask = L.gmask;
-  A.gw1 = L.gw1; A.gb1 = L.gb1; A.gw2 = L.gw2; A.gb2 = L.gb2; A.gwsa = L.gwsa; A.gbeta = L.gbeta;
-  A.c = ctx_ptrs(const_cast<void*>(L.ctx), L.B, L.C, L.H, L.W, L.p.hidden);
-  A.p = make_params(L.p);
-  A.g = make_geo(L.B, L.C, L.H, L.W, L.p);
-  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k);
-  char* sp = static_cast<char*>(L.scratch);
-  A.s.A_part = reinterpret_cast<float*>(sp + SL.A_part);
-  A.s.gpre = reinterpret_cast<float*>(sp + SL.gpre); A.s.gplanes = reinterpret_cast<float*>(sp + SL.gplanes);
-  A.s.gwsa_part = reinterpret_cast<float*>(sp + SL.gwsa_part);
-  A.s.gz = reinterpret_cast<float*>(sp + SL.gz); A.s.gbq = reinterpret_cast<float*>(sp + SL.gbq);
-  A.s.gh_avg = reinterpret_cast<float*>(sp + SL.gh_avg); A.s.gh_mx = reinterpret_cast<float*>(sp + SL.gh_mx);
-  A.s.pgh = reinterpret_cast<float*>(sp + SL.pgh);
-  N.n = nhwc_geo(L.C, L.H, L.W, VEC);
-  N.ncb = (L.C + kNhwcFoldC - 1) / kNhwcFoldC;
-  A.nt = N.n.nchunk;
-  A.nconv = A.g.B * conv_tiles(A.t, A.g.H, A.g.W);
-  A.nwsa = A.g.B * wsa_tiles(A.t, A.g.H, A.g.W);
-  A.npg = params_blocks(A.g);
-  A.ncg = N.ncb;
-  A.nflag = static_cast<int>(sync_flags(static_cast<size_t>(L.H) * L.W));
-  A.bflag0 = A.cflag0 = A.mbflag0 = A.mcflag0 = A.wflag0 = A.sflag0 = 0;   // (no in-launch hand-off on this path)
-  A.merged = 0;
-  A.vec = VEC;
-  { const Knobs kn = knobs(); A.trace = kn.trace; A.spin_limit = kn.spin_limit; }
-  A.g.proj_h = 0;                                               // (HAVE_PROJ is ignored: the NHWC apply reads x for dL/dmask)
-  sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, L.gmask != nullptr, 0};
-  sig.nhwc = 1;
-  return 0;
-}
-
 static int backward_group_nhwc(NhwcBwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
   Group<NhwcBwdArgs> G;
   Group<BwdArgs> GB;                                            // the layout-free kernels take the plain level arguments
   G.n = GB.n = n;
   for (int l = 0; l < n; ++l) { G.lv[l] = lv[l]; GB.lv[l] = lv[l].a; }
-  auto fill = [&](auto blocks_of) { int tot = 0; for (int l = 0; l < n; ++l) { G.start[l] = tot; tot += blocks_of(lv[l]); } G.start[n] = tot; return tot; };
-  auto fillb = [&](auto blocks_of) { int tot = 0; for (int l = 0; l < n; ++l) { GB.start[l] = tot; tot += blocks_of(lv[l].a); } GB.start[n] = tot; return tot; };
-  auto chunks = [&]() { return fill([&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }); };
+  auto chunks = [&]() { return fill_starts(G, lv, n, [&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }); };
   if (stages & MGACBAM_BWD_REDUCE1) {  // 1. chunk partials of A and D, g_pre
     size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, (3 * ((static_cast<size_t>(lv[l].a.g.C) + 3) & ~static_cast<size_t>(3)) + 2 * kBlock * sig.vec) * sizeof(float));
+    for (int l = 0; l < n; ++l) smem = std::max(smem, nhwc_reduce1_smem(lv[l].a.g, sig.vec));
     const int grid = chunks();
 #define CALL_NR1(Tt, Vv) LAUNCH((k_bwd_reduce1_nhwc<Tt, Vv>), grid, smem, st, G)
-    DISPATCH_T_NVEC(sig.dtype, sig.vec, CALL_NR1);
+    DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_NR1);
 #undef CALL_NR1
     if (int e = launch_status("k_bwd_reduce1_nhwc")) return e;
   }
-  if (stages & MGACBAM_BWD_CONVT) {  // 2. transposed conv
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, convT_smem(lv[l].a.t, sig.k));
-    const int grid = fillb([&](const BwdArgs& a) { return a.nconv; });
-    switch (sig.k) {
-      case 3: LAUNCH(k_bwd_convT<3>, grid, smem, st, GB); break;
-      case 5: LAUNCH(k_bwd_convT<5>, grid, smem, st, GB); break;
-      case 7: LAUNCH(k_bwd_convT<7>, grid, smem, st, GB); break;
-      default: LAUNCH(k_bwd_convT<0>, grid, smem, st, GB); break;
-    }
-    if (int e = launch_status("k_bwd_convT")) return e;
-  }
+  if (stages & MGACBAM_BWD_CONVT)  // 2. transposed conv
+    if (int e = launch_convT(GB, sig.k, st)) return e;
   if (stages & MGACBAM_BWD_REDUCE2) {  // 3. chunk partials of the g_planes term, then their fold: g_z, D, hidden-gradient partials
     size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, static_cast<size_t>(lv[l].a.g.C) * sizeof(float));
+    for (int l = 0; l < n; ++l) smem = std::max(smem, nhwc_reduce2_smem(lv[l].a.g));
     const int grid = chunks();
 #define CALL_NR2(Tt, Vv) LAUNCH((k_bwd_reduce2_nhwc<Tt, Vv>), grid, smem, st, G)
-    DISPATCH_T_NVEC(sig.dtype, sig.vec, CALL_NR2);
+    DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_NR2);
 #undef CALL_NR2
     if (int e = launch_status("k_bwd_reduce2_nhwc")) return e;
-    const int fgrid = fill([&](const NhwcBwdArgs& a) { return a.a.g.B * a.ncb; });
+    const int fgrid = fill_starts(G, lv, n, [&](const NhwcBwdArgs& a) { return a.a.g.B * a.ncb; });
     LAUNCH(k_bwd_fold_nhwc, fgrid, 0, st, G);
     if (int e = launch_status("k_bwd_fold_nhwc")) return e;
   }
-  if (stages & MGACBAM_BWD_WSA) {  // 4. dWsa tile partials
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, wsa_smem(lv[l].a.t, sig.k));
-    const int grid = fillb([&](const BwdArgs& a) { return a.nwsa; });
-    switch (sig.k) {
-      case 3: LAUNCH(k_bwd_wsa<3>, grid, smem, st, GB); break;
-      case 5: LAUNCH(k_bwd_wsa<5>, grid, smem, st, GB); break;
-      case 7: LAUNCH(k_bwd_wsa<7>, grid, smem, st, GB); break;
-      default: LAUNCH(k_bwd_wsa<0>, grid, smem, st, GB); break;
-    }
-    if (int e = launch_status("k_bwd_wsa")) return e;
-  }
-  if (stages & MGACBAM_BWD_PARAMGRAD) {  // 5. every parameter gradient
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, params_smem(lv[l].a.g));
-    const int grid = fillb([&](const BwdArgs& a) { return a.npg; });
-    LAUNCH(k_bwd_params, grid, smem, st, GB);
-    if (int e = launch_status("k_bwd_params")) return e;
-  }
+  if (stages & MGACBAM_BWD_WSA)  // 4. dWsa tile partials
+    if (int e = launch_wsa(GB, sig.k, st)) return e;
+  if (stages & MGACBAM_BWD_PARAMGRAD)  // 5. every parameter gradient
+    if (int e = launch_params(GB, st)) return e;
   if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask)
     size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, (5 * static_cast<size_t>(lv[l].a.g.C) + 2 * lv[l].a.g.hidden) * sizeof(float));
-    const int grid = fill([&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); });
+    for (int l = 0; l < n; ++l) smem = std::max(smem, nhwc_bwd_apply_smem(lv[l].a.g));
+    const int grid = fill_starts(G, lv, n, [&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); });
 #define CALL_NAP(Tt, Vv) if (sig.gmask) LAUNCH((k_bwd_apply_nhwc<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_bwd_apply_nhwc<Tt, Vv, false>), grid, smem, st, G)
-    DISPATCH_T_NVEC(sig.dtype, sig.vec, CALL_NAP);
+    DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_NAP);
 #undef CALL_NAP
     if (int e = launch_status("k_bwd_apply_nhwc")) return e;
   }
@@ -336,8 +263,10 @@ extern "C" int mgacbam_backward_stages(const mgacbam_bwd_level_t* levels, int n_
   Sig nsigs[MGACBAM_MAX_LEVELS];
   int nc = 0, nn = 0;                                           // NCHW levels, NHWC levels (every level is checked before any launch)
   for (int l = 0; l < n_levels; ++l) {
-    if (levels[l].flags & MGACBAM_LAYOUT_NHWC) { if (int e = nhwc_backward_args(levels[l], nargs[nn], nsigs[nn])) return e; ++nn; }
-    else { if (int e = backward_args(levels[l], args[nc], sigs[nc])) return e; ++nc; }
+    NhwcBwdArgs N;
+    Sig s;
+    if (int e = backward_args(levels[l], N, s)) return e;
+    if (s.nhwc) { nargs[nn] = N; nsigs[nn++] = s; } else { args[nc] = N.a; sigs[nc++] = s; }
   }
   if (nc) if (int e = for_each_group(args, sigs, nc, [&](BwdArgs* g, int m, const Sig& s) { return backward_group(g, m, s, stages, st); })) return e;
   if (nn) if (int e = for_each_group(nargs, nsigs, nn, [&](NhwcBwdArgs* g, int m, const Sig& s) { return backward_group_nhwc(g, m, s, stages, st); })) return e;

@@ -31,16 +31,15 @@ extern "C" int mgacbam_ctx_layout(int B, int C, int H, int W, int hidden, mgacba
 
 extern "C" size_t mgacbam_fwd_ws_bytes(int B, int C, int H, int W, int hidden, int flags) {
   if (check_shape(B, C, H, W, hidden, 7)) return 0;
-  return (flags & MGACBAM_LAYOUT_NHWC) ? nhwc_ws_bytes_any(B, C, H, W) : 0;
+  return ws_bytes_any(B, C, H, W, (flags & MGACBAM_LAYOUT_NHWC) != 0);
 }
 
 extern "C" size_t mgacbam_bwd_scratch_bytes_flags(int B, int C, int H, int W, int hidden, int k, int flags) {
   if (check_shape(B, C, H, W, hidden, k)) return 0;
-  return (flags & MGACBAM_LAYOUT_NHWC) ? nhwc_scratch_bytes_any(B, C, H, W, hidden, k) : scratch_layout(B, C, H, W, hidden, k).total;
+  return scratch_bytes_any(B, C, H, W, hidden, k, (flags & MGACBAM_LAYOUT_NHWC) != 0);
 }
 
 extern "C" size_t mgacbam_bwd_scratch_bytes(int B, int C, int H, int W, int hidden, int k) {
-  if (check_shape(B, C, H, W, hidden, k)) return 0;
-  return scratch_layout(B, C, H, W, hidden, k).total;          // (the same for every element type: the geometry does not depend on it)
+  return mgacbam_bwd_scratch_bytes_flags(B, C, H, W, hidden, k, 0);
 }
 

@@ -45,8 +45,7 @@ static int eca_forward_group(EcaFwdArgs* lv, int n, const Sig& sig, hipStream_t 
   G.n = n;
   const int cpt = group_cpt(lv, n);
   for (int l = 0; l < n; ++l) { lv[l].t.pool_cpt = cpt; G.lv[l] = lv[l]; }
-  auto fill = [&](auto blocks_of) { int tot = 0; for (int l = 0; l < n; ++l) { G.start[l] = tot; tot += blocks_of(lv[l]); } G.start[n] = tot; return tot; };
-  const int grid = fill([&](const EcaFwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); });
+  const int grid = fill_starts(G, lv, n, [&](const EcaFwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); });
 #define CALL_EP2(CPTV) if (sig.has_mask) LAUNCH((k_eca_pool<TT, VV, CPTV, true>), grid, 0, st, G); else LAUNCH((k_eca_pool<TT, VV, CPTV, false>), grid, 0, st, G)
 #define CALL_EP(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_EP2); }
   DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_EP);
@@ -90,6 +89,7 @@ extern "C" int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_
     A.g = eca_geo(L.B, L.C, L.H, L.W, L.p);
     A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
     sigs[l] = Sig{L.dtype, VEC, L.mask != nullptr, 0, 0, 0};
+    sigs[l].weight = L.C * A.t.chan_tx;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int e = for_each_group(args, sigs, n_levels, [&](EcaFwdArgs* g, int m, const Sig& s) { return eca_forward_group(g, m, s, st); })) return e;
@@ -102,9 +102,8 @@ static int eca_backward_group(EcaBwdArgs* lv, int n, const Sig& sig, hipStream_t
   G.n = n;
   const int cpt = group_cpt(lv, n);
   for (int l = 0; l < n; ++l) { lv[l].t.pool_cpt = cpt; G.lv[l] = lv[l]; }
-  auto fill = [&](auto blocks_of) { int tot = 0; for (int l = 0; l < n; ++l) { G.start[l] = tot; tot += blocks_of(lv[l]); } G.start[n] = tot; return tot; };
   {
-    const int grid = fill([&](const EcaBwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); });
+    const int grid = fill_starts(G, lv, n, [&](const EcaBwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); });
 #define CALL_ER2(CPTV) LAUNCH((k_eca_reduce<TT, VV, CPTV>), grid, 0, st, G)
 #define CALL_ER(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_ER2); }
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_ER);
@@ -115,7 +114,7 @@ static int eca_backward_group(EcaBwdArgs* lv, int n, const Sig& sig, hipStream_t
   {
     size_t smem = 0;
     for (int l = 0; l < n; ++l) smem = std::max(smem, (3 * static_cast<size_t>(lv[l].g.C) + kBlock * sig.vec) * sizeof(float));
-    const int grid = fill([&](const EcaBwdArgs& a) { return kEcaRoles + xcd_grid(a.g.B, a.nt); });
+    const int grid = fill_starts(G, lv, n, [&](const EcaBwdArgs& a) { return kEcaRoles + xcd_grid(a.g.B, a.nt); });
 #define CALL_EB(Tt, Vv) if (sig.gmask) LAUNCH((k_eca_bwd<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_eca_bwd<Tt, Vv, false>), grid, smem, st, G)
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_EB);
 #undef CALL_EB
@@ -152,6 +151,7 @@ extern "C" int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n
     A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
     A.nt = chan_tiles(A.t, L.H, L.W, VEC);
     sigs[l] = Sig{L.dtype, VEC, L.mask != nullptr, 0, L.gmask != nullptr, 0};
+    sigs[l].weight = L.C * A.t.chan_tx;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int e = for_each_group(args, sigs, n_levels, [&](EcaBwdArgs* g, int m, const Sig& s) { return eca_backward_group(g, m, s, st); })) return e;

@@ -145,6 +145,7 @@ static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, in
   A.nwg_out = t.nwg_out; A.out_ppt = t.out_ppt; A.out_px = t.out_px; A.out_per = t.out_per; A.nwg1 = t.nwg1; A.act_ppt = t.act_ppt; A.act_hl_max = t.act_hl; A.ncb = t.ncb; A.nshare = t.nshare; A.gw2 = t.gw2;
   sig = Sig{dtype, t.vec, 0, 0, 0, 0};
   if (nhwc) { sig.nhwc = 1; sig.cvec = C % 4 == 0 ? 4 : 1; }
+  sig.weight = C;
   return 0;
 }
 static size_t head_gemm_smem(const HeadArgs* lv, int n) {
@@ -156,13 +157,6 @@ static int max_hidp(const HeadArgs* lv, int n) {
   int m = 0;
   for (int l = 0; l < n; ++l) m = std::max(m, lv[l].g.hidp);
   return m;
-}
-template <typename Fn>
-static int head_fill(Group<HeadArgs>& G, const HeadArgs* lv, int n, Fn blocks_of) {
-  int tot = 0;
-  for (int l = 0; l < n; ++l) { G.start[l] = tot; tot += blocks_of(lv[l]); }
-  G.start[n] = tot;
-  return tot;
 }
 static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t st) {
   Group<HeadArgs> G;
@@ -186,11 +180,9 @@ static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t s
       for (int l = 0; l < Gm.n; ++l) Gm.lv[l].trace_base = pass * 8192;
       if (sig.nhwc) {                                             // channels-last features: head_nhwc.cuh (the level's MTW is its own fw_mtw)
         const size_t nsmem = static_cast<size_t>(8) * max_hidp(lv, n) * sizeof(float);
-#define CALL_HN3(Tt, Cv) { if (mtw <= 2) { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 2>), grid, nsmem, st, Gm); } else { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 4>), grid, nsmem, st, Gm); } }
-#define CALL_HN(Tt) { if (sig.cvec == 4) { CALL_HN3(Tt, 4); } else { CALL_HN3(Tt, 1); } }
-        if (sig.dtype == MGACBAM_F32) { CALL_HN(float); } else if (sig.dtype == MGACBAM_F16) { CALL_HN(__half); } else { CALL_HN(bf16_t); }
+#define CALL_HN(Tt, Cv) { if (mtw <= 2) { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 2>), grid, nsmem, st, Gm); } else { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 4>), grid, nsmem, st, Gm); } }
+        DISPATCH_T_VEC(sig.dtype, sig.cvec, CALL_HN);
 #undef CALL_HN
-#undef CALL_HN3
         if (int e = launch_status("k_head_gemm_nhwc")) return e;
         continue;
       }
@@ -201,21 +193,19 @@ static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t s
       }
 #define CALL_HP3(Tt, Vv, Mm) LAUNCH((k_head_gemm<Tt, Vv, false, Mm>), grid, smem, st, Gm)
 #define CALL_HP(Tt, Vv) { if (mtw <= 2) { CALL_HP3(Tt, Vv, 2); } else { CALL_HP3(Tt, Vv, 4); } }
-      if (sig.dtype == MGACBAM_F32) { if (sig.vec == 4) { CALL_HP(float, 4); } else { CALL_HP(float, 1); } }
-      else if (sig.dtype == MGACBAM_F16) { if (sig.vec == 4) { CALL_HP(__half, 4); } else { CALL_HP(__half, 1); } }
-      else { if (sig.vec == 4) { CALL_HP(bf16_t, 4); } else { CALL_HP(bf16_t, 1); } }
+      DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_HP);
 #undef CALL_HP
 #undef CALL_HP3
       if (int e = launch_status("k_head_gemm<fwd>")) return e;
     }
   }
   {
-    const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.g.hid; });
+    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.hid; });
     LAUNCH(k_head_stats, grid, 0, st, G);
     if (int e = launch_status("k_head_stats")) return e;
   }
   {
-    const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.nwg_out; });
+    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.nwg_out; });
     const size_t smem = 0;
 #define CALL_HO(Tt) { if (sig.vec == 4) { LAUNCH((k_head_out<Tt, 4>), grid, smem, st, G); } else { LAUNCH((k_head_out<Tt, 1>), grid, smem, st, G); } }
     switch (sig.lf32 ? MGACBAM_F32 : sig.dtype) {              // (the kernel's element type is the LOGITS' type: z is fp32)
@@ -257,7 +247,7 @@ static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t 
     int hl = 0;
     for (int l = 0; l < n; ++l) hl = std::max(hl, lv[l].act_hl_max);
     for (int l = 0; l < n; ++l) { lv[l].act_hl_max = hl; G.lv[l].act_hl_max = hl; }      // the reduction scratch sits behind the launch's longest run
-    const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.nwg1 * ((a.g.hid + kHeadJC - 1) / kHeadJC); });
+    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.nwg1 * ((a.g.hid + kHeadJC - 1) / kHeadJC); });
     const size_t smem = (static_cast<size_t>(hl) + 16 * kHeadJC * kHeadNStat) * sizeof(float);
     switch (sig.lf32 ? MGACBAM_F32 : sig.dtype) {              // (the kernel's element type is g_logits' type)
       case MGACBAM_F32: LAUNCH(k_head_bwd_act<float>, grid, smem, st, G); break;
@@ -267,37 +257,35 @@ static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t 
     if (int e = launch_status("k_head_bwd_act")) return e;
   }
   {
-    const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.g.hid; });
+    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.hid; });
     LAUNCH(k_head_bwd_fin, grid, 0, st, G);
     if (int e = launch_status("k_head_bwd_fin")) return e;
   }
   if (sig.nhwc) {                                                 // channels-last features: head_nhwc.cuh
     const size_t hp = static_cast<size_t>(max_hidp(lv, n));
     {
-      const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
+      const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
       const size_t smem = 5 * hp * sizeof(float);
-#define CALL_HX(Tt) { if (sig.cvec == 4) { LAUNCH((k_head_gx_nhwc<Tt, 4>), grid, smem, st, G); } else { LAUNCH((k_head_gx_nhwc<Tt, 1>), grid, smem, st, G); } }
-      if (sig.dtype == MGACBAM_F32) { CALL_HX(float); } else if (sig.dtype == MGACBAM_F16) { CALL_HX(__half); } else { CALL_HX(bf16_t); }
+#define CALL_HX(Tt, Cv) LAUNCH((k_head_gx_nhwc<Tt, Cv>), grid, smem, st, G)
+      DISPATCH_T_VEC(sig.dtype, sig.cvec, CALL_HX);
 #undef CALL_HX
       if (int e = launch_status("k_head_gx_nhwc")) return e;
     }
     {
-      const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.ncb * a.nshare; });
+      const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.ncb * a.nshare; });
       const size_t smem = (5 * hp + 2 * static_cast<size_t>(kHeadGwPx) * kHeadGwPitch) * sizeof(float);
-#define CALL_HW(Tt) { if (sig.cvec == 4) { LAUNCH((k_head_gw_nhwc<Tt, 4>), grid, smem, st, G); } else { LAUNCH((k_head_gw_nhwc<Tt, 1>), grid, smem, st, G); } }
-      if (sig.dtype == MGACBAM_F32) { CALL_HW(float); } else if (sig.dtype == MGACBAM_F16) { CALL_HW(__half); } else { CALL_HW(bf16_t); }
+#define CALL_HW(Tt, Cv) LAUNCH((k_head_gw_nhwc<Tt, Cv>), grid, smem, st, G)
+      DISPATCH_T_VEC(sig.dtype, sig.cvec, CALL_HW);
 #undef CALL_HW
       if (int e = launch_status("k_head_gw_nhwc")) return e;
     }
   } else {
   {
     for (int l = 0; l < n; ++l) G.lv[l].trace_base = 16384;
-    const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
+    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
     const size_t smem = head_gemm_smem(lv, n);
 #define CALL_HX(Tt, Vv) LAUNCH((k_head_gemm<Tt, Vv, true, 2>), grid, smem, st, G)
-    if (sig.dtype == MGACBAM_F32) { if (sig.vec == 4) { CALL_HX(float, 4); } else { CALL_HX(float, 1); } }
-    else if (sig.dtype == MGACBAM_F16) { if (sig.vec == 4) { CALL_HX(__half, 4); } else { CALL_HX(__half, 1); } }
-    else { if (sig.vec == 4) { CALL_HX(bf16_t, 4); } else { CALL_HX(bf16_t, 1); } }
+    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_HX);
 #undef CALL_HX
     if (int e = launch_status("k_head_gemm<gx>")) return e;
   }
@@ -325,16 +313,14 @@ static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t 
         continue;
       }
 #define CALL_HW(Tt, Vv) LAUNCH((k_head_bwd_gw<Tt, Vv>), grid, smem, st, Gw)
-      if (sig.dtype == MGACBAM_F32) { if (sig.vec == 4) { CALL_HW(float, 4); } else { CALL_HW(float, 1); } }
-      else if (sig.dtype == MGACBAM_F16) { if (sig.vec == 4) { CALL_HW(__half, 4); } else { CALL_HW(__half, 1); } }
-      else { if (sig.vec == 4) { CALL_HW(bf16_t, 4); } else { CALL_HW(bf16_t, 1); } }
+      DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_HW);
 #undef CALL_HW
       if (int e = launch_status("k_head_bwd_gw")) return e;
     }
   }
   }
   {
-    const int grid = head_fill(G, lv, n, [](const HeadArgs& a) { return (a.g.hid * a.g.C + kHeadGwfOut - 1) / kHeadGwfOut; });
+    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return (a.g.hid * a.g.C + kHeadGwfOut - 1) / kHeadGwfOut; });
     LAUNCH(k_head_bwd_gwf, grid, 0, st, G);
     if (int e = launch_status("k_head_bwd_gwf")) return e;
   }

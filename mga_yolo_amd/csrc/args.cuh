@@ -47,7 +47,7 @@ struct Tune {
 struct FwdArgs {
   const void* x; const float* mask; void* y;
   CtxPtrs c; ParamPtrs p; Geo g; Tune t;
-  int nflag;       // flags per sample in c.sync (host: sync_flags(HW))
+  int nflag;       // flags per sample in c.sync (host: sync_layout)
   int fused;       // MGACBAM_FWD_FUSE path selected for this level's group
   unsigned spin_limit;   // bound of every hand-off spin (knob MGACBAM_SPIN_LIMIT, default 2^20 ~ 1 s)
   int fault;       // fault injection for tests (knob MGACBAM_FAULT=1): sample 0's role workgroup never publishes ca

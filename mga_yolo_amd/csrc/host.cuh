@@ -63,8 +63,29 @@ static int check_shape(int B, int C, int H, int W, int hidden, int k) {
   return 0;
 }
 
-// hand-off flags per sample: one per tile of >= kSyncPx pixels, whatever tile size the launch geometry picks
-static size_t sync_flags(size_t HW) { return (HW + kSyncPx - 1) / kSyncPx + 1; }
+// The hand-off region of the ctx (CtxPtrs::sync), in ints from its start; every word is a generation counter.  nflag flags per sample: one
+// per tile of >= kSyncPx pixels, whatever tile size the launch geometry picks.  The merged backward launch (k_bwd_r12) has tile /
+// conv-tile flags of its OWN beside its dWsa-tile and sweep flags: every class of counters is bumped exactly once per launch of its
+// kind, so the two launch forms can alternate on one ctx without their counters drifting apart.  (_lib.sync_regions mirrors this.)
+struct SyncLayout {
+  size_t nflag;
+  size_t gate;               // [B][nflag] k_gate tile flags
+  size_t status;             // 4 status words, [0] = time-out
+  size_t ca;                 // [B] per-sample ca flags
+  size_t bflag, cflag;       // [B][nflag] k_bwd_reduce1 tile flags, [B][nflag] folded conv-tile flags
+  size_t mbflag, mcflag;     // the same two of the merged launch
+  size_t wflag, sflag;       // the merged launch's [B][nflag] dWsa-tile flags and [B][C] per-channel sweep flags
+  size_t len;
+};
+static SyncLayout sync_layout(int B, int C, size_t HW) {
+  SyncLayout S;
+  S.nflag = (HW + kSyncPx - 1) / kSyncPx + 1;
+  const size_t per = static_cast<size_t>(B) * S.nflag;
+  S.gate = 0; S.status = per; S.ca = S.status + 4; S.bflag = S.ca + B;
+  S.cflag = S.bflag + per; S.mbflag = S.cflag + per; S.mcflag = S.mbflag + per; S.wflag = S.mcflag + per; S.sflag = S.wflag + per;
+  S.len = S.sflag + static_cast<size_t>(B) * C;
+  return S;
+}
 
 static void ctx_layout(int B, int C, int H, int W, int hidden, mgacbam_ctx_layout_t* L) {
   const size_t HW = static_cast<size_t>(H) * W;
@@ -79,12 +100,9 @@ static void ctx_layout(int B, int C, int H, int W, int hidden, mgacbam_ctx_layou
   L->cidx = take(static_cast<size_t>(B) * HW);
   L->sa = take(static_cast<size_t>(B) * HW);
   L->proj = take(hidden <= MGACBAM_PROJ_MAX_HIDDEN ? static_cast<size_t>(B) * hidden * HW : 0);
-  // hand-off state: [B][nflag] k_gate tile flags, 4 status words, [B] ca flags, [B][nflag] k_bwd_reduce1 tile flags, [B][nflag] folded
-  // conv-tile flags; merged backward launch (k_bwd_r12): [B][nflag] tile, [B][nflag] conv-tile, [B][nflag] dWsa-tile and [B][C] per-channel sweep flags
-  // (the merged launch has tile / conv-tile flags of its OWN beside its dWsa-tile and sweep flags: every class of generation counters is
-  //  bumped exactly once per launch of its kind, so the two launch forms can alternate on one ctx without their counters drifting apart)
-  L->sync = take(6 * static_cast<size_t>(B) * sync_flags(HW) + 4 + B + static_cast<size_t>(B) * C);
-  L->status = L->sync + static_cast<int64_t>(4 * static_cast<size_t>(B) * sync_flags(HW));   // status word 0 (time-out) follows the k_gate tile flags
+  const SyncLayout S = sync_layout(B, C, HW);
+  L->sync = take(S.len);
+  L->status = L->sync + static_cast<int64_t>(4 * S.status);
   L->total = static_cast<int64_t>(o);
 }
 
@@ -257,10 +275,6 @@ static Tune choose_tune(int B, int C, int H, int W, int k) {
   int rows = (t.chan_tx * VEC - 1) / W + 2;
   if (rows > H) rows = H;
   t.apply_rows = rows + k - 1;
-  // k_gate (x-resident chan+apply): every thread keeps kGateR channels, so TY = ceil(C / kGateR) slices (power of two) and the
-  // rest of the 256 threads go along H*W.  Eligible when a tile is >= kSyncPx pixels (ctx.sync has one flag per kSyncPx) and >= one image row,
-  // the tiles a k x k window reaches are few (their workgroups must be co-resident: 8 ids apart per tile, common.cuh) and
-  // the staged rows fit in LDS; otherwise the three-launch forward runs.
   gate_geometry(C, H, W, k, VEC, t);
   return t;
 }
@@ -278,31 +292,13 @@ static int chan_tiles(const Tune& t, int H, int W, int vec) {
   return (nv + t.chan_tx - 1) / t.chan_tx;
 }
 
-struct ScratchLayout { size_t A_part, gpre, gplanes, gwsa_part, gz, gbq, gh_avg, gh_mx, pgh, total; };
-static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int k) {
-  // the tile counts follow the launch geometry, which follows the knobs
-  const Tune t = choose_tune(B, C, H, W, k);
-  const size_t HW = static_cast<size_t>(H) * W, BC = static_cast<size_t>(B) * C;
-  const size_t nt = chan_tiles(t, H, W, vec_of(H, W)), nconv = static_cast<size_t>(B) * wsa_tiles(t, H, W);
-  ScratchLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n_elems) { size_t at = o; o = align16(o + n_elems * 4); return at; };
-  L.A_part = take(2 * BC * nt);                          // tile partials of A and Q live together: (B, nt, 2, C)
-  L.gpre = take(B * HW); L.gplanes = take(static_cast<size_t>(B) * 3 * HW);
-  L.gwsa_part = take(nconv * 3 * k * k);
-  L.gz = take(BC); L.gbq = take(BC);
-  L.gh_avg = take(static_cast<size_t>(B) * hidden); L.gh_mx = take(static_cast<size_t>(B) * hidden);
-  const size_t ty = kBlock / t.pool_tx;                               // channel groups per sample, worst case (1 channel per row)
-  L.pgh = take(static_cast<size_t>(B) * ((C + ty - 1) / ty) * hidden);
-  L.total = o;
-  return L;
-}
-
 // ------------------------------------------------------------------------------------------------
 // channels-last levels (MGACBAM_LAYOUT_NHWC, nhwc.cuh): chunk geometry and work buffers, functions of the level alone
 // ------------------------------------------------------------------------------------------------
 // elements per lane along C: 16 B when C allows it (fp32: 4, fp16 / bf16: 8), else 4 or scalar
 static int nhwc_vec(int C, int dtype) { return (dtype != MGACBAM_F32 && C % 8 == 0) ? 8 : (C % 4 == 0 ? 4 : 1); }
+// a level's vector width: along H*W for NCHW levels, along C for NHWC levels
+static int level_vec(bool nhwc, int C, int H, int W, int dtype) { return nhwc ? nhwc_vec(C, dtype) : vec_of(H, W); }
 static NhwcGeo nhwc_geo(int C, int H, int W, int vec) {
   NhwcGeo n;
   n.ng = (C + vec - 1) / vec;
@@ -318,30 +314,42 @@ static NhwcGeo nhwc_geo(int C, int H, int W, int vec) {
 static size_t nhwc_ws_bytes(int B, int C, int H, int W, int vec) {
   return static_cast<size_t>(B) * nhwc_geo(C, H, W, vec).nchunk * (4 * static_cast<size_t>(C) + 4) * sizeof(float);
 }
-static ScratchLayout nhwc_scratch_layout(int B, int C, int H, int W, int hidden, int k, int vec) {
-  const Tune t = choose_tune(B, C, H, W, k);                  // (only its conv tiling, which does not depend on B, is used)
-  const NhwcGeo n = nhwc_geo(C, H, W, vec);
+
+// backward scratch of a level of either layout (vec: level_vec); the two layouts differ in the partials of A_part and pgh
+struct ScratchLayout { size_t A_part, gpre, gplanes, gwsa_part, gz, gbq, gh_avg, gh_mx, pgh, total; };
+static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int k, bool nhwc, int vec) {
+  // the tile counts follow the launch geometry, which follows the knobs (NHWC: only the conv tiling, which does not depend on B, is used)
+  const Tune t = choose_tune(B, C, H, W, k);
   const size_t HW = static_cast<size_t>(H) * W, BC = static_cast<size_t>(B) * C;
-  const size_t nwsa = static_cast<size_t>(B) * wsa_tiles(t, H, W), ncb = (C + kNhwcFoldC - 1) / kNhwcFoldC;
+  const size_t nwsa = static_cast<size_t>(B) * wsa_tiles(t, H, W);
   ScratchLayout L;
   size_t o = 0;
   auto take = [&](size_t n_elems) { size_t at = o; o = align16(o + n_elems * 4); return at; };
-  L.A_part = take(3 * BC * n.nchunk);                          // (B, nchunk, 3, C): A, D, sum x*wgt
+  // NCHW: tile partials of A and Q live together, (B, nt, 2, C); NHWC: (B, nchunk, 3, C) = A, D, sum x*wgt
+  L.A_part = take(nhwc ? 3 * BC * nhwc_geo(C, H, W, vec).nchunk : 2 * BC * chan_tiles(t, H, W, vec));
   L.gpre = take(B * HW); L.gplanes = take(static_cast<size_t>(B) * 3 * HW);
   L.gwsa_part = take(nwsa * 3 * k * k);
   L.gz = take(BC); L.gbq = take(BC);
   L.gh_avg = take(static_cast<size_t>(B) * hidden); L.gh_mx = take(static_cast<size_t>(B) * hidden);
-  L.pgh = take(static_cast<size_t>(B) * ncb * hidden);
+  // channel groups per sample -- NCHW: worst case (1 channel per row of the sweep kernels), NHWC: blocks of kNhwcFoldC
+  const size_t cpg = nhwc ? kNhwcFoldC : kBlock / t.pool_tx;
+  L.pgh = take(static_cast<size_t>(B) * ((C + cpg - 1) / cpg) * hidden);
   L.total = o;
   return L;
 }
-// the size queries take no element type: the answer covers every one
-static size_t nhwc_ws_bytes_any(int B, int C, int H, int W) {
+static ScratchPtrs scratch_ptrs(void* base, const ScratchLayout& L) {
+  char* p = static_cast<char*>(base);
+  auto at = [&](size_t off) { return reinterpret_cast<float*>(p + off); };
+  return ScratchPtrs{at(L.A_part), at(L.gpre), at(L.gplanes), at(L.gwsa_part), at(L.gz), at(L.gbq), at(L.gh_avg), at(L.gh_mx), at(L.pgh)};
+}
+// the size queries take no element type: the answer covers every one (the NCHW geometry does not depend on it)
+static size_t ws_bytes_any(int B, int C, int H, int W, bool nhwc) {
+  if (!nhwc) return 0;
   return std::max(nhwc_ws_bytes(B, C, H, W, nhwc_vec(C, MGACBAM_F32)), nhwc_ws_bytes(B, C, H, W, nhwc_vec(C, MGACBAM_F16)));
 }
-static size_t nhwc_scratch_bytes_any(int B, int C, int H, int W, int hidden, int k) {
-  return std::max(nhwc_scratch_layout(B, C, H, W, hidden, k, nhwc_vec(C, MGACBAM_F32)).total,
-                  nhwc_scratch_layout(B, C, H, W, hidden, k, nhwc_vec(C, MGACBAM_F16)).total);
+static size_t scratch_bytes_any(int B, int C, int H, int W, int hidden, int k, bool nhwc) {
+  return std::max(scratch_layout(B, C, H, W, hidden, k, nhwc, level_vec(nhwc, C, H, W, MGACBAM_F32)).total,
+                  scratch_layout(B, C, H, W, hidden, k, nhwc, level_vec(nhwc, C, H, W, MGACBAM_F16)).total);
 }
 
 // ABI 14: every work buffer travels with its capacity; the requirement is recomputed under the CURRENT knobs at every call
@@ -367,16 +375,13 @@ static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintp
     else if ((dtype) == MGACBAM_F16) { if ((VECV) == 4) { CALL(__half, 4); } else { CALL(__half, 1); } }  \
     else { if ((VECV) == 4) { CALL(bf16_t, 4); } else { CALL(bf16_t, 1); } }                              \
   } while (0)
-// T x VEC of k_gate alone (Sig::gvec): fp16 / bf16 also 8
-#define DISPATCH_T_GVEC(dtype, VECV, CALL)                                                                                          \
+// T x VEC of k_gate (Sig::gvec) and of the NHWC kernels (nhwc_vec): fp16 / bf16 also 8
+#define DISPATCH_T_VEC8(dtype, VECV, CALL)                                                                                          \
   do {                                                                                                                              \
     if ((dtype) == MGACBAM_F32) { if ((VECV) == 4) { CALL(float, 4); } else { CALL(float, 1); } }                                    \
     else if ((dtype) == MGACBAM_F16) { if ((VECV) == 8) { CALL(__half, 8); } else if ((VECV) == 4) { CALL(__half, 4); } else { CALL(__half, 1); } } \
     else { if ((VECV) == 8) { CALL(bf16_t, 8); } else if ((VECV) == 4) { CALL(bf16_t, 4); } else { CALL(bf16_t, 1); } }          \
   } while (0)
-
-// T x VEC of the NHWC kernels (nhwc_vec): fp16 / bf16 also 8
-#define DISPATCH_T_NVEC(dtype, VECV, CALL) DISPATCH_T_GVEC(dtype, VECV, CALL)
 
 #define DISPATCH_CPT(CPTV, CALL2)                                              \
   do { if ((CPTV) == 4) { CALL2(4); } else if ((CPTV) == 2) { CALL2(2); } else { CALL2(1); } } while (0)
@@ -394,6 +399,32 @@ static int check_params(const mgacbam_params_t& p) {
   return 0;
 }
 
+// What a MaskCBAM level of either direction and layout is checked for after its pointers, and the part of its kernel arguments that
+// does not depend on direction or layout (Level: mgacbam_fwd_level_t / mgacbam_bwd_level_t, Args: FwdArgs / BwdArgs)
+template <typename Level>
+static int check_level(const char* what, const Level& L) {
+  if (int e = check_params(L.p)) return e;
+  if (int e = check_shape(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k)) return e;
+  if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "%s: dtype %d", what, L.dtype);
+  return 0;
+}
+template <typename Level>
+static int check_ctx_capacity(const char* what, const Level& L) {
+  mgacbam_ctx_layout_t CL;
+  ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, &CL);
+  return check_capacity(what, "ctx", static_cast<size_t>(CL.total), L.ctx_bytes);
+}
+template <typename Level, typename Args>
+static void level_setup(const Level& L, Args& A) {
+  A.c = ctx_ptrs(const_cast<void*>(static_cast<const void*>(L.ctx)), L.B, L.C, L.H, L.W, L.p.hidden);
+  A.p = make_params(L.p);
+  A.g = make_geo(L.B, L.C, L.H, L.W, L.p);
+  A.t = choose_tune(L.B, L.C, L.H, L.W, L.p.k);
+  A.nflag = static_cast<int>(sync_layout(L.B, L.C, static_cast<size_t>(L.H) * L.W).nflag);
+  const Knobs kn = knobs();
+  A.trace = kn.trace; A.spin_limit = kn.spin_limit;
+}
+
 // Levels that share every compile-time property of the kernels (element type, vector width, mask / no mask,
 // conv size, dL/dmask wanted) are launched together: one grid per stage, the levels' grids concatenated.
 struct Sig {
@@ -404,6 +435,8 @@ struct Sig {
   int gvec = 0;   // forward only: elements per lane of k_gate for this level -- a function of the LEVEL alone (dtype, shape, k, knobs), never of
                   // the levels it happens to be called with: the hand-off flags in ctx.sync count calls per TILE, so a ctx must see the same
                   // tiling in every call whatever the group composition (levels of different gvec go to different launches)
+  int weight = 0; // not part of the signature: ~ how long a workgroup of the level runs (C x channels per thread of the tile kernels where the
+                  // family has them, else C), set by the *_args functions; for_each_group launches the levels of a group longest first
   bool operator==(const Sig& o) const {
     return dtype == o.dtype && vec == o.vec && has_mask == o.has_mask && k == o.k && gmask == o.gmask && proj == o.proj && gvec == o.gvec && lf32 == o.lf32 && nhwc == o.nhwc && cvec == o.cvec;
   }
@@ -461,10 +494,27 @@ static int gate_tiles(const Tune& t, int H, int W, int vec) {
 }
 static size_t bwd_apply_smem(const Geo& g, int vec) { return (5 * static_cast<size_t>(g.C) + 2 * g.hidden + kBlock * vec) * sizeof(float); }
 static size_t reduce1_smem(const Geo& g, int vec) { return (3 * static_cast<size_t>(g.C) + kBlock * vec) * sizeof(float); }
+static size_t mlp_smem(const Geo& g) { return (3 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }
+// their NHWC siblings (n: nhwc_geo of the level)
+static size_t nhwc_pool_smem(const Geo& g) { return 4 * static_cast<size_t>(g.C) * sizeof(float); }
+static size_t nhwc_chan_smem(const Geo& g) { return static_cast<size_t>(g.C) * sizeof(float); }
+static size_t nhwc_apply_smem(const Geo& g, const Tune& t, const NhwcGeo& n) {
+  return (((3 * g.k * g.k + 3) & ~3) + 3 * static_cast<size_t>(t.apply_rows) * (g.W + g.k - 1) + n.ch + g.C) * sizeof(float);
+}
+static size_t nhwc_reduce1_smem(const Geo& g, int vec) {
+  return (3 * ((static_cast<size_t>(g.C) + 3) & ~static_cast<size_t>(3)) + 2 * kBlock * vec) * sizeof(float);
+}
+static size_t nhwc_reduce2_smem(const Geo& g) { return static_cast<size_t>(g.C) * sizeof(float); }
+static size_t nhwc_bwd_apply_smem(const Geo& g) { return (5 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }
 
-// ~ how long a workgroup of the level runs (channels per thread of the tile kernels); levels are launched longest first
-template <typename A> static auto level_weight(const A& a, int) -> decltype(a.t.chan_tx, 0) { return a.g.C * a.t.chan_tx; }
-template <typename A> static int level_weight(const A& a, long) { return a.g.C; }
+// concatenate the levels' grids: workgroup ids [start[l], start[l+1]) of the launch belong to level l; returns the grid
+template <typename Args, typename Fn>
+static int fill_starts(Group<Args>& G, const Args* lv, int n, Fn blocks_of) {
+  int tot = 0;
+  for (int l = 0; l < n; ++l) { G.start[l] = tot; tot += blocks_of(lv[l]); }
+  G.start[n] = tot;
+  return tot;
+}
 
 // partition the levels into launch groups (same signature, at most kGroupMax levels) and run `run` on each
 template <typename Args, typename Run>
@@ -472,11 +522,12 @@ static int for_each_group(Args* args, const Sig* sigs, int n, Run run) {
   bool done[MGACBAM_MAX_LEVELS] = {false};
   for (int l = 0; l < n; ++l) {
     if (done[l]) continue;
-    Args grp[kGroupMax];
-    int m = 0;
+    int idx[kGroupMax], m = 0;
     for (int j = l; j < n && m < kGroupMax; ++j)
-      if (!done[j] && sigs[j] == sigs[l]) { grp[m++] = args[j]; done[j] = true; }
-    std::stable_sort(grp, grp + m, [](const Args& a, const Args& b) { return level_weight(a, 0) > level_weight(b, 0); });
+      if (!done[j] && sigs[j] == sigs[l]) { idx[m++] = j; done[j] = true; }
+    std::stable_sort(idx, idx + m, [&](int a, int b) { return sigs[a].weight > sigs[b].weight; });
+    Args grp[kGroupMax];
+    for (int j = 0; j < m; ++j) grp[j] = args[idx[j]];
     if (int e = run(grp, m, sigs[l])) return e;
   }
   return 0;

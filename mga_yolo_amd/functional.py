@@ -379,10 +379,7 @@ def ctx_views(cbuf: torch.Tensor, B, Cc, H, W, hidden) -> dict:
                   h_avg=(B, hidden), h_mx=(B, hidden), ca=(B, Cc), planes=(B, 3, HW), cidx=(B, HW), sa=(B, HW))
     if hidden <= _lib.PROJ_MAX_HIDDEN:
         shapes["proj"] = (B, hidden, HW)
-    nflag = (HW + 15) // 16 + 1
-    # hand-off state: (B, nflag) k_gate flags, [time-out status, 3 spare], (B) ca flags, (B, nflag) BWD_FOLD tile flags, (B, nflag) conv-tile flags,
-    # then the merged backward launch's own (B, nflag) tile, conv-tile and dWsa-tile flags and (B, C) sweep flags
-    shapes["sync"] = (6 * B * nflag + 4 + B + B * Cc,)
+    shapes["sync"] = (_lib.sync_len(B, Cc, H, W),)          # hand-off state: _lib.sync_regions
     ints = {"valid", "amax", "cidx", "sync"}
     out = {}
     for name, shp in shapes.items():

@@ -106,7 +106,7 @@ class PyramidPlan:
         if not self.fuse_forward:
             return False
         torch.cuda.synchronize(self.device)
-        return all(int(self.ctx_view(l)["sync"][:Bn * ((H * W + 15) // 16 + 1)].max()) != 0 for l, (Bn, C, H, W) in enumerate(self.shapes))
+        return all(int(self.ctx_view(l)["sync"][_lib.sync_slices(*shp)["gate"]].max()) != 0 for l, shp in enumerate(self.shapes))
 
     def fold_active(self) -> bool:
         """True when MGACBAM_BWD_FOLD really folds the transposed conv into the k_bwd_reduce1 launch for these shapes (the library
@@ -118,9 +118,8 @@ class PyramidPlan:
         def counters():
             torch.cuda.synchronize(self.device)
             out = []
-            for l, (Bn, C, H, W) in enumerate(self.shapes):
-                nf = Bn * ((H * W + 15) // 16 + 1)
-                out.append(self.ctx_view(l)["sync"][nf + 4 + Bn:nf + 4 + Bn + nf].clone())
+            for l, shp in enumerate(self.shapes):
+                out.append(self.ctx_view(l)["sync"][_lib.sync_slices(*shp)["tiles"]].clone())
             return out
         self.forward()
         before = counters()

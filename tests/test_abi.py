@@ -70,6 +70,9 @@ def test_ctx_layout_is_packed_aligned_and_ordered(built_lib, shape):
     sizes = dict(S=B, use=B, den=B, avg=B * Cc, mx=B * Cc, mavg=B * Cc, valid=B * Cc, amax=B * Cc, h_avg=B * hid, h_mx=B * hid,
                  ca=B * Cc, planes=B * 3 * H * W, cidx=B * H * W, sa=B * H * W,
                  proj=B * hid * H * W if hid <= _lib.PROJ_MAX_HIDDEN else 0, sync=6 * B * ((H * W + 15) // 16 + 1) + 4 + B + B * Cc)
+    # the Python description of the hand-off region (_lib.sync_regions) agrees with the library's
+    assert lay["status"] == lay["sync"] + 4 * _lib.sync_regions(B, Cc, H, W)["status"][0]
+    assert (lay["sync"] + 4 * _lib.sync_len(B, Cc, H, W) + 15) // 16 * 16 == lay["total"]
     prev_end = 0
     for n in order:
         assert lay[n] % 16 == 0 and lay[n] >= prev_end, n

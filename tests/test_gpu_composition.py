@@ -85,6 +85,7 @@ def test_sweep_generations_count_merged_launches_under_any_composition(F, widths
     """P3 alone / P3+P4+P5 / P3 alone (or the reverse) on ONE pooled ctx: afterwards the generation every sweep of the next merged
     launch derives -- under either channel grouping -- must be 3, the number of merged launches the ctx has seen.  A counter per
     channel group lags wherever a grouping with fewer groups ran, and the next sweep of such a group stops waiting at once."""
+    from mga_yolo_amd import _lib
     shapes = LEVELS[widths]
     params = _params(shapes)
     B, C, H, W = shapes[0]
@@ -103,11 +104,10 @@ def test_sweep_generations_count_merged_launches_under_any_composition(F, widths
         ptr = free[0].data_ptr()
     F.handoff_report()
     sync = F.ctx_views(F._POOL.free[key][0], B, C, H, W, hidden)["sync"].cpu()
-    nf = B * ((H * W + 15) // 16 + 1)
-    o = nf + 4 + B
-    tiles = sync[o + 2 * nf:o + 3 * nf]
+    r = _lib.sync_slices(B, C, H, W)
+    tiles = sync[r["merged_tiles"]]
     assert int(tiles.max()) == 3, "the backward did not run as the merged launch three times"
-    sweeps = sync[o + 5 * nf:o + 5 * nf + B * C].reshape(B, C)
+    sweeps = sync[r["sweeps"]].reshape(B, C)
     for name, cpb in (("alone", cpb_single), ("grouped", cpb_group)):
         gen = sweeps[:, ::cpb]                                   # a sweep of channel group cg reads the counter of channel cg * cpb
         lag = (gen != 3).nonzero().tolist()

@@ -377,6 +377,7 @@ def test_fused_forward_launch_equals_three_launches(F, shapes, with_mask, fused,
 
 
 def _fused_vs_three(F, PyramidPlan, shapes, with_mask, fused):
+    from mga_yolo_amd import _lib
     params, cfgs = [], []
     for l, (B, C, H, W) in enumerate(shapes):
         p = O.Params.default_init(C, seed=l)
@@ -406,12 +407,11 @@ def _fused_vs_three(F, PyramidPlan, shapes, with_mask, fused):
                     assert torch.equal(a[name], b[name]), (calls, l, name)
                 else:
                     assert rel_err(b[name], a[name]) < 1e-6, (calls, l, name)
-            sync = b["sync"]
-            nf = B * ((H * W + 15) // 16 + 1)
-            assert int(sync[nf:nf + 4].abs().sum()) == 0, (calls, l, "hand-off timed out")
-            assert bool((sync[nf + 4:nf + 4 + B] == (calls if fused else 0)).all()), (calls, l, "per-sample ca flags")
-            assert int(sync[nf + 4 + B:].abs().sum()) == 0, (calls, l, "no backward ran: its counters are untouched")
-            flags = sync[:nf]
+            sync, r = b["sync"], _lib.sync_slices(B, C, H, W)
+            assert int(sync[r["status"]].abs().sum()) == 0, (calls, l, "hand-off timed out")
+            assert bool((sync[r["ca"]] == (calls if fused else 0)).all()), (calls, l, "per-sample ca flags")
+            assert int(sync[r["tiles"].start:].abs().sum()) == 0, (calls, l, "no backward ran: its counters are untouched")
+            flags = sync[r["gate"]]
             want = calls if fused else 0                                    # ineligible groups never touch the flags
             assert int(flags.max()) == want and set(flags.unique().tolist()) <= {0, want}, (calls, l)
 
@@ -465,6 +465,7 @@ def test_fused_forward_half_precision(F, shapes, dtype, tol):
 
 def test_fused_forward_generation_flags_wrap_around(F):
     """The hand-off flags count fused calls for the life of ctx; the compare is modulo 2^32, so crossing INT32_MAX is harmless."""
+    from mga_yolo_amd import _lib
     from mga_yolo_amd.plan import PyramidPlan
     shapes = [(5, 64, 24, 24), (5, 128, 12, 12)]
     params, cfgs = [], []
@@ -480,10 +481,9 @@ def test_fused_forward_generation_flags_wrap_around(F):
             pl.x[l].copy_(x); pl.mask[l].copy_(m)
     plans[0].forward()
     for l, (B, C, H, W) in enumerate(shapes):
-        sync = plans[1].ctx_view(l)["sync"]
-        nf = B * ((H * W + 15) // 16 + 1)
-        sync[:nf] = 0x7FFFFFFE                      # every flag two calls before the wrap (as after 2^31 - 2 fused calls)
-        sync[nf + 4:nf + 4 + B] = 0x7FFFFFFE
+        sync, r = plans[1].ctx_view(l)["sync"], _lib.sync_slices(B, C, H, W)
+        sync[r["gate"]] = 0x7FFFFFFE                # every flag two calls before the wrap (as after 2^31 - 2 fused calls)
+        sync[r["ca"]] = 0x7FFFFFFE
     for rep in range(4):
         for l in range(len(shapes)):
             plans[1].y[l].zero_()
@@ -492,8 +492,7 @@ def test_fused_forward_generation_flags_wrap_around(F):
         for l, (B, C, H, W) in enumerate(shapes):
             assert rel_err(plans[1].y[l], plans[0].y[l]) < 1e-6, (rep, l)
             sync = plans[1].ctx_view(l)["sync"]
-            nf = B * ((H * W + 15) // 16 + 1)
-            assert int(sync[nf:nf + 4].abs().sum()) == 0, (rep, l, "hand-off timed out")
+            assert int(sync[_lib.sync_slices(B, C, H, W)["status"]].abs().sum()) == 0, (rep, l, "hand-off timed out")
     want = (0x7FFFFFFE + 4) - (1 << 32)
     assert int(plans[1].ctx_view(0)["sync"][0]) == want
 
@@ -763,16 +762,14 @@ def test_fold_counters_survive_a_half_finished_backward(F):
     for a, b in zip(plan.gx + plan.gmask + [plan.grad_bucket], ref.gx + ref.gmask + [ref.grad_bucket]):
         assert torch.equal(a, b)
     for l, (Bn, C, H, W) in enumerate(plan.shapes):
-        nf = Bn * ((H * W + 15) // 16 + 1)
-        sync = plan.ctx_view(l)["sync"]
-        o = nf + 4 + Bn
-        tiles, convs = sync[o:o + nf], sync[o + nf:o + 2 * nf]
+        sync, r = plan.ctx_view(l)["sync"], _lib.sync_slices(Bn, C, H, W)
+        tiles, convs = sync[r["tiles"]], sync[r["conv_tiles"]]
         assert set(tiles.unique().tolist()) <= {0, 4} and int(tiles.max()) == 4      # fold_active's launch + 3 folded launches
         assert set(convs.unique().tolist()) <= {0, 4} and int(convs.max()) == 4
         # the full backward ran as the MERGED launch (k_bwd_r12), which counts in generation counters of its own -- one class per kind
         # of workgroup, each bumped exactly once per merged launch -- so the two launch forms can alternate on one ctx
-        for name, blk in (("tiles", sync[o + 2 * nf:o + 3 * nf]), ("conv tiles", sync[o + 3 * nf:o + 4 * nf]),
-                          ("dWsa tiles", sync[o + 4 * nf:o + 5 * nf]), ("sweeps", sync[o + 5 * nf:])):
+        for name, blk in (("tiles", sync[r["merged_tiles"]]), ("conv tiles", sync[r["merged_conv_tiles"]]),
+                          ("dWsa tiles", sync[r["wsa_tiles"]]), ("sweeps", sync[r["sweeps"]])):
             assert set(blk.unique().tolist()) <= {0, 1} and int(blk.max()) == 1, (l, name)
     plan.forward(); plan.backward()                       # and once more: merged generation 2 next to fold generation 4
     ref.forward(); ref.backward()

@@ -6,6 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 import bench
+from mga_yolo_amd import _lib
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
 plan, desc, batch = bench.make_plan("cfg2", torch.device("cuda", 0), seed=1, dtype_name="f32")
@@ -24,12 +25,12 @@ for a, b in zip(ref, list(plan.y) + list(plan.gx) + [plan.grad_bucket]):
     ok &= bool(torch.equal(a, b))
 for l, (B, C, H, W) in enumerate(plan.shapes):
     s = plan.ctx_view(l)["sync"]
-    nf = B * ((H * W + 15) // 16 + 1)
-    flags = s[:nf]
+    r = _lib.sync_slices(B, C, H, W)
+    flags = s[r["gate"]]
     calls = int(flags.max())
-    ok &= int(s[nf:nf + 4].abs().sum()) == 0 and set(flags.unique().tolist()) <= {0, calls}
-    bw = s[nf + 4 + B:]                                             # MGACBAM_BWD_FOLD's tile / conv-tile counters: one bump per folded launch
+    ok &= int(s[r["status"]].abs().sum()) == 0 and set(flags.unique().tolist()) <= {0, calls}
+    bw = s[r["tiles"].start:]                                       # every backward counter: one bump per launch of its kind
     ok &= set(bw.unique().tolist()) <= {0, int(bw.max())}
-    print(f"level {l}: fused calls {calls}, status words {s[nf:nf + 4].tolist()}")
+    print(f"level {l}: fused calls {calls}, status words {s[r['status']].tolist()}")
 print("soak:", "OK" if ok else "FAILED")
 sys.exit(0 if ok else 1)
