@@ -25,9 +25,12 @@ __global__ __launch_bounds__(kBlock) void k_pmg_fwd(const GaterArgs A) {
     float p = fminf(fmaxf(A.p[i], 0.f), 1.f);
     if (A.p_min > 0.f) p = fmaxf(p, A.p_min);
     const float a = fminf(fmaxf(A.u1[i], kGateEps), 1.f - kGateEps), b = fminf(fmaxf(A.u2[i], kGateEps), 1.f - kGateEps);
-    const float g = -logf(-logf(a)) + logf(-logf(b));                       // logistic noise
     const float q = fminf(fmaxf(p, kGateEps), 1.f - kGateEps);
-    const float z = (logf(q) - log1pf(-q) + g) * A.inv_tau;
+    // logit(q) + g, g = -log(-log a) + log(-log b) (logistic noise), as ONE logarithm of q (-log b) / ((1 - q) (-log a)).  The four
+    // terms reach 13.8 each and cancel where m is mid-range: summed in fp32 they carry about 1e-6 of rounding, which 1 / tau = 3.3
+    // turns into 1e-6 of m; the quotient carries four relative roundings (3e-7) whatever the terms' size.  1 - q is exact for
+    // q >= 0.5 and never below 1e-6; the quotient stays within 1e-14 .. 1e14.
+    const float z = logf((q * -logf(b)) / ((1.f - q) * -logf(a))) * A.inv_tau;
     const float m = 1.f / (1.f + expf(-z));
     A.msoft[i] = m;
     A.out[i] = A.hard ? (m > A.threshold ? 1.f : 0.f) : m;
