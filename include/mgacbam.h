@@ -35,11 +35,15 @@ extern "C" {
 
 enum { MGACBAM_F32 = 0, MGACBAM_F16 = 1, MGACBAM_BF16 = 2 };
 
-/* Level flags.  The forward can save P[b,j,hw] = sum_c W1[j,c] x[b,c,hw] (hidden <= MGACBAM_PROJ_MAX_HIDDEN planes per sample)
- * while it streams x anyway; the backward then forms the masked-average part of dL/dmask, sum_c g_avg[b,c] x[b,c,hw] =
- * sum_j g_h[b,j] P[b,j,hw], from those planes and its largest kernel does not read x at all (3 -> 2 feature-sized streams).
- * Set MGACBAM_FWD_SAVE_PROJ in the forward of a step whose backward will ask for gmask, and MGACBAM_BWD_HAVE_PROJ in that
- * backward.  Levels with a larger hidden size ignore the flags and read x. */
+/* W1-projection planes.  P[b,j,hw] = sum_c W1[j,c] x[b,c,hw] (hidden <= MGACBAM_PROJ_MAX_HIDDEN planes per sample) lets the backward
+ * form the masked-average part of dL/dmask, sum_c g_avg[b,c] x[b,c,hw] = sum_j g_h[b,j] P[b,j,hw], without its largest kernel reading
+ * x (3 -> 2 feature-sized streams for that level).  The BACKWARD makes the planes itself: for every fp32 NCHW level with gmask != NULL
+ * and hidden <= MGACBAM_PROJ_MAX_HIDDEN (and C up to ~1,700) the MGACBAM_BWD_REDUCE1 stage writes them into ctx.proj while it streams
+ * x, and the MGACBAM_BWD_APPLY stage reads them instead of x (fp16 / bf16 levels keep reading x: there the planes measured slower).  The rule depends on the level alone, never on the other levels of a call
+ * or on the stages a call runs, so REDUCE1 in one call and APPLY in a later call on the same ctx agree.  No flag is needed.
+ * MGACBAM_FWD_SAVE_PROJ makes the forward's fallback kernel (k_chan) save the same planes (it disables MGACBAM_FWD_FUSE for the
+ * level's group); MGACBAM_BWD_HAVE_PROJ tells the backward that it did, and the REDUCE1 stage then leaves ctx.proj alone.  Levels
+ * with a larger hidden size ignore both flags and read x. */
 #define MGACBAM_PROJ_MAX_HIDDEN 4
 enum { MGACBAM_FWD_SAVE_PROJ = 1 };
 enum { MGACBAM_BWD_HAVE_PROJ = 1 };

@@ -31,6 +31,7 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
   A.nwsa = A.g.B * wsa_tiles(A.t, A.g.H, A.g.W);
   A.npg = params_blocks(A.g);
   A.merged = 0;
+  A.make_proj = 0;
   A.vec = VEC;
   sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, L.gmask != nullptr, 0};
   if (nhwc) {
@@ -39,7 +40,7 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
     A.nt = N.n.nchunk;
     A.ncg = N.ncb;
     A.bflag0 = A.cflag0 = A.mbflag0 = A.mcflag0 = A.wflag0 = A.sflag0 = 0;   // (no in-launch hand-off on this path)
-    sig.nhwc = 1;                                                 // (HAVE_PROJ is ignored: the NHWC apply reads x for dL/dmask)
+    sig.nhwc = 1;                                                 // (no projection planes, HAVE_PROJ is ignored: the NHWC apply reads x for dL/dmask)
     sig.weight = L.C;
     return 0;
   }
@@ -50,8 +51,18 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
   A.mbflag0 = static_cast<int>(S.mbflag); A.mcflag0 = static_cast<int>(S.mcflag);
   A.wflag0 = static_cast<int>(S.wflag); A.sflag0 = static_cast<int>(S.sflag);
   sig.weight = L.C * A.t.chan_tx;
-  sig.proj = (L.flags & MGACBAM_BWD_HAVE_PROJ) && L.gmask != nullptr;
-  A.g.proj_h = (sig.proj && L.p.hidden <= MGACBAM_PROJ_MAX_HIDDEN) ? L.p.hidden : 0;
+  // dL/dmask from the W1-projection planes (bwd.cuh): a property of the LEVEL alone -- gmask wanted (which implies a mask), a hidden
+  // width the ctx has planes for, and either planes the caller's forward saved (MGACBAM_BWD_HAVE_PROJ) or an fp32 level, whose
+  // k_bwd_reduce1 tiles then write them -- so a call that runs REDUCE1 and a later call that runs APPLY on the same ctx agree, whatever
+  // other levels share either call.  fp32 only: at config 2 with bf16 / fp16 features the tiles lose more than k_bwd_apply gains
+  // (step 0.1382 -> 0.1396 ms and 0.1519 -> 0.1547 ms, three interleaved pairs each), so those levels keep reading x.
+  // (W1^T of the level must fit beside the tiles' combine buffer in the LDS every launch may ask for: C up to ~1,700.)
+  // sig.proj follows "gmask wanted" only: the levels of a pyramid stay ONE launch group whichever of them qualify.
+  const bool have = (L.flags & MGACBAM_BWD_HAVE_PROJ) != 0;
+  const bool make = !have && L.dtype == MGACBAM_F32 && reduce1_smem(A.g, VEC, true) <= 64 * 1024;
+  sig.proj = L.gmask != nullptr;
+  A.g.proj_h = (L.gmask && L.p.hidden <= MGACBAM_PROJ_MAX_HIDDEN && (have || make)) ? L.p.hidden : 0;
+  A.make_proj = A.g.proj_h > 0 && make;
   return 0;
 }
 
@@ -116,6 +127,10 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
     fold = TP >= kSyncPx && TP >= lv[l].g.W && 8 * (((lv[l].t.conv_th + lv[l].g.k) * lv[l].g.W + TP - 1) / TP + 1) <= 512 &&
            lv[l].nconv <= lv[l].g.B * lv[l].nflag;                 // one flag per conv tile fits the region reserved in ctx.sync
   }
+  // the plane-making instantiation of the tile kernels only where some level of the group makes planes: every other group runs the
+  // kernels it ran before the planes moved into the backward
+  bool mkproj = false;
+  for (int l = 0; l < n; ++l) mkproj = mkproj || lv[l].make_proj;
   // k_bwd_r12: the folded launch AND k_bwd_reduce2 with its dWsa roles as one launch (bwd.cuh), when both stages are in this call
   const bool fuse = (stages & MGACBAM_BWD_FUSE) != 0;
   bool merge = fold && fuse && (stages & MGACBAM_BWD_REDUCE2) && (stages & MGACBAM_BWD_WSA) && sig.k == 7 && knobs().bwd_merge;
@@ -127,7 +142,7 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
     for (int l = 0; l < n; ++l) {
       lv[l].merged = 1; lv[l].bflag0 = lv[l].mbflag0; lv[l].cflag0 = lv[l].mcflag0;
       R.g.lv[l] = lv[l];
-      smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec), convT_smem(lv[l].t, sig.k), wsa_smem(lv[l].t, sig.k),
+      smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec, lv[l].make_proj), convT_smem(lv[l].t, sig.k), wsa_smem(lv[l].t, sig.k),
                        reduce2_smem(lv[l].t)});
     }
     int tot = 0;
@@ -139,7 +154,7 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
       R.seg[p][n] = tot;
     }
     const int grid = tot;
-#define CALL_R12B(CPTV) LAUNCH((k_bwd_r12<TT, VV, CPTV>), grid, smem, st, R)
+#define CALL_R12B(CPTV) if (mkproj) LAUNCH((k_bwd_r12<TT, VV, CPTV, true>), grid, smem, st, R); else LAUNCH((k_bwd_r12<TT, VV, CPTV, false>), grid, smem, st, R)
 #define CALL_R12(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_R12B); }
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R12);
 #undef CALL_R12
@@ -149,18 +164,20 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
   }
   if (fold && !merge) {
     size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec), convT_smem(lv[l].t, sig.k)});
+    for (int l = 0; l < n; ++l) smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec, lv[l].make_proj), convT_smem(lv[l].t, sig.k)});
     const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt) + pad8(a.nconv); });
-#define CALL_R1F(Tt, Vv) if (sig.k == 7) LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 7>), grid, smem, st, G); else LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 0>), grid, smem, st, G)
+#define CALL_R1F2(Tt, Vv, PJ) if (sig.k == 7) LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 7, PJ>), grid, smem, st, G); else LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 0, PJ>), grid, smem, st, G)
+#define CALL_R1F(Tt, Vv) if (mkproj) { CALL_R1F2(Tt, Vv, true); } else { CALL_R1F2(Tt, Vv, false); }
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R1F);
 #undef CALL_R1F
+#undef CALL_R1F2
     if (int e = launch_status("k_bwd_reduce1_fold")) return e;
   }
   if ((stages & MGACBAM_BWD_REDUCE1) && !fold) {  // 1. per-(b,c) and per-pixel reductions of gy*x
     size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, reduce1_smem(lv[l].g, sig.vec));
+    for (int l = 0; l < n; ++l) smem = std::max(smem, reduce1_smem(lv[l].g, sig.vec, lv[l].make_proj));
     const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt); });
-#define CALL_R1(Tt, Vv) LAUNCH((k_bwd_reduce1<Tt, Vv>), grid, smem, st, G)
+#define CALL_R1(Tt, Vv) if (mkproj) LAUNCH((k_bwd_reduce1<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_bwd_reduce1<Tt, Vv, false>), grid, smem, st, G)
     DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R1);
 #undef CALL_R1
     if (int e = launch_status("k_bwd_reduce1")) return e;

@@ -10,7 +10,7 @@ struct Geo {
   int hidden, k;
   int use_sigmoid;
   float thr, eps;
-  int proj_h;      // > 0: W1-projection planes of x are saved (forward) / available (backward); = hidden (<= kProjMax)
+  int proj_h;      // > 0: W1-projection planes of x are saved (forward) / used by k_bwd_apply (backward); = hidden (<= kProjMax)
 };
 constexpr int kProjMax = 4;   // MGACBAM_PROJ_MAX_HIDDEN
 constexpr int kGateR = 16;   // channels a thread of the x-resident kernels keeps in registers (x VEC pixels each)
@@ -83,6 +83,7 @@ struct BwdArgs {
   int sflag0;   // ... of k_bwd_reduce2's sweep workgroups in the merged launch: [B][C], one counter per CHANNEL (a sweep reads its first
                 // channel's, bumps all of its own): the channel grouping depends on the call's other levels, the counts do not
   int mbflag0, mcflag0;   // the merged launch's own tile / conv-tile flags (the host puts them into bflag0 / cflag0 for that launch)
+  int make_proj;   // 1: g.proj_h > 0 and the k_bwd_reduce1 tiles write the level's W1-projection planes (0 with MGACBAM_BWD_HAVE_PROJ: the forward did)
   int merged;   // 1: k_bwd_reduce1 tiles, transposed-conv tiles, dWsa tiles and k_bwd_reduce2 sweeps are ONE launch (k_bwd_r12)
   unsigned spin_limit;
   int vec;      // elements per lane of the tile kernels (TP = chan_tx * vec pixels per tile)

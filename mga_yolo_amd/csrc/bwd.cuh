@@ -5,19 +5,25 @@
 // P3+P4+P5:
 //   k_bwd_reduce1  x, gy (1 read each) -> A[b,c] = sum_hw gy*x*sa, D[b,c] = sum_hw gy*(v-x)   (per hw-tile partials)
 //                                         g_pre[b,hw] = a * sa(1-sa) * sum_c ca*gy*x
+//                                         P[b,j,hw] = sum_c W1[j,c]*x   (levels whose dL/dmask is wanted, hidden <= kProjMax: ctx.proj)
 //   k_bwd_convT    g_pre               -> g_planes = conv_transpose(g_pre, Wsa)     [tiny; with MGACBAM_BWD_FOLD its tiles are the
 //                                         last workgroups of the k_bwd_reduce1 launch and take g_pre over inside the launch]
 //   k_bwd_reduce2  x (1 read)          -> g_ca[b,c] = a*A + sum_hw x * ([c == cidx]*gp0 + gp1/C) ; g_z ; D ;
 //                                         per-channel-group partials of W2^T g_z
 //                                         + role workgroups (k_bwd_wsa body): dWsa tile partials
-//   k_bwd_apply    gy (+ x when dL/dmask is wanted) -> prologue: g_h from the partials, g_avg, g_mx = W1^T g_h ;
+//   k_bwd_apply    gy (+ x when dL/dmask is wanted and the level has no planes P) -> prologue: g_h from the partials, g_avg, g_mx = W1^T g_h ;
 //                                         body: gx (1 write), gmask
 //                                         + role workgroups (k_bwd_params body): dW1 db1 dW2 db2 dWsa dbeta
 //   (k_bwd_wsa / k_bwd_params also exist as stand-alone launches: MGACBAM_BWD_PARAMS, the split form for callers that want
 //    the parameter gradients complete before the largest kernel runs.)
 //
 // Algebra that keeps traffic at 2+1+3 passes: the term of g_ca that needs g_planes only needs x (not gy),
-// and gx needs gy, the saved arg-max indices and planes but x only for the masked-average part of dL/dmask.
+// and gx needs gy, the saved arg-max indices and planes but x only for the masked-average part of dL/dmask,
+// sum_c g_avg[b,c]*x[b,c,hw].  With g_avg = W1^T g_h that term is sum_j g_h[b,j]*P[b,j,hw]: for hidden <= kProjMax the k_bwd_reduce1
+// tiles, which stream x anyway, form the hidden planes P beside g_pre and k_bwd_apply reads those instead of the level's x (2+1+2 passes
+// for such a level).  The tiles make planes for fp32 levels only: VEC is 4 or 1 here for every element type, so the cost is the same
+// 4*VEC accumulators, but with half the bytes per element the bf16 / fp16 step measured slower with them (api_bwd.hip: backward_args,
+// where the rule lives -- per level, the same for the producing and the consuming stage).
 // All cross-workgroup sums are two-stage (partials, then one reader, fixed order), never float atomics, so results are
 // bitwise reproducible run to run.
 #pragma once
@@ -32,8 +38,14 @@ constexpr int kPghLds = 2048;   // floats of LDS for k_bwd_reduce2's hidden-grad
 // ---------------------------------------------------------------------------------------------
 // k_bwd_reduce1     (thread layout of k_chan: one H*W vector per lane, rows take channel slices; TX <= 64)
 // ---------------------------------------------------------------------------------------------
-template <typename T, int VEC, bool FOLD = false>   // FOLD: the transposed-conv tiles ride at the end of this launch (k_bwd_reduce1, ROLES)
+// PROJ: the tiles of a level with A.make_proj also form the W1-projection planes P[b,j,hw] = sum_c W1[j,c] x[b,c,hw] (j < g.proj_h <= kProjMax)
+// of the x they stream anyway -- a second per-pixel reduction over C beside g_pre -- and write them to ctx.proj for k_bwd_apply, which then
+// takes the masked-average part of dL/dmask from proj_h planes instead of re-reading the level's x.  Nothing in this launch reads the planes:
+// plain stores, ordered before k_bwd_apply by the launch boundary.
+template <typename T, int VEC, bool FOLD = false, bool PROJ = false>   // FOLD: the transposed-conv tiles ride at the end of this launch (k_bwd_reduce1, ROLES)
 __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid, float* smem) {
+  constexpr int HP = kProjMax;
+  static_assert(HP % 4 == 0, "the W1 rows of a channel are read as float4");
   const Geo& g = A.g;
   const int tid = threadIdx.x;
   const int TX = A.t.chan_tx, lt = ilog2(TX);
@@ -49,11 +61,21 @@ __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid
   const T* xp = static_cast<const T*>(A.x) + base;
   const T* gp = static_cast<const T*>(A.gy) + base;
   const float a = softplusf_(*A.p.beta);
-  // LDS: [C ca][2*C tile partials (A then D)][256*VEC combine]
+  // LDS: [C ca][2*C tile partials (A then D)][256*VEC combine]; a plane-making level: [..., padded to 4][C*kProjMax W1^T][4*256*VEC combine]
   float* s_ca = smem;
   float* s_aq = smem + g.C;
-  float* sm = s_aq + 2 * g.C;
+  const bool proj = PROJ && A.make_proj;                        // (host: only where g.proj_h > 0)
+  float* s_w1t = smem + ((3 * g.C + 3) & ~3);                   // [c][HP], zero padded past proj_h
+  float* sm = proj ? s_w1t + g.C * HP : s_aq + 2 * g.C;
   for (int c = tid; c < g.C; c += kBlock) s_ca[c] = A.c.ca[static_cast<size_t>(b) * g.C + c];
+  if (PROJ) {
+    if (proj) {
+      for (int idx = tid; idx < g.C * HP; idx += kBlock) {
+        const int c = idx / HP, j = idx - c * HP;
+        s_w1t[idx] = j < g.proj_h ? A.p.w1[static_cast<size_t>(j) * g.C + c] : 0.f;
+      }
+    }
+  }
 
   float sav[VEC];
   load_vec<float, VEC>(A.c.sa + static_cast<size_t>(b) * g.HW + static_cast<size_t>(ii) * VEC, sav);
@@ -61,6 +83,11 @@ __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid
   float accp[VEC];
 #pragma unroll
   for (int e = 0; e < VEC; ++e) accp[e] = 0.f;
+  float accP[PROJ ? HP : 1][VEC];
+#pragma unroll
+  for (int j = 0; j < (PROJ ? HP : 1); ++j)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) accP[j][e] = 0.f;
   __syncthreads();
 
 #pragma unroll 4
@@ -69,6 +96,20 @@ __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid
     load_vec<T, VEC>(xp + static_cast<size_t>(c) * g.HW, xv);
     load_vec<T, VEC>(gp + static_cast<size_t>(c) * g.HW, gv);
     const float cac = s_ca[c];
+    if (PROJ) {
+      if (proj) {
+        float w[HP];
+#pragma unroll
+        for (int q4 = 0; q4 < HP / 4; ++q4) {
+          const float4 wv = *reinterpret_cast<const float4*>(s_w1t + c * HP + 4 * q4);
+          w[4 * q4] = wv.x; w[4 * q4 + 1] = wv.y; w[4 * q4 + 2] = wv.z; w[4 * q4 + 3] = wv.w;
+        }
+#pragma unroll
+        for (int j = 0; j < HP; ++j)
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) accP[j][e] += w[j] * xv[e];
+      }
+    }
     float pa = 0.f, pq = 0.f;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
@@ -106,14 +147,44 @@ __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid
     }
   }
   if (FOLD) handoff_publish(A.c.sync + A.bflag0 + static_cast<size_t>(b) * A.nflag + tile);   // this tile's g_pre rows are out
+  if (PROJ) {
+    if (proj) {                                                  // TY partials of the planes, 4 planes per LDS round, rows summed in fixed order
+      // (after the hand-off: the conv tiles wait for g_pre, nobody in this launch for the planes)
+#pragma unroll
+      for (int half = 0; half < HP / 4; ++half) {
+        if (half * 4 >= g.proj_h) break;
+        if (!FOLD || half) __syncthreads();                      // the combine buffer is free (FOLD: the publish ended in a barrier)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) sm[(jj * kBlock + tid) * VEC + e] = accP[half * 4 + jj][e];
+        __syncthreads();
+        if (ty == 0 && active) {
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int j = half * 4 + jj;
+            if (j < g.proj_h) {
+              float pv[VEC];
+#pragma unroll
+              for (int e = 0; e < VEC; ++e) pv[e] = accP[j][e];
+              for (int r = 1; r < TY; ++r)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) pv[e] += sm[(jj * kBlock + r * TX + tx) * VEC + e];
+              store_vec<float, VEC>(A.c.proj + (static_cast<size_t>(b) * g.proj_h + j) * g.HW + static_cast<size_t>(i) * VEC, pv);
+            }
+          }
+        }
+      }
+    }
+  }
 }
 
-template <typename T, int VEC>
+template <typename T, int VEC, bool PROJ>
 __global__ __launch_bounds__(kBlock) void k_bwd_reduce1(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  bwd_reduce1_body<T, VEC>(G.lv[l], local, smem);
+  bwd_reduce1_body<T, VEC, false, PROJ>(G.lv[l], local, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -220,7 +291,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_convT(const Group<BwdArgs> G) {
 // The conv tiles start as the streaming workgroups retire and need only the g_pre rows of a few tiles each, so most of the
 // latency-bound conv overlaps the streaming tail and one launch boundary disappears.  Flags: one generation counter per k_bwd_reduce1
 // tile and per conv tile in ctx.sync (zero-filled by the caller once, never reset: see bwd_convT_body).
-template <typename T, int VEC, int K>
+template <typename T, int VEC, int K, bool PROJ>
 __global__ __launch_bounds__(kBlock) void k_bwd_reduce1_fold(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
@@ -231,7 +302,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_reduce1_fold(const Group<BwdArgs
     if (local - tiles < A.nconv) bwd_convT_body<K, true>(A, local - tiles, smem);
     return;
   }
-  bwd_reduce1_body<T, VEC, true>(A, local, smem);
+  bwd_reduce1_body<T, VEC, true, PROJ>(A, local, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -536,7 +607,7 @@ struct R12Group {
   Group<BwdArgs> g;
   int seg[4][kGroupMax + 1];     // seg[p][l]: first workgroup id of level l in phase p; seg[p][n]: end of phase p
 };
-template <typename T, int VEC, int CPT>
+template <typename T, int VEC, int CPT, bool PROJ>   // PROJ: some level's tiles make the W1-projection planes (bwd_reduce1_body)
 __global__ __launch_bounds__(kBlock) void k_bwd_r12(const R12Group R) {
   extern __shared__ __align__(16) float smem[];
   const int bid = blockIdx.x;
@@ -554,7 +625,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_r12(const R12Group R) {
   TRACE_MARK(A.trace, blockIdx.x, 0);                           // tools/trace_r12.py: start, phase (slot 14), end
   if (A.trace && threadIdx.x == 0) A.trace[static_cast<size_t>(blockIdx.x) * 16 + 14] = p + 1;
 #endif
-  if (p == 0) bwd_reduce1_body<T, VEC, true>(A, local, smem);
+  if (p == 0) bwd_reduce1_body<T, VEC, true, PROJ>(A, local, smem);
   else if (p == 1) { if (local < A.nconv) bwd_convT_body<7, true>(A, local, smem); }
   else if (p == 2) { if (local < A.nwsa) bwd_wsa_body<7, true>(A, local, smem); }
   else bwd_reduce2_body<T, VEC, CPT, true>(A, local, smem);
@@ -726,7 +797,8 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
 #pragma unroll
   for (int e = 0; e < VEC; ++e) accp[e] = 0.f;
 
-  // With the W1-projection planes saved by k_chan, sum_c g_avg[b,c]*x[b,c,hw] = sum_j g_h[b,j]*P[b,j,hw]: x is not read.
+  // With the W1-projection planes (written by the k_bwd_reduce1 tiles, or by the forward's k_chan), sum_c g_avg[b,c]*x[b,c,hw] =
+  // sum_j g_h[b,j]*P[b,j,hw]: x is not read.
   const bool need_x = GMASK && g.proj_h == 0;
   // first feature vectors are requested before the prologue so its latency overlaps theirs
   float g0v[UN][VEC], x0v[UN][VEC];

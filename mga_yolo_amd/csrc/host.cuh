@@ -493,7 +493,11 @@ static int gate_tiles(const Tune& t, int H, int W, int vec) {
   return (nv + t.gate_tx - 1) / t.gate_tx;
 }
 static size_t bwd_apply_smem(const Geo& g, int vec) { return (5 * static_cast<size_t>(g.C) + 2 * g.hidden + kBlock * vec) * sizeof(float); }
-static size_t reduce1_smem(const Geo& g, int vec) { return (3 * static_cast<size_t>(g.C) + kBlock * vec) * sizeof(float); }
+// (proj: the level's tiles also make its W1-projection planes -- W1^T staged after the partials, four planes per combine round)
+static size_t reduce1_smem(const Geo& g, int vec, bool proj) {
+  if (!proj) return (3 * static_cast<size_t>(g.C) + kBlock * vec) * sizeof(float);
+  return (((3 * static_cast<size_t>(g.C) + 3) & ~static_cast<size_t>(3)) + static_cast<size_t>(g.C) * kProjMax + 4 * kBlock * vec) * sizeof(float);
+}
 static size_t mlp_smem(const Geo& g) { return (3 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }
 // their NHWC siblings (n: nhwc_geo of the level)
 static size_t nhwc_pool_smem(const Geo& g) { return 4 * static_cast<size_t>(g.C) * sizeof(float); }

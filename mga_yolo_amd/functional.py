@@ -257,8 +257,8 @@ class _PyramidFn(torch.autograd.Function):
                 ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, flags), dtype=torch.uint8, device=dev)
                 L.ws, L.ws_bytes, L.flags = ws.data_ptr(), ws.numel(), flags
                 hold.append(ws)
-            # (L.flags has no SAVE_PROJ: the W1-projection planes are not saved here -- at YOLOv8n sizes what k_bwd_apply saves (x of P3) k_chan
-            #  pays back; PyramidPlan(use_proj=True) and forward_with_ctx still drive that path)
+            # (L.flags has no SAVE_PROJ: the backward makes the W1-projection planes itself where they pay (include/mgacbam.h), and the
+            #  forward keeps k_gate; PyramidPlan(use_proj=True) and forward_with_ctx still drive the forward producer, k_chan)
             keep += [xc, m32, *pc]
             outs.append(y)
             layouts.append(flags)
