@@ -13,7 +13,7 @@
  *     frees, copies to the host or synchronises, so every call may be captured in a hipGraph.
  *   - re-entrant: no mutable globals except a thread-local error string.
  *   - return value: 0 = ok, <0 = argument error (MGACBAM_E_*), >0 = hipError_t from a launch.
- *   - tensors are dense NCHW, or dense NHWC (channels_last) for MaskCBAM levels flagged MGACBAM_LAYOUT_NHWC; `dtype` selects the element type of x / y / gy / gx (mask, parameters,
+ *   - tensors are dense NCHW, or dense NHWC (channels_last) for MaskCBAM and MaskECA levels flagged MGACBAM_LAYOUT_NHWC; `dtype` selects the element type of x / y / gy / gx (mask, parameters,
  *     every accumulator and every saved statistic are fp32).
  *
  * Entry-point families: mgacbam_*  MaskCBAM (the hot path) + mgacbam_eca_* MaskECA + mgacbam_resize_nearest;
@@ -259,6 +259,9 @@ typedef struct mgacbam_eca_fwd_level {
   mgacbam_eca_params_t p;
   int32_t B, C, H, W;
   int32_t dtype;
+  int32_t flags;             /* 0 or MGACBAM_LAYOUT_NHWC: x / y are dense (B,H,W,C).  Appended within ABI 15: the struct had 4 bytes of
+                                tail padding here, so its size (96) and every other offset are unchanged, and a level a current caller
+                                zero-fills and sets field by field has flags == 0 = exactly the behaviour before the field existed */
 } mgacbam_eca_fwd_level_t;
 
 typedef struct mgacbam_eca_bwd_level {
@@ -276,12 +279,23 @@ typedef struct mgacbam_eca_bwd_level {
   mgacbam_eca_params_t p;
   int32_t B, C, H, W;
   int32_t dtype;
+  int32_t flags;             /* 0 or MGACBAM_LAYOUT_NHWC: x / gy / gx are dense (B,H,W,C); as in the forward level, the field took the
+                                struct's tail padding (size 144 as before) and 0 keeps the behaviour before it existed */
 } mgacbam_eca_bwd_level_t;
 
 size_t mgacbam_eca_ctx_bytes(int B, int C, int H, int W);
 size_t mgacbam_eca_scratch_bytes(int B, int C, int H, int W);
-int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_levels, void* stream);    /* 2 launches */
-int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n_levels, void* stream);   /* 2 launches */
+/* Layout-aware size queries, `flags` = the level's flags: with MGACBAM_LAYOUT_NHWC clear exactly the two queries above; with it set they add
+ * the per-chunk partials of the channels-last kernels as a tail (forward: after the ctx fields, whose layout is the same in both layouts;
+ * backward: after gg in scratch), enough for every element type.  0 means a bad shape or unknown flag bits.
+ * MGACBAM_LAYOUT_NHWC levels: mask, gmask and the saved statistics are the same memory in both layouts; x / y / gy / gx must be aligned to
+ * the element size times the lane width along C (the MaskCBAM rule: 8 for fp16 / bf16 with C % 8 == 0, else 4 when C % 4 == 0, else 1;
+ * MGACBAM_E_ALIGN); ctx and scratch are sized by these queries (MGACBAM_E_SIZE otherwise); C <= 4096 (MGACBAM_E_SHAPE).  Levels of both
+ * layouts may share a call: each layout gets launch groups of its own. */
+size_t mgacbam_eca_ctx_bytes_flags(int B, int C, int H, int W, int flags);
+size_t mgacbam_eca_scratch_bytes_flags(int B, int C, int H, int W, int flags);
+int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_levels, void* stream);    /* 2 launches for the NCHW levels, 3 for the NHWC ones */
+int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n_levels, void* stream);   /* 2 launches for the NCHW levels, 3 for the NHWC ones */
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-scale segmentation loss on the mask logits: replaces SegmentationLoss.forward in its default mode,

@@ -17,7 +17,7 @@ FWD_STAGES = dict(pool=1, chan=2, apply=4)
 BWD_STAGES = dict(reduce1=1, convT=2, reduce2=4, wsa=8, params=16, apply=32)
 BWD_FUSE = 64
 FWD_SAVE_PROJ, BWD_HAVE_PROJ, PROJ_MAX_HIDDEN = 1, 1, 4
-LAYOUT_NHWC = 2   # level flag (forward and backward): x, y, gy, gx are (B,H,W,C) -- torch's channels_last
+LAYOUT_NHWC = 2   # level flag (MaskCBAM and MaskECA, forward and backward): x, y, gy, gx are (B,H,W,C) -- torch's channels_last
 FWD_ALL, BWD_PARAMS, BWD_INPUTS, BWD_ALL = 7, 31, 32, 127
 BWD_FOLD = 128   # with BWD_ALL: transposed conv folded into the k_bwd_reduce1 launch (ctx.sync zero-filled once by the caller)
 FWD_FUSE = 8   # with FWD_ALL: one launch, in-launch hand-off through ctx.sync (caller zero-fills it once)
@@ -54,14 +54,14 @@ class EcaParams(C.Structure):                    # mgacbam_eca_params_t
 
 class EcaFwdLevel(C.Structure):                  # mgacbam_eca_fwd_level_t
     _fields_ = [("x", C.c_void_p), ("mask", C.c_void_p), ("y", C.c_void_p), ("ctx", C.c_void_p), ("ctx_bytes", C.c_size_t), ("p", EcaParams),
-                ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("dtype", C.c_int32)]
+                ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("dtype", C.c_int32), ("flags", C.c_int32)]
 
 
 class EcaBwdLevel(C.Structure):                  # mgacbam_eca_bwd_level_t
     _fields_ = [("x", C.c_void_p), ("mask", C.c_void_p), ("gy", C.c_void_p), ("ctx", C.c_void_p), ("scratch", C.c_void_p),
                 ("ctx_bytes", C.c_size_t), ("scratch_bytes", C.c_size_t),
                 ("gx", C.c_void_p), ("gmask", C.c_void_p), ("gw", C.c_void_p), ("gbeta", C.c_void_p), ("p", EcaParams),
-                ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("dtype", C.c_int32)]
+                ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("dtype", C.c_int32), ("flags", C.c_int32)]
 
 
 CTX_FIELDS = ("S", "use", "den", "avg", "mx", "mavg", "valid", "amax", "h_avg", "h_mx", "ca", "planes", "cidx", "sa", "proj", "sync", "total", "status")
@@ -131,6 +131,8 @@ SYMBOLS = {
     "mgacbam_resize_nearest": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "mgacbam_eca_ctx_bytes": (C.c_size_t, [C.c_int] * 4),
     "mgacbam_eca_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
+    "mgacbam_eca_ctx_bytes_flags": (C.c_size_t, [C.c_int] * 5),
+    "mgacbam_eca_scratch_bytes_flags": (C.c_size_t, [C.c_int] * 5),
     "mgacbam_eca_forward": (C.c_int, [C.POINTER(EcaFwdLevel), C.c_int, C.c_void_p]),
     "mgacbam_eca_backward": (C.c_int, [C.POINTER(EcaBwdLevel), C.c_int, C.c_void_p]),
     "mgaseg_ws_bytes": (C.c_size_t, [C.POINTER(SegLevel), C.c_int]),
@@ -247,6 +249,30 @@ def fwd_ws_bytes(B, Cc, H, W, hidden, flags: int) -> int:
         n = load().mgacbam_fwd_ws_bytes(B, Cc, H, W, hidden, LAYOUT_NHWC)
         if n == 0:
             check(-2, "mgacbam_fwd_ws_bytes")
+        _size_cache[key] = n
+    return n
+
+
+def eca_ctx_bytes(B, Cc, H, W, flags: int = 0) -> int:
+    """ctx of a MaskECA level: the saved statistics, plus the per-chunk pooling partials for LAYOUT_NHWC levels."""
+    key = ("eca_ctx", B, Cc, H, W, flags & LAYOUT_NHWC)
+    n = _size_cache.get(key)
+    if n is None:
+        n = load().mgacbam_eca_ctx_bytes_flags(B, Cc, H, W, flags & LAYOUT_NHWC)
+        if n == 0:
+            check(-2, "mgacbam_eca_ctx_bytes_flags")
+        _size_cache[key] = n
+    return n
+
+
+def eca_scratch_bytes(B, Cc, H, W, flags: int = 0) -> int:
+    """Backward scratch of a MaskECA level: gg, plus its per-chunk partials for LAYOUT_NHWC levels."""
+    key = ("eca_scratch", B, Cc, H, W, flags & LAYOUT_NHWC)
+    n = _size_cache.get(key)
+    if n is None:
+        n = load().mgacbam_eca_scratch_bytes_flags(B, Cc, H, W, flags & LAYOUT_NHWC)
+        if n == 0:
+            check(-2, "mgacbam_eca_scratch_bytes_flags")
         _size_cache[key] = n
     return n
 

@@ -403,8 +403,14 @@ class EcaConfig:
     eps: float = 1e-6
 
 
+# the channels-last MaskECA kernels keep 3 floats per channel in LDS (csrc/api_eca.hip: kEcaNhwcMaxC); a wider channels_last feature keeps
+# the path it always had: one copy to NCHW and the NCHW kernels
+_ECA_NHWC_MAX_C = 4096
+
+
 class _EcaFn(torch.autograd.Function):
-    """n independent levels; flat inputs = n x (x, mask|None, conv1d.weight, beta)."""
+    """n independent levels; flat inputs = n x (x, mask|None, conv1d.weight, beta).  The layout decides the kernels, per level (MaskCBAM's
+    rule, _is_nhwc): a channels_last x runs the channels-last kernels without a copy and y / gx come back channels_last."""
 
     @staticmethod
     def forward(ctx, cfgs: Tuple[EcaConfig, ...], *flat):
@@ -412,7 +418,7 @@ class _EcaFn(torch.autograd.Function):
         assert len(flat) == 4 * n and 1 <= n <= _lib.MAX_LEVELS
         lib = _lib.load()
         levels = (_lib.EcaFwdLevel * n)()
-        keep, outs, meta = [], [], []
+        keep, outs, meta, layouts = [], [], [], []
         dev = flat[0].device
         for l in range(n):
             x, mask, w, beta = flat[4 * l:4 * l + 4]
@@ -430,23 +436,26 @@ class _EcaFn(torch.autograd.Function):
                     raise RuntimeError(f"mask shape {tuple(mask.shape)} does not match feature (B,1,H,W)=({B},1,{H},{W})")
             if tuple(w.shape) != (1, 1, cfg.k) or beta.dim() != 0:
                 raise ValueError(f"MaskECA parameters: expected conv1d.weight (1,1,{cfg.k}) and scalar beta")
-            xc = _aligned(x.detach())
+            nhwc = _is_nhwc(x) and Cc <= _ECA_NHWC_MAX_C
+            flags = _lib.LAYOUT_NHWC if nhwc else 0
+            xc = _ready_nhwc(x) if nhwc else _aligned(x.detach())
             m32 = None if mask is None else _aligned(mask.detach().reshape(B, 1, H, W).float())
             wc, bc = _aligned(w.detach().float()), _aligned(beta.detach().float())
-            y = torch.empty_like(xc)
-            cbuf = torch.empty(lib.mgacbam_eca_ctx_bytes(B, Cc, H, W), dtype=torch.uint8, device=dev)
+            y = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
+            cbuf = torch.empty(_lib.eca_ctx_bytes(B, Cc, H, W, flags), dtype=torch.uint8, device=dev)
             L = levels[l]
             L.x, L.mask, L.y, L.ctx = xc.data_ptr(), (None if m32 is None else m32.data_ptr()), y.data_ptr(), cbuf.data_ptr()
             L.ctx_bytes = cbuf.numel()
             L.p = _lib.EcaParams(wc.data_ptr(), bc.data_ptr(), cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
-            L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[x.dtype]
+            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[x.dtype], flags
             keep += [xc, m32, cbuf, wc, bc]
             outs.append(y)
+            layouts.append(flags)
             meta.append(None if mask is None else (mask.dtype, tuple(mask.shape)))
         with torch.cuda.device(dev):
             _lib.check(lib.mgacbam_eca_forward(levels, n, torch.cuda.current_stream(dev).cuda_stream), "mgacbam_eca_forward")
         ctx.save_for_backward(*keep)
-        ctx.cfgs, ctx.meta = cfgs, meta
+        ctx.cfgs, ctx.meta, ctx.layouts = cfgs, meta, layouts
         return tuple(outs)
 
     @staticmethod
@@ -462,20 +471,26 @@ class _EcaFn(torch.autograd.Function):
             xc, m32, cbuf, wc, bc = saved[5 * l:5 * l + 5]
             cfg = cfgs[l]
             B, Cc, H, W = xc.shape
+            flags = ctx.layouts[l]
             gy = gys[l]
-            gy = torch.zeros_like(xc) if gy is None else _aligned(gy.to(xc.dtype))
+            if gy is None:
+                gy = torch.zeros_like(xc)
+            elif flags & _lib.LAYOUT_NHWC:                         # a gy of any other layout is converted once
+                gy = _ready_nhwc(gy.to(xc.dtype))
+            else:
+                gy = _aligned(gy.to(xc.dtype))
             want_gmask = m32 is not None and ctx.needs_input_grad[1 + 4 * l + 1]
-            gx = torch.empty_like(xc)
+            gx = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
             gmask = torch.empty_like(m32) if want_gmask else None
             gw, gb = torch.empty_like(wc), torch.empty_like(bc)
-            scratch = torch.empty(lib.mgacbam_eca_scratch_bytes(B, Cc, H, W), dtype=torch.uint8, device=dev)
+            scratch = torch.empty(_lib.eca_scratch_bytes(B, Cc, H, W, flags), dtype=torch.uint8, device=dev)
             L = levels[l]
             L.x, L.mask, L.gy, L.ctx, L.scratch = (xc.data_ptr(), None if m32 is None else m32.data_ptr(), gy.data_ptr(),
                                                    cbuf.data_ptr(), scratch.data_ptr())
             L.ctx_bytes, L.scratch_bytes = cbuf.numel(), scratch.numel()
             L.gx, L.gmask, L.gw, L.gbeta = gx.data_ptr(), (None if gmask is None else gmask.data_ptr()), gw.data_ptr(), gb.data_ptr()
             L.p = _lib.EcaParams(wc.data_ptr(), bc.data_ptr(), cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
-            L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[xc.dtype]
+            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[xc.dtype], flags
             hold += [gy, scratch]
             grads += [gx, gmask, gw, gb]
         with torch.cuda.device(dev):
@@ -490,11 +505,15 @@ class _EcaFn(torch.autograd.Function):
 
 
 def mask_eca(x: torch.Tensor, mask: Optional[torch.Tensor], w: torch.Tensor, beta: torch.Tensor, cfg: EcaConfig) -> torch.Tensor:
-    """y = x * (1 + softplus(beta) * (sigmoid(conv1d(masked_avg(x, mask))) - 0.5)) for a device tensor (masked_eca.py:167-196)."""
+    """y = x * (1 + softplus(beta) * (sigmoid(conv1d(masked_avg(x, mask))) - 0.5)) for a device tensor (masked_eca.py:167-196).
+    A channels_last x with C <= 4096 is taken as it is (no layout copy); y and dL/dx are then channels_last too.  Any other layout, and a
+    wider channels_last feature, is copied to NCHW once and runs the NCHW kernels, as before."""
     return _EcaFn.apply((cfg,), x, mask, w, beta)[0]
 
 
 def mask_eca_pyramid(levels: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, torch.Tensor, EcaConfig]]):
+    """levels: [(x, mask|None, conv1d.weight, beta, EcaConfig), ...] -> tuple of outputs (one library call each way).  Levels may mix
+    layouts: each channels_last feature runs the channels-last kernels, the others the NCHW ones."""
     cfgs, flat = [], []
     for x, mask, w, beta, cfg in levels:
         cfgs.append(cfg)

@@ -8,7 +8,8 @@ state on the instance -- EMA deep-copies the module, U/utils/torch_utils.py:722)
 
 Device tensors run the hand-written HIP kernels through ``functional.mask_cbam`` (one library call forward, one backward).
 A ``channels_last`` feature (``model.to(memory_format=torch.channels_last)``) runs the channels-last kernels without a layout copy, and
-its output and input gradient come back ``channels_last``; any other layout takes the NCHW kernels.
+its output and input gradient come back ``channels_last``; any other layout takes the NCHW kernels.  ``MaskECA`` and ``MGAMaskHead``
+follow the same rule (a channels_last feature is taken as it is, the feature gradient comes back channels_last).
 Host (CPU) tensors -- the 256x256 stride probe ``parse_model`` runs at build time (U/nn/tasks.py:413-429) and BASELINE
 config 0 (``device='cpu'``) -- run ``_host_forward``, a plain-PyTorch statement of the same mathematics; it is never
 used for a device tensor, and a device tensor with the library missing raises.
@@ -206,7 +207,10 @@ class MaskECA(nn.Module):
     """Mask-guided Efficient Channel Attention: masked average pooling (GAP fallback for tiny masks) -> conv1d over the
     channel axis -> sigmoid -> ``x * (1 + softplus(beta) * (w - 0.5))``.  Same constructor, parameter names
     (``conv1d.weight`` (1,1,k), ``beta``), ``alpha`` / ``scale_name`` / ``cfg`` attributes and ``[feat, mask]`` input as the
-    reference class; device tensors run the HIP kernels (2 launches forward, 2 backward), host tensors plain PyTorch."""
+    reference class; device tensors run the HIP kernels (2 launches forward, 2 backward), host tensors plain PyTorch.
+    A channels_last device feature (``model.to(memory_format=torch.channels_last)``) of up to 4096 channels runs the channels-last
+    kernels (3 launches each way) without a layout copy, and the output and dL/dx come back channels_last; the mask stays (B,1,H,W).
+    Wider channels_last features are copied to NCHW once, as every other layout is."""
 
     def __init__(self, channels: int, gamma: float = 2.0, b: float = 1.0, k_min: int = 3, k_max: int = 15,
                  use_sigmoid_mask: bool = True, tiny_mask_threshold: float = 1e-4, eps: float = 1e-6) -> None:
@@ -241,6 +245,7 @@ class MaskECA(nn.Module):
         else:
             feat, mask = x, None
         assert isinstance(feat, torch.Tensor) and feat.dim() == 4, "feature must be (B,C,H,W)"
+        # (a channels_last device feature needs no branch here: mask_eca picks the kernels from the feature's strides, per call)
         self._maybe_rebuild_conv(feat.shape[1])
         if feat.is_cuda:
             return mask_eca(feat, mask, self.conv1d.weight, self.beta, self.eca_config())

@@ -176,12 +176,17 @@ class PyramidPlan:
 class EcaPyramidPlan:
     """The same static executor for MaskECA: per level x, mask, y, gy, gx, gmask, ctx, scratch and one flat bucket
     with the parameter gradients (conv1d.weight, beta) of all levels; ``forward`` / ``backward`` = one library call each
-    (2 kernel launches each for all levels together)."""
+    (2 kernel launches each for all levels together).  ``channels_last=True`` allocates x / y / gy / gx in torch.channels_last and runs the
+    channels-last kernels (MGACBAM_LAYOUT_NHWC; 3 launches each way); masks and parameter gradients are the same in both layouts."""
 
-    def __init__(self, shapes, params, cfgs, dtype=torch.float32, device="cuda", with_mask=True, want_gmask=True):
+    def __init__(self, shapes, params, cfgs, dtype=torch.float32, device="cuda", with_mask=True, want_gmask=True,
+                 channels_last: bool = False):
         self.lib = _lib.load()
         self.device = torch.device(device)
         self.n, self.shapes, self.cfgs, self.dtype = len(shapes), list(shapes), list(cfgs), dtype
+        self.channels_last = bool(channels_last)
+        flags = _lib.LAYOUT_NHWC if self.channels_last else 0
+        fmt = torch.channels_last if self.channels_last else torch.contiguous_format
         dev = self.device
         self.params = [[p.detach().to(dev, torch.float32).contiguous() for p in ps] for ps in params]
         self.x, self.mask, self.y, self.gy, self.gx, self.gmask, self.ctx, self.scratch = ([] for _ in range(8))
@@ -192,11 +197,12 @@ class EcaPyramidPlan:
         ptr = lambda t: None if t is None else t.data_ptr()
         for l, ((B, C, H, W), (w, beta), cfg) in enumerate(zip(shapes, self.params, cfgs)):
             mk = lambda *s_, dt=dtype: torch.zeros(*s_, dtype=dt, device=dev)
-            self.x.append(mk(B, C, H, W)); self.y.append(mk(B, C, H, W)); self.gy.append(mk(B, C, H, W)); self.gx.append(mk(B, C, H, W))
+            mkf = lambda: torch.zeros(B, C, H, W, dtype=dtype, device=dev).contiguous(memory_format=fmt)
+            self.x.append(mkf()); self.y.append(mkf()); self.gy.append(mkf()); self.gx.append(mkf())
             self.mask.append(mk(B, 1, H, W, dt=torch.float32) if with_mask else None)
             self.gmask.append(mk(B, 1, H, W, dt=torch.float32) if (with_mask and want_gmask) else None)
-            self.ctx.append(torch.zeros(self.lib.mgacbam_eca_ctx_bytes(B, C, H, W), dtype=torch.uint8, device=dev))
-            self.scratch.append(torch.zeros(self.lib.mgacbam_eca_scratch_bytes(B, C, H, W), dtype=torch.uint8, device=dev))
+            self.ctx.append(torch.zeros(_lib.eca_ctx_bytes(B, C, H, W, flags), dtype=torch.uint8, device=dev))
+            self.scratch.append(torch.zeros(_lib.eca_scratch_bytes(B, C, H, W, flags), dtype=torch.uint8, device=dev))
             gw = self.grad_bucket[off:off + w.numel()].view(w.shape); off += w.numel()
             gb = self.grad_bucket[off:off + 1].view(()); off += 1
             self.param_grads.append([gw, gb])
@@ -209,6 +215,7 @@ class EcaPyramidPlan:
             Bw.x, Bw.mask, Bw.gy, Bw.ctx, Bw.scratch = ptr(self.x[l]), ptr(self.mask[l]), ptr(self.gy[l]), ptr(self.ctx[l]), ptr(self.scratch[l])
             Bw.gx, Bw.gmask, Bw.gw, Bw.gbeta, Bw.p = ptr(self.gx[l]), ptr(self.gmask[l]), gw.data_ptr(), gb.data_ptr(), P
             Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype = B, C, H, W, _DTYPES[dtype]
+            F.flags = Bw.flags = flags
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
