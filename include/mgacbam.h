@@ -436,6 +436,8 @@ int mgapmg_forward(const float* p, const float* u1, const float* u2, float* out,
                    void* stream);
 int mgapmg_backward(const float* p, const float* msoft, const float* gout, float* gp, size_t n, const mgapmg_cfg_t* cfg, void* stream);
 
+/* MaskSPADE (mgaspade_level_t, mgaspade_*): include/mgaspade.h -- same conventions, same error codes, errors through mgacbam_last_error. */
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,17 @@ class PmgCfg(C.Structure):                       # mgapmg_cfg_t
     _fields_ = [("tau", C.c_float), ("p_min", C.c_float), ("threshold", C.c_float), ("hard", C.c_int32)]
 
 
+NORM_IN, NORM_BN = 0, 1
+
+
+class SpadeLevel(C.Structure):                   # mgaspade_level_t (include/mgaspade.h)
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "mask", "y", "gy", "gx", "gmask", "w0", "b0", "wg", "bg", "wb", "bb", "running_mean",
+                                           "running_var", "num_batches_tracked", "gw0", "gb0", "gwg", "gbg", "gwb", "gbb")] +
+                [("ctx", C.c_void_p), ("ctx_bytes", C.c_size_t), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)] +
+                [(n, C.c_int32) for n in ("B", "C", "H", "W", "hidden", "dtype", "norm_type", "training", "use_sigmoid_mask", "save_gamma")] +
+                [("eps", C.c_float), ("momentum", C.c_float), ("flags", C.c_int32)])
+
+
 SYMBOLS = {
     "mgacbam_abi_version": (C.c_int, []),
     "mgacbam_last_error": (C.c_char_p, []),
@@ -151,6 +162,13 @@ SYMBOLS = {
     "mgapmg_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(PmgCfg), C.c_void_p]),
     "mgapmg_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(PmgCfg), C.c_void_p]),
 }
+# every symbol include/mgaspade.h declares (MaskSPADE: a header of its own, include/mgacbam.h is unchanged by it)
+SPADE_SYMBOLS = {
+    "mgaspade_ctx_bytes": (C.c_size_t, [C.c_int] * 5),
+    "mgaspade_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
+    "mgaspade_forward": (C.c_int, [C.POINTER(SpadeLevel), C.c_int, C.c_void_p]),
+    "mgaspade_backward": (C.c_int, [C.POINTER(SpadeLevel), C.c_int, C.c_void_p]),
+}
 
 _lib = None
 _lock = threading.Lock()
@@ -174,7 +192,7 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -275,6 +293,27 @@ def eca_scratch_bytes(B, Cc, H, W, flags: int = 0) -> int:
             check(-2, "mgacbam_eca_scratch_bytes_flags")
         _size_cache[key] = n
     return n
+
+
+def _spade_size(which: str, B, Cc, H, W, hidden) -> int:
+    key = ("spade_" + which, B, Cc, H, W, hidden)
+    n = _size_cache.get(key)
+    if n is None:
+        n = getattr(load(), f"mgaspade_{which}_bytes")(B, Cc, H, W, hidden)
+        if n == 0:
+            check(-2, f"mgaspade_{which}_bytes")
+        _size_cache[key] = n
+    return n
+
+
+def spade_ctx_bytes(B, Cc, H, W, hidden) -> int:
+    """ctx of a MaskSPADE level: statistics, the packed conv weights and the saved gamma (sized for fp32 features)."""
+    return _spade_size("ctx", B, Cc, H, W, hidden)
+
+
+def spade_scratch_bytes(B, Cc, H, W, hidden) -> int:
+    """Backward scratch of a MaskSPADE level: plane sums, the split-K partials of dW, the tap planes of ds, the dW0 partials."""
+    return _spade_size("scratch", B, Cc, H, W, hidden)
 
 
 def sync_regions(B, Cc, H, W) -> dict:

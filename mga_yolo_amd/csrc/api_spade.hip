@@ -1,0 +1,245 @@
+// libmgacbam.so, C ABI (include/mgaspade.h): MaskSPADE
+#include "host.cuh"
+#include "../../include/mgaspade.h"
+#include "spade.cuh"
+
+constexpr int kSpMaxC = 1024;
+constexpr int kSpDwTarget = 512;     // workgroups k_spade_dw aims for: (C / 16) M tiles x pixel chunks
+
+struct SpTiling { int TW, TH, ltw, tiles_x, tiles; };
+// TW in {4, 8, 16, 32} (TH = 128 / TW): the choice that pads the level's H x W the least, the widest rows on a tie
+static SpTiling sp_tiling(int H, int W) {
+  SpTiling best{};
+  long long best_px = -1;
+  for (int ltw = 5; ltw >= 2; --ltw) {
+    const int TW = 1 << ltw, TH = kSpPx / TW;
+    const int tx = (W + TW - 1) / TW, ty = (H + TH - 1) / TH;
+    const long long px = static_cast<long long>(tx) * ty;
+    if (best_px < 0 || px < best_px) { best_px = px; best = SpTiling{TW, TH, ltw, tx, tx * ty}; }
+  }
+  return best;
+}
+struct SpLayout { size_t mean, rstd, wpack, wpackT, gamma, base; };
+static SpLayout sp_ctx_layout(int B, int C, int hidden) {
+  SpLayout L;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
+  const size_t BC = static_cast<size_t>(B) * C, nw = static_cast<size_t>(2) * 9 * C * hidden;
+  L.mean = take(BC); L.rstd = take(BC); L.wpack = take(nw); L.wpackT = take(nw);
+  L.gamma = o; L.base = o;
+  return L;
+}
+static size_t sp_gamma_bytes(int B, int C, int H, int W, size_t elem) { return align16(static_cast<size_t>(B) * C * H * W * elem); }
+struct SpScratch { size_t red, stat, dwpart, u, w0part, total; int nchunk, tpc; };
+static SpScratch sp_scratch_layout(int B, int C, int H, int W, int hidden) {
+  const SpTiling t = sp_tiling(H, W);
+  const int total = B * t.tiles;
+  int nchunk = std::max(1, std::min(total, kSpDwTarget / (C / 16)));
+  const int tpc = (total + nchunk - 1) / nchunk;
+  nchunk = (total + tpc - 1) / tpc;
+  SpScratch L;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
+  const size_t BC = static_cast<size_t>(B) * C;
+  L.red = take(4 * BC); L.stat = take(2 * BC);
+  L.dwpart = take(static_cast<size_t>(nchunk) * 2 * C * hidden * 9);
+  L.u = take(static_cast<size_t>(B) * 9 * H * W);
+  L.w0part = take(static_cast<size_t>(total) * hidden * 10);
+  L.total = o; L.nchunk = nchunk; L.tpc = tpc;
+  return L;
+}
+static int sp_check_shape(const char* what, int B, int C, int H, int W, int hidden) {
+  if (int e = check_shape(B, C, H, W, hidden, 3)) return e;
+  if (hidden % 16 || hidden > kSpMaxHid) return fail(MGACBAM_E_SHAPE, "%s: hidden=%d must be a multiple of 16 and <= %d", what, hidden, kSpMaxHid);
+  if (C % 16 || C > kSpMaxC) return fail(MGACBAM_E_SHAPE, "%s: C=%d must be a multiple of 16 and <= %d", what, C, kSpMaxC);
+  if (static_cast<long long>(B) * C * H * W >= (1ll << 31)) return fail(MGACBAM_E_SHAPE, "%s: tensor too large B=%d C=%d H=%d W=%d", what, B, C, H, W);
+  return 0;
+}
+extern "C" size_t mgaspade_ctx_bytes(int B, int C, int H, int W, int hidden) {
+  if (sp_check_shape("mgaspade_ctx_bytes", B, C, H, W, hidden)) return 0;
+  return sp_ctx_layout(B, C, hidden).base + sp_gamma_bytes(B, C, H, W, 4);
+}
+extern "C" size_t mgaspade_scratch_bytes(int B, int C, int H, int W, int hidden) {
+  if (sp_check_shape("mgaspade_scratch_bytes", B, C, H, W, hidden)) return 0;
+  return sp_scratch_layout(B, C, H, W, hidden).total;
+}
+
+static size_t sp_head_floats(const SpadeArgs& a) { return ((a.hid * 10 + 3) & ~3) + (((a.TH + 4) * (a.TW + 4) + 3) & ~3); }
+static size_t sp_nph(const SpadeArgs& a) { return static_cast<size_t>(a.TH + 2) * (a.TW + 2); }
+static size_t sp_fwd_smem(const SpadeArgs& a) { return (sp_head_floats(a) + sp_nph(a) * (a.hid + 4)) * sizeof(float); }
+static size_t sp_dw_smem(const SpadeArgs& a) { return (sp_head_floats(a) + ((sp_nph(a) * a.hid + 3) & ~size_t(3)) + 2 * 16 * kSpAStride) * sizeof(float); }
+static size_t sp_dh_smem(const SpadeArgs& a) {
+  const size_t cc = std::min(a.C, kSpDhCC);
+  return (sp_head_floats(a) + std::max(sp_nph(a) * 2 * (cc + 4), static_cast<size_t>(a.hid) * kSpAStride)) * sizeof(float);
+}
+// dynamic LDS above 48 KB: the kernel's limit is raised first (an attribute of the function: no stream work, no allocation)
+// Done once per (device, kernel) and size reached, so a warmed-up call -- the state a stream capture starts from -- makes no runtime call here.
+template <typename K>
+static void sp_allow_lds(K kernel, size_t smem) {
+  if (smem <= 48 * 1024) return;
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, size_t> allowed;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  const auto key = std::make_pair(dev, reinterpret_cast<const void*>(kernel));
+  std::lock_guard<std::mutex> lk(mu);
+  size_t& have = allowed[key];
+  if (have >= smem) return;
+  if (hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) == hipSuccess) have = smem;
+}
+#define SP_DISPATCH_T(dtype, CALL) \
+  do { if ((dtype) == MGACBAM_F32) { CALL(float); } else if ((dtype) == MGACBAM_F16) { CALL(__half); } else { CALL(bf16_t); } } while (0)
+
+// everything a level is checked for before the first launch, and its kernel arguments
+static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, SpadeArgs& A, Sig& sig) {
+  if (!L.x || !L.ctx) return fail(MGACBAM_E_NULL, "%s: x / ctx is NULL", what);
+  if (!bwd && !L.y) return fail(MGACBAM_E_NULL, "%s: y is NULL", what);
+  if (bwd && (!L.gy || !L.gx || !L.scratch)) return fail(MGACBAM_E_NULL, "%s: gy / gx / scratch is NULL", what);
+  if (L.flags) return fail(MGACBAM_E_SHAPE, "%s: flags=0x%x (reserved: 0)", what, L.flags);
+  if (int e = sp_check_shape(what, L.B, L.C, L.H, L.W, L.hidden)) return e;
+  if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "%s: dtype %d", what, L.dtype);
+  if (L.norm_type != MGASPADE_NORM_IN && L.norm_type != MGASPADE_NORM_BN) return fail(MGACBAM_E_SHAPE, "%s: norm_type %d", what, L.norm_type);
+  const bool bn = L.norm_type == MGASPADE_NORM_BN;
+  if (bn && (!L.running_mean || !L.running_var)) return fail(MGACBAM_E_NULL, "%s: batch norm needs running_mean / running_var", what);
+  if (!(L.eps >= 0.f)) return fail(MGACBAM_E_SHAPE, "%s: eps=%g", what, L.eps);
+  const long long per = bn && L.training ? static_cast<long long>(L.B) * L.H * L.W : static_cast<long long>(L.H) * L.W;
+  if (!bwd && (!bn || L.training) && per < 2) return fail(MGACBAM_E_SHAPE, "%s: the normalisation needs more than one value per channel", what);
+  if (L.mask && (!L.w0 || !L.b0 || !L.wg || !L.bg || !L.wb || !L.bb)) return fail(MGACBAM_E_NULL, "%s: NULL parameter pointer", what);
+  if (bwd && L.mask && (!L.gw0 || !L.gb0 || !L.gwg || !L.gbg || !L.gwb || !L.gbb)) return fail(MGACBAM_E_NULL, "%s: NULL parameter-gradient pointer", what);
+  if (bwd && L.gmask && !L.mask) return fail(MGACBAM_E_NULL, "%s: gmask requested but mask is NULL", what);
+  if (!aligned_to(L.x, 16) || !aligned_to(L.ctx, 16) || (!bwd && !aligned_to(L.y, 16)) ||
+      (bwd && (!aligned_to(L.gy, 16) || !aligned_to(L.gx, 16) || !aligned_to(L.scratch, 16))) || (L.mask && !aligned_to(L.mask, 16)))
+    return fail(MGACBAM_E_ALIGN, "%s: x / y / gy / gx / ctx / scratch / mask must be 16-byte aligned", what);
+  const SpLayout CL = sp_ctx_layout(L.B, L.C, L.hidden);
+  const bool gamma_kept = L.mask && (bwd || L.save_gamma);
+  if (int e = check_capacity(what, "ctx", CL.base + (gamma_kept ? sp_gamma_bytes(L.B, L.C, L.H, L.W, elem_size(L.dtype)) : 0), L.ctx_bytes)) return e;
+  const SpScratch SL = sp_scratch_layout(L.B, L.C, L.H, L.W, L.hidden);
+  if (bwd) if (int e = check_capacity(what, "scratch", SL.total, L.scratch_bytes)) return e;
+  const SpTiling t = sp_tiling(L.H, L.W);
+  A = SpadeArgs{};
+  A.x = L.x; A.mask = L.mask; A.y = L.y; A.gy = L.gy; A.gx = L.gx; A.gmask = L.gmask;
+  A.w0 = L.w0; A.b0 = L.b0; A.wg = L.wg; A.bg = L.bg; A.wb = L.wb; A.bb = L.bb;
+  A.rmean = L.running_mean; A.rvar = L.running_var; A.nbt = L.num_batches_tracked;
+  A.gw0 = L.gw0; A.gb0 = L.gb0; A.gwg = L.gwg; A.gbg = L.gbg; A.gwb = L.gwb; A.gbb = L.gbb;
+  char* c = static_cast<char*>(L.ctx);
+  auto cf = [&](size_t off) { return reinterpret_cast<float*>(c + off); };
+  A.mean = cf(CL.mean); A.rstd = cf(CL.rstd); A.wpack = cf(CL.wpack); A.wpackT = cf(CL.wpackT);
+  A.gamma = gamma_kept ? static_cast<void*>(c + CL.gamma) : nullptr;
+  if (bwd) {
+    char* s = static_cast<char*>(L.scratch);
+    auto sf = [&](size_t off) { return reinterpret_cast<float*>(s + off); };
+    A.red = sf(SL.red); A.stat = sf(SL.stat); A.dwpart = sf(SL.dwpart); A.u = sf(SL.u); A.w0part = sf(SL.w0part);
+  }
+  A.B = L.B; A.C = L.C; A.H = L.H; A.W = L.W; A.HW = L.H * L.W; A.hid = L.hidden;
+  A.bn = bn; A.train = L.training ? 1 : 0; A.use_sigmoid = L.use_sigmoid_mask ? 1 : 0; A.has_mask = L.mask ? 1 : 0;
+  A.eps = L.eps; A.momentum = L.momentum;
+  A.TW = t.TW; A.TH = t.TH; A.ltw = t.ltw; A.tiles_x = t.tiles_x; A.tiles = t.tiles;
+  // channels per forward workgroup: halved while the grid is small, always whole 16-channel M tiles (the last block may hold fewer)
+  int cblk = std::min(L.C, 256);
+  while (cblk > 64 && static_cast<long long>(L.B) * t.tiles * ((L.C + cblk - 1) / cblk) < 512) cblk = (cblk / 2 + 15) & ~15;
+  A.cblk = cblk; A.ncb = (L.C + cblk - 1) / cblk;
+  A.nchunk = SL.nchunk; A.tpc = SL.tpc;
+  sig = Sig{L.dtype, 0, L.mask != nullptr, 0, bwd ? (L.gmask != nullptr) : (gamma_kept ? 1 : 0), 0};
+  sig.weight = L.C;
+  return 0;
+}
+static int sp_ew_blocks(const SpadeArgs& a) {
+  const long long n = (static_cast<long long>(a.B) * a.C * a.HW + kBlock - 1) / kBlock;
+  return static_cast<int>(std::min<long long>(n, 4096));
+}
+static int sp_plane_blocks(const SpadeArgs& a) { return (a.B * a.C + 3) / 4; }
+
+static int sp_forward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
+  Group<SpadeArgs> G;
+  G.n = n;
+  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
+  int grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return !a.bn ? sp_plane_blocks(a) : a.train ? a.C : (a.B * a.C + kBlock - 1) / kBlock; });
+#define CALL_SS(Tt) LAUNCH(k_spade_stats<Tt>, grid, 0, st, G)
+  SP_DISPATCH_T(sig.dtype, CALL_SS);
+#undef CALL_SS
+  if (int e = launch_status("k_spade_stats")) return e;
+  if (!sig.has_mask) {
+    grid = fill_starts(G, lv, n, sp_ew_blocks);
+#define CALL_SE(Tt) LAUNCH((k_spade_ew<Tt, 0>), grid, 0, st, G)
+    SP_DISPATCH_T(sig.dtype, CALL_SE);
+#undef CALL_SE
+    return launch_status("k_spade_ew");
+  }
+  grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (2 * a.C * a.hid * 9 + kBlock - 1) / kBlock; });
+  LAUNCH(k_spade_pack, grid, 0, st, G);
+  if (int e = launch_status("k_spade_pack")) return e;
+  size_t smem = 0;
+  for (int l = 0; l < n; ++l) smem = std::max(smem, sp_fwd_smem(lv[l]));
+  grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return a.B * a.tiles * a.ncb; });
+#define CALL_SF(Tt) if (sig.gmask) { sp_allow_lds(k_spade_fwd<Tt, true>, smem); LAUNCH((k_spade_fwd<Tt, true>), grid, smem, st, G); } \
+                    else { sp_allow_lds(k_spade_fwd<Tt, false>, smem); LAUNCH((k_spade_fwd<Tt, false>), grid, smem, st, G); }
+  SP_DISPATCH_T(sig.dtype, CALL_SF);
+#undef CALL_SF
+  return launch_status("k_spade_fwd");
+}
+
+static int sp_backward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
+  Group<SpadeArgs> G;
+  G.n = n;
+  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
+  int grid = fill_starts(G, lv, n, sp_plane_blocks);
+#define CALL_SR(Tt) LAUNCH(k_spade_bwd_reduce<Tt>, grid, 0, st, G)
+  SP_DISPATCH_T(sig.dtype, CALL_SR);
+#undef CALL_SR
+  if (int e = launch_status("k_spade_bwd_reduce")) return e;
+  grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (a.C + kBlock - 1) / kBlock; });
+  LAUNCH(k_spade_bwd_fin, grid, 0, st, G);
+  if (int e = launch_status("k_spade_bwd_fin")) return e;
+  if (sig.has_mask) {
+    size_t smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, sp_dw_smem(lv[l]));
+    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (a.C / 16) * a.nchunk; });
+#define CALL_SW(Tt) { sp_allow_lds(k_spade_dw<Tt>, smem); LAUNCH(k_spade_dw<Tt>, grid, smem, st, G); }
+    SP_DISPATCH_T(sig.dtype, CALL_SW);
+#undef CALL_SW
+    if (int e = launch_status("k_spade_dw")) return e;
+    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (2 * a.C * a.hid * 9 + kBlock - 1) / kBlock; });
+    LAUNCH(k_spade_dw_fin, grid, 0, st, G);
+    if (int e = launch_status("k_spade_dw_fin")) return e;
+    smem = 0;
+    for (int l = 0; l < n; ++l) smem = std::max(smem, sp_dh_smem(lv[l]));
+    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return a.B * a.tiles; });
+#define CALL_SH(Tt) { sp_allow_lds(k_spade_dh<Tt>, smem); LAUNCH(k_spade_dh<Tt>, grid, smem, st, G); }
+    SP_DISPATCH_T(sig.dtype, CALL_SH);
+#undef CALL_SH
+    if (int e = launch_status("k_spade_dh")) return e;
+    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return a.hid * 10; });
+    LAUNCH(k_spade_w0_fin, grid, 0, st, G);
+    if (int e = launch_status("k_spade_w0_fin")) return e;
+    if (sig.gmask) {
+      grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (a.B * a.HW + kBlock - 1) / kBlock; });
+      LAUNCH(k_spade_gmask, grid, 0, st, G);
+      if (int e = launch_status("k_spade_gmask")) return e;
+    }
+  }
+  grid = fill_starts(G, lv, n, sp_ew_blocks);
+#define CALL_SG(Tt) LAUNCH((k_spade_ew<Tt, 1>), grid, 0, st, G)
+  SP_DISPATCH_T(sig.dtype, CALL_SG);
+#undef CALL_SG
+  return launch_status("k_spade_ew");
+}
+
+static int sp_run(const char* what, const mgaspade_level_t* levels, int n_levels, void* stream, bool bwd) {
+  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
+  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
+  SpadeArgs args[MGACBAM_MAX_LEVELS];
+  Sig sigs[MGACBAM_MAX_LEVELS];
+  for (int l = 0; l < n_levels; ++l)
+    if (int e = sp_level(what, levels[l], bwd, args[l], sigs[l])) return e;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int e = for_each_group(args, sigs, n_levels, [&](SpadeArgs* g, int m, const Sig& s) {
+        return bwd ? sp_backward_group(g, m, s, st) : sp_forward_group(g, m, s, st); })) return e;
+  g_err[0] = 0;
+  return 0;
+}
+extern "C" int mgaspade_forward(const mgaspade_level_t* levels, int n_levels, void* stream) {
+  return sp_run("mgaspade_forward", levels, n_levels, stream, false);
+}
+extern "C" int mgaspade_backward(const mgaspade_level_t* levels, int n_levels, void* stream) {
+  return sp_run("mgaspade_backward", levels, n_levels, stream, true);
+}

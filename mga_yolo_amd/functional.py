@@ -681,3 +681,237 @@ def mask_head_pyramid(levels):
         state.append((rm, rv, nbt, eps, mom, tr))
         flat += [x, w1, g_, b_, wh, bh]
     return _HeadFn.apply(tuple(state), *flat)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# MaskSPADE (mga_yolo/nn/modules/masked_spade.py)
+# ---------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class SpadeConfig:
+    """Non-tensor state of a MaskSPADE call: the constructor's fields (masked_spade.py:30-37) and the norm's mode."""
+    hidden: int = 64
+    mask_channels: int = 1
+    norm_type: str = "in"
+    use_sigmoid_mask: bool = True
+    eps: float = 1e-6
+    momentum: float = 0.1
+    training: bool = True
+
+    @property
+    def bn(self) -> bool:
+        return self.norm_type.lower() == "bn"
+
+
+SPADE_MAX_C, SPADE_MAX_HIDDEN = 1024, 64
+_SPADE_SLOTS = 11    # x, mask, w0, b0, wg, bg, wb, bb, running_mean, running_var, num_batches_tracked
+_spade_warned = set()
+
+
+def spade_kernel_reason(x: torch.Tensor, mask: Optional[torch.Tensor], cfg: SpadeConfig) -> Optional[str]:
+    """None when the HIP kernels take this call; otherwise why the block's torch composition runs instead (documented limits, not errors)."""
+    Cc = x.shape[1]
+    if x.dtype not in _DTYPES:
+        return f"feature dtype {x.dtype}"
+    if mask is not None and (mask.dim() == 4 and mask.shape[1] != 1 or cfg.mask_channels > 1):
+        return "mask_channels > 1"
+    if cfg.hidden % 16 or cfg.hidden > SPADE_MAX_HIDDEN:
+        return f"hidden={cfg.hidden} (kernels: a multiple of 16, at most {SPADE_MAX_HIDDEN})"
+    if Cc % 16 or Cc > SPADE_MAX_C:
+        return f"C={Cc} (kernels: a multiple of 16, at most {SPADE_MAX_C})"
+    if x.numel() >= 2 ** 31:
+        return "feature of 2^31 elements or more"
+    return None
+
+
+def spade_check_norm(x: torch.Tensor, cfg: SpadeConfig) -> None:
+    """The inputs torch's norms refuse (torch.nn.functional: _verify_spatial_size / _verify_batch_size), refused the same way."""
+    B, Cc, H, W = x.shape
+    if not cfg.bn and H * W == 1:
+        raise ValueError(f"Expected more than 1 spatial element when training, got input size {x.size()}")
+    if cfg.bn and cfg.training and B * H * W == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
+
+
+def spade_compose(x, mask, params, cfg: SpadeConfig, running=None) -> torch.Tensor:
+    """The block as torch operators, on whatever device x lives (masked_spade.py:113-139): host tensors, and the device shapes outside the
+    kernels' limits (spade_kernel_reason)."""
+    import torch.nn.functional as F
+    w0, b0, wg, bg, wb, bb = params
+    if cfg.bn:
+        rm, rv, nbt = running
+        if cfg.training and nbt is not None:
+            nbt.add_(1)
+        x_hat = F.batch_norm(x, rm, rv, None, None, cfg.training, cfg.momentum, cfg.eps)
+    else:
+        x_hat = F.instance_norm(x, None, None, None, None, True, 0.1, cfg.eps)
+    if mask is None:
+        return x_hat
+    m = mask.unsqueeze(1) if mask.dim() == 3 else mask
+    H, W = x.shape[-2:]
+    if tuple(m.shape[-2:]) != (H, W):
+        m = F.interpolate(m, size=(H, W), mode="bilinear", align_corners=False)
+    if cfg.use_sigmoid_mask:
+        m = m.sigmoid()
+    h = F.relu(F.conv2d(m.to(wg.dtype), w0, b0, padding=1))
+    gamma = F.conv2d(h, wg, bg, padding=1).to(x.dtype)
+    beta = F.conv2d(h, wb, bb, padding=1).to(x.dtype)
+    return gamma * x_hat + beta
+
+
+class _SpadeFn(torch.autograd.Function):
+    """n independent levels; flat inputs = n x (x, mask|None, w0, b0, wg, bg, wb, bb, running_mean|None, running_var|None, nbt|None).
+    Forward: statistics, weight pack and ONE fused launch (MFMA convs + FiLM); backward: plain launches (csrc/spade.cuh)."""
+
+    @staticmethod
+    def forward(ctx, cfgs: Tuple[SpadeConfig, ...], *flat):
+        n = len(cfgs)
+        assert len(flat) == _SPADE_SLOTS * n and 1 <= n <= _lib.MAX_LEVELS
+        lib = _lib.load()
+        levels = (_lib.SpadeLevel * n)()
+        dev = flat[0].device
+        want_grad = any(ctx.needs_input_grad)
+        keep, outs, meta = [], [], []
+        for l in range(n):
+            x, mask, w0, b0, wg, bg, wb, bb, rm, rv, nbt = flat[_SPADE_SLOTS * l:_SPADE_SLOTS * (l + 1)]
+            cfg = cfgs[l]
+            if not x.is_cuda or x.device != dev:
+                raise RuntimeError("mask_spade: all features must live on the same GPU")
+            B, Cc, H, W = x.shape
+            xc = _aligned(x.detach())
+            m32 = None if mask is None else _aligned(mask.detach().reshape(B, 1, H, W).float())
+            ps = [None] * 6 if mask is None else [_aligned(t.detach().float()) for t in (w0, b0, wg, bg, wb, bb)]
+            y = torch.empty_like(xc)
+            elem = xc.element_size()
+            full = _lib.spade_ctx_bytes(B, Cc, H, W, cfg.hidden)
+            a16 = lambda v: (v + 15) & ~15
+            base = full - a16(xc.numel() * 4)
+            save = want_grad and m32 is not None
+            cbuf = torch.empty(base + (a16(xc.numel() * elem) if save else 0), dtype=torch.uint8, device=dev)
+            L = levels[l]
+            _spade_fill(L, xc, m32, ps, cfg, (rm, rv, nbt), cbuf)
+            L.y, L.save_gamma = y.data_ptr(), int(save)
+            keep += [xc, m32, cbuf] + ps
+            outs.append(y)
+            meta.append((None if mask is None else (mask.dtype, tuple(mask.shape)), (rm, rv, nbt)))
+        with torch.cuda.device(dev):
+            _lib.check(lib.mgaspade_forward(levels, n, _raw_stream(dev)), "mgaspade_forward")
+        ctx.save_for_backward(*keep)
+        ctx.cfgs, ctx.meta = cfgs, meta
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gys):
+        cfgs, n = ctx.cfgs, len(ctx.cfgs)
+        lib = _lib.load()
+        saved = ctx.saved_tensors
+        levels = (_lib.SpadeLevel * n)()
+        grads: List[Optional[torch.Tensor]] = [None]
+        hold = []
+        dev = saved[0].device
+        for l in range(n):
+            xc, m32, cbuf = saved[9 * l:9 * l + 3]
+            ps = list(saved[9 * l + 3:9 * l + 9])
+            cfg = cfgs[l]
+            B, Cc, H, W = xc.shape
+            gy = gys[l]
+            gy = torch.zeros_like(xc) if gy is None else _aligned(gy.to(xc.dtype))
+            gx = torch.empty_like(xc)
+            i0 = 1 + _SPADE_SLOTS * l
+            want_gmask = m32 is not None and ctx.needs_input_grad[i0 + 1]
+            gmask = torch.empty_like(m32) if want_gmask else None
+            gps = [None] * 6 if m32 is None else [torch.empty_like(p) for p in ps]
+            scratch = torch.empty(_lib.spade_scratch_bytes(B, Cc, H, W, cfg.hidden), dtype=torch.uint8, device=dev)
+            L = levels[l]
+            _spade_fill(L, xc, m32, ps, cfg, ctx.meta[l][1], cbuf)
+            L.gy, L.gx, L.gmask = gy.data_ptr(), gx.data_ptr(), (None if gmask is None else gmask.data_ptr())
+            if m32 is not None:
+                L.gw0, L.gb0, L.gwg, L.gbg, L.gwb, L.gbb = [g.data_ptr() for g in gps]
+            L.scratch, L.scratch_bytes = scratch.data_ptr(), scratch.numel()
+            hold += [gy, scratch]
+            grads += [gx, gmask] + gps + [None, None, None]
+        with torch.cuda.device(dev):
+            _lib.check(lib.mgaspade_backward(levels, n, _raw_stream(dev)), "mgaspade_backward")
+        del hold
+        for l in range(n):
+            i1 = 1 + _SPADE_SLOTS * l + 1
+            if grads[i1] is not None:
+                mdtype, mshape = ctx.meta[l][0]
+                grads[i1] = grads[i1].reshape(mshape).to(mdtype)
+        return tuple(grads)
+
+
+def _spade_fill(L, xc, m32, ps, cfg: SpadeConfig, running, cbuf) -> None:
+    B, Cc, H, W = xc.shape
+    L.x, L.mask = xc.data_ptr(), (None if m32 is None else m32.data_ptr())
+    if m32 is not None:
+        L.w0, L.b0, L.wg, L.bg, L.wb, L.bb = [p.data_ptr() for p in ps]
+    rm, rv, nbt = running
+    if cfg.bn:
+        L.running_mean, L.running_var = rm.data_ptr(), rv.data_ptr()
+        L.num_batches_tracked = None if nbt is None else nbt.data_ptr()
+    L.ctx, L.ctx_bytes = cbuf.data_ptr(), cbuf.numel()
+    L.B, L.C, L.H, L.W, L.hidden, L.dtype = B, Cc, H, W, cfg.hidden, _DTYPES[xc.dtype]
+    L.norm_type, L.training = (_lib.NORM_BN if cfg.bn else _lib.NORM_IN), int(cfg.training)
+    L.use_sigmoid_mask, L.eps, L.momentum, L.flags = int(cfg.use_sigmoid_mask), cfg.eps, cfg.momentum, 0
+
+
+def _spade_prepare(x, mask, params, cfg: SpadeConfig, running):
+    """Checks shared by the single and the pyramid call; returns the flat slots of a kernel level, or None when the torch composition takes it."""
+    if x.dim() != 4:
+        raise AssertionError("feature must be (B,C,H,W)")                        # masked_spade.py:119
+    spade_check_norm(x, cfg)
+    why = spade_kernel_reason(x, mask, cfg)
+    if why is not None:
+        if why not in _spade_warned:
+            _spade_warned.add(why)
+            import warnings
+            warnings.warn(f"MaskSPADE: {why}: this call runs the block's torch composition on the device, not the HIP kernels")
+        return None
+    B, Cc, H, W = x.shape
+    if mask is not None:
+        m = mask.unsqueeze(1) if mask.dim() == 3 else mask
+        if m.dim() != 4 or m.shape[0] != B:
+            raise RuntimeError(f"mask shape {tuple(mask.shape)} does not match feature batch {B}")
+        if tuple(m.shape[-2:]) != (H, W):                                        # resampled on the device, differentiably, then the kernels
+            mask = torch.nn.functional.interpolate(m.float(), size=(H, W), mode="bilinear", align_corners=False)
+        want = {"shared.0.weight": (cfg.hidden, 1, 3, 3), "shared.0.bias": (cfg.hidden,), "conv_gamma.weight": (Cc, cfg.hidden, 3, 3),
+                "conv_gamma.bias": (Cc,), "conv_beta.weight": (Cc, cfg.hidden, 3, 3), "conv_beta.bias": (Cc,)}
+        for (name, shape), t in zip(want.items(), params):
+            if tuple(t.shape) != shape or t.device != x.device:
+                raise ValueError(f"MaskSPADE parameter {name}: expected {shape} on {x.device}, got {tuple(t.shape)} on {t.device}")
+    rm, rv, nbt = running if running is not None else (None, None, None)
+    if cfg.bn:
+        if rm is None or rv is None or rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous():
+            raise ValueError("MaskSPADE with norm_type='bn' needs contiguous fp32 running_mean / running_var")
+    if not x.is_contiguous():
+        x = x.contiguous()                                                       # channels_last and every other layout: one copy to NCHW
+    return [x, mask] + list(params) + [rm, rv, nbt]
+
+
+def mask_spade(x: torch.Tensor, mask: Optional[torch.Tensor], params: Sequence[torch.Tensor], cfg: SpadeConfig, running=None) -> torch.Tensor:
+    """y = gamma(mask) * norm(x) + beta(mask) for a device tensor.  params = (shared.0.weight, shared.0.bias, conv_gamma.weight,
+    conv_gamma.bias, conv_beta.weight, conv_beta.bias); running = (running_mean, running_var, num_batches_tracked) for norm_type 'bn'
+    (updated in place by a training call).  Gradients reach x, the mask and the six parameters."""
+    flat = _spade_prepare(x, mask, params, cfg, running)
+    if flat is None:
+        return spade_compose(x, mask, params, cfg, running)
+    return _SpadeFn.apply((cfg,), *flat)[0]
+
+
+def mask_spade_pyramid(levels):
+    """levels: [(x, mask|None, params, SpadeConfig[, running]), ...] -> tuple of outputs.  The levels the kernels take share one library
+    call each way; a level outside their limits runs the torch composition."""
+    outs: List[Optional[torch.Tensor]] = [None] * len(levels)
+    cfgs, flat, idx = [], [], []
+    for i, lv in enumerate(levels):
+        x, mask, params, cfg = lv[:4]
+        running = lv[4] if len(lv) > 4 else None
+        f = _spade_prepare(x, mask, params, cfg, running)
+        if f is None:
+            outs[i] = spade_compose(x, mask, params, cfg, running)
+        else:
+            cfgs.append(cfg); flat += f; idx.append(i)
+    if cfgs:
+        for i, y in zip(idx, _SpadeFn.apply(tuple(cfgs), *flat)):
+            outs[i] = y
+    return tuple(outs)

@@ -17,13 +17,15 @@ used for a device tensor, and a device tensor with the library missing raises.
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass as _dataclass
 from typing import Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .functional import BlockConfig, EcaConfig, mask_cbam, mask_eca, mask_head, prob_mask_gate
+from .functional import (BlockConfig, EcaConfig, SpadeConfig, mask_cbam, mask_eca, mask_head, mask_spade, prob_mask_gate,
+                         spade_compose)
 
 _GATER_MODES = ("deterministic", "gumbel", "hard_st", "bernoulli_detach")
 
@@ -274,6 +276,84 @@ def _eca_host_forward(x, mask, w, beta, cfg: EcaConfig) -> torch.Tensor:
         v = masked * valid + gap * (1.0 - valid)
     gate = torch.sigmoid(F.conv1d(v.unsqueeze(1).to(w.dtype), w, padding=cfg.k // 2).squeeze(1)).view(B, Cc, 1, 1)
     return x * (1.0 + F.softplus(beta).to(gate.dtype) * (gate - 0.5)).to(x.dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# MaskSPADE: mirror of mga_yolo/nn/modules/masked_spade.py
+# ---------------------------------------------------------------------------------------------------------
+
+
+@_dataclass
+class MaskSPADEConfig:
+    """The reference's ``cfg`` dataclass, field for field (masked_spade.py:30-37)."""
+    channels: int
+    hidden: int = 64
+    mask_channels: int = 1
+    norm_type: str = "in"
+    use_sigmoid_mask: bool = True
+    eps: float = 1e-6
+
+
+class MaskSPADE(nn.Module):
+    """Mask-conditioned SPADE: ``y = gamma(m) * norm(x) + beta(m)``, gamma / beta = two 3x3 convolutions of ``relu(conv3x3(mask))``.
+    Same constructor, submodule creation and initialisation order (so the same seed gives the same ``state_dict``), ``cfg`` /
+    ``scale_name`` / ``extra_repr`` and ``[feat, mask]`` input as the reference class.  Device tensors run the HIP kernels (statistics,
+    weight pack and one fused MFMA launch forward; plain launches backward) for ``mask_channels == 1``, ``hidden`` a multiple of 16 up to
+    64 and ``C`` a multiple of 16 up to 1024; a mask of another size is resampled on the device first and a channels_last feature is
+    copied to NCHW once.  Every other device configuration runs the block's torch composition on the device (one warning per reason);
+    host tensors always do."""
+
+    def __init__(self, channels: int, hidden: int = 64, mask_channels: int = 1, norm_type: str = "in", use_sigmoid_mask: bool = True,
+                 eps: float = 1e-6) -> None:
+        super().__init__()
+        self.cfg = MaskSPADEConfig(channels=channels, hidden=hidden, mask_channels=mask_channels, norm_type=norm_type,
+                                   use_sigmoid_mask=use_sigmoid_mask, eps=eps)
+        self.norm: nn.Module
+        if norm_type.lower() == "bn":
+            self.norm = nn.BatchNorm2d(channels, affine=False, eps=eps)
+        else:
+            self.norm = nn.InstanceNorm2d(channels, affine=False, eps=eps)
+        self.shared = nn.Sequential(nn.Conv2d(max(1, mask_channels), hidden, kernel_size=3, padding=1, bias=True), nn.ReLU(inplace=True))
+        self.conv_gamma = nn.Conv2d(hidden, channels, kernel_size=3, padding=1, bias=True)
+        self.conv_beta = nn.Conv2d(hidden, channels, kernel_size=3, padding=1, bias=True)
+        self.scale_name: str = {256: "P3", 512: "P4", 1024: "P5"}.get(channels, f"C{channels}")
+        self._initialize()
+
+    def _initialize(self) -> None:                                # masked_spade.py:91-99 (same module traversal order)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+
+    def spade_config(self) -> SpadeConfig:
+        bn = isinstance(self.norm, nn.BatchNorm2d)
+        mom = self.norm.momentum if bn and self.norm.momentum is not None else 0.1
+        return SpadeConfig(hidden=int(self.cfg.hidden), mask_channels=int(self.cfg.mask_channels), norm_type="bn" if bn else "in",
+                           use_sigmoid_mask=bool(self.cfg.use_sigmoid_mask), eps=float(self.norm.eps), momentum=float(mom),
+                           training=bool(self.norm.training) if bn else True)
+
+    def spade_params(self):
+        c0 = self.shared[0]
+        return (c0.weight, c0.bias, self.conv_gamma.weight, self.conv_gamma.bias, self.conv_beta.weight, self.conv_beta.bias)
+
+    def forward(self, x: Union[torch.Tensor, Sequence[torch.Tensor]]) -> torch.Tensor:
+        if isinstance(x, (list, tuple)):
+            assert len(x) == 2, "MaskSPADE expects [feature, mask] as inputs"
+            feat, mask = x
+        else:
+            feat, mask = x, None
+        assert isinstance(feat, torch.Tensor) and feat.dim() == 4, "feature must be (B,C,H,W)"
+        cfg = self.spade_config()
+        running = (self.norm.running_mean, self.norm.running_var, self.norm.num_batches_tracked) if cfg.bn else None
+        if feat.is_cuda:
+            return mask_spade(feat, mask, self.spade_params(), cfg, running)
+        return spade_compose(feat, mask, self.spade_params(), cfg, running)
+
+    def extra_repr(self) -> str:
+        c = self.cfg
+        return (f"C={c.channels}, hidden={c.hidden}, maskC={c.mask_channels}, norm={c.norm_type}, "
+                f"sigmoid_mask={c.use_sigmoid_mask}, scale='{self.scale_name}'")
 
 
 # ---------------------------------------------------------------------------------------------------------
