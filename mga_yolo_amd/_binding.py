@@ -1,0 +1,162 @@
+"""The torch side of the binding: the one place where tensors become C-ABI level structs (include/mgacbam.h, include/mgaspade.h) and
+where a library entry point is called on torch's current stream.  One fill function per struct sets EVERY field of it; the autograd
+Functions (functional.py, segloss.py) and the static plans (plan.py, slice.py) all build their level tables here and differ only in the
+arguments they pass.  Sizes are asked in _lib.py (`_lib.size`)."""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib
+
+DTYPES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}    # element type -> ABI code
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+# ---- library calls
+def raw_stream(dev: torch.device) -> int:
+    """hipStream_t of torch's current stream on `dev` (the private accessor is ~10x cheaper than building a Stream object: this
+    sits on the eager path's per-call critical path)."""
+    try:
+        return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
+    except AttributeError:
+        return torch.cuda.current_stream(dev).cuda_stream
+
+
+class on_device:
+    """`with torch.cuda.device(dev)` only when dev is not already current (the common case costs one integer compare)."""
+    __slots__ = ("dev", "guard")
+
+    def __init__(self, dev):
+        self.dev, self.guard = dev, None
+
+    def __enter__(self):
+        idx = self.dev.index
+        if idx is not None and idx != torch.cuda.current_device():
+            self.guard = torch.cuda.device(self.dev)
+            self.guard.__enter__()
+
+    def __exit__(self, *a):
+        if self.guard is not None:
+            self.guard.__exit__(*a)
+
+
+def call(name: str, dev: torch.device, *args) -> None:
+    """Entry point `name`(*args, stream) on the stream that is current on `dev` NOW (looked up on every call: the caller may be inside
+    torch.cuda.stream(...)); a non-zero return code raises with the entry point's name."""
+    with on_device(dev):
+        rc = getattr(_lib.load(), name)(*args, raw_stream(dev))
+    if rc:
+        _lib.check(rc, name)
+
+
+# ---- MaskCBAM
+def cbam_params(params: Sequence[torch.Tensor], cfg) -> _lib.Params:
+    w1, b1, w2, b2, wsa, beta = params
+    return _lib.Params(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), wsa.data_ptr(), beta.data_ptr(),
+                       cfg.hidden, cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
+
+
+def fill_cbam_fwd(L: _lib.FwdLevel, x, mask, y, ctx, params, cfg, flags: int = 0, ws=None) -> None:
+    """flags: LAYOUT_NHWC (x, y channels_last; needs ws, the per-chunk pooling partials) | FWD_SAVE_PROJ."""
+    B, Cc, H, W = x.shape
+    L.x, L.mask, L.y, L.ctx, L.ctx_bytes = x.data_ptr(), _ptr(mask), y.data_ptr(), ctx.data_ptr(), ctx.numel()
+    L.p = cbam_params(params, cfg)
+    L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, DTYPES[x.dtype], flags
+    L.ws, L.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+
+
+def fill_cbam_bwd(L: _lib.BwdLevel, x, mask, gy, ctx, scratch, gx, gmask, pgrads, params, cfg, flags: int = 0) -> None:
+    """pgrads: (gw1, gb1, gw2, gb2, gwsa, gbeta); flags: LAYOUT_NHWC | BWD_HAVE_PROJ."""
+    B, Cc, H, W = x.shape
+    L.x, L.mask, L.gy, L.ctx, L.scratch = x.data_ptr(), _ptr(mask), gy.data_ptr(), ctx.data_ptr(), scratch.data_ptr()
+    L.ctx_bytes, L.scratch_bytes = ctx.numel(), scratch.numel()
+    L.gx, L.gmask = gx.data_ptr(), _ptr(gmask)
+    L.gw1, L.gb1, L.gw2, L.gb2, L.gwsa, L.gbeta = (t.data_ptr() for t in pgrads)
+    L.p = cbam_params(params, cfg)
+    L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, DTYPES[x.dtype], flags
+
+
+# ---- MaskECA
+def eca_params(w, beta, cfg) -> _lib.EcaParams:
+    return _lib.EcaParams(w.data_ptr(), beta.data_ptr(), cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
+
+
+def fill_eca_fwd(L: _lib.EcaFwdLevel, x, mask, y, ctx, w, beta, cfg, flags: int = 0) -> None:
+    B, Cc, H, W = x.shape
+    L.x, L.mask, L.y, L.ctx, L.ctx_bytes = x.data_ptr(), _ptr(mask), y.data_ptr(), ctx.data_ptr(), ctx.numel()
+    L.p = eca_params(w, beta, cfg)
+    L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, DTYPES[x.dtype], flags
+
+
+def fill_eca_bwd(L: _lib.EcaBwdLevel, x, mask, gy, ctx, scratch, gx, gmask, gw, gbeta, w, beta, cfg, flags: int = 0) -> None:
+    B, Cc, H, W = x.shape
+    L.x, L.mask, L.gy, L.ctx, L.scratch = x.data_ptr(), _ptr(mask), gy.data_ptr(), ctx.data_ptr(), scratch.data_ptr()
+    L.ctx_bytes, L.scratch_bytes = ctx.numel(), scratch.numel()
+    L.gx, L.gmask, L.gw, L.gbeta = gx.data_ptr(), _ptr(gmask), gw.data_ptr(), gbeta.data_ptr()
+    L.p = eca_params(w, beta, cfg)
+    L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, DTYPES[x.dtype], flags
+
+
+# ---- MGAMaskHead
+def head_params(w1, gamma, beta, rmean, rvar, nbt, wh, bh, hidden, eps, momentum, training) -> _lib.HeadParams:
+    return _lib.HeadParams(w1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), _ptr(nbt),
+                           wh.data_ptr(), bh.data_ptr(), hidden, eps, momentum, int(training))
+
+
+def fill_head_fwd(L: _lib.HeadFwdLevel, x, logits, ctx, params, running, hidden, eps, momentum, training, flags: int = 0) -> None:
+    """params: (proj.0.weight, proj.1.weight, proj.1.bias, head.weight, head.bias); running: (running_mean, running_var,
+    num_batches_tracked | None); flags: HEAD_LAYOUT_NHWC | HEAD_LOGITS_F32."""
+    B, Cc, H, W = x.shape
+    L.x, L.logits, L.ctx, L.ctx_bytes = x.data_ptr(), logits.data_ptr(), ctx.data_ptr(), ctx.numel()
+    L.p = head_params(*params[:3], *running, *params[3:], hidden, eps, momentum, training)
+    L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, DTYPES[x.dtype], flags
+
+
+def fill_head_bwd(L: _lib.HeadBwdLevel, x, g_logits, g_logits2, ctx, scratch, gx, pgrads, params, running, hidden, eps, momentum,
+                  training, flags: int = 0) -> None:
+    """g_logits2: a second dL/dlogits summed while the backward loads them (slice.SlicePlan: MaskCBAM's dL/dmask), or None;
+    pgrads: gradients in the order of params; flags: HEAD_LAYOUT_NHWC | HEAD_BWD_ACCUM_GX | HEAD_LOGITS_F32.  The backward never
+    counts a batch: its parameter struct carries no num_batches_tracked, whatever `running` holds."""
+    B, Cc, H, W = x.shape
+    L.x, L.g_logits, L.g_logits2 = x.data_ptr(), g_logits.data_ptr(), _ptr(g_logits2)
+    L.ctx, L.scratch, L.gx = ctx.data_ptr(), scratch.data_ptr(), gx.data_ptr()
+    L.ctx_bytes, L.scratch_bytes = ctx.numel(), scratch.numel()
+    L.gw1, L.gbn_weight, L.gbn_bias, L.gwh, L.gbh = (t.data_ptr() for t in pgrads)
+    L.p = head_params(*params[:3], running[0], running[1], None, *params[3:], hidden, eps, momentum, training)
+    L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, DTYPES[x.dtype], flags
+
+
+# ---- segmentation loss
+def fill_seg(L: _lib.SegLevel, logits, target, glogits, scale_weight: float, resize: int) -> None:
+    """logits (B,1,H,W), target (B,1,Ht,Wt) fp32; glogits: where the backward writes dL/dlogits, None in a forward-only table."""
+    B, _, H, W = logits.shape
+    L.logits, L.target, L.glogits = logits.data_ptr(), target.data_ptr(), _ptr(glogits)
+    L.B, L.H, L.W, L.Ht, L.Wt = B, H, W, target.shape[-2], target.shape[-1]
+    L.dtype, L.scale_weight, L.resize = DTYPES[logits.dtype], scale_weight, resize
+
+
+# ---- MaskSPADE: one struct for both directions
+_SPADE_P = ("w0", "b0", "wg", "bg", "wb", "bb")
+
+
+def fill_spade(L: _lib.SpadeLevel, x, mask, params, cfg, running, ctx, y=None, save_gamma: bool = False,
+               gy=None, gx=None, gmask=None, pgrads=None, scratch=None) -> None:
+    """params / pgrads: six tensors, or six None for a level without a mask; running: (running_mean, running_var, num_batches_tracked),
+    read for norm_type 'bn' only.  Forward passes y and save_gamma, backward gy, gx, gmask, pgrads and scratch."""
+    B, Cc, H, W = x.shape
+    L.x, L.mask, L.y, L.gy, L.gx, L.gmask = x.data_ptr(), _ptr(mask), _ptr(y), _ptr(gy), _ptr(gx), _ptr(gmask)
+    for name, p, g in zip(_SPADE_P, params, pgrads or (None,) * 6):
+        setattr(L, name, _ptr(p))
+        setattr(L, "g" + name, _ptr(g))
+    rm, rv, nbt = running if cfg.bn else (None, None, None)
+    L.running_mean, L.running_var, L.num_batches_tracked = _ptr(rm), _ptr(rv), _ptr(nbt)
+    L.ctx, L.ctx_bytes = ctx.data_ptr(), ctx.numel()
+    L.scratch, L.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel())
+    L.B, L.C, L.H, L.W, L.hidden, L.dtype = B, Cc, H, W, cfg.hidden, DTYPES[x.dtype]
+    L.norm_type, L.training = (_lib.NORM_BN if cfg.bn else _lib.NORM_IN), int(cfg.training)
+    L.use_sigmoid_mask, L.save_gamma, L.eps, L.momentum, L.flags = int(cfg.use_sigmoid_mask), int(save_gamma), cfg.eps, cfg.momentum, 0

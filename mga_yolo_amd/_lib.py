@@ -229,91 +229,71 @@ def check(rc: int, what: str):
         raise RuntimeError(f"{what}: {kind} {rc}: {msg}")
 
 
-_size_cache = {}     # (fn, shape...) -> bytes: the eager path asks on every call; the answer only depends on the shape
+_size_cache = {}     # (symbol, ints...) -> bytes: the eager path asks on every call; the answer only depends on the shape and the knobs
 
 
-def ctx_bytes(B, Cc, H, W, hidden) -> int:
-    key = ("ctx", B, Cc, H, W, hidden)
+def size(symbol: str, *ints) -> int:
+    """The one size query: `symbol`(*ints) in bytes, cached until reload_env(); 0 is the library's refusal and raises as E_SHAPE."""
+    key = (symbol, *ints)
     n = _size_cache.get(key)
     if n is None:
-        n = load().mgacbam_ctx_bytes(B, Cc, H, W, hidden)
+        n = getattr(load(), symbol)(*ints)
         if n == 0:
-            check(-2, "mgacbam_ctx_bytes")
+            check(E_SHAPE, symbol)
         _size_cache[key] = n
     return n
+
+
+# The plain and the _flags form of a query agree at flags = 0 (tests/test_abi.py pins every pair), so each block asks the _flags form only.
+def ctx_bytes(B, Cc, H, W, hidden) -> int:
+    return size("mgacbam_ctx_bytes", B, Cc, H, W, hidden)
 
 
 def scratch_bytes(B, Cc, H, W, hidden, k, flags: int = 0) -> int:
-    key = ("scratch", B, Cc, H, W, hidden, k, flags & LAYOUT_NHWC)
-    n = _size_cache.get(key)
-    if n is None:
-        if flags & LAYOUT_NHWC:
-            n = load().mgacbam_bwd_scratch_bytes_flags(B, Cc, H, W, hidden, k, LAYOUT_NHWC)
-        else:
-            n = load().mgacbam_bwd_scratch_bytes(B, Cc, H, W, hidden, k)
-        if n == 0:
-            check(-2, "mgacbam_bwd_scratch_bytes")
-        _size_cache[key] = n
-    return n
+    return size("mgacbam_bwd_scratch_bytes_flags", B, Cc, H, W, hidden, k, flags & LAYOUT_NHWC)
 
 
 def fwd_ws_bytes(B, Cc, H, W, hidden, flags: int) -> int:
     """Forward workspace of a level: 0 for NCHW levels, the per-chunk pooling partials for LAYOUT_NHWC levels."""
-    if not flags & LAYOUT_NHWC:
-        return 0
-    key = ("ws", B, Cc, H, W, hidden)
-    n = _size_cache.get(key)
-    if n is None:
-        n = load().mgacbam_fwd_ws_bytes(B, Cc, H, W, hidden, LAYOUT_NHWC)
-        if n == 0:
-            check(-2, "mgacbam_fwd_ws_bytes")
-        _size_cache[key] = n
-    return n
+    return size("mgacbam_fwd_ws_bytes", B, Cc, H, W, hidden, LAYOUT_NHWC) if flags & LAYOUT_NHWC else 0
 
 
 def eca_ctx_bytes(B, Cc, H, W, flags: int = 0) -> int:
     """ctx of a MaskECA level: the saved statistics, plus the per-chunk pooling partials for LAYOUT_NHWC levels."""
-    key = ("eca_ctx", B, Cc, H, W, flags & LAYOUT_NHWC)
-    n = _size_cache.get(key)
-    if n is None:
-        n = load().mgacbam_eca_ctx_bytes_flags(B, Cc, H, W, flags & LAYOUT_NHWC)
-        if n == 0:
-            check(-2, "mgacbam_eca_ctx_bytes_flags")
-        _size_cache[key] = n
-    return n
+    return size("mgacbam_eca_ctx_bytes_flags", B, Cc, H, W, flags & LAYOUT_NHWC)
 
 
 def eca_scratch_bytes(B, Cc, H, W, flags: int = 0) -> int:
     """Backward scratch of a MaskECA level: gg, plus its per-chunk partials for LAYOUT_NHWC levels."""
-    key = ("eca_scratch", B, Cc, H, W, flags & LAYOUT_NHWC)
-    n = _size_cache.get(key)
-    if n is None:
-        n = load().mgacbam_eca_scratch_bytes_flags(B, Cc, H, W, flags & LAYOUT_NHWC)
-        if n == 0:
-            check(-2, "mgacbam_eca_scratch_bytes_flags")
-        _size_cache[key] = n
-    return n
+    return size("mgacbam_eca_scratch_bytes_flags", B, Cc, H, W, flags & LAYOUT_NHWC)
 
 
-def _spade_size(which: str, B, Cc, H, W, hidden) -> int:
-    key = ("spade_" + which, B, Cc, H, W, hidden)
-    n = _size_cache.get(key)
-    if n is None:
-        n = getattr(load(), f"mgaspade_{which}_bytes")(B, Cc, H, W, hidden)
-        if n == 0:
-            check(-2, f"mgaspade_{which}_bytes")
-        _size_cache[key] = n
-    return n
+def head_ctx_bytes(B, Cc, H, W, hidden, flags: int = 0) -> int:
+    """ctx of a mask-head level; only HEAD_LAYOUT_NHWC changes the size (the other level flags do not)."""
+    return size("mgahead_ctx_bytes_flags", B, Cc, H, W, hidden, flags & HEAD_LAYOUT_NHWC)
+
+
+def head_scratch_bytes(B, Cc, H, W, hidden, flags: int = 0) -> int:
+    """Backward scratch of a mask-head level; only HEAD_LAYOUT_NHWC changes the size."""
+    return size("mgahead_bwd_scratch_bytes_flags", B, Cc, H, W, hidden, flags & HEAD_LAYOUT_NHWC)
 
 
 def spade_ctx_bytes(B, Cc, H, W, hidden) -> int:
     """ctx of a MaskSPADE level: statistics, the packed conv weights and the saved gamma (sized for fp32 features)."""
-    return _spade_size("ctx", B, Cc, H, W, hidden)
+    return size("mgaspade_ctx_bytes", B, Cc, H, W, hidden)
 
 
 def spade_scratch_bytes(B, Cc, H, W, hidden) -> int:
     """Backward scratch of a MaskSPADE level: plane sums, the split-K partials of dW, the tap planes of ds, the dW0 partials."""
-    return _spade_size("scratch", B, Cc, H, W, hidden)
+    return size("mgaspade_scratch_bytes", B, Cc, H, W, hidden)
+
+
+def seg_ws_bytes(levels, n: int) -> int:
+    """Workspace of a segmentation-loss call.  It depends on the whole level table, not on a few integers, so it is asked every time."""
+    nbytes = load().mgaseg_ws_bytes(levels, n)
+    if nbytes == 0:
+        check(E_SHAPE, "mgaseg_ws_bytes")
+    return nbytes
 
 
 def sync_regions(B, Cc, H, W) -> dict:

@@ -18,6 +18,9 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._binding import DTYPES as _DTYPES, call as _call, raw_stream as _raw_stream
+from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_head_bwd, fill_head_fwd, fill_spade
+from ._binding import head_params as _head_params  # noqa: F401  (tests fill head levels by hand with it)
 
 
 @dataclass(frozen=True)
@@ -30,34 +33,6 @@ class BlockConfig:
     eps: float = 1e-6
 
 
-_DTYPES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
-
-
-def _raw_stream(dev: torch.device) -> int:
-    """hipStream_t of torch's current stream on `dev` (the private accessor is ~10x cheaper than building a Stream object: this
-    sits on the eager path's per-call critical path)."""
-    try:
-        return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
-    except AttributeError:
-        return torch.cuda.current_stream(dev).cuda_stream
-
-
-class _on_device:
-    """`with torch.cuda.device(dev)` only when dev is not already current (the common case costs one integer compare)."""
-    __slots__ = ("dev", "guard")
-
-    def __init__(self, dev):
-        self.dev, self.guard = dev, None
-
-    def __enter__(self):
-        idx = self.dev.index
-        if idx is not None and idx != torch.cuda.current_device():
-            self.guard = torch.cuda.device(self.dev)
-            self.guard.__enter__()
-
-    def __exit__(self, *a):
-        if self.guard is not None:
-            self.guard.__exit__(*a)
 # k_chan + k_apply as ONE x-resident launch (k_gate, MGACBAM_FWD_FUSE); MGACBAM_FUSE_FWD=0 restores the three-launch forward
 _FUSE_FWD = bool(int(os.environ.get("MGACBAM_FUSE_FWD", "1")))
 # transposed conv folded into the k_bwd_reduce1 launch (MGACBAM_BWD_FOLD); needs the zero-filled ctx tail the fused forward sets up
@@ -178,37 +153,64 @@ def _ready_nhwc(t: torch.Tensor) -> torch.Tensor:
     return t.detach().clone(memory_format=torch.channels_last)
 
 
-def _mask32(mask: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
-    m = mask
-    if m.dim() == 3:
-        m = m.unsqueeze(1)
-    if m.dtype != torch.float32:
-        m = m.float()
-    return _ready(m)
+def _param32(t: torch.Tensor) -> torch.Tensor:
+    """A parameter as the kernels read it: fp32, detached, contiguous, aligned (MaskECA, the mask head and MaskSPADE cast; MaskCBAM
+    refuses anything but fp32, _check_params)."""
+    return _ready(t.float())
 
 
-def _check_level(x: torch.Tensor, mask: Optional[torch.Tensor], params: Sequence[torch.Tensor], cfg: BlockConfig):
+def _mask_in(mask: Optional[torch.Tensor], B: int, H: int, W: int):
+    """-> (the mask as the kernels read it: fp32 (B,1,H,W), detached, aligned; (dtype, shape) it came in), or (None, None)."""
+    if mask is None:
+        return None, None
+    m = mask.unsqueeze(1) if mask.dim() == 3 else mask                        # masked_cbam.py:81-85
+    if tuple(m.shape) != (B, 1, H, W):                                        # the reference's expand() raises too
+        raise RuntimeError(f"mask shape {tuple(mask.shape)} does not match feature (B,1,H,W)=({B},1,{H},{W})")
+    return _ready(m if m.dtype == torch.float32 else m.float()), (mask.dtype, tuple(mask.shape))
+
+
+def _grad_in(gy: Optional[torch.Tensor], like: torch.Tensor, nhwc: bool) -> torch.Tensor:
+    """The incoming gradient of an output in `like`'s element type and layout: zeros for None, a gy of any other layout converted once."""
+    if gy is None:
+        return torch.zeros_like(like)
+    gy = gy.to(like.dtype)
+    return _ready_nhwc(gy) if nhwc else _aligned(gy)
+
+
+def _gmask_out(grads: list, slots: int, metas: Sequence[Optional[tuple]]) -> None:
+    """Give dL/dmask (slot 1 of each level's `slots` gradients, after the leading None) back in the mask's own shape / element type.
+    This runs AFTER the launch that writes it: a cast enqueued before it would read unwritten memory (that was the case for
+    half-precision masks until the AMP test of round 3)."""
+    for l, meta in enumerate(metas):
+        i = 2 + l * slots
+        if grads[i] is not None:
+            grads[i] = grads[i].reshape(meta[1]).to(meta[0])
+
+
+def _check_feature(x: torch.Tensor, what: str) -> None:
     if x.dim() != 4:
-        raise AssertionError("MaskCBAM expects a (B,C,H,W) feature")          # masked_cbam.py:160
+        raise AssertionError(what)
     if x.dtype not in _DTYPES:
         raise TypeError(f"unsupported feature dtype {x.dtype}")
-    B, Cc, H, W = x.shape
-    if mask is not None:
-        m = mask.unsqueeze(1) if mask.dim() == 3 else mask                    # masked_cbam.py:81-85
-        if tuple(m.shape) != (B, 1, H, W):                                    # the reference's expand() raises too
-            raise RuntimeError(f"mask shape {tuple(mask.shape)} does not match feature (B,1,H,W)=({B},1,{H},{W})")
-    w1, b1, w2, b2, wsa, beta = params
-    h, k = cfg.hidden, cfg.k
+
+
+def _check_params(x: torch.Tensor, params: Sequence[torch.Tensor], cfg: BlockConfig) -> None:
+    Cc, h, k = x.shape[1], cfg.hidden, cfg.k
     want = {"w1": (h, Cc), "b1": (h,), "w2": (Cc, h), "b2": (Cc,), "wsa": (1, 3, k, k), "beta": ()}
     for name, t in zip(want, params):
         if tuple(t.shape) != want[name] or t.dtype != torch.float32 or t.device != x.device:
             raise ValueError(f"parameter {name}: expected fp32 {want[name]} on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
-def _params_struct(params: Sequence[torch.Tensor], cfg: BlockConfig) -> _lib.Params:
-    w1, b1, w2, b2, wsa, beta = params
-    return _lib.Params(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), wsa.data_ptr(), beta.data_ptr(),
-                       cfg.hidden, cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
+def _cbam_inputs(x, mask, params, cfg: BlockConfig):
+    """Checks (the AssertionError / TypeError / RuntimeError / ValueError split mirrors the reference, in its order) and the tensors a
+    MaskCBAM level reads -> (x, fp32 mask | None, params, level flags, mask meta).  The layout decides the kernels, per level; y keeps it."""
+    _check_feature(x, "MaskCBAM expects a (B,C,H,W) feature")                 # masked_cbam.py:160
+    B, _, H, W = x.shape
+    m32, mmeta = _mask_in(mask, B, H, W)
+    _check_params(x, params, cfg)
+    nhwc = _is_nhwc(x)
+    return (_ready_nhwc(x) if nhwc else _ready(x)), m32, [_ready(p) for p in params], (_lib.LAYOUT_NHWC if nhwc else 0), mmeta
 
 
 class _PyramidFn(torch.autograd.Function):
@@ -218,7 +220,7 @@ class _PyramidFn(torch.autograd.Function):
     def forward(ctx, cfgs: Tuple[BlockConfig, ...], *flat):
         n = len(cfgs)
         assert len(flat) == n * SLOTS and 1 <= n <= _lib.MAX_LEVELS
-        lib = _lib.load()
+        _lib.load()                                             # a missing library is the first thing a call reports
         levels = (_lib.FwdLevel * n)()
         keep: List[Optional[torch.Tensor]] = []
         outs, meta, leases, layouts, hold = [], [], [], [], []
@@ -231,13 +233,8 @@ class _PyramidFn(torch.autograd.Function):
             cfg = cfgs[l]
             if not x.is_cuda or x.device != dev:
                 raise RuntimeError("mask_cbam: all features must live on the same GPU")
-            _check_level(x, mask, params, cfg)
+            xc, m32, pc, flags, mmeta = _cbam_inputs(x, mask, params, cfg)
             B, Cc, H, W = x.shape
-            nhwc = _is_nhwc(x)                                  # the layout decides the kernels, per level; y keeps it
-            flags = _lib.LAYOUT_NHWC if nhwc else 0
-            xc = _ready_nhwc(x) if nhwc else _ready(x)
-            m32 = None if mask is None else _mask32(mask, B, H, W)
-            pc = [_ready(p) for p in params]
             y = torch.empty_like(xc)
             # FWD_FUSE / BWD_FOLD contract: the hand-off flags at the end of ctx were zero-filled once (by the pool, at creation)
             # (the flags count calls PER TILE, so a buffer is only reused under the tiling it was used with.  The library derives every
@@ -246,27 +243,19 @@ class _PyramidFn(torch.autograd.Function):
             #  channel instead: tests/test_gpu_composition.py)
             key = (dev.index, stream, B, Cc, H, W, cfg.hidden, x.dtype, _lib.ENV_EPOCH, cfg.k) + ((flags,) if flags else ())
             lease = _Lease(key, _POOL.take(key, _lib.ctx_bytes(B, Cc, H, W, cfg.hidden), _lib.ctx_layout(B, Cc, H, W, cfg.hidden)["sync"], dev))
-            cbuf = lease.buf
             leases.append(lease)
-            L = levels[l]
-            L.x, L.mask, L.y, L.ctx = xc.data_ptr(), (None if m32 is None else m32.data_ptr()), y.data_ptr(), cbuf.data_ptr()
-            L.ctx_bytes = cbuf.numel()
-            L.p = _params_struct(pc, cfg)
-            L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[x.dtype]
-            if nhwc:                                            # per-chunk pooling partials, consumed inside this call
+            ws = None
+            if flags:                                           # per-chunk pooling partials, consumed inside this call
                 ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, flags), dtype=torch.uint8, device=dev)
-                L.ws, L.ws_bytes, L.flags = ws.data_ptr(), ws.numel(), flags
                 hold.append(ws)
-            # (L.flags has no SAVE_PROJ: the backward makes the W1-projection planes itself where they pay (include/mgacbam.h), and the
+            # (no SAVE_PROJ in flags: the backward makes the W1-projection planes itself where they pay (include/mgacbam.h), and the
             #  forward keeps k_gate; PyramidPlan(use_proj=True) and forward_with_ctx still drive the forward producer, k_chan)
+            fill_cbam_fwd(levels[l], xc, m32, y, lease.buf, pc, cfg, flags, ws)
             keep += [xc, m32, *pc]
             outs.append(y)
             layouts.append(flags)
-            meta.append(None if mask is None else (mask.dtype, tuple(mask.shape)))
-        with _on_device(dev):
-            rc = lib.mgacbam_forward_stages(levels, n, _FWD_STAGES, stream)
-        if rc:
-            _lib.check(rc, "mgacbam_forward_stages")
+            meta.append(mmeta)
+        _call("mgacbam_forward_stages", dev, levels, n, _FWD_STAGES)
         del hold
         if _CHECK_HANDOFF:
             _check_status([(ls.buf, ls.key[2:7]) for ls in leases], "mask_cbam forward")
@@ -277,51 +266,28 @@ class _PyramidFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gys):
         cfgs, n = ctx.cfgs, len(ctx.cfgs)
-        lib = _lib.load()
         saved = ctx.saved_tensors
-        per = 2 + 6
         levels = (_lib.BwdLevel * n)()
         grads: List[Optional[torch.Tensor]] = [None]
         hold = []
         dev = saved[0].device
         for l in range(n):
-            xc, m32, *pc = saved[l * per:(l + 1) * per]
-            cbuf = ctx.leases[l].buf
+            xc, m32, *pc = saved[l * SLOTS:(l + 1) * SLOTS]
             cfg = cfgs[l]
             B, Cc, H, W = xc.shape
             flags = ctx.layouts[l]
-            gy = gys[l]
-            if gy is None:
-                gy = torch.zeros_like(xc)
-            elif flags & _lib.LAYOUT_NHWC:                         # a gy of any other layout is converted once
-                gy = _ready_nhwc(gy.to(xc.dtype))
-            else:
-                gy = _aligned(gy.to(xc.dtype))
+            gy = _grad_in(gys[l], xc, flags & _lib.LAYOUT_NHWC)
             want_gmask = m32 is not None and ctx.needs_input_grad[1 + l * SLOTS + 1]
             gx = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
             gmask = torch.empty_like(m32) if want_gmask else None
             pg = [torch.empty_like(p) for p in pc]
             scratch = torch.empty(_lib.scratch_bytes(B, Cc, H, W, cfg.hidden, cfg.k, flags), dtype=torch.uint8, device=dev)
-            L = levels[l]
-            L.x, L.mask, L.gy, L.ctx, L.scratch = (xc.data_ptr(), None if m32 is None else m32.data_ptr(), gy.data_ptr(),
-                                                   cbuf.data_ptr(), scratch.data_ptr())
-            L.ctx_bytes, L.scratch_bytes = cbuf.numel(), scratch.numel()
-            L.gx, L.gmask = gx.data_ptr(), (None if gmask is None else gmask.data_ptr())
-            L.gw1, L.gb1, L.gw2, L.gb2, L.gwsa, L.gbeta = (t.data_ptr() for t in pg)
-            L.p = _params_struct(pc, cfg)
-            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[xc.dtype], flags
+            fill_cbam_bwd(levels[l], xc, m32, gy, ctx.leases[l].buf, scratch, gx, gmask, pg, pc, cfg, flags)
             hold += [gy, scratch]
             grads += [gx, gmask, *pg]
-        with _on_device(dev):
-            rc = lib.mgacbam_backward_stages(levels, n, _BWD_STAGES, _raw_stream(dev))
-        if rc:
-            _lib.check(rc, "mgacbam_backward_stages")
+        _call("mgacbam_backward_stages", dev, levels, n, _BWD_STAGES)
         del hold
-        for l in range(n):                                         # dL/dmask in the mask's own shape / element type -- AFTER the launch that
-            gm = grads[1 + l * SLOTS + 1]                          # writes it (a cast enqueued before it would read unwritten memory: that
-            if gm is not None:                                     # was the case for half-precision masks until the AMP test of round 3)
-                mdtype, mshape = ctx.meta[l]
-                grads[1 + l * SLOTS + 1] = gm.reshape(mshape).to(mdtype)
+        _gmask_out(grads, SLOTS, ctx.meta)
         if _CHECK_HANDOFF:
             _check_status([(ls.buf, ls.key[2:7]) for ls in ctx.leases], "mask_cbam backward")
         return tuple(grads)
@@ -347,28 +313,14 @@ def mask_cbam(x: torch.Tensor, mask: Optional[torch.Tensor], w1, b1, w2, b2, wsa
 def forward_with_ctx(x, mask, params, cfg: BlockConfig, save_proj: bool = True):
     """-> (y, {name: tensor view into ctx}) without autograd; names follow mgacbam_ctx_layout_t.  A channels_last x runs the
     channels-last kernels (y comes back channels_last); the ctx views are the same for both layouts."""
-    lib = _lib.load()
-    _check_level(x, mask, params, cfg)
+    xc, m32, pc, flags, _ = _cbam_inputs(x.detach(), None if mask is None else mask.detach(), [p.detach() for p in params], cfg)
     B, Cc, H, W = x.shape
-    nhwc = _is_nhwc(x)
-    xc = _ready_nhwc(x.detach()) if nhwc else _aligned(x.detach())
-    m32 = None if mask is None else _aligned(mask.detach().reshape(B, 1, H, W).float())
-    pc = [_aligned(p.detach()) for p in params]
     y = torch.empty_like(xc)
     cbuf = torch.zeros(_lib.ctx_bytes(B, Cc, H, W, cfg.hidden), dtype=torch.uint8, device=x.device)
+    ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, flags), dtype=torch.uint8, device=x.device) if flags else None
     lv = (_lib.FwdLevel * 1)()
-    L = lv[0]
-    L.x, L.mask, L.y, L.ctx = xc.data_ptr(), (None if m32 is None else m32.data_ptr()), y.data_ptr(), cbuf.data_ptr()
-    L.ctx_bytes = cbuf.numel()
-    L.p = _params_struct(pc, cfg)
-    L.B, L.C, L.H, L.W, L.dtype = B, Cc, H, W, _DTYPES[x.dtype]
-    L.flags = _lib.FWD_SAVE_PROJ if (save_proj and mask is not None) else 0
-    ws = None
-    if nhwc:
-        ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, _lib.LAYOUT_NHWC), dtype=torch.uint8, device=x.device)
-        L.ws, L.ws_bytes, L.flags = ws.data_ptr(), ws.numel(), L.flags | _lib.LAYOUT_NHWC
-    with torch.cuda.device(x.device):
-        _lib.check(lib.mgacbam_forward(lv, 1, torch.cuda.current_stream(x.device).cuda_stream), "mgacbam_forward")
+    fill_cbam_fwd(lv[0], xc, m32, y, cbuf, pc, cfg, flags | (_lib.FWD_SAVE_PROJ if (save_proj and mask is not None) else 0), ws)
+    _call("mgacbam_forward", x.device, lv, 1)
     return y, ctx_views(cbuf, B, Cc, H, W, cfg.hidden)
 
 
@@ -416,7 +368,7 @@ class _EcaFn(torch.autograd.Function):
     def forward(ctx, cfgs: Tuple[EcaConfig, ...], *flat):
         n = len(cfgs)
         assert len(flat) == 4 * n and 1 <= n <= _lib.MAX_LEVELS
-        lib = _lib.load()
+        _lib.load()                                             # a missing library is the first thing a call reports
         levels = (_lib.EcaFwdLevel * n)()
         keep, outs, meta, layouts = [], [], [], []
         dev = flat[0].device
@@ -425,35 +377,23 @@ class _EcaFn(torch.autograd.Function):
             cfg = cfgs[l]
             if not x.is_cuda or x.device != dev:
                 raise RuntimeError("mask_eca: all features must live on the same GPU")
-            if x.dim() != 4:
-                raise AssertionError("feature must be (B,C,H,W)")                    # masked_eca.py:174
-            if x.dtype not in _DTYPES:
-                raise TypeError(f"unsupported feature dtype {x.dtype}")
+            _check_feature(x, "feature must be (B,C,H,W)")                            # masked_eca.py:174
             B, Cc, H, W = x.shape
-            if mask is not None:
-                m4 = mask.unsqueeze(1) if mask.dim() == 3 else mask
-                if tuple(m4.shape) != (B, 1, H, W):
-                    raise RuntimeError(f"mask shape {tuple(mask.shape)} does not match feature (B,1,H,W)=({B},1,{H},{W})")
+            m32, mmeta = _mask_in(mask, B, H, W)
             if tuple(w.shape) != (1, 1, cfg.k) or beta.dim() != 0:
                 raise ValueError(f"MaskECA parameters: expected conv1d.weight (1,1,{cfg.k}) and scalar beta")
             nhwc = _is_nhwc(x) and Cc <= _ECA_NHWC_MAX_C
             flags = _lib.LAYOUT_NHWC if nhwc else 0
-            xc = _ready_nhwc(x) if nhwc else _aligned(x.detach())
-            m32 = None if mask is None else _aligned(mask.detach().reshape(B, 1, H, W).float())
-            wc, bc = _aligned(w.detach().float()), _aligned(beta.detach().float())
+            xc = _ready_nhwc(x) if nhwc else _ready(x)
+            wc, bc = _param32(w), _param32(beta)
             y = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
             cbuf = torch.empty(_lib.eca_ctx_bytes(B, Cc, H, W, flags), dtype=torch.uint8, device=dev)
-            L = levels[l]
-            L.x, L.mask, L.y, L.ctx = xc.data_ptr(), (None if m32 is None else m32.data_ptr()), y.data_ptr(), cbuf.data_ptr()
-            L.ctx_bytes = cbuf.numel()
-            L.p = _lib.EcaParams(wc.data_ptr(), bc.data_ptr(), cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
-            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[x.dtype], flags
+            fill_eca_fwd(levels[l], xc, m32, y, cbuf, wc, bc, cfg, flags)
             keep += [xc, m32, cbuf, wc, bc]
             outs.append(y)
             layouts.append(flags)
-            meta.append(None if mask is None else (mask.dtype, tuple(mask.shape)))
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgacbam_eca_forward(levels, n, torch.cuda.current_stream(dev).cuda_stream), "mgacbam_eca_forward")
+            meta.append(mmeta)
+        _call("mgacbam_eca_forward", dev, levels, n)
         ctx.save_for_backward(*keep)
         ctx.cfgs, ctx.meta, ctx.layouts = cfgs, meta, layouts
         return tuple(outs)
@@ -461,7 +401,6 @@ class _EcaFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gys):
         cfgs, n = ctx.cfgs, len(ctx.cfgs)
-        lib = _lib.load()
         saved = ctx.saved_tensors
         levels = (_lib.EcaBwdLevel * n)()
         grads: List[Optional[torch.Tensor]] = [None]
@@ -469,38 +408,20 @@ class _EcaFn(torch.autograd.Function):
         dev = saved[0].device
         for l in range(n):
             xc, m32, cbuf, wc, bc = saved[5 * l:5 * l + 5]
-            cfg = cfgs[l]
             B, Cc, H, W = xc.shape
             flags = ctx.layouts[l]
-            gy = gys[l]
-            if gy is None:
-                gy = torch.zeros_like(xc)
-            elif flags & _lib.LAYOUT_NHWC:                         # a gy of any other layout is converted once
-                gy = _ready_nhwc(gy.to(xc.dtype))
-            else:
-                gy = _aligned(gy.to(xc.dtype))
+            gy = _grad_in(gys[l], xc, flags & _lib.LAYOUT_NHWC)
             want_gmask = m32 is not None and ctx.needs_input_grad[1 + 4 * l + 1]
             gx = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
             gmask = torch.empty_like(m32) if want_gmask else None
             gw, gb = torch.empty_like(wc), torch.empty_like(bc)
             scratch = torch.empty(_lib.eca_scratch_bytes(B, Cc, H, W, flags), dtype=torch.uint8, device=dev)
-            L = levels[l]
-            L.x, L.mask, L.gy, L.ctx, L.scratch = (xc.data_ptr(), None if m32 is None else m32.data_ptr(), gy.data_ptr(),
-                                                   cbuf.data_ptr(), scratch.data_ptr())
-            L.ctx_bytes, L.scratch_bytes = cbuf.numel(), scratch.numel()
-            L.gx, L.gmask, L.gw, L.gbeta = gx.data_ptr(), (None if gmask is None else gmask.data_ptr()), gw.data_ptr(), gb.data_ptr()
-            L.p = _lib.EcaParams(wc.data_ptr(), bc.data_ptr(), cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
-            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[xc.dtype], flags
+            fill_eca_bwd(levels[l], xc, m32, gy, cbuf, scratch, gx, gmask, gw, gb, wc, bc, cfgs[l], flags)
             hold += [gy, scratch]
             grads += [gx, gmask, gw, gb]
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgacbam_eca_backward(levels, n, torch.cuda.current_stream(dev).cuda_stream), "mgacbam_eca_backward")
+        _call("mgacbam_eca_backward", dev, levels, n)
         del hold
-        for l in range(n):                                         # (after the launch that writes it, see _PyramidFn.backward)
-            gm = grads[1 + 4 * l + 1]
-            if gm is not None:
-                mdtype, mshape = ctx.meta[l]
-                grads[1 + 4 * l + 1] = gm.reshape(mshape).to(mdtype)
+        _gmask_out(grads, 4, ctx.meta)
         return tuple(grads)
 
 
@@ -526,14 +447,12 @@ def resize_nearest(src: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
     mga_yolo/nn/losses/segmentation.py:103-110, bit-exact (pure gather)."""
     if not src.is_cuda or src.dtype != torch.float32 or src.dim() < 2:
         raise TypeError("resize_nearest expects an fp32 device tensor (..., H, W)")
-    lib = _lib.load()
+    _lib.load()
     s = _aligned(src)
     in_h, in_w = s.shape[-2:]
     planes = s.numel() // (in_h * in_w)
     dst = torch.empty(*s.shape[:-2], out_h, out_w, dtype=torch.float32, device=s.device)
-    with torch.cuda.device(s.device):
-        _lib.check(lib.mgacbam_resize_nearest(s.data_ptr(), dst.data_ptr(), planes, in_h, in_w, out_h, out_w,
-                                              torch.cuda.current_stream(s.device).cuda_stream), "mgacbam_resize_nearest")
+    _call("mgacbam_resize_nearest", s.device, s.data_ptr(), dst.data_ptr(), planes, in_h, in_w, out_h, out_w)
     return dst
 
 
@@ -543,15 +462,13 @@ def resize_nearest(src: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
 class _GaterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, u1, u2, tau: float, p_min: float, threshold: float, hard: bool):
-        lib = _lib.load()
+        _lib.load()
         pc, a, b = (_ready(t) for t in (p, u1, u2))
         if pc.dtype != torch.float32 or a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape != pc.shape or b.shape != pc.shape:
             raise RuntimeError("prob_mask_gate: p, u1, u2 must be fp32 tensors of one shape")
         out, msoft = torch.empty_like(pc), torch.empty_like(pc)
         cfg = _lib.PmgCfg(float(tau), float(p_min), float(threshold), int(bool(hard)))
-        with torch.cuda.device(pc.device):
-            _lib.check(lib.mgapmg_forward(pc.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), msoft.data_ptr(), pc.numel(),
-                                          C.byref(cfg), torch.cuda.current_stream(pc.device).cuda_stream), "mgapmg_forward")
+        _call("mgapmg_forward", pc.device, pc.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), msoft.data_ptr(), pc.numel(), C.byref(cfg))
         ctx.save_for_backward(pc, msoft)
         ctx.cfg = (float(tau), float(p_min), float(threshold), int(bool(hard)))
         return out
@@ -559,13 +476,10 @@ class _GaterFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         pc, msoft = ctx.saved_tensors
-        lib = _lib.load()
         g = _ready(gout.to(torch.float32))
         gp = torch.empty_like(pc)
         cfg = _lib.PmgCfg(*ctx.cfg)
-        with torch.cuda.device(pc.device):
-            _lib.check(lib.mgapmg_backward(pc.data_ptr(), msoft.data_ptr(), g.data_ptr(), gp.data_ptr(), pc.numel(), C.byref(cfg),
-                                           torch.cuda.current_stream(pc.device).cuda_stream), "mgapmg_backward")
+        _call("mgapmg_backward", pc.device, pc.data_ptr(), msoft.data_ptr(), g.data_ptr(), gp.data_ptr(), pc.numel(), C.byref(cfg))
         return gp, None, None, None, None, None, None
 
 
@@ -580,11 +494,6 @@ def prob_mask_gate(p: torch.Tensor, u1: torch.Tensor, u2: torch.Tensor, tau: flo
 # MGAMaskHead: Conv1x1 -> BatchNorm2d -> SiLU -> Conv3x3 as 3 launches forward, 5 backward (csrc/head.cuh); a channels_last
 # feature takes the NHWC forms of the GEMM kernels (csrc/head_nhwc.cuh) without a copy, and its gx comes back channels_last
 # ---------------------------------------------------------------------------------------------------------
-def _head_params(w1, gamma, beta, rmean, rvar, nbt, wh, bh, hidden, eps, momentum, training) -> "_lib.HeadParams":
-    return _lib.HeadParams(w1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(),
-                           None if nbt is None else nbt.data_ptr(), wh.data_ptr(), bh.data_ptr(), hidden, eps, momentum, int(training))
-
-
 class _HeadFn(torch.autograd.Function):
     """n independent levels; flat inputs = n x (x, proj.0.weight, proj.1.weight, proj.1.bias, head.weight, head.bias);
     ``state`` = per level (running_mean, running_var, num_batches_tracked | None, eps, momentum, training): buffers updated in place."""
@@ -593,7 +502,7 @@ class _HeadFn(torch.autograd.Function):
     def forward(ctx, state: tuple, *flat):
         n = len(state)
         assert len(flat) == 6 * n and 1 <= n <= _lib.MAX_LEVELS
-        lib = _lib.load()
+        _lib.load()                                             # a missing library is the first thing a call reports
         levels = (_lib.HeadFwdLevel * n)()
         keep, outs, meta = [], [], []
         dev = flat[0].device
@@ -613,21 +522,17 @@ class _HeadFn(torch.autograd.Function):
             nhwc = _is_nhwc(x)                                  # the layout decides the GEMM kernels, per level (MaskCBAM's rule)
             fl = _lib.HEAD_LAYOUT_NHWC if nhwc else 0
             xc = _ready_nhwc(x) if nhwc else _ready(x)
-            pc = [_ready(t.float() if t.dtype != torch.float32 else t) for t in (w1, gamma, beta, wh, bh)]
+            pc = [_param32(t) for t in (w1, gamma, beta, wh, bh)]
             for t in (rmean, rvar):
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
                     raise ValueError("mask_head: running statistics must be contiguous fp32 tensors on the feature's device")
             logits = torch.empty(B, 1, H, W, dtype=x.dtype, device=dev)
-            cbuf = torch.empty(lib.mgahead_ctx_bytes_flags(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
-            L = levels[l]
-            L.x, L.logits, L.ctx, L.ctx_bytes = xc.data_ptr(), logits.data_ptr(), cbuf.data_ptr(), cbuf.numel()
-            L.p = _head_params(*pc[:3], rmean, rvar, nbt, *pc[3:], hid, float(eps), float(momentum), training)
-            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[x.dtype], fl
+            cbuf = torch.empty(_lib.head_ctx_bytes(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
+            fill_head_fwd(levels[l], xc, logits, cbuf, pc, (rmean, rvar, nbt), hid, float(eps), float(momentum), training, fl)
             keep += [xc, cbuf, *pc, rmean, rvar]
             outs.append(logits)
             meta.append((hid, float(eps), float(momentum), bool(training), tuple(w1.shape), fl))
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgahead_forward(levels, n, torch.cuda.current_stream(dev).cuda_stream), "mgahead_forward")
+        _call("mgahead_forward", dev, levels, n)
         ctx.save_for_backward(*keep)
         ctx.meta = meta
         return tuple(outs)
@@ -635,32 +540,25 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gls):
         n = len(ctx.meta)
-        lib = _lib.load()
         saved = ctx.saved_tensors
         levels = (_lib.HeadBwdLevel * n)()
         grads: List[Optional[torch.Tensor]] = [None]
         hold = []
         dev = saved[0].device
         for l in range(n):
-            xc, cbuf, w1, gamma, beta, wh, bh, rmean, rvar = saved[9 * l:9 * l + 9]
+            xc, cbuf, *pc, rmean, rvar = saved[9 * l:9 * l + 9]
             hid, eps, momentum, training, w1_shape, fl = ctx.meta[l]
             B, Cc, H, W = xc.shape
             gl = gls[l]
             gl = torch.zeros(B, 1, H, W, dtype=xc.dtype, device=dev) if gl is None else _aligned(gl.to(xc.dtype))
             gx = torch.empty_like(xc, memory_format=torch.channels_last if fl else torch.contiguous_format)
-            pg = [torch.empty_like(t) for t in (w1, gamma, beta, wh, bh)]
-            scratch = torch.empty(lib.mgahead_bwd_scratch_bytes_flags(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
-            L = levels[l]
-            L.x, L.g_logits, L.g_logits2, L.ctx, L.scratch, L.gx = xc.data_ptr(), gl.data_ptr(), None, cbuf.data_ptr(), scratch.data_ptr(), gx.data_ptr()
-            L.ctx_bytes, L.scratch_bytes = cbuf.numel(), scratch.numel()
-            L.gw1, L.gbn_weight, L.gbn_bias, L.gwh, L.gbh = (t.data_ptr() for t in pg)
-            L.p = _head_params(w1, gamma, beta, rmean, rvar, None, wh, bh, hid, eps, momentum, training)
-            L.B, L.C, L.H, L.W, L.dtype, L.flags = B, Cc, H, W, _DTYPES[xc.dtype], fl
+            pg = [torch.empty_like(t) for t in pc]
+            scratch = torch.empty(_lib.head_scratch_bytes(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
+            fill_head_bwd(levels[l], xc, gl, None, cbuf, scratch, gx, pg, pc, (rmean, rvar), hid, eps, momentum, training, fl)
             hold += [gl, scratch]
             pg[0] = pg[0].view(w1_shape)
             grads += [gx, *pg]
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgahead_backward(levels, n, torch.cuda.current_stream(dev).cuda_stream), "mgahead_backward")
+        _call("mgahead_backward", dev, levels, n)
         del hold
         return tuple(grads)
 
@@ -766,20 +664,20 @@ class _SpadeFn(torch.autograd.Function):
     def forward(ctx, cfgs: Tuple[SpadeConfig, ...], *flat):
         n = len(cfgs)
         assert len(flat) == _SPADE_SLOTS * n and 1 <= n <= _lib.MAX_LEVELS
-        lib = _lib.load()
+        _lib.load()                                             # a missing library is the first thing a call reports
         levels = (_lib.SpadeLevel * n)()
         dev = flat[0].device
         want_grad = any(ctx.needs_input_grad)
-        keep, outs, meta = [], [], []
+        keep, outs, meta, running = [], [], [], []
         for l in range(n):
             x, mask, w0, b0, wg, bg, wb, bb, rm, rv, nbt = flat[_SPADE_SLOTS * l:_SPADE_SLOTS * (l + 1)]
             cfg = cfgs[l]
             if not x.is_cuda or x.device != dev:
                 raise RuntimeError("mask_spade: all features must live on the same GPU")
             B, Cc, H, W = x.shape
-            xc = _aligned(x.detach())
-            m32 = None if mask is None else _aligned(mask.detach().reshape(B, 1, H, W).float())
-            ps = [None] * 6 if mask is None else [_aligned(t.detach().float()) for t in (w0, b0, wg, bg, wb, bb)]
+            xc = _ready(x)
+            m32, mmeta = _mask_in(mask, B, H, W)
+            ps = [None] * 6 if mask is None else [_param32(t) for t in (w0, b0, wg, bg, wb, bb)]
             y = torch.empty_like(xc)
             elem = xc.element_size()
             full = _lib.spade_ctx_bytes(B, Cc, H, W, cfg.hidden)
@@ -787,22 +685,19 @@ class _SpadeFn(torch.autograd.Function):
             base = full - a16(xc.numel() * 4)
             save = want_grad and m32 is not None
             cbuf = torch.empty(base + (a16(xc.numel() * elem) if save else 0), dtype=torch.uint8, device=dev)
-            L = levels[l]
-            _spade_fill(L, xc, m32, ps, cfg, (rm, rv, nbt), cbuf)
-            L.y, L.save_gamma = y.data_ptr(), int(save)
+            fill_spade(levels[l], xc, m32, ps, cfg, (rm, rv, nbt), cbuf, y=y, save_gamma=save)
             keep += [xc, m32, cbuf] + ps
             outs.append(y)
-            meta.append((None if mask is None else (mask.dtype, tuple(mask.shape)), (rm, rv, nbt)))
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgaspade_forward(levels, n, _raw_stream(dev)), "mgaspade_forward")
+            meta.append(mmeta)
+            running.append((rm, rv, nbt))
+        _call("mgaspade_forward", dev, levels, n)
         ctx.save_for_backward(*keep)
-        ctx.cfgs, ctx.meta = cfgs, meta
+        ctx.cfgs, ctx.meta, ctx.running = cfgs, meta, running
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *gys):
         cfgs, n = ctx.cfgs, len(ctx.cfgs)
-        lib = _lib.load()
         saved = ctx.saved_tensors
         levels = (_lib.SpadeLevel * n)()
         grads: List[Optional[torch.Tensor]] = [None]
@@ -813,46 +708,19 @@ class _SpadeFn(torch.autograd.Function):
             ps = list(saved[9 * l + 3:9 * l + 9])
             cfg = cfgs[l]
             B, Cc, H, W = xc.shape
-            gy = gys[l]
-            gy = torch.zeros_like(xc) if gy is None else _aligned(gy.to(xc.dtype))
+            gy = _grad_in(gys[l], xc, False)
             gx = torch.empty_like(xc)
-            i0 = 1 + _SPADE_SLOTS * l
-            want_gmask = m32 is not None and ctx.needs_input_grad[i0 + 1]
+            want_gmask = m32 is not None and ctx.needs_input_grad[1 + _SPADE_SLOTS * l + 1]
             gmask = torch.empty_like(m32) if want_gmask else None
             gps = [None] * 6 if m32 is None else [torch.empty_like(p) for p in ps]
             scratch = torch.empty(_lib.spade_scratch_bytes(B, Cc, H, W, cfg.hidden), dtype=torch.uint8, device=dev)
-            L = levels[l]
-            _spade_fill(L, xc, m32, ps, cfg, ctx.meta[l][1], cbuf)
-            L.gy, L.gx, L.gmask = gy.data_ptr(), gx.data_ptr(), (None if gmask is None else gmask.data_ptr())
-            if m32 is not None:
-                L.gw0, L.gb0, L.gwg, L.gbg, L.gwb, L.gbb = [g.data_ptr() for g in gps]
-            L.scratch, L.scratch_bytes = scratch.data_ptr(), scratch.numel()
+            fill_spade(levels[l], xc, m32, ps, cfg, ctx.running[l], cbuf, gy=gy, gx=gx, gmask=gmask, pgrads=gps, scratch=scratch)
             hold += [gy, scratch]
             grads += [gx, gmask] + gps + [None, None, None]
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgaspade_backward(levels, n, _raw_stream(dev)), "mgaspade_backward")
+        _call("mgaspade_backward", dev, levels, n)
         del hold
-        for l in range(n):
-            i1 = 1 + _SPADE_SLOTS * l + 1
-            if grads[i1] is not None:
-                mdtype, mshape = ctx.meta[l][0]
-                grads[i1] = grads[i1].reshape(mshape).to(mdtype)
+        _gmask_out(grads, _SPADE_SLOTS, ctx.meta)
         return tuple(grads)
-
-
-def _spade_fill(L, xc, m32, ps, cfg: SpadeConfig, running, cbuf) -> None:
-    B, Cc, H, W = xc.shape
-    L.x, L.mask = xc.data_ptr(), (None if m32 is None else m32.data_ptr())
-    if m32 is not None:
-        L.w0, L.b0, L.wg, L.bg, L.wb, L.bb = [p.data_ptr() for p in ps]
-    rm, rv, nbt = running
-    if cfg.bn:
-        L.running_mean, L.running_var = rm.data_ptr(), rv.data_ptr()
-        L.num_batches_tracked = None if nbt is None else nbt.data_ptr()
-    L.ctx, L.ctx_bytes = cbuf.data_ptr(), cbuf.numel()
-    L.B, L.C, L.H, L.W, L.hidden, L.dtype = B, Cc, H, W, cfg.hidden, _DTYPES[xc.dtype]
-    L.norm_type, L.training = (_lib.NORM_BN if cfg.bn else _lib.NORM_IN), int(cfg.training)
-    L.use_sigmoid_mask, L.eps, L.momentum, L.flags = int(cfg.use_sigmoid_mask), cfg.eps, cfg.momentum, 0
 
 
 def _spade_prepare(x, mask, params, cfg: SpadeConfig, running):

@@ -17,7 +17,8 @@ import os
 import torch
 
 from . import _lib
-from .functional import BlockConfig, HandoffTimeout, _DTYPES, _params_struct, ctx_views
+from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd
+from .functional import BlockConfig, HandoffTimeout, ctx_views
 
 PARAM_NAMES = ("w1", "b1", "w2", "b2", "wsa", "beta")
 
@@ -61,20 +62,10 @@ class PyramidPlan:
                 views.append(self.grad_bucket[off:off + p.numel()].view(p.shape))
                 off += p.numel()
             self.param_grads.append(views)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            F, Bw = self._fwd[l], self._bwd[l]
-            F.x, F.mask, F.y, F.ctx = ptr(self.x[l]), ptr(self.mask[l]), ptr(self.y[l]), ptr(self.ctx[l])
-            F.ctx_bytes = self.ctx[l].numel()
-            F.p = _params_struct(ps, cfg)
-            F.B, F.C, F.H, F.W, F.dtype = B, C, H, W, _DTYPES[dtype]
-            F.flags = _lib.FWD_SAVE_PROJ if (with_mask and want_gmask and use_proj) else 0
-            Bw.x, Bw.mask, Bw.gy, Bw.ctx, Bw.scratch = ptr(self.x[l]), ptr(self.mask[l]), ptr(self.gy[l]), ptr(self.ctx[l]), ptr(self.scratch[l])
-            Bw.ctx_bytes, Bw.scratch_bytes = self.ctx[l].numel(), self.scratch[l].numel()
-            Bw.gx, Bw.gmask = ptr(self.gx[l]), ptr(self.gmask[l])
-            Bw.gw1, Bw.gb1, Bw.gw2, Bw.gb2, Bw.gwsa, Bw.gbeta = (v.data_ptr() for v in views)
-            Bw.p = _params_struct(ps, cfg)
-            Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype = B, C, H, W, _DTYPES[dtype]
-            Bw.flags = _lib.BWD_HAVE_PROJ if (with_mask and want_gmask and use_proj) else 0
+            proj = with_mask and want_gmask and use_proj     # the forward saves the W1-projection planes, the backward reads them
+            fill_cbam_fwd(self._fwd[l], self.x[l], self.mask[l], self.y[l], self.ctx[l], ps, cfg, _lib.FWD_SAVE_PROJ if proj else 0)
+            fill_cbam_bwd(self._bwd[l], self.x[l], self.mask[l], self.gy[l], self.ctx[l], self.scratch[l], self.gx[l], self.gmask[l],
+                          views, ps, cfg, _lib.BWD_HAVE_PROJ if proj else 0)
 
     # ------------------------------------------------------------------ library calls on the current stream
     def _stream(self):
@@ -194,7 +185,6 @@ class EcaPyramidPlan:
         self.param_grads = []
         self._fwd, self._bwd = (_lib.EcaFwdLevel * self.n)(), (_lib.EcaBwdLevel * self.n)()
         off = 0
-        ptr = lambda t: None if t is None else t.data_ptr()
         for l, ((B, C, H, W), (w, beta), cfg) in enumerate(zip(shapes, self.params, cfgs)):
             mk = lambda *s_, dt=dtype: torch.zeros(*s_, dtype=dt, device=dev)
             mkf = lambda: torch.zeros(B, C, H, W, dtype=dtype, device=dev).contiguous(memory_format=fmt)
@@ -206,16 +196,9 @@ class EcaPyramidPlan:
             gw = self.grad_bucket[off:off + w.numel()].view(w.shape); off += w.numel()
             gb = self.grad_bucket[off:off + 1].view(()); off += 1
             self.param_grads.append([gw, gb])
-            P = _lib.EcaParams(w.data_ptr(), beta.data_ptr(), cfg.k, int(cfg.use_sigmoid_mask), cfg.tiny_thr, cfg.eps)
-            F, Bw = self._fwd[l], self._bwd[l]
-            F.x, F.mask, F.y, F.ctx, F.p = ptr(self.x[l]), ptr(self.mask[l]), ptr(self.y[l]), ptr(self.ctx[l]), P
-            F.ctx_bytes = Bw.ctx_bytes = self.ctx[l].numel()
-            Bw.scratch_bytes = self.scratch[l].numel()
-            F.B, F.C, F.H, F.W, F.dtype = B, C, H, W, _DTYPES[dtype]
-            Bw.x, Bw.mask, Bw.gy, Bw.ctx, Bw.scratch = ptr(self.x[l]), ptr(self.mask[l]), ptr(self.gy[l]), ptr(self.ctx[l]), ptr(self.scratch[l])
-            Bw.gx, Bw.gmask, Bw.gw, Bw.gbeta, Bw.p = ptr(self.gx[l]), ptr(self.gmask[l]), gw.data_ptr(), gb.data_ptr(), P
-            Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype = B, C, H, W, _DTYPES[dtype]
-            F.flags = Bw.flags = flags
+            fill_eca_fwd(self._fwd[l], self.x[l], self.mask[l], self.y[l], self.ctx[l], w, beta, cfg, flags)
+            fill_eca_bwd(self._bwd[l], self.x[l], self.mask[l], self.gy[l], self.ctx[l], self.scratch[l], self.gx[l], self.gmask[l],
+                         gw, gb, w, beta, cfg, flags)
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream

@@ -18,9 +18,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._binding import DTYPES, call, fill_seg
 
 SCALE_KEYS = ("p3", "p4", "p5")
-_DTYPE_CODES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 
 
 @dataclass
@@ -43,26 +43,19 @@ class _SegFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg: tuple, weights: Tuple[float, ...], resize: Tuple[int, ...], *flat):
         n = len(flat) // 2
-        lib = _lib.load()
+        _lib.load()
         levels = (_lib.SegLevel * n)()
         keep = []
         dev = flat[0].device
         for l in range(n):
-            x, t = flat[2 * l], flat[2 * l + 1]
-            xc = x.contiguous()
-            tc = t.detach().to(torch.float32).contiguous()
-            B, _, H, W = xc.shape
-            L = levels[l]
-            L.logits, L.target, L.glogits = xc.data_ptr(), tc.data_ptr(), None
-            L.B, L.H, L.W, L.Ht, L.Wt = B, H, W, tc.shape[-2], tc.shape[-1]
-            L.dtype, L.scale_weight, L.resize = _DTYPE_CODES[xc.dtype], weights[l], resize[l]
+            xc = flat[2 * l].contiguous()
+            tc = flat[2 * l + 1].detach().to(torch.float32).contiguous()
+            fill_seg(levels[l], xc, tc, None, weights[l], resize[l])
             keep += [xc, tc]
         c = _lib.SegCfg(*cfg)
-        ws = torch.empty(lib.mgaseg_ws_bytes(levels, n), dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.seg_ws_bytes(levels, n), dtype=torch.uint8, device=dev)
         out = torch.empty(1 + 3 * n, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgaseg_forward(levels, n, C.byref(c), ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream), "mgaseg_forward")
+        call("mgaseg_forward", dev, levels, n, C.byref(c), ws.data_ptr(), ws.numel(), out.data_ptr())
         ctx.save_for_backward(ws, *keep)
         ctx.cfg, ctx.weights, ctx.resize = cfg, weights, resize
         return out
@@ -71,24 +64,16 @@ class _SegFn(torch.autograd.Function):
     def backward(ctx, gout):
         ws, *keep = ctx.saved_tensors
         n = len(keep) // 2
-        lib = _lib.load()
         levels = (_lib.SegLevel * n)()
-        dev = ws.device
         grads = []
         for l in range(n):
             xc, tc = keep[2 * l], keep[2 * l + 1]
             gx = torch.empty_like(xc)
-            B, _, H, W = xc.shape
-            L = levels[l]
-            L.logits, L.target, L.glogits = xc.data_ptr(), tc.data_ptr(), gx.data_ptr()
-            L.B, L.H, L.W, L.Ht, L.Wt = B, H, W, tc.shape[-2], tc.shape[-1]
-            L.dtype, L.scale_weight, L.resize = _DTYPE_CODES[xc.dtype], ctx.weights[l], ctx.resize[l]
+            fill_seg(levels[l], xc, tc, gx, ctx.weights[l], ctx.resize[l])
             grads += [gx, None]
         g0 = gout[0:1].to(torch.float32).contiguous()       # only `total` is differentiable; the log entries are detached copies
         c = _lib.SegCfg(*ctx.cfg)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mgaseg_backward(levels, n, C.byref(c), ws.data_ptr(), ws.numel(), g0.data_ptr(),
-                                           torch.cuda.current_stream(dev).cuda_stream), "mgaseg_backward")
+        call("mgaseg_backward", ws.device, levels, n, C.byref(c), ws.data_ptr(), ws.numel(), g0.data_ptr())
         return (None, None, None, *grads)
 
 
@@ -141,7 +126,7 @@ class SegmentationLoss(nn.Module):
         if all(on_device):
             # device tensors have no other path.  Levels of different element types (never produced by the reference's layer loop,
             # which runs all three mask heads under one autocast state) are computed in fp32, like the loss's own accumulators
-            if len({p.dtype for _, p, _, _ in used}) != 1 or used[0][1].dtype not in _DTYPE_CODES:
+            if len({p.dtype for _, p, _, _ in used}) != 1 or used[0][1].dtype not in DTYPES:
                 used = [(sk, p.float(), t, w) for sk, p, t, w in used]
             return self._device_forward(used, prob_mode)
         if any(on_device):
@@ -206,12 +191,10 @@ class SegmentationLoss(nn.Module):
 class _KendallFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, det, seg, log_vars):
-        lib = _lib.load()
+        _lib.load()
         d, s_, lv = det.detach().float().contiguous(), seg.detach().float().reshape(()).contiguous(), log_vars.detach().float().contiguous()
         total = torch.empty_like(d)
-        with torch.cuda.device(d.device):
-            _lib.check(lib.mgakendall_forward(d.data_ptr(), d.numel(), s_.data_ptr(), lv.data_ptr(), total.data_ptr(),
-                                              torch.cuda.current_stream(d.device).cuda_stream), "mgakendall_forward")
+        call("mgakendall_forward", d.device, d.data_ptr(), d.numel(), s_.data_ptr(), lv.data_ptr(), total.data_ptr())
         ctx.save_for_backward(d, s_, lv)
         ctx.shapes = (det.shape, seg.shape)
         return total.view(det.shape)
@@ -219,13 +202,10 @@ class _KendallFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total):
         d, s_, lv = ctx.saved_tensors
-        lib = _lib.load()
         g = g_total.float().contiguous()
         g_det, g_seg, g_lv = torch.empty_like(d), torch.empty_like(s_), torch.empty_like(lv)
-        with torch.cuda.device(d.device):
-            _lib.check(lib.mgakendall_backward(d.data_ptr(), d.numel(), s_.data_ptr(), lv.data_ptr(), g.data_ptr(), g_det.data_ptr(),
-                                               g_seg.data_ptr(), g_lv.data_ptr(), torch.cuda.current_stream(d.device).cuda_stream),
-                       "mgakendall_backward")
+        call("mgakendall_backward", d.device, d.data_ptr(), d.numel(), s_.data_ptr(), lv.data_ptr(), g.data_ptr(), g_det.data_ptr(),
+             g_seg.data_ptr(), g_lv.data_ptr())
         return g_det.view(ctx.shapes[0]), g_seg.view(ctx.shapes[1]), g_lv
 
 

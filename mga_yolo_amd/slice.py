@@ -22,7 +22,8 @@ from typing import List, Sequence, Tuple
 import torch
 
 from . import _lib
-from .functional import BlockConfig, _head_params
+from ._binding import fill_head_bwd, fill_head_fwd, fill_seg
+from .functional import BlockConfig
 from .plan import PyramidPlan
 
 HEAD_PARAM_NAMES = ("proj.0.weight", "proj.1.weight", "proj.1.bias", "head.weight", "head.bias")
@@ -55,7 +56,6 @@ class SlicePlan:
         n_head = sum(p.numel() for ps in self.head_params for p in ps)
         self.grad_bucket = torch.zeros(n_cbam + n_head + 2, dtype=f32, device=dev)
         self.dtype = dtype
-        dcode = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}[dtype]
         self.cbam = PyramidPlan(shapes, cbam_params, cbam_cfgs, dtype=dtype, device=dev, with_mask=True, want_gmask=True,
                                 grad_bucket=self.grad_bucket[:n_cbam])
         self.x, self.logits, self.y, self.gy, self.gx = self.cbam.x, self.cbam.mask, self.cbam.y, self.cbam.gy, self.cbam.gx
@@ -80,36 +80,22 @@ class SlicePlan:
         self.seg_glogits = [torch.zeros(B, 1, H, W, dtype=f32, device=dev) for B, _, H, W in shapes]
         self.seg_out = torch.zeros(1 + 3 * self.n, dtype=f32, device=dev)
         self._seg = (_lib.SegLevel * self.n)()
-        for l, ((B, Cc, H, W), (th, tw)) in enumerate(zip(shapes, target_hw)):
-            S = self._seg[l]
-            S.logits, S.target, S.glogits = self.logits[l].data_ptr(), self.targets[l].data_ptr(), self.seg_glogits[l].data_ptr()
-            S.B, S.H, S.W, S.Ht, S.Wt = B, H, W, th, tw
-            S.dtype, S.scale_weight, S.resize = _lib.F32, float(scale_weights[l]), _lib.SEG_NEAREST
+        for l in range(self.n):
+            fill_seg(self._seg[l], self.logits[l], self.targets[l], self.seg_glogits[l], float(scale_weights[l]), _lib.SEG_NEAREST)
         self._seg_cfg = _lib.SegCfg(1.0, 1.0, 1.0, 1.0, 0, 0.5, 0.6, 0.5)      # SegLossConfig defaults (losses/segmentation.py:9-21)
-        self.seg_ws = torch.zeros(self.lib.mgaseg_ws_bytes(self._seg, self.n), dtype=torch.uint8, device=dev)
+        self.seg_ws = torch.zeros(_lib.seg_ws_bytes(self._seg, self.n), dtype=torch.uint8, device=dev)
         # ---- mask heads -------------------------------------------------------------------------------------------------------------
         self._hf, self._hb = (_lib.HeadFwdLevel * self.n)(), (_lib.HeadBwdLevel * self.n)()
         self.head_ctx, self.head_scratch = [], []
         for l, (B, Cc, H, W) in enumerate(shapes):
-            hid = self.hidden[l]
-            w1, gamma, beta, wh, bh = self.head_params[l]
-            rm, rv, nbt = self.head_buffers[l]
-            self.head_ctx.append(torch.zeros(self.lib.mgahead_ctx_bytes(B, Cc, H, W, hid), dtype=torch.uint8, device=dev))
-            self.head_scratch.append(torch.zeros(self.lib.mgahead_bwd_scratch_bytes(B, Cc, H, W, hid), dtype=torch.uint8, device=dev))
-            P = _head_params(w1, gamma, beta, rm, rv, nbt, wh, bh, hid, bn_eps, bn_momentum, training)
-            F, Bw = self._hf[l], self._hb[l]
-            F.x, F.logits, F.ctx, F.p = self.x[l].data_ptr(), self.logits[l].data_ptr(), self.head_ctx[l].data_ptr(), P
-            F.ctx_bytes = Bw.ctx_bytes = self.head_ctx[l].numel()
-            Bw.scratch_bytes = self.head_scratch[l].numel()
-            F.B, F.C, F.H, F.W, F.dtype, F.flags = B, Cc, H, W, dcode, _lib.HEAD_LOGITS_F32
-            gw1, gg, gb, gwh, gbh = self.head_grads[l]
+            bn = (self.hidden[l], bn_eps, bn_momentum, training)
+            self.head_ctx.append(torch.zeros(_lib.head_ctx_bytes(B, Cc, H, W, self.hidden[l]), dtype=torch.uint8, device=dev))
+            self.head_scratch.append(torch.zeros(_lib.head_scratch_bytes(B, Cc, H, W, self.hidden[l]), dtype=torch.uint8, device=dev))
+            fill_head_fwd(self._hf[l], self.x[l], self.logits[l], self.head_ctx[l], self.head_params[l], self.head_buffers[l], *bn,
+                          _lib.HEAD_LOGITS_F32)
             # dL/dlogits = the loss's part (seg_glogits) + MaskCBAM's dL/dmask (g_logits2): summed while the head's backward loads them
-            Bw.x, Bw.g_logits, Bw.g_logits2, Bw.ctx, Bw.scratch, Bw.gx = (self.x[l].data_ptr(), self.seg_glogits[l].data_ptr(),
-                                                                          self.cbam.gmask[l].data_ptr(), self.head_ctx[l].data_ptr(),
-                                                                          self.head_scratch[l].data_ptr(), self.gx[l].data_ptr())
-            Bw.gw1, Bw.gbn_weight, Bw.gbn_bias, Bw.gwh, Bw.gbh = gw1.data_ptr(), gg.data_ptr(), gb.data_ptr(), gwh.data_ptr(), gbh.data_ptr()
-            Bw.p = _head_params(w1, gamma, beta, rm, rv, None, wh, bh, hid, bn_eps, bn_momentum, training)
-            Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype, Bw.flags = B, Cc, H, W, dcode, _lib.HEAD_BWD_ACCUM_GX | _lib.HEAD_LOGITS_F32
+            fill_head_bwd(self._hb[l], self.x[l], self.seg_glogits[l], self.cbam.gmask[l], self.head_ctx[l], self.head_scratch[l], self.gx[l],
+                          self.head_grads[l], self.head_params[l], self.head_buffers[l], *bn, _lib.HEAD_BWD_ACCUM_GX | _lib.HEAD_LOGITS_F32)
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def _stream(self):

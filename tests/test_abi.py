@@ -289,3 +289,19 @@ def test_host_tensor_never_reaches_the_device_entry_point(built_lib):
     ps = [torch.zeros(1, 16), torch.zeros(1), torch.zeros(16, 1), torch.zeros(16), torch.zeros(1, 3, 7, 7), torch.zeros(())]
     with pytest.raises(RuntimeError, match="device tensors only"):
         functional.mask_cbam(x, None, *ps, functional.BlockConfig(hidden=1))
+
+
+def test_plain_and_flags_size_queries_agree_without_a_layout_flag(built_lib):
+    """The binding asks the _flags form of a size query only (_lib.scratch_bytes, head_ctx_bytes, head_scratch_bytes).  That is the plain
+    query exactly when the two agree at flags = 0 -- sizes and refusals (0) alike -- over small, odd, training-size and refused shapes."""
+    from mga_yolo_amd import _lib
+    lib = _lib.load()
+    for B in (1, 3, 32):
+        for Cc in (1, 8, 20, 64, 768, 4097):
+            for H, W in ((1, 1), (3, 5), (9, 11), (80, 80), (2, 500), (2, 501)):
+                for hid in (0, 1, 4, 16, 200):
+                    s = (B, Cc, H, W, hid)
+                    assert lib.mgahead_ctx_bytes_flags(*s, 0) == lib.mgahead_ctx_bytes(*s)
+                    assert lib.mgahead_bwd_scratch_bytes_flags(*s, 0) == lib.mgahead_bwd_scratch_bytes(*s)
+                    for k in (1, 4, 7, 15, 17):
+                        assert lib.mgacbam_bwd_scratch_bytes_flags(*s, k, 0) == lib.mgacbam_bwd_scratch_bytes(*s, k)
