@@ -67,45 +67,20 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
 }
 
 // The layout-free kernels take the plain level arguments: each launch computes its own grid and LDS size from the group
-template <typename SmemOf>
-static size_t group_smem(const Group<BwdArgs>& G, SmemOf smem_of) {
-  size_t smem = 0;
-  for (int l = 0; l < G.n; ++l) smem = std::max(smem, smem_of(G.lv[l]));
-  return smem;
-}
 static size_t reduce2_smem(const Tune& t) { return (64 + static_cast<size_t>(std::max(kPghLds, kBlock / t.pool_tx))) * sizeof(float); }
 static int launch_convT(Group<BwdArgs>& G, int k, hipStream_t st) {
-  const size_t smem = group_smem(G, [&](const BwdArgs& a) { return convT_smem(a.t, k); });
-  const int grid = fill_starts(G, G.lv, G.n, [](const BwdArgs& a) { return a.nconv; });
-  switch (k) {
-    case 3: LAUNCH(k_bwd_convT<3>, grid, smem, st, G); break;
-    case 5: LAUNCH(k_bwd_convT<5>, grid, smem, st, G); break;
-    case 7: LAUNCH(k_bwd_convT<7>, grid, smem, st, G); break;
-    default: LAUNCH(k_bwd_convT<0>, grid, smem, st, G); break;
-  }
-  return launch_status("k_bwd_convT");
+  auto kernel = with_k(k, [](auto kk) { return k_bwd_convT<kk.value>; });
+  return launch_group("k_bwd_convT", kernel, G, [](const BwdArgs& a) { return a.nconv; }, [&](const BwdArgs& a) { return convT_smem(a.t, k); }, st);
 }
 static int launch_wsa(Group<BwdArgs>& G, int k, hipStream_t st) {
-  const size_t smem = group_smem(G, [&](const BwdArgs& a) { return wsa_smem(a.t, k); });
-  const int grid = fill_starts(G, G.lv, G.n, [](const BwdArgs& a) { return a.nwsa; });
-  switch (k) {
-    case 3: LAUNCH(k_bwd_wsa<3>, grid, smem, st, G); break;
-    case 5: LAUNCH(k_bwd_wsa<5>, grid, smem, st, G); break;
-    case 7: LAUNCH(k_bwd_wsa<7>, grid, smem, st, G); break;
-    default: LAUNCH(k_bwd_wsa<0>, grid, smem, st, G); break;
-  }
-  return launch_status("k_bwd_wsa");
+  auto kernel = with_k(k, [](auto kk) { return k_bwd_wsa<kk.value>; });
+  return launch_group("k_bwd_wsa", kernel, G, [](const BwdArgs& a) { return a.nwsa; }, [&](const BwdArgs& a) { return wsa_smem(a.t, k); }, st);
 }
 static int launch_params(Group<BwdArgs>& G, hipStream_t st) {
-  const size_t smem = group_smem(G, [](const BwdArgs& a) { return params_smem(a.g); });
-  const int grid = fill_starts(G, G.lv, G.n, [](const BwdArgs& a) { return a.npg; });
-  LAUNCH(k_bwd_params, grid, smem, st, G);
-  return launch_status("k_bwd_params");
+  return launch_group("k_bwd_params", k_bwd_params, G, [](const BwdArgs& a) { return a.npg; }, [](const BwdArgs& a) { return params_smem(a.g); }, st);
 }
 
 static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
-  Group<BwdArgs> G;
-  G.n = n;
   // k_bwd_reduce2 re-reads three planes (g_planes x 2, cidx) per channel group: 4 channels per row halve that share of its loads
   // (config 4: 88 -> 80 us) whenever the grid still fills the chip; k_pool (one mask plane per group) measured slower with 4
   constexpr int kReduce2MaxCpt = 4;
@@ -114,8 +89,8 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
     lv[l].t.pool_cpt = cpt;
     const int cpb = (kBlock / lv[l].t.pool_tx) * cpt;
     lv[l].ncg = (lv[l].g.C + cpb - 1) / cpb;
-    G.lv[l] = lv[l];
   }
+  Group<BwdArgs> G = make_group(lv, n);
 
   // MGACBAM_BWD_FOLD: transposed conv as trailing role workgroups of the k_bwd_reduce1 launch (whole backward in this call, a tile at
   // least one image row and at least kSyncPx pixels -- one flag per tile in ctx.sync -- and few tiles per conv window)
@@ -153,70 +128,44 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
       }
       R.seg[p][n] = tot;
     }
-    const int grid = tot;
-#define CALL_R12B(CPTV) if (mkproj) LAUNCH((k_bwd_r12<TT, VV, CPTV, true>), grid, smem, st, R); else LAUNCH((k_bwd_r12<TT, VV, CPTV, false>), grid, smem, st, R)
-#define CALL_R12(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_R12B); }
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R12);
-#undef CALL_R12
-#undef CALL_R12B
-    if (int e = launch_status("k_bwd_r12")) return e;
+    auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_cpt(cpt, [&](auto c) {
+      return with_bool(mkproj, [&](auto pj) { return k_bwd_r12<elem_t<decltype(t)>, v.value, c.value, pj.value>; }); }); });
+    if (int e = launch("k_bwd_r12", kernel, tot, kBlock, smem, st, R)) return e;
     for (int l = 0; l < n; ++l) G.lv[l] = lv[l];                  // (the later launches of this call see the same level state)
   }
   if (fold && !merge) {
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max({smem, reduce1_smem(lv[l].g, sig.vec, lv[l].make_proj), convT_smem(lv[l].t, sig.k)});
-    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt) + pad8(a.nconv); });
-#define CALL_R1F2(Tt, Vv, PJ) if (sig.k == 7) LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 7, PJ>), grid, smem, st, G); else LAUNCH((k_bwd_reduce1_fold<Tt, Vv, 0, PJ>), grid, smem, st, G)
-#define CALL_R1F(Tt, Vv) if (mkproj) { CALL_R1F2(Tt, Vv, true); } else { CALL_R1F2(Tt, Vv, false); }
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R1F);
-#undef CALL_R1F
-#undef CALL_R1F2
-    if (int e = launch_status("k_bwd_reduce1_fold")) return e;
+    auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_k7(sig.k, [&](auto k) {
+      return with_bool(mkproj, [&](auto pj) { return k_bwd_reduce1_fold<elem_t<decltype(t)>, v.value, k.value, pj.value>; }); }); });
+    if (int e = launch_group("k_bwd_reduce1_fold", kernel, G, [](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt) + pad8(a.nconv); },
+                             [&](const BwdArgs& a) { return std::max(reduce1_smem(a.g, sig.vec, a.make_proj), convT_smem(a.t, sig.k)); },
+                             st)) return e;
   }
   if ((stages & MGACBAM_BWD_REDUCE1) && !fold) {  // 1. per-(b,c) and per-pixel reductions of gy*x
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, reduce1_smem(lv[l].g, sig.vec, lv[l].make_proj));
-    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt); });
-#define CALL_R1(Tt, Vv) if (mkproj) LAUNCH((k_bwd_reduce1<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_bwd_reduce1<Tt, Vv, false>), grid, smem, st, G)
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R1);
-#undef CALL_R1
-    if (int e = launch_status("k_bwd_reduce1")) return e;
+    auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) {
+      return with_bool(mkproj, [&](auto pj) { return k_bwd_reduce1<elem_t<decltype(t)>, v.value, pj.value>; }); });
+    if (int e = launch_group("k_bwd_reduce1", kernel, G, [](const BwdArgs& a) { return xcd_grid(a.g.B, a.nt); },
+                             [&](const BwdArgs& a) { return reduce1_smem(a.g, sig.vec, a.make_proj); }, st)) return e;
   }
   if ((stages & MGACBAM_BWD_CONVT) && !fold)  // 2. transposed conv
     if (int e = launch_convT(G, sig.k, st)) return e;
   const bool fuse_pg = fuse && (stages & MGACBAM_BWD_APPLY) && (stages & MGACBAM_BWD_PARAMGRAD);
   const bool fuse_wsa = fuse && (stages & MGACBAM_BWD_REDUCE2) && (stages & MGACBAM_BWD_WSA) && sig.k == 7;   // dWsa tile partials: leading roles of k_bwd_reduce2
   if ((stages & MGACBAM_BWD_REDUCE2) && !merge) {  // 3. rest of g_ca (needs g_planes), g_z [+ dWsa partials as role workgroups]
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) {
-      smem = std::max(smem, reduce2_smem(lv[l].t));
-      if (fuse_wsa) smem = std::max(smem, wsa_smem(lv[l].t, sig.k));
-    }
-    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return (fuse_wsa ? pad8(a.nwsa) : 0) + sweep_blocks(a, a.t.pool_tx, cpt); });
-#define CALL_R22(CPTV) if (fuse_wsa) LAUNCH((k_bwd_reduce2<TT, VV, CPTV, true>), grid, smem, st, G); else LAUNCH((k_bwd_reduce2<TT, VV, CPTV, false>), grid, smem, st, G)
-#define CALL_R2(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_R22); }
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_R2);
-#undef CALL_R2
-#undef CALL_R22
-    if (int e = launch_status("k_bwd_reduce2")) return e;
+    auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_cpt(cpt, [&](auto c) {
+      return with_bool(fuse_wsa, [&](auto fw) { return k_bwd_reduce2<elem_t<decltype(t)>, v.value, c.value, fw.value>; }); }); });
+    if (int e = launch_group("k_bwd_reduce2", kernel, G,
+                             [&](const BwdArgs& a) { return (fuse_wsa ? pad8(a.nwsa) : 0) + sweep_blocks(a, a.t.pool_tx, cpt); },
+                             [&](const BwdArgs& a) { return std::max(reduce2_smem(a.t), fuse_wsa ? wsa_smem(a.t, sig.k) : 0); }, st)) return e;
   }
   if ((stages & MGACBAM_BWD_WSA) && !fuse_wsa && !merge)  // 4. dWsa tile partials (depends on stage 1 only)
     if (int e = launch_wsa(G, sig.k, st)) return e;
   if ((stages & MGACBAM_BWD_PARAMGRAD) && !fuse_pg)  // 5. every parameter gradient
     if (int e = launch_params(G, st)) return e;
   if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask) [+ parameter gradients as role workgroups]
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) {
-      smem = std::max(smem, bwd_apply_smem(lv[l].g, sig.vec));
-      if (fuse_pg) smem = std::max(smem, params_smem(lv[l].g));
-    }
-    const int grid = fill_starts(G, lv, n, [&](const BwdArgs& a) { return (fuse_pg ? pad8(a.npg) : 0) + xcd_grid(a.g.B, a.nt); });
-#define CALL_AP2(GM) if (fuse_pg) LAUNCH((k_bwd_apply<TT, VV, GM, true>), grid, smem, st, G); else LAUNCH((k_bwd_apply<TT, VV, GM, false>), grid, smem, st, G)
-#define CALL_AP(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; if (sig.gmask) { CALL_AP2(true); } else { CALL_AP2(false); } }
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_AP);
-#undef CALL_AP
-#undef CALL_AP2
-    if (int e = launch_status("k_bwd_apply")) return e;
+    auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_bool(sig.gmask, [&](auto gm) {
+      return with_bool(fuse_pg, [&](auto pg) { return k_bwd_apply<elem_t<decltype(t)>, v.value, gm.value, pg.value>; }); }); });
+    if (int e = launch_group("k_bwd_apply", kernel, G, [&](const BwdArgs& a) { return (fuse_pg ? pad8(a.npg) : 0) + xcd_grid(a.g.B, a.nt); },
+                             [&](const BwdArgs& a) { return std::max(bwd_apply_smem(a.g, sig.vec), fuse_pg ? params_smem(a.g) : 0); }, st)) return e;
   }
   return 0;
 }
@@ -226,71 +175,42 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
 // k_bwd_params, k_bwd_apply_nhwc -- the layout-free kernels are the NCHW path's own
 // ------------------------------------------------------------------------------------------------
 static int backward_group_nhwc(NhwcBwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
-  Group<NhwcBwdArgs> G;
+  Group<NhwcBwdArgs> G = make_group(lv, n);
   Group<BwdArgs> GB;                                            // the layout-free kernels take the plain level arguments
-  G.n = GB.n = n;
-  for (int l = 0; l < n; ++l) { G.lv[l] = lv[l]; GB.lv[l] = lv[l].a; }
-  auto chunks = [&]() { return fill_starts(G, lv, n, [&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }); };
+  GB.n = n;
+  for (int l = 0; l < n; ++l) GB.lv[l] = lv[l].a;
+  auto chunks = [](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); };
   if (stages & MGACBAM_BWD_REDUCE1) {  // 1. chunk partials of A and D, g_pre
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, nhwc_reduce1_smem(lv[l].a.g, sig.vec));
-    const int grid = chunks();
-#define CALL_NR1(Tt, Vv) LAUNCH((k_bwd_reduce1_nhwc<Tt, Vv>), grid, smem, st, G)
-    DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_NR1);
-#undef CALL_NR1
-    if (int e = launch_status("k_bwd_reduce1_nhwc")) return e;
+    auto kernel = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_bwd_reduce1_nhwc<elem_t<decltype(t)>, v.value>; });
+    if (int e = launch_group("k_bwd_reduce1_nhwc", kernel, G, chunks,
+                             [&](const NhwcBwdArgs& a) { return nhwc_reduce1_smem(a.a.g, sig.vec); }, st)) return e;
   }
   if (stages & MGACBAM_BWD_CONVT)  // 2. transposed conv
     if (int e = launch_convT(GB, sig.k, st)) return e;
   if (stages & MGACBAM_BWD_REDUCE2) {  // 3. chunk partials of the g_planes term, then their fold: g_z, D, hidden-gradient partials
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, nhwc_reduce2_smem(lv[l].a.g));
-    const int grid = chunks();
-#define CALL_NR2(Tt, Vv) LAUNCH((k_bwd_reduce2_nhwc<Tt, Vv>), grid, smem, st, G)
-    DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_NR2);
-#undef CALL_NR2
-    if (int e = launch_status("k_bwd_reduce2_nhwc")) return e;
-    const int fgrid = fill_starts(G, lv, n, [&](const NhwcBwdArgs& a) { return a.a.g.B * a.ncb; });
-    LAUNCH(k_bwd_fold_nhwc, fgrid, 0, st, G);
-    if (int e = launch_status("k_bwd_fold_nhwc")) return e;
+    auto kernel = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_bwd_reduce2_nhwc<elem_t<decltype(t)>, v.value>; });
+    if (int e = launch_group("k_bwd_reduce2_nhwc", kernel, G, chunks, [](const NhwcBwdArgs& a) { return nhwc_reduce2_smem(a.a.g); }, st)) return e;
+    if (int e = launch_group("k_bwd_fold_nhwc", k_bwd_fold_nhwc, G, [](const NhwcBwdArgs& a) { return a.a.g.B * a.ncb; }, 0, st)) return e;
   }
   if (stages & MGACBAM_BWD_WSA)  // 4. dWsa tile partials
     if (int e = launch_wsa(GB, sig.k, st)) return e;
   if (stages & MGACBAM_BWD_PARAMGRAD)  // 5. every parameter gradient
     if (int e = launch_params(GB, st)) return e;
   if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask)
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, nhwc_bwd_apply_smem(lv[l].a.g));
-    const int grid = fill_starts(G, lv, n, [&](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); });
-#define CALL_NAP(Tt, Vv) if (sig.gmask) LAUNCH((k_bwd_apply_nhwc<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_bwd_apply_nhwc<Tt, Vv, false>), grid, smem, st, G)
-    DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_NAP);
-#undef CALL_NAP
-    if (int e = launch_status("k_bwd_apply_nhwc")) return e;
+    auto kernel = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
+      return with_bool(sig.gmask, [&](auto gm) { return k_bwd_apply_nhwc<elem_t<decltype(t)>, v.value, gm.value>; }); });
+    if (int e = launch_group("k_bwd_apply_nhwc", kernel, G, [](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); },
+                             [](const NhwcBwdArgs& a) { return nhwc_bwd_apply_smem(a.a.g); }, st)) return e;
   }
   return 0;
 }
 
 extern "C" int mgacbam_backward_stages(const mgacbam_bwd_level_t* levels, int n_levels, int stages, void* stream) {
-  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
-  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  BwdArgs args[MGACBAM_MAX_LEVELS];
-  Sig sigs[MGACBAM_MAX_LEVELS];
-  NhwcBwdArgs nargs[MGACBAM_MAX_LEVELS];
-  Sig nsigs[MGACBAM_MAX_LEVELS];
-  int nc = 0, nn = 0;                                           // NCHW levels, NHWC levels (every level is checked before any launch)
-  for (int l = 0; l < n_levels; ++l) {
-    NhwcBwdArgs N;
-    Sig s;
-    if (int e = backward_args(levels[l], N, s)) return e;
-    if (s.nhwc) { nargs[nn] = N; nsigs[nn++] = s; } else { args[nc] = N.a; sigs[nc++] = s; }
-  }
-  if (nc) if (int e = for_each_group(args, sigs, nc, [&](BwdArgs* g, int m, const Sig& s) { return backward_group(g, m, s, stages, st); })) return e;
-  if (nn) if (int e = for_each_group(nargs, nsigs, nn, [&](NhwcBwdArgs* g, int m, const Sig& s) { return backward_group_nhwc(g, m, s, stages, st); })) return e;
-  g_err[0] = 0;
-  return 0;
+  return run_levels<BwdArgs, NhwcBwdArgs>(levels, n_levels, backward_args,
+      [&](BwdArgs* g, int m, const Sig& s) { return backward_group(g, m, s, stages, st); },
+      [&](NhwcBwdArgs* g, int m, const Sig& s) { return backward_group_nhwc(g, m, s, stages, st); });
 }
 extern "C" int mgacbam_backward(const mgacbam_bwd_level_t* levels, int n_levels, void* stream) {
   return mgacbam_backward_stages(levels, n_levels, MGACBAM_BWD_ALL, stream);
 }
-

@@ -12,19 +12,16 @@ struct EcaCtxLayout { size_t S, use, den, avg, mavg, w, splane, total; };
 static EcaCtxLayout eca_ctx_layout(int B, int C, int H, int W) {
   const size_t HW = static_cast<size_t>(H) * W, BC = static_cast<size_t>(B) * C;
   EcaCtxLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
-  L.S = take(B); L.use = take(B); L.den = take(B);
-  L.avg = take(BC); L.mavg = take(BC); L.w = take(BC);
-  L.splane = take(B * HW);
-  L.total = o;
+  Carver cv;
+  L.S = cv.take(B); L.use = cv.take(B); L.den = cv.take(B);
+  L.avg = cv.take(BC); L.mavg = cv.take(BC); L.w = cv.take(BC);
+  L.splane = cv.take(B * HW);
+  L.total = cv.total;
   return L;
 }
-static EcaCtx eca_ctx_ptrs(void* base, int B, int C, int H, int W) {
+static EcaCtx eca_ctx_ptrs(const void* p, int B, int C, int H, int W) {
   const EcaCtxLayout L = eca_ctx_layout(B, C, H, W);
-  char* p = static_cast<char*>(base);
-  auto f = [&](size_t off) { return reinterpret_cast<float*>(p + off); };
-  return EcaCtx{f(L.S), f(L.use), f(L.den), f(L.avg), f(L.mavg), f(L.w), f(L.splane)};
+  return EcaCtx{at(p, L.S), at(p, L.use), at(p, L.den), at(p, L.avg), at(p, L.mavg), at(p, L.w), at(p, L.splane)};
 }
 // Channels-last levels (MGACBAM_LAYOUT_NHWC, eca_nhwc.cuh) carry their chunk partials as a TAIL of the same buffers: the forward's pool
 // partials after the ctx fields (whose layout stays as it is), the backward's gg partials after gg in scratch.  vec: nhwc_vec of the level.
@@ -74,199 +71,132 @@ static Geo eca_geo(int B, int C, int H, int W, const mgacbam_eca_params_t& p) {
   return g;
 }
 
-static int eca_forward_group(EcaFwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<EcaFwdArgs> G;
-  G.n = n;
-  const int cpt = group_cpt(lv, n);
-  for (int l = 0; l < n; ++l) { lv[l].t.pool_cpt = cpt; G.lv[l] = lv[l]; }
-  const int grid = fill_starts(G, lv, n, [&](const EcaFwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); });
-#define CALL_EP2(CPTV) if (sig.has_mask) LAUNCH((k_eca_pool<TT, VV, CPTV, true>), grid, 0, st, G); else LAUNCH((k_eca_pool<TT, VV, CPTV, false>), grid, 0, st, G)
-#define CALL_EP(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_EP2); }
-  DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_EP);
-#undef CALL_EP
-#undef CALL_EP2
-  if (int e = launch_status("k_eca_pool")) return e;
-#define CALL_EA2(CPTV) LAUNCH((k_eca_apply<TT, VV, CPTV>), grid, 0, st, G)
-#define CALL_EA(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_EA2); }
-  DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_EA);
-#undef CALL_EA
-#undef CALL_EA2
-  return launch_status("k_eca_apply");
-}
-
-// channels-last levels: k_eca_pool_nhwc, k_eca_fin, k_eca_apply_nhwc
-static int eca_forward_group_nhwc(EcaNhwcFwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<EcaNhwcFwdArgs> G;
-  G.n = n;
-  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
-  const int chunk_grid = fill_starts(G, lv, n, [&](const EcaNhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); });
-#define CALL_ENP(Tt, Vv) if (sig.has_mask) LAUNCH((k_eca_pool_nhwc<Tt, Vv, true>), chunk_grid, 0, st, G); else LAUNCH((k_eca_pool_nhwc<Tt, Vv, false>), chunk_grid, 0, st, G)
-  DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_ENP);
-#undef CALL_ENP
-  if (int e = launch_status("k_eca_pool_nhwc")) return e;
-  const int fgrid = fill_starts(G, lv, n, [&](const EcaNhwcFwdArgs& a) { return a.a.g.B * ((a.a.g.C + kNhwcFoldC - 1) / kNhwcFoldC); });
-  if (sig.has_mask) LAUNCH(k_eca_fin<true>, fgrid, 0, st, G); else LAUNCH(k_eca_fin<false>, fgrid, 0, st, G);
-  if (int e = launch_status("k_eca_fin")) return e;
-  size_t smem = 0;
-  for (int l = 0; l < n; ++l) smem = std::max(smem, static_cast<size_t>(lv[l].a.g.C) * sizeof(float));
-  const int tgrid = fill_starts(G, lv, n, [&](const EcaNhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); });
-#define CALL_ENA(Tt, Vv) LAUNCH((k_eca_apply_nhwc<Tt, Vv>), tgrid, smem, st, G)
-  DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_ENA);
-#undef CALL_ENA
-  return launch_status("k_eca_apply_nhwc");
-}
-
 static int eca_check_params(const mgacbam_eca_params_t& p) {
   if (!p.w || !p.beta) return fail(MGACBAM_E_NULL, "eca: NULL parameter pointer");
   if (p.k < 1 || p.k > 15 || (p.k & 1) == 0) return fail(MGACBAM_E_SHAPE, "eca: conv1d kernel k=%d must be odd and in 1..15", p.k);
   return 0;
 }
-
-extern "C" int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_levels, void* stream) {
-  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
-  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
-  EcaFwdArgs args[MGACBAM_MAX_LEVELS];
-  Sig sigs[MGACBAM_MAX_LEVELS];
-  EcaNhwcFwdArgs nargs[MGACBAM_MAX_LEVELS];
-  Sig nsigs[MGACBAM_MAX_LEVELS];
-  int nc = 0, nn = 0;                                           // NCHW levels, NHWC levels (every level is checked before any launch)
-  for (int l = 0; l < n_levels; ++l) {
-    const mgacbam_eca_fwd_level_t& L = levels[l];
-    if (!L.x || !L.y || !L.ctx) return fail(MGACBAM_E_NULL, "eca forward: x / y / ctx is NULL");
-    if (int e = eca_check_params(L.p)) return e;
-    if (int e = check_shape(L.B, L.C, L.H, L.W, 1, L.p.k)) return e;
-    if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "eca forward: dtype %d", L.dtype);
-    if (int e = eca_check_flags("eca forward", L.flags, L.C)) return e;
-    const bool nhwc = (L.flags & MGACBAM_LAYOUT_NHWC) != 0;
-    const int VEC = level_vec(nhwc, L.C, L.H, L.W, L.dtype);
-    const size_t need = VEC * elem_size(L.dtype);
-    if (!aligned_to(L.x, need) || !aligned_to(L.y, need) || !aligned_to(L.ctx, 16) || (L.mask && !aligned_to(L.mask, 16)))
-      return fail(MGACBAM_E_ALIGN, "eca forward%s: x/y must be %zu-byte aligned, ctx and mask 16-byte", nhwc ? " (NHWC)" : "", need);
-    if (int e = check_capacity("eca forward", "ctx", eca_ctx_need(L.B, L.C, L.H, L.W, nhwc, VEC), L.ctx_bytes)) return e;
-    EcaFwdArgs A;
-    A.x = L.x; A.mask = L.mask; A.y = L.y;
-    A.c = eca_ctx_ptrs(L.ctx, L.B, L.C, L.H, L.W);
-    A.w1d = L.p.w; A.beta = L.p.beta;
-    A.g = eca_geo(L.B, L.C, L.H, L.W, L.p);
-    A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
-    Sig s{L.dtype, VEC, L.mask != nullptr, 0, 0, 0};
-    if (nhwc) {
-      s.nhwc = 1;
-      s.weight = L.C;
-      nargs[nn] = EcaNhwcFwdArgs{A, nhwc_geo(L.C, L.H, L.W, VEC),
-                                 reinterpret_cast<float*>(static_cast<char*>(L.ctx) + eca_ctx_layout(L.B, L.C, L.H, L.W).total)};
-      nsigs[nn++] = s;
-    } else {
-      s.weight = L.C * A.t.chan_tx;
-      args[nc] = A;
-      sigs[nc++] = s;
-    }
+// One level of either direction (Level: mgacbam_eca_fwd_level_t / mgacbam_eca_bwd_level_t, N: EcaNhwcFwdArgs / EcaNhwcBwdArgs) and
+// layout: validated (NULL, parameters, shape, dtype, flags, alignment, capacity), then its kernel arguments.  N.a is the whole
+// result for an NCHW level; a channels-last level (sig.nhwc) also gets its chunk geometry and the partials' tail of ctx / scratch.
+template <typename Level, typename N>
+static int eca_level(const char* what, const Level& L, N& out, Sig& sig) {
+  constexpr bool bwd = std::is_same_v<N, EcaNhwcBwdArgs>;
+  if constexpr (bwd) {
+    if (!L.x || !L.gy || !L.ctx || !L.scratch || !L.gx || !L.gw || !L.gbeta) return fail(MGACBAM_E_NULL, "%s: NULL pointer", what);
+    if (L.gmask && !L.mask) return fail(MGACBAM_E_NULL, "%s: gmask requested but mask is NULL", what);
+  } else {
+    if (!L.x || !L.y || !L.ctx) return fail(MGACBAM_E_NULL, "%s: x / y / ctx is NULL", what);
   }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (nc) if (int e = for_each_group(args, sigs, nc, [&](EcaFwdArgs* g, int m, const Sig& s) { return eca_forward_group(g, m, s, st); })) return e;
-  if (nn) if (int e = for_each_group(nargs, nsigs, nn, [&](EcaNhwcFwdArgs* g, int m, const Sig& s) { return eca_forward_group_nhwc(g, m, s, st); })) return e;
-  g_err[0] = 0;
+  if (int e = eca_check_params(L.p)) return e;
+  if (int e = check_shape(L.B, L.C, L.H, L.W, 1, L.p.k)) return e;
+  if (int e = check_dtype(what, L.dtype)) return e;
+  if (int e = eca_check_flags(what, L.flags, L.C)) return e;
+  const bool nhwc = (L.flags & MGACBAM_LAYOUT_NHWC) != 0;
+  const int VEC = level_vec(nhwc, L.C, L.H, L.W, L.dtype);
+  const size_t need = VEC * elem_size(L.dtype);
+  auto& A = out.a;
+  if constexpr (bwd) {
+    if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
+        !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 16)))
+      return fail(MGACBAM_E_ALIGN, "%s%s: x/gy/gx must be %zu-byte aligned, ctx/scratch/gmask 16-byte", what, nhwc ? " (NHWC)" : "", need);
+    if (int e = check_capacity(what, "ctx", eca_ctx_need(L.B, L.C, L.H, L.W, nhwc, VEC), L.ctx_bytes)) return e;
+    if (int e = check_capacity(what, "scratch", eca_scratch_need(L.B, L.C, L.H, L.W, nhwc, VEC), L.scratch_bytes)) return e;
+    A.x = L.x; A.mask = L.mask; A.gy = L.gy; A.gx = L.gx; A.gmask = L.gmask; A.gw = L.gw; A.gbeta = L.gbeta;
+    A.s.gg = static_cast<float*>(L.scratch);
+  } else {
+    if (!aligned_to(L.x, need) || !aligned_to(L.y, need) || !aligned_to(L.ctx, 16) || (L.mask && !aligned_to(L.mask, 16)))
+      return fail(MGACBAM_E_ALIGN, "%s%s: x/y must be %zu-byte aligned, ctx and mask 16-byte", what, nhwc ? " (NHWC)" : "", need);
+    if (int e = check_capacity(what, "ctx", eca_ctx_need(L.B, L.C, L.H, L.W, nhwc, VEC), L.ctx_bytes)) return e;
+    A.x = L.x; A.mask = L.mask; A.y = L.y;
+  }
+  A.c = eca_ctx_ptrs(L.ctx, L.B, L.C, L.H, L.W);
+  A.w1d = L.p.w; A.beta = L.p.beta;
+  A.g = eca_geo(L.B, L.C, L.H, L.W, L.p);
+  A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
+  sig = Sig{L.dtype, VEC, L.mask != nullptr, 0, 0, 0};
+  if constexpr (bwd) { sig.gmask = L.gmask != nullptr; A.nt = nhwc ? 0 : chan_tiles(A.t, L.H, L.W, VEC); }
+  sig.nhwc = nhwc;
+  sig.weight = nhwc ? L.C : L.C * A.t.chan_tx;
+  if (nhwc) {
+    out.n = nhwc_geo(L.C, L.H, L.W, VEC);
+    if constexpr (bwd) out.part = at(L.scratch, eca_gg_bytes(L.B, L.C));
+    else out.part = at(L.ctx, eca_ctx_layout(L.B, L.C, L.H, L.W).total);
+  }
   return 0;
 }
 
-static int eca_backward_group(EcaBwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<EcaBwdArgs> G;
-  G.n = n;
+static size_t eca_apply_nhwc_smem(const Geo& g) { return static_cast<size_t>(g.C) * sizeof(float); }
+static size_t eca_bwd_smem(const Geo& g, int vec) { return (3 * static_cast<size_t>(g.C) + kBlock * vec) * sizeof(float); }
+static size_t eca_bwd_nhwc_smem(const Geo& g) {
+  return (((static_cast<size_t>(g.C) + 1) & ~static_cast<size_t>(1)) + 2 * static_cast<size_t>(g.C)) * sizeof(float);
+}
+
+static int eca_forward_group(EcaFwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
   const int cpt = group_cpt(lv, n);
-  for (int l = 0; l < n; ++l) { lv[l].t.pool_cpt = cpt; G.lv[l] = lv[l]; }
-  {
-    const int grid = fill_starts(G, lv, n, [&](const EcaBwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); });
-#define CALL_ER2(CPTV) LAUNCH((k_eca_reduce<TT, VV, CPTV>), grid, 0, st, G)
-#define CALL_ER(Tt, Vv) { using TT = Tt; constexpr int VV = Vv; DISPATCH_CPT(cpt, CALL_ER2); }
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_ER);
-#undef CALL_ER
-#undef CALL_ER2
-    if (int e = launch_status("k_eca_reduce")) return e;
-  }
-  {
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, (3 * static_cast<size_t>(lv[l].g.C) + kBlock * sig.vec) * sizeof(float));
-    const int grid = fill_starts(G, lv, n, [&](const EcaBwdArgs& a) { return kEcaRoles + xcd_grid(a.g.B, a.nt); });
-#define CALL_EB(Tt, Vv) if (sig.gmask) LAUNCH((k_eca_bwd<Tt, Vv, true>), grid, smem, st, G); else LAUNCH((k_eca_bwd<Tt, Vv, false>), grid, smem, st, G)
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_EB);
-#undef CALL_EB
-    if (int e = launch_status("k_eca_bwd")) return e;
-  }
-  return 0;
+  for (int l = 0; l < n; ++l) lv[l].t.pool_cpt = cpt;
+  Group<EcaFwdArgs> G = make_group(lv, n);
+  auto sweeps = [&](const EcaFwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); };
+  auto pool = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_cpt(cpt, [&](auto c) {
+    return with_bool(sig.has_mask, [&](auto m) { return k_eca_pool<elem_t<decltype(t)>, v.value, c.value, m.value>; }); }); });
+  if (int e = launch_group("k_eca_pool", pool, G, sweeps, 0, st)) return e;
+  auto apply = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) {
+    return with_cpt(cpt, [&](auto c) { return k_eca_apply<elem_t<decltype(t)>, v.value, c.value>; }); });
+  return launch_group("k_eca_apply", apply, G, sweeps, 0, st);
+}
+
+// channels-last levels: k_eca_pool_nhwc, k_eca_fin, k_eca_apply_nhwc
+static int eca_forward_group_nhwc(EcaNhwcFwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
+  Group<EcaNhwcFwdArgs> G = make_group(lv, n);
+  auto pool = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
+    return with_bool(sig.has_mask, [&](auto m) { return k_eca_pool_nhwc<elem_t<decltype(t)>, v.value, m.value>; }); });
+  if (int e = launch_group("k_eca_pool_nhwc", pool, G, [](const EcaNhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }, 0, st)) return e;
+  auto fin = with_bool(sig.has_mask, [](auto m) { return k_eca_fin<m.value>; });
+  if (int e = launch_group("k_eca_fin", fin, G, [](const EcaNhwcFwdArgs& a) { return nhwc_fold_blocks(a.a.g); }, 0, st)) return e;
+  auto apply = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_eca_apply_nhwc<elem_t<decltype(t)>, v.value>; });
+  return launch_group("k_eca_apply_nhwc", apply, G, [](const EcaNhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); },
+                      [](const EcaNhwcFwdArgs& a) { return eca_apply_nhwc_smem(a.a.g); }, st);
+}
+
+extern "C" int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_levels, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return run_levels<EcaFwdArgs, EcaNhwcFwdArgs>(levels, n_levels,
+      [](const mgacbam_eca_fwd_level_t& L, EcaNhwcFwdArgs& N, Sig& s) { return eca_level("eca forward", L, N, s); },
+      [&](EcaFwdArgs* g, int m, const Sig& s) { return eca_forward_group(g, m, s, st); },
+      [&](EcaNhwcFwdArgs* g, int m, const Sig& s) { return eca_forward_group_nhwc(g, m, s, st); });
+}
+
+static int eca_backward_group(EcaBwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
+  const int cpt = group_cpt(lv, n);
+  for (int l = 0; l < n; ++l) lv[l].t.pool_cpt = cpt;
+  Group<EcaBwdArgs> G = make_group(lv, n);
+  auto reduce = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) {
+    return with_cpt(cpt, [&](auto c) { return k_eca_reduce<elem_t<decltype(t)>, v.value, c.value>; }); });
+  if (int e = launch_group("k_eca_reduce", reduce, G, [&](const EcaBwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, cpt); }, 0, st)) return e;
+  auto bwd = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) {
+    return with_bool(sig.gmask, [&](auto gm) { return k_eca_bwd<elem_t<decltype(t)>, v.value, gm.value>; }); });
+  return launch_group("k_eca_bwd", bwd, G, [](const EcaBwdArgs& a) { return kEcaRoles + xcd_grid(a.g.B, a.nt); },
+                      [&](const EcaBwdArgs& a) { return eca_bwd_smem(a.g, sig.vec); }, st);
 }
 
 // channels-last levels: k_eca_reduce_nhwc, k_eca_fold, k_eca_bwd_nhwc (+ the layout-free role workgroups)
 static int eca_backward_group_nhwc(EcaNhwcBwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<EcaNhwcBwdArgs> G;
-  G.n = n;
-  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
-  const int chunk_grid = fill_starts(G, lv, n, [&](const EcaNhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); });
-#define CALL_ENR(Tt, Vv) LAUNCH((k_eca_reduce_nhwc<Tt, Vv>), chunk_grid, 0, st, G)
-  DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_ENR);
-#undef CALL_ENR
-  if (int e = launch_status("k_eca_reduce_nhwc")) return e;
-  const int fgrid = fill_starts(G, lv, n, [&](const EcaNhwcBwdArgs& a) { return a.a.g.B * ((a.a.g.C + kNhwcFoldC - 1) / kNhwcFoldC); });
-  LAUNCH(k_eca_fold, fgrid, 0, st, G);
-  if (int e = launch_status("k_eca_fold")) return e;
-  size_t smem = 0;
-  for (int l = 0; l < n; ++l) smem = std::max(smem, (((static_cast<size_t>(lv[l].a.g.C) + 1) & ~static_cast<size_t>(1)) + 2 * static_cast<size_t>(lv[l].a.g.C)) * sizeof(float));
-  const int tgrid = fill_starts(G, lv, n, [&](const EcaNhwcBwdArgs& a) { return kEcaRoles + xcd_grid(a.a.g.B, a.n.ntile); });
-#define CALL_ENB(Tt, Vv) if (sig.gmask) LAUNCH((k_eca_bwd_nhwc<Tt, Vv, true>), tgrid, smem, st, G); else LAUNCH((k_eca_bwd_nhwc<Tt, Vv, false>), tgrid, smem, st, G)
-  DISPATCH_T_VEC8(sig.dtype, sig.vec, CALL_ENB);
-#undef CALL_ENB
-  return launch_status("k_eca_bwd_nhwc");
+  Group<EcaNhwcBwdArgs> G = make_group(lv, n);
+  auto reduce = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_eca_reduce_nhwc<elem_t<decltype(t)>, v.value>; });
+  if (int e = launch_group("k_eca_reduce_nhwc", reduce, G, [](const EcaNhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }, 0, st)) return e;
+  if (int e = launch_group("k_eca_fold", k_eca_fold, G, [](const EcaNhwcBwdArgs& a) { return nhwc_fold_blocks(a.a.g); }, 0, st)) return e;
+  auto bwd = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
+    return with_bool(sig.gmask, [&](auto gm) { return k_eca_bwd_nhwc<elem_t<decltype(t)>, v.value, gm.value>; }); });
+  return launch_group("k_eca_bwd_nhwc", bwd, G, [](const EcaNhwcBwdArgs& a) { return kEcaRoles + xcd_grid(a.a.g.B, a.n.ntile); },
+                      [](const EcaNhwcBwdArgs& a) { return eca_bwd_nhwc_smem(a.a.g); }, st);
 }
 
 extern "C" int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n_levels, void* stream) {
-  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
-  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
-  EcaBwdArgs args[MGACBAM_MAX_LEVELS];
-  Sig sigs[MGACBAM_MAX_LEVELS];
-  EcaNhwcBwdArgs nargs[MGACBAM_MAX_LEVELS];
-  Sig nsigs[MGACBAM_MAX_LEVELS];
-  int nc = 0, nn = 0;
-  for (int l = 0; l < n_levels; ++l) {
-    const mgacbam_eca_bwd_level_t& L = levels[l];
-    if (!L.x || !L.gy || !L.ctx || !L.scratch || !L.gx || !L.gw || !L.gbeta) return fail(MGACBAM_E_NULL, "eca backward: NULL pointer");
-    if (L.gmask && !L.mask) return fail(MGACBAM_E_NULL, "eca backward: gmask requested but mask is NULL");
-    if (int e = eca_check_params(L.p)) return e;
-    if (int e = check_shape(L.B, L.C, L.H, L.W, 1, L.p.k)) return e;
-    if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "eca backward: dtype %d", L.dtype);
-    if (int e = eca_check_flags("eca backward", L.flags, L.C)) return e;
-    const bool nhwc = (L.flags & MGACBAM_LAYOUT_NHWC) != 0;
-    const int VEC = level_vec(nhwc, L.C, L.H, L.W, L.dtype);
-    const size_t need = VEC * elem_size(L.dtype);
-    if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
-        !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 16)))
-      return fail(MGACBAM_E_ALIGN, "eca backward%s: x/gy/gx must be %zu-byte aligned, ctx/scratch/gmask 16-byte", nhwc ? " (NHWC)" : "", need);
-    if (int e = check_capacity("eca backward", "ctx", eca_ctx_need(L.B, L.C, L.H, L.W, nhwc, VEC), L.ctx_bytes)) return e;
-    if (int e = check_capacity("eca backward", "scratch", eca_scratch_need(L.B, L.C, L.H, L.W, nhwc, VEC), L.scratch_bytes)) return e;
-    EcaBwdArgs A;
-    A.x = L.x; A.mask = L.mask; A.gy = L.gy; A.gx = L.gx; A.gmask = L.gmask; A.gw = L.gw; A.gbeta = L.gbeta;
-    A.c = eca_ctx_ptrs(const_cast<void*>(L.ctx), L.B, L.C, L.H, L.W);
-    A.w1d = L.p.w; A.beta = L.p.beta;
-    A.s.gg = static_cast<float*>(L.scratch);
-    A.g = eca_geo(L.B, L.C, L.H, L.W, L.p);
-    A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
-    Sig s{L.dtype, VEC, L.mask != nullptr, 0, L.gmask != nullptr, 0};
-    if (nhwc) {
-      A.nt = 0;
-      s.nhwc = 1;
-      s.weight = L.C;
-      nargs[nn] = EcaNhwcBwdArgs{A, nhwc_geo(L.C, L.H, L.W, VEC), reinterpret_cast<float*>(static_cast<char*>(L.scratch) + eca_gg_bytes(L.B, L.C))};
-      nsigs[nn++] = s;
-    } else {
-      A.nt = chan_tiles(A.t, L.H, L.W, VEC);
-      s.weight = L.C * A.t.chan_tx;
-      args[nc] = A;
-      sigs[nc++] = s;
-    }
-  }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (nc) if (int e = for_each_group(args, sigs, nc, [&](EcaBwdArgs* g, int m, const Sig& s) { return eca_backward_group(g, m, s, st); })) return e;
-  if (nn) if (int e = for_each_group(nargs, nsigs, nn, [&](EcaNhwcBwdArgs* g, int m, const Sig& s) { return eca_backward_group_nhwc(g, m, s, st); })) return e;
-  g_err[0] = 0;
-  return 0;
+  return run_levels<EcaBwdArgs, EcaNhwcBwdArgs>(levels, n_levels,
+      [](const mgacbam_eca_bwd_level_t& L, EcaNhwcBwdArgs& N, Sig& s) { return eca_level("eca backward", L, N, s); },
+      [&](EcaBwdArgs* g, int m, const Sig& s) { return eca_backward_group(g, m, s, st); },
+      [&](EcaNhwcBwdArgs* g, int m, const Sig& s) { return eca_backward_group_nhwc(g, m, s, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -279,10 +209,8 @@ extern "C" int mgacbam_resize_nearest(const float* src, float* dst, int n_planes
   const size_t total = static_cast<size_t>(n_planes) * out_h * out_w;
   size_t grid = (total + kBlock - 1) / kBlock;
   if (grid > 4096) grid = 4096;
-  void* kargs[] = {&src, &dst, &n_planes, &in_h, &in_w, &out_h, &out_w};
-  g_launch_err = hipLaunchKernel(reinterpret_cast<const void*>(k_resize_nearest), dim3(static_cast<unsigned>(grid)), dim3(kBlock), kargs, 0,
-                                 static_cast<hipStream_t>(stream));
-  if (int e = launch_status("k_resize_nearest")) return e;
+  if (int e = launch("k_resize_nearest", k_resize_nearest, grid, kBlock, 0, static_cast<hipStream_t>(stream), src, dst, n_planes, in_h, in_w,
+                     out_h, out_w)) return e;
   g_err[0] = 0;
   return 0;
 }
@@ -304,8 +232,7 @@ extern "C" int mgapmg_forward(const float* p, const float* u1, const float* u2, 
   GaterArgs A;
   if (int e = pmg_args(n, cfg, A)) return e;
   A.p = p; A.u1 = u1; A.u2 = u2; A.out = out; A.msoft = msoft;
-  LAUNCH(k_pmg_fwd, pmg_grid(n), 0, static_cast<hipStream_t>(stream), A);
-  if (int e = launch_status("k_pmg_fwd")) return e;
+  if (int e = launch("k_pmg_fwd", k_pmg_fwd, pmg_grid(n), kBlock, 0, static_cast<hipStream_t>(stream), A)) return e;
   g_err[0] = 0;
   return 0;
 }
@@ -315,9 +242,7 @@ extern "C" int mgapmg_backward(const float* p, const float* msoft, const float* 
   GaterArgs A;
   if (int e = pmg_args(n, cfg, A)) return e;
   A.p = p; A.msoft = const_cast<float*>(msoft); A.gout = gout; A.gp = gp;
-  LAUNCH(k_pmg_bwd, pmg_grid(n), 0, static_cast<hipStream_t>(stream), A);
-  if (int e = launch_status("k_pmg_bwd")) return e;
+  if (int e = launch("k_pmg_bwd", k_pmg_bwd, pmg_grid(n), kBlock, 0, static_cast<hipStream_t>(stream), A)) return e;
   g_err[0] = 0;
   return 0;
 }
-

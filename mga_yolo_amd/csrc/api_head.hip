@@ -128,7 +128,7 @@ static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, in
   if (!P.w1 || !P.bn_weight || !P.bn_bias || !P.running_mean || !P.running_var || !P.wh || !P.bh)
     return fail(MGACBAM_E_NULL, "mask head: NULL parameter pointer");
   if (int e = head_check_shape(B, C, H, W, P.hidden)) return e;
-  if (dtype < MGACBAM_F32 || dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "mask head: dtype %d", dtype);
+  if (int e = check_dtype("mask head", dtype)) return e;
   if (!(P.eps > 0.f) || !(P.momentum >= 0.f && P.momentum <= 1.f)) return fail(MGACBAM_E_SHAPE, "mask head: eps=%g momentum=%g", P.eps, P.momentum);
   const HeadTiling t = head_tiling(B, C, H, W, P.hidden, nhwc);
   memset(&A, 0, sizeof(A));
@@ -136,9 +136,7 @@ static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, in
   A.g.B = B; A.g.C = C; A.g.hid = P.hidden; A.g.H = H; A.g.W = W; A.g.HW = H * W; A.g.hidp = t.hidp; A.g.cp = t.cp;
   A.g.eps = P.eps; A.g.momentum = P.momentum; A.g.training = P.training ? 1 : 0;
   const HeadCtxLayout L = head_ctx_layout(B, C, H, W, P.hidden, nhwc);
-  char* cp = static_cast<char*>(ctx);
-  A.c = HeadCtx{reinterpret_cast<float*>(cp + L.z), reinterpret_cast<float*>(cp + L.mean), reinterpret_cast<float*>(cp + L.rstd),
-                reinterpret_cast<float*>(cp + L.par), reinterpret_cast<float*>(cp + L.part)};
+  A.c = HeadCtx{at(ctx, L.z), at(ctx, L.mean), at(ctx, L.rstd), at(ctx, L.par), at(ctx, L.part)};
   A.tile_px = t.tile_px; A.tiles_per_sample = t.tps; A.nwg = t.nwg;
   A.gx_tile_px = t.gx_tile_px; A.gx_tiles_per_sample = t.gx_tps; A.fw_kw = t.fw_kw; A.gx_kw = t.gx_kw; A.fw_mtw = t.fw_mtw; A.gx_mtw = t.gx_mtw;
   A.trace = knobs().trace; A.trace_base = 0;
@@ -148,24 +146,18 @@ static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, in
   sig.weight = C;
   return 0;
 }
-static size_t head_gemm_smem(const HeadArgs* lv, int n) {
-  size_t m = 0;
-  for (int l = 0; l < n; ++l) m = std::max(m, (static_cast<size_t>(kHeadLdsX) + 8 * lv[l].g.hidp) * sizeof(float));
-  return m;
-}
+static size_t head_gemm_smem(const HeadArgs& a) { return (static_cast<size_t>(kHeadLdsX) + 8 * a.g.hidp) * sizeof(float); }
 static int max_hidp(const HeadArgs* lv, int n) {
   int m = 0;
   for (int l = 0; l < n; ++l) m = std::max(m, lv[l].g.hidp);
   return m;
 }
 static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<HeadArgs> G;
-  G.n = n;
-  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
+  Group<HeadArgs> G = make_group(lv, n);
   {
     // one launch per accumulator template (two tiles per wave: hidden <= 128, i.e. every level of the n/s models; four beyond): each level
     // alone is latency-bound, so levels that share a launch overlap each other
-    const size_t smem = head_gemm_smem(lv, n);
+    const size_t smem = group_smem(G, head_gemm_smem);
     for (int pass = 0; pass < 2; ++pass) {
       Group<HeadArgs> Gm;
       Gm.n = 0;
@@ -180,10 +172,9 @@ static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t s
       for (int l = 0; l < Gm.n; ++l) Gm.lv[l].trace_base = pass * 8192;
       if (sig.nhwc) {                                             // channels-last features: head_nhwc.cuh (the level's MTW is its own fw_mtw)
         const size_t nsmem = static_cast<size_t>(8) * max_hidp(lv, n) * sizeof(float);
-#define CALL_HN(Tt, Cv) { if (mtw <= 2) { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 2>), grid, nsmem, st, Gm); } else { LAUNCH((k_head_gemm_nhwc<Tt, Cv, 4>), grid, nsmem, st, Gm); } }
-        DISPATCH_T_VEC(sig.dtype, sig.cvec, CALL_HN);
-#undef CALL_HN
-        if (int e = launch_status("k_head_gemm_nhwc")) return e;
+        auto kernel = with_elem_vec(sig.dtype, sig.cvec, [&](auto t, auto cv) {
+          return with_bool(mtw <= 2, [&](auto two) { return k_head_gemm_nhwc<elem_t<decltype(t)>, cv.value, two.value ? 2 : 4>; }); });
+        if (int e = launch("k_head_gemm_nhwc", kernel, grid, kBlock, nsmem, st, Gm)) return e;
         continue;
       }
       for (int l = 0; l < Gm.n; ++l) {                            // the wave arrangement follows the template the level runs under
@@ -191,105 +182,56 @@ static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t s
         head_waves(Gm.lv[l].g.hidp / 16, mtw, Gm.lv[l].g.C, pw, Gm.lv[l].fw_kw);
         if (pw * 16 * sig.vec != Gm.lv[l].tile_px) return fail(MGACBAM_E_SHAPE, "mask head: inconsistent tiling");   // (cannot happen: see head_tiling)
       }
-#define CALL_HP3(Tt, Vv, Mm) LAUNCH((k_head_gemm<Tt, Vv, false, Mm>), grid, smem, st, Gm)
-#define CALL_HP(Tt, Vv) { if (mtw <= 2) { CALL_HP3(Tt, Vv, 2); } else { CALL_HP3(Tt, Vv, 4); } }
-      DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_HP);
-#undef CALL_HP
-#undef CALL_HP3
-      if (int e = launch_status("k_head_gemm<fwd>")) return e;
+      auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) {
+        return with_bool(mtw <= 2, [&](auto two) { return k_head_gemm<elem_t<decltype(t)>, v.value, false, two.value ? 2 : 4>; }); });
+      if (int e = launch("k_head_gemm<fwd>", kernel, grid, kBlock, smem, st, Gm)) return e;
     }
   }
-  {
-    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.hid; });
-    LAUNCH(k_head_stats, grid, 0, st, G);
-    if (int e = launch_status("k_head_stats")) return e;
-  }
-  {
-    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.nwg_out; });
-    const size_t smem = 0;
-#define CALL_HO(Tt) { if (sig.vec == 4) { LAUNCH((k_head_out<Tt, 4>), grid, smem, st, G); } else { LAUNCH((k_head_out<Tt, 1>), grid, smem, st, G); } }
-    switch (sig.lf32 ? MGACBAM_F32 : sig.dtype) {              // (the kernel's element type is the LOGITS' type: z is fp32)
-      case MGACBAM_F32: CALL_HO(float); break;
-      case MGACBAM_F16: CALL_HO(__half); break;
-      default: CALL_HO(bf16_t); break;
-    }
-#undef CALL_HO
-    if (int e = launch_status("k_head_out")) return e;
-  }
+  if (int e = launch_group("k_head_stats", k_head_stats, G, [](const HeadArgs& a) { return a.g.hid; }, 0, st)) return e;
+  // (the kernel's element type is the LOGITS' type: z is fp32)
+  auto out = with_elem(sig.lf32 ? MGACBAM_F32 : sig.dtype, [&](auto t) {
+    return with_int<4, 1>(sig.vec, [&](auto v) { return k_head_out<elem_t<decltype(t)>, v.value>; }); });
+  return launch_group("k_head_out", out, G, [](const HeadArgs& a) { return a.nwg_out; }, 0, st);
+}
+static int head_forward_level(const mgahead_fwd_level_t& L, HeadArgs& A, Sig& sig) {
+  if (!L.x || !L.logits || !L.ctx) return fail(MGACBAM_E_NULL, "mask head forward: x / logits / ctx is NULL");
+  const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
+  if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, nhwc, L.ctx, A, sig)) return e;
+  if (int e = check_capacity("mask head forward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc).total, L.ctx_bytes)) return e;
+  const size_t need = (nhwc ? nhwc_vec(L.C, L.dtype) : sig.vec) * elem_size(L.dtype);
+  if (!aligned_to(L.x, need) || !aligned_to(L.ctx, 16)) return fail(MGACBAM_E_ALIGN, "mask head forward: x must be %zu-byte aligned, ctx 16-byte", need);
+  A.x = L.x; A.logits = L.logits;
+  sig.lf32 = (L.flags & MGAHEAD_LOGITS_F32) ? 1 : 0;
   return 0;
 }
 extern "C" int mgahead_forward(const mgahead_fwd_level_t* levels, int n_levels, void* stream) {
-  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
-  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
-  HeadArgs args[MGACBAM_MAX_LEVELS];
-  Sig sigs[MGACBAM_MAX_LEVELS];
-  for (int l = 0; l < n_levels; ++l) {
-    const mgahead_fwd_level_t& L = levels[l];
-    if (!L.x || !L.logits || !L.ctx) return fail(MGACBAM_E_NULL, "mask head forward: x / logits / ctx is NULL");
-    const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
-    if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, nhwc, L.ctx, args[l], sigs[l])) return e;
-    if (int e = check_capacity("mask head forward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc).total, L.ctx_bytes)) return e;
-    const size_t need = (nhwc ? nhwc_vec(L.C, L.dtype) : sigs[l].vec) * elem_size(L.dtype);
-    if (!aligned_to(L.x, need) || !aligned_to(L.ctx, 16)) return fail(MGACBAM_E_ALIGN, "mask head forward: x must be %zu-byte aligned, ctx 16-byte", need);
-    args[l].x = L.x; args[l].logits = L.logits;
-    sigs[l].lf32 = (L.flags & MGAHEAD_LOGITS_F32) ? 1 : 0;
-  }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int e = for_each_group(args, sigs, n_levels, [&](HeadArgs* g, int m, const Sig& s) { return head_forward_group(g, m, s, st); })) return e;
-  g_err[0] = 0;
-  return 0;
+  return run_levels<HeadArgs>(levels, n_levels, head_forward_level,
+                              [&](HeadArgs* g, int m, const Sig& s) { return head_forward_group(g, m, s, st); });
 }
 static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<HeadArgs> G;
-  G.n = n;
-  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
-  {
-    int hl = 0;
-    for (int l = 0; l < n; ++l) hl = std::max(hl, lv[l].act_hl_max);
-    for (int l = 0; l < n; ++l) { lv[l].act_hl_max = hl; G.lv[l].act_hl_max = hl; }      // the reduction scratch sits behind the launch's longest run
-    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.nwg1 * ((a.g.hid + kHeadJC - 1) / kHeadJC); });
-    const size_t smem = (static_cast<size_t>(hl) + 16 * kHeadJC * kHeadNStat) * sizeof(float);
-    switch (sig.lf32 ? MGACBAM_F32 : sig.dtype) {              // (the kernel's element type is g_logits' type)
-      case MGACBAM_F32: LAUNCH(k_head_bwd_act<float>, grid, smem, st, G); break;
-      case MGACBAM_F16: LAUNCH(k_head_bwd_act<__half>, grid, smem, st, G); break;
-      default: LAUNCH(k_head_bwd_act<bf16_t>, grid, smem, st, G); break;
-    }
-    if (int e = launch_status("k_head_bwd_act")) return e;
-  }
-  {
-    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.hid; });
-    LAUNCH(k_head_bwd_fin, grid, 0, st, G);
-    if (int e = launch_status("k_head_bwd_fin")) return e;
-  }
+  int hl = 0;
+  for (int l = 0; l < n; ++l) hl = std::max(hl, lv[l].act_hl_max);
+  for (int l = 0; l < n; ++l) lv[l].act_hl_max = hl;            // the reduction scratch sits behind the launch's longest run
+  Group<HeadArgs> G = make_group(lv, n);
+  // (the kernel's element type is g_logits' type)
+  auto act = with_elem(sig.lf32 ? MGACBAM_F32 : sig.dtype, [](auto t) { return k_head_bwd_act<elem_t<decltype(t)>>; });
+  if (int e = launch_group("k_head_bwd_act", act, G, [](const HeadArgs& a) { return a.nwg1 * ((a.g.hid + kHeadJC - 1) / kHeadJC); },
+                           (static_cast<size_t>(hl) + 16 * kHeadJC * kHeadNStat) * sizeof(float), st)) return e;
+  if (int e = launch_group("k_head_bwd_fin", k_head_bwd_fin, G, [](const HeadArgs& a) { return a.g.hid; }, 0, st)) return e;
+  auto gx_tiles = [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; };
   if (sig.nhwc) {                                                 // channels-last features: head_nhwc.cuh
     const size_t hp = static_cast<size_t>(max_hidp(lv, n));
-    {
-      const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
-      const size_t smem = 5 * hp * sizeof(float);
-#define CALL_HX(Tt, Cv) LAUNCH((k_head_gx_nhwc<Tt, Cv>), grid, smem, st, G)
-      DISPATCH_T_VEC(sig.dtype, sig.cvec, CALL_HX);
-#undef CALL_HX
-      if (int e = launch_status("k_head_gx_nhwc")) return e;
-    }
-    {
-      const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.ncb * a.nshare; });
-      const size_t smem = (5 * hp + 2 * static_cast<size_t>(kHeadGwPx) * kHeadGwPitch) * sizeof(float);
-#define CALL_HW(Tt, Cv) LAUNCH((k_head_gw_nhwc<Tt, Cv>), grid, smem, st, G)
-      DISPATCH_T_VEC(sig.dtype, sig.cvec, CALL_HW);
-#undef CALL_HW
-      if (int e = launch_status("k_head_gw_nhwc")) return e;
-    }
+    auto gx = with_elem_vec(sig.dtype, sig.cvec, [](auto t, auto cv) { return k_head_gx_nhwc<elem_t<decltype(t)>, cv.value>; });
+    if (int e = launch_group("k_head_gx_nhwc", gx, G, gx_tiles, 5 * hp * sizeof(float), st)) return e;
+    auto gw = with_elem_vec(sig.dtype, sig.cvec, [](auto t, auto cv) { return k_head_gw_nhwc<elem_t<decltype(t)>, cv.value>; });
+    if (int e = launch_group("k_head_gw_nhwc", gw, G, [](const HeadArgs& a) { return a.ncb * a.nshare; },
+                             (5 * hp + 2 * static_cast<size_t>(kHeadGwPx) * kHeadGwPitch) * sizeof(float), st)) return e;
   } else {
-  {
     for (int l = 0; l < n; ++l) G.lv[l].trace_base = 16384;
-    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return a.g.B * a.gx_tiles_per_sample; });
-    const size_t smem = head_gemm_smem(lv, n);
-#define CALL_HX(Tt, Vv) LAUNCH((k_head_gemm<Tt, Vv, true, 2>), grid, smem, st, G)
-    DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_HX);
-#undef CALL_HX
-    if (int e = launch_status("k_head_gemm<gx>")) return e;
-  }
-  {                                                               // dW1 partials
+    auto gx = with_elem_vec(sig.dtype, sig.vec, [](auto t, auto v) { return k_head_gemm<elem_t<decltype(t)>, v.value, true, 2>; });
+    if (int e = launch_group("k_head_gemm<gx>", gx, G, gx_tiles, head_gemm_smem, st)) return e;
+    // dW1 partials
     for (int pass = 0; pass < 2; ++pass) {                         // pass 0: the levels that take the LDS-staged form, pass 1: the rest
       Group<HeadArgs> Gw;
       Gw.n = 0;
@@ -304,58 +246,38 @@ static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t 
       if (!Gw.n) continue;
       Gw.start[Gw.n] = grid;
       if (pass == 0) {
-        switch (sig.dtype) {
-          case MGACBAM_F32: LAUNCH(k_head_bwd_gw2<float>, grid, smem, st, Gw); break;
-          case MGACBAM_F16: LAUNCH(k_head_bwd_gw2<__half>, grid, smem, st, Gw); break;
-          default: LAUNCH(k_head_bwd_gw2<bf16_t>, grid, smem, st, Gw); break;
-        }
-        if (int e = launch_status("k_head_bwd_gw2")) return e;
+        auto gw2 = with_elem(sig.dtype, [](auto t) { return k_head_bwd_gw2<elem_t<decltype(t)>>; });
+        if (int e = launch("k_head_bwd_gw2", gw2, grid, kBlock, smem, st, Gw)) return e;
         continue;
       }
-#define CALL_HW(Tt, Vv) LAUNCH((k_head_bwd_gw<Tt, Vv>), grid, smem, st, Gw)
-      DISPATCH_T_VEC(sig.dtype, sig.vec, CALL_HW);
-#undef CALL_HW
-      if (int e = launch_status("k_head_bwd_gw")) return e;
+      auto gw = with_elem_vec(sig.dtype, sig.vec, [](auto t, auto v) { return k_head_bwd_gw<elem_t<decltype(t)>, v.value>; });
+      if (int e = launch("k_head_bwd_gw", gw, grid, kBlock, smem, st, Gw)) return e;
     }
   }
-  }
-  {
-    const int grid = fill_starts(G, lv, n, [](const HeadArgs& a) { return (a.g.hid * a.g.C + kHeadGwfOut - 1) / kHeadGwfOut; });
-    LAUNCH(k_head_bwd_gwf, grid, 0, st, G);
-    if (int e = launch_status("k_head_bwd_gwf")) return e;
-  }
+  return launch_group("k_head_bwd_gwf", k_head_bwd_gwf, G,
+                      [](const HeadArgs& a) { return (a.g.hid * a.g.C + kHeadGwfOut - 1) / kHeadGwfOut; }, 0, st);
+}
+static int head_backward_level(const mgahead_bwd_level_t& L, HeadArgs& A, Sig& sig) {
+  if (!L.x || !L.g_logits || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "mask head backward: x / g_logits / ctx / scratch / gx is NULL");
+  if (!L.gw1 || !L.gbn_weight || !L.gbn_bias || !L.gwh || !L.gbh) return fail(MGACBAM_E_NULL, "mask head backward: NULL parameter-gradient pointer");
+  const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
+  if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, nhwc, const_cast<void*>(L.ctx), A, sig)) return e;
+  const size_t need = (nhwc ? nhwc_vec(L.C, L.dtype) : sig.vec) * elem_size(L.dtype);
+  if (!aligned_to(L.x, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) || !aligned_to(L.scratch, 16))
+    return fail(MGACBAM_E_ALIGN, "mask head backward: x/gx must be %zu-byte aligned, ctx/scratch 16-byte", need);
+  A.x = L.x; A.gl = L.g_logits; A.gx = L.gx;
+  A.gw1 = L.gw1; A.ggamma = L.gbn_weight; A.gbeta = L.gbn_bias; A.gwh = L.gwh; A.gbh = L.gbh;
+  A.accum_gx = (L.flags & MGAHEAD_BWD_ACCUM_GX) ? 1 : 0;
+  sig.lf32 = (L.flags & MGAHEAD_LOGITS_F32) ? 1 : 0;
+  A.gl2 = L.g_logits2;
+  const HeadScratchLayout SL = head_scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc);
+  if (int e = check_capacity("mask head backward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc).total, L.ctx_bytes)) return e;
+  if (int e = check_capacity("mask head backward", "scratch", SL.total, L.scratch_bytes)) return e;
+  A.s = HeadScratch{at(L.scratch, SL.ga), at(L.scratch, SL.part1), at(L.scratch, SL.kst), at(L.scratch, SL.gwpart)};
   return 0;
 }
 extern "C" int mgahead_backward(const mgahead_bwd_level_t* levels, int n_levels, void* stream) {
-  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
-  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
-  HeadArgs args[MGACBAM_MAX_LEVELS];
-  Sig sigs[MGACBAM_MAX_LEVELS];
-  for (int l = 0; l < n_levels; ++l) {
-    const mgahead_bwd_level_t& L = levels[l];
-    if (!L.x || !L.g_logits || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "mask head backward: x / g_logits / ctx / scratch / gx is NULL");
-    if (!L.gw1 || !L.gbn_weight || !L.gbn_bias || !L.gwh || !L.gbh) return fail(MGACBAM_E_NULL, "mask head backward: NULL parameter-gradient pointer");
-    const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
-    if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, nhwc, const_cast<void*>(L.ctx), args[l], sigs[l])) return e;
-    const size_t need = (nhwc ? nhwc_vec(L.C, L.dtype) : sigs[l].vec) * elem_size(L.dtype);
-    if (!aligned_to(L.x, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) || !aligned_to(L.scratch, 16))
-      return fail(MGACBAM_E_ALIGN, "mask head backward: x/gx must be %zu-byte aligned, ctx/scratch 16-byte", need);
-    HeadArgs& A = args[l];
-    A.x = L.x; A.gl = L.g_logits; A.gx = L.gx;
-    A.gw1 = L.gw1; A.ggamma = L.gbn_weight; A.gbeta = L.gbn_bias; A.gwh = L.gwh; A.gbh = L.gbh;
-    A.accum_gx = (L.flags & MGAHEAD_BWD_ACCUM_GX) ? 1 : 0;
-    sigs[l].lf32 = (L.flags & MGAHEAD_LOGITS_F32) ? 1 : 0;
-    A.gl2 = L.g_logits2;
-    const HeadScratchLayout SL = head_scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc);
-    if (int e = check_capacity("mask head backward", "ctx", head_ctx_layout(L.B, L.C, L.H, L.W, L.p.hidden, nhwc).total, L.ctx_bytes)) return e;
-    if (int e = check_capacity("mask head backward", "scratch", SL.total, L.scratch_bytes)) return e;
-    char* sp = static_cast<char*>(L.scratch);
-    A.s = HeadScratch{reinterpret_cast<float*>(sp + SL.ga), reinterpret_cast<float*>(sp + SL.part1), reinterpret_cast<float*>(sp + SL.kst),
-                      reinterpret_cast<float*>(sp + SL.gwpart)};
-  }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int e = for_each_group(args, sigs, n_levels, [&](HeadArgs* g, int m, const Sig& s) { return head_backward_group(g, m, s, st); })) return e;
-  g_err[0] = 0;
-  return 0;
+  return run_levels<HeadArgs>(levels, n_levels, head_backward_level,
+                              [&](HeadArgs* g, int m, const Sig& s) { return head_backward_group(g, m, s, st); });
 }
-

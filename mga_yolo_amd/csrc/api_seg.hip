@@ -13,7 +13,8 @@ static int seg_check(const mgaseg_level_t* levels, int n, const mgaseg_cfg_t* cf
     if (!L.logits || !L.target || (bwd && !L.glogits)) return fail(MGACBAM_E_NULL, "segloss: level %d has a NULL pointer", l);
     if (L.B < 1 || L.H < 1 || L.W < 1 || L.Ht < 1 || L.Wt < 1 || static_cast<long long>(L.H) * L.W > (1ll << 30))
       return fail(MGACBAM_E_SHAPE, "segloss: level %d bad shape B=%d H=%d W=%d Ht=%d Wt=%d", l, L.B, L.H, L.W, L.Ht, L.Wt);
-    if (L.dtype != levels[0].dtype || L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "segloss: dtype %d", L.dtype);
+    if (L.dtype != levels[0].dtype) return fail(MGACBAM_E_DTYPE, "segloss: dtype %d", L.dtype);
+    if (int e = check_dtype("segloss", L.dtype)) return e;
     if (L.resize != MGASEG_NEAREST && L.resize != MGASEG_BILINEAR) return fail(MGACBAM_E_SHAPE, "segloss: level %d resize mode %d", l, L.resize);
   }
   return 0;
@@ -56,14 +57,9 @@ static int seg_forward_impl(const mgaseg_level_t* levels, int n, const mgaseg_cf
   A.out = out;
   if (kd) { A.has_kd = 1; A.kd = *kd; }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (levels[0].dtype) {
-    case MGACBAM_F32: LAUNCH(k_seg_partial<float>, grid, 0, st, A); break;
-    case MGACBAM_F16: LAUNCH(k_seg_partial<__half>, grid, 0, st, A); break;
-    default: LAUNCH(k_seg_partial<bf16_t>, grid, 0, st, A); break;
-  }
-  if (int e = launch_status("k_seg_partial")) return e;
-  LAUNCH(k_seg_final, 1, 0, st, A);
-  if (int e = launch_status("k_seg_final")) return e;
+  auto partial = with_elem(levels[0].dtype, [](auto t) { return k_seg_partial<elem_t<decltype(t)>>; });
+  if (int e = launch("k_seg_partial", partial, grid, kBlock, 0, st, A)) return e;
+  if (int e = launch("k_seg_final", k_seg_final, 1, kBlock, 0, st, A)) return e;
   g_err[0] = 0;
   return 0;
 }
@@ -76,12 +72,8 @@ static int seg_backward_impl(const mgaseg_level_t* levels, int n, const mgaseg_c
   A.gout = gout;
   if (kd) { A.has_kd = 1; A.kd = *kd; }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (levels[0].dtype) {
-    case MGACBAM_F32: LAUNCH(k_seg_bwd<float>, grid, 0, st, A); break;
-    case MGACBAM_F16: LAUNCH(k_seg_bwd<__half>, grid, 0, st, A); break;
-    default: LAUNCH(k_seg_bwd<bf16_t>, grid, 0, st, A); break;
-  }
-  if (int e = launch_status("k_seg_bwd")) return e;
+  auto bwd = with_elem(levels[0].dtype, [](auto t) { return k_seg_bwd<elem_t<decltype(t)>>; });
+  if (int e = launch("k_seg_bwd", bwd, grid, kBlock, 0, st, A)) return e;
   g_err[0] = 0;
   return 0;
 }
@@ -117,9 +109,7 @@ extern "C" int mgakendall_forward(const float* det, int n_det, const float* seg,
   if (!det || !seg || !log_vars || !total) return fail(MGACBAM_E_NULL, "kendall: NULL pointer");
   if (n_det < 1 || n_det > 4096) return fail(MGACBAM_E_SHAPE, "kendall: n_det=%d", n_det);
   KendallArgs A{det, seg, log_vars, nullptr, total, nullptr, nullptr, nullptr, n_det};
-  void* p[] = {&A};
-  g_launch_err = hipLaunchKernel(reinterpret_cast<const void*>(k_kendall_fwd), dim3(1), dim3(kWave), p, 0, static_cast<hipStream_t>(stream));
-  if (int e = launch_status("k_kendall_fwd")) return e;
+  if (int e = launch("k_kendall_fwd", k_kendall_fwd, 1, kWave, 0, static_cast<hipStream_t>(stream), A)) return e;
   g_err[0] = 0;
   return 0;
 }
@@ -128,10 +118,7 @@ extern "C" int mgakendall_backward(const float* det, int n_det, const float* seg
   if (!det || !seg || !log_vars || !g_total || !g_det || !g_seg || !g_log_vars) return fail(MGACBAM_E_NULL, "kendall: NULL pointer");
   if (n_det < 1 || n_det > 4096) return fail(MGACBAM_E_SHAPE, "kendall: n_det=%d", n_det);
   KendallArgs A{det, seg, log_vars, g_total, nullptr, g_det, g_seg, g_log_vars, n_det};
-  void* p[] = {&A};
-  g_launch_err = hipLaunchKernel(reinterpret_cast<const void*>(k_kendall_bwd), dim3(1), dim3(kWave), p, 0, static_cast<hipStream_t>(stream));
-  if (int e = launch_status("k_kendall_bwd")) return e;
+  if (int e = launch("k_kendall_bwd", k_kendall_bwd, 1, kWave, 0, static_cast<hipStream_t>(stream), A)) return e;
   g_err[0] = 0;
   return 0;
 }
-

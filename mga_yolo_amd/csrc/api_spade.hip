@@ -22,11 +22,10 @@ static SpTiling sp_tiling(int H, int W) {
 struct SpLayout { size_t mean, rstd, wpack, wpackT, gamma, base; };
 static SpLayout sp_ctx_layout(int B, int C, int hidden) {
   SpLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
+  Carver cv;
   const size_t BC = static_cast<size_t>(B) * C, nw = static_cast<size_t>(2) * 9 * C * hidden;
-  L.mean = take(BC); L.rstd = take(BC); L.wpack = take(nw); L.wpackT = take(nw);
-  L.gamma = o; L.base = o;
+  L.mean = cv.take(BC); L.rstd = cv.take(BC); L.wpack = cv.take(nw); L.wpackT = cv.take(nw);
+  L.gamma = cv.total; L.base = cv.total;
   return L;
 }
 static size_t sp_gamma_bytes(int B, int C, int H, int W, size_t elem) { return align16(static_cast<size_t>(B) * C * H * W * elem); }
@@ -38,14 +37,13 @@ static SpScratch sp_scratch_layout(int B, int C, int H, int W, int hidden) {
   const int tpc = (total + nchunk - 1) / nchunk;
   nchunk = (total + tpc - 1) / tpc;
   SpScratch L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
+  Carver cv;
   const size_t BC = static_cast<size_t>(B) * C;
-  L.red = take(4 * BC); L.stat = take(2 * BC);
-  L.dwpart = take(static_cast<size_t>(nchunk) * 2 * C * hidden * 9);
-  L.u = take(static_cast<size_t>(B) * 9 * H * W);
-  L.w0part = take(static_cast<size_t>(total) * hidden * 10);
-  L.total = o; L.nchunk = nchunk; L.tpc = tpc;
+  L.red = cv.take(4 * BC); L.stat = cv.take(2 * BC);
+  L.dwpart = cv.take(static_cast<size_t>(nchunk) * 2 * C * hidden * 9);
+  L.u = cv.take(static_cast<size_t>(B) * 9 * H * W);
+  L.w0part = cv.take(static_cast<size_t>(total) * hidden * 10);
+  L.total = cv.total; L.nchunk = nchunk; L.tpc = tpc;
   return L;
 }
 static int sp_check_shape(const char* what, int B, int C, int H, int W, int hidden) {
@@ -87,8 +85,6 @@ static void sp_allow_lds(K kernel, size_t smem) {
   if (have >= smem) return;
   if (hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) == hipSuccess) have = smem;
 }
-#define SP_DISPATCH_T(dtype, CALL) \
-  do { if ((dtype) == MGACBAM_F32) { CALL(float); } else if ((dtype) == MGACBAM_F16) { CALL(__half); } else { CALL(bf16_t); } } while (0)
 
 // everything a level is checked for before the first launch, and its kernel arguments
 static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, SpadeArgs& A, Sig& sig) {
@@ -97,7 +93,7 @@ static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, Spade
   if (bwd && (!L.gy || !L.gx || !L.scratch)) return fail(MGACBAM_E_NULL, "%s: gy / gx / scratch is NULL", what);
   if (L.flags) return fail(MGACBAM_E_SHAPE, "%s: flags=0x%x (reserved: 0)", what, L.flags);
   if (int e = sp_check_shape(what, L.B, L.C, L.H, L.W, L.hidden)) return e;
-  if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "%s: dtype %d", what, L.dtype);
+  if (int e = check_dtype(what, L.dtype)) return e;
   if (L.norm_type != MGASPADE_NORM_IN && L.norm_type != MGASPADE_NORM_BN) return fail(MGACBAM_E_SHAPE, "%s: norm_type %d", what, L.norm_type);
   const bool bn = L.norm_type == MGASPADE_NORM_BN;
   if (bn && (!L.running_mean || !L.running_var)) return fail(MGACBAM_E_NULL, "%s: batch norm needs running_mean / running_var", what);
@@ -121,14 +117,11 @@ static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, Spade
   A.w0 = L.w0; A.b0 = L.b0; A.wg = L.wg; A.bg = L.bg; A.wb = L.wb; A.bb = L.bb;
   A.rmean = L.running_mean; A.rvar = L.running_var; A.nbt = L.num_batches_tracked;
   A.gw0 = L.gw0; A.gb0 = L.gb0; A.gwg = L.gwg; A.gbg = L.gbg; A.gwb = L.gwb; A.gbb = L.gbb;
-  char* c = static_cast<char*>(L.ctx);
-  auto cf = [&](size_t off) { return reinterpret_cast<float*>(c + off); };
-  A.mean = cf(CL.mean); A.rstd = cf(CL.rstd); A.wpack = cf(CL.wpack); A.wpackT = cf(CL.wpackT);
-  A.gamma = gamma_kept ? static_cast<void*>(c + CL.gamma) : nullptr;
+  A.mean = at(L.ctx, CL.mean); A.rstd = at(L.ctx, CL.rstd); A.wpack = at(L.ctx, CL.wpack); A.wpackT = at(L.ctx, CL.wpackT);
+  A.gamma = gamma_kept ? at<void>(L.ctx, CL.gamma) : nullptr;
   if (bwd) {
-    char* s = static_cast<char*>(L.scratch);
-    auto sf = [&](size_t off) { return reinterpret_cast<float*>(s + off); };
-    A.red = sf(SL.red); A.stat = sf(SL.stat); A.dwpart = sf(SL.dwpart); A.u = sf(SL.u); A.w0part = sf(SL.w0part);
+    A.red = at(L.scratch, SL.red); A.stat = at(L.scratch, SL.stat); A.dwpart = at(L.scratch, SL.dwpart); A.u = at(L.scratch, SL.u);
+    A.w0part = at(L.scratch, SL.w0part);
   }
   A.B = L.B; A.C = L.C; A.H = L.H; A.W = L.W; A.HW = L.H * L.W; A.hid = L.hidden;
   A.bn = bn; A.train = L.training ? 1 : 0; A.use_sigmoid = L.use_sigmoid_mask ? 1 : 0; A.has_mask = L.mask ? 1 : 0;
@@ -149,93 +142,50 @@ static int sp_ew_blocks(const SpadeArgs& a) {
 }
 static int sp_plane_blocks(const SpadeArgs& a) { return (a.B * a.C + 3) / 4; }
 
+static int sp_pack_blocks(const SpadeArgs& a) { return (2 * a.C * a.hid * 9 + kBlock - 1) / kBlock; }
+
 static int sp_forward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<SpadeArgs> G;
-  G.n = n;
-  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
-  int grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return !a.bn ? sp_plane_blocks(a) : a.train ? a.C : (a.B * a.C + kBlock - 1) / kBlock; });
-#define CALL_SS(Tt) LAUNCH(k_spade_stats<Tt>, grid, 0, st, G)
-  SP_DISPATCH_T(sig.dtype, CALL_SS);
-#undef CALL_SS
-  if (int e = launch_status("k_spade_stats")) return e;
+  Group<SpadeArgs> G = make_group(lv, n);
+  auto stats = with_elem(sig.dtype, [](auto t) { return k_spade_stats<elem_t<decltype(t)>>; });
+  auto stat_blocks = [](const SpadeArgs& a) { return !a.bn ? sp_plane_blocks(a) : a.train ? a.C : (a.B * a.C + kBlock - 1) / kBlock; };
+  if (int e = launch_group("k_spade_stats", stats, G, stat_blocks, 0, st)) return e;
   if (!sig.has_mask) {
-    grid = fill_starts(G, lv, n, sp_ew_blocks);
-#define CALL_SE(Tt) LAUNCH((k_spade_ew<Tt, 0>), grid, 0, st, G)
-    SP_DISPATCH_T(sig.dtype, CALL_SE);
-#undef CALL_SE
-    return launch_status("k_spade_ew");
+    auto ew = with_elem(sig.dtype, [](auto t) { return k_spade_ew<elem_t<decltype(t)>, 0>; });
+    return launch_group("k_spade_ew", ew, G, sp_ew_blocks, 0, st);
   }
-  grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (2 * a.C * a.hid * 9 + kBlock - 1) / kBlock; });
-  LAUNCH(k_spade_pack, grid, 0, st, G);
-  if (int e = launch_status("k_spade_pack")) return e;
-  size_t smem = 0;
-  for (int l = 0; l < n; ++l) smem = std::max(smem, sp_fwd_smem(lv[l]));
-  grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return a.B * a.tiles * a.ncb; });
-#define CALL_SF(Tt) if (sig.gmask) { sp_allow_lds(k_spade_fwd<Tt, true>, smem); LAUNCH((k_spade_fwd<Tt, true>), grid, smem, st, G); } \
-                    else { sp_allow_lds(k_spade_fwd<Tt, false>, smem); LAUNCH((k_spade_fwd<Tt, false>), grid, smem, st, G); }
-  SP_DISPATCH_T(sig.dtype, CALL_SF);
-#undef CALL_SF
-  return launch_status("k_spade_fwd");
+  if (int e = launch_group("k_spade_pack", k_spade_pack, G, sp_pack_blocks, 0, st)) return e;
+  auto fwd = with_elem(sig.dtype, [&](auto t) {
+    return with_bool(sig.gmask, [](auto keep) { return k_spade_fwd<elem_t<decltype(t)>, keep.value>; }); });
+  sp_allow_lds(fwd, group_smem(G, sp_fwd_smem));
+  return launch_group("k_spade_fwd", fwd, G, [](const SpadeArgs& a) { return a.B * a.tiles * a.ncb; }, sp_fwd_smem, st);
 }
 
 static int sp_backward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<SpadeArgs> G;
-  G.n = n;
-  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
-  int grid = fill_starts(G, lv, n, sp_plane_blocks);
-#define CALL_SR(Tt) LAUNCH(k_spade_bwd_reduce<Tt>, grid, 0, st, G)
-  SP_DISPATCH_T(sig.dtype, CALL_SR);
-#undef CALL_SR
-  if (int e = launch_status("k_spade_bwd_reduce")) return e;
-  grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (a.C + kBlock - 1) / kBlock; });
-  LAUNCH(k_spade_bwd_fin, grid, 0, st, G);
-  if (int e = launch_status("k_spade_bwd_fin")) return e;
+  Group<SpadeArgs> G = make_group(lv, n);
+  auto reduce = with_elem(sig.dtype, [](auto t) { return k_spade_bwd_reduce<elem_t<decltype(t)>>; });
+  if (int e = launch_group("k_spade_bwd_reduce", reduce, G, sp_plane_blocks, 0, st)) return e;
+  if (int e = launch_group("k_spade_bwd_fin", k_spade_bwd_fin, G, [](const SpadeArgs& a) { return (a.C + kBlock - 1) / kBlock; }, 0, st)) return e;
   if (sig.has_mask) {
-    size_t smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, sp_dw_smem(lv[l]));
-    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (a.C / 16) * a.nchunk; });
-#define CALL_SW(Tt) { sp_allow_lds(k_spade_dw<Tt>, smem); LAUNCH(k_spade_dw<Tt>, grid, smem, st, G); }
-    SP_DISPATCH_T(sig.dtype, CALL_SW);
-#undef CALL_SW
-    if (int e = launch_status("k_spade_dw")) return e;
-    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (2 * a.C * a.hid * 9 + kBlock - 1) / kBlock; });
-    LAUNCH(k_spade_dw_fin, grid, 0, st, G);
-    if (int e = launch_status("k_spade_dw_fin")) return e;
-    smem = 0;
-    for (int l = 0; l < n; ++l) smem = std::max(smem, sp_dh_smem(lv[l]));
-    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return a.B * a.tiles; });
-#define CALL_SH(Tt) { sp_allow_lds(k_spade_dh<Tt>, smem); LAUNCH(k_spade_dh<Tt>, grid, smem, st, G); }
-    SP_DISPATCH_T(sig.dtype, CALL_SH);
-#undef CALL_SH
-    if (int e = launch_status("k_spade_dh")) return e;
-    grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return a.hid * 10; });
-    LAUNCH(k_spade_w0_fin, grid, 0, st, G);
-    if (int e = launch_status("k_spade_w0_fin")) return e;
-    if (sig.gmask) {
-      grid = fill_starts(G, lv, n, [&](const SpadeArgs& a) { return (a.B * a.HW + kBlock - 1) / kBlock; });
-      LAUNCH(k_spade_gmask, grid, 0, st, G);
-      if (int e = launch_status("k_spade_gmask")) return e;
-    }
+    auto dw = with_elem(sig.dtype, [](auto t) { return k_spade_dw<elem_t<decltype(t)>>; });
+    sp_allow_lds(dw, group_smem(G, sp_dw_smem));
+    if (int e = launch_group("k_spade_dw", dw, G, [](const SpadeArgs& a) { return (a.C / 16) * a.nchunk; }, sp_dw_smem, st)) return e;
+    if (int e = launch_group("k_spade_dw_fin", k_spade_dw_fin, G, sp_pack_blocks, 0, st)) return e;
+    auto dh = with_elem(sig.dtype, [](auto t) { return k_spade_dh<elem_t<decltype(t)>>; });
+    sp_allow_lds(dh, group_smem(G, sp_dh_smem));
+    if (int e = launch_group("k_spade_dh", dh, G, [](const SpadeArgs& a) { return a.B * a.tiles; }, sp_dh_smem, st)) return e;
+    if (int e = launch_group("k_spade_w0_fin", k_spade_w0_fin, G, [](const SpadeArgs& a) { return a.hid * 10; }, 0, st)) return e;
+    if (sig.gmask)
+      if (int e = launch_group("k_spade_gmask", k_spade_gmask, G,
+                               [](const SpadeArgs& a) { return (a.B * a.HW + kBlock - 1) / kBlock; }, 0, st)) return e;
   }
-  grid = fill_starts(G, lv, n, sp_ew_blocks);
-#define CALL_SG(Tt) LAUNCH((k_spade_ew<Tt, 1>), grid, 0, st, G)
-  SP_DISPATCH_T(sig.dtype, CALL_SG);
-#undef CALL_SG
-  return launch_status("k_spade_ew");
+  auto ew = with_elem(sig.dtype, [](auto t) { return k_spade_ew<elem_t<decltype(t)>, 1>; });
+  return launch_group("k_spade_ew", ew, G, sp_ew_blocks, 0, st);
 }
 
 static int sp_run(const char* what, const mgaspade_level_t* levels, int n_levels, void* stream, bool bwd) {
-  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
-  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
-  SpadeArgs args[MGACBAM_MAX_LEVELS];
-  Sig sigs[MGACBAM_MAX_LEVELS];
-  for (int l = 0; l < n_levels; ++l)
-    if (int e = sp_level(what, levels[l], bwd, args[l], sigs[l])) return e;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int e = for_each_group(args, sigs, n_levels, [&](SpadeArgs* g, int m, const Sig& s) {
-        return bwd ? sp_backward_group(g, m, s, st) : sp_forward_group(g, m, s, st); })) return e;
-  g_err[0] = 0;
-  return 0;
+  return run_levels<SpadeArgs>(levels, n_levels, [&](const mgaspade_level_t& L, SpadeArgs& A, Sig& s) { return sp_level(what, L, bwd, A, s); },
+      [&](SpadeArgs* g, int m, const Sig& s) { return bwd ? sp_backward_group(g, m, s, st) : sp_forward_group(g, m, s, st); });
 }
 extern "C" int mgaspade_forward(const mgaspade_level_t* levels, int n_levels, void* stream) {
   return sp_run("mgaspade_forward", levels, n_levels, stream, false);

@@ -17,6 +17,7 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #include "args.cuh"
@@ -35,21 +36,17 @@ static int fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
-// Every launch goes through hipLaunchKernel and its OWN return value is checked: the process-wide sticky error state (which
-// may hold an asynchronous error of the framework's kernels on this thread) is neither read nor cleared.
-inline thread_local hipError_t g_launch_err = hipSuccess;
-template <typename K, typename A>
-static void launch(K kernel, unsigned grid, size_t smem, hipStream_t st, const A& args) {
-  void* p[] = {const_cast<A*>(&args)};
-  g_launch_err = hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3(grid), dim3(kBlock), p, smem, st);
-}
-static int launch_status(const char* what) {
-  const hipError_t e = g_launch_err;
-  g_launch_err = hipSuccess;
+// Every launch goes through hipLaunchKernel, here and nowhere else, and its OWN return value is checked: the process-wide sticky
+// error state (which may hold an asynchronous error of the framework's kernels on this thread) is neither read nor cleared.
+// The arguments are taken as the kernel's own parameter types (a Group by reference: no copy), so a wrong one does not compile.
+template <typename... P>
+static int launch(const char* what, void (*kernel)(P...), long long grid, int block, size_t smem, hipStream_t st,
+                  const std::common_type_t<P>&... args) {
+  void* p[] = {const_cast<void*>(static_cast<const void*>(&args))...};
+  const hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3(static_cast<unsigned>(grid)), dim3(block), p, smem, st);
   if (e != hipSuccess) return fail(static_cast<int>(e), "%s: %s", what, hipGetErrorString(e));
   return 0;
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // layouts
@@ -87,39 +84,38 @@ static SyncLayout sync_layout(int B, int C, size_t HW) {
   return S;
 }
 
+// Carves a work buffer into 16-byte aligned fields of 4-byte elements, in the order they are taken (every ctx / scratch layout of the
+// library); at<T>: the field at a byte offset of a caller's buffer
+struct Carver {
+  size_t total = 0;
+  size_t take(size_t n_elems) { const size_t off = total; total = align16(total + n_elems * 4); return off; }
+};
+template <typename T = float>
+static T* at(const void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(const_cast<void*>(base)) + off); }
+
 static void ctx_layout(int B, int C, int H, int W, int hidden, mgacbam_ctx_layout_t* L) {
-  const size_t HW = static_cast<size_t>(H) * W;
-  size_t o = 0;
-  auto take = [&](size_t n_elems) { size_t at = o; o = align16(o + n_elems * 4); return static_cast<int64_t>(at); };
-  L->S = take(B); L->use = take(B); L->den = take(B);
-  L->avg = take(static_cast<size_t>(B) * C); L->mx = take(static_cast<size_t>(B) * C); L->mavg = take(static_cast<size_t>(B) * C);
-  L->valid = take(static_cast<size_t>(B) * C); L->amax = take(static_cast<size_t>(B) * C);
-  L->h_avg = take(static_cast<size_t>(B) * hidden); L->h_mx = take(static_cast<size_t>(B) * hidden);
-  L->ca = take(static_cast<size_t>(B) * C);
-  L->planes = take(static_cast<size_t>(B) * 3 * HW);
-  L->cidx = take(static_cast<size_t>(B) * HW);
-  L->sa = take(static_cast<size_t>(B) * HW);
-  L->proj = take(hidden <= MGACBAM_PROJ_MAX_HIDDEN ? static_cast<size_t>(B) * hidden * HW : 0);
+  const size_t HW = static_cast<size_t>(H) * W, BC = static_cast<size_t>(B) * C;
+  Carver cv;                                                    // (its size_t offsets become the ABI struct's int64_t)
+  L->S = cv.take(B); L->use = cv.take(B); L->den = cv.take(B);
+  L->avg = cv.take(BC); L->mx = cv.take(BC); L->mavg = cv.take(BC);
+  L->valid = cv.take(BC); L->amax = cv.take(BC);
+  L->h_avg = cv.take(static_cast<size_t>(B) * hidden); L->h_mx = cv.take(static_cast<size_t>(B) * hidden);
+  L->ca = cv.take(BC);
+  L->planes = cv.take(static_cast<size_t>(B) * 3 * HW);
+  L->cidx = cv.take(static_cast<size_t>(B) * HW);
+  L->sa = cv.take(static_cast<size_t>(B) * HW);
+  L->proj = cv.take(hidden <= MGACBAM_PROJ_MAX_HIDDEN ? static_cast<size_t>(B) * hidden * HW : 0);
   const SyncLayout S = sync_layout(B, C, HW);
-  L->sync = take(S.len);
+  L->sync = cv.take(S.len);
   L->status = L->sync + static_cast<int64_t>(4 * S.status);
-  L->total = static_cast<int64_t>(o);
+  L->total = static_cast<int64_t>(cv.total);
 }
 
-static CtxPtrs ctx_ptrs(void* base, int B, int C, int H, int W, int hidden) {
+static CtxPtrs ctx_ptrs(void* p, int B, int C, int H, int W, int hidden) {
   mgacbam_ctx_layout_t L;
   ctx_layout(B, C, H, W, hidden, &L);
-  char* p = static_cast<char*>(base);
-  CtxPtrs c;
-  c.S = reinterpret_cast<float*>(p + L.S); c.use = reinterpret_cast<float*>(p + L.use); c.den = reinterpret_cast<float*>(p + L.den);
-  c.avg = reinterpret_cast<float*>(p + L.avg); c.mx = reinterpret_cast<float*>(p + L.mx); c.mavg = reinterpret_cast<float*>(p + L.mavg);
-  c.valid = reinterpret_cast<int*>(p + L.valid); c.amax = reinterpret_cast<int*>(p + L.amax);
-  c.h_avg = reinterpret_cast<float*>(p + L.h_avg); c.h_mx = reinterpret_cast<float*>(p + L.h_mx);
-  c.ca = reinterpret_cast<float*>(p + L.ca);
-  c.planes = reinterpret_cast<float*>(p + L.planes); c.cidx = reinterpret_cast<int*>(p + L.cidx); c.sa = reinterpret_cast<float*>(p + L.sa);
-  c.proj = reinterpret_cast<float*>(p + L.proj);
-  c.sync = reinterpret_cast<int*>(p + L.sync);
-  return c;
+  return CtxPtrs{at(p, L.S), at(p, L.use), at(p, L.den), at(p, L.avg), at(p, L.mx), at(p, L.mavg), at<int>(p, L.valid), at<int>(p, L.amax),
+                 at(p, L.h_avg), at(p, L.h_mx), at(p, L.ca), at(p, L.planes), at<int>(p, L.cidx), at(p, L.sa), at(p, L.proj), at<int>(p, L.sync)};
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -311,6 +307,8 @@ static NhwcGeo nhwc_geo(int C, int H, int W, int vec) {
   n.nchunk = (n.ntile + n.rp - 1) / n.rp;
   return n;
 }
+// workgroups of the NHWC fold kernels (k_pool_fin, k_eca_fin, k_eca_fold): blocks of kNhwcFoldC channels per sample
+static int nhwc_fold_blocks(const Geo& g) { return g.B * ((g.C + kNhwcFoldC - 1) / kNhwcFoldC); }
 static size_t nhwc_ws_bytes(int B, int C, int H, int W, int vec) {
   return static_cast<size_t>(B) * nhwc_geo(C, H, W, vec).nchunk * (4 * static_cast<size_t>(C) + 4) * sizeof(float);
 }
@@ -323,24 +321,22 @@ static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int 
   const size_t HW = static_cast<size_t>(H) * W, BC = static_cast<size_t>(B) * C;
   const size_t nwsa = static_cast<size_t>(B) * wsa_tiles(t, H, W);
   ScratchLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n_elems) { size_t at = o; o = align16(o + n_elems * 4); return at; };
+  Carver cv;
   // NCHW: tile partials of A and Q live together, (B, nt, 2, C); NHWC: (B, nchunk, 3, C) = A, D, sum x*wgt
-  L.A_part = take(nhwc ? 3 * BC * nhwc_geo(C, H, W, vec).nchunk : 2 * BC * chan_tiles(t, H, W, vec));
-  L.gpre = take(B * HW); L.gplanes = take(static_cast<size_t>(B) * 3 * HW);
-  L.gwsa_part = take(nwsa * 3 * k * k);
-  L.gz = take(BC); L.gbq = take(BC);
-  L.gh_avg = take(static_cast<size_t>(B) * hidden); L.gh_mx = take(static_cast<size_t>(B) * hidden);
+  L.A_part = cv.take(nhwc ? 3 * BC * nhwc_geo(C, H, W, vec).nchunk : 2 * BC * chan_tiles(t, H, W, vec));
+  L.gpre = cv.take(B * HW); L.gplanes = cv.take(static_cast<size_t>(B) * 3 * HW);
+  L.gwsa_part = cv.take(nwsa * 3 * k * k);
+  L.gz = cv.take(BC); L.gbq = cv.take(BC);
+  L.gh_avg = cv.take(static_cast<size_t>(B) * hidden); L.gh_mx = cv.take(static_cast<size_t>(B) * hidden);
   // channel groups per sample -- NCHW: worst case (1 channel per row of the sweep kernels), NHWC: blocks of kNhwcFoldC
   const size_t cpg = nhwc ? kNhwcFoldC : kBlock / t.pool_tx;
-  L.pgh = take(static_cast<size_t>(B) * ((C + cpg - 1) / cpg) * hidden);
-  L.total = o;
+  L.pgh = cv.take(static_cast<size_t>(B) * ((C + cpg - 1) / cpg) * hidden);
+  L.total = cv.total;
   return L;
 }
-static ScratchPtrs scratch_ptrs(void* base, const ScratchLayout& L) {
-  char* p = static_cast<char*>(base);
-  auto at = [&](size_t off) { return reinterpret_cast<float*>(p + off); };
-  return ScratchPtrs{at(L.A_part), at(L.gpre), at(L.gplanes), at(L.gwsa_part), at(L.gz), at(L.gbq), at(L.gh_avg), at(L.gh_mx), at(L.pgh)};
+static ScratchPtrs scratch_ptrs(void* p, const ScratchLayout& L) {
+  return ScratchPtrs{at(p, L.A_part), at(p, L.gpre), at(p, L.gplanes), at(p, L.gwsa_part), at(p, L.gz), at(p, L.gbq),
+                     at(p, L.gh_avg), at(p, L.gh_mx), at(p, L.pgh)};
 }
 // the size queries take no element type: the answer covers every one (the NCHW geometry does not depend on it)
 static size_t ws_bytes_any(int B, int C, int H, int W, bool nhwc) {
@@ -366,25 +362,54 @@ static int check_capacity(const char* what, const char* buf, size_t want, size_t
 static size_t elem_size(int dtype) { return dtype == MGACBAM_F32 ? 4 : 2; }
 static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-#define LAUNCH(kernel, grid, smem, stream, args) launch(kernel, static_cast<unsigned>(grid), smem, stream, args)
+static int check_dtype(const char* what, int dtype) {
+  if (dtype < MGACBAM_F32 || dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "%s: dtype %d", what, dtype);
+  return 0;
+}
 
-// T x VEC (vec_of: 1 or 4)
-#define DISPATCH_T_VEC(dtype, VECV, CALL)                                                                \
-  do {                                                                                                   \
-    if ((dtype) == MGACBAM_F32) { if ((VECV) == 4) { CALL(float, 4); } else { CALL(float, 1); } }         \
-    else if ((dtype) == MGACBAM_F16) { if ((VECV) == 4) { CALL(__half, 4); } else { CALL(__half, 1); } }  \
-    else { if ((VECV) == 4) { CALL(bf16_t, 4); } else { CALL(bf16_t, 1); } }                              \
-  } while (0)
-// T x VEC of k_gate (Sig::gvec) and of the NHWC kernels (nhwc_vec): fp16 / bf16 also 8
-#define DISPATCH_T_VEC8(dtype, VECV, CALL)                                                                                          \
-  do {                                                                                                                              \
-    if ((dtype) == MGACBAM_F32) { if ((VECV) == 4) { CALL(float, 4); } else { CALL(float, 1); } }                                    \
-    else if ((dtype) == MGACBAM_F16) { if ((VECV) == 8) { CALL(__half, 8); } else if ((VECV) == 4) { CALL(__half, 4); } else { CALL(__half, 1); } } \
-    else { if ((VECV) == 8) { CALL(bf16_t, 8); } else if ((VECV) == 4) { CALL(bf16_t, 4); } else { CALL(bf16_t, 1); } }          \
-  } while (0)
-
-#define DISPATCH_CPT(CPTV, CALL2)                                              \
-  do { if ((CPTV) == 4) { CALL2(4); } else if ((CPTV) == 2) { CALL2(2); } else { CALL2(1); } } while (0)
+// Kernel selection: a run-time value becomes a compile-time one by calling a generic lambda with a tag -- f(Ty<float>{}),
+// f(Int<4>{}), f(std::true_type{}) -- and returning what it returns: nested, the innermost lambda names ONE instantiation
+// (`return k_pool<T, v.value, c.value, m.value>;`) and the selection is a typed expression that yields the kernel.  Only the
+// combinations a selector can form are instantiated; the LAST listed value is where every other run-time value goes.
+template <typename T> struct Ty { using type = T; };
+template <int V> using Int = std::integral_constant<int, V>;
+// any dtype other than F32 / F16 is bf16_t
+template <typename F>
+static auto with_elem(int dtype, F f) {
+  if (dtype == MGACBAM_F32) return f(Ty<float>{});
+  if (dtype == MGACBAM_F16) return f(Ty<__half>{});
+  return f(Ty<bf16_t>{});
+}
+template <int V0, int... Vs, typename F>
+static auto with_int(int v, F f) {
+  if constexpr (sizeof...(Vs) == 0) {
+    return f(Int<V0>{});
+  } else {
+    if (v == V0) return f(Int<V0>{});
+    return with_int<Vs...>(v, f);
+  }
+}
+template <typename F>
+static auto with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// T x VEC (vec_of: 1 or 4): f(Ty<T>, Int<VEC>)
+template <typename F>
+static auto with_elem_vec(int dtype, int vec, F f) {
+  return with_elem(dtype, [&](auto t) { return with_int<4, 1>(vec, [&](auto v) { return f(t, v); }); });
+}
+// T x VEC of k_gate (Sig::gvec) and of the NHWC kernels (nhwc_vec): fp16 / bf16 also 8 (float x 8 is never formed)
+template <typename F>
+static auto with_elem_vec8(int dtype, int vec, F f) {
+  return with_elem(dtype, [&](auto t) {
+    if constexpr (sizeof(typename decltype(t)::type) == 2) return with_int<8, 4, 1>(vec, [&](auto v) { return f(t, v); });
+    else return with_int<4, 1>(vec, [&](auto v) { return f(t, v); });
+  });
+}
+// channels per thread of the sweep kernels (group_cpt), the conv size of the kernels specialised for 3 / 5 / 7 (0: any k, loops
+// not unrolled) and of those that know only 7
+template <typename F> static auto with_cpt(int cpt, F f) { return with_int<4, 2, 1>(cpt, f); }
+template <typename F> static auto with_k(int k, F f) { return with_int<3, 5, 7, 0>(k, f); }
+template <typename F> static auto with_k7(int k, F f) { return with_int<7, 0>(k, f); }
+template <typename Tag> using elem_t = typename Tag::type;
 
 static Geo make_geo(int B, int C, int H, int W, const mgacbam_params_t& p) {
   Geo g;
@@ -405,8 +430,7 @@ template <typename Level>
 static int check_level(const char* what, const Level& L) {
   if (int e = check_params(L.p)) return e;
   if (int e = check_shape(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k)) return e;
-  if (L.dtype < MGACBAM_F32 || L.dtype > MGACBAM_BF16) return fail(MGACBAM_E_DTYPE, "%s: dtype %d", what, L.dtype);
-  return 0;
+  return check_dtype(what, L.dtype);
 }
 template <typename Level>
 static int check_ctx_capacity(const char* what, const Level& L) {
@@ -519,6 +543,31 @@ static int fill_starts(Group<Args>& G, const Args* lv, int n, Fn blocks_of) {
   G.start[n] = tot;
   return tot;
 }
+template <typename Args>
+static Group<Args> make_group(const Args* lv, int n) {
+  Group<Args> G;
+  G.n = n;
+  for (int l = 0; l < n; ++l) G.lv[l] = lv[l];
+  return G;
+}
+// dynamic LDS of a launch: the largest any level of the group asks for (smem_of: a function of the level, or a plain size)
+template <typename Args, typename SmemOf>
+static size_t group_smem(const Group<Args>& G, SmemOf smem_of) {
+  if constexpr (std::is_convertible_v<SmemOf, size_t>) {
+    return smem_of;
+  } else {
+    size_t smem = 0;
+    for (int l = 0; l < G.n; ++l) smem = std::max(smem, static_cast<size_t>(smem_of(G.lv[l])));
+    return smem;
+  }
+}
+// One grouped launch: the levels' grids concatenated (G.start), the group's LDS size, kBlock threads.  The launches whose grid is not
+// a concatenation per level (k_gate, k_bwd_r12, the mask head's per-pass sub-groups) compute it themselves and call launch().
+template <typename Args, typename BlocksOf, typename SmemOf>
+static int launch_group(const char* what, void (*kernel)(Group<Args>), Group<Args>& G, BlocksOf blocks_of, SmemOf smem_of, hipStream_t st) {
+  const int grid = fill_starts(G, G.lv, G.n, blocks_of);
+  return launch(what, kernel, grid, kBlock, group_smem(G, smem_of), st, G);
+}
 
 // partition the levels into launch groups (same signature, at most kGroupMax levels) and run `run` on each
 template <typename Args, typename Run>
@@ -534,5 +583,35 @@ static int for_each_group(Args* args, const Sig* sigs, int n, Run run) {
     for (int j = 0; j < m; ++j) grp[j] = args[idx[j]];
     if (int e = run(grp, m, sigs[l])) return e;
   }
+  return 0;
+}
+
+// The frame of every grouped entry point: `level` checks one level and builds its arguments and signature
+// (int level(const Level&, NArgs&, Sig&)); EVERY level is checked before anything is launched; then the NCHW levels' groups run
+// (`run`), then the channels-last ones' (`nrun`), each in for_each_group's order.  With two runners the NCHW kernels take the `.a` member
+// of the channels-last argument block (Args); a family with one runner (nrun = nullptr) sends every level to it as it is.
+template <typename Args, typename NArgs = Args, typename Level, typename LevelFn, typename Run, typename NRun = std::nullptr_t>
+static int run_levels(const Level* levels, int n_levels, LevelFn level, Run run, NRun nrun = nullptr) {
+  constexpr bool two = !std::is_same_v<NRun, std::nullptr_t>;
+  if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
+  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
+  Args args[MGACBAM_MAX_LEVELS];
+  NArgs nargs[two ? MGACBAM_MAX_LEVELS : 1];
+  Sig sigs[MGACBAM_MAX_LEVELS], nsigs[MGACBAM_MAX_LEVELS];
+  int nc = 0, nn = 0;                                             // NCHW levels, NHWC levels
+  for (int l = 0; l < n_levels; ++l) {
+    if constexpr (two) {
+      NArgs N;
+      Sig s;
+      if (int e = level(levels[l], N, s)) return e;
+      if (s.nhwc) { nargs[nn] = N; nsigs[nn++] = s; } else { args[nc] = N.a; sigs[nc++] = s; }
+    } else {
+      if (int e = level(levels[l], args[nc], sigs[nc])) return e;
+      ++nc;
+    }
+  }
+  if (nc) if (int e = for_each_group(args, sigs, nc, run)) return e;
+  if constexpr (two) if (nn) if (int e = for_each_group(nargs, nsigs, nn, nrun)) return e;
+  g_err[0] = 0;
   return 0;
 }
