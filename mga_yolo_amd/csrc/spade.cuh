@@ -466,7 +466,7 @@ __global__ __launch_bounds__(kBlock) void k_spade_dh(const Group<SpadeArgs> G) {
   const T* x = static_cast<const T*>(A.x);
   const T* gy = static_cast<const T*>(A.gy);
   const bool active = wave * 16 < hid;
-  sp_v4f32 acc[kSpNT];
+  sp_v4f32 acc[kSpNT], part[kSpNT];                        // acc: the rounds finished so far; part: the current round (K <= 18 * kSpDhCC)
 #pragma unroll
   for (int nt = 0; nt < kSpNT; ++nt) acc[nt] = sp_v4f32{0.f, 0.f, 0.f, 0.f};
   int poff[kSpNT];                                         // the lane's pixel of every N tile at halo offset (2,2): minus the tap's (dy,dx)
@@ -492,6 +492,8 @@ __global__ __launch_bounds__(kBlock) void k_spade_dh(const Group<SpadeArgs> G) {
     }
     __syncthreads();
     if (active) {
+#pragma unroll
+      for (int nt = 0; nt < kSpNT; ++nt) part[nt] = sp_v4f32{0.f, 0.f, 0.f, 0.f};
       for (int tap = 0; tap < 9; ++tap) {
         const int toff = ((tap / 3) * PW + tap % 3) * GS;
         const float* wa = A.wpackT + (static_cast<size_t>(tap) * hid + wave * 16 + ln) * A.C + cc0 + 4 * g;
@@ -504,11 +506,15 @@ __global__ __launch_bounds__(kBlock) void k_spade_dh(const Group<SpadeArgs> G) {
             float va[4], vb[4];
             ld4(gs + poff[nt] - toff + kk, va);
             ld4(gs + poff[nt] - toff + CC + 4 + kk, vb);
-            acc[nt] = SpMma<T>::mma(fa, va, acc[nt]);
-            acc[nt] = SpMma<T>::mma(fb, vb, acc[nt]);
+            part[nt] = SpMma<T>::mma(fa, va, part[nt]);
+            part[nt] = SpMma<T>::mma(fb, vb, part[nt]);
           }
         }
       }
+      // K = 18 C runs to 18432 terms of mixed sign.  One running fp32 sum over all of them missed the element-wise bar on dL/dmask at
+      // C = 1024 by 1.14x; rounds summed from zero and then added stay 5x inside it.  (C <= kSpDhCC: the one round is added to zero.)
+#pragma unroll
+      for (int nt = 0; nt < kSpNT; ++nt) acc[nt] += part[nt];
     }
   }
   __syncthreads();

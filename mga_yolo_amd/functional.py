@@ -723,6 +723,14 @@ class _SpadeFn(torch.autograd.Function):
         return tuple(grads)
 
 
+def _spade_apply(cfgs, flat):
+    """The levels the kernels take, through autograd.  With gradients off (torch.no_grad) the inputs go in detached: autograd reports a
+    parameter that requires grad as needing one whatever the grad mode, and the forward would keep gamma for a backward that cannot come."""
+    if not torch.is_grad_enabled():
+        flat = [t.detach() if isinstance(t, torch.Tensor) else t for t in flat]
+    return _SpadeFn.apply(tuple(cfgs), *flat)
+
+
 def _spade_prepare(x, mask, params, cfg: SpadeConfig, running):
     """Checks shared by the single and the pyramid call; returns the flat slots of a kernel level, or None when the torch composition takes it."""
     if x.dim() != 4:
@@ -763,7 +771,7 @@ def mask_spade(x: torch.Tensor, mask: Optional[torch.Tensor], params: Sequence[t
     flat = _spade_prepare(x, mask, params, cfg, running)
     if flat is None:
         return spade_compose(x, mask, params, cfg, running)
-    return _SpadeFn.apply((cfg,), *flat)[0]
+    return _spade_apply((cfg,), flat)[0]
 
 
 def mask_spade_pyramid(levels):
@@ -780,6 +788,6 @@ def mask_spade_pyramid(levels):
         else:
             cfgs.append(cfg); flat += f; idx.append(i)
     if cfgs:
-        for i, y in zip(idx, _SpadeFn.apply(tuple(cfgs), *flat)):
+        for i, y in zip(idx, _spade_apply(cfgs, flat)):
             outs[i] = y
     return tuple(outs)

@@ -105,10 +105,10 @@ def live_case(B, C, H, W, norm, seed=77, hidden=64):
     return m, x, mask, gy
 
 
-def oracle_of(m, x, mask, gy, norm):
+def oracle_of(m, x, mask, gy, norm, eps=1e-6, momentum=0.1):
     params = {k: v.detach().cpu() for k, v in m.state_dict().items() if k in KEYS}
     runs = (m.norm.running_mean.detach().cpu().clone(), m.norm.running_var.detach().cpu().clone()) if norm == "bn" else None
-    y, ctx = SO.forward(x, mask, params, norm, True, True, 1e-6, runs)
+    y, ctx = SO.forward(x, mask, params, norm, True, True, eps, runs, momentum)
     g = SO.backward(gy, ctx)
     g["y"] = y
     return g, ctx
