@@ -15,15 +15,20 @@ extern "C" {
  * h = relu(conv3x3(s)), gamma = conv3x3(h; wg) + bg, beta = conv3x3(h; wb) + bb; norm = instance norm, or batch norm (batch statistics
  * and a running-statistics update when `training`, the running statistics otherwise).  The two hidden -> C convolutions run on the matrix
  * cores (fp32 features: v_mfma_f32_16x16x4_f32; fp16 / bf16: the native 16x16x16 forms, fp32 accumulation) fused with the FiLM apply.
- * One struct serves both directions; a direction ignores the other's pointers.  NCHW-contiguous x / y / gy / gx of `dtype`; the mask is
+ * One struct serves both directions; a direction ignores the other's pointers.  x / y / gy / gx of `dtype` are NCHW-contiguous, or with
+ * MGASPADE_LAYOUT_NHWC in `flags` dense (B,H,W,C) (torch's channels_last); the mask, gmask, the parameters, their gradients and the
+ * running statistics are the same memory in both layouts, and so are the sizes of ctx and scratch.  A channels-last level returns, bit
+ * for bit, what the same data returns as an NCHW level.  The gamma kept in ctx has the level's layout: a backward must carry the flag
+ * its forward carried.  Levels of both layouts may share a call.  The mask is
  * (B,1,H,W) fp32 at the feature's size or NULL (then y = norm(x) and no parameter is read); parameters and their gradients fp32.
  * hidden % 16 == 0, hidden <= 64, C % 16 == 0, C <= 1024 (MGACBAM_E_SHAPE otherwise).  x, y, gy, gx, ctx and scratch must be 16-byte
  * aligned (MGACBAM_E_ALIGN).  save_gamma: the forward keeps gamma (feature dtype) in ctx for the backward, which then needs the ctx of
  * such a forward.  Every argument is checked before the first launch; nothing is allocated or synchronised.
  * ------------------------------------------------------------------------------------------------ */
 enum { MGASPADE_NORM_IN = 0, MGASPADE_NORM_BN = 1 };
+enum { MGASPADE_LAYOUT_NHWC = 2 };   /* mgaspade_level_t.flags; the value of MGACBAM_LAYOUT_NHWC.  Every other bit: MGACBAM_E_SHAPE */
 typedef struct mgaspade_level {
-  const void* x;             /* (B,C,H,W) dtype                                                    */
+  const void* x;             /* (B,C,H,W) dtype; x, y, gy, gx: (B,H,W,C) with MGASPADE_LAYOUT_NHWC  */
   const float* mask;         /* (B,1,H,W) fp32 or NULL                                             */
   void* y;                   /* forward: (B,C,H,W) dtype                                           */
   const void* gy;            /* backward: dL/dy (B,C,H,W) dtype                                    */
@@ -55,7 +60,7 @@ typedef struct mgaspade_level {
   int32_t use_sigmoid_mask;
   int32_t save_gamma;        /* forward: keep gamma in ctx (a backward will follow)                */
   float eps, momentum;
-  int32_t flags;             /* reserved: 0                                                        */
+  int32_t flags;             /* 0 or MGASPADE_LAYOUT_NHWC                                          */
 } mgaspade_level_t;
 size_t mgaspade_ctx_bytes(int B, int C, int H, int W, int hidden);       /* covers every dtype, with save_gamma; 0 on a bad shape */
 size_t mgaspade_scratch_bytes(int B, int C, int H, int W, int hidden);

@@ -145,9 +145,10 @@ _SPADE_P = ("w0", "b0", "wg", "bg", "wb", "bb")
 
 
 def fill_spade(L: _lib.SpadeLevel, x, mask, params, cfg, running, ctx, y=None, save_gamma: bool = False,
-               gy=None, gx=None, gmask=None, pgrads=None, scratch=None) -> None:
+               gy=None, gx=None, gmask=None, pgrads=None, scratch=None, flags: int = 0) -> None:
     """params / pgrads: six tensors, or six None for a level without a mask; running: (running_mean, running_var, num_batches_tracked),
-    read for norm_type 'bn' only.  Forward passes y and save_gamma, backward gy, gx, gmask, pgrads and scratch."""
+    read for norm_type 'bn' only.  Forward passes y and save_gamma, backward gy, gx, gmask, pgrads and scratch.  flags: 0, or
+    _lib.SPADE_LAYOUT_NHWC when x / y / gy / gx are channels_last (x.shape stays (B,C,H,W)); a backward carries its forward's flag."""
     B, Cc, H, W = x.shape
     L.x, L.mask, L.y, L.gy, L.gx, L.gmask = x.data_ptr(), _ptr(mask), _ptr(y), _ptr(gy), _ptr(gx), _ptr(gmask)
     for name, p, g in zip(_SPADE_P, params, pgrads or (None,) * 6):
@@ -159,4 +160,4 @@ def fill_spade(L: _lib.SpadeLevel, x, mask, params, cfg, running, ctx, y=None, s
     L.scratch, L.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel())
     L.B, L.C, L.H, L.W, L.hidden, L.dtype = B, Cc, H, W, cfg.hidden, DTYPES[x.dtype]
     L.norm_type, L.training = (_lib.NORM_BN if cfg.bn else _lib.NORM_IN), int(cfg.training)
-    L.use_sigmoid_mask, L.save_gamma, L.eps, L.momentum, L.flags = int(cfg.use_sigmoid_mask), int(save_gamma), cfg.eps, cfg.momentum, 0
+    L.use_sigmoid_mask, L.save_gamma, L.eps, L.momentum, L.flags = int(cfg.use_sigmoid_mask), int(save_gamma), cfg.eps, cfg.momentum, int(flags)

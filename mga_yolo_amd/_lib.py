@@ -117,6 +117,9 @@ class PmgCfg(C.Structure):                       # mgapmg_cfg_t
 NORM_IN, NORM_BN = 0, 1
 
 
+SPADE_LAYOUT_NHWC = 2  # MaskSPADE level flag (MGASPADE_LAYOUT_NHWC, forward and backward): x, y, gy, gx are (B,H,W,C); sizes are unchanged
+
+
 class SpadeLevel(C.Structure):                   # mgaspade_level_t (include/mgaspade.h)
     _fields_ = ([(n, C.c_void_p) for n in ("x", "mask", "y", "gy", "gx", "gmask", "w0", "b0", "wg", "bg", "wb", "bb", "running_mean",
                                            "running_var", "num_batches_tracked", "gw0", "gb0", "gwg", "gbg", "gwb", "gbb")] +

@@ -1,7 +1,7 @@
 // libmgacbam.so, C ABI (include/mgaspade.h): MaskSPADE
 #include "host.cuh"
 #include "../../include/mgaspade.h"
-#include "spade.cuh"
+#include "spade_nhwc.cuh"
 
 constexpr int kSpMaxC = 1024;
 constexpr int kSpDwTarget = 512;     // workgroups k_spade_dw aims for: (C / 16) M tiles x pixel chunks
@@ -91,7 +91,8 @@ static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, Spade
   if (!L.x || !L.ctx) return fail(MGACBAM_E_NULL, "%s: x / ctx is NULL", what);
   if (!bwd && !L.y) return fail(MGACBAM_E_NULL, "%s: y is NULL", what);
   if (bwd && (!L.gy || !L.gx || !L.scratch)) return fail(MGACBAM_E_NULL, "%s: gy / gx / scratch is NULL", what);
-  if (L.flags) return fail(MGACBAM_E_SHAPE, "%s: flags=0x%x (reserved: 0)", what, L.flags);
+  if (L.flags != 0 && L.flags != MGASPADE_LAYOUT_NHWC)
+    return fail(MGACBAM_E_SHAPE, "%s: flags=0x%x (0 or MGASPADE_LAYOUT_NHWC; every other bit is reserved)", what, L.flags);
   if (int e = sp_check_shape(what, L.B, L.C, L.H, L.W, L.hidden)) return e;
   if (int e = check_dtype(what, L.dtype)) return e;
   if (L.norm_type != MGASPADE_NORM_IN && L.norm_type != MGASPADE_NORM_BN) return fail(MGACBAM_E_SHAPE, "%s: norm_type %d", what, L.norm_type);
@@ -134,6 +135,7 @@ static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, Spade
   A.nchunk = SL.nchunk; A.tpc = SL.tpc;
   sig = Sig{L.dtype, 0, L.mask != nullptr, 0, bwd ? (L.gmask != nullptr) : (gamma_kept ? 1 : 0), 0};
   sig.weight = L.C;
+  sig.nhwc = L.flags == MGASPADE_LAYOUT_NHWC;
   return 0;
 }
 static int sp_ew_blocks(const SpadeArgs& a) {
@@ -144,33 +146,67 @@ static int sp_plane_blocks(const SpadeArgs& a) { return (a.B * a.C + 3) / 4; }
 
 static int sp_pack_blocks(const SpadeArgs& a) { return (2 * a.C * a.hid * 9 + kBlock - 1) / kBlock; }
 
+// Channels-last levels (Sig::nhwc: launch groups of their own) run the same launches with the kernels' NHWC instantiations; tiling, grids
+// of the tile kernels, ctx and scratch are the NCHW ones.  Their reductions (spade_nhwc.cuh) take 16 channels of a sample per workgroup.
+static int sp_nhwc_plane_blocks(const SpadeArgs& a) { return a.B * (a.C / kSpNhCB); }
+static int sp_nhwc_bn_blocks(const SpadeArgs& a) { return a.bn && a.train ? (a.C / kSpNhCB) * (kBlock / kWave) : 0; }
+static int sp_nhwc_bn_fin_blocks(const SpadeArgs& a) { return a.bn && a.train ? (a.C + kBlock - 1) / kBlock : 0; }
+static int sp_stats_nhwc(Group<SpadeArgs>& G, const Sig& sig, hipStream_t st) {
+  auto stats = with_elem(sig.dtype, [](auto t) { return k_spade_stats_nhwc<elem_t<decltype(t)>>; });
+  auto stat_blocks = [](const SpadeArgs& a) { return !a.bn ? sp_nhwc_plane_blocks(a) : a.train ? sp_nhwc_bn_blocks(a) : (a.B * a.C + kBlock - 1) / kBlock; };
+  if (int e = launch_group("k_spade_stats_nhwc", stats, G, stat_blocks, 0, st)) return e;
+  bool bn_train = false;
+  for (int l = 0; l < G.n; ++l) bn_train = bn_train || (G.lv[l].bn && G.lv[l].train);
+  if (!bn_train) return 0;
+  // batch norm in training (the other levels get no workgroup): the mean from the four parked sums, the centred squares, then rstd and
+  // the running statistics.  The sums are parked in ctx where k_spade_pack, which runs after this, writes the weight packs.
+  if (int e = launch_group("k_spade_bn_fin_nhwc", k_spade_bn_fin_nhwc<false>, G, sp_nhwc_bn_fin_blocks, 0, st)) return e;
+  auto sq = with_elem(sig.dtype, [](auto t) { return k_spade_bn_sq_nhwc<elem_t<decltype(t)>>; });
+  if (int e = launch_group("k_spade_bn_sq_nhwc", sq, G, sp_nhwc_bn_blocks, 0, st)) return e;
+  return launch_group("k_spade_bn_fin_nhwc", k_spade_bn_fin_nhwc<true>, G, sp_nhwc_bn_fin_blocks, 0, st);
+}
+// T x layout: f(Ty<T>, std::bool_constant<NHWC>)
+template <typename F>
+static auto with_elem_layout(const Sig& sig, F f) {
+  return with_elem(sig.dtype, [&](auto t) { return with_bool(sig.nhwc, [&](auto n) { return f(t, n); }); });
+}
+
 static int sp_forward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
   Group<SpadeArgs> G = make_group(lv, n);
-  auto stats = with_elem(sig.dtype, [](auto t) { return k_spade_stats<elem_t<decltype(t)>>; });
-  auto stat_blocks = [](const SpadeArgs& a) { return !a.bn ? sp_plane_blocks(a) : a.train ? a.C : (a.B * a.C + kBlock - 1) / kBlock; };
-  if (int e = launch_group("k_spade_stats", stats, G, stat_blocks, 0, st)) return e;
+  if (sig.nhwc) {
+    if (int e = sp_stats_nhwc(G, sig, st)) return e;
+  } else {
+    auto stats = with_elem(sig.dtype, [](auto t) { return k_spade_stats<elem_t<decltype(t)>>; });
+    auto stat_blocks = [](const SpadeArgs& a) { return !a.bn ? sp_plane_blocks(a) : a.train ? a.C : (a.B * a.C + kBlock - 1) / kBlock; };
+    if (int e = launch_group("k_spade_stats", stats, G, stat_blocks, 0, st)) return e;
+  }
   if (!sig.has_mask) {
-    auto ew = with_elem(sig.dtype, [](auto t) { return k_spade_ew<elem_t<decltype(t)>, 0>; });
+    auto ew = with_elem_layout(sig, [](auto t, auto l) { return k_spade_ew<elem_t<decltype(t)>, 0, decltype(l)::value>; });
     return launch_group("k_spade_ew", ew, G, sp_ew_blocks, 0, st);
   }
   if (int e = launch_group("k_spade_pack", k_spade_pack, G, sp_pack_blocks, 0, st)) return e;
-  auto fwd = with_elem(sig.dtype, [&](auto t) {
-    return with_bool(sig.gmask, [](auto keep) { return k_spade_fwd<elem_t<decltype(t)>, keep.value>; }); });
+  auto fwd = with_elem_layout(sig, [&](auto t, auto l) {
+    return with_bool(sig.gmask, [](auto keep) { return k_spade_fwd<elem_t<decltype(t)>, keep.value, decltype(l)::value>; }); });
   sp_allow_lds(fwd, group_smem(G, sp_fwd_smem));
   return launch_group("k_spade_fwd", fwd, G, [](const SpadeArgs& a) { return a.B * a.tiles * a.ncb; }, sp_fwd_smem, st);
 }
 
 static int sp_backward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
   Group<SpadeArgs> G = make_group(lv, n);
-  auto reduce = with_elem(sig.dtype, [](auto t) { return k_spade_bwd_reduce<elem_t<decltype(t)>>; });
-  if (int e = launch_group("k_spade_bwd_reduce", reduce, G, sp_plane_blocks, 0, st)) return e;
+  if (sig.nhwc) {
+    auto reduce = with_elem(sig.dtype, [](auto t) { return k_spade_bwd_reduce_nhwc<elem_t<decltype(t)>>; });
+    if (int e = launch_group("k_spade_bwd_reduce_nhwc", reduce, G, sp_nhwc_plane_blocks, 0, st)) return e;
+  } else {
+    auto reduce = with_elem(sig.dtype, [](auto t) { return k_spade_bwd_reduce<elem_t<decltype(t)>>; });
+    if (int e = launch_group("k_spade_bwd_reduce", reduce, G, sp_plane_blocks, 0, st)) return e;
+  }
   if (int e = launch_group("k_spade_bwd_fin", k_spade_bwd_fin, G, [](const SpadeArgs& a) { return (a.C + kBlock - 1) / kBlock; }, 0, st)) return e;
   if (sig.has_mask) {
-    auto dw = with_elem(sig.dtype, [](auto t) { return k_spade_dw<elem_t<decltype(t)>>; });
+    auto dw = with_elem_layout(sig, [](auto t, auto l) { return k_spade_dw<elem_t<decltype(t)>, decltype(l)::value>; });
     sp_allow_lds(dw, group_smem(G, sp_dw_smem));
     if (int e = launch_group("k_spade_dw", dw, G, [](const SpadeArgs& a) { return (a.C / 16) * a.nchunk; }, sp_dw_smem, st)) return e;
     if (int e = launch_group("k_spade_dw_fin", k_spade_dw_fin, G, sp_pack_blocks, 0, st)) return e;
-    auto dh = with_elem(sig.dtype, [](auto t) { return k_spade_dh<elem_t<decltype(t)>>; });
+    auto dh = with_elem_layout(sig, [](auto t, auto l) { return k_spade_dh<elem_t<decltype(t)>, decltype(l)::value>; });
     sp_allow_lds(dh, group_smem(G, sp_dh_smem));
     if (int e = launch_group("k_spade_dh", dh, G, [](const SpadeArgs& a) { return a.B * a.tiles; }, sp_dh_smem, st)) return e;
     if (int e = launch_group("k_spade_w0_fin", k_spade_w0_fin, G, [](const SpadeArgs& a) { return a.hid * 10; }, 0, st)) return e;
@@ -178,7 +214,7 @@ static int sp_backward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t s
       if (int e = launch_group("k_spade_gmask", k_spade_gmask, G,
                                [](const SpadeArgs& a) { return (a.B * a.HW + kBlock - 1) / kBlock; }, 0, st)) return e;
   }
-  auto ew = with_elem(sig.dtype, [](auto t) { return k_spade_ew<elem_t<decltype(t)>, 1>; });
+  auto ew = with_elem_layout(sig, [](auto t, auto l) { return k_spade_ew<elem_t<decltype(t)>, 1, decltype(l)::value>; });
   return launch_group("k_spade_ew", ew, G, sp_ew_blocks, 0, st);
 }
 

@@ -75,6 +75,39 @@ __device__ __forceinline__ void ld4(const float* p, float (&o)[4]) {
   o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
 }
 
+template <int N> __device__ __forceinline__ void ldn(const float* p, float (&o)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; k += 4) { const float4 v = *reinterpret_cast<const float4*>(p + k); o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; o[k + 3] = v.w; }
+}
+
+// The per-element arithmetic that reads or writes a feature element, one function per expression.  The NCHW kernels here and the
+// channels-last ones (NHWC = true, spade_nhwc.cuh) both call these, so an expression is contracted to FMAs the same way in either layout:
+// a channels-last level gives the NCHW level's bits.
+__device__ __forceinline__ float sp_xhat(float x, float mean, float rstd) { return (x - mean) * rstd; }
+__device__ __forceinline__ float sp_ggamma(float gy, float x, float mean, float rstd) { return gy * (x - mean) * rstd; }
+__device__ __forceinline__ float sp_film(float gm, float xh, float beta) { return fmaf(gm, xh, beta); }
+__device__ __forceinline__ float sp_gx_inner(float gv, float m1, float xh, float m2) { return gv - m1 - xh * m2; }
+// The element a * b of an output of type T (k_spade_ew: xhat = (x - mean) * rstd, gx = rstd * inner).  For fp16 the compiler folds the
+// product and the conversion of scalar code into ONE v_fma_mixlo_f16 -- the exact product rounded once -- but multiplies and then packs
+// two conversions (two roundings, rarely another fp16) in vector code.  The folded form is what the NCHW kernel has always computed;
+// it is spelled out here so that both layouts compute it whatever the code around it looks like.
+template <typename T> __device__ __forceinline__ T sp_product_to(float a, float b) {
+  if constexpr (__is_same(T, __half)) {
+    unsigned r;                                              // (the instruction writes the low half; the high half is not used)
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
+    return __builtin_bit_cast(__half, static_cast<unsigned short>(r));
+  } else {
+    return from_f32<T>(a * b);
+  }
+}
+__device__ __forceinline__ void sp_red_terms(float (&s)[4], float gyv, float xh, float gv) {   // gv = gyv * gamma | gyv
+  s[0] += gv; s[1] = fmaf(gv, xh, s[1]); s[2] = fmaf(gyv, xh, s[2]); s[3] += gyv;
+}
+__device__ __forceinline__ float sp_sum4(float s, const float (&v)[4]) { return s + ((v[0] + v[1]) + (v[2] + v[3])); }
+__device__ __forceinline__ float sp_sq(float q, float x, float mean) { const float d = x - mean; return fmaf(d, d, q); }
+__device__ __forceinline__ float sp_mean_of(float sum, int n) { return sum / n; }
+__device__ __forceinline__ float sp_rstd_of(float var, float eps) { return 1.0f / sqrtf(var + eps); }
+
 // LDS carve shared by the tile kernels: w0s [hid*9] | b0s [hid] | s tile (TH+4)(TW+4), each rounded to 4 floats
 __device__ __forceinline__ int sp_r4(int n) { return (n + 3) & ~3; }
 struct SpTile { int b, y0, x0; };
@@ -120,6 +153,15 @@ __device__ __forceinline__ void sp_form_h(const SpadeArgs& A, const SpTile& t, c
   }
 }
 
+// batch norm in training, the end of a channel: q = the channel's sum of centred squares over its n = B * HW values
+__device__ __forceinline__ void sp_bn_finish(const SpadeArgs& A, int c, float mean, float q, float n) {
+  const float var = q / n, rstd = sp_rstd_of(var, A.eps);
+  for (int b = 0; b < A.B; ++b) { A.mean[b * A.C + c] = mean; A.rstd[b * A.C + c] = rstd; }
+  A.rmean[c] = (1.f - A.momentum) * A.rmean[c] + A.momentum * mean;
+  A.rvar[c] = (1.f - A.momentum) * A.rvar[c] + A.momentum * (q / (n - 1.f));
+  if (c == 0 && A.nbt) *A.nbt += 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // statistics: mode 0 = per (b,c) plane (one wave each), 1 = batch norm in training (one workgroup per channel, running update),
 // 2 = batch norm in eval (from the running statistics).  Two passes (mean, then the centred squares): no cancellation.
@@ -138,23 +180,23 @@ __global__ __launch_bounds__(kBlock) void k_spade_stats(const Group<SpadeArgs> G
     const T* p = x + static_cast<size_t>(plane) * HW;
     float s = 0.f;
     if ((HW & 3) == 0) {
-      for (int i = lane * 4; i < HW; i += 256) { float v[4]; load_vec<T, 4>(p + i, v); s += (v[0] + v[1]) + (v[2] + v[3]); }
+      for (int i = lane * 4; i < HW; i += 256) { float v[4]; load_vec<T, 4>(p + i, v); s = sp_sum4(s, v); }
     } else {
       for (int i = lane; i < HW; i += 64) s += to_f32<T>(p[i]);
     }
-    const float mean = wave_group_sum(s, 64) / HW;
+    const float mean = sp_mean_of(wave_group_sum(s, 64), HW);
     float q = 0.f;
     if ((HW & 3) == 0) {
       for (int i = lane * 4; i < HW; i += 256) {
         float v[4]; load_vec<T, 4>(p + i, v);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q = fmaf(d, d, q); }
+        for (int e = 0; e < 4; ++e) q = sp_sq(q, v[e], mean);
       }
     } else {
-      for (int i = lane; i < HW; i += 64) { const float d = to_f32<T>(p[i]) - mean; q = fmaf(d, d, q); }
+      for (int i = lane; i < HW; i += 64) q = sp_sq(q, to_f32<T>(p[i]), mean);
     }
-    const float var = wave_group_sum(q, 64) / HW;
-    if (lane == 0) { A.mean[plane] = mean; A.rstd[plane] = 1.0f / sqrtf(var + A.eps); }
+    const float var = sp_mean_of(wave_group_sum(q, 64), HW);
+    if (lane == 0) { A.mean[plane] = mean; A.rstd[plane] = sp_rstd_of(var, A.eps); }
   } else if (A.train) {
     const int c = local;
     const float n = static_cast<float>(A.B) * HW;
@@ -171,22 +213,16 @@ __global__ __launch_bounds__(kBlock) void k_spade_stats(const Group<SpadeArgs> G
     float q = 0.f;
     for (int b = 0; b < A.B; ++b) {
       const T* p = x + (static_cast<size_t>(b) * A.C + c) * HW;
-      for (int i = tid; i < HW; i += kBlock) { const float d = to_f32<T>(p[i]) - mean; q = fmaf(d, d, q); }
+      for (int i = tid; i < HW; i += kBlock) q = sp_sq(q, to_f32<T>(p[i]), mean);
     }
     q = block_sum(q, tid, red);
-    if (tid == 0) {
-      const float var = q / n, rstd = 1.0f / sqrtf(var + A.eps);
-      for (int b = 0; b < A.B; ++b) { A.mean[b * A.C + c] = mean; A.rstd[b * A.C + c] = rstd; }
-      A.rmean[c] = (1.f - A.momentum) * A.rmean[c] + A.momentum * mean;
-      A.rvar[c] = (1.f - A.momentum) * A.rvar[c] + A.momentum * (q / (n - 1.f));
-      if (c == 0 && A.nbt) *A.nbt += 1;
-    }
+    if (tid == 0) sp_bn_finish(A, c, mean, q, n);
   } else {
     const int i = local * kBlock + tid;
     if (i >= A.B * A.C) return;
     const int c = i % A.C;
     A.mean[i] = A.rmean[c];
-    A.rstd[i] = 1.0f / sqrtf(A.rvar[c] + A.eps);
+    A.rstd[i] = sp_rstd_of(A.rvar[c], A.eps);
   }
 }
 
@@ -208,7 +244,9 @@ __global__ __launch_bounds__(kBlock) void k_spade_pack(const Group<SpadeArgs> G)
 // forward: workgroup = (tile, channel block); wave w runs the 16-channel M tiles w, w + 4, ... of the block, gamma and beta of the same
 // channels side by side (8 N tiles x 2 x 4 accumulator registers).  LDS: w0s | s | h [halo pixel][hid + 4].
 // ---------------------------------------------------------------------------------------------------------------------------
-template <typename T, bool SAVE>
+// NHWC (here and in k_spade_ew / dw / dh): x / y / gy / gx and the saved gamma are (B,H,W,C).  Only the global accesses differ: the LDS
+// images, the MFMA order and every sum after them are the NCHW ones.  The reductions of a channels-last level are in spade_nhwc.cuh.
+template <typename T, bool SAVE, bool NHWC>
 __global__ __launch_bounds__(kBlock) void k_spade_fwd(const Group<SpadeArgs> G) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int local;
@@ -254,21 +292,48 @@ __global__ __launch_bounds__(kBlock) void k_spade_fwd(const Group<SpadeArgs> G) 
         }
       }
     }
+    if constexpr (NHWC) {
+      // the lane's four accumulator registers are four consecutive channels of one pixel: one vector access per tensor
+      const int cq = c0 + 4 * g;
+      const size_t plane = static_cast<size_t>(t.b) * A.C + cq;
+      float mean[4], rstd[4], bgv[4], bbv[4];
+      ld4(A.mean + plane, mean);
+      ld4(A.rstd + plane, rstd);
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int c = c0 + 4 * g + v;
-      const size_t plane = static_cast<size_t>(t.b) * A.C + c;
-      const float mean = A.mean[plane], rstd = A.rstd[plane], bgv = A.bg[c], bbv = A.bb[c];
+      for (int v = 0; v < 4; ++v) { bgv[v] = A.bg[cq + v]; bbv[v] = A.bb[cq + v]; }   // (parameters: no alignment is asked of them)
 #pragma unroll
       for (int nt = 0; nt < kSpNT; ++nt) {
         const int p = nt * 16 + ln;
         const int yy = t.y0 + (p >> A.ltw), xx = t.x0 + (p & (A.TW - 1));
         if (yy < A.H && xx < A.W) {
-          const size_t at = plane * A.HW + static_cast<size_t>(yy) * A.W + xx;
-          const float gm = ag[nt][v] + bgv;
-          const float xh = (to_f32<T>(x[at]) - mean) * rstd;
-          y[at] = from_f32<T>(fmaf(gm, xh, ab[nt][v] + bbv));
-          if constexpr (SAVE) gsave[at] = from_f32<T>(gm);
+          const size_t at = (static_cast<size_t>(t.b) * A.HW + static_cast<size_t>(yy) * A.W + xx) * A.C + cq;
+          float xv[4], yv[4], gm[4];
+          load_vec<T, 4>(x + at, xv);
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            gm[v] = ag[nt][v] + bgv[v];
+            yv[v] = sp_film(gm[v], sp_xhat(xv[v], mean[v], rstd[v]), ab[nt][v] + bbv[v]);
+          }
+          store_vec<T, 4>(y + at, yv);
+          if constexpr (SAVE) store_vec<T, 4>(gsave + at, gm);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int c = c0 + 4 * g + v;
+        const size_t plane = static_cast<size_t>(t.b) * A.C + c;
+        const float mean = A.mean[plane], rstd = A.rstd[plane], bgv = A.bg[c], bbv = A.bb[c];
+#pragma unroll
+        for (int nt = 0; nt < kSpNT; ++nt) {
+          const int p = nt * 16 + ln;
+          const int yy = t.y0 + (p >> A.ltw), xx = t.x0 + (p & (A.TW - 1));
+          if (yy < A.H && xx < A.W) {
+            const size_t at = plane * A.HW + static_cast<size_t>(yy) * A.W + xx;
+            const float gm = ag[nt][v] + bgv;
+            y[at] = from_f32<T>(sp_film(gm, sp_xhat(to_f32<T>(x[at]), mean, rstd), ab[nt][v] + bbv));
+            if constexpr (SAVE) gsave[at] = from_f32<T>(gm);
+          }
         }
       }
     }
@@ -276,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void k_spade_fwd(const Group<SpadeArgs> G) 
 }
 
 // element-wise passes.  MODE 0: y = xhat (forward without a mask).  MODE 1: gx = rstd * (g - m1 - xhat * m2), g = gy * gamma | gy.
-template <typename T, int MODE>
+template <typename T, int MODE, bool NHWC>
 __global__ __launch_bounds__(kBlock) void k_spade_ew(const Group<SpadeArgs> G) {
   int local;
   const int l = find_level(G, blockIdx.x, local);
@@ -287,15 +352,47 @@ __global__ __launch_bounds__(kBlock) void k_spade_ew(const Group<SpadeArgs> G) {
   const T* gam = static_cast<const T*>(A.gamma);
   T* out = static_cast<T*>(MODE == 0 ? A.y : A.gx);
   const size_t n = static_cast<size_t>(A.B) * A.C * A.HW;
-  for (size_t i = static_cast<size_t>(local) * kBlock + threadIdx.x; i < n; i += static_cast<size_t>(nblk) * kBlock) {
-    const size_t plane = i / A.HW;
-    const float xh = (to_f32<T>(x[i]) - A.mean[plane]) * A.rstd[plane];
-    if constexpr (MODE == 0) {
-      out[i] = from_f32<T>(xh);
-    } else {
-      float gv = to_f32<T>(gy[i]);
-      if (A.has_mask) gv *= to_f32<T>(gam[i]);
-      out[i] = from_f32<T>(A.rstd[plane] * (gv - A.stat[2 * plane] - xh * A.stat[2 * plane + 1]));
+  if constexpr (NHWC) {
+    constexpr int V = 16 / sizeof(T);                        // channels per lane: one 16-byte access per tensor
+    const size_t per = static_cast<size_t>(A.HW) * A.C;
+    for (size_t iv = static_cast<size_t>(local) * kBlock + threadIdx.x; iv * V < n; iv += static_cast<size_t>(nblk) * kBlock) {
+      const size_t i = iv * V;
+      const size_t plane = (i / per) * A.C + i % A.C;
+      float xv[V], mean[V], rstd[V];
+      Pack<T, V> ov;
+      load_vec<T, V>(x + i, xv);
+      ldn<V>(A.mean + plane, mean);
+      ldn<V>(A.rstd + plane, rstd);
+      if constexpr (MODE == 0) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) ov.v[e] = sp_product_to<T>(xv[e] - mean[e], rstd[e]);
+      } else {
+        float gv[V], st[2 * V];
+        load_vec<T, V>(gy + i, gv);
+        ldn<2 * V>(A.stat + 2 * plane, st);
+        if (A.has_mask) {
+          float gm[V];
+          load_vec<T, V>(gam + i, gm);
+#pragma unroll
+          for (int e = 0; e < V; ++e) gv[e] *= gm[e];
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e)
+          ov.v[e] = sp_product_to<T>(rstd[e], sp_gx_inner(gv[e], st[2 * e], sp_xhat(xv[e], mean[e], rstd[e]), st[2 * e + 1]));
+      }
+      *reinterpret_cast<Pack<T, V>*>(out + i) = ov;
+    }
+  } else {
+    for (size_t i = static_cast<size_t>(local) * kBlock + threadIdx.x; i < n; i += static_cast<size_t>(nblk) * kBlock) {
+      const size_t plane = i / A.HW;
+      if constexpr (MODE == 0) {
+        out[i] = sp_product_to<T>(to_f32<T>(x[i]) - A.mean[plane], A.rstd[plane]);
+      } else {
+        const float xh = sp_xhat(to_f32<T>(x[i]), A.mean[plane], A.rstd[plane]);
+        float gv = to_f32<T>(gy[i]);
+        if (A.has_mask) gv *= to_f32<T>(gam[i]);
+        out[i] = sp_product_to<T>(A.rstd[plane], sp_gx_inner(gv, A.stat[2 * plane], xh, A.stat[2 * plane + 1]));
+      }
     }
   }
 }
@@ -316,9 +413,9 @@ __global__ __launch_bounds__(kBlock) void k_spade_bwd_reduce(const Group<SpadeAr
   const float mean = A.mean[plane], rstd = A.rstd[plane];
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   for (int i = lane; i < A.HW; i += 64) {
-    const float gyv = to_f32<T>(gy[i]), xh = (to_f32<T>(x[i]) - mean) * rstd;
+    const float gyv = to_f32<T>(gy[i]), xh = sp_xhat(to_f32<T>(x[i]), mean, rstd);
     const float gv = A.has_mask ? gyv * to_f32<T>(gam[i]) : gyv;
-    s[0] += gv; s[1] = fmaf(gv, xh, s[1]); s[2] = fmaf(gyv, xh, s[2]); s[3] += gyv;
+    sp_red_terms(s, gyv, xh, gv);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) s[k] = wave_group_sum(s[k], 64);
@@ -354,7 +451,7 @@ __global__ __launch_bounds__(kBlock) void k_spade_bwd_fin(const Group<SpadeArgs>
 // LDS: w0s | s | h [halo pixel][hid] | ga [16][kSpAStride] | gb [16][kSpAStride]
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int kSpDwQ = 9;            // N tiles per wave at hid = 64
-template <typename T>
+template <typename T, bool NHWC>
 __global__ __launch_bounds__(kBlock) void k_spade_dw(const Group<SpadeArgs> G) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int local;
@@ -378,18 +475,41 @@ __global__ __launch_bounds__(kBlock) void k_spade_dw(const Group<SpadeArgs> G) {
     const SpTile t = sp_tile(A, ti);
     __syncthreads();                                       // the previous tile's operands are no longer read
     sp_stage_s(A, t, ss);
-    for (int e = tid; e < 16 * kSpPx; e += kBlock) {
-      const int c = e >> 7, p = e & (kSpPx - 1);
-      const int yy = t.y0 + (p >> A.ltw), xx = t.x0 + (p & (A.TW - 1));
-      float va = 0.f, vb = 0.f;
-      if (yy < A.H && xx < A.W) {
-        const size_t plane = static_cast<size_t>(t.b) * A.C + c0 + c;
-        const size_t at = plane * A.HW + static_cast<size_t>(yy) * A.W + xx;
-        vb = to_f32<T>(gy[at]);
-        va = vb * (to_f32<T>(x[at]) - A.mean[plane]) * A.rstd[plane];
+    if constexpr (NHWC) {
+      constexpr int V = 16 / sizeof(T), CV = 16 / V;         // the 16 channels of a pixel are contiguous: CV 16-byte accesses
+      for (int e = tid; e < kSpPx * CV; e += kBlock) {
+        const int p = e / CV, cq = (e - p * CV) * V;
+        const int yy = t.y0 + (p >> A.ltw), xx = t.x0 + (p & (A.TW - 1));
+        float xv[V] = {}, gv[V] = {}, mean[V] = {}, rstd[V] = {};
+        const bool in = yy < A.H && xx < A.W;
+        if (in) {
+          const size_t plane = static_cast<size_t>(t.b) * A.C + c0 + cq;
+          const size_t at = (static_cast<size_t>(t.b) * A.HW + static_cast<size_t>(yy) * A.W + xx) * A.C + c0 + cq;
+          load_vec<T, V>(gy + at, gv);
+          load_vec<T, V>(x + at, xv);
+          ldn<V>(A.mean + plane, mean);
+          ldn<V>(A.rstd + plane, rstd);
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+          ga[(cq + i) * kSpAStride + p] = in ? sp_ggamma(gv[i], xv[i], mean[i], rstd[i]) : 0.f;
+          gb[(cq + i) * kSpAStride + p] = in ? gv[i] : 0.f;
+        }
       }
-      ga[c * kSpAStride + p] = va;
-      gb[c * kSpAStride + p] = vb;
+    } else {
+      for (int e = tid; e < 16 * kSpPx; e += kBlock) {
+        const int c = e >> 7, p = e & (kSpPx - 1);
+        const int yy = t.y0 + (p >> A.ltw), xx = t.x0 + (p & (A.TW - 1));
+        float va = 0.f, vb = 0.f;
+        if (yy < A.H && xx < A.W) {
+          const size_t plane = static_cast<size_t>(t.b) * A.C + c0 + c;
+          const size_t at = plane * A.HW + static_cast<size_t>(yy) * A.W + xx;
+          vb = to_f32<T>(gy[at]);
+          va = sp_ggamma(vb, to_f32<T>(x[at]), A.mean[plane], A.rstd[plane]);
+        }
+        ga[c * kSpAStride + p] = va;
+        gb[c * kSpAStride + p] = vb;
+      }
     }
     __syncthreads();
     sp_form_h(A, t, w0s, ss, hs, HS);
@@ -449,7 +569,7 @@ __global__ __launch_bounds__(kBlock) void k_spade_dw_fin(const Group<SpadeArgs> 
 // time with a 1-pixel halo as [halo pixel][2][CC + 4].  Epilogue: ReLU mask from the re-formed pre-activation, dpre to LDS [j][128 + 4]
 // (over the staging area), then the 9 tap planes u[t][p] = sum_j w0[j][t] dpre[j][p] and the tile's dW0 / db0 partials.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool NHWC>
 __global__ __launch_bounds__(kBlock) void k_spade_dh(const Group<SpadeArgs> G) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int local;
@@ -476,19 +596,44 @@ __global__ __launch_bounds__(kBlock) void k_spade_dh(const Group<SpadeArgs> G) {
   for (int cc0 = 0; cc0 < A.C; cc0 += CC) {
     const int cn = min(CC, A.C - cc0);                     // the last round holds 16 channels when C % 32 == 16
     __syncthreads();
-    for (int e = tid; e < cn * NPH; e += kBlock) {
-      const int c = e / NPH, ph = e - c * NPH;
-      const int r = ph / PW, cx = ph - r * PW;
-      const int yy = t.y0 + r - 1, xx = t.x0 + cx - 1;
-      float va = 0.f, vb = 0.f;
-      if (yy >= 0 && yy < A.H && xx >= 0 && xx < A.W) {
-        const size_t plane = static_cast<size_t>(t.b) * A.C + cc0 + c;
-        const size_t at = plane * A.HW + static_cast<size_t>(yy) * A.W + xx;
-        vb = to_f32<T>(gy[at]);
-        va = vb * (to_f32<T>(x[at]) - A.mean[plane]) * A.rstd[plane];
+    if constexpr (NHWC) {
+      constexpr int V = 16 / sizeof(T);                      // the round's cn channels of a halo pixel are contiguous: cn / V 16-byte accesses
+      const int cv = cn / V;
+      for (int e = tid; e < NPH * cv; e += kBlock) {
+        const int ph = e / cv, cq = (e - ph * cv) * V;
+        const int r = ph / PW, cx = ph - r * PW;
+        const int yy = t.y0 + r - 1, xx = t.x0 + cx - 1;
+        float xv[V] = {}, gv[V] = {}, mean[V] = {}, rstd[V] = {};
+        const bool in = yy >= 0 && yy < A.H && xx >= 0 && xx < A.W;
+        if (in) {
+          const size_t plane = static_cast<size_t>(t.b) * A.C + cc0 + cq;
+          const size_t at = (static_cast<size_t>(t.b) * A.HW + static_cast<size_t>(yy) * A.W + xx) * A.C + cc0 + cq;
+          load_vec<T, V>(gy + at, gv);
+          load_vec<T, V>(x + at, xv);
+          ldn<V>(A.mean + plane, mean);
+          ldn<V>(A.rstd + plane, rstd);
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+          gs[ph * GS + cq + i] = in ? sp_ggamma(gv[i], xv[i], mean[i], rstd[i]) : 0.f;
+          gs[ph * GS + CC + 4 + cq + i] = in ? gv[i] : 0.f;
+        }
       }
-      gs[ph * GS + c] = va;
-      gs[ph * GS + CC + 4 + c] = vb;
+    } else {
+      for (int e = tid; e < cn * NPH; e += kBlock) {
+        const int c = e / NPH, ph = e - c * NPH;
+        const int r = ph / PW, cx = ph - r * PW;
+        const int yy = t.y0 + r - 1, xx = t.x0 + cx - 1;
+        float va = 0.f, vb = 0.f;
+        if (yy >= 0 && yy < A.H && xx >= 0 && xx < A.W) {
+          const size_t plane = static_cast<size_t>(t.b) * A.C + cc0 + c;
+          const size_t at = plane * A.HW + static_cast<size_t>(yy) * A.W + xx;
+          vb = to_f32<T>(gy[at]);
+          va = sp_ggamma(vb, to_f32<T>(x[at]), A.mean[plane], A.rstd[plane]);
+        }
+        gs[ph * GS + c] = va;
+        gs[ph * GS + CC + 4 + c] = vb;
+      }
     }
     __syncthreads();
     if (active) {

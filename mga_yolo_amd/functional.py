@@ -658,7 +658,9 @@ def spade_compose(x, mask, params, cfg: SpadeConfig, running=None) -> torch.Tens
 
 class _SpadeFn(torch.autograd.Function):
     """n independent levels; flat inputs = n x (x, mask|None, w0, b0, wg, bg, wb, bb, running_mean|None, running_var|None, nbt|None).
-    Forward: statistics, weight pack and ONE fused launch (MFMA convs + FiLM); backward: plain launches (csrc/spade.cuh)."""
+    Forward: statistics, weight pack and ONE fused launch (MFMA convs + FiLM); backward: plain launches (csrc/spade.cuh).  The layout
+    decides the kernels, per level (_is_nhwc): a channels_last x runs the channels-last kernels (csrc/spade_nhwc.cuh) without a copy, y and
+    gx come back channels_last, and the results are the NCHW kernels' bit for bit."""
 
     @staticmethod
     def forward(ctx, cfgs: Tuple[SpadeConfig, ...], *flat):
@@ -675,17 +677,19 @@ class _SpadeFn(torch.autograd.Function):
             if not x.is_cuda or x.device != dev:
                 raise RuntimeError("mask_spade: all features must live on the same GPU")
             B, Cc, H, W = x.shape
-            xc = _ready(x)
+            nhwc = _is_nhwc(x)
+            xc = _ready_nhwc(x) if nhwc else _ready(x)
             m32, mmeta = _mask_in(mask, B, H, W)
             ps = [None] * 6 if mask is None else [_param32(t) for t in (w0, b0, wg, bg, wb, bb)]
-            y = torch.empty_like(xc)
+            y = torch.empty_like(xc)                                # (preserve_format: channels_last for a channels_last level)
             elem = xc.element_size()
             full = _lib.spade_ctx_bytes(B, Cc, H, W, cfg.hidden)
             a16 = lambda v: (v + 15) & ~15
             base = full - a16(xc.numel() * 4)
             save = want_grad and m32 is not None
             cbuf = torch.empty(base + (a16(xc.numel() * elem) if save else 0), dtype=torch.uint8, device=dev)
-            fill_spade(levels[l], xc, m32, ps, cfg, (rm, rv, nbt), cbuf, y=y, save_gamma=save)
+            fill_spade(levels[l], xc, m32, ps, cfg, (rm, rv, nbt), cbuf, y=y, save_gamma=save,
+                       flags=_lib.SPADE_LAYOUT_NHWC if nhwc else 0)
             keep += [xc, m32, cbuf] + ps
             outs.append(y)
             meta.append(mmeta)
@@ -708,13 +712,15 @@ class _SpadeFn(torch.autograd.Function):
             ps = list(saved[9 * l + 3:9 * l + 9])
             cfg = cfgs[l]
             B, Cc, H, W = xc.shape
-            gy = _grad_in(gys[l], xc, False)
+            nhwc = _is_nhwc(xc)                                     # xc is dense in one of the two layouts: the forward's answer
+            gy = _grad_in(gys[l], xc, nhwc)
             gx = torch.empty_like(xc)
             want_gmask = m32 is not None and ctx.needs_input_grad[1 + _SPADE_SLOTS * l + 1]
             gmask = torch.empty_like(m32) if want_gmask else None
             gps = [None] * 6 if m32 is None else [torch.empty_like(p) for p in ps]
             scratch = torch.empty(_lib.spade_scratch_bytes(B, Cc, H, W, cfg.hidden), dtype=torch.uint8, device=dev)
-            fill_spade(levels[l], xc, m32, ps, cfg, ctx.running[l], cbuf, gy=gy, gx=gx, gmask=gmask, pgrads=gps, scratch=scratch)
+            fill_spade(levels[l], xc, m32, ps, cfg, ctx.running[l], cbuf, gy=gy, gx=gx, gmask=gmask, pgrads=gps, scratch=scratch,
+                       flags=_lib.SPADE_LAYOUT_NHWC if nhwc else 0)
             hold += [gy, scratch]
             grads += [gx, gmask] + gps + [None, None, None]
         _call("mgaspade_backward", dev, levels, n)
@@ -759,8 +765,8 @@ def _spade_prepare(x, mask, params, cfg: SpadeConfig, running):
     if cfg.bn:
         if rm is None or rv is None or rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous():
             raise ValueError("MaskSPADE with norm_type='bn' needs contiguous fp32 running_mean / running_var")
-    if not x.is_contiguous():
-        x = x.contiguous()                                                       # channels_last and every other layout: one copy to NCHW
+    if not x.is_contiguous() and not _is_nhwc(x):
+        x = x.contiguous()                                                       # neither NCHW nor channels_last: one copy to NCHW
     return [x, mask] + list(params) + [rm, rv, nbt]
 
 

@@ -154,7 +154,8 @@ static void head() {
   }
 }
 // ---- MaskSPADE
-static mgaspade_level_t spade_level(int dt, Shape s, int hid, int bn, int train, bool mask, bool gmask, int save) {
+static const int kSpadeNhwc = 2;   // MGASPADE_LAYOUT_NHWC, as a literal: the driver also builds against a revision from before the flag (which refuses it)
+static mgaspade_level_t spade_level(int dt, Shape s, int hid, int bn, int train, bool mask, bool gmask, int save, int flags = 0) {
   mgaspade_level_t L{};
   L.x = dev(); L.y = dev(); L.gy = dev(); L.gx = dev(); L.mask = mask ? devf() : nullptr; L.gmask = gmask ? devf() : nullptr;
   L.w0 = devf(); L.b0 = devf(); L.wg = devf(); L.bg = devf(); L.wb = devf(); L.bb = devf();
@@ -162,7 +163,7 @@ static mgaspade_level_t spade_level(int dt, Shape s, int hid, int bn, int train,
   L.gw0 = devf(); L.gb0 = devf(); L.gwg = devf(); L.gbg = devf(); L.gwb = devf(); L.gbb = devf();
   L.ctx = dev(); L.ctx_bytes = mgaspade_ctx_bytes(s.B, s.C, s.H, s.W, hid); L.scratch = dev(); L.scratch_bytes = mgaspade_scratch_bytes(s.B, s.C, s.H, s.W, hid);
   L.B = s.B; L.C = s.C; L.H = s.H; L.W = s.W; L.hidden = hid; L.dtype = dt; L.norm_type = bn; L.training = train; L.use_sigmoid_mask = 1;
-  L.save_gamma = save; L.eps = 1e-5f; L.momentum = 0.1f;
+  L.save_gamma = save; L.eps = 1e-5f; L.momentum = 0.1f; L.flags = flags;
   return L;
 }
 static void spade() {
@@ -175,9 +176,16 @@ static void spade() {
         rc(F("spade fwd dt=%d B=%d C=%d H=%d W=%d hid=%d norm=%d mask=%d save=%d", dt, s.B, s.C, s.H, s.W, hid, norm, mask, gs), mgaspade_forward(&L, 1, ST));
         rc(F("spade bwd dt=%d B=%d C=%d H=%d W=%d hid=%d norm=%d mask=%d gmask=%d", dt, s.B, s.C, s.H, s.W, hid, norm, mask, gs), mgaspade_backward(&L, 1, ST));
         if (n < MGACBAM_MAX_LEVELS && hid == 16 && (norm + mask + gs) % 2) P[n++] = L;
+        if (hid != 16) continue;
+        const mgaspade_level_t N = spade_level(dt, s, hid, norm != 0, norm == 2, mask, gs, gs, kSpadeNhwc);
+        rc(F("spade fwd nhwc dt=%d B=%d C=%d H=%d W=%d hid=%d norm=%d mask=%d save=%d", dt, s.B, s.C, s.H, s.W, hid, norm, mask, gs), mgaspade_forward(&N, 1, ST));
+        rc(F("spade bwd nhwc dt=%d B=%d C=%d H=%d W=%d hid=%d norm=%d mask=%d gmask=%d", dt, s.B, s.C, s.H, s.W, hid, norm, mask, gs), mgaspade_backward(&N, 1, ST));
       }
     rc(F("spade fwd pyramid dt=%d n=%d", dt, n), mgaspade_forward(P, n, ST));
     rc(F("spade bwd pyramid dt=%d n=%d", dt, n), mgaspade_backward(P, n, ST));
+    for (int l = 0; l < n; l += 2) P[l].flags = kSpadeNhwc;   // levels of both layouts in one call: the sizes do not change
+    rc(F("spade fwd pyramid mixed layouts dt=%d n=%d", dt, n), mgaspade_forward(P, n, ST));
+    rc(F("spade bwd pyramid mixed layouts dt=%d n=%d", dt, n), mgaspade_backward(P, n, ST));
   }
 }
 // ---- segmentation loss, Kendall combine, gater, resize
@@ -308,8 +316,7 @@ static void invalid() {
     bad("mgahead_backward", hb, hbwd); bad_bwd("mgahead_backward", hb, hbwd);
     bad1("mgahead_backward", "gwh NULL", hb, hbwd, [](mgahead_bwd_level_t& L) { L.gwh = nullptr; });
     bad1("mgahead_backward", "eps=0", hb, hbwd, [](mgahead_bwd_level_t& L) { L.p.eps = 0.f; });
-    if (nhwc) continue;
-    const mgaspade_level_t sp = spade_level(dt, s, 16, 1, 1, true, true, 1);
+    const mgaspade_level_t sp = spade_level(dt, s, 16, 1, 1, true, true, 1, nhwc ? kSpadeNhwc : 0);
     auto sfwd = [](const mgaspade_level_t* L, int n) { return mgaspade_forward(L, n, ST); };
     auto sbwd = [](const mgaspade_level_t* L, int n) { return mgaspade_backward(L, n, ST); };
     bad("mgaspade_forward", sp, sfwd); bad("mgaspade_backward", sp, sbwd); bad_bwd("mgaspade_backward", sp, sbwd);
