@@ -161,3 +161,11 @@ def fill_spade(L: _lib.SpadeLevel, x, mask, params, cfg, running, ctx, y=None, s
     L.B, L.C, L.H, L.W, L.hidden, L.dtype = B, Cc, H, W, cfg.hidden, DTYPES[x.dtype]
     L.norm_type, L.training = (_lib.NORM_BN if cfg.bn else _lib.NORM_IN), int(cfg.training)
     L.use_sigmoid_mask, L.save_gamma, L.eps, L.momentum, L.flags = int(cfg.use_sigmoid_mask), int(save_gamma), cfg.eps, cfg.momentum, int(flags)
+
+
+# ---- ProbMaskGater on a pyramid (include/mgagate.h): one struct for both directions
+def fill_gate(L: _lib.GateLevel, p, out, msoft, gout, gp, mode: int, stream_id: int, tau: float, p_min: float, threshold: float) -> None:
+    """p: the gate's fp32 input; forward passes out (and msoft for the two soft modes), backward gout, gp (and that msoft); mode: _lib.GATE_*."""
+    L.p, L.out, L.msoft, L.gout, L.gp = p.data_ptr(), _ptr(out), _ptr(msoft), _ptr(gout), _ptr(gp)
+    L.n, L.mode, L.stream_id = p.numel(), int(mode), int(stream_id)
+    L.tau, L.p_min, L.threshold = float(tau), float(p_min), float(threshold)

@@ -128,6 +128,17 @@ class SpadeLevel(C.Structure):                   # mgaspade_level_t (include/mga
                 [("eps", C.c_float), ("momentum", C.c_float), ("flags", C.c_int32)])
 
 
+# ProbMaskGater on a pyramid with in-kernel noise (include/mgagate.h): mgagate_level_t.mode, by the module's mode name
+GATE_DETERMINISTIC, GATE_GUMBEL, GATE_HARD_ST, GATE_BERNOULLI_DETACH = 0, 1, 2, 3
+GATE_MODES = dict(deterministic=GATE_DETERMINISTIC, gumbel=GATE_GUMBEL, hard_st=GATE_HARD_ST, bernoulli_detach=GATE_BERNOULLI_DETACH)
+
+
+class GateLevel(C.Structure):                    # mgagate_level_t (include/mgagate.h)
+    _fields_ = [("p", C.c_void_p), ("out", C.c_void_p), ("msoft", C.c_void_p), ("gout", C.c_void_p), ("gp", C.c_void_p),
+                ("n", C.c_uint32), ("mode", C.c_int32), ("stream_id", C.c_int32),
+                ("tau", C.c_float), ("p_min", C.c_float), ("threshold", C.c_float)]
+
+
 SYMBOLS = {
     "mgacbam_abi_version": (C.c_int, []),
     "mgacbam_last_error": (C.c_char_p, []),
@@ -172,6 +183,13 @@ SPADE_SYMBOLS = {
     "mgaspade_forward": (C.c_int, [C.POINTER(SpadeLevel), C.c_int, C.c_void_p]),
     "mgaspade_backward": (C.c_int, [C.POINTER(SpadeLevel), C.c_int, C.c_void_p]),
 }
+# every symbol include/mgagate.h declares (the pyramid gate with in-kernel Philox noise: a header of its own as well)
+GATE_SYMBOLS = {
+    "mgagate_forward": (C.c_int, [C.POINTER(GateLevel), C.c_int, C.c_void_p, C.c_void_p]),
+    "mgagate_backward": (C.c_int, [C.POINTER(GateLevel), C.c_int, C.c_void_p]),
+    "mgagate_philox4x32": (None, [C.POINTER(C.c_uint32)] * 3),
+    "mgagate_uniforms": (None, [C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_float)]),
+}
 
 _lib = None
 _lock = threading.Lock()
@@ -195,7 +213,7 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:

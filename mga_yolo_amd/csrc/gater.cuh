@@ -20,34 +20,55 @@ struct GaterArgs {
   int hard;
 };
 
+// The gate's arithmetic, element by element: k_pmg_fwd / k_pmg_bwd below and the multi-level kernels of gate_rng.cuh (which draw the
+// uniforms themselves) call these same functions, so equal uniforms give equal bits on either path.
+// p = max(clamp(p_in, 0, 1), p_min)
+__device__ __forceinline__ float gate_clamp(float pin, float p_min) {
+  float p = fminf(fmaxf(pin, 0.f), 1.f);
+  if (p_min > 0.f) p = fmaxf(p, p_min);
+  return p;
+}
+// the soft sample m of a clamped p and two uniforms
+__device__ __forceinline__ float gate_soft(float p, float u1, float u2, float inv_tau) {
+  const float a = fminf(fmaxf(u1, kGateEps), 1.f - kGateEps), b = fminf(fmaxf(u2, kGateEps), 1.f - kGateEps);
+  const float q = fminf(fmaxf(p, kGateEps), 1.f - kGateEps);
+  // logit(q) + g, g = -log(-log a) + log(-log b) (logistic noise), as ONE logarithm of q (-log b) / ((1 - q) (-log a)).  The four
+  // terms reach 13.8 each and cancel where m is mid-range: summed in fp32 they carry about 1e-6 of rounding, which 1 / tau = 3.3
+  // turns into 1e-6 of m; the quotient carries four relative roundings (3e-7) whatever the terms' size.  1 - q is exact for
+  // q >= 0.5 and never below 1e-6; the quotient stays within 1e-14 .. 1e14.
+  const float z = logf((q * -logf(b)) / ((1.f - q) * -logf(a))) * inv_tau;
+  return 1.f / (1.f + expf(-z));
+}
+// does dL/dp_in pass the two clamps?  (torch's rule: inside the bounds, the bounds included)
+__device__ __forceinline__ bool gate_clamp_pass(float pin, float p_min) {
+  bool pass = pin >= 0.f && pin <= 1.f;
+  if (p_min > 0.f) pass = pass && fminf(fmaxf(pin, 0.f), 1.f) >= p_min;
+  return pass;
+}
+// dL/dp_in of the soft sample m (both soft modes: hard_st is straight-through)
+__device__ __forceinline__ float gate_soft_bwd(float pin, float p_min, float m, float gout, float inv_tau) {
+  float p = fminf(fmaxf(pin, 0.f), 1.f);
+  bool pass = pin >= 0.f && pin <= 1.f;                                   // clamp(0,1) passes gradient inside, bounds included
+  if (p_min > 0.f) { pass = pass && p >= p_min; p = fmaxf(p, p_min); }
+  pass = pass && p >= kGateEps && p <= 1.f - kGateEps;                    // the logit's own clamp
+  const float dlogit = 1.f / p + 1.f / (1.f - p);
+  return pass ? gout * m * (1.f - m) * inv_tau * dlogit : 0.f;
+}
+
+// (the two kernels belong to ONE translation unit, api_eca.hip; api_gate.hip takes the functions above alone)
+#ifndef MGACBAM_GATE_MATH_ONLY
 __global__ __launch_bounds__(kBlock) void k_pmg_fwd(const GaterArgs A) {
   for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < A.n; i += static_cast<size_t>(gridDim.x) * kBlock) {
-    float p = fminf(fmaxf(A.p[i], 0.f), 1.f);
-    if (A.p_min > 0.f) p = fmaxf(p, A.p_min);
-    const float a = fminf(fmaxf(A.u1[i], kGateEps), 1.f - kGateEps), b = fminf(fmaxf(A.u2[i], kGateEps), 1.f - kGateEps);
-    const float q = fminf(fmaxf(p, kGateEps), 1.f - kGateEps);
-    // logit(q) + g, g = -log(-log a) + log(-log b) (logistic noise), as ONE logarithm of q (-log b) / ((1 - q) (-log a)).  The four
-    // terms reach 13.8 each and cancel where m is mid-range: summed in fp32 they carry about 1e-6 of rounding, which 1 / tau = 3.3
-    // turns into 1e-6 of m; the quotient carries four relative roundings (3e-7) whatever the terms' size.  1 - q is exact for
-    // q >= 0.5 and never below 1e-6; the quotient stays within 1e-14 .. 1e14.
-    const float z = logf((q * -logf(b)) / ((1.f - q) * -logf(a))) * A.inv_tau;
-    const float m = 1.f / (1.f + expf(-z));
+    const float m = gate_soft(gate_clamp(A.p[i], A.p_min), A.u1[i], A.u2[i], A.inv_tau);
     A.msoft[i] = m;
     A.out[i] = A.hard ? (m > A.threshold ? 1.f : 0.f) : m;
   }
 }
 
 __global__ __launch_bounds__(kBlock) void k_pmg_bwd(const GaterArgs A) {
-  for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < A.n; i += static_cast<size_t>(gridDim.x) * kBlock) {
-    const float pin = A.p[i];
-    float p = fminf(fmaxf(pin, 0.f), 1.f);
-    bool pass = pin >= 0.f && pin <= 1.f;                                   // clamp(0,1) passes gradient inside, bounds included
-    if (A.p_min > 0.f) { pass = pass && p >= A.p_min; p = fmaxf(p, A.p_min); }
-    pass = pass && p >= kGateEps && p <= 1.f - kGateEps;                    // the logit's own clamp
-    const float m = A.msoft[i];
-    const float dlogit = 1.f / p + 1.f / (1.f - p);
-    A.gp[i] = pass ? A.gout[i] * m * (1.f - m) * A.inv_tau * dlogit : 0.f;
-  }
+  for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < A.n; i += static_cast<size_t>(gridDim.x) * kBlock)
+    A.gp[i] = gate_soft_bwd(A.p[i], A.p_min, A.msoft[i], A.gout[i], A.inv_tau);
 }
+#endif
 
 }  // namespace mgacbam

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._binding import DTYPES as _DTYPES, call as _call, raw_stream as _raw_stream
-from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_head_bwd, fill_head_fwd, fill_spade
+from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_gate, fill_head_bwd, fill_head_fwd, fill_spade
 from ._binding import head_params as _head_params  # noqa: F401  (tests fill head levels by hand with it)
 
 
@@ -488,6 +488,98 @@ def prob_mask_gate(p: torch.Tensor, u1: torch.Tensor, u2: torch.Tensor, tau: flo
     """Gumbel-sigmoid gate of ProbMaskGater for device tensors: max(clamp(p,0,1), p_min) -> sigmoid((logit + logistic(u1,u2)) / tau),
     thresholded with a straight-through gradient when ``hard``.  u1, u2: uniform draws, as torch.rand gives them."""
     return _GaterFn.apply(p, u1, u2, tau, p_min, threshold, hard)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# ProbMaskGater on a pyramid (include/mgagate.h): every level in one launch each way, the uniforms drawn IN the kernel from a Philox4x32-10
+# stream keyed by a device-resident (seed, step) -- nothing is drawn by torch, so the call can sit inside a captured graph
+# ---------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class GateConfig:
+    """One level's ProbMaskGater settings (probmaskgater.py:8-30).  mode: 'gumbel' | 'hard_st' | 'bernoulli_detach' | 'deterministic';
+    a gate that is not ``training`` returns the clamped input whatever its mode, as the module does in eval.  stream_id: the level's word in
+    the Philox counter; None = the level's position in the call."""
+    mode: str = "gumbel"
+    tau: float = 1.0
+    p_min: float = 0.0
+    threshold: float = 0.5
+    training: bool = True
+    stream_id: Optional[int] = None
+
+    def __post_init__(self):
+        if self.mode not in _lib.GATE_MODES:
+            raise ValueError(f"GateConfig: mode {self.mode!r} is none of {sorted(_lib.GATE_MODES)}")
+        if not self.tau > 0:
+            raise ValueError("GateConfig: tau must be > 0")
+
+    def code(self) -> int:
+        """mgagate_level_t.mode"""
+        return _lib.GATE_MODES[self.mode] if self.training else _lib.GATE_DETERMINISTIC
+
+    def stream(self, level: int) -> int:
+        return level if self.stream_id is None else int(self.stream_id)
+
+
+def gate_state(seed: int = 0, step: int = 0, device="cuda") -> torch.Tensor:
+    """The noise state of prob_mask_gate_pyramid: int64 {seed, step, arrivals = 0, 0} on the device.  A noisy forward leaves step + 1."""
+    return torch.tensor([int(seed), int(step), 0, 0], dtype=torch.int64, device=device)
+
+
+def _check_gate_state(state: torch.Tensor, dev: torch.device) -> None:
+    if not (isinstance(state, torch.Tensor) and state.dtype == torch.int64 and state.numel() == 4 and state.is_contiguous() and state.device == dev):
+        raise RuntimeError("prob_mask_gate_pyramid: state must be a contiguous int64 tensor of 4 elements on the masks' device (gate_state())")
+
+
+class _GatePyramidFn(torch.autograd.Function):
+    """n levels; inputs after (cfgs, state): the n fp32 masks."""
+
+    @staticmethod
+    def forward(ctx, cfgs, state, *masks):
+        _lib.load()
+        n = len(masks)
+        ps = [_ready(m) for m in masks]
+        dev = ps[0].device
+        _check_gate_state(state, dev)
+        outs = [torch.empty_like(p) for p in ps]
+        soft = [c.code() in (_lib.GATE_GUMBEL, _lib.GATE_HARD_ST) for c in cfgs]
+        msoft = [torch.empty_like(p) if s else None for p, s in zip(ps, soft)]
+        levels = (_lib.GateLevel * n)()
+        for l, (p, c) in enumerate(zip(ps, cfgs)):
+            fill_gate(levels[l], p, outs[l], msoft[l], None, None, c.code(), c.stream(l), c.tau, c.p_min, c.threshold)
+        _call("mgagate_forward", dev, levels, n, state.data_ptr())
+        ctx.cfgs = cfgs
+        ctx.save_for_backward(*ps, *(m for m in msoft if m is not None))
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        cfgs, n = ctx.cfgs, len(ctx.cfgs)
+        ps, rest = ctx.saved_tensors[:n], list(ctx.saved_tensors[n:])
+        levels = (_lib.GateLevel * n)()
+        gps = []
+        for l, (p, c) in enumerate(zip(ps, cfgs)):
+            ms = rest.pop(0) if c.code() in (_lib.GATE_GUMBEL, _lib.GATE_HARD_ST) else None
+            g = torch.zeros_like(p) if gouts[l] is None else _ready(gouts[l].to(torch.float32))
+            gps.append(torch.empty_like(p))
+            fill_gate(levels[l], p, None, ms, g, gps[l], c.code(), c.stream(l), c.tau, c.p_min, c.threshold)
+        _call("mgagate_backward", ps[0].device, levels, n)
+        return (None, None, *gps)
+
+
+def prob_mask_gate_pyramid(masks: Sequence[torch.Tensor], state: torch.Tensor, cfgs: Sequence[GateConfig]) -> tuple:
+    """ProbMaskGater on every level of a pyramid, one launch forward and one backward, for device tensors.  masks: per level (B,1,H,W) or
+    (B,H,W) of any float dtype (they enter as ``.float()``, as the module takes them); state: ``gate_state(seed, step)``, advanced in
+    place by a forward that draws noise; cfgs: one GateConfig per level.  -> the gated masks, fp32 (B,1,H,W).
+    The noise is this library's own Philox stream (include/mgagate.h): statistically, not bitwise, what the ProbMaskGater module draws."""
+    if len(masks) != len(cfgs) or not 1 <= len(masks) <= _lib.MAX_LEVELS:
+        raise RuntimeError(f"prob_mask_gate_pyramid: {len(masks)} masks, {len(cfgs)} configs (1..{_lib.MAX_LEVELS} of each)")
+    ms = []
+    for m in masks:
+        if not m.is_cuda or not m.is_floating_point():
+            raise TypeError("prob_mask_gate_pyramid expects floating-point device tensors")
+        m = m.unsqueeze(1) if m.dim() == 3 else m
+        ms.append(m.float())
+    return _GatePyramidFn.apply(tuple(cfgs), state, *ms)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -7,6 +7,12 @@ A ``PyramidPlan`` owns, per level: x, mask, y, gy, gx, gmask, ctx, scratch; and 
 gradients of all levels (what data-parallel training all-reduces, see ``dp.py``).  ``forward`` / ``backward`` each make ONE
 library call on the current stream (5 kernel launches per step in total).  ``backward_params`` + ``backward_inputs`` is
 the split form for callers that want the parameter gradients early (see ``dp.py``).
+
+With ``gate`` (one ``GateConfig`` per level) the plan also runs the reference's ProbMaskGater between the mask it is given and the block
+-- what a ``MGA_PROB_MODE`` training run does: it then owns ``logits`` (the gate's input, what the caller fills instead of ``mask``),
+``msoft``, ``glogits`` (dL/dlogits, the gate's backward of ``gmask``) and ``rng_state``; ``forward`` is gate -> block and ``backward``
+block -> gate, one more launch each.  The noise is drawn in the kernel from the Philox stream of include/mgagate.h, keyed by the
+device-resident (seed, step) of ``rng_state`` that every forward advances: a captured graph replays with fresh noise.
 """
 from __future__ import annotations
 
@@ -17,8 +23,8 @@ import os
 import torch
 
 from . import _lib
-from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd
-from .functional import BlockConfig, HandoffTimeout, ctx_views
+from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_gate
+from .functional import BlockConfig, GateConfig, HandoffTimeout, ctx_views, gate_state
 
 PARAM_NAMES = ("w1", "b1", "w2", "b2", "wsa", "beta")
 
@@ -27,7 +33,8 @@ class PyramidPlan:
     def __init__(self, shapes: Sequence[Tuple[int, int, int, int]], params: Sequence[Sequence[torch.Tensor]],
                  cfgs: Sequence[BlockConfig], dtype: torch.dtype = torch.float32, device="cuda",
                  with_mask: bool = True, want_gmask: bool = True, use_proj: bool = False,
-                 fuse_forward: Optional[bool] = None, grad_bucket: Optional[torch.Tensor] = None):
+                 fuse_forward: Optional[bool] = None, grad_bucket: Optional[torch.Tensor] = None,
+                 gate: Optional[Sequence[GateConfig]] = None, seed: int = 0):
         # fuse_forward: k_chan + k_apply as ONE x-resident launch, k_gate (MGACBAM_FWD_FUSE); None = env MGACBAM_FUSE_FWD (on)
         self.fuse_forward = bool(int(os.environ.get("MGACBAM_FUSE_FWD", "1"))) if fuse_forward is None else bool(fuse_forward)
         # transposed conv folded into the k_bwd_reduce1 launch (MGACBAM_BWD_FOLD) whenever the whole backward is one call
@@ -66,12 +73,31 @@ class PyramidPlan:
             fill_cbam_fwd(self._fwd[l], self.x[l], self.mask[l], self.y[l], self.ctx[l], ps, cfg, _lib.FWD_SAVE_PROJ if proj else 0)
             fill_cbam_bwd(self._bwd[l], self.x[l], self.mask[l], self.gy[l], self.ctx[l], self.scratch[l], self.gx[l], self.gmask[l],
                           views, ps, cfg, _lib.BWD_HAVE_PROJ if proj else 0)
+        self.gate = None if gate is None else list(gate)
+        if self.gate is not None:
+            self._init_gate(seed)
+
+    def _init_gate(self, seed: int) -> None:
+        """logits -> [gate] -> mask, gmask -> [gate backward] -> glogits: the buffers and the two level tables (include/mgagate.h)"""
+        assert len(self.gate) == self.n and all(m is not None for m in self.mask), "a gate needs one GateConfig per level and with_mask"
+        self.logits = [torch.zeros_like(m) for m in self.mask]
+        self.msoft = [torch.zeros_like(m) for m in self.mask]
+        self.glogits = [None if g is None else torch.zeros_like(g) for g in self.gmask]
+        self.rng_state = gate_state(seed, 0, self.device)
+        self._gate_fwd, self._gate_bwd = (_lib.GateLevel * self.n)(), (_lib.GateLevel * self.n)()
+        for l, c in enumerate(self.gate):
+            a = (c.code(), c.stream(l), c.tau, c.p_min, c.threshold)
+            fill_gate(self._gate_fwd[l], self.logits[l], self.mask[l], self.msoft[l], None, None, *a)
+            if self.glogits[l] is not None:
+                fill_gate(self._gate_bwd[l], self.logits[l], None, self.msoft[l], self.gmask[l], self.glogits[l], *a)
 
     # ------------------------------------------------------------------ library calls on the current stream
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def forward(self, stages: int = _lib.FWD_ALL):
+        if self.gate is not None and stages & _lib.FWD_STAGES["pool"]:     # the first stage reads the mask: the gate fills it before
+            _lib.check(self.lib.mgagate_forward(self._gate_fwd, self.n, self.rng_state.data_ptr(), self._stream()), "mgagate_forward")
         both = _lib.FWD_STAGES["chan"] | _lib.FWD_STAGES["apply"]
         if self.fuse_forward and (stages & both) == both:
             stages |= _lib.FWD_FUSE     # ctx is zero-filled at allocation, as the flag's contract asks
@@ -124,6 +150,8 @@ class PyramidPlan:
         if stages == _lib.BWD_ALL and self.fold_backward:
             stages |= _lib.BWD_FOLD     # ctx is zero-filled at allocation, as the flag's contract asks
         _lib.check(self.lib.mgacbam_backward_stages(self._bwd, self.n, stages, self._stream()), "mgacbam_backward_stages")
+        if self.gate is not None and stages & _lib.BWD_STAGES["apply"] and self.glogits[0] is not None:   # k_bwd_apply has written gmask
+            _lib.check(self.lib.mgagate_backward(self._gate_bwd, self.n, self._stream()), "mgagate_backward")
 
     def backward_params(self):
         """Every stage the parameter gradients depend on, as separate launches: they are complete when this returns to the

@@ -34,9 +34,11 @@ def _cbs(cin: int, cout: int, stride: int) -> nn.Sequential:
 class HarnessModel(nn.Module):
     """image (B,3,S,S) -> refined P3/P4/P5 features (what Detect would take) + the three mask-logit maps."""
 
-    def __init__(self, scale: str = "n", depth: int = 3):      # depth 3: 2.75 M parameters at n (YOLOv8n+MGA: 2.96 M), 11.0 M at s (10.9 M)
+    def __init__(self, scale: str = "n", depth: int = 3, prob_mode: Optional[str] = None):
+        # depth 3: 2.75 M parameters at n (YOLOv8n+MGA: 2.96 M), 11.0 M at s (10.9 M)
+        # prob_mode: MGA_PROB_MODE with this MGA_PROB_APPROACH -- a ProbMaskGater between every head and its block (masked_cbam.py:67-78)
         super().__init__()
-        from mga_yolo_amd import MGAMaskHead, MaskCBAM
+        from mga_yolo_amd import MGAMaskHead, MaskCBAM, ProbMaskGater
         c3, c4, c5 = WIDTHS[scale]
         stem = max(16, c3 // 4)
         self.stem = nn.Sequential(_cbs(3, stem, 2), _cbs(stem, 2 * stem, 2))                   # /4
@@ -45,6 +47,7 @@ class HarnessModel(nn.Module):
         self.to_p5 = nn.Sequential(_cbs(c4, c5, 2), *[_cbs(c5, c5, 1) for _ in range(depth)])             # /32
         self.heads = nn.ModuleList([MGAMaskHead(c, max(8, c // 4)) for c in (c3, c4, c5)])     # yolov8_cbam.yaml: hidden = C / 4
         self.blocks = nn.ModuleList([MaskCBAM(c) for c in (c3, c4, c5)])
+        self.gaters = nn.ModuleList([ProbMaskGater(prob_mode) for _ in range(3)]) if prob_mode else None
         self.mtl_log_vars = nn.Parameter(torch.zeros(2))                                        # model.py:119-121
         from mga_yolo_amd import SegLossConfig, SegmentationLoss
         self.criterion = SegmentationLoss(SegLossConfig())
@@ -54,10 +57,10 @@ class HarnessModel(nn.Module):
         p4 = self.to_p4(p3)
         p5 = self.to_p5(p4)
         refined, seg = [], {}
-        for key, f, head, blk in zip(("p3", "p4", "p5"), (p3, p4, p5), self.heads, self.blocks):
+        for l, (key, f, head, blk) in enumerate(zip(("p3", "p4", "p5"), (p3, p4, p5), self.heads, self.blocks)):
             m = head(f)                                            # model.py:57-64: the layer loop's list input
-            seg[key] = m
-            refined.append(blk([f, m]))
+            seg[key] = m                                           # the loss reads the head's output, the block the gated one
+            refined.append(blk([f, m if self.gaters is None else self.gaters[l](m)]))
         return refined, seg
 
     def forward(self, img: torch.Tensor, masks: Optional[List[torch.Tensor]] = None):
@@ -79,9 +82,9 @@ def synthetic_batch(batch: int, size: int, device, seed: int = 0):
     return img, masks
 
 
-def build(scale: str, device, world: int = 1, depth: int = 3):
+def build(scale: str, device, world: int = 1, depth: int = 3, prob_mode: Optional[str] = None):
     torch.manual_seed(0)
-    model = HarnessModel(scale, depth).to(device)
+    model = HarnessModel(scale, depth, prob_mode).to(device)
     if device.type == "cuda":
         model = model.to(memory_format=torch.channels_last)
     wrapped = model
@@ -108,12 +111,12 @@ def train_step(wrapped, opt, img, masks, amp: Optional[torch.dtype] = None, scal
 
 
 def run(scale: str = "n", batch: int = 32, size: int = 640, steps: int = 10, warmup: int = 3, device=None, world: int = 1, rank: int = 0,
-        amp: Optional[str] = None) -> dict:
+        amp: Optional[str] = None, prob_mode: Optional[str] = None) -> dict:
     """Time `steps` train steps; returns images/s over all ranks (max elapsed over ranks when world > 1)."""
     import torch.distributed as dist
     device = device or torch.device("cuda", 0)
     amp_dt = {None: None, "fp16": torch.float16, "bf16": torch.bfloat16}[amp]
-    model, wrapped, opt = build(scale, device, world)
+    model, wrapped, opt = build(scale, device, world, prob_mode=prob_mode)
     scaler = torch.amp.GradScaler(device.type, enabled=amp_dt is torch.float16) if amp_dt is not None else None
     img, masks = synthetic_batch(batch, size, device, seed=100 + rank)
     if device.type == "cuda":
@@ -138,12 +141,20 @@ def run(scale: str = "n", batch: int = 32, size: int = 640, steps: int = 10, war
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     nparam = sum(p.numel() for p in model.parameters())
-    return dict(images_per_s=round(world * batch * steps / el, 1), ms_per_step=round(el * 1e3 / steps, 3), steps=steps, warmup=warmup,
+    extra = dict(prob_mode=prob_mode) if prob_mode else {}
+    return dict(**extra, images_per_s=round(world * batch * steps / el, 1), ms_per_step=round(el * 1e3 / steps, 3), steps=steps, warmup=warmup,
                 batch_per_gpu=batch, image=size, scale=scale, amp=amp, loss=float(loss), parameters=nparam, grad_bytes_per_step=4 * nparam,
                 ddp=bool(world > 1), note="plain Conv-BN-SiLU stride stack with YOLOv8 widths (stand-in for the out-of-scope backbone) -> "
                 "MGAMaskHead / MaskCBAM / SegmentationLoss / Kendall combine of this package; fwd + loss + bwd + SGD step, eager autograd")
 
 
 if __name__ == "__main__":
+    import argparse
     import json
-    print(json.dumps(run(sys.argv[1] if len(sys.argv) > 1 else "n", steps=int(sys.argv[2]) if len(sys.argv) > 2 else 10)))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("scale", nargs="?", default="n")
+    ap.add_argument("steps", nargs="?", type=int, default=10)
+    ap.add_argument("--prob-mode", choices=["gumbel", "hard_st", "bernoulli_detach", "deterministic"], default=None,
+                    help="MGA_PROB_MODE: a ProbMaskGater of this approach between every mask head and its MaskCBAM (the reference's default is gumbel)")
+    a = ap.parse_args()
+    print(json.dumps(run(a.scale, steps=a.steps, prob_mode=a.prob_mode)))
