@@ -70,4 +70,8 @@ int mgaspade_backward(const mgaspade_level_t* levels, int n_levels, void* stream
 #ifdef __cplusplus
 }
 #endif
+
+/* The mask resample of the static plans (a mask given at another resolution): declared in a file of its own, which this header brings in,
+ * so that the declarations above stay exactly as they were. */
+#include "mgaresample.h"
 #endif /* MGASPADE_H_ */

@@ -11,9 +11,12 @@ from .functional import BlockConfig, EcaConfig, HandoffTimeout, handoff_report, 
 from .functional import SpadeConfig, mask_spade, mask_spade_pyramid  # noqa: F401
 from .functional import GateConfig, gate_state, prob_mask_gate_pyramid  # noqa: F401
 from .install import install, uninstall  # noqa: F401
+from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan  # noqa: F401
+from .slice import SlicePlan  # noqa: F401
 from .module import MGAMaskHead, MaskCBAM, MaskECA, MaskSPADE, MaskSPADEConfig, ProbMaskGater  # noqa: F401
 from .segloss import SegLossConfig, SegmentationLoss, kendall_combine  # noqa: F401
 
 __all__ = ["MaskCBAM", "MaskECA", "MaskSPADE", "MaskSPADEConfig", "SpadeConfig", "mask_spade", "mask_spade_pyramid", "MGAMaskHead", "mask_head", "mask_head_pyramid", "ProbMaskGater", "BlockConfig", "EcaConfig", "mask_cbam", "mask_cbam_pyramid", "mask_eca",
-           "mask_eca_pyramid", "prob_mask_gate", "prob_mask_gate_pyramid", "GateConfig", "gate_state", "resize_nearest", "install", "uninstall", "SegLossConfig", "SegmentationLoss", "kendall_combine", "HandoffTimeout", "handoff_report"]
+           "mask_eca_pyramid", "prob_mask_gate", "prob_mask_gate_pyramid", "GateConfig", "gate_state", "resize_nearest", "install", "uninstall", "SegLossConfig", "SegmentationLoss", "kendall_combine", "HandoffTimeout", "handoff_report",
+           "PyramidPlan", "EcaPyramidPlan", "SpadePyramidPlan", "SlicePlan"]
 __version__ = "0.1.0"

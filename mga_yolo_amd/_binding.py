@@ -163,6 +163,14 @@ def fill_spade(L: _lib.SpadeLevel, x, mask, params, cfg, running, ctx, y=None, s
     L.use_sigmoid_mask, L.save_gamma, L.eps, L.momentum, L.flags = int(cfg.use_sigmoid_mask), int(save_gamma), cfg.eps, cfg.momentum, int(flags)
 
 
+# ---- the mask resample of the static plans (include/mgaresample.h): one struct for both directions
+def fill_resample(L: _lib.ResampleLevel, src, dst, in_hw, out_hw) -> None:
+    """in_hw / out_hw: the sizes of the FORWARD's source and destination in both directions.  Forward: src (B,1,*in_hw) -> dst (B,1,*out_hw);
+    backward: src = dL/d(forward dst) (B,1,*out_hw), dst = dL/d(forward src) (B,1,*in_hw)."""
+    L.src, L.dst, L.B = src.data_ptr(), dst.data_ptr(), src.shape[0]
+    (L.in_h, L.in_w), (L.out_h, L.out_w) = in_hw, out_hw
+
+
 # ---- ProbMaskGater on a pyramid (include/mgagate.h): one struct for both directions
 def fill_gate(L: _lib.GateLevel, p, out, msoft, gout, gp, mode: int, stream_id: int, tau: float, p_min: float, threshold: float) -> None:
     """p: the gate's fp32 input; forward passes out (and msoft for the two soft modes), backward gout, gp (and that msoft); mode: _lib.GATE_*."""

@@ -128,6 +128,11 @@ class SpadeLevel(C.Structure):                   # mgaspade_level_t (include/mga
                 [("eps", C.c_float), ("momentum", C.c_float), ("flags", C.c_int32)])
 
 
+class ResampleLevel(C.Structure):                # mgaspade_resample_level_t (include/mgaresample.h)
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("B", C.c_int32), ("in_h", C.c_int32), ("in_w", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32)]
+
+
 # ProbMaskGater on a pyramid with in-kernel noise (include/mgagate.h): mgagate_level_t.mode, by the module's mode name
 GATE_DETERMINISTIC, GATE_GUMBEL, GATE_HARD_ST, GATE_BERNOULLI_DETACH = 0, 1, 2, 3
 GATE_MODES = dict(deterministic=GATE_DETERMINISTIC, gumbel=GATE_GUMBEL, hard_st=GATE_HARD_ST, bernoulli_detach=GATE_BERNOULLI_DETACH)
@@ -191,6 +196,12 @@ GATE_SYMBOLS = {
     "mgagate_uniforms": (None, [C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_float)]),
 }
 
+# every symbol include/mgaresample.h declares (the mask resample of the static plans; include/mgaspade.h brings that header in)
+RESAMPLE_SYMBOLS = {
+    "mgaspade_resample_forward": (C.c_int, [C.POINTER(ResampleLevel), C.c_int, C.c_void_p]),
+    "mgaspade_resample_backward": (C.c_int, [C.POINTER(ResampleLevel), C.c_int, C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -213,7 +224,7 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:

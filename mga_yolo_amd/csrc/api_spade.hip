@@ -2,6 +2,7 @@
 #include "host.cuh"
 #include "../../include/mgaspade.h"
 #include "spade_nhwc.cuh"
+#include "resample.cuh"
 
 constexpr int kSpMaxC = 1024;
 constexpr int kSpDwTarget = 512;     // workgroups k_spade_dw aims for: (C / 16) M tiles x pixel chunks
@@ -228,4 +229,56 @@ extern "C" int mgaspade_forward(const mgaspade_level_t* levels, int n_levels, vo
 }
 extern "C" int mgaspade_backward(const mgaspade_level_t* levels, int n_levels, void* stream) {
   return sp_run("mgaspade_backward", levels, n_levels, stream, true);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the mask resample of the static plans (include/mgaresample.h): one launch per direction for every level of the call
+// ------------------------------------------------------------------------------------------------
+static_assert(kResampleLevelsMax == MGACBAM_MAX_LEVELS, "ResampleGroup holds every level a call may carry");
+constexpr int kResampleMaxSize = 65536;     // per axis: the adjoint's inverse map is fp32 arithmetic, exact enough (one index) far beyond this
+
+// everything a call is checked for before its launch, and the kernel's arguments; returns the grid in `grid`
+static int resample_group(const char* what, const mgaspade_resample_level_t* levels, int n_levels, bool bwd, ResampleGroup& G, int& grid) {
+  if (!levels) return fail(MGACBAM_E_NULL, "%s: levels is NULL", what);
+  if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "%s: n_levels=%d", what, n_levels);
+  G.n = n_levels;
+  grid = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const mgaspade_resample_level_t& L = levels[l];
+    if (!L.src || !L.dst) return fail(MGACBAM_E_NULL, "%s: level %d: src / dst is NULL", what, l);
+    const int dims[5] = {L.B, L.in_h, L.in_w, L.out_h, L.out_w};
+    for (int d : dims)
+      if (d < 1 || d > kResampleMaxSize)
+        return fail(MGACBAM_E_SHAPE, "%s: level %d: B=%d in=%dx%d out=%dx%d (every size in 1..%d)", what, l, L.B, L.in_h, L.in_w, L.out_h, L.out_w,
+                    kResampleMaxSize);
+    const long long n_in = static_cast<long long>(L.B) * L.in_h * L.in_w, n_out = static_cast<long long>(L.B) * L.out_h * L.out_w;
+    if (n_in >= (1ll << 31) || n_out >= (1ll << 31))
+      return fail(MGACBAM_E_SHAPE, "%s: level %d: tensor too large B=%d in=%dx%d out=%dx%d", what, l, L.B, L.in_h, L.in_w, L.out_h, L.out_w);
+    if (!aligned_to(L.src, 4) || !aligned_to(L.dst, 4)) return fail(MGACBAM_E_ALIGN, "%s: level %d: fp32 buffers must be 4-byte aligned", what, l);
+    ResampleLevel& A = G.lv[l];
+    A.src = L.src; A.dst = L.dst; A.B = L.B; A.in_h = L.in_h; A.in_w = L.in_w; A.out_h = L.out_h; A.out_w = L.out_w;
+    A.vec = (!bwd && L.out_w % 4 == 0 && aligned_to(L.dst, 16)) ? 4 : 1;
+    const long long threads = bwd ? n_in : n_out / A.vec;
+    const long long blocks = (threads + kBlock - 1) / kBlock;
+    if (grid + blocks >= (1ll << 31)) return fail(MGACBAM_E_SHAPE, "%s: the call's grid is too large", what);
+    G.start[l] = grid;
+    grid += static_cast<int>(blocks);
+  }
+  for (int l = n_levels; l <= kResampleLevelsMax; ++l) G.start[l] = grid;
+  return 0;
+}
+static int resample_run(const char* what, const mgaspade_resample_level_t* levels, int n_levels, void* stream, bool bwd) {
+  ResampleGroup G;
+  int grid;
+  if (int e = resample_group(what, levels, n_levels, bwd, G, grid)) return e;
+  if (int e = launch(bwd ? "k_resample_bwd" : "k_resample_fwd", bwd ? k_resample_bwd : k_resample_fwd, grid, kBlock, 0,
+                     static_cast<hipStream_t>(stream), G)) return e;
+  g_err[0] = 0;
+  return 0;
+}
+extern "C" int mgaspade_resample_forward(const mgaspade_resample_level_t* levels, int n_levels, void* stream) {
+  return resample_run("mgaspade_resample_forward", levels, n_levels, stream, false);
+}
+extern "C" int mgaspade_resample_backward(const mgaspade_resample_level_t* levels, int n_levels, void* stream) {
+  return resample_run("mgaspade_resample_backward", levels, n_levels, stream, true);
 }

@@ -235,6 +235,16 @@ __device__ __forceinline__ float block_sum(float v, int tid, float* red) {
 
 __device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
 
+// One axis of F.interpolate(mode="bilinear", align_corners=False), torch's fp32 coordinate rule (scale = n / destination length, in fp32):
+// source coordinate max(scale * (d + 0.5) - 0.5, 0), taps i0 <= i1 (equal at the last index), weights 1 - lam and lam.  The ONE statement
+// of the rule: the loss's bilinear targets (segloss.cuh), the mask resample and its adjoint (resample.cuh) all call it.
+__device__ __forceinline__ void bilinear_tap(float scale, int d, int n, int& i0, int& i1, float& lam) {
+  const float f = fmaxf(scale * (static_cast<float>(d) + 0.5f) - 0.5f, 0.f);
+  i0 = min(static_cast<int>(f), n - 1);
+  i1 = i0 + (i0 < n - 1 ? 1 : 0);
+  lam = f - static_cast<float>(i0);
+}
+
 // XCD-aware workgroup -> (sample, part) map.  MI355X deals workgroup ids round-robin over its 8 XCDs (id % 8 labels the
 // workgroups that share an XCD and therefore an L2).  Every workgroup of sample b gets id % 8 == b % 8, so the per-sample
 // planes / masks / gates that all parts of a sample re-read are fetched into ONE L2 instead of all eight (PMC before:

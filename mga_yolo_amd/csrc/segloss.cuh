@@ -50,10 +50,10 @@ __device__ __forceinline__ float seg_target(const SegLevel& L, int b, int y, int
   const float sh = static_cast<float>(L.Ht) / static_cast<float>(L.H), sw = static_cast<float>(L.Wt) / static_cast<float>(L.W);
   if (L.bilinear) {
     // F.interpolate(mode="bilinear", align_corners=False): src = max(scale * (dst + 0.5) - 0.5, 0), 4 taps, upper index clamped
-    const float fy = fmaxf(sh * (static_cast<float>(y) + 0.5f) - 0.5f, 0.f), fx = fmaxf(sw * (static_cast<float>(x) + 0.5f) - 0.5f, 0.f);
-    const int y0 = min(static_cast<int>(fy), L.Ht - 1), x0 = min(static_cast<int>(fx), L.Wt - 1);
-    const int y1 = y0 + (y0 < L.Ht - 1 ? 1 : 0), x1 = x0 + (x0 < L.Wt - 1 ? 1 : 0);
-    const float ly = fy - static_cast<float>(y0), lx = fx - static_cast<float>(x0);
+    int y0, y1, x0, x1;
+    float ly, lx;
+    bilinear_tap(sh, y, L.Ht, y0, y1, ly);
+    bilinear_tap(sw, x, L.Wt, x0, x1, lx);
     const float* tb = L.target + static_cast<size_t>(b) * L.Ht * L.Wt;
     const float top = (1.f - lx) * tb[static_cast<size_t>(y0) * L.Wt + x0] + lx * tb[static_cast<size_t>(y0) * L.Wt + x1];
     const float bot = (1.f - lx) * tb[static_cast<size_t>(y1) * L.Wt + x0] + lx * tb[static_cast<size_t>(y1) * L.Wt + x1];

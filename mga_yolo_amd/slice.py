@@ -17,7 +17,11 @@ every parameter of the slice (three MaskCBAM blocks, three mask heads, the two K
 
 With ``gate=`` the slice is the one an MGA_PROB_MODE run trains (the default of every shipped hyper-parameter file): logits_l go through
 ProbMaskGater before MaskCBAM_l (masked_cbam.py:163-164) while the loss keeps reading the logits -- one launch more each way for all
-levels, the noise drawn in the kernel (include/mgagate.h)."""
+levels, the noise drawn in the kernel (include/mgagate.h).
+
+``SlicePlan.create(..., block="cbam" | "eca" | "spade", channels_last=, target_resize=, block_running=)`` builds the same slice around MaskECA or
+MaskSPADE (configs/models/yolov8_eca.yaml, yolov8_spade.yaml share the layer loop) and in either feature layout; the constructor itself keeps its
+arguments and builds the MaskCBAM / NCHW slice."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,8 +32,10 @@ import torch
 from . import _lib
 from ._binding import fill_head_bwd, fill_head_fwd, fill_seg
 from .functional import BlockConfig, GateConfig
-from .plan import PyramidPlan
+from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan
 
+BLOCKS = ("cbam", "eca", "spade")
+TARGET_RESIZE = {"nearest": _lib.SEG_NEAREST, "bilinear": _lib.SEG_BILINEAR}
 HEAD_PARAM_NAMES = ("proj.0.weight", "proj.1.weight", "proj.1.bias", "head.weight", "head.bias")
 
 
@@ -48,14 +54,50 @@ class SlicePlan:
         163-164: what MGA_PROB_MODE, set in every shipped hyper-parameter file, builds).  The heads then write `logits`, which the loss reads
         as before; the gate (plan.PyramidPlan, one launch each way) fills MaskCBAM's mask from them and turns its dL/dmask into the second
         dL/dlogits of the head's backward.  Its noise is the in-kernel Philox stream of include/mgagate.h, seeded with `seed`."""
+        self._setup(shapes, hidden, cbam_params, cbam_cfgs, head_states, target_hw, scale_weights, bn_eps, bn_momentum, device, training, dtype,
+                    gate, seed, "cbam", False, "nearest", None)
+
+    @classmethod
+    def create(cls, shapes, hidden, block_params, block_cfgs, head_states, *, block: str = "cbam", channels_last: bool = False,
+               target_resize: str = "nearest", block_running=None, **kw) -> "SlicePlan":
+        """The constructor for every model file of the reference (yolov8_cbam / _eca / _spade.yaml share this slice) and both feature layouts;
+        the constructor's own argument list is what every caller passes today and stays as it is.
+        block: "cbam" | "eca" | "spade" -- block_params / block_cfgs are then per level (w1,b1,w2,b2,wsa,beta) with BlockConfig,
+        (conv1d.weight, beta) with EcaConfig, or the six MaskSPADE tensors with SpadeConfig; block_running: per level MaskSPADE's batch-norm
+        buffers (running_mean, running_var, num_batches_tracked) or None.  The matching pyramid plan is ``plan.block`` (``plan.cbam`` as well
+        for "cbam"); the bucket is [block grads of all levels][head grads of all levels][log_vars].
+        channels_last: x / y / gy / gx in torch.channels_last, the block's and the heads' channels-last kernels (what tools/harness.py trains in).
+        target_resize: "nearest" | "bilinear" -- how targets at another size are read (losses/segmentation.py:103-110: bilinear is what an
+        MGA_PROB_MODE run does).  gate: MaskCBAM only (the reference builds a ProbMaskGater nowhere else): ValueError otherwise.
+        **kw: the constructor's keyword arguments (target_hw, scale_weights, bn_eps, bn_momentum, device, training, dtype, gate, seed)."""
+        self = cls.__new__(cls)
+        args = dict(target_hw=None, scale_weights=(1.0, 1.0, 1.0), bn_eps=1e-3, bn_momentum=0.03, device="cuda", training=True,
+                    dtype=torch.float32, gate=None, seed=0)
+        unknown = set(kw) - set(args)
+        if unknown:
+            raise TypeError(f"SlicePlan.create: unexpected arguments {sorted(unknown)}")
+        args.update(kw)
+        self._setup(shapes, hidden, block_params, block_cfgs, head_states, block=block, channels_last=channels_last,
+                    target_resize=target_resize, block_running=block_running, **args)
+        return self
+
+    def _setup(self, shapes, hidden, block_params, block_cfgs, head_states, target_hw, scale_weights, bn_eps, bn_momentum, device, training,
+               dtype, gate, seed, block, channels_last, target_resize, block_running) -> None:
+        if block not in BLOCKS:
+            raise ValueError(f"SlicePlan: block {block!r} is none of {BLOCKS}")
+        if target_resize not in TARGET_RESIZE:
+            raise ValueError(f"SlicePlan: target_resize {target_resize!r} is none of {sorted(TARGET_RESIZE)}")
+        if gate is not None and block != "cbam":
+            raise ValueError(f"SlicePlan: gate= with block={block!r} (the reference builds a ProbMaskGater inside MaskCBAM only)")
         self.lib = _lib.load()
         self.device = torch.device(device)
         dev = self.device
         self.n = len(shapes)
         self.shapes, self.hidden = list(shapes), list(hidden)
+        self.block_name, self.channels_last, self.target_resize = block, bool(channels_last), target_resize
         f32 = torch.float32
-        # ---- one flat gradient bucket: [cbam grads of all levels][head grads of all levels][log_vars] ---------------------------------
-        n_cbam = sum(p.numel() for ps in cbam_params for p in ps)
+        # ---- one flat gradient bucket: [block grads of all levels][head grads of all levels][log_vars] --------------------------------
+        n_block = sum(p.numel() for ps in block_params for p in ps)
         self.head_params: List[List[torch.Tensor]] = []
         self.head_buffers: List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = []
         for sd in head_states:
@@ -63,15 +105,22 @@ class SlicePlan:
             self.head_buffers.append((sd["proj.1.running_mean"].detach().to(dev, f32).clone(), sd["proj.1.running_var"].detach().to(dev, f32).clone(),
                                       sd["proj.1.num_batches_tracked"].detach().to(dev).clone()))
         n_head = sum(p.numel() for ps in self.head_params for p in ps)
-        self.grad_bucket = torch.zeros(n_cbam + n_head + 2, dtype=f32, device=dev)
+        self.grad_bucket = torch.zeros(n_block + n_head + 2, dtype=f32, device=dev)
         self.dtype = dtype
-        self.cbam = PyramidPlan(shapes, cbam_params, cbam_cfgs, dtype=dtype, device=dev, with_mask=True, want_gmask=True,
-                                grad_bucket=self.grad_bucket[:n_cbam], gate=gate, seed=seed)
+        common = dict(dtype=dtype, device=dev, with_mask=True, want_gmask=True, grad_bucket=self.grad_bucket[:n_block])
+        if block == "cbam":
+            self.block = PyramidPlan.create(shapes, block_params, block_cfgs, channels_last=channels_last, gate=gate, seed=seed, **common)
+            self.cbam = self.block
+        elif block == "eca":
+            self.block = EcaPyramidPlan.create(shapes, block_params, block_cfgs, channels_last=channels_last, **common)
+        else:
+            self.block = SpadePyramidPlan(shapes, block_params, block_cfgs, channels_last=channels_last, running=block_running, **common)
+        blk = self.block
         self.gated = gate is not None
-        # without a gate the heads write straight into MaskCBAM's mask input; with one, into the gate's input
-        self.x, self.logits, self.y, self.gy, self.gx = self.cbam.x, (self.cbam.logits if self.gated else self.cbam.mask), self.cbam.y, self.cbam.gy, self.cbam.gx
-        g_logits2 = self.cbam.glogits if self.gated else self.cbam.gmask
-        off = n_cbam
+        # without a gate the heads write straight into the block's mask input; with one, into the gate's input
+        self.x, self.logits, self.y, self.gy, self.gx = blk.x, (blk.logits if self.gated else blk.mask), blk.y, blk.gy, blk.gx
+        g_logits2 = blk.glogits if self.gated else blk.gmask
+        off = n_block
         self.head_grads: List[List[torch.Tensor]] = []
         for ps in self.head_params:
             views = []
@@ -93,22 +142,24 @@ class SlicePlan:
         self.seg_out = torch.zeros(1 + 3 * self.n, dtype=f32, device=dev)
         self._seg = (_lib.SegLevel * self.n)()
         for l in range(self.n):
-            fill_seg(self._seg[l], self.logits[l], self.targets[l], self.seg_glogits[l], float(scale_weights[l]), _lib.SEG_NEAREST)
+            fill_seg(self._seg[l], self.logits[l], self.targets[l], self.seg_glogits[l], float(scale_weights[l]), TARGET_RESIZE[target_resize])
         self._seg_cfg = _lib.SegCfg(1.0, 1.0, 1.0, 1.0, 0, 0.5, 0.6, 0.5)      # SegLossConfig defaults (losses/segmentation.py:9-21)
         self.seg_ws = torch.zeros(_lib.seg_ws_bytes(self._seg, self.n), dtype=torch.uint8, device=dev)
         # ---- mask heads -------------------------------------------------------------------------------------------------------------
         self._hf, self._hb = (_lib.HeadFwdLevel * self.n)(), (_lib.HeadBwdLevel * self.n)()
         self.head_ctx, self.head_scratch = [], []
+        hfl = _lib.HEAD_LAYOUT_NHWC if self.channels_last else 0        # x, gx channels_last: the NHWC forms of the heads' GEMM kernels
         for l, (B, Cc, H, W) in enumerate(shapes):
             bn = (self.hidden[l], bn_eps, bn_momentum, training)
-            self.head_ctx.append(torch.zeros(_lib.head_ctx_bytes(B, Cc, H, W, self.hidden[l]), dtype=torch.uint8, device=dev))
-            self.head_scratch.append(torch.zeros(_lib.head_scratch_bytes(B, Cc, H, W, self.hidden[l]), dtype=torch.uint8, device=dev))
+            self.head_ctx.append(torch.zeros(_lib.head_ctx_bytes(B, Cc, H, W, self.hidden[l], hfl), dtype=torch.uint8, device=dev))
+            self.head_scratch.append(torch.zeros(_lib.head_scratch_bytes(B, Cc, H, W, self.hidden[l], hfl), dtype=torch.uint8, device=dev))
             fill_head_fwd(self._hf[l], self.x[l], self.logits[l], self.head_ctx[l], self.head_params[l], self.head_buffers[l], *bn,
-                          _lib.HEAD_LOGITS_F32)
-            # dL/dlogits = the loss's part (seg_glogits) + MaskCBAM's dL/dmask, through the gate's backward when there is one (g_logits2):
+                          hfl | _lib.HEAD_LOGITS_F32)
+            # dL/dlogits = the loss's part (seg_glogits) + the block's dL/dmask, through the gate's backward when there is one (g_logits2):
             # summed while the head's backward loads them
             fill_head_bwd(self._hb[l], self.x[l], self.seg_glogits[l], g_logits2[l], self.head_ctx[l], self.head_scratch[l], self.gx[l],
-                          self.head_grads[l], self.head_params[l], self.head_buffers[l], *bn, _lib.HEAD_BWD_ACCUM_GX | _lib.HEAD_LOGITS_F32)
+                          self.head_grads[l], self.head_params[l], self.head_buffers[l], *bn,
+                          hfl | _lib.HEAD_BWD_ACCUM_GX | _lib.HEAD_LOGITS_F32)
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -117,7 +168,7 @@ class SlicePlan:
     def forward(self):
         st = self._stream()
         _lib.check(self.lib.mgahead_forward(self._hf, self.n, st), "mgahead_forward")                 # features -> mask logits
-        self.cbam.forward()                                                                            # [feature, logits] -> refined (a gate first: logits -> mask)
+        self.block.forward()                                                                           # [feature, logits] -> refined (a gate first: logits -> mask)
         # logits, targets -> seg_total (+ log entries) -> Kendall total, the combine riding in the loss's last launch
         _lib.check(self.lib.mgaseg_kendall_forward(self._seg, self.n, C.byref(self._seg_cfg), self.seg_ws.data_ptr(), self.seg_ws.numel(), self.seg_out.data_ptr(),
                                                    self.det_loss.data_ptr(), 3, self.log_vars.data_ptr(), self.total.data_ptr(), st),
@@ -129,7 +180,7 @@ class SlicePlan:
                                                     self.det_loss.data_ptr(), 3, self.log_vars.data_ptr(), self.g_total.data_ptr(),
                                                     self.g_det.data_ptr(), self.g_seg.data_ptr(), self.g_log_vars.data_ptr(), st),
                    "mgaseg_kendall_backward")                                                          # -> seg_glogits, g_det, g_log_vars
-        self.cbam.backward()                                                                           # gy -> gx (MaskCBAM's part), dL/dmask (its part of dL/dlogits; a gate's backward last)
+        self.block.backward()                                                                          # gy -> gx (MaskCBAM's part), dL/dmask (its part of dL/dlogits; a gate's backward last)
         _lib.check(self.lib.mgahead_backward(self._hb, self.n, st), "mgahead_backward")                # gx += head's part; head parameter gradients
 
     def step(self):
@@ -139,12 +190,19 @@ class SlicePlan:
     capture = PyramidPlan.capture
 
     def check_handoff(self):
-        self.cbam.check_handoff()
+        if self.block_name == "cbam":                                  # the other blocks have no in-launch hand-off
+            self.block.check_handoff()
 
     def images(self) -> int:
         return self.shapes[0][0]
 
     def launches(self) -> dict:
+        if self.block_name == "cbam" and not self.channels_last:
+            g = " + 1 (gate)" if self.gated else ""
+            return dict(forward=f"3 (heads){g} + 2 (MaskCBAM) + 2 (seg loss + Kendall)",
+                        backward=f"1 (seg loss + Kendall) + 2 (MaskCBAM){g} + 5 (heads)")
+        name = dict(cbam="MaskCBAM", eca="MaskECA", spade="MaskSPADE")[self.block_name]
         g = " + 1 (gate)" if self.gated else ""
-        return dict(forward=f"3 (heads){g} + 2 (MaskCBAM) + 2 (seg loss + Kendall)",
-                    backward=f"1 (seg loss + Kendall) + 2 (MaskCBAM){g} + 5 (heads)")
+        fwd, bwd = self.block.launch_counts()                          # what the block's library calls enqueue (plan.py)
+        return dict(forward=f"3 (heads){g} + {fwd} ({name}) + 2 (seg loss + Kendall)",
+                    backward=f"1 (seg loss + Kendall) + {bwd} ({name}){g} + 5 (heads)")
