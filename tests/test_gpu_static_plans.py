@@ -15,6 +15,7 @@ import torch.nn.functional as F
 from conftest import rel_err
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import plan_replays as R  # noqa: E402
 import spade_plan as P  # noqa: E402
 from test_gpu_spade import dev, live_case  # noqa: E402,F401  (dev: the module's device fixture)
 
@@ -291,35 +292,7 @@ def test_cbam_plan_channels_last_equals_the_autograd_call_bit_for_bit(built_lib,
 # ------------------------------------------------------------------------------------------------------------------------------------
 # 4. SlicePlan.create(block=, channels_last=) == the module composition
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _build(block, shapes, hidden, seed=0):
-    from mga_yolo_amd import MGAMaskHead, MaskCBAM, MaskECA, MaskSPADE
-    heads, blocks = [], []
-    for l, ((B, C_, H, W), hid) in enumerate(zip(shapes, hidden)):
-        torch.manual_seed(seed + l)
-        h = MGAMaskHead(C_, hid)
-        h.proj[1].eps, h.proj[1].momentum = 1e-3, 0.03
-        torch.manual_seed(seed + 10 + l)
-        if block == "cbam":
-            b = MaskCBAM(C_)
-        elif block == "eca":
-            b = MaskECA(C_)
-        else:
-            b = MaskSPADE(C_, hidden=hid, norm_type="bn" if l == 1 else "in")      # the middle level: batch norm, in training
-        if block != "spade":
-            with torch.no_grad():
-                b.beta.fill_(0.2 * (l - 1))
-        heads.append(h.cuda().train()); blocks.append(b.cuda().train())
-    return heads, blocks
-
-
-def _block_args(block, blocks):
-    """-> (per-level parameters as the plan takes them, configs, running buffers | None)"""
-    if block == "cbam":
-        return [b.block_params() for b in blocks], [b.block_config() for b in blocks], None
-    if block == "eca":
-        return [(b.conv1d.weight, b.beta) for b in blocks], [b.eca_config() for b in blocks], None
-    running = [(b.norm.running_mean, b.norm.running_var, b.norm.num_batches_tracked) if b.spade_config().bn else None for b in blocks]
-    return [b.spade_params() for b in blocks], [b.spade_config() for b in blocks], running
+_build, _block_args = R.build_modules, R.block_args     # the module-side reference lives in tests/plan_replays.py, shared with test_gpu_plan_replays.py
 
 
 def _make_slice(block, cl, shapes, hidden, heads, blocks, **kw):
@@ -347,8 +320,7 @@ SLICE_ROWS = [
 
 @pytest.mark.parametrize("shapes,hidden,target_hw,resize", SLICE_ROWS, ids=["p3p4p5", "two-levels-bilinear"])
 @pytest.mark.parametrize("block,cl", COMBOS, ids=[f"{b}-{'channels_last' if c else 'nchw'}" for b, c in COMBOS])
-def test_slice_plan_equals_the_module_composition(built_lib, monkeypatch, block, cl, shapes, hidden, target_hw, resize):
-    from mga_yolo_amd import SegLossConfig, SegmentationLoss, kendall_combine
+def test_slice_plan_equals_the_module_composition(built_lib, block, cl, shapes, hidden, target_hw, resize):
     from mga_yolo_amd.slice import HEAD_PARAM_NAMES
     heads, blocks = _build(block, shapes, hidden)
     plan = _make_slice(block, cl, shapes, hidden, heads, blocks, target_hw=target_hw, target_resize=resize)
@@ -373,18 +345,8 @@ def test_slice_plan_equals_the_module_composition(built_lib, monkeypatch, block,
     # ---- the same slice through the modules + autograd --------------------------------------------------------------------------------
     for h in heads:
         h.proj[1].reset_running_stats()
-    xl = [x.clone(memory_format=torch.preserve_format).requires_grad_(True) for x in xs]
-    lvl = lv.clone().requires_grad_(True)
-    logits = [h(x) for h, x in zip(heads, xl)]
-    ys = [b([x, m]) for b, x, m in zip(blocks, xl, logits)]
-    crit = SegmentationLoss(SegLossConfig(scale_weights=(1.0, 0.5, 2.0)))
-    with monkeypatch.context() as mp:
-        if resize == "bilinear":
-            mp.setenv("MGA_PROB_MODE", "1")                                # the loss reads targets of another size bilinearly (segmentation.py:103-108)
-        seg_total, logs = crit({k: m for k, m in zip(("p3", "p4", "p5"), logits)}, tgs)
-    total = kendall_combine(det, seg_total, lvl)
-    torch.autograd.backward([total.sum()] + ys, [None] + gys)
-    torch.cuda.synchronize()
+    c = R.module_composition(heads, blocks, xs, gys, tgs, det, lv, resize)     # (sets MGA_PROB_MODE for the bilinear row's loss)
+    xl, lvl, logits, ys, total, logs = c.xl, c.lvl, c.logits, c.ys, c.total, c.logs
     assert rel_err(plan.total, total) < 1e-6 and abs(float(plan.seg_out[0]) - logs["seg_total"]) < 1e-5
     assert rel_err(plan.g_log_vars, lvl.grad) < 1e-5
     params, _, running = _block_args(block, blocks)
