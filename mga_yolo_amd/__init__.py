@@ -15,8 +15,9 @@ from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan  # noqa: F401
 from .slice import SlicePlan  # noqa: F401
 from .module import MGAMaskHead, MaskCBAM, MaskECA, MaskSPADE, MaskSPADEConfig, ProbMaskGater  # noqa: F401
 from .segloss import SegLossConfig, SegmentationLoss, kendall_combine  # noqa: F401
+from .optim import BucketOptimizer, OptConfig  # noqa: F401
 
 __all__ = ["MaskCBAM", "MaskECA", "MaskSPADE", "MaskSPADEConfig", "SpadeConfig", "mask_spade", "mask_spade_pyramid", "MGAMaskHead", "mask_head", "mask_head_pyramid", "ProbMaskGater", "BlockConfig", "EcaConfig", "mask_cbam", "mask_cbam_pyramid", "mask_eca",
            "mask_eca_pyramid", "prob_mask_gate", "prob_mask_gate_pyramid", "GateConfig", "gate_state", "resize_nearest", "install", "uninstall", "SegLossConfig", "SegmentationLoss", "kendall_combine", "HandoffTimeout", "handoff_report",
-           "PyramidPlan", "EcaPyramidPlan", "SpadePyramidPlan", "SlicePlan"]
+           "PyramidPlan", "EcaPyramidPlan", "SpadePyramidPlan", "SlicePlan", "BucketOptimizer", "OptConfig"]
 __version__ = "0.1.0"

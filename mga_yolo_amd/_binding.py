@@ -177,3 +177,11 @@ def fill_gate(L: _lib.GateLevel, p, out, msoft, gout, gp, mode: int, stream_id: 
     L.p, L.out, L.msoft, L.gout, L.gp = p.data_ptr(), _ptr(out), _ptr(msoft), _ptr(gout), _ptr(gp)
     L.n, L.mode, L.stream_id = p.numel(), int(mode), int(stream_id)
     L.tau, L.p_min, L.threshold = float(tau), float(p_min), float(threshold)
+
+
+# ---- the fused optimizer step (include/mgaopt.h)
+def fill_opt_segment(S: _lib.OptSegment, param, grad, state0, state1, ema, group: int) -> None:
+    """param: the fp32 tensor updated in place; grad: its gradient (a view into the bucket or the accumulator), None for an EMA-only segment;
+    state0 / state1: SGD's momentum buffer / AdamW's exp_avg, exp_avg_sq; ema: the average or None; group: 0 biases, 1 decayed, 2 norm weights."""
+    S.param, S.grad, S.state0, S.state1, S.ema = param.data_ptr(), _ptr(grad), _ptr(state0), _ptr(state1), _ptr(ema)
+    S.n, S.group, S.reserved = param.numel(), int(group), 0

@@ -202,6 +202,37 @@ RESAMPLE_SYMBOLS = {
     "mgaspade_resample_backward": (C.c_int, [C.POINTER(ResampleLevel), C.c_int, C.c_void_p]),
 }
 
+# the fused optimizer step over the plans' gradient bucket (include/mgaopt.h: a header of its own as well)
+OPT_SGD, OPT_ADAMW = 0, 1
+OPT_KINDS = dict(sgd=OPT_SGD, adamw=OPT_ADAMW)
+OPT_GROUPS, OPT_MAX_SEGMENTS, OPT_CHUNK = 3, 4096, 1024
+
+
+class OptSegment(C.Structure):                   # mgaopt_segment_t
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state0", C.c_void_p), ("state1", C.c_void_p), ("ema", C.c_void_p),
+                ("n", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptCfg(C.Structure):                       # mgaopt_cfg_t
+    _fields_ = [("kind", C.c_int32), ("check_finite", C.c_int32), ("zero_grad", C.c_int32), ("reserved", C.c_int32),
+                ("beta2", C.c_double), ("eps", C.c_double), ("max_norm", C.c_double), ("ema_decay", C.c_double), ("ema_tau", C.c_double)]
+
+
+class OptHyper(C.Structure):                     # mgaopt_hyper_t: device memory; the mirror gives optim.py the word offsets
+    _fields_ = ([(n, C.c_float * OPT_GROUPS) for n in ("lr", "momentum", "one_minus_momentum", "ln_momentum", "weight_decay")] +
+                [("inv_scale", C.c_float), ("ext_sumsq", C.c_float), ("ext_found_inf", C.c_int32), ("updates", C.c_int32),
+                 ("t", C.c_int32 * 2), ("grad_norm", C.c_float), ("clip_coef", C.c_float), ("found_inf", C.c_int32),
+                 ("reserved", C.c_int32 * 8)])
+
+
+# every symbol include/mgaopt.h declares
+OPT_SYMBOLS = {
+    "mgaopt_ws_bytes": (C.c_size_t, [C.POINTER(OptSegment), C.c_int]),
+    "mgaopt_ws_init": (C.c_int, [C.POINTER(OptSegment), C.c_int, C.c_void_p, C.c_size_t]),
+    "mgaopt_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mgaopt_step": (C.c_int, [C.POINTER(OptSegment), C.c_int, C.POINTER(OptCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -224,7 +255,7 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS, **OPT_SYMBOLS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
