@@ -39,18 +39,30 @@ static size_t eca_gg_bytes(int B, int C) { return align16(static_cast<size_t>(B)
 static size_t eca_scratch_need(int B, int C, int H, int W, bool nhwc, int vec) {
   return eca_gg_bytes(B, C) + (nhwc ? eca_nhwc_scratch_tail(B, C, H, W, vec) : 0);
 }
+// An NCHW level's backward (k_eca_bwd) keeps 3 floats per channel and 256 * vec combine floats in dynamic LDS beside its static red[]; a
+// workgroup may ask for 64 KB in all.  kEcaNchwMaxC is the widest C that fits at vec 4 (the larger request), and the limit of every
+// NCHW level whatever its vec: the forward refuses what the backward could not launch, and the size queries answer 0.
+constexpr size_t kLdsPerWorkgroup = 64 * 1024;
+constexpr size_t eca_bwd_smem(int C, int vec) { return (3 * static_cast<size_t>(C) + kBlock * vec) * sizeof(float); }
+constexpr size_t eca_bwd_lds(int C, int vec) { return eca_bwd_smem(C, vec) + kEcaBwdRed * sizeof(float); }
+constexpr int kEcaNchwMaxC = static_cast<int>((kLdsPerWorkgroup - eca_bwd_lds(0, 4)) / (eca_bwd_smem(1, 4) - eca_bwd_smem(0, 4)));
+static_assert(eca_bwd_lds(kEcaNchwMaxC, 4) <= kLdsPerWorkgroup && eca_bwd_lds(kEcaNchwMaxC + 1, 4) > kLdsPerWorkgroup, "kEcaNchwMaxC");
+static_assert(kEcaNchwMaxC >= kEcaNhwcMaxC, "a channels_last feature wider than kEcaNhwcMaxC is copied to NCHW");
 static int eca_check_flags(const char* what, int flags, int C) {
   if (flags & ~MGACBAM_LAYOUT_NHWC) return fail(MGACBAM_E_SHAPE, "%s: unknown flag bits 0x%x (MGACBAM_LAYOUT_NHWC is the only one)", what, flags);
   if ((flags & MGACBAM_LAYOUT_NHWC) && C > kEcaNhwcMaxC)
     return fail(MGACBAM_E_SHAPE, "%s: a channels-last level takes C <= %d, got C=%d", what, kEcaNhwcMaxC, C);
+  if (!(flags & MGACBAM_LAYOUT_NHWC) && C > kEcaNchwMaxC)
+    return fail(MGACBAM_E_SHAPE, "%s: an NCHW level takes C <= %d (its backward keeps 3 floats per channel in the %zu bytes of LDS a workgroup "
+                "may ask for), got C=%d", what, kEcaNchwMaxC, kLdsPerWorkgroup, C);
   return 0;
 }
 extern "C" size_t mgacbam_eca_ctx_bytes(int B, int C, int H, int W) {
-  if (check_shape(B, C, H, W, 1, 3)) return 0;
+  if (check_shape(B, C, H, W, 1, 3) || eca_check_flags("mgacbam_eca_ctx_bytes", 0, C)) return 0;
   return eca_ctx_layout(B, C, H, W).total;
 }
 extern "C" size_t mgacbam_eca_scratch_bytes(int B, int C, int H, int W) {
-  if (check_shape(B, C, H, W, 1, 3)) return 0;
+  if (check_shape(B, C, H, W, 1, 3) || eca_check_flags("mgacbam_eca_scratch_bytes", 0, C)) return 0;
   return eca_gg_bytes(B, C);
 }
 // the layout-aware queries take no element type: the answer covers every one (fp32 and fp16 / bf16 chunk differently)
@@ -127,7 +139,6 @@ static int eca_level(const char* what, const Level& L, N& out, Sig& sig) {
 }
 
 static size_t eca_apply_nhwc_smem(const Geo& g) { return static_cast<size_t>(g.C) * sizeof(float); }
-static size_t eca_bwd_smem(const Geo& g, int vec) { return (3 * static_cast<size_t>(g.C) + kBlock * vec) * sizeof(float); }
 static size_t eca_bwd_nhwc_smem(const Geo& g) {
   return (((static_cast<size_t>(g.C) + 1) & ~static_cast<size_t>(1)) + 2 * static_cast<size_t>(g.C)) * sizeof(float);
 }
@@ -176,7 +187,7 @@ static int eca_backward_group(EcaBwdArgs* lv, int n, const Sig& sig, hipStream_t
   auto bwd = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) {
     return with_bool(sig.gmask, [&](auto gm) { return k_eca_bwd<elem_t<decltype(t)>, v.value, gm.value>; }); });
   return launch_group("k_eca_bwd", bwd, G, [](const EcaBwdArgs& a) { return kEcaRoles + xcd_grid(a.g.B, a.nt); },
-                      [&](const EcaBwdArgs& a) { return eca_bwd_smem(a.g, sig.vec); }, st);
+                      [&](const EcaBwdArgs& a) { return eca_bwd_smem(a.g.C, sig.vec); }, st);
 }
 
 // channels-last levels: k_eca_reduce_nhwc, k_eca_fold, k_eca_bwd_nhwc (+ the layout-free role workgroups)

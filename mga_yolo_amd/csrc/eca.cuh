@@ -225,6 +225,7 @@ __global__ __launch_bounds__(kBlock) void k_eca_reduce(const Group<EcaBwdArgs> G
 // the tail of the launch: 79 us):  r < k: dW1d[r] = sum_{b,c} gy1[b,c] * avg[b, c+r-pad]   r == 15: dbeta = sigmoid(beta) *
 // sum_{b,c} gg*(w-0.5).  Fixed summation order => reproducible.
 constexpr int kEcaRoles = 16;
+constexpr int kEcaBwdRed = 8;         // k_eca_bwd's static LDS floats (block_sum's per-wave slots + K_b); api_eca.hip counts them in kEcaNchwMaxC
 __device__ __forceinline__ void eca_params_body(const EcaBwdArgs& A, const int r, float* red) {
   const Geo& g = A.g;
   const int tid = threadIdx.x, k = g.k, pad = k / 2, BC = g.B * g.C;
@@ -254,7 +255,7 @@ __device__ __forceinline__ void eca_params_body(const EcaBwdArgs& A, const int r
 template <typename T, int VEC, bool GMASK>
 __global__ __launch_bounds__(kBlock) void k_eca_bwd(const Group<EcaBwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
-  __shared__ float red[8];
+  __shared__ float red[kEcaBwdRed];
   int bid;
   const int l = find_level(G, blockIdx.x, bid);
   const EcaBwdArgs& A = G.lv[l];

@@ -428,7 +428,8 @@ class _EcaFn(torch.autograd.Function):
 def mask_eca(x: torch.Tensor, mask: Optional[torch.Tensor], w: torch.Tensor, beta: torch.Tensor, cfg: EcaConfig) -> torch.Tensor:
     """y = x * (1 + softplus(beta) * (sigmoid(conv1d(masked_avg(x, mask))) - 0.5)) for a device tensor (masked_eca.py:167-196).
     A channels_last x with C <= 4096 is taken as it is (no layout copy); y and dL/dx are then channels_last too.  Any other layout, and a
-    wider channels_last feature, is copied to NCHW once and runs the NCHW kernels, as before."""
+    wider channels_last feature, is copied to NCHW once and runs the NCHW kernels, as before.  The NCHW kernels take C <= 5117 (the
+    backward's LDS, csrc/api_eca.hip: kEcaNchwMaxC); a wider feature raises here, at the forward, with the library's message."""
     return _EcaFn.apply((cfg,), x, mask, w, beta)[0]
 
 
