@@ -75,11 +75,20 @@ class HeadCtx:
     new_running_var: torch.Tensor
 
 
-def forward(x: torch.Tensor, p: HeadParams, training: bool = True) -> Tuple[torch.Tensor, HeadCtx]:
+def forward(x: torch.Tensor, p: HeadParams, training: bool = True, double: bool = False, z: Optional[torch.Tensor] = None,
+            mma_dtype: Optional[torch.dtype] = None):
+    """-> (logits, HeadCtx) in fp32.  double=True: everything in float64 from the given (already rounded) inputs, and a third result,
+    the TERM MAGNITUDE of every element of logits and of the updated running statistics (see _forward_mag).  z: a projection output to
+    go on from instead of W1 x (tests derive wrong results from it).  mma_dtype (fp32 path): W1 rounded to that type in the projection,
+    as a half-precision MFMA takes its operands (x is given in that type already); everything else stays fp32."""
     B, C, H, W = x.shape
     hid = p.w1.shape[0]
-    xf = x.float()
-    z = torch.einsum("jc,bchw->bjhw", p.w1, xf)                                   # segmentation.py:81 (1x1 conv, no bias)
+    if double:
+        p = _p64(p)
+    xf = x.double() if double else x.float()
+    if z is None:
+        w1 = p.w1 if mma_dtype is None else p.w1.to(mma_dtype).float()
+        z = torch.einsum("jc,bchw->bjhw", w1, xf)                                 # segmentation.py:81 (1x1 conv, no bias)
     n = B * H * W
     if training:                                                                  # segmentation.py:83 (BatchNorm2d, batch statistics)
         mean = z.mean(dim=(0, 2, 3))
@@ -95,14 +104,41 @@ def forward(x: torch.Tensor, p: HeadParams, training: bool = True) -> Tuple[torc
     a = zhat * p.gamma.view(1, hid, 1, 1) + p.beta.view(1, hid, 1, 1)
     s = a * torch.sigmoid(a)                                                      # segmentation.py:87 (SiLU)
     logits = F.conv2d(s, p.wh, p.bh, padding=1)                                   # segmentation.py:92
-    return logits, HeadCtx(z, mean, var, rstd, zhat, a, s, new_rm, new_rv)
+    c = HeadCtx(z, mean, var, rstd, zhat, a, s, new_rm, new_rv)
+    return (logits, c, _forward_mag(p, c, training, n)) if double else (logits, c)
 
 
-def backward(g: torch.Tensor, x: torch.Tensor, p: HeadParams, c: HeadCtx, training: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+def _p64(p: HeadParams) -> HeadParams:
+    return HeadParams(*(t.double() for t in (p.w1, p.gamma, p.beta, p.running_mean, p.running_var, p.wh, p.bh)), p.eps, p.momentum)
+
+
+def _forward_mag(p: HeadParams, c: HeadCtx, training: bool, n: int) -> Dict[str, torch.Tensor]:
+    """What each element was summed from, as the fp64 sum of the absolute values of its terms: logits |W_h| (*) |s| + |b_h|; the running
+    statistics (1-m) |old| + m * (sum |z| / n, resp. the unbiased sum (z - mean)^2 / n, all of whose terms are positive)."""
+    mag = dict(logits=F.conv2d(c.s.abs(), p.wh.abs(), p.bh.abs(), padding=1))
+    if training:
+        unb = c.var * (n / (n - 1)) if n > 1 else c.var
+        mag["running_mean"] = (1 - p.momentum) * p.running_mean.abs() + p.momentum * c.z.abs().mean(dim=(0, 2, 3))
+        mag["running_var"] = (1 - p.momentum) * p.running_var.abs() + p.momentum * unb
+    else:
+        mag["running_mean"], mag["running_var"] = p.running_mean.abs(), p.running_var.abs()
+    return mag
+
+
+def backward(g: torch.Tensor, x: torch.Tensor, p: HeadParams, c: HeadCtx, training: bool = True, double: bool = False,
+             mma_dtype: Optional[torch.dtype] = None, mma_gw1: bool = True):
+    """-> the gradients in fp32.  mma_dtype (fp32 path): g_z and W1 rounded to that type as operands of gx (and g_z as operand of gw1 when
+    mma_gw1), as a half-precision MFMA takes them.  double=True (c from forward(double=True)): in float64, with g_z among the results, and as a second
+    result the term magnitude of every element of every gradient:
+        g_z |k| (|g_a| + |gbeta|/n + |zhat| |ggamma|/n)  (eval: |k| |g_a|),   gx |W1|^T mag(g_z),   gw1 sum mag(g_z) |x|,
+        ggamma sum |g_a zhat|,   gbeta sum |g_a|,   gwh sum |g| |s shifted|,   gbh sum |g|."""
     B, C, H, W = x.shape
     hid = p.w1.shape[0]
     n = B * H * W
-    g = g.float()
+    if double:
+        p = _p64(p)
+    g = g.double() if double else g.float()
+    xf = x.double() if double else x.float()
     g_s = F.conv_transpose2d(g, p.wh, padding=1)
     sp = F.pad(c.s, (1, 1, 1, 1))
     gwh = torch.zeros_like(p.wh)
@@ -119,9 +155,38 @@ def backward(g: torch.Tensor, x: torch.Tensor, p: HeadParams, c: HeadCtx, traini
         g_z = k * (g_a - gbeta.view(1, hid, 1, 1) / n - c.zhat * ggamma.view(1, hid, 1, 1) / n)
     else:
         g_z = k * g_a
-    gx = torch.einsum("jc,bjhw->bchw", p.w1, g_z)
-    gw1 = torch.einsum("bjhw,bchw->jc", g_z, x.float())
-    return dict(gx=gx, gw1=gw1, ggamma=ggamma, gbeta=gbeta, gwh=gwh, gbh=gbh)
+    if mma_dtype is None:
+        gx = torch.einsum("jc,bjhw->bchw", p.w1, g_z)
+        gw1 = torch.einsum("bjhw,bchw->jc", g_z, xf)
+    else:
+        g_zr = g_z.to(mma_dtype).float()
+        gx = torch.einsum("jc,bjhw->bchw", p.w1.to(mma_dtype).float(), g_zr)
+        gw1 = torch.einsum("bjhw,bchw->jc", g_zr if mma_gw1 else g_z, xf)
+    out = dict(gx=gx, gw1=gw1, ggamma=ggamma, gbeta=gbeta, gwh=gwh, gbh=gbh)
+    if not double:
+        return out
+    out["g_z"] = g_z
+    m_gz = k.abs() * g_a.abs()
+    if training:
+        m_gz = k.abs() * (g_a.abs() + gbeta.abs().view(1, hid, 1, 1) / n + c.zhat.abs() * ggamma.abs().view(1, hid, 1, 1) / n)
+    m_gwh = torch.zeros_like(p.wh)
+    spa = sp.abs()
+    for u in range(3):
+        for v in range(3):
+            m_gwh[:, :, u, v] = torch.einsum("bohw,bjhw->oj", g.abs(), spa[:, :, u:u + H, v:v + W])
+    mag = dict(g_z=m_gz, gx=torch.einsum("jc,bjhw->bchw", p.w1.abs(), m_gz), gw1=torch.einsum("bjhw,bchw->jc", m_gz, xf.abs()),
+               ggamma=(g_a * c.zhat).abs().sum(dim=(0, 2, 3)), gbeta=g_a.abs().sum(dim=(0, 2, 3)), gwh=m_gwh, gbh=g.abs().sum(dim=(0, 2, 3)))
+    return out, mag
+
+
+def elem_u(got: torch.Tensor, want: torch.Tensor, mag: torch.Tensor, floor: float = 0.0) -> float:
+    """max_i |got_i - want_i| / (mag_i + floor): the error in units of what the element was summed from, so a cancelling element is not
+    held to its own tiny value and a large neighbour does not hide a wrong small one.  An element summed from nothing but zeros must be
+    exact.  floor: the smallest normal number of a half-precision output (below it the format rounds absolutely)."""
+    d = (got.detach().double().cpu().reshape(want.shape) - want.double()).abs()
+    m = mag.double() + floor
+    r = torch.where(m > 0, d / m.clamp_min(1e-300), torch.where(d > 0, torch.full_like(d, float("inf")), torch.zeros_like(d)))
+    return float(r.max())
 
 
 def reference_form_step(x, p: HeadParams, g, training: bool = True):
