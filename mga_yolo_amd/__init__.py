@@ -10,6 +10,7 @@ Layout: ``csrc/`` hand-written HIP kernels + the C ABI of ``include/mgacbam.h``;
 from .functional import BlockConfig, EcaConfig, HandoffTimeout, handoff_report, mask_cbam, mask_cbam_pyramid, mask_eca, mask_eca_pyramid, mask_head, mask_head_pyramid, prob_mask_gate, resize_nearest  # noqa: F401
 from .functional import SpadeConfig, mask_spade, mask_spade_pyramid  # noqa: F401
 from .functional import GateConfig, gate_state, prob_mask_gate_pyramid  # noqa: F401
+from .functional import mask_pyramid  # noqa: F401
 from .install import install, uninstall  # noqa: F401
 from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan  # noqa: F401
 from .slice import SlicePlan  # noqa: F401
@@ -18,6 +19,6 @@ from .segloss import SegLossConfig, SegmentationLoss, kendall_combine  # noqa: F
 from .optim import BucketOptimizer, OptConfig  # noqa: F401
 
 __all__ = ["MaskCBAM", "MaskECA", "MaskSPADE", "MaskSPADEConfig", "SpadeConfig", "mask_spade", "mask_spade_pyramid", "MGAMaskHead", "mask_head", "mask_head_pyramid", "ProbMaskGater", "BlockConfig", "EcaConfig", "mask_cbam", "mask_cbam_pyramid", "mask_eca",
-           "mask_eca_pyramid", "prob_mask_gate", "prob_mask_gate_pyramid", "GateConfig", "gate_state", "resize_nearest", "install", "uninstall", "SegLossConfig", "SegmentationLoss", "kendall_combine", "HandoffTimeout", "handoff_report",
+           "mask_eca_pyramid", "prob_mask_gate", "prob_mask_gate_pyramid", "GateConfig", "gate_state", "resize_nearest", "mask_pyramid", "install", "uninstall", "SegLossConfig", "SegmentationLoss", "kendall_combine", "HandoffTimeout", "handoff_report",
            "PyramidPlan", "EcaPyramidPlan", "SpadePyramidPlan", "SlicePlan", "BucketOptimizer", "OptConfig"]
 __version__ = "0.1.0"

@@ -185,3 +185,21 @@ def fill_opt_segment(S: _lib.OptSegment, param, grad, state0, state1, ema, group
     state0 / state1: SGD's momentum buffer / AdamW's exp_avg, exp_avg_sq; ema: the average or None; group: 0 biases, 1 decayed, 2 norm weights."""
     S.param, S.grad, S.state0, S.state1, S.ema = param.data_ptr(), _ptr(grad), _ptr(state0), _ptr(state1), _ptr(ema)
     S.n, S.group, S.reserved = param.numel(), int(group), 0
+
+
+# ---- the multi-scale segmentation targets (include/mgatargets.h)
+TGT_SRC = {torch.uint8: _lib.TGT_SRC_U8, torch.float32: _lib.TGT_SRC_F32}
+
+
+def fill_targets(D: _lib.TargetsDesc, src, dsts, strides, method: int, flags: int = 0, scratch=None) -> None:
+    """src: (B,H,W) contiguous uint8 or fp32; dsts: per stride the (B,1,ceil(H/s),ceil(W/s)) fp32 tensor that is written; method:
+    _lib.TGT_AVGPOOL | TGT_MAXPOOL; flags: 0 | _lib.TGT_CLOSE3, which needs scratch (uint8, _lib.targets_scratch_bytes of the filled struct:
+    fill once without it to ask, then again with it)."""
+    B, H, W = src.shape
+    D.src = src.data_ptr()
+    for l in range(_lib.TGT_MAX_LEVELS):
+        on = l < len(dsts)
+        D.dst[l], D.stride[l] = (dsts[l].data_ptr(), int(strides[l])) if on else (None, 0)
+    D.n_levels, D.B, D.H, D.W = len(dsts), B, H, W
+    D.src_dtype, D.method, D.flags, D.reserved = TGT_SRC[src.dtype], int(method), int(flags), 0
+    D.scratch, D.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel())

@@ -12,6 +12,7 @@ ABI_VERSION = 15
 MAX_LEVELS = 8
 F32, F16, BF16 = 0, 1, 2
 E_NULL, E_SHAPE, E_DTYPE, E_ALIGN, E_LEVELS, E_SIZE = -1, -2, -3, -4, -5, -6
+E_ARG = -7         # include/mgatargets.h: an argument outside what the entry point takes
 # stage bit masks (include/mgacbam.h)
 FWD_STAGES = dict(pool=1, chan=2, apply=4)
 BWD_STAGES = dict(reduce1=1, convT=2, reduce2=4, wsa=8, params=16, apply=32)
@@ -233,6 +234,27 @@ OPT_SYMBOLS = {
     "mgaopt_step": (C.c_int, [C.POINTER(OptSegment), C.c_int, C.POINTER(OptCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# the multi-scale segmentation targets from full-resolution masks (include/mgatargets.h: a header of its own as well)
+TGT_AVGPOOL, TGT_MAXPOOL = 0, 1
+TGT_METHODS = dict(avgpool=TGT_AVGPOOL, maxpool=TGT_MAXPOOL)
+TGT_SRC_U8, TGT_SRC_F32 = 0, 1
+TGT_CLOSE3 = 1
+TGT_MAX_LEVELS = 4
+
+
+class TargetsDesc(C.Structure):                  # mgatgt_desc_t
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p * TGT_MAX_LEVELS), ("stride", C.c_int32 * TGT_MAX_LEVELS),
+                ("n_levels", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("src_dtype", C.c_int32), ("method", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+# every symbol include/mgatargets.h declares
+TARGETS_SYMBOLS = {
+    "mgatgt_scratch_bytes": (C.c_size_t, [C.POINTER(TargetsDesc)]),
+    "mgatgt_forward": (C.c_int, [C.POINTER(TargetsDesc), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -255,7 +277,7 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS, **OPT_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS, **OPT_SYMBOLS, **TARGETS_SYMBOLS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -356,6 +378,15 @@ def seg_ws_bytes(levels, n: int) -> int:
     nbytes = load().mgaseg_ws_bytes(levels, n)
     if nbytes == 0:
         check(E_SHAPE, "mgaseg_ws_bytes")
+    return nbytes
+
+
+def targets_scratch_bytes(desc) -> int:
+    """Scratch of a target-pyramid call: 0 without TGT_CLOSE3.  0 is also the library's refusal, told apart by its message."""
+    lib = load()
+    nbytes = lib.mgatgt_scratch_bytes(C.byref(desc))
+    if nbytes == 0 and lib.mgacbam_last_error():
+        check(E_ARG, "mgatgt_scratch_bytes")
     return nbytes
 
 

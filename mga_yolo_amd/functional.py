@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._binding import DTYPES as _DTYPES, call as _call, raw_stream as _raw_stream
-from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_gate, fill_head_bwd, fill_head_fwd, fill_spade
+from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_gate, fill_head_bwd, fill_head_fwd, fill_spade, fill_targets
 from ._binding import head_params as _head_params  # noqa: F401  (tests fill head levels by hand with it)
 
 
@@ -455,6 +455,116 @@ def resize_nearest(src: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
     dst = torch.empty(*s.shape[:-2], out_h, out_w, dtype=torch.float32, device=s.device)
     _call("mgacbam_resize_nearest", s.device, s.data_ptr(), dst.data_ptr(), planes, in_h, in_w, out_h, out_w)
     return dst
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The multi-scale segmentation targets (include/mgatargets.h): what the reference's dataset builds per sample on its dataloader workers
+# (mga_yolo/data/dataset.py:94-103) and collate_fn stacks into masks_multi, here from the batch's masks where they lie
+# ---------------------------------------------------------------------------------------------------------
+TARGET_CHAIN = (8, 16, 32)      # the model's strides: every prefix of it reads the source once (k_tgt_pool)
+
+
+def target_pyramid_check(strides, method: str, bridge: bool) -> Tuple[int, ...]:
+    """The argument rules of a target pyramid, the library's own (include/mgatargets.h), raised as ValueError on either device: 1..4
+    strides, powers of two in 2..64, strictly ascending; method 'avgpool' | 'maxpool'; the closing with 'maxpool' only."""
+    strides = tuple(int(s) for s in strides)
+    if not 1 <= len(strides) <= _lib.TGT_MAX_LEVELS:
+        raise ValueError(f"mask_pyramid: {len(strides)} strides (1 .. {_lib.TGT_MAX_LEVELS})")
+    for i, s in enumerate(strides):
+        if s < 2 or s > 64 or s & (s - 1):
+            raise ValueError(f"mask_pyramid: stride {s} is no power of two in 2 .. 64")
+        if i and s <= strides[i - 1]:
+            raise ValueError(f"mask_pyramid: strides {strides} are not strictly ascending")
+    if method not in _lib.TGT_METHODS:
+        raise ValueError(f"mask_pyramid: method {method!r} is none of {sorted(_lib.TGT_METHODS)} ('area' and 'nearest' through cv2, 'pyrdown' "
+                         "and the skeleton path of the reference are not built)")
+    if bridge and method != "maxpool":
+        raise ValueError("mask_pyramid: bridge=True closes binary levels: it goes with method='maxpool' only")
+    return strides
+
+
+def target_pyramid_shapes(B: int, H: int, W: int, strides) -> List[Tuple[int, int, int, int]]:
+    return [(B, 1, -(-H // s), -(-W // s)) for s in strides]
+
+
+class TargetPyramidCall:
+    """One filled mgatgt_desc_t with the scratch it needs: `src` (B,H,W) -> `dsts`, launched by run() on the current stream (one launch,
+    two with the closing).  The static plans keep one (slice.SlicePlan); mask_pyramid builds one per call."""
+
+    def __init__(self, src: torch.Tensor, dsts: Sequence[torch.Tensor], strides, method: str, bridge: bool):
+        self.src, self.dsts = src, list(dsts)                  # kept alive: the descriptor holds their addresses
+        self.launches = 2 if bridge else 1
+        self.desc = _lib.TargetsDesc()
+        a = (src, self.dsts, strides, _lib.TGT_METHODS[method], _lib.TGT_CLOSE3 if bridge else 0)
+        fill_targets(self.desc, *a)
+        self.scratch = None
+        if bridge:
+            self.scratch = torch.empty(_lib.targets_scratch_bytes(self.desc), dtype=torch.uint8, device=src.device)
+            fill_targets(self.desc, *a, scratch=self.scratch)
+
+    def run(self) -> None:
+        _call("mgatgt_forward", self.src.device, C.byref(self.desc))
+
+
+def _mask_pyramid_host(m: torch.Tensor, strides, method: str, bridge: bool) -> List[torch.Tensor]:
+    """The torch composition (any device): binarise, zero-pad, count per block.  The counts are integers, so this is the reference's
+    numpy (a float32 mean of 0/1 over a padded block; a block max) bit for bit."""
+    B, H, W = m.shape
+    fg = (m > 0).to(torch.int32)
+    out = []
+    for s in strides:
+        Hs, Ws = -(-H // s), -(-W // s)
+        cnt = torch.nn.functional.pad(fg, (0, Ws * s - W, 0, Hs * s - H)).view(B, Hs, s, Ws, s).sum(dim=(2, 4))
+        lvl = (cnt > 0).to(torch.float32) if method == "maxpool" else cnt.to(torch.float32) / float(s * s)
+        lvl = lvl.unsqueeze(1)
+        if bridge:                                             # 3x3 dilation, then 3x3 erosion; max_pool2d pads with -inf: outside is ignored
+            mp = torch.nn.functional.max_pool2d
+            lvl = -mp(-mp(lvl, 3, 1, 1), 3, 1, 1)
+        out.append(lvl)
+    return out
+
+
+def mask_pyramid(mask: torch.Tensor, strides=TARGET_CHAIN, method: str = "avgpool", bridge: bool = False,
+                 out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """The segmentation targets of a batch -- what ``masks_multi`` is after the reference's collate_fn: per stride one (B,1,ceil(H/s),ceil(W/s))
+    fp32 tensor -- from its full-resolution masks ``mask``, (B,H,W) or (B,1,H,W), uint8 (or bool) or fp32.  A pixel is foreground iff its value > 0
+    (dataset.py:89 binarises before the call; unlike MaskUtils, uint8 values other than 0 / 1 are binarised too); the mask is zero-padded on
+    the bottom and right to a multiple of each stride.
+    method: 'avgpool' -- the foreground share of every s x s block, MaskUtils.downsample_mask_prob(method='avgpool'): the exact block-mean
+    form of the 'area' targets an MGA_PROB_MODE run trains on; 'maxpool' -- 1 where the block holds a foreground pixel,
+    MaskUtils.downsample_mask with MGA_MASK_METHOD=maxpool.  bridge: with 'maxpool', a 3x3 closing of every level (MGA_MASK_BRIDGE).
+    Both methods are integer counts: the result equals the reference's bit for bit.
+    Device tensors take ONE launch for all levels (two with bridge): include/mgatargets.h; ``out`` = the tensors to write (static buffers),
+    returned as they are.  CPU tensors take a torch composition."""
+    strides = target_pyramid_check(strides, method, bridge)
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)                 # the same bytes: True is 1
+    if mask.dim() != 3 or mask.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"mask_pyramid expects a uint8 or fp32 (B,H,W) or (B,1,H,W) tensor, got {mask.dtype} {tuple(mask.shape)}")
+    B, H, W = mask.shape
+    shapes = target_pyramid_shapes(B, H, W, strides)
+    if out is not None:
+        out = list(out)
+        if len(out) != len(shapes):
+            raise ValueError(f"mask_pyramid: {len(out)} out tensors for {len(shapes)} strides")
+        for o, shp in zip(out, shapes):
+            if tuple(o.shape) != shp or o.dtype != torch.float32 or o.device != mask.device or not o.is_contiguous():
+                raise ValueError(f"mask_pyramid: out tensor {tuple(o.shape)} {o.dtype} on {o.device}: expected contiguous fp32 {shp} on {mask.device}")
+    if not mask.is_cuda:
+        res = _mask_pyramid_host(mask, strides, method, bridge)
+        if out is None:
+            return res
+        for o, r in zip(out, res):
+            o.copy_(r)
+        return out
+    _lib.load()
+    src = mask.detach().contiguous()              # no copy for alignment's sake: the kernel takes an unaligned base through its element loads
+    if out is None:
+        out = [torch.empty(shp, dtype=torch.float32, device=src.device) for shp in shapes]
+    TargetPyramidCall(src, out, strides, method, bridge).run()
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -21,7 +21,11 @@ levels, the noise drawn in the kernel (include/mgagate.h).
 
 ``SlicePlan.create(..., block="cbam" | "eca" | "spade", channels_last=, target_resize=, block_running=)`` builds the same slice around MaskECA or
 MaskSPADE (configs/models/yolov8_eca.yaml, yolov8_spade.yaml share the layer loop) and in either feature layout; the constructor itself keeps its
-arguments and builds the MaskCBAM / NCHW slice."""
+arguments and builds the MaskCBAM / NCHW slice.
+
+``SlicePlan.create(..., target_source=(Hm, Wm), target_method=, target_bridge=)`` makes the targets part of the step: the plan owns
+``mask_full`` (B,Hm,Wm) uint8 -- the batch's masks at image resolution, what the caller fills instead of ``targets`` -- and ``forward`` starts
+with the pyramid launch that writes ``targets`` from it (include/mgatargets.h; mga_yolo/data/dataset.py:94-103 on the device)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -31,12 +35,32 @@ import torch
 
 from . import _lib
 from ._binding import fill_head_bwd, fill_head_fwd, fill_seg
-from .functional import BlockConfig, GateConfig
+from .functional import BlockConfig, GateConfig, TargetPyramidCall, target_pyramid_check, target_pyramid_shapes
 from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan
 
 BLOCKS = ("cbam", "eca", "spade")
 TARGET_RESIZE = {"nearest": _lib.SEG_NEAREST, "bilinear": _lib.SEG_BILINEAR}
 HEAD_PARAM_NAMES = ("proj.0.weight", "proj.1.weight", "proj.1.bias", "head.weight", "head.bias")
+
+
+def target_strides(shapes, target_source) -> Tuple[int, ...]:
+    """Per level the stride that takes a (Hm, Wm) mask to the level's (H, W): the smallest power of two s in 2..64 with ceil(Hm / s) == H and
+    ceil(Wm / s) == W (Hm / H itself where the sizes divide).  ValueError where none does, or the strides do not ascend."""
+    Hm, Wm = (int(v) for v in target_source)
+    if Hm < 1 or Wm < 1:
+        raise ValueError(f"SlicePlan: target_source {target_source}")
+    out = []
+    for (_, _, H, W) in shapes:
+        fit_h = [s for s in (2, 4, 8, 16, 32, 64) if -(-Hm // s) == H]
+        fit_w = [s for s in (2, 4, 8, 16, 32, 64) if -(-Wm // s) == W]
+        fit = [s for s in fit_h if s in fit_w]
+        if not fit:
+            why = "H and W ask for different strides" if fit_h and fit_w else "no power-of-two stride in 2..64 gives that size"
+            raise ValueError(f"SlicePlan: a {Hm}x{Wm} mask and a {H}x{W} level: {why}")
+        out.append(fit[0])
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"SlicePlan: the levels' strides {out} do not ascend")
+    return tuple(out)
 
 
 class SlicePlan:
@@ -69,16 +93,40 @@ class SlicePlan:
         channels_last: x / y / gy / gx in torch.channels_last, the block's and the heads' channels-last kernels (what tools/harness.py trains in).
         target_resize: "nearest" | "bilinear" -- how targets at another size are read (losses/segmentation.py:103-110: bilinear is what an
         MGA_PROB_MODE run does).  gate: MaskCBAM only (the reference builds a ProbMaskGater nowhere else): ValueError otherwise.
-        **kw: the constructor's keyword arguments (target_hw, scale_weights, bn_eps, bn_momentum, device, training, dtype, gate, seed)."""
+        target_source=, target_method=, target_bridge= (keywords taken out of **kw: the named arguments are the ones callers bind by position or
+        inspect).  target_source: (Hm, Wm) of the batch's full-resolution masks.  The plan then owns ``mask_full`` (B,Hm,Wm) uint8 (foreground: > 0), which
+        the caller fills instead of ``targets``; forward() first builds ``targets`` from it -- one launch more, two with target_bridge -- with
+        target_method "avgpool" (MGA_PROB_MODE's block-mean targets) or "maxpool", target_bridge: the 3x3 closing of the binary levels.  Level
+        l's stride is the power of two s in 2..64 with ceil(Hm / s) == H_l and ceil(Wm / s) == W_l (the smallest, should several fit), its
+        target is that size; ValueError if there is none -- the ratio is no such integer, or H and W disagree -- or the strides do not ascend,
+        and if target_hw is passed as well.
+        **kw: those three and the constructor's keyword arguments (target_hw, scale_weights, bn_eps, bn_momentum, device, training, dtype, gate,
+        seed)."""
         self = cls.__new__(cls)
+        target_source, target_method = kw.pop("target_source", None), kw.pop("target_method", "avgpool")
+        target_bridge = kw.pop("target_bridge", False)
         args = dict(target_hw=None, scale_weights=(1.0, 1.0, 1.0), bn_eps=1e-3, bn_momentum=0.03, device="cuda", training=True,
                     dtype=torch.float32, gate=None, seed=0)
         unknown = set(kw) - set(args)
         if unknown:
             raise TypeError(f"SlicePlan.create: unexpected arguments {sorted(unknown)}")
         args.update(kw)
+        strides = None
+        if target_source is not None:                                  # checked on the shapes alone, before anything touches the device
+            if args["target_hw"] is not None:
+                raise ValueError("SlicePlan.create: target_hw is derived from target_source; pass one of the two")
+            strides = target_strides(shapes, target_source)
+            target_pyramid_check(strides, target_method, target_bridge)
+            args["target_hw"] = [shp[2:] for shp in target_pyramid_shapes(1, *target_source, strides)]
+        elif target_bridge or target_method != "avgpool":
+            raise ValueError("SlicePlan.create: target_method / target_bridge without target_source")
         self._setup(shapes, hidden, block_params, block_cfgs, head_states, block=block, channels_last=channels_last,
                     target_resize=target_resize, block_running=block_running, **args)
+        if strides is not None:
+            B = shapes[0][0]
+            self.target_strides, self.target_method, self.target_bridge = strides, target_method, bool(target_bridge)
+            self.mask_full = torch.zeros(B, *target_source, dtype=torch.uint8, device=self.device)
+            self._tgt = TargetPyramidCall(self.mask_full, self.targets, strides, target_method, target_bridge)
         return self
 
     def _setup(self, shapes, hidden, block_params, block_cfgs, head_states, target_hw, scale_weights, bn_eps, bn_momentum, device, training,
@@ -93,6 +141,7 @@ class SlicePlan:
         self.device = torch.device(device)
         dev = self.device
         self.n = len(shapes)
+        self._tgt = None                                               # create(target_source=...): the pyramid call that fills self.targets
         self.shapes, self.hidden = list(shapes), list(hidden)
         self.block_name, self.channels_last, self.target_resize = block, bool(channels_last), target_resize
         f32 = torch.float32
@@ -167,6 +216,8 @@ class SlicePlan:
 
     def forward(self):
         st = self._stream()
+        if self._tgt is not None:
+            self._tgt.run()                                                                            # mask_full -> targets
         _lib.check(self.lib.mgahead_forward(self._hf, self.n, st), "mgahead_forward")                 # features -> mask logits
         self.block.forward()                                                                           # [feature, logits] -> refined (a gate first: logits -> mask)
         # logits, targets -> seg_total (+ log entries) -> Kendall total, the combine riding in the loss's last launch
@@ -197,12 +248,13 @@ class SlicePlan:
         return self.shapes[0][0]
 
     def launches(self) -> dict:
+        t = "" if self._tgt is None else f"{self._tgt.launches} (targets) + "
         if self.block_name == "cbam" and not self.channels_last:
             g = " + 1 (gate)" if self.gated else ""
-            return dict(forward=f"3 (heads){g} + 2 (MaskCBAM) + 2 (seg loss + Kendall)",
+            return dict(forward=f"{t}3 (heads){g} + 2 (MaskCBAM) + 2 (seg loss + Kendall)",
                         backward=f"1 (seg loss + Kendall) + 2 (MaskCBAM){g} + 5 (heads)")
         name = dict(cbam="MaskCBAM", eca="MaskECA", spade="MaskSPADE")[self.block_name]
         g = " + 1 (gate)" if self.gated else ""
         fwd, bwd = self.block.launch_counts()                          # what the block's library calls enqueue (plan.py)
-        return dict(forward=f"3 (heads){g} + {fwd} ({name}) + 2 (seg loss + Kendall)",
+        return dict(forward=f"{t}3 (heads){g} + {fwd} ({name}) + 2 (seg loss + Kendall)",
                     backward=f"1 (seg loss + Kendall) + {bwd} ({name}){g} + 5 (heads)")
