@@ -203,3 +203,27 @@ def fill_targets(D: _lib.TargetsDesc, src, dsts, strides, method: int, flags: in
     D.n_levels, D.B, D.H, D.W = len(dsts), B, H, W
     D.src_dtype, D.method, D.flags, D.reserved = TGT_SRC[src.dtype], int(method), int(flags), 0
     D.scratch, D.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel())
+
+
+# ---- the detection criterion (include/mgadet.h): one struct for both directions
+def fill_det(D: _lib.DetDesc, feats, strides, nc: int, topk: int, m_cap: int, gains, batch_idx, cls, bboxes, n, assign_gt, assign_score,
+             out, items, status, ws=None, g_feats=None, upstream=None) -> None:
+    """feats: the Detect maps (B, 64 + nc, H_l, W_l), NCHW contiguous, one element type; batch_idx / cls (n_cap) and bboxes (n_cap, 4)
+    fp32; n: the int32 device word of live rows or None (= n_cap); assign_gt int32 / assign_score fp32 (B, A), out / items fp32 (3) and
+    status int32 (1) are written by the forward.  The backward passes g_feats and upstream (3, fp32) as well, and the forward's ws
+    (uint8, _lib.det_ws_bytes of the filled struct: fill once without it to ask, then again with it)."""
+    for l in range(_lib.DET_MAX_LEVELS):
+        on = l < len(feats)
+        D.feats[l] = feats[l].data_ptr() if on else None
+        D.g_feats[l] = g_feats[l].data_ptr() if on and g_feats is not None else None
+        D.H[l], D.W[l], D.stride[l] = (feats[l].shape[2], feats[l].shape[3], int(strides[l])) if on else (0, 0, 0)
+    D.n_levels, D.B, D.nc, D.reg_max = len(feats), feats[0].shape[0], int(nc), _lib.DET_REG_MAX
+    D.dtype, D.topk, D.n_cap, D.m_cap = DTYPES[feats[0].dtype], int(topk), batch_idx.shape[0], int(m_cap)
+    D.gains[0], D.gains[1], D.gains[2] = (float(g) for g in gains)
+    D.reserved = 0
+    has = batch_idx.shape[0] > 0
+    D.batch_idx, D.cls, D.bboxes = (batch_idx.data_ptr(), cls.data_ptr(), bboxes.data_ptr()) if has else (None, None, None)
+    D.n = _ptr(n)
+    D.assign_gt, D.assign_score, D.out, D.items, D.status = (t.data_ptr() for t in (assign_gt, assign_score, out, items, status))
+    D.upstream = _ptr(upstream)
+    D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())

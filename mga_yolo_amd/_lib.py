@@ -255,6 +255,28 @@ TARGETS_SYMBOLS = {
     "mgatgt_forward": (C.c_int, [C.POINTER(TargetsDesc), C.c_void_p]),
 }
 
+# the detection criterion -- TAL assignment, CIoU, DFL, BCE -- on the Detect maps (include/mgadet.h: a header of its own as well)
+DET_MAX_LEVELS, DET_MAX_TOPK, DET_MAX_GT, DET_REG_MAX = 4, 16, 256, 16
+
+
+class DetDesc(C.Structure):                      # mgadet_desc_t
+    _fields_ = [("feats", C.c_void_p * DET_MAX_LEVELS), ("g_feats", C.c_void_p * DET_MAX_LEVELS),
+                ("H", C.c_int32 * DET_MAX_LEVELS), ("W", C.c_int32 * DET_MAX_LEVELS), ("stride", C.c_int32 * DET_MAX_LEVELS),
+                ("n_levels", C.c_int32), ("B", C.c_int32), ("nc", C.c_int32), ("reg_max", C.c_int32),
+                ("dtype", C.c_int32), ("topk", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32),
+                ("gains", C.c_float * 3), ("reserved", C.c_int32),
+                ("batch_idx", C.c_void_p), ("cls", C.c_void_p), ("bboxes", C.c_void_p), ("n", C.c_void_p),
+                ("assign_gt", C.c_void_p), ("assign_score", C.c_void_p), ("out", C.c_void_p), ("items", C.c_void_p), ("status", C.c_void_p),
+                ("upstream", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
+# every symbol include/mgadet.h declares
+DET_SYMBOLS = {
+    "mgadet_ws_bytes": (C.c_size_t, [C.POINTER(DetDesc)]),
+    "mgadet_forward": (C.c_int, [C.POINTER(DetDesc), C.c_void_p]),
+    "mgadet_backward": (C.c_int, [C.POINTER(DetDesc), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -277,7 +299,8 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS, **OPT_SYMBOLS, **TARGETS_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS, **OPT_SYMBOLS, **TARGETS_SYMBOLS,
+                                         **DET_SYMBOLS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -387,6 +410,14 @@ def targets_scratch_bytes(desc) -> int:
     nbytes = lib.mgatgt_scratch_bytes(C.byref(desc))
     if nbytes == 0 and lib.mgacbam_last_error():
         check(E_ARG, "mgatgt_scratch_bytes")
+    return nbytes
+
+
+def det_ws_bytes(desc) -> int:
+    """Workspace of a detection-criterion call; 0 is the library's refusal and raises with its message."""
+    nbytes = load().mgadet_ws_bytes(C.byref(desc))
+    if nbytes == 0:
+        check(E_ARG, "mgadet_ws_bytes")
     return nbytes
 
 

@@ -1,0 +1,513 @@
+// The detection criterion (include/mgadet.h): task-aligned assignment, CIoU, DFL and BCE on the three Detect maps, read in place.
+//   k_det_assign  : one workgroup per (image, ground-truth slot).  It finds the slot's label row, visits the rectangle of cells per level
+//                   whose centres can lie inside the box, decodes each cell's box, and keeps the top-k cells by (metric, lowest anchor
+//                   index): cells are staged in LDS kDetChunk at a time and the best k so far are carried from chunk to chunk, each
+//                   taken by one workgroup arg-max.  It also clears its share of the image's per-anchor assignment.
+//   k_det_resolve : one workgroup per image, the <= topk * m_cap candidates in LDS.  An anchor claimed by several slots goes to the
+//                   arg-max over ALL slots of the overlap (which may be a slot that did not claim it); then the per-slot maxima of
+//                   metric and overlap, the anchors' target scores and the image's share of their sum.
+//   k_det_loss    : one thread per anchor: BCE over the classes; box and DFL terms for assigned anchors; per-workgroup partials.
+//   k_det_final   : one workgroup: the partials in a fixed order, max(sum of target scores, 1), gains, the status word.
+//   k_det_bwd     : one thread per anchor: every channel's gradient, in the features' element type and layout.
+// No atomics on floating-point sums: every sum has a fixed order, two runs give the same bits.
+#pragma once
+#include "common.cuh"
+
+namespace mgacbam {
+
+constexpr int kDetLevelsMax = 4;               // = MGADET_MAX_LEVELS (api_det.hip asserts these)
+constexpr int kDetReg = 16;                    // bins per box side
+constexpr int kDetTopkMax = 16;
+constexpr int kDetMMax = 256;                  // ground truths per image
+constexpr int kDetChunk = 2048;                // cells a k_det_assign workgroup stages in LDS at a time
+
+struct DetArgs {
+  const void* feat[kDetLevelsMax];             // (B, 64 + nc, H_l, W_l)
+  void* gfeat[kDetLevelsMax];
+  int H[kDetLevelsMax], W[kDetLevelsMax];
+  int a0[kDetLevelsMax + 1];                   // anchors [a0[l], a0[l+1]) belong to level l
+  float stride[kDetLevelsMax];
+  int n_levels, B, nc, no, A, topk, n_cap, m_cap;
+  float gain[3];
+  float img_w, img_h;                          // W_0 * stride_0, H_0 * stride_0
+  const float* batch_idx; const float* cls; const float* bboxes; const int* n_ptr;
+  int* asg_gt; float* asg_score;               // (B, A): the label row an anchor is assigned to (-1: background), its target score
+  int* cand_n; int* cand_row;                  // (B, m_cap): candidates kept, the slot's label row (-1: the image has fewer rows)
+  int* cand_anchor; float* cand_metric; float* cand_overlap;   // (B, m_cap, kDetTopkMax)
+  float* tss_part; int* ovf;                   // (B)
+  float* partial;                              // (nblk, 3)
+  float* fin;                                  // [0] = max(sum of target scores, 1), NaN for a poisoned call; [1] = the status as a float
+  int nblk;
+  float* out; float* items; int* status;
+  const float* upstream;
+};
+
+struct DetBox { float x1, y1, x2, y2; };
+
+__device__ __forceinline__ int det_n(const DetArgs& A) {
+  const int n = A.n_ptr ? *A.n_ptr : A.n_cap;
+  return min(max(n, 0), A.n_cap);
+}
+// loss.py:231 and ops.xywh2xyxy: the row scaled by (W, H, W, H), then centre -+ half the size
+__device__ __forceinline__ DetBox det_gt_box(const DetArgs& A, int r) {
+  const float cx = A.bboxes[4 * r] * A.img_w, cy = A.bboxes[4 * r + 1] * A.img_h;
+  const float hw = A.bboxes[4 * r + 2] * A.img_w * 0.5f, hh = A.bboxes[4 * r + 3] * A.img_h * 0.5f;
+  return DetBox{cx - hw, cy - hh, cx + hw, cy + hh};
+}
+__device__ __forceinline__ bool det_gt_valid(const DetBox& g) { return ((g.x1 + g.y1) + g.x2) + g.y2 > 0.f; }      // loss.py:263
+__device__ __forceinline__ int det_label(const DetArgs& A, int r) { return min(max(static_cast<int>(A.cls[r]), 0), A.nc - 1); }
+__device__ __forceinline__ int det_level(const DetArgs& A, int a) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < kDetLevelsMax; ++i)
+    if (i < A.n_levels && a >= A.a0[i]) l = i;
+  return l;
+}
+
+// metrics.py:113-141 with xywh=False, CIoU=True: box1's and box2's heights carry the eps
+constexpr float kDetEps = 1e-7f;
+constexpr float kDetAtanK = 0.40528473456935109f;      // 4 / pi^2
+__device__ __forceinline__ float det_ciou(const DetBox& p, const DetBox& q) {
+  const float w1 = p.x2 - p.x1, h1 = p.y2 - p.y1 + kDetEps, w2 = q.x2 - q.x1, h2 = q.y2 - q.y1 + kDetEps;
+  const float iw = fmaxf(fminf(p.x2, q.x2) - fmaxf(p.x1, q.x1), 0.f), ih = fmaxf(fminf(p.y2, q.y2) - fmaxf(p.y1, q.y1), 0.f);
+  const float inter = iw * ih, uni = w1 * h1 + w2 * h2 - inter + kDetEps, iou = inter / uni;
+  const float cw = fmaxf(p.x2, q.x2) - fminf(p.x1, q.x1), ch = fmaxf(p.y2, q.y2) - fminf(p.y1, q.y1);
+  const float c2 = cw * cw + ch * ch + kDetEps;
+  const float sx = q.x1 + q.x2 - p.x1 - p.x2, sy = q.y1 + q.y2 - p.y1 - p.y2;
+  const float rho2 = (sx * sx + sy * sy) * 0.25f;
+  const float da = atanf(w2 / h2) - atanf(w1 / h1), v = kDetAtanK * da * da;
+  const float alpha = v / (v - iou + (1.f + kDetEps));
+  return iou - (rho2 / c2 + v * alpha);
+}
+// the share of a two-argument max / min that goes to its first argument (torch: an equal pair shares the gradient)
+__device__ __forceinline__ float det_gt_share(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
+// CIoU(p, q) and its gradient with respect to p = (x1, y1, x2, y2); alpha is a constant (metrics.py:139-140)
+__device__ __forceinline__ float det_ciou_grad(const DetBox& p, const DetBox& q, float (&g)[4]) {
+  const float w1 = p.x2 - p.x1, h1 = p.y2 - p.y1 + kDetEps, w2 = q.x2 - q.x1, h2 = q.y2 - q.y1 + kDetEps;
+  const float iwr = fminf(p.x2, q.x2) - fmaxf(p.x1, q.x1), ihr = fminf(p.y2, q.y2) - fmaxf(p.y1, q.y1);
+  const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
+  const float inter = iw * ih, uni = w1 * h1 + w2 * h2 - inter + kDetEps, iou = inter / uni;
+  const float cw = fmaxf(p.x2, q.x2) - fminf(p.x1, q.x1), ch = fmaxf(p.y2, q.y2) - fminf(p.y1, q.y1);
+  const float c2 = cw * cw + ch * ch + kDetEps;
+  const float sx = q.x1 + q.x2 - p.x1 - p.x2, sy = q.y1 + q.y2 - p.y1 - p.y2;
+  const float rho2 = (sx * sx + sy * sy) * 0.25f;
+  const float da = atanf(w2 / h2) - atanf(w1 / h1), v = kDetAtanK * da * da;
+  const float alpha = v / (v - iou + (1.f + kDetEps));
+  // per coordinate: d iw or ih, d (w1 h1), d cw or ch, d rho2, d atan(w1 / h1)
+  const float onx = iwr >= 0.f ? 1.f : 0.f, ony = ihr >= 0.f ? 1.f : 0.f;
+  const float diw[4] = {-onx * det_gt_share(p.x1, q.x1), 0.f, onx * det_gt_share(q.x2, p.x2), 0.f};
+  const float dih[4] = {0.f, -ony * det_gt_share(p.y1, q.y1), 0.f, ony * det_gt_share(q.y2, p.y2)};
+  const float dwh[4] = {-h1, -w1, h1, w1};
+  const float dcw[4] = {-det_gt_share(q.x1, p.x1), 0.f, det_gt_share(p.x2, q.x2), 0.f};
+  const float dch[4] = {0.f, -det_gt_share(q.y1, p.y1), 0.f, det_gt_share(p.y2, q.y2)};
+  const float drho[4] = {-0.5f * sx, -0.5f * sy, -0.5f * sx, -0.5f * sy};
+  const float r2 = 1.f / (h1 * h1 + w1 * w1);
+  const float dat[4] = {-h1 * r2, w1 * r2, h1 * r2, -w1 * r2};          // atan(w1/h1): d/dw1 = h1 / (h1^2 + w1^2), d/dh1 = -w1 / (...)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float dinter = diw[k] * ih + iw * dih[k];
+    const float duni = dwh[k] - dinter;
+    const float diou = (dinter - iou * duni) / uni;
+    const float dc2 = 2.f * (cw * dcw[k] + ch * dch[k]);
+    const float dv = -2.f * kDetAtanK * da * dat[k];
+    g[k] = diou - (drho[k] * c2 - rho2 * dc2) / (c2 * c2) - alpha * dv;
+  }
+  return iou - (rho2 / c2 + v * alpha);
+}
+
+// one side's 16 bins of an anchor: softmax probabilities, their expectation (loss.py:238) and the log of the sum of exponentials
+template <typename T>
+__device__ __forceinline__ void det_side(const T* __restrict__ f, size_t hw, int side, float (&p)[kDetReg], float& d, float& lse) {
+  float m = -FLT_MAX;
+#pragma unroll
+  for (int j = 0; j < kDetReg; ++j) { p[j] = to_f32<T>(f[(side * kDetReg + j) * hw]); m = fmaxf(m, p[j]); }
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < kDetReg; ++j) { p[j] = expf(p[j] - m); sum += p[j]; }
+  const float inv = 1.f / sum;
+  d = 0.f;
+#pragma unroll
+  for (int j = 0; j < kDetReg; ++j) { p[j] *= inv; d += p[j] * static_cast<float>(j); }
+  lse = m + logf(sum);
+}
+// the decoded box of the anchor at (ax, ay), in grid units (tal.py:382-391)
+template <typename T>
+__device__ __forceinline__ DetBox det_decode(const T* __restrict__ f, size_t hw, float ax, float ay) {
+  float p[kDetReg], d[4], lse;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) det_side<T>(f, hw, s, p, d[s], lse);
+  return DetBox{ax - d[0], ay - d[1], ax + d[2], ay + d[3]};
+}
+// tal.py:279-299: the anchor's centre, in pixels, lies inside the box by more than 1e-9
+__device__ __forceinline__ bool det_inside(const DetBox& g, float px, float py) {
+  return fminf(fminf(px - g.x1, py - g.y1), fminf(g.x2 - px, g.y2 - py)) > 1e-9f;
+}
+// tal.py:156-188 for one (ground truth, anchor) pair that passed det_inside: overlap = clamp(CIoU, 0), metric = score^0.5 overlap^6
+template <typename T>
+__device__ __forceinline__ void det_pair(const T* __restrict__ f, size_t hw, float ax, float ay, float s, const DetBox& g, int label,
+                                         float& met, float& ov) {
+  const DetBox pg = det_decode<T>(f, hw, ax, ay);
+  const DetBox pb{pg.x1 * s, pg.y1 * s, pg.x2 * s, pg.y2 * s};
+  ov = fmaxf(det_ciou(g, pb), 0.f);
+  const float sc = sigmoidf_(to_f32<T>(f[(4 * kDetReg + label) * hw]));
+  const float o2 = ov * ov;
+  met = sqrtf(sc) * (o2 * o2 * o2);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
+  __shared__ float s_met[kDetChunk + kDetTopkMax], s_ov[kDetChunk + kDetTopkMax];
+  __shared__ int s_anc[kDetChunk + kDetTopkMax];
+  __shared__ float sel_met[kDetTopkMax], sel_ov[kDetTopkMax], r_v[kBlock / kWave];
+  __shared__ int sel_anc[kDetTopkMax], r_i[kBlock / kWave], s_cnt[kBlock / kWave], s_row;
+  const int tid = static_cast<int>(threadIdx.x), lane = tid & (kWave - 1), wave = tid / kWave;
+  const int b = static_cast<int>(blockIdx.x) / A.m_cap, g = static_cast<int>(blockIdx.x) % A.m_cap;
+  const int slot = b * A.m_cap + g;
+  {                                                            // this workgroup's share of the image's assignment: background
+    const int per = (A.A + A.m_cap - 1) / A.m_cap, hi = min((g + 1) * per, A.A);
+    for (int a = g * per + tid; a < hi; a += kBlock) {
+      A.asg_gt[static_cast<size_t>(b) * A.A + a] = -1;
+      A.asg_score[static_cast<size_t>(b) * A.A + a] = 0.f;
+    }
+  }
+  // loss.py:217-232: the g-th row whose batch_idx is b
+  const int n = det_n(A);
+  if (tid == 0) s_row = -1;
+  int base = 0;
+  for (int r0 = 0; r0 < n; r0 += kBlock) {
+    const int r = r0 + tid;
+    const bool mine = r < n && A.batch_idx[r] == static_cast<float>(b);
+    const unsigned long long mask = __ballot(mine);
+    __syncthreads();
+    if (lane == 0) s_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    int before = base;
+    for (int w = 0; w < kBlock / kWave; ++w) {
+      if (w < wave) before += s_cnt[w];
+      base += s_cnt[w];
+    }
+    if (mine && before + __popcll(mask & ((1ull << lane) - 1ull)) == g) s_row = r;
+  }
+  __syncthreads();
+  const int row = s_row;
+  DetBox gt{0.f, 0.f, 0.f, 0.f};
+  if (row >= 0) gt = det_gt_box(A, row);
+  if (row < 0 || !det_gt_valid(gt)) {                          // uniform over the workgroup
+    if (tid == 0) { A.cand_n[slot] = 0; A.cand_row[slot] = row; }
+    return;
+  }
+  const int label = det_label(A, row);
+  // per level, the rectangle of cells whose centres can lie inside the box (one cell of margin; det_inside decides)
+  int ix0[kDetLevelsMax], iy0[kDetLevelsMax], rw[kDetLevelsMax], tot[kDetLevelsMax + 1];
+  tot[0] = 0;
+#pragma unroll
+  for (int l = 0; l < kDetLevelsMax; ++l) {
+    int cells = 0;
+    ix0[l] = iy0[l] = 0; rw[l] = 1;
+    if (l < A.n_levels) {
+      const float s = A.stride[l];
+      const int x0 = static_cast<int>(fminf(fmaxf(floorf(gt.x1 / s - 0.5f) - 1.f, 0.f), static_cast<float>(A.W[l] - 1)));
+      const int y0 = static_cast<int>(fminf(fmaxf(floorf(gt.y1 / s - 0.5f) - 1.f, 0.f), static_cast<float>(A.H[l] - 1)));
+      const int x1 = static_cast<int>(fmaxf(fminf(ceilf(gt.x2 / s - 0.5f) + 1.f, static_cast<float>(A.W[l] - 1)), 0.f));
+      const int y1 = static_cast<int>(fmaxf(fminf(ceilf(gt.y2 / s - 0.5f) + 1.f, static_cast<float>(A.H[l] - 1)), 0.f));
+      ix0[l] = x0; iy0[l] = y0; rw[l] = max(x1 - x0 + 1, 1);
+      cells = max(x1 - x0 + 1, 0) * max(y1 - y0 + 1, 0);
+    }
+    tot[l + 1] = tot[l] + cells;
+  }
+  const int T_ = tot[kDetLevelsMax];
+  int ncarry = 0;
+  for (int c0 = 0; c0 < T_; c0 += kDetChunk) {
+    const int cn = min(kDetChunk, T_ - c0);
+    for (int i = tid; i < cn; i += kBlock) {
+      const int idx = c0 + i;
+      int l = 0;
+#pragma unroll
+      for (int k = 1; k < kDetLevelsMax; ++k)
+        if (idx >= tot[k]) l = k;                              // levels past n_levels hold no cell: tot[k] = T_ > idx
+      int x0 = ix0[0], y0 = iy0[0], w = rw[0], t0 = tot[0];
+#pragma unroll
+      for (int k = 1; k < kDetLevelsMax; ++k)
+        if (l == k) { x0 = ix0[k]; y0 = iy0[k]; w = rw[k]; t0 = tot[k]; }
+      const int local = idx - t0, x = x0 + local % w, y = y0 + local / w;
+      const int Wl = A.W[l], Hl = A.H[l];
+      const float s = A.stride[l], ax = static_cast<float>(x) + 0.5f, ay = static_cast<float>(y) + 0.5f;
+      float met = -1.f, ov = 0.f;
+      if (det_inside(gt, ax * s, ay * s)) {
+        const size_t hw = static_cast<size_t>(Hl) * Wl;
+        const T* f = static_cast<const T*>(A.feat[l]) + static_cast<size_t>(b) * A.no * hw + static_cast<size_t>(y) * Wl + x;
+        det_pair<T>(f, hw, ax, ay, s, gt, label, met, ov);
+      }
+      s_met[i] = met; s_ov[i] = ov; s_anc[i] = A.a0[l] + y * Wl + x;
+    }
+    if (tid < ncarry) { s_met[cn + tid] = sel_met[tid]; s_ov[cn + tid] = sel_ov[tid]; s_anc[cn + tid] = sel_anc[tid]; }
+    __syncthreads();
+    const int have = cn + ncarry;
+    int nsel = 0;
+    for (int k = 0; k < A.topk; ++k) {
+      float v = -1.f;
+      int ai = 0x7fffffff, at_ = -1;
+      for (int i = tid; i < have; i += kBlock) {
+        const float m = s_met[i];
+        const int a = s_anc[i];
+        if (m > v || (m == v && a < ai)) { v = m; ai = a; at_ = i; }
+      }
+      float wv = v;
+      int wi = ai;
+      wave_group_argmax(wv, wi, kWave);
+      if (lane == 0) { r_v[wave] = wv; r_i[wave] = wi; }
+      __syncthreads();
+      float bv = r_v[0];
+      int bi = r_i[0];
+      for (int w = 1; w < kBlock / kWave; ++w) argmax_combine(bv, bi, r_v[w], r_i[w]);
+      if (bv < 0.f) break;                                     // nothing left inside the box (uniform: every thread read the same words)
+      if (at_ >= 0 && ai == bi && v == bv) {                   // anchors are distinct: exactly one thread owns the winner
+        sel_met[k] = v; sel_ov[k] = s_ov[at_]; sel_anc[k] = ai;
+        s_met[at_] = -1.f;
+      }
+      nsel = k + 1;
+      __syncthreads();
+    }
+    ncarry = nsel;
+    __syncthreads();
+  }
+  if (tid < ncarry) {
+    A.cand_anchor[slot * kDetTopkMax + tid] = sel_anc[tid];
+    A.cand_metric[slot * kDetTopkMax + tid] = sel_met[tid];
+    A.cand_overlap[slot * kDetTopkMax + tid] = sel_ov[tid];
+  }
+  if (tid == 0) { A.cand_n[slot] = ncarry; A.cand_row[slot] = row; }
+}
+
+// entry e of an image: slot e / kDetTopkMax's candidate e % kDetTopkMax.  e_gt: the slot the entry belongs to after the resolve, plus
+// an action in the bits above kDetSlotMask while it runs.
+constexpr int kDetSlotMask = 0x1ff, kDetDrop = 0x200, kDetLead = 0x400;
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
+  extern __shared__ int det_smem[];
+  const int M = A.m_cap, E = M * kDetTopkMax;
+  int* e_anc = det_smem;
+  float* e_met = reinterpret_cast<float*>(e_anc + E);
+  float* e_ov = e_met + E;
+  int* pos_m = reinterpret_cast<int*>(e_ov + E);
+  int* pos_o = pos_m + M;
+  int* s_row = pos_o + M;
+  short* e_gt = reinterpret_cast<short*>(s_row + M);
+  __shared__ float red[kBlock / kWave];
+  const int tid = static_cast<int>(threadIdx.x), b = static_cast<int>(blockIdx.x);
+  for (int g = tid; g < M; g += kBlock) { s_row[g] = A.cand_row[b * M + g]; pos_m[g] = 0; pos_o[g] = 0; }
+  for (int e = tid; e < E; e += kBlock) {
+    const int g = e / kDetTopkMax, j = e % kDetTopkMax;
+    const bool on = j < A.cand_n[b * M + g];
+    const int src = (b * M + g) * kDetTopkMax + j;
+    e_anc[e] = on ? A.cand_anchor[src] : -1;
+    e_met[e] = on ? A.cand_metric[src] : 0.f;
+    e_ov[e] = on ? A.cand_overlap[src] : 0.f;
+    e_gt[e] = static_cast<short>(g);
+  }
+  {                                                            // an image with more rows than slots: the call's status
+    const int n = det_n(A);
+    float cnt = 0.f;
+    for (int r = tid; r < n; r += kBlock) cnt += A.batch_idx[r] == static_cast<float>(b) ? 1.f : 0.f;
+    cnt = block_sum(cnt, tid, red);
+    if (tid == 0) A.ovf[b] = cnt > static_cast<float>(M) ? 1 : 0;
+  }
+  __syncthreads();
+  // tal.py:317-326: an anchor several slots claim.  The first of its entries leads, the others go.
+  for (int e = tid; e < E; e += kBlock) {
+    const int a = e_anc[e];
+    if (a < 0) continue;
+    int lead = e;
+    bool contested = false;
+    for (int o = 0; o < E; ++o)
+      if (o != e && e_anc[o] == a) { contested = true; lead = min(lead, o); }
+    if (contested) e_gt[e] = static_cast<short>(e_gt[e] | (lead == e ? kDetLead : kDetDrop));
+  }
+  __syncthreads();
+  for (int e = tid; e < E; e += kBlock) {
+    const int act = e_gt[e];
+    if (act & kDetDrop) { e_anc[e] = -1; continue; }
+    if (!(act & kDetLead)) continue;
+    // the arg-max over every slot of the overlap, 0 where the anchor is not inside a valid box; the first slot wins a tie
+    const int a = e_anc[e], l = det_level(A, a);
+    const int Wl = A.W[l], p = a - A.a0[l], x = p % Wl, y = p / Wl;
+    const float s = A.stride[l], ax = static_cast<float>(x) + 0.5f, ay = static_cast<float>(y) + 0.5f;
+    const size_t hw = static_cast<size_t>(A.H[l]) * Wl;
+    const T* f = static_cast<const T*>(A.feat[l]) + static_cast<size_t>(b) * A.no * hw + p;
+    float best_ov = -1.f, best_met = 0.f;
+    int best = 0;
+    for (int g = 0; g < M; ++g) {
+      const int row = s_row[g];
+      if (row < 0) break;                                      // rows fill the slots from 0: the rest are empty, overlap 0, never first
+      float met = 0.f, ov = 0.f;
+      const DetBox gt = det_gt_box(A, row);
+      if (det_gt_valid(gt) && det_inside(gt, ax * s, ay * s)) det_pair<T>(f, hw, ax, ay, s, gt, det_label(A, row), met, ov);
+      if (ov > best_ov) { best_ov = ov; best_met = met; best = g; }
+    }
+    e_gt[e] = static_cast<short>(best);
+    e_met[e] = best_met; e_ov[e] = fmaxf(best_ov, 0.f);
+  }
+  __syncthreads();
+  // tal.py:121-125: per slot the largest metric and overlap among its anchors (maxima of non-negative floats: their bit patterns order)
+  for (int e = tid; e < E; e += kBlock) {
+    if (e_anc[e] < 0) continue;
+    const int g = e_gt[e] & kDetSlotMask;
+    atomicMax(&pos_m[g], __float_as_int(e_met[e]));
+    atomicMax(&pos_o[g], __float_as_int(e_ov[e]));
+  }
+  __syncthreads();
+  float sum = 0.f;
+  for (int e = tid; e < E; e += kBlock) {
+    const int a = e_anc[e];
+    if (a < 0) continue;
+    const int g = e_gt[e] & kDetSlotMask;
+    const float sc = e_met[e] * __int_as_float(pos_o[g]) / (__int_as_float(pos_m[g]) + 1e-9f);
+    A.asg_gt[static_cast<size_t>(b) * A.A + a] = s_row[g];
+    A.asg_score[static_cast<size_t>(b) * A.A + a] = sc;
+    sum += sc;
+  }
+  sum = block_sum(sum, tid, red);
+  if (tid == 0) A.tss_part[b] = sum;
+}
+
+// loss.py:95-105 for one side: the target distance clamped to [0, 14.99], its two neighbouring bins and their weights
+__device__ __forceinline__ void det_dfl_target(float dist, int& tl, float& wl) {
+  const float t = fminf(fmaxf(dist, 0.f), 14.99f);
+  tl = static_cast<int>(t);
+  wl = static_cast<float>(tl + 1) - t;
+}
+__device__ __forceinline__ float det_side_target(const DetBox& tb, float ax, float ay, int side) {    // tal.py:394-397
+  return side == 0 ? ax - tb.x1 : side == 1 ? ay - tb.y1 : side == 2 ? tb.x2 - ax : tb.y2 - ay;
+}
+
+// what a thread of the two sweeps owns: anchor `idx` of (B, A)
+struct DetAnchor { int b, l, p, gi; size_t hw; float ax, ay, s, sc; };
+__device__ __forceinline__ DetAnchor det_anchor(const DetArgs& A, long long idx) {
+  DetAnchor t;
+  t.b = static_cast<int>(idx / A.A);
+  const int a = static_cast<int>(idx % A.A);
+  t.l = det_level(A, a);
+  t.p = a - A.a0[t.l];
+  const int Wl = A.W[t.l];
+  t.hw = static_cast<size_t>(A.H[t.l]) * Wl;
+  t.ax = static_cast<float>(t.p % Wl) + 0.5f; t.ay = static_cast<float>(t.p / Wl) + 0.5f;
+  t.s = A.stride[t.l];
+  t.gi = A.asg_gt[idx]; t.sc = A.asg_score[idx];
+  return t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_det_loss(const DetArgs A) {
+  __shared__ float red[kBlock / kWave];
+  const int tid = static_cast<int>(threadIdx.x);
+  const long long idx = static_cast<long long>(blockIdx.x) * kBlock + tid;
+  float lbox = 0.f, lcls = 0.f, ldfl = 0.f;
+  if (idx < static_cast<long long>(A.B) * A.A) {
+    const DetAnchor t = det_anchor(A, idx);
+    const T* f = static_cast<const T*>(A.feat[t.l]) + static_cast<size_t>(t.b) * A.no * t.hw + t.p;
+    const int label = t.gi >= 0 ? det_label(A, t.gi) : -1;
+    for (int c = 0; c < A.nc; ++c) {                           // BCEWithLogits against onehot(label) * score (loss.py:284)
+      const float x = to_f32<T>(f[(4 * kDetReg + c) * t.hw]);
+      lcls += fmaxf(x, 0.f) - (c == label ? x * t.sc : 0.f) + log1pf(expf(-fabsf(x)));
+    }
+    if (t.gi >= 0) {
+      const DetBox gp = det_gt_box(A, t.gi);
+      const DetBox tb{gp.x1 / t.s, gp.y1 / t.s, gp.x2 / t.s, gp.y2 / t.s};            // loss.py:288
+      float d[4], dfl = 0.f;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        float p[kDetReg], lse, wl;
+        int tl;
+        float vl = 0.f, vr = 0.f;
+        det_dfl_target(det_side_target(tb, t.ax, t.ay, s), tl, wl);
+#pragma unroll
+        for (int j = 0; j < kDetReg; ++j) {
+          const float v = to_f32<T>(f[(s * kDetReg + j) * t.hw]);
+          vl = j == tl ? v : vl; vr = j == tl + 1 ? v : vr;
+        }
+        det_side<T>(f, t.hw, s, p, d[s], lse);
+        dfl += (lse - vl) * wl + (lse - vr) * (1.f - wl);
+      }
+      const DetBox pb{t.ax - d[0], t.ay - d[1], t.ax + d[2], t.ay + d[3]};
+      lbox = (1.f - det_ciou(pb, tb)) * t.sc;                  // loss.py:127-129
+      ldfl = dfl * 0.25f * t.sc;                               // loss.py:134: the mean over the four sides
+    }
+  }
+  lbox = block_sum(lbox, tid, red);
+  lcls = block_sum(lcls, tid, red);
+  ldfl = block_sum(ldfl, tid, red);
+  if (tid == 0) {
+    A.partial[blockIdx.x * 3 + 0] = lbox; A.partial[blockIdx.x * 3 + 1] = lcls; A.partial[blockIdx.x * 3 + 2] = ldfl;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_det_final(const DetArgs A) {
+  __shared__ float red[kBlock / kWave];
+  const int tid = static_cast<int>(threadIdx.x);
+  float s[3] = {0.f, 0.f, 0.f}, tss = 0.f, bad = 0.f;
+  for (int i = tid; i < A.nblk; i += kBlock) {
+    s[0] += A.partial[i * 3]; s[1] += A.partial[i * 3 + 1]; s[2] += A.partial[i * 3 + 2];
+  }
+  for (int b = tid; b < A.B; b += kBlock) { tss += A.tss_part[b]; bad += A.ovf[b] ? 1.f : 0.f; }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s[k] = block_sum(s[k], tid, red);
+  tss = block_sum(tss, tid, red);
+  bad = block_sum(bad, tid, red);
+  if (tid != 0) return;
+  const float nan = __int_as_float(0x7fc00000);
+  tss = fmaxf(tss, 1.f);                                       // loss.py:280
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float item = bad > 0.f ? nan : s[k] / tss * A.gain[k];
+    A.items[k] = item;
+    A.out[k] = item * static_cast<float>(A.B);                 // loss.py:297
+  }
+  A.fin[0] = bad > 0.f ? nan : tss;
+  A.fin[1] = bad;
+  *A.status = bad > 0.f ? 1 : 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_det_bwd(const DetArgs A) {
+  const long long idx = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (idx >= static_cast<long long>(A.B) * A.A) return;
+  const float tss = uniform_load(A.fin), Bf = static_cast<float>(A.B);      // tss: divided by, not multiplied with its reciprocal (one rounding less)
+  const float fbox = uniform_load(A.upstream) * A.gain[0] * Bf / tss, fcls = uniform_load(A.upstream + 1) * A.gain[1] * Bf / tss,
+              fdfl = uniform_load(A.upstream + 2) * A.gain[2] * Bf / tss;
+  const DetAnchor t = det_anchor(A, idx);
+  const size_t off = static_cast<size_t>(t.b) * A.no * t.hw + t.p;
+  const T* f = static_cast<const T*>(A.feat[t.l]) + off;
+  T* g = static_cast<T*>(A.gfeat[t.l]) + off;
+  const int label = t.gi >= 0 ? det_label(A, t.gi) : -1;
+  for (int c = 0; c < A.nc; ++c) {
+    const float x = to_f32<T>(f[(4 * kDetReg + c) * t.hw]);
+    g[(4 * kDetReg + c) * t.hw] = from_f32<T>(fcls * (sigmoidf_(x) - (c == label ? t.sc : 0.f)));
+  }
+  if (t.gi < 0 || !(tss == tss)) {                             // background, or the poisoned call: no box terms (NaN where poisoned)
+    const T z = from_f32<T>(t.gi < 0 && tss == tss ? 0.f : tss);
+    for (int c = 0; c < 4 * kDetReg; ++c) g[c * t.hw] = z;
+    return;
+  }
+  const DetBox gp = det_gt_box(A, t.gi);
+  const DetBox tb{gp.x1 / t.s, gp.y1 / t.s, gp.x2 / t.s, gp.y2 / t.s};
+  const DetBox pb = det_decode<T>(f, t.hw, t.ax, t.ay);
+  float gc[4];
+  det_ciou_grad(pb, tb, gc);
+  // the loss is (1 - CIoU) score: x1 = ax - d_l, y1 = ay - d_t, x2 = ax + d_r, y2 = ay + d_b
+  const float wbox = fbox * t.sc, wdfl = fdfl * t.sc * 0.25f;
+#pragma unroll 1
+  for (int s = 0; s < 4; ++s) {                                // a side at a time: 16 bins live, not 64
+    float p[kDetReg], d, lse, wl;
+    int tl;
+    const float gds = s == 0 ? gc[0] : s == 1 ? gc[1] : s == 2 ? -gc[2] : -gc[3];
+    det_side<T>(f, t.hw, s, p, d, lse);
+    det_dfl_target(det_side_target(tb, t.ax, t.ay, s), tl, wl);
+#pragma unroll
+    for (int j = 0; j < kDetReg; ++j) {
+      const float hit = j == tl ? wl : (j == tl + 1 ? 1.f - wl : 0.f);
+      g[(s * kDetReg + j) * t.hw] = from_f32<T>(wdfl * (p[j] - hit) + wbox * gds * p[j] * (static_cast<float>(j) - d));
+    }
+  }
+}
+
+}  // namespace mgacbam
