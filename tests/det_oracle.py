@@ -62,7 +62,7 @@ def ciou(p, q, parts=False):
 
 def oracle(feats, batch_idx, cls, bboxes, *, nc, strides=(8, 16, 32), gains=(7.5, 0.5, 1.5), topk=10, lowest_first=True):
     """feats: fp64 leaves or plain tensors (B, 64 + nc, H_l, W_l).  Returns loss, items, fg, target_gt (label row), target_scores,
-    target_bboxes (pixels), weight, comp_grads (per component, per level) and terms."""
+    target_bboxes (pixels), weight, comp_grads (per component, per level), terms and picks."""
     f64 = torch.float64
     xs = [f.detach().to(f64).clone().requires_grad_(True) for f in feats]
     B = xs[0].shape[0]
@@ -87,6 +87,7 @@ def oracle(feats, batch_idx, cls, bboxes, *, nc, strides=(8, 16, 32), gains=(7.5
     t_lab = torch.zeros(B, A, dtype=torch.int64)
     amp = torch.ones(B, A, dtype=f64)
     pp, ap, sg = (pred * st).detach(), anc * st, scores.detach().sigmoid()
+    picks = {}                                                   # per labelled image: its rows, the top-k picks before the contest, the metrics
     for b in range(B):
         rows = [r for r in range(bidx.numel()) if int(bidx[r]) == b]
         if not rows:
@@ -111,6 +112,7 @@ def oracle(feats, batch_idx, cls, bboxes, *, nc, strides=(8, 16, 32), gains=(7.5
             inside.sort(key=lambda a: (-float(met[g, a]), a if lowest_first else -a))
             for a in inside[:topk]:
                 pos[g, a] = True
+        picks[b] = (rows, pos.clone(), met.clone())
         for a in range(A):
             if pos[:, a].sum() > 1:
                 win = int(ov[:, a].argmax())                     # first index on a tie
@@ -168,7 +170,7 @@ def oracle(feats, batch_idx, cls, bboxes, *, nc, strides=(8, 16, 32), gains=(7.5
         mags.append(lv)
     terms["grad_mags"] = mags
     return dict(loss=loss.detach(), items=(comp * gn).detach(), fg=fg, target_gt=t_row, target_scores=t_scores.detach(),
-                target_bboxes=t_box, weight=norm, comp_grads=comp_grads, terms=terms, tss=float(tss))
+                target_bboxes=t_box, weight=norm, comp_grads=comp_grads, terms=terms, tss=float(tss), picks=picks)
 
 
 def grads(o, level, upstream):

@@ -2,6 +2,8 @@
 text is copied).
 
     python tools/gen_golden_det.py --reference <checkout of the reference project>
+    python tools/gen_golden_det.py --reference <checkout> --shapes [--only NAME ...]     (tests/golden/detx_*.npz, det_ratios_shapes.json:
+                                                                                          the rebuilt cases of tests/det_cases.py, see shapes_main)
 
 Run on the build machine, where the reference is available; it never travels with this repository.  The reference is imported with the
 recipe of DESIGN 8 (a stand-in ``cv2``, an answered ``torchvision`` version).  The criterion is built on a stand-in model: ``model[-1]``
@@ -105,7 +107,7 @@ def make_inputs(torch, B, hw, nc, rows, seed):
     return feats, bidx, cls, xywh
 
 
-def run_reference(torch, Crit, feats, bidx, cls, xywh, nc, dtype):
+def run_reference(torch, Crit, feats, bidx, cls, xywh, nc, dtype, strides=STRIDES, topk=TOPK):
     """One forward and two backwards of the reference's criterion in `dtype`; also what its assigner saw (for the guards)."""
     torch.set_default_dtype(dtype)
     try:
@@ -113,9 +115,9 @@ def run_reference(torch, Crit, feats, bidx, cls, xywh, nc, dtype):
             def __init__(self):
                 super().__init__()
                 self.p = torch.nn.Parameter(torch.zeros(1))
-                self.model = [SimpleNamespace(nc=nc, reg_max=16, stride=torch.tensor([float(s) for s in STRIDES]))]
+                self.model = [SimpleNamespace(nc=nc, reg_max=16, stride=torch.tensor([float(s) for s in strides]))]
                 self.args = SimpleNamespace(box=GAINS[0], cls=GAINS[1], dfl=GAINS[2])
-        crit = Crit(Stand(), tal_topk=TOPK)
+        crit = Crit(Stand(), tal_topk=topk)
         seen = {}
         asg = crit.assigner
         inner_pos, inner_fwd = asg.get_pos_mask, asg.forward
@@ -143,7 +145,7 @@ def run_reference(torch, Crit, feats, bidx, cls, xywh, nc, dtype):
         torch.set_default_dtype(torch.float32)
 
 
-def guards(torch, seen, want_terms: bool):
+def guards(torch, seen, want_terms: bool, topk=TOPK):
     """The near-tie guard on the fp64 run; returns a reason to re-seed, or None."""
     if "metric" not in seen:
         return None
@@ -155,9 +157,9 @@ def guards(torch, seen, want_terms: bool):
     if near.any():
         return "an in-box delta within 1e-3 px of 0"
     m = torch.where(inbox, met, -torch.ones_like(met)).sort(-1, descending=True).values
-    if m.shape[-1] > TOPK:
-        a, b = m[..., TOPK - 1], m[..., TOPK].clamp(min=0)
-        if ((a > 0) & (m[..., TOPK] >= 0) & (a - b <= 1e-4 * a)).any():
+    if m.shape[-1] > topk:
+        a, b = m[..., topk - 1], m[..., topk].clamp(min=0)
+        if ((a > 0) & (m[..., topk] >= 0) & (a - b <= 1e-4 * a)).any():
             return "k-th and (k+1)-th metric within 1e-4"
     contested = pos.sum(1) > 1
     if contested.any() and ov.shape[1] > 1:
@@ -171,9 +173,103 @@ def guards(torch, seen, want_terms: bool):
     return None
 
 
+def _ratio(a, b, t, eps):
+    t = np.broadcast_to(np.asarray(t, dtype=np.float64), np.shape(b))
+    d = np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))
+    ok = t > 0
+    return float((d[ok] / (eps * t[ok])).max()) if ok.any() else 0.0
+
+
+def shapes_main(torch, Crit, det_oracle, only=None):
+    """--shapes: tests/golden/detx_<name>.npz for the cases of tests/det_cases.py and det_ratios_shapes.json.  The features are rebuilt
+    on the test machine from the recorded seed, so a record holds no tensor of the features' size: the labels, the seed, the digest, the
+    reference's loss and items (fp32 and fp64 runs), its fp64 target scores and foreground mask (sparse), and per quantity the ratio of
+    its fp32 run against its fp64 run.  The gradients are compared here, against the oracle, and not stored: a seed is accepted only
+    where the oracle equals the reference's fp64 run on them (and on everything else) at the bars of tests/test_det_abi.py."""
+    import det_cases as DC
+    eps32 = float(np.finfo(np.float32).eps)
+    ratios = {}
+    path = os.path.join(OUT, "det_ratios_shapes.json")
+    if only and os.path.exists(path):
+        with open(path) as f:
+            ratios = json.load(f)["cases"]
+    for name, spec in DC.CASES.items():
+        if only and name not in only:
+            continue
+        B, nc, strides, topk = spec["B"], spec["nc"], tuple(spec["strides"]), spec["topk"]
+        bidx, cls, xywh = (t.double() for t in DC.labels(name))
+        kw = dict(nc=nc, strides=strides, gains=GAINS, topk=topk)
+        want_terms = name != "chunk_zero"
+        for seed in range(100, 140):
+            feats = [f.double() for f in DC.build_feats(name, seed)]
+            why = None
+            for tag, fs in (("fp32", feats), ("fp16", [f.half().double() for f in feats]), ("bf16", [f.bfloat16().double() for f in feats])):
+                l64, i64, g64, seen = run_reference(torch, Crit, fs, bidx, cls, xywh, nc, torch.float64, strides, topk)
+                why = guards(torch, seen, want_terms, topk)
+                if why is not None:
+                    why = f"{tag} values: {why}"
+                    break
+            if why is None:
+                l64, i64, g64, seen = run_reference(torch, Crit, feats, bidx, cls, xywh, nc, torch.float64, strides, topk)
+                raw = l64 / torch.tensor(GAINS, dtype=torch.float64) / B
+                if want_terms and not (raw[0] > 0.05 and raw[2] > 0.05):
+                    why = f"box {float(raw[0]):.3f} / dfl {float(raw[2]):.3f} not above 0.05"
+                if not want_terms and not (raw[1] > 0 and float(seen["target_scores"].sum()) > 0):
+                    why = "cls or every weight is 0"
+            if why is None:
+                lo = det_oracle.oracle(feats, bidx, cls, xywh, **kw)
+                hi = det_oracle.oracle(feats, bidx, cls, xywh, lowest_first=False, **kw)
+                same = torch.equal(lo["loss"], hi["loss"]) and torch.equal(lo["target_scores"], hi["target_scores"]) and all(
+                    torch.equal(a, b) for i in range(3) for a, b in zip(lo["comp_grads"][i], hi["comp_grads"][i]))
+                if not same:
+                    why = "the two tie orders differ"
+            if why is None:
+                why = "; ".join(DC.built_for(name, lo)) or None
+            if why is None:                                      # the oracle against the reference's fp64 run, as test_oracle_equals_the_reference_fp64_run
+                K, t = det_oracle.K, lo["terms"]
+                try:
+                    det_oracle.check("loss", lo["loss"], l64, t["loss"], 1e-9 / K["loss"], K["loss"])
+                    det_oracle.check("items", lo["items"], i64, t["loss"] / B, 1e-9 / K["loss"], K["loss"])
+                    det_oracle.check("target_scores", lo["target_scores"], seen["target_scores"], t["target_scores"], 1e-9 / K["target_scores"],
+                                     K["target_scores"])
+                    for key, up in (("g1", (1.0, 1.0, 1.0)), ("gnu", UPSTREAM)):
+                        for l in range(len(feats)):
+                            det_oracle.check(f"{key}[{l}]", det_oracle.grads(lo, l, up), g64[key][l], det_oracle.grad_terms(t, l, up), 1e-9 / K["grad"],
+                                             K["grad"])
+                except AssertionError as e:
+                    why = f"the oracle is not the reference: {e}"
+            if why is None:
+                break
+            print(f"{name}: seed {seed} rejected: {why}")
+        else:
+            raise SystemExit(f"{name}: no seed passed the guards")
+        l32, i32, g32, seen32 = run_reference(torch, Crit, feats, bidx, cls, xywh, nc, torch.float32, strides, topk)
+        t = lo["terms"]
+        r = dict(loss=_ratio(l32.numpy(), l64.numpy(), t["loss"].numpy(), eps32),
+                 target_scores=_ratio(seen32["target_scores"].numpy(), seen["target_scores"].numpy(), t["target_scores"].numpy(), eps32))
+        for key, up in (("g1", (1.0, 1.0, 1.0)), ("gnu", UPSTREAM)):
+            r[key] = max(_ratio(g32[key][l].numpy(), g64[key][l].numpy(), det_oracle.grad_terms(t, l, up).numpy(), eps32) for l in range(len(feats)))
+        ts = seen["target_scores"].numpy().reshape(-1)
+        rec = dict(strides=np.array(strides), gains=np.array(GAINS), topk=topk, seed=seed, options=json.dumps(DC.options(name)),
+                   sha256=DC.digest(DC.build_feats(name, seed)), batch_idx=bidx.numpy().astype(np.float32), cls=cls.numpy().astype(np.float32),
+                   bboxes=xywh.numpy().astype(np.float32), loss_f32=l32.numpy(), items_f32=i32.numpy(), loss_f64=l64.numpy(), items_f64=i64.numpy(),
+                   ts_index=np.flatnonzero(ts).astype(np.int64), ts_value=ts[np.flatnonzero(ts)],
+                   fg_index=np.flatnonzero(seen["fg_mask"].numpy().reshape(-1)).astype(np.int64),
+                   ratio_names=np.array(sorted(r)), ratio_values=np.array([r[k] for k in sorted(r)]))
+        np.savez_compressed(DC.path(name), **rec)
+        ratios[name] = r
+        print(f"{name}: seed {seed}, {os.path.getsize(DC.path(name)) / 1024:.0f} KB, loss {l64.tolist()}, ratios {r}")
+    worst = {k: max(r[k] for r in ratios.values()) for k in ("loss", "target_scores", "g1", "gnu")}
+    with open(path, "w") as f:
+        json.dump(dict(cases=ratios, worst=worst, eps="float32"), f, indent=1, sort_keys=True)
+    print("worst", worst)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True)
+    ap.add_argument("--shapes", action="store_true", help="write the detx_* records of tests/det_cases.py instead of the six stored cases")
+    ap.add_argument("--only", nargs="*", help="with --shapes: these cases only (the others' ratios are kept)")
     args = ap.parse_args()
     Crit = import_reference(args.reference)
     import torch
@@ -181,6 +277,8 @@ def main():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     sys.path.insert(0, ROOT)
     import det_oracle
+    if args.shapes:
+        return shapes_main(torch, Crit, det_oracle, args.only)
     ratios = {}
     for name, (B, hw, nc, rows) in CASES.items():
         for seed in range(100, 140):
