@@ -3,7 +3,7 @@
 // through the exact adjoint.  Both are a few hundred KB at most: one launch per direction covers every level of the call.
 //   k_resample_fwd: one thread per destination pixel (four of a row where out_w % 4 == 0: one 16-byte store), four taps.
 //   k_resample_bwd: one thread per SOURCE pixel i, gather form.  The operator is separable, so per axis the thread walks the contiguous
-//                   range of destination indices j whose footprint may hold i -- the inverse map widened by one -- in ascending order, and
+//                   range of destination indices j whose footprint may hold i -- the inverse map, two indices wider -- in ascending order, and
 //                   the forward's own index function (bilinear_tap, common.cuh) decides membership and weight: i0(j) == i gives 1 - lam,
 //                   i1(j) == i gives lam (both at the clamped last index).  No atomics, a fixed order: two runs give the same bits.
 #pragma once
@@ -51,9 +51,11 @@ __device__ __forceinline__ void resample_fwd_px(const ResampleLevel& L, int t) {
     int x0, x1;
     float lx;
     bilinear_tap(sw, xq * VEC + e, L.in_w, x0, x1, lx);
-    const float top = (1.f - lx) * r0[x0] + lx * r0[x1];
-    const float bot = (1.f - lx) * r1[x0] + lx * r1[x1];
-    out[e] = (1.f - ly) * top + ly * bot;
+    // the FMAs are spelled out: left to contraction, the compiler fused the OTHER product in pixels 2 and 3 of the four-pixel path, so a
+    // pixel's bits depended on the path its row took (tests/test_gpu_resample.py::test_misaligned_buffers_give_the_same_bits)
+    const float top = fmaf(lx, r0[x1], (1.f - lx) * r0[x0]);
+    const float bot = fmaf(lx, r1[x1], (1.f - lx) * r1[x0]);
+    out[e] = fmaf(1.f - ly, top, ly * bot);
   }
   store_vec<float, VEC>(L.dst + (static_cast<size_t>(b) * L.out_h + y) * L.out_w + xq * VEC, out);
 }
@@ -67,7 +69,10 @@ __global__ __launch_bounds__(kBlock) void k_resample_fwd(const ResampleGroup G) 
   else resample_fwd_px<1>(L, t);
 }
 
-// the destination indices j of one axis whose footprint can hold source index i: f(j) in [i - 1, i + 1) inverted, widened by one each way
+// the destination indices j of one axis whose footprint can hold source index i: f(j) in (i - 1, i + 1) inverts to the open interval
+// ((i - 0.5) / scale - 0.5, (i + 1.5) / scale - 0.5).  floor / ceil of its ends already lie one index outside it and the range takes one
+// more each way: two indices of margin against the fp32 rounding of the ends (a range narrower by two at either end still passes every
+// test, one narrower by three fails nearly all of them: DESIGN 7f-1)
 __device__ __forceinline__ void resample_range(float inv_scale, int i, int n_out, int& lo, int& hi) {
   lo = max(static_cast<int>(floorf((static_cast<float>(i) - 0.5f) * inv_scale - 0.5f)) - 1, 0);
   hi = min(static_cast<int>(ceilf((static_cast<float>(i) + 1.5f) * inv_scale - 0.5f)) + 1, n_out - 1);

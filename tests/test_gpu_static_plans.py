@@ -16,6 +16,7 @@ from conftest import rel_err
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import plan_replays as R  # noqa: E402
+import resample_oracle as RO  # noqa: E402
 import spade_plan as P  # noqa: E402
 from test_gpu_spade import dev, live_case  # noqa: E402,F401  (dev: the module's device fixture)
 
@@ -235,6 +236,35 @@ def test_spade_plan_with_masks_at_another_resolution(dev):
                 report.append((l, k, e))
     assert not report, (report, bar)
     assert torch.equal(plan.y[1], ref["y"][1]) and torch.equal(plan.gmask[1], ref["gmask"][1])     # the level without a resample: the same bits
+
+
+def test_spade_plan_with_a_mask_at_eight_times_the_level(dev):
+    """mask_hw=[(8H, 8W), None, None], the workload's ratio at P3.  After a captured replay the plan's resampled mask and its dL/dmask at
+    the mask's own resolution are the bits of stand-alone calls of the two entry points on the plan's tensors, every element is within
+    the resample's own bar (tests/resample_oracle.py: K x terms, exactly 0 where the terms are 0), and the 60 of 64 source
+    pixels per 8 x 8 cell that no destination reads get a gradient of exactly 0."""
+    ins = _spade_inputs(torch.float32)
+    B, _, H, W = ins[0][1].shape
+    big = (8 * H, 8 * W)
+    plan = _spade_plan(torch.float32, False, "full", [big, None, None])
+    plan.mask_src[0].copy_(torch.randn(B, 1, *big, generator=torch.Generator().manual_seed(11)))
+    graph = plan.capture(lambda: (plan.forward(), plan.backward()))
+    plan.mask[0].fill_(float("nan")); plan.gmask_src[0].fill_(float("nan"))   # the replay must write both
+    graph.replay()
+    torch.cuda.synchronize()
+    alone_f, alone_b = torch.full_like(plan.mask[0], float("nan")), torch.full_like(plan.gmask_src[0], float("nan"))
+    _resample("forward", plan.mask_src[0], alone_f, big, (H, W))
+    _resample("backward", plan.gmask[0], alone_b, big, (H, W))
+    torch.cuda.synchronize()
+    assert torch.equal(plan.mask[0], alone_f) and torch.equal(plan.gmask_src[0], alone_b)
+    op = RO.Resample(big, (H, W))
+    kf, kb = RO.load_k()
+    rf, _, nzf, badf = RO.ratio(plan.mask[0], *op.forward(plan.mask_src[0]))
+    rb, zb, nzb, badb = RO.ratio(plan.gmask_src[0], *op.backward(plan.gmask[0]))
+    print(f"mask_hw 8x: forward {rf:.3f} (K {kf:.3f}) backward {rb:.3f} (K {kb:.3f}), {zb} of {plan.gmask_src[0].numel()} zero-terms elements")
+    assert badf == 0 and badb == 0 and nzf == 0 and nzb == 0 and rf <= kf and rb <= kb
+    assert bool(torch.isfinite(plan.gmask[0]).all()) and float(plan.gmask[0].abs().max()) > 0
+    assert float((plan.gmask_src[0] == 0).double().mean()) >= 0.90
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
