@@ -63,6 +63,14 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
   sig.proj = L.gmask != nullptr;
   A.g.proj_h = (L.gmask && L.p.hidden <= MGACBAM_PROJ_MAX_HIDDEN && (have || make)) ? L.p.hidden : 0;
   A.make_proj = A.g.proj_h > 0 && make;
+  // kProjMax < hidden <= kProjWide: the tiles form the planes on the matrix cores (bwd.cuh) into the SCRATCH buffer -- made and used inside
+  // one backward, the ctx has no room for them -- whether or not HAVE_PROJ is set (the forward never saves planes this wide).  Again the
+  // level alone decides (wide_proj_shape: the lane layout the MFMA needs and a level too large to stay in the cache).
+  if (L.gmask && L.dtype == MGACBAM_F32 && wide_proj_shape(L.B, L.C, L.H, L.W, L.p.hidden, false, VEC, A.t)) {
+    A.g.proj_h = L.p.hidden;
+    A.make_proj = 2;
+    A.c.proj = A.s.proj;                                          // k_bwd_apply reads a level's planes through c.proj wherever they live
+  }
   return 0;
 }
 
@@ -162,8 +170,19 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
   if ((stages & MGACBAM_BWD_PARAMGRAD) && !fuse_pg)  // 5. every parameter gradient
     if (int e = launch_params(G, st)) return e;
   if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask) [+ parameter gradients as role workgroups]
+    // A group whose fp32 levels ALL have planes runs the instantiation that cannot read x (fewer registers, one more workgroup per CU);
+    // a level's results are the same bits under either, so this is a property of the launch, not of the level (it is not in Sig: a
+    // mixed pyramid stays one launch).  Half-precision groups keep the one instantiation they had.
+    bool nox = sig.gmask && sig.dtype == MGACBAM_F32 && sig.vec == 4;
+    for (int l = 0; l < n; ++l) nox = nox && lv[l].g.proj_h > 0;
     auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_bool(sig.gmask, [&](auto gm) {
-      return with_bool(fuse_pg, [&](auto pg) { return k_bwd_apply<elem_t<decltype(t)>, v.value, gm.value, pg.value>; }); }); });
+      return with_bool(fuse_pg, [&](auto pg) {
+        using T = elem_t<decltype(t)>;
+        if constexpr (std::is_same_v<T, float> && v.value == 4 && gm.value) {
+          return nox ? k_bwd_apply<T, v.value, gm.value, pg.value, false> : k_bwd_apply<T, v.value, gm.value, pg.value, true>;
+        } else {
+          return k_bwd_apply<T, v.value, gm.value, pg.value, true>;
+        } }); }); });
     if (int e = launch_group("k_bwd_apply", kernel, G, [&](const BwdArgs& a) { return (fuse_pg ? pad8(a.npg) : 0) + xcd_grid(a.g.B, a.nt); },
                              [&](const BwdArgs& a) { return std::max(bwd_apply_smem(a.g, sig.vec), fuse_pg ? params_smem(a.g) : 0); }, st)) return e;
   }

@@ -10,9 +10,11 @@ struct Geo {
   int hidden, k;
   int use_sigmoid;
   float thr, eps;
-  int proj_h;      // > 0: W1-projection planes of x are saved (forward) / used by k_bwd_apply (backward); = hidden (<= kProjMax)
+  int proj_h;      // > 0: W1-projection planes of x are saved (forward) / used by k_bwd_apply (backward); = hidden (<= kProjMax in the ctx,
+                   // <= kProjWide in the backward's scratch)
 };
 constexpr int kProjMax = 4;   // MGACBAM_PROJ_MAX_HIDDEN
+constexpr int kProjWide = 16; // widest hidden layer the backward makes planes for: the 16 output rows of one v_mfma_f32_16x16x4_f32
 constexpr int kGateR = 16;   // channels a thread of the x-resident kernels keeps in registers (x VEC pixels each)
 constexpr int kSyncPx = 16;   // a hand-off tile is at least this many pixels: ctx.sync holds ceil(HW/kSyncPx)+1 flags per sample
 
@@ -23,7 +25,7 @@ struct CtxPtrs {
   int* valid; int* amax;
   float* h_avg; float* h_mx; float* ca;
   float* planes; int* cidx; float* sa;
-  float* proj;     // (B, hidden, HW) when hidden <= kProjMax
+  float* proj;     // (B, hidden, HW) when hidden <= kProjMax (a backward level with wider planes: ScratchPtrs::proj, put here by the host)
   int* sync;       // in-launch hand-off state, all generation counters (zero-filled once by the caller, never reset): [B][nflag] k_gate tile flags,
                    // 4 status words ([0] = time-out), [B] per-sample ca flags, [B][nflag] k_bwd_reduce1 tile flags, [B][nflag] folded conv-tile flags
 };
@@ -65,6 +67,7 @@ struct ScratchPtrs {
   float* gh_avg;    // (B,hidden)
   float* gh_mx;     // (B,hidden)
   float* pgh;       // (B,ncg,hidden) per-channel-group partials of W2^T g_z (k_bwd_reduce2 -> k_bwd_apply prologue)
+  float* proj;      // (B,hidden,HW) W1-projection planes of a level with kProjMax < hidden <= kProjWide (k_bwd_reduce1 tiles -> k_bwd_apply)
 };
 
 struct BwdArgs {
@@ -83,7 +86,8 @@ struct BwdArgs {
   int sflag0;   // ... of k_bwd_reduce2's sweep workgroups in the merged launch: [B][C], one counter per CHANNEL (a sweep reads its first
                 // channel's, bumps all of its own): the channel grouping depends on the call's other levels, the counts do not
   int mbflag0, mcflag0;   // the merged launch's own tile / conv-tile flags (the host puts them into bflag0 / cflag0 for that launch)
-  int make_proj;   // 1: g.proj_h > 0 and the k_bwd_reduce1 tiles write the level's W1-projection planes (0 with MGACBAM_BWD_HAVE_PROJ: the forward did)
+  int make_proj;   // > 0: g.proj_h > 0 and the k_bwd_reduce1 tiles write the level's W1-projection planes (0 with MGACBAM_BWD_HAVE_PROJ: the
+                   // forward did) -- 1: proj_h <= kProjMax, VALU form; 2: proj_h <= kProjWide, MFMA form (bwd.cuh)
   int merged;   // 1: k_bwd_reduce1 tiles, transposed-conv tiles, dWsa tiles and k_bwd_reduce2 sweeps are ONE launch (k_bwd_r12)
   unsigned spin_limit;
   int vec;      // elements per lane of the tile kernels (TP = chan_tx * vec pixels per tile)

@@ -5,7 +5,8 @@
 // P3+P4+P5:
 //   k_bwd_reduce1  x, gy (1 read each) -> A[b,c] = sum_hw gy*x*sa, D[b,c] = sum_hw gy*(v-x)   (per hw-tile partials)
 //                                         g_pre[b,hw] = a * sa(1-sa) * sum_c ca*gy*x
-//                                         P[b,j,hw] = sum_c W1[j,c]*x   (levels whose dL/dmask is wanted, hidden <= kProjMax: ctx.proj)
+//                                         P[b,j,hw] = sum_c W1[j,c]*x   (levels whose dL/dmask is wanted: hidden <= kProjMax into ctx.proj,
+//                                         kProjMax < hidden <= kProjWide on the matrix cores into the scratch buffer)
 //   k_bwd_convT    g_pre               -> g_planes = conv_transpose(g_pre, Wsa)     [tiny; with MGACBAM_BWD_FOLD its tiles are the
 //                                         last workgroups of the k_bwd_reduce1 launch and take g_pre over inside the launch]
 //   k_bwd_reduce2  x (1 read)          -> g_ca[b,c] = a*A + sum_hw x * ([c == cidx]*gp0 + gp1/C) ; g_z ; D ;
@@ -24,6 +25,12 @@
 // for such a level).  The tiles make planes for fp32 levels only: VEC is 4 or 1 here for every element type, so the cost is the same
 // 4*VEC accumulators, but with half the bytes per element the bf16 / fp16 step measured slower with them (api_bwd.hip: backward_args,
 // where the rule lives -- per level, the same for the producing and the consuming stage).
+// Levels with kProjMax < hidden <= kProjWide (16) get the same planes without the hidden*VEC accumulators the VALU form would need: where a
+// wave of a tile is 4 channel rows x 16 lanes of 4 pixels (chan_tx 16, VEC 4) it is the B operand of v_mfma_f32_16x16x4_f32 as loaded, W1 is
+// the A operand, and four MFMAs per channel step keep 16 hidden rows x 64 pixels in 16 registers per lane -- the registers of the VALU form,
+// so the PROJ instantiations keep their occupancy.  Such planes live in the backward's scratch (they are made and used inside one backward;
+// the ctx layout is unchanged), for fp32 levels of at least 1 MiB: a smaller level's x is still in the cache when k_bwd_apply reads it.
+// A launch group of k_bwd_apply in which EVERY level has planes runs the NEEDX = false instantiation, which has no x path at all.
 // All cross-workgroup sums are two-stage (partials, then one reader, fixed order), never float atomics, so results are
 // bitwise reproducible run to run.
 #pragma once
@@ -34,6 +41,7 @@
 namespace mgacbam {
 
 constexpr int kPghLds = 2048;   // floats of LDS for k_bwd_reduce2's hidden-gradient partials (rows x hidden chunk)
+typedef float v4f32_t __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
 // k_bwd_reduce1     (thread layout of k_chan: one H*W vector per lane, rows take channel slices; TX <= 64)
@@ -62,11 +70,13 @@ __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid
   const T* gp = static_cast<const T*>(A.gy) + base;
   const float a = softplusf_(*A.p.beta);
   // LDS: [C ca][2*C tile partials (A then D)][256*VEC combine]; a plane-making level: [..., padded to 4][C*kProjMax W1^T][4*256*VEC combine]
+  // (VALU form) or [..., padded to 4][3*16*64 combine] (MFMA form: W1 is read from memory)
   float* s_ca = smem;
   float* s_aq = smem + g.C;
-  const bool proj = PROJ && A.make_proj;                        // (host: only where g.proj_h > 0)
+  const bool proj = PROJ && A.make_proj == 1;                   // (host: only where g.proj_h > 0) VALU form, proj_h <= kProjMax
+  const bool wide = PROJ && A.make_proj == 2;                   // MFMA form, kProjMax < proj_h <= kProjWide: [..., padded to 4][3*16*64 combine]
   float* s_w1t = smem + ((3 * g.C + 3) & ~3);                   // [c][HP], zero padded past proj_h
-  float* sm = proj ? s_w1t + g.C * HP : s_aq + 2 * g.C;
+  float* sm = proj ? s_w1t + g.C * HP : wide ? s_w1t : s_aq + 2 * g.C;
   for (int c = tid; c < g.C; c += kBlock) s_ca[c] = A.c.ca[static_cast<size_t>(b) * g.C + c];
   if (PROJ) {
     if (proj) {
@@ -90,8 +100,49 @@ __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid
     for (int e = 0; e < VEC; ++e) accP[j][e] = 0.f;
   __syncthreads();
 
+  bool mfma_done = false;
+  if constexpr (PROJ && VEC == 4 && sizeof(T) == 4) {
+    if (wide) {
+      // MFMA form (TX = 16: a wave = 4 channel rows x 16 lanes of 4 pixels, the B operand as loaded).  Per channel step and element e of the
+      // lane's vector one v_mfma_f32_16x16x4_f32: D_e[j][n] += sum_k W1[j][c0 + k] * x[c0 + k][4 n + e], k = lane / 16 = ty % 4, n = lane % 16 = tx;
+      // A = W1[tx][c] of the lane's own channel (rows >= proj_h and channels >= C are zero).  The lane ends with planes 4 (ty % 4) .. + 3 of its
+      // own four pixels, summed over the wave's channels, in the 16 registers of accP.  The matrix cores need every lane: the loop is uniform
+      // and a lane past C contributes zeros -- to g_pre and the (b,c) partials as well, which keep the bits of the other loop.
+      static_assert(HP == 4, "accP is the four accumulator quads of the MFMA form");
+      v4f32_t m[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) m[e] = v4f32_t{accP[0][e], accP[1][e], accP[2][e], accP[3][e]};
+      const bool arow = tx < g.proj_h;
+      const float* w1r = A.p.w1 + static_cast<size_t>(arow ? tx : 0) * g.C;
 #pragma unroll 4
-  for (int c = ty; c < g.C; c += TY) {
+      for (int c0 = 0; c0 < g.C; c0 += TY) {
+        const bool ok = c0 + ty < g.C;
+        const int c = ok ? c0 + ty : g.C - 1;
+        float xv[VEC], gv[VEC];
+        load_vec<T, VEC>(xp + static_cast<size_t>(c) * g.HW, xv);
+        load_vec<T, VEC>(gp + static_cast<size_t>(c) * g.HW, gv);
+        const float aw = (arow && ok) ? w1r[c] : 0.f;
+        const float cac = s_ca[c];
+        float pa = 0.f, pq = 0.f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          m[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw, ok ? xv[e] : 0.f, m[e], 0, 0, 0);
+          const float p = ok ? xv[e] * gv[e] * live : 0.f;
+          accp[e] += cac * p;
+          pa += p * sav[e];
+          pq += p * (cac * sav[e] - 1.f);
+        }
+        pa = wave_group_sum(pa, TX);
+        pq = wave_group_sum(pq, TX);
+        if (tx == 0 && ok) { s_aq[c] = pa; s_aq[g.C + c] = pq; }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { accP[0][e] = m[e].x; accP[1][e] = m[e].y; accP[2][e] = m[e].z; accP[3][e] = m[e].w; }
+      mfma_done = true;
+    }
+  }
+#pragma unroll 4
+  for (int c = mfma_done ? g.C : ty; c < g.C; c += TY) {
     float xv[VEC], gv[VEC];
     load_vec<T, VEC>(xp + static_cast<size_t>(c) * g.HW, xv);
     load_vec<T, VEC>(gp + static_cast<size_t>(c) * g.HW, gv);
@@ -176,11 +227,38 @@ __device__ __forceinline__ void bwd_reduce1_body(const BwdArgs& A, const int bid
         }
       }
     }
+    if constexpr (VEC == 4 && sizeof(T) == 4) {
+      if (wide) {                                                // the four waves' 16 x 64 partials: waves 1..3 through LDS, wave 0 adds them in order
+        const int wave = tid >> 6, lane = tid & (kWave - 1);
+        if (!FOLD) __syncthreads();                              // the combine buffer is free (FOLD: the publish ended in a barrier)
+        if (wave) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sm[(((wave - 1) * 4 + r) * 4 + e) * kWave + lane] = accP[r][e];
+        }
+        __syncthreads();
+        if (wave == 0) {
+          for (int w = 0; w < kBlock / kWave - 1; ++w)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) accP[r][e] += sm[((w * 4 + r) * 4 + e) * kWave + lane];
+          if (active) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int j = 4 * ty + r;                          // (wave 0: ty = lane / 16)
+              if (j < g.proj_h) store_vec<float, VEC>(A.c.proj + (static_cast<size_t>(b) * g.proj_h + j) * g.HW + static_cast<size_t>(i) * VEC, accP[r]);
+            }
+          }
+        }
+      }
+    }
   }
 }
 
 template <typename T, int VEC, bool PROJ>
-__global__ __launch_bounds__(kBlock) void k_bwd_reduce1(const Group<BwdArgs> G) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PROJ ? 2 : 1))) void k_bwd_reduce1(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
@@ -292,7 +370,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_convT(const Group<BwdArgs> G) {
 // latency-bound conv overlaps the streaming tail and one launch boundary disappears.  Flags: one generation counter per k_bwd_reduce1
 // tile and per conv tile in ctx.sync (zero-filled by the caller once, never reset: see bwd_convT_body).
 template <typename T, int VEC, int K, bool PROJ>
-__global__ __launch_bounds__(kBlock) void k_bwd_reduce1_fold(const Group<BwdArgs> G) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PROJ ? 2 : 1))) void k_bwd_reduce1_fold(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
@@ -406,7 +484,6 @@ __global__ __launch_bounds__(kBlock) void k_bwd_wsa(const Group<BwdArgs> G) {
 // (ROCm 7.2's clang narrows the b128 builtin to ONE dword splatted over the vector when its elements are extracted with a loop index
 //  -- seen in the .s and on the device -- so the vector is bit-cast whole and its members are named)
 typedef unsigned int v4u32_t __attribute__((ext_vector_type(4)));
-typedef float v4f32_t __attribute__((ext_vector_type(4)));
 template <int VEC>
 __device__ __forceinline__ void load_plane_agent(__amdgpu_buffer_rsrc_t rsrc, const int elem, float (&out)[VEC]) {
   if constexpr (VEC % 4 == 0) {
@@ -608,7 +685,7 @@ struct R12Group {
   int seg[4][kGroupMax + 1];     // seg[p][l]: first workgroup id of level l in phase p; seg[p][n]: end of phase p
 };
 template <typename T, int VEC, int CPT, bool PROJ>   // PROJ: some level's tiles make the W1-projection planes (bwd_reduce1_body)
-__global__ __launch_bounds__(kBlock) void k_bwd_r12(const R12Group R) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PROJ ? 2 : 1))) void k_bwd_r12(const R12Group R) {
   extern __shared__ __align__(16) float smem[];
   const int bid = blockIdx.x;
   int p = 0;
@@ -751,7 +828,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_params(const Group<BwdArgs> G) {
 //   the arg-max position, g_mx/N for the GAP fallback} in LDS, and K_b = sum_c g_avg * mavg * [S >= eps].
 //   LDS: [C float4 q][2*hidden][256*VEC combine]
 // ---------------------------------------------------------------------------------------------
-template <typename T, int VEC, bool GMASK>
+template <typename T, int VEC, bool GMASK, bool NEEDX>   // NEEDX = false: every level of the launch has planes (host), no lane reads x
 __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, float* smem, float* red) {
   constexpr int UN = 2;   // channels a thread requests before the prologue (1 or 2, and unroll 1/2/4/8 of the channel loop: within noise, 54.5-57.7 us)
   const Geo& g = A.g;
@@ -799,7 +876,7 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
 
   // With the W1-projection planes (written by the k_bwd_reduce1 tiles, or by the forward's k_chan), sum_c g_avg[b,c]*x[b,c,hw] =
   // sum_j g_h[b,j]*P[b,j,hw]: x is not read.
-  const bool need_x = GMASK && g.proj_h == 0;
+  const bool need_x = NEEDX && GMASK && g.proj_h == 0;
   // first feature vectors are requested before the prologue so its latency overlaps theirs
   float g0v[UN][VEC], x0v[UN][VEC];
 #pragma unroll
@@ -807,6 +884,14 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
     const size_t co = static_cast<size_t>(min(ty + u * TY, g.C - 1)) * g.HW;
     load_vec<T, VEC>(gp + co, g0v[u]);
     if (GMASK) { if (need_x) load_vec<T, VEC>(xp + co, x0v[u]); }
+  }
+  // a level with planes: row j of the thread grid requests plane j of the tile's pixels now (TY >= 4; the host gives wider planes only to
+  // TX = 16 levels, TY = 16), so the planes cost no memory latency after the streaming loop: one vector per lane, held across it
+  // (fp32 levels; the half-precision kernels, whose planes only the forward can have saved, keep the loop after the streaming loop)
+  const bool prow = GMASK && sizeof(T) == 4 && g.proj_h > 0 && g.proj_h <= TY;
+  float pjv[VEC];
+  if (GMASK) {
+    if (prow && ty < g.proj_h) load_vec<float, VEC>(A.c.proj + (static_cast<size_t>(b) * g.proj_h + ty) * g.HW + static_cast<size_t>(ii) * VEC, pjv);
   }
 
   // ---- prologue: q[c] and K_b for this sample -------------------------------------------------------------------
@@ -925,6 +1010,12 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
 #pragma unroll
       for (int e = 0; e < VEC; ++e) sm[tid * VEC + e] = accp[e];
       __syncthreads();
+    } else if (prow) {
+      if (ty < g.proj_h) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) sm[tid * VEC + e] = pjv[e];
+      }
+      __syncthreads();
     }
     if (ty == 0 && active) {
       if (need_x) {
@@ -933,8 +1024,15 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
 #pragma unroll
           for (int e = 0; e < VEC; ++e) accp[e] += sm[o + e];
         }
+      } else if (prow) {                                       // sum_j g_h_avg[b,j] * P[b,j,hw], j ascending: the order of the loop below
+        for (int j = 0; j < g.proj_h; ++j) {
+          const float gh = s_gh[j];
+          const int o = (j * TX + tx) * VEC;
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) accp[e] += gh * sm[o + e];
+        }
       } else {
-        for (int j = 0; j < g.proj_h; ++j) {                   // sum_j g_h_avg[b,j] * P[b,j,hw]
+        for (int j = 0; j < g.proj_h; ++j) {                   // (half-precision levels with planes the forward saved)
           float pv[VEC];
           load_vec<float, VEC>(A.c.proj + (static_cast<size_t>(b) * g.proj_h + j) * g.HW + static_cast<size_t>(i) * VEC, pv);
           const float gh = s_gh[j];
@@ -964,7 +1062,7 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
 // (amdgpu_waves_per_eu(5) -- 94 instead of 104 VGPRs, 5 instead of 4 workgroups per CU -- was measured: config 2 fp32 57.9 -> 55.8 us,
 //  bf16 37.3 -> 38.5, config 4 200 -> 225 us; not adopted.  tools/trace_gate.py bwd shows the launch as two rounds of
 //  ~5 us prologue + ~19 us streaming per workgroup with HBM saturated during the streaming.)
-template <typename T, int VEC, bool GMASK, bool ROLES>
+template <typename T, int VEC, bool GMASK, bool ROLES, bool NEEDX = true>
 __global__ __launch_bounds__(kBlock) void k_bwd_apply(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   __shared__ float red[8];
@@ -987,7 +1085,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_apply(const Group<BwdArgs> G) {
     }
     local -= npad;
   }
-  bwd_apply_body<T, VEC, GMASK>(A, local, smem, red);
+  bwd_apply_body<T, VEC, GMASK, NEEDX>(A, local, smem, red);
 }
 
 }  // namespace mgacbam

@@ -314,7 +314,16 @@ static size_t nhwc_ws_bytes(int B, int C, int H, int W, int vec) {
 }
 
 // backward scratch of a level of either layout (vec: level_vec); the two layouts differ in the partials of A_part and pgh
-struct ScratchLayout { size_t A_part, gpre, gplanes, gwsa_part, gz, gbq, gh_avg, gh_mx, pgh, total; };
+struct ScratchLayout { size_t A_part, gpre, gplanes, gwsa_part, gz, gbq, gh_avg, gh_mx, pgh, proj, total; };
+// W1-projection planes of a level with kProjMax < hidden <= kProjWide (bwd.cuh): made by the k_bwd_reduce1 tiles on the matrix cores and
+// read by k_bwd_apply within one backward, so they live in the scratch buffer (its LAST region), not in the ctx.  Everything the rule asks
+// of the level except what the scratch size cannot know (fp32 features, gmask wanted: backward_args).  The tiles' wave must be the B operand
+// of v_mfma_f32_16x16x4_f32 -- 4 channel rows x 16 lanes of 4 pixels: VEC 4, chan_tx 16 -- and x at least 1 MiB: a smaller level is still
+// in the cache when k_bwd_apply reads it again, so its planes would save nothing.
+static bool wide_proj_shape(int B, int C, int H, int W, int hidden, bool nhwc, int vec, const Tune& t) {
+  return !nhwc && hidden > kProjMax && hidden <= kProjWide && vec == 4 && t.chan_tx == 16 &&
+         static_cast<size_t>(B) * C * H * W * sizeof(float) >= (size_t(1) << 20);
+}
 static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int k, bool nhwc, int vec) {
   // the tile counts follow the launch geometry, which follows the knobs (NHWC: only the conv tiling, which does not depend on B, is used)
   const Tune t = choose_tune(B, C, H, W, k);
@@ -331,12 +340,13 @@ static ScratchLayout scratch_layout(int B, int C, int H, int W, int hidden, int 
   // channel groups per sample -- NCHW: worst case (1 channel per row of the sweep kernels), NHWC: blocks of kNhwcFoldC
   const size_t cpg = nhwc ? kNhwcFoldC : kBlock / t.pool_tx;
   L.pgh = cv.take(static_cast<size_t>(B) * ((C + cpg - 1) / cpg) * hidden);
+  L.proj = cv.take(wide_proj_shape(B, C, H, W, hidden, nhwc, vec, t) ? static_cast<size_t>(B) * hidden * HW : 0);   // (B, hidden, HW)
   L.total = cv.total;
   return L;
 }
 static ScratchPtrs scratch_ptrs(void* p, const ScratchLayout& L) {
   return ScratchPtrs{at(p, L.A_part), at(p, L.gpre), at(p, L.gplanes), at(p, L.gwsa_part), at(p, L.gz), at(p, L.gbq),
-                     at(p, L.gh_avg), at(p, L.gh_mx), at(p, L.pgh)};
+                     at(p, L.gh_avg), at(p, L.gh_mx), at(p, L.pgh), at(p, L.proj)};
 }
 // the size queries take no element type: the answer covers every one (the NCHW geometry does not depend on it)
 static size_t ws_bytes_any(int B, int C, int H, int W, bool nhwc) {
@@ -517,9 +527,11 @@ static int gate_tiles(const Tune& t, int H, int W, int vec) {
   return (nv + t.gate_tx - 1) / t.gate_tx;
 }
 static size_t bwd_apply_smem(const Geo& g, int vec) { return (5 * static_cast<size_t>(g.C) + 2 * g.hidden + kBlock * vec) * sizeof(float); }
-// (proj: the level's tiles also make its W1-projection planes -- W1^T staged after the partials, four planes per combine round)
-static size_t reduce1_smem(const Geo& g, int vec, bool proj) {
+// (proj: the level's tiles also make its W1-projection planes -- 1, the VALU form: W1^T staged after the partials, four planes per combine
+//  round; 2, the MFMA form: W1 comes from memory, and three waves' 16 x 64 partials are combined in one round)
+static size_t reduce1_smem(const Geo& g, int vec, int proj) {
   if (!proj) return (3 * static_cast<size_t>(g.C) + kBlock * vec) * sizeof(float);
+  if (proj == 2) return (((3 * static_cast<size_t>(g.C) + 3) & ~static_cast<size_t>(3)) + 3 * 16 * kWave) * sizeof(float);
   return (((3 * static_cast<size_t>(g.C) + 3) & ~static_cast<size_t>(3)) + static_cast<size_t>(g.C) * kProjMax + 4 * kBlock * vec) * sizeof(float);
 }
 static size_t mlp_smem(const Geo& g) { return (3 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }
