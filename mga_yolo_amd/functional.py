@@ -96,6 +96,16 @@ class _Lease:
             pass
 
 
+def status_words(bufs_and_shapes) -> List[int]:
+    """The hand-off status word (include/mgacbam.h) of each ctx buffer, given as (buffer, (B,C,H,W,hidden)), after ONE concatenated device
+    read -- which waits for the work queued before it, as any read-back does.  Non-zero: a hand-off into that buffer timed out."""
+    words = []
+    for buf, (B, Cc, H, W, hidden) in bufs_and_shapes:
+        off = _lib.ctx_layout(B, Cc, H, W, hidden)["status"]
+        words.append(buf[off:off + 4].view(torch.int32))
+    return torch.cat(words).cpu().tolist()
+
+
 def handoff_report(clear_pool: bool = False):
     """Synchronise and read the hand-off status word of every ctx buffer the eager path has handed out and that is still alive.
     Returns the number of buffers checked; raises HandoffTimeout if any word is set.  Call it where the training loop synchronises
@@ -104,12 +114,7 @@ def handoff_report(clear_pool: bool = False):
     live = [(b, k) for b, k in live if b is not None]
     if not live:
         return 0
-    words = []
-    for buf, key in live:
-        B, Cc, H, W, hidden = key[2:7]
-        off = _lib.ctx_layout(B, Cc, H, W, hidden)["status"]
-        words.append(buf[off:off + 4].view(torch.int32))
-    bad = [k for (b, k), w in zip(live, torch.cat(words).cpu().tolist()) if w != 0]
+    bad = [k for (b, k), w in zip(live, status_words((b, k[2:7]) for b, k in live)) if w != 0]
     if clear_pool:
         _POOL.clear()
     if bad:
@@ -119,9 +124,8 @@ def handoff_report(clear_pool: bool = False):
 
 
 def _check_status(bufs_and_shapes, what: str):
-    for buf, (B, Cc, H, W, hidden) in bufs_and_shapes:
-        off = _lib.ctx_layout(B, Cc, H, W, hidden)["status"]
-        if int(buf[off:off + 4].view(torch.int32).item()) != 0:          # (.item() synchronises)
+    for (_, (B, Cc, H, W, _)), w in zip(bufs_and_shapes, status_words(bufs_and_shapes)):     # (the read synchronises)
+        if w != 0:
             raise HandoffTimeout(f"{what}: in-launch hand-off timed out for level (B,C,H,W)=({B},{Cc},{H},{W})")
 
 
@@ -151,6 +155,13 @@ def _ready_nhwc(t: torch.Tensor) -> torch.Tensor:
     if t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0:
         return t
     return t.detach().clone(memory_format=torch.channels_last)
+
+
+def _feature_in(x: torch.Tensor, nhwc_ok: bool = True):
+    """-> (x as the kernels read it, whether that is channels_last).  The layout decides the kernels, per level (_is_nhwc); nhwc_ok=False
+    keeps a level the channels-last kernels do not take on the NCHW path."""
+    nhwc = nhwc_ok and _is_nhwc(x)
+    return (_ready_nhwc(x) if nhwc else _ready(x)), nhwc
 
 
 def _param32(t: torch.Tensor) -> torch.Tensor:
@@ -209,8 +220,8 @@ def _cbam_inputs(x, mask, params, cfg: BlockConfig):
     B, _, H, W = x.shape
     m32, mmeta = _mask_in(mask, B, H, W)
     _check_params(x, params, cfg)
-    nhwc = _is_nhwc(x)
-    return (_ready_nhwc(x) if nhwc else _ready(x)), m32, [_ready(p) for p in params], (_lib.LAYOUT_NHWC if nhwc else 0), mmeta
+    xc, nhwc = _feature_in(x)
+    return xc, m32, [_ready(p) for p in params], (_lib.LAYOUT_NHWC if nhwc else 0), mmeta
 
 
 class _PyramidFn(torch.autograd.Function):
@@ -382,9 +393,8 @@ class _EcaFn(torch.autograd.Function):
             m32, mmeta = _mask_in(mask, B, H, W)
             if tuple(w.shape) != (1, 1, cfg.k) or beta.dim() != 0:
                 raise ValueError(f"MaskECA parameters: expected conv1d.weight (1,1,{cfg.k}) and scalar beta")
-            nhwc = _is_nhwc(x) and Cc <= _ECA_NHWC_MAX_C
+            xc, nhwc = _feature_in(x, Cc <= _ECA_NHWC_MAX_C)
             flags = _lib.LAYOUT_NHWC if nhwc else 0
-            xc = _ready_nhwc(x) if nhwc else _ready(x)
             wc, bc = _param32(w), _param32(beta)
             y = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
             cbuf = torch.empty(_lib.eca_ctx_bytes(B, Cc, H, W, flags), dtype=torch.uint8, device=dev)
@@ -722,9 +732,8 @@ class _HeadFn(torch.autograd.Function):
                 raise ValueError(f"mask_head: parameter shapes do not match C={Cc}, hidden={hid} (out_channels must be 1)")
             if training and B * H * W == 1:                     # torch.nn.functional.batch_norm refuses this too (no variance from one value)
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
-            nhwc = _is_nhwc(x)                                  # the layout decides the GEMM kernels, per level (MaskCBAM's rule)
+            xc, nhwc = _feature_in(x)                           # the layout decides the GEMM kernels, per level (MaskCBAM's rule)
             fl = _lib.HEAD_LAYOUT_NHWC if nhwc else 0
-            xc = _ready_nhwc(x) if nhwc else _ready(x)
             pc = [_param32(t) for t in (w1, gamma, beta, wh, bh)]
             for t in (rmean, rvar):
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
@@ -880,8 +889,7 @@ class _SpadeFn(torch.autograd.Function):
             if not x.is_cuda or x.device != dev:
                 raise RuntimeError("mask_spade: all features must live on the same GPU")
             B, Cc, H, W = x.shape
-            nhwc = _is_nhwc(x)
-            xc = _ready_nhwc(x) if nhwc else _ready(x)
+            xc, nhwc = _feature_in(x)
             m32, mmeta = _mask_in(mask, B, H, W)
             ps = [None] * 6 if mask is None else [_param32(t) for t in (w0, b0, wg, bg, wb, bb)]
             y = torch.empty_like(xc)                                # (preserve_format: channels_last for a channels_last level)

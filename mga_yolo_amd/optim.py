@@ -27,6 +27,8 @@ import torch
 
 from . import _lib
 from ._binding import call, fill_opt_segment
+from .plan import _BlockPlan
+from .slice import HEAD_PARAM_NAMES, SlicePlan
 
 GROUP_BIAS, GROUP_DECAY, GROUP_NORM = 0, 1, 2         # optimizer.param_groups after build_optimizer (trainer.py:929, 940, 941)
 # plan-side parameter names -> the reference modules' names (MaskECA's, MaskSPADE's and the head's already are the reference's)
@@ -345,17 +347,11 @@ class BucketOptimizer:
 
 def plan_segments(plan, ema: bool = True) -> List[Segment]:
     """for_plan's segment list: every parameter tensor the plan reads, under its reference name, classified with the reference's rule."""
-    from .plan import ECA_PARAM_NAMES, PARAM_NAMES, SPADE_PARAM_NAMES, EcaPyramidPlan, PyramidPlan, SpadePyramidPlan
-    from .slice import HEAD_PARAM_NAMES, SlicePlan
     blk = plan.block if isinstance(plan, SlicePlan) else plan
-    if isinstance(blk, PyramidPlan):
-        kind, names = "cbam", [CBAM_REFERENCE_NAMES[n] for n in PARAM_NAMES]
-    elif isinstance(blk, EcaPyramidPlan):
-        kind, names = "eca", list(ECA_PARAM_NAMES)
-    elif isinstance(blk, SpadePyramidPlan):
-        kind, names = "spade", list(SPADE_PARAM_NAMES)
-    else:
+    if not isinstance(blk, _BlockPlan):
         raise TypeError(f"BucketOptimizer.for_plan: {type(plan).__name__} is none of the static plans")
+    kind = blk.kind
+    names = [CBAM_REFERENCE_NAMES[n] for n in blk.param_names] if kind == "cbam" else blk.param_names
     segs = []
     for l in range(blk.n):
         segs += [Segment(f"block{l}.{n}", p, g, reference_group(kind, n)) for n, p, g in zip(names, blk.params[l], blk.param_grads[l])]
@@ -364,7 +360,7 @@ def plan_segments(plan, ema: bool = True) -> List[Segment]:
             segs += [Segment(f"head{l}.{n}", p, g, reference_group("head", n)) for n, p, g in zip(HEAD_PARAM_NAMES, plan.head_params[l], plan.head_grads[l])]
         segs.append(Segment("mtl_log_vars", plan.log_vars, plan.g_log_vars, reference_group("model", "mtl_log_vars")))
     if ema:                                                              # the floating-point buffers of the state dict (torch_utils.py:771-774)
-        for l, run in enumerate(getattr(blk, "running", [])):
+        for l, run in enumerate(blk.running):
             if run is not None and run[0] is not None:
                 segs += [Segment(f"block{l}.norm.{n}", b, None, GROUP_DECAY) for n, b in zip(("running_mean", "running_var"), run)]
         if isinstance(plan, SlicePlan):

@@ -20,8 +20,9 @@ ProbMaskGater before MaskCBAM_l (masked_cbam.py:163-164) while the loss keeps re
 levels, the noise drawn in the kernel (include/mgagate.h).
 
 ``SlicePlan.create(..., block="cbam" | "eca" | "spade", channels_last=, target_resize=, block_running=)`` builds the same slice around MaskECA or
-MaskSPADE (configs/models/yolov8_eca.yaml, yolov8_spade.yaml share the layer loop) and in either feature layout; the constructor itself keeps its
-arguments and builds the MaskCBAM / NCHW slice.
+MaskSPADE (configs/models/yolov8_eca.yaml, yolov8_spade.yaml share the layer loop) and in either feature layout; the constructor builds the
+MaskCBAM / NCHW slice.  The block is one of plan.py's pyramid plans (``plan.block``), whose buffers the heads and the loss are wired to; the
+slice issues and captures its library calls the way they do (``plan._Executor``).
 
 ``SlicePlan.create(..., target_source=(Hm, Wm), target_method=, target_bridge=)`` makes the targets part of the step: the plan owns
 ``mask_full`` (B,Hm,Wm) uint8 -- the batch's masks at image resolution, what the caller fills instead of ``targets`` -- and ``forward`` starts
@@ -36,7 +37,7 @@ import torch
 from . import _lib
 from ._binding import fill_head_bwd, fill_head_fwd, fill_seg
 from .functional import BlockConfig, GateConfig, TargetPyramidCall, target_pyramid_check, target_pyramid_shapes
-from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan
+from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan, _carve, _Executor
 
 BLOCKS = ("cbam", "eca", "spade")
 TARGET_RESIZE = {"nearest": _lib.SEG_NEAREST, "bilinear": _lib.SEG_BILINEAR}
@@ -63,7 +64,7 @@ def target_strides(shapes, target_source) -> Tuple[int, ...]:
     return tuple(out)
 
 
-class SlicePlan:
+class SlicePlan(_Executor):
     def __init__(self, shapes: Sequence[Tuple[int, int, int, int]], hidden: Sequence[int], cbam_params, cbam_cfgs: Sequence[BlockConfig],
                  head_states: Sequence[dict], target_hw: Sequence[Tuple[int, int]] = None, scale_weights=(1.0, 1.0, 1.0),
                  bn_eps: float = 1e-3, bn_momentum: float = 0.03, device="cuda", training: bool = True, dtype: torch.dtype = torch.float32,
@@ -84,8 +85,8 @@ class SlicePlan:
     @classmethod
     def create(cls, shapes, hidden, block_params, block_cfgs, head_states, *, block: str = "cbam", channels_last: bool = False,
                target_resize: str = "nearest", block_running=None, **kw) -> "SlicePlan":
-        """The constructor for every model file of the reference (yolov8_cbam / _eca / _spade.yaml share this slice) and both feature layouts;
-        the constructor's own argument list is what every caller passes today and stays as it is.
+        """The constructor for every model file of the reference (yolov8_cbam / _eca / _spade.yaml share this slice) and both feature layouts
+        (why there are two: plan._BlockPlan).
         block: "cbam" | "eca" | "spade" -- block_params / block_cfgs are then per level (w1,b1,w2,b2,wsa,beta) with BlockConfig,
         (conv1d.weight, beta) with EcaConfig, or the six MaskSPADE tensors with SpadeConfig; block_running: per level MaskSPADE's batch-norm
         buffers (running_mean, running_var, num_batches_tracked) or None.  The matching pyramid plan is ``plan.block`` (``plan.cbam`` as well
@@ -156,27 +157,19 @@ class SlicePlan:
         n_head = sum(p.numel() for ps in self.head_params for p in ps)
         self.grad_bucket = torch.zeros(n_block + n_head + 2, dtype=f32, device=dev)
         self.dtype = dtype
-        common = dict(dtype=dtype, device=dev, with_mask=True, want_gmask=True, grad_bucket=self.grad_bucket[:n_block])
+        common = dict(dtype=dtype, device=dev, with_mask=True, want_gmask=True, channels_last=channels_last, grad_bucket=self.grad_bucket[:n_block])
         if block == "cbam":
-            self.block = PyramidPlan.create(shapes, block_params, block_cfgs, channels_last=channels_last, gate=gate, seed=seed, **common)
-            self.cbam = self.block
+            self.block = self.cbam = PyramidPlan.create(shapes, block_params, block_cfgs, gate=gate, seed=seed, **common)
         elif block == "eca":
-            self.block = EcaPyramidPlan.create(shapes, block_params, block_cfgs, channels_last=channels_last, **common)
+            self.block = EcaPyramidPlan.create(shapes, block_params, block_cfgs, **common)
         else:
-            self.block = SpadePyramidPlan(shapes, block_params, block_cfgs, channels_last=channels_last, running=block_running, **common)
+            self.block = SpadePyramidPlan(shapes, block_params, block_cfgs, running=block_running, **common)
         blk = self.block
         self.gated = gate is not None
         # without a gate the heads write straight into the block's mask input; with one, into the gate's input
         self.x, self.logits, self.y, self.gy, self.gx = blk.x, (blk.logits if self.gated else blk.mask), blk.y, blk.gy, blk.gx
         g_logits2 = blk.glogits if self.gated else blk.gmask
-        off = n_block
-        self.head_grads: List[List[torch.Tensor]] = []
-        for ps in self.head_params:
-            views = []
-            for p in ps:
-                views.append(self.grad_bucket[off:off + p.numel()].view(p.shape))
-                off += p.numel()
-            self.head_grads.append(views)
+        self.head_grads, off = _carve(self.grad_bucket, self.head_params, n_block)       # behind the block's views
         self.g_log_vars = self.grad_bucket[off:off + 2]
         # ---- loss side --------------------------------------------------------------------------------------------------------------
         self.log_vars = torch.zeros(2, dtype=f32, device=dev)          # mtl_log_vars (model.py:119-121)
@@ -211,48 +204,32 @@ class SlicePlan:
                           hfl | _lib.HEAD_BWD_ACCUM_GX | _lib.HEAD_LOGITS_F32)
 
     # ------------------------------------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def forward(self):
-        st = self._stream()
         if self._tgt is not None:
             self._tgt.run()                                                                            # mask_full -> targets
-        _lib.check(self.lib.mgahead_forward(self._hf, self.n, st), "mgahead_forward")                 # features -> mask logits
+        self._call("mgahead_forward", self._hf, self.n)                                                # features -> mask logits
         self.block.forward()                                                                           # [feature, logits] -> refined (a gate first: logits -> mask)
         # logits, targets -> seg_total (+ log entries) -> Kendall total, the combine riding in the loss's last launch
-        _lib.check(self.lib.mgaseg_kendall_forward(self._seg, self.n, C.byref(self._seg_cfg), self.seg_ws.data_ptr(), self.seg_ws.numel(), self.seg_out.data_ptr(),
-                                                   self.det_loss.data_ptr(), 3, self.log_vars.data_ptr(), self.total.data_ptr(), st),
-                   "mgaseg_kendall_forward")
+        self._call("mgaseg_kendall_forward", self._seg, self.n, C.byref(self._seg_cfg), self.seg_ws.data_ptr(), self.seg_ws.numel(), self.seg_out.data_ptr(),
+                   self.det_loss.data_ptr(), 3, self.log_vars.data_ptr(), self.total.data_ptr())
 
     def backward(self):
-        st = self._stream()
-        _lib.check(self.lib.mgaseg_kendall_backward(self._seg, self.n, C.byref(self._seg_cfg), self.seg_ws.data_ptr(), self.seg_ws.numel(), self.seg_out.data_ptr(),
-                                                    self.det_loss.data_ptr(), 3, self.log_vars.data_ptr(), self.g_total.data_ptr(),
-                                                    self.g_det.data_ptr(), self.g_seg.data_ptr(), self.g_log_vars.data_ptr(), st),
-                   "mgaseg_kendall_backward")                                                          # -> seg_glogits, g_det, g_log_vars
+        self._call("mgaseg_kendall_backward", self._seg, self.n, C.byref(self._seg_cfg), self.seg_ws.data_ptr(), self.seg_ws.numel(), self.seg_out.data_ptr(),
+                   self.det_loss.data_ptr(), 3, self.log_vars.data_ptr(), self.g_total.data_ptr(),
+                   self.g_det.data_ptr(), self.g_seg.data_ptr(), self.g_log_vars.data_ptr())          # -> seg_glogits, g_det, g_log_vars
         self.block.backward()                                                                          # gy -> gx (MaskCBAM's part), dL/dmask (its part of dL/dlogits; a gate's backward last)
-        _lib.check(self.lib.mgahead_backward(self._hb, self.n, st), "mgahead_backward")                # gx += head's part; head parameter gradients
+        self._call("mgahead_backward", self._hb, self.n)                                               # gx += head's part; head parameter gradients
 
     def step(self):
         self.forward()
         self.backward()
 
-    capture = PyramidPlan.capture
-
     def check_handoff(self):
         if self.block_name == "cbam":                                  # the other blocks have no in-launch hand-off
             self.block.check_handoff()
 
-    def images(self) -> int:
-        return self.shapes[0][0]
-
     def launches(self) -> dict:
         t = "" if self._tgt is None else f"{self._tgt.launches} (targets) + "
-        if self.block_name == "cbam" and not self.channels_last:
-            g = " + 1 (gate)" if self.gated else ""
-            return dict(forward=f"{t}3 (heads){g} + 2 (MaskCBAM) + 2 (seg loss + Kendall)",
-                        backward=f"1 (seg loss + Kendall) + 2 (MaskCBAM){g} + 5 (heads)")
         name = dict(cbam="MaskCBAM", eca="MaskECA", spade="MaskSPADE")[self.block_name]
         g = " + 1 (gate)" if self.gated else ""
         fwd, bwd = self.block.launch_counts()                          # what the block's library calls enqueue (plan.py)

@@ -116,6 +116,57 @@ def test_slice_plan_constructor_is_the_cbam_nchw_plan(built_lib):
                                    backward="1 (seg loss + Kendall) + 2 (MaskCBAM) + 5 (heads)")
 
 
+# ---------------------------------------------------------------------------------------------------------------- one base
+@pytest.mark.parametrize("block", ["cbam", "eca", "spade"])
+def test_pyramid_plans_share_one_base(built_lib, block):
+    """one set-up for the three plans: a subclass brings its library calls, and defines none of what the base owns a second time"""
+    from mga_yolo_amd import plan as P
+    plan, _ = _pyramid(block)
+    cls = type(plan)
+    assert isinstance(plan, P._BlockPlan) and cls.__mro__[1] is P._BlockPlan and plan.kind == block
+    for name in ("x", "mask", "y", "gy", "gx", "gmask", "ctx", "scratch", "params", "param_grads", "cfgs", "shapes", "_fwd", "_bwd"):
+        assert len(getattr(plan, name)) == plan.n == 3, name
+    assert len(plan.running) == 3 and all(len(run) == 3 for run in plan.running)
+    assert [run[0] is not None for run in plan.running] == [False, block == "spade", False]          # the batch-norm level of _modules
+    assert len(plan.param_names) == len(plan.grad_names) == len(plan.params[0])
+    for name in ("forward", "backward", "launch_counts"):
+        assert name in vars(cls), name
+    for name in ("capture", "elements", "images", "named_param_grads", "_stream", "_call"):
+        assert name not in vars(cls) and callable(getattr(plan, name)), name
+    from mga_yolo_amd import SlicePlan
+    assert SlicePlan.capture is P._BlockPlan.capture and SlicePlan._call is P._BlockPlan._call and "images" not in vars(SlicePlan)
+
+
+_HEAD_SEGMENTS = [f"head{l}.{n}" for l in range(3) for n in ("proj.0.weight", "proj.1.weight", "proj.1.bias", "head.weight", "head.bias")]
+_HEAD_EMA_SEGMENTS = ["head0.proj.1.running_mean", "head0.proj.1.running_var", "head1.proj.1.running_mean", "head1.proj.1.running_var",
+                      "head2.proj.1.running_mean", "head2.proj.1.running_var"]
+_BLOCK_SEGMENTS = dict(
+    cbam=["block0.cam_mlp.0.weight", "block0.cam_mlp.0.bias", "block0.cam_mlp.2.weight", "block0.cam_mlp.2.bias", "block0.sam_conv.weight", "block0.beta",
+          "block1.cam_mlp.0.weight", "block1.cam_mlp.0.bias", "block1.cam_mlp.2.weight", "block1.cam_mlp.2.bias", "block1.sam_conv.weight", "block1.beta",
+          "block2.cam_mlp.0.weight", "block2.cam_mlp.0.bias", "block2.cam_mlp.2.weight", "block2.cam_mlp.2.bias", "block2.sam_conv.weight", "block2.beta"],
+    eca=["block0.conv1d.weight", "block0.beta", "block1.conv1d.weight", "block1.beta", "block2.conv1d.weight", "block2.beta"],
+    spade=["block0.shared.0.weight", "block0.shared.0.bias", "block0.conv_gamma.weight", "block0.conv_gamma.bias", "block0.conv_beta.weight", "block0.conv_beta.bias",
+           "block1.shared.0.weight", "block1.shared.0.bias", "block1.conv_gamma.weight", "block1.conv_gamma.bias", "block1.conv_beta.weight", "block1.conv_beta.bias",
+           "block2.shared.0.weight", "block2.shared.0.bias", "block2.conv_gamma.weight", "block2.conv_gamma.bias", "block2.conv_beta.weight", "block2.conv_beta.bias"])
+_BLOCK_EMA_SEGMENTS = dict(cbam=[], eca=[], spade=["block1.norm.running_mean", "block1.norm.running_var"])       # the batch-norm level of _modules
+
+
+@pytest.mark.parametrize("block", ["cbam", "eca", "spade"])
+def test_segment_order(built_lib, block):
+    """The names and the order of optim.plan_segments for SHAPES, as recorded before the plans shared a base: optimizer state and checkpoints
+    are keyed and laid out by them.  [block, level by level][heads, level by level][mtl_log_vars][the block's averaged buffers][the heads']."""
+    from mga_yolo_amd import SlicePlan
+    from mga_yolo_amd.optim import plan_segments
+    plan, params = _pyramid(block)
+    assert [s.name for s in plan_segments(plan)] == _BLOCK_SEGMENTS[block] + _BLOCK_EMA_SEGMENTS[block]
+    _, cfgs, running = _modules(block)
+    sp = SlicePlan.create(SHAPES, HIDDEN, params, cfgs, _head_states(), block=block, block_running=running, device="cpu")
+    assert [s.name for s in plan_segments(sp)] == (_BLOCK_SEGMENTS[block] + _HEAD_SEGMENTS + ["mtl_log_vars"] + _BLOCK_EMA_SEGMENTS[block]
+                                                   + _HEAD_EMA_SEGMENTS)
+    with pytest.raises(TypeError, match="none of the static plans"):
+        plan_segments(object())
+
+
 # ---------------------------------------------------------------------------------------------------------------- flags and sizes
 @pytest.mark.parametrize("channels_last", [False, True])
 @pytest.mark.parametrize("block", ["cbam", "eca", "spade"])
