@@ -18,9 +18,10 @@ from .module import MGAMaskHead, MaskCBAM, MaskECA, MaskSPADE, MaskSPADEConfig, 
 from .segloss import SegLossConfig, SegmentationLoss, kendall_combine  # noqa: F401
 from .optim import BucketOptimizer, OptConfig  # noqa: F401
 from .detloss import DetLossPlan, V8DetectionLoss, detection_loss  # noqa: F401
+from .detpost import DetPostPlan, detect_postprocess, non_max_suppression  # noqa: F401
 
 __all__ = ["MaskCBAM", "MaskECA", "MaskSPADE", "MaskSPADEConfig", "SpadeConfig", "mask_spade", "mask_spade_pyramid", "MGAMaskHead", "mask_head", "mask_head_pyramid", "ProbMaskGater", "BlockConfig", "EcaConfig", "mask_cbam", "mask_cbam_pyramid", "mask_eca",
            "mask_eca_pyramid", "prob_mask_gate", "prob_mask_gate_pyramid", "GateConfig", "gate_state", "resize_nearest", "mask_pyramid", "install", "uninstall", "SegLossConfig", "SegmentationLoss", "kendall_combine", "HandoffTimeout", "handoff_report",
            "PyramidPlan", "EcaPyramidPlan", "SpadePyramidPlan", "SlicePlan", "BucketOptimizer", "OptConfig",
-           "detection_loss", "V8DetectionLoss", "DetLossPlan"]
+           "detection_loss", "V8DetectionLoss", "DetLossPlan", "detect_postprocess", "non_max_suppression", "DetPostPlan"]
 __version__ = "0.1.0"

@@ -227,3 +227,24 @@ def fill_det(D: _lib.DetDesc, feats, strides, nc: int, topk: int, m_cap: int, ga
     D.assign_gt, D.assign_score, D.out, D.items, D.status = (t.data_ptr() for t in (assign_gt, assign_score, out, items, status))
     D.upstream = _ptr(upstream)
     D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+
+
+# ---- the detection post-process (include/mganms.h)
+def fill_nms(D: _lib.NmsDesc, feats, pred, strides, nc: int, conf_thres: float, iou_thres: float, max_det: int, max_nms: int, flags: int,
+             cand_cap: int, dets, count, keep, status, ws=None) -> None:
+    """Exactly one of feats (the Detect maps (B, 64 + nc, H_l, W_l), NCHW contiguous, one element type, with their strides) and pred (the
+    decoded (B, 4 + nc, A) tensor) is given, the other is None; dets fp32 (B, max_det, 6), count int32 (B), keep int32 (B, max_det) and
+    status int32 (1) are written; flags: _lib.NMS_MULTI_LABEL | _lib.NMS_AGNOSTIC; ws: uint8, _lib.nms_ws_bytes of the filled struct (fill
+    once without it to ask, then again with it), zero-filled once before its first call."""
+    feats = list(feats) if feats is not None else []
+    for l in range(_lib.NMS_MAX_LEVELS):
+        on = l < len(feats)
+        D.feats[l] = feats[l].data_ptr() if on else None
+        D.H[l], D.W[l], D.stride[l] = (feats[l].shape[2], feats[l].shape[3], int(strides[l])) if on else (0, 0, 0)
+    src = feats[0] if feats else pred
+    D.pred = _ptr(pred)
+    D.n_levels, D.A, D.B, D.nc = len(feats), (0 if feats else pred.shape[2]), src.shape[0], int(nc)
+    D.dtype, D.max_det, D.max_nms, D.flags = DTYPES[src.dtype], int(max_det), int(max_nms), int(flags)
+    D.conf_thres, D.iou_thres, D.cand_cap, D.reserved = float(conf_thres), float(iou_thres), int(cand_cap), 0
+    D.dets, D.count, D.keep, D.status = (t.data_ptr() for t in (dets, count, keep, status))
+    D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())

@@ -277,6 +277,26 @@ DET_SYMBOLS = {
     "mgadet_backward": (C.c_int, [C.POINTER(DetDesc), C.c_void_p]),
 }
 
+# the detection post-process -- Detect decode, candidates, greedy NMS -- (include/mganms.h: a header of its own as well)
+NMS_MAX_LEVELS, NMS_MULTI_LABEL, NMS_AGNOSTIC = 4, 1, 2
+
+
+class NmsDesc(C.Structure):                      # mganms_desc_t
+    _fields_ = [("feats", C.c_void_p * NMS_MAX_LEVELS), ("pred", C.c_void_p),
+                ("H", C.c_int32 * NMS_MAX_LEVELS), ("W", C.c_int32 * NMS_MAX_LEVELS), ("stride", C.c_int32 * NMS_MAX_LEVELS),
+                ("n_levels", C.c_int32), ("A", C.c_int32), ("B", C.c_int32), ("nc", C.c_int32),
+                ("dtype", C.c_int32), ("max_det", C.c_int32), ("max_nms", C.c_int32), ("flags", C.c_int32),
+                ("conf_thres", C.c_float), ("iou_thres", C.c_float), ("cand_cap", C.c_int32), ("reserved", C.c_int32),
+                ("dets", C.c_void_p), ("count", C.c_void_p), ("keep", C.c_void_p), ("status", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
+# every symbol include/mganms.h declares
+NMS_SYMBOLS = {
+    "mganms_ws_bytes": (C.c_size_t, [C.POINTER(NmsDesc)]),
+    "mganms_run": (C.c_int, [C.POINTER(NmsDesc), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -300,7 +320,7 @@ def load():
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS, **OPT_SYMBOLS, **TARGETS_SYMBOLS,
-                                         **DET_SYMBOLS}.items():
+                                         **DET_SYMBOLS, **NMS_SYMBOLS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -418,6 +438,14 @@ def det_ws_bytes(desc) -> int:
     nbytes = load().mgadet_ws_bytes(C.byref(desc))
     if nbytes == 0:
         check(E_ARG, "mgadet_ws_bytes")
+    return nbytes
+
+
+def nms_ws_bytes(desc) -> int:
+    """Workspace of a detection post-process call; 0 is the library's refusal and raises with its message."""
+    nbytes = load().mganms_ws_bytes(C.byref(desc))
+    if nbytes == 0:
+        check(E_ARG, "mganms_ws_bytes")
     return nbytes
 
 

@@ -9,7 +9,9 @@ mga_yolo/__init__.py:16-41) and ``mga_yolo.external.ultralytics.ultralytics.nn.t
 that binds one of the class names to a class of that name is rebound.  The trainer's alpha logger finds the blocks by
 ``isinstance`` against ``mga_yolo.nn.modules.masked_cbam.MaskCBAM`` imported at call time (mga_yolo/model/trainer.py:286-295),
 ``MGAModel.init_criterion`` imports the loss classes at call time (model/model.py:103-117): covered by the same rule.
-Nothing else in the reference changes.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
+Nothing else in the reference changes.  ``install(nms=True)`` -- opt-in -- also rebinds ``non_max_suppression`` in the reference's
+``ultralytics.utils.ops`` modules: the validator and the predictor look it up through ``ops.`` at call time (U/models/yolo/detect/val.py,
+predict.py), so the unchanged ``postprocess`` then runs ``detpost.non_max_suppression``.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
 """
 from __future__ import annotations
 
@@ -40,11 +42,12 @@ def _is_reference_module(name: str) -> bool:
     return any(name == p or name.startswith(p + ".") for p in _PREFIXES) and not name.startswith("mga_yolo_amd")
 
 
-def install(strict: bool = False) -> List[str]:
+def install(strict: bool = False, nms: bool = False) -> List[str]:
     """Rebind the block classes in every loaded reference module that exports them.  Returns the module names patched.
     ``strict=True`` raises unless the module whose ``parse_model`` builds ``MGAModel`` (the one providing
-    ``mga_yolo.model.model.DetectionModel``; ``ultralytics.nn.tasks`` when mga_yolo is absent) was patched."""
-    for name in _PRELOAD:
+    ``mga_yolo.model.model.DetectionModel``; ``ultralytics.nn.tasks`` when mga_yolo is absent) was patched.
+    ``nms=True`` also rebinds ``non_max_suppression`` in the reference's ``ultralytics.utils.ops`` modules (see ``_install_nms``)."""
+    for name in _PRELOAD + (_OPS_PRELOAD if nms else ()):
         if name not in sys.modules:
             try:
                 importlib.import_module(name)
@@ -68,12 +71,35 @@ def install(strict: bool = False) -> List[str]:
                 hit = True
         if hit:
             patched.append(name)
+    if nms:
+        patched += _install_nms()
     if strict:
         need = _factory_module_name()
         if need not in patched:
             raise RuntimeError(f"{need} (the module whose parse_model builds the model) could not be patched: "
                                f"patched = {patched}")
     return sorted(patched)
+
+
+_OPS_PRELOAD = ("ultralytics.utils.ops", "mga_yolo.external.ultralytics.ultralytics.utils.ops")
+_OPS_SUFFIX = "ultralytics.utils.ops"
+
+
+def _install_nms() -> List[str]:
+    """Rebind ``non_max_suppression`` in every loaded ``ultralytics.utils.ops`` module of the reference (it holds two module objects of that
+    file, as it does of tasks.py).  uninstall() restores them."""
+    from .detpost import non_max_suppression
+    done = []
+    for name, mod in list(sys.modules.items()):
+        if mod is None or not _is_reference_module(name) or not name.endswith(_OPS_SUFFIX):
+            continue
+        cur = mod.__dict__.get("non_max_suppression", _MISSING)
+        if cur is _MISSING or cur is non_max_suppression:
+            continue
+        _UNDO.append((name, "non_max_suppression", cur))
+        mod.non_max_suppression = non_max_suppression
+        done.append(name)
+    return done
 
 
 _MISSING = object()
