@@ -205,6 +205,16 @@ def fill_targets(D: _lib.TargetsDesc, src, dsts, strides, method: int, flags: in
     D.scratch, D.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel())
 
 
+# ---- the Detect maps of the two descriptors below (detmaps.py, csrc/detmaps.cuh)
+def fill_maps(D, feats, strides, max_levels: int) -> None:
+    """feats, H, W and stride of every level (NULL and 0 past the last map) and n_levels."""
+    for l in range(max_levels):
+        on = l < len(feats)
+        D.feats[l] = feats[l].data_ptr() if on else None
+        D.H[l], D.W[l], D.stride[l] = (feats[l].shape[2], feats[l].shape[3], int(strides[l])) if on else (0, 0, 0)
+    D.n_levels = len(feats)
+
+
 # ---- the detection criterion (include/mgadet.h): one struct for both directions
 def fill_det(D: _lib.DetDesc, feats, strides, nc: int, topk: int, m_cap: int, gains, batch_idx, cls, bboxes, n, assign_gt, assign_score,
              out, items, status, ws=None, g_feats=None, upstream=None) -> None:
@@ -212,12 +222,10 @@ def fill_det(D: _lib.DetDesc, feats, strides, nc: int, topk: int, m_cap: int, ga
     fp32; n: the int32 device word of live rows or None (= n_cap); assign_gt int32 / assign_score fp32 (B, A), out / items fp32 (3) and
     status int32 (1) are written by the forward.  The backward passes g_feats and upstream (3, fp32) as well, and the forward's ws
     (uint8, _lib.det_ws_bytes of the filled struct: fill once without it to ask, then again with it)."""
+    fill_maps(D, feats, strides, _lib.DET_MAX_LEVELS)
     for l in range(_lib.DET_MAX_LEVELS):
-        on = l < len(feats)
-        D.feats[l] = feats[l].data_ptr() if on else None
-        D.g_feats[l] = g_feats[l].data_ptr() if on and g_feats is not None else None
-        D.H[l], D.W[l], D.stride[l] = (feats[l].shape[2], feats[l].shape[3], int(strides[l])) if on else (0, 0, 0)
-    D.n_levels, D.B, D.nc, D.reg_max = len(feats), feats[0].shape[0], int(nc), _lib.DET_REG_MAX
+        D.g_feats[l] = g_feats[l].data_ptr() if l < len(feats) and g_feats is not None else None
+    D.B, D.nc, D.reg_max = feats[0].shape[0], int(nc), _lib.DET_REG_MAX
     D.dtype, D.topk, D.n_cap, D.m_cap = DTYPES[feats[0].dtype], int(topk), batch_idx.shape[0], int(m_cap)
     D.gains[0], D.gains[1], D.gains[2] = (float(g) for g in gains)
     D.reserved = 0
@@ -237,13 +245,10 @@ def fill_nms(D: _lib.NmsDesc, feats, pred, strides, nc: int, conf_thres: float, 
     status int32 (1) are written; flags: _lib.NMS_MULTI_LABEL | _lib.NMS_AGNOSTIC; ws: uint8, _lib.nms_ws_bytes of the filled struct (fill
     once without it to ask, then again with it), zero-filled once before its first call."""
     feats = list(feats) if feats is not None else []
-    for l in range(_lib.NMS_MAX_LEVELS):
-        on = l < len(feats)
-        D.feats[l] = feats[l].data_ptr() if on else None
-        D.H[l], D.W[l], D.stride[l] = (feats[l].shape[2], feats[l].shape[3], int(strides[l])) if on else (0, 0, 0)
+    fill_maps(D, feats, strides, _lib.NMS_MAX_LEVELS)
     src = feats[0] if feats else pred
     D.pred = _ptr(pred)
-    D.n_levels, D.A, D.B, D.nc = len(feats), (0 if feats else pred.shape[2]), src.shape[0], int(nc)
+    D.A, D.B, D.nc = (0 if feats else pred.shape[2]), src.shape[0], int(nc)
     D.dtype, D.max_det, D.max_nms, D.flags = DTYPES[src.dtype], int(max_det), int(max_nms), int(flags)
     D.conf_thres, D.iou_thres, D.cand_cap, D.reserved = float(conf_thres), float(iou_thres), int(cand_cap), 0
     D.dets, D.count, D.keep, D.status = (t.data_ptr() for t in (dets, count, keep, status))

@@ -1,10 +1,10 @@
 // libmgacbam.so, C ABI (include/mgadet.h): the detection criterion -- task-aligned assignment, CIoU, DFL, BCE -- on the Detect maps
-#include "host.cuh"
+#include "detmaps_host.cuh"
 #include "det.cuh"
 
 #include "../../include/mgadet.h"
 
-static_assert(kDetLevelsMax == MGADET_MAX_LEVELS && kDetTopkMax == MGADET_MAX_TOPK && kDetMMax == MGADET_MAX_GT, "DetArgs against the ABI");
+static_assert(kMapsLevelsMax == MGADET_MAX_LEVELS && kDetTopkMax == MGADET_MAX_TOPK && kDetMMax == MGADET_MAX_GT, "DetArgs against the ABI");
 static_assert(kDetMMax <= kDetSlotMask, "a slot fits under the resolve's action bits");
 static_assert(sizeof(mgadet_desc_t) == 256, "the descriptor's layout (mirrored by _lib.DetDesc)");
 
@@ -14,35 +14,20 @@ struct DetLayout { size_t cand_n, cand_row, cand_anchor, cand_metric, cand_overl
 // Everything a descriptor is checked for that does not involve a pointer; fills the kernel arguments' geometry and the ws layout.
 static int det_check(const char* what, const mgadet_desc_t* D, DetArgs& A, DetLayout& L) {
   if (!D) return fail(MGACBAM_E_NULL, "%s: desc is NULL", what);
-  if (D->n_levels < 1 || D->n_levels > MGADET_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "%s: n_levels=%d (1 .. %d)", what, D->n_levels, MGADET_MAX_LEVELS);
+  if (int e = maps_levels(what, 1, D->n_levels)) return e;
   if (int e = check_dtype(what, D->dtype)) return e;
-  if (D->reg_max != kDetReg) return fail(MGACBAM_E_ARG, "%s: reg_max=%d (16 is the one built)", what, D->reg_max);
+  if (D->reg_max != kMapsReg) return fail(MGACBAM_E_ARG, "%s: reg_max=%d (16 is the one built)", what, D->reg_max);
   if (D->topk < 1 || D->topk > MGADET_MAX_TOPK) return fail(MGACBAM_E_ARG, "%s: topk=%d (1 .. %d)", what, D->topk, MGADET_MAX_TOPK);
   if (D->m_cap < 1 || D->m_cap > MGADET_MAX_GT) return fail(MGACBAM_E_ARG, "%s: m_cap=%d (1 .. %d)", what, D->m_cap, MGADET_MAX_GT);
   if (D->reserved != 0) return fail(MGACBAM_E_ARG, "%s: reserved=%d (0)", what, D->reserved);
-  if (D->B < 1 || D->nc < 1 || D->nc > 65536 || D->n_cap < 0) return fail(MGACBAM_E_SHAPE, "%s: B=%d nc=%d n_cap=%d", what, D->B, D->nc, D->n_cap);
-  long long anchors = 0;
-  for (int l = 0; l < D->n_levels; ++l) {
-    if (D->H[l] < 1 || D->W[l] < 1) return fail(MGACBAM_E_SHAPE, "%s: level %d is %d x %d", what, l, D->H[l], D->W[l]);
-    if (D->stride[l] < 1 || (l > 0 && D->stride[l] <= D->stride[l - 1]))
-      return fail(MGACBAM_E_ARG, "%s: stride[%d]=%d (positive, strictly ascending)", what, l, D->stride[l]);
-    anchors += static_cast<long long>(D->H[l]) * D->W[l];
-    if (anchors * D->B >= (1ll << 31)) return fail(MGACBAM_E_SHAPE, "%s: B * anchors must stay below 2^31", what);
-  }
+  if (D->n_cap < 0) return fail(MGACBAM_E_SHAPE, "%s: n_cap=%d", what, D->n_cap);
+  if (int e = maps_check(what, D->n_levels, D->H, D->W, D->stride, D->B, D->nc, true, A.maps)) return e;
   if (static_cast<long long>(D->W[0]) * D->stride[0] > (1 << 24) || static_cast<long long>(D->H[0]) * D->stride[0] > (1 << 24))
     return fail(MGACBAM_E_SHAPE, "%s: an image side above 2^24 pixels", what);
-  A.n_levels = D->n_levels; A.B = D->B; A.nc = D->nc; A.no = 4 * kDetReg + D->nc; A.A = static_cast<int>(anchors);
   A.topk = D->topk; A.n_cap = D->n_cap; A.m_cap = D->m_cap;
-  A.a0[0] = 0;
-  for (int l = 0; l < MGADET_MAX_LEVELS; ++l) {
-    const bool on = l < D->n_levels;
-    A.H[l] = on ? D->H[l] : 0; A.W[l] = on ? D->W[l] : 0; A.stride[l] = on ? static_cast<float>(D->stride[l]) : 0.f;
-    A.a0[l + 1] = A.a0[l] + A.H[l] * A.W[l];
-    A.feat[l] = nullptr; A.gfeat[l] = nullptr;
-  }
   for (int k = 0; k < 3; ++k) A.gain[k] = D->gains[k];
   A.img_w = static_cast<float>(D->W[0] * D->stride[0]); A.img_h = static_cast<float>(D->H[0] * D->stride[0]);
-  A.nblk = static_cast<int>((static_cast<long long>(D->B) * anchors + kBlock - 1) / kBlock);
+  A.nblk = static_cast<int>((static_cast<long long>(D->B) * A.maps.A + kBlock - 1) / kBlock);
   const size_t slots = static_cast<size_t>(D->B) * D->m_cap;
   Carver cv;
   L.cand_n = cv.take(slots); L.cand_row = cv.take(slots);
@@ -64,21 +49,13 @@ extern "C" size_t mgadet_ws_bytes(const mgadet_desc_t* desc) {
 
 // the pointers of a call; bwd: g_feats and upstream as well
 static int det_bind(const char* what, const mgadet_desc_t* D, DetArgs& A, const DetLayout& L, bool bwd) {
-  const size_t es = elem_size(D->dtype);
-  for (int l = 0; l < D->n_levels; ++l) {
-    if (!D->feats[l] || (bwd && !D->g_feats[l])) return fail(MGACBAM_E_NULL, "%s: feats[%d] or g_feats[%d] is NULL", what, l, l);
-    if (!aligned_to(D->feats[l], es) || (bwd && !aligned_to(D->g_feats[l], es)))
-      return fail(MGACBAM_E_ALIGN, "%s: level %d must be aligned to its element (%zu bytes)", what, l, es);
-    A.feat[l] = D->feats[l]; A.gfeat[l] = bwd ? D->g_feats[l] : nullptr;
-  }
+  if (int e = maps_bind(what, D->feats, bwd ? D->g_feats : nullptr, D->dtype, A.maps)) return e;
+  for (int l = 0; l < kMapsLevelsMax; ++l) A.gfeat[l] = bwd && l < D->n_levels ? D->g_feats[l] : nullptr;
   if (D->n_cap > 0 && (!D->batch_idx || !D->cls || !D->bboxes)) return fail(MGACBAM_E_NULL, "%s: a label buffer is NULL with n_cap=%d", what, D->n_cap);
   if (!D->assign_gt || !D->assign_score || !D->out || !D->items || !D->status || !D->ws || (bwd && !D->upstream))
     return fail(MGACBAM_E_NULL, "%s: assign_gt, assign_score, out, items, status, ws%s must not be NULL", what, bwd ? ", upstream" : "");
   const void* words[] = {D->batch_idx, D->cls, D->bboxes, D->n, D->assign_gt, D->assign_score, D->out, D->items, D->status, D->upstream};
-  for (const void* p : words)
-    if (!aligned_to(p, 4)) return fail(MGACBAM_E_ALIGN, "%s: every fp32 / int32 buffer must be 4-byte aligned", what);
-  if (!aligned_to(D->ws, 16)) return fail(MGACBAM_E_ALIGN, "%s: ws must be 16-byte aligned", what);
-  if (int e = check_capacity(what, "ws", L.total, D->ws_bytes)) return e;
+  if (int e = check_words_and_ws(what, words, D->ws, L.total, D->ws_bytes)) return e;
   A.batch_idx = D->batch_idx; A.cls = D->cls; A.bboxes = D->bboxes; A.n_ptr = D->n;
   A.asg_gt = D->assign_gt; A.asg_score = D->assign_score;
   A.cand_n = at<int>(D->ws, L.cand_n); A.cand_row = at<int>(D->ws, L.cand_row); A.cand_anchor = at<int>(D->ws, L.cand_anchor);
@@ -92,34 +69,24 @@ template <typename T>
 static int det_forward(const DetArgs& A, hipStream_t st) {
   const size_t E = static_cast<size_t>(A.m_cap) * kDetTopkMax;
   const size_t smem = E * 14 + static_cast<size_t>(A.m_cap) * 12;       // k_det_resolve: e_anc, e_met, e_ov, e_gt; pos_m, pos_o, s_row
-  if (int e = launch("k_det_assign", k_det_assign<T>, static_cast<long long>(A.B) * A.m_cap, kBlock, 0, st, A)) return e;
-  if (int e = launch("k_det_resolve", k_det_resolve<T>, A.B, kBlock, smem, st, A)) return e;
+  if (int e = launch("k_det_assign", k_det_assign<T>, static_cast<long long>(A.maps.B) * A.m_cap, kBlock, 0, st, A)) return e;
+  if (int e = launch("k_det_resolve", k_det_resolve<T>, A.maps.B, kBlock, smem, st, A)) return e;
   if (int e = launch("k_det_loss", k_det_loss<T>, A.nblk, kBlock, 0, st, A)) return e;
   return launch("k_det_final", k_det_final, 1, kBlock, 0, st, A);
 }
 
-extern "C" int mgadet_forward(const mgadet_desc_t* D, void* stream) {
-  const char* what = "mgadet_forward";
+// either direction: check, bind, launch in the maps' element type
+static int det_run(const char* what, const mgadet_desc_t* D, void* stream, bool bwd) {
   DetArgs A;
   DetLayout L;
   if (int e = det_check(what, D, A, L)) return e;
-  if (int e = det_bind(what, D, A, L, false)) return e;
+  if (int e = det_bind(what, D, A, L, bwd)) return e;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int e = D->dtype == MGACBAM_F32 ? det_forward<float>(A, st) : D->dtype == MGACBAM_F16 ? det_forward<__half>(A, st) : det_forward<bf16_t>(A, st);
-  if (e) return e;
-  g_err[0] = 0;
-  return 0;
+  const int e = with_elem(D->dtype, [&](auto t) {
+    return bwd ? launch("k_det_bwd", k_det_bwd<elem_t<decltype(t)>>, A.nblk, kBlock, 0, st, A) : det_forward<elem_t<decltype(t)>>(A, st);
+  });
+  if (!e) g_err[0] = 0;
+  return e;
 }
-
-extern "C" int mgadet_backward(const mgadet_desc_t* D, void* stream) {
-  const char* what = "mgadet_backward";
-  DetArgs A;
-  DetLayout L;
-  if (int e = det_check(what, D, A, L)) return e;
-  if (int e = det_bind(what, D, A, L, true)) return e;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  auto k = D->dtype == MGACBAM_F32 ? k_det_bwd<float> : D->dtype == MGACBAM_F16 ? k_det_bwd<__half> : k_det_bwd<bf16_t>;
-  if (int e = launch("k_det_bwd", k, A.nblk, kBlock, 0, st, A)) return e;
-  g_err[0] = 0;
-  return 0;
-}
+extern "C" int mgadet_forward(const mgadet_desc_t* D, void* stream) { return det_run("mgadet_forward", D, stream, false); }
+extern "C" int mgadet_backward(const mgadet_desc_t* D, void* stream) { return det_run("mgadet_backward", D, stream, true); }

@@ -1,10 +1,10 @@
 // libmgacbam.so, C ABI (include/mganms.h): the detection post-process -- Detect decode, candidates, greedy NMS -- in two launches
-#include "host.cuh"
+#include "detmaps_host.cuh"
 #include "nms.cuh"
 
 #include "../../include/mganms.h"
 
-static_assert(kNmsLevelsMax == MGANMS_MAX_LEVELS, "NmsArgs against the ABI");
+static_assert(kMapsLevelsMax == MGANMS_MAX_LEVELS, "NmsArgs against the ABI");
 static_assert(kBlock == 256, "k_nms_greedy's radix select has one bin per thread");
 static_assert(sizeof(mganms_desc_t) == 184, "the descriptor's layout (mirrored by _lib.NmsDesc)");
 
@@ -14,7 +14,7 @@ struct NmsLayout { size_t cnt, keys, boxes, total; };
 // Everything a descriptor is checked for that does not involve a pointer's value; fills the kernel arguments' geometry and the ws layout.
 static int nms_check(const char* what, const mganms_desc_t* D, NmsArgs& A, NmsLayout& L) {
   if (!D) return fail(MGACBAM_E_NULL, "%s: desc is NULL", what);
-  if (D->n_levels < 0 || D->n_levels > MGANMS_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "%s: n_levels=%d (0 with pred, 1 .. %d with feats)", what, D->n_levels, MGANMS_MAX_LEVELS);
+  if (int e = maps_levels(what, 0, D->n_levels)) return e;                     // 0 with pred, 1 .. with feats
   bool any_feat = false;
   for (int l = 0; l < MGANMS_MAX_LEVELS; ++l) any_feat = any_feat || D->feats[l] != nullptr;
   if (int e = check_dtype(what, D->dtype)) return e;
@@ -25,29 +25,15 @@ static int nms_check(const char* what, const mganms_desc_t* D, NmsArgs& A, NmsLa
   if (D->max_det < 1 || D->max_nms < 1 || D->cand_cap < 1) return fail(MGACBAM_E_ARG, "%s: max_det=%d max_nms=%d cand_cap=%d (all >= 1)", what, D->max_det, D->max_nms, D->cand_cap);
   if (D->flags & ~(MGANMS_MULTI_LABEL | MGANMS_AGNOSTIC)) return fail(MGACBAM_E_ARG, "%s: flags=0x%x", what, D->flags);
   if (D->reserved != 0) return fail(MGACBAM_E_ARG, "%s: reserved=%d (0)", what, D->reserved);
-  if (D->B < 1 || D->nc < 1 || D->nc > 65536 || D->A < 0) return fail(MGACBAM_E_SHAPE, "%s: B=%d nc=%d A=%d", what, D->B, D->nc, D->A);
-  long long anchors = 0;
-  for (int l = 0; l < D->n_levels; ++l) {
-    if (D->H[l] < 1 || D->W[l] < 1) return fail(MGACBAM_E_SHAPE, "%s: level %d is %d x %d", what, l, D->H[l], D->W[l]);
-    if (D->stride[l] < 1 || (l > 0 && D->stride[l] <= D->stride[l - 1]))
-      return fail(MGACBAM_E_ARG, "%s: stride[%d]=%d (positive, strictly ascending)", what, l, D->stride[l]);
-    anchors += static_cast<long long>(D->H[l]) * D->W[l];
-    if (anchors >= (1ll << 31)) return fail(MGACBAM_E_SHAPE, "%s: anchors must stay below 2^31", what);
-  }
-  if (D->n_levels > 0 && D->A != 0 && D->A != anchors) return fail(MGACBAM_E_SHAPE, "%s: A=%d, the levels hold %lld anchors", what, D->A, anchors);
-  if (D->n_levels == 0) anchors = D->A;
+  if (D->A < 0) return fail(MGACBAM_E_SHAPE, "%s: A=%d", what, D->A);
+  if (int e = maps_check(what, D->n_levels, D->H, D->W, D->stride, D->B, D->nc, false, A.maps)) return e;
+  if (D->n_levels > 0 && D->A != 0 && D->A != A.maps.A) return fail(MGACBAM_E_SHAPE, "%s: A=%d, the levels hold %d anchors", what, D->A, A.maps.A);
+  if (D->n_levels == 0) A.maps.A = D->A;                                       // with pred: the descriptor's
+  const long long anchors = A.maps.A;
   if (anchors < 1) return fail(MGACBAM_E_SHAPE, "%s: A=%lld", what, anchors);
   if (anchors * D->nc >= (1ll << 31) || anchors * D->B >= (1ll << 31))
     return fail(MGACBAM_E_SHAPE, "%s: A * nc and B * A must stay below 2^31", what);
-  A.n_levels = D->n_levels; A.B = D->B; A.nc = D->nc; A.no = 4 * kNmsReg + D->nc; A.A = static_cast<int>(anchors);
-  A.bpi = (A.A + kBlock - 1) / kBlock;
-  A.a0[0] = 0;
-  for (int l = 0; l < MGANMS_MAX_LEVELS; ++l) {
-    const bool on = l < D->n_levels;
-    A.H[l] = on ? D->H[l] : 0; A.W[l] = on ? D->W[l] : 0; A.stride[l] = on ? static_cast<float>(D->stride[l]) : 0.f;
-    A.a0[l + 1] = A.a0[l] + A.H[l] * A.W[l];
-    A.feat[l] = nullptr;
-  }
+  A.bpi = (A.maps.A + kBlock - 1) / kBlock;
   A.pred = nullptr;
   A.conf = D->conf_thres; A.iou = D->iou_thres; A.max_det = D->max_det; A.max_nms = D->max_nms; A.cand_cap = D->cand_cap;
   A.multi = (D->flags & MGANMS_MULTI_LABEL) && D->nc > 1 ? 1 : 0;              // ops.py:266
@@ -69,20 +55,13 @@ extern "C" size_t mganms_ws_bytes(const mganms_desc_t* desc) {
 
 static int nms_bind(const char* what, const mganms_desc_t* D, NmsArgs& A, const NmsLayout& L) {
   const size_t es = elem_size(D->dtype);
-  for (int l = 0; l < D->n_levels; ++l) {
-    if (!D->feats[l]) return fail(MGACBAM_E_NULL, "%s: feats[%d] is NULL", what, l);
-    if (!aligned_to(D->feats[l], es)) return fail(MGACBAM_E_ALIGN, "%s: level %d must be aligned to its element (%zu bytes)", what, l, es);
-    A.feat[l] = D->feats[l];
-  }
+  if (int e = maps_bind(what, D->feats, nullptr, D->dtype, A.maps)) return e;
   if (D->n_levels == 0 && !D->pred) return fail(MGACBAM_E_NULL, "%s: pred is NULL with n_levels=0", what);
   if (D->pred && !aligned_to(D->pred, es)) return fail(MGACBAM_E_ALIGN, "%s: pred must be aligned to its element (%zu bytes)", what, es);
   A.pred = D->pred;
   if (!D->dets || !D->count || !D->keep || !D->status || !D->ws) return fail(MGACBAM_E_NULL, "%s: dets, count, keep, status, ws must not be NULL", what);
   const void* words[] = {D->dets, D->count, D->keep, D->status};
-  for (const void* p : words)
-    if (!aligned_to(p, 4)) return fail(MGACBAM_E_ALIGN, "%s: every fp32 / int32 buffer must be 4-byte aligned", what);
-  if (!aligned_to(D->ws, 16)) return fail(MGACBAM_E_ALIGN, "%s: ws must be 16-byte aligned", what);
-  if (int e = check_capacity(what, "ws", L.total, D->ws_bytes)) return e;
+  if (int e = check_words_and_ws(what, words, D->ws, L.total, D->ws_bytes)) return e;
   A.cnt = at<int>(D->ws, L.cnt); A.keys = at<nms_key_t>(D->ws, L.keys); A.boxes = at<float4>(D->ws, L.boxes);
   A.dets = D->dets; A.count = D->count; A.keep = D->keep; A.status = D->status;
   return 0;
@@ -95,9 +74,9 @@ extern "C" int mganms_run(const mganms_desc_t* D, void* stream) {
   if (int e = nms_check(what, D, A, L)) return e;
   if (int e = nms_bind(what, D, A, L)) return e;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  auto cand = D->dtype == MGACBAM_F32 ? k_nms_cand<float> : D->dtype == MGACBAM_F16 ? k_nms_cand<__half> : k_nms_cand<bf16_t>;
-  if (int e = launch("k_nms_cand", cand, static_cast<long long>(A.B) * A.bpi, kBlock, 0, st, A)) return e;
-  if (int e = launch("k_nms_greedy", k_nms_greedy, A.B, kBlock, 0, st, A)) return e;
+  auto cand = with_elem(D->dtype, [](auto t) { return k_nms_cand<elem_t<decltype(t)>>; });
+  if (int e = launch("k_nms_cand", cand, static_cast<long long>(A.maps.B) * A.bpi, kBlock, 0, st, A)) return e;
+  if (int e = launch("k_nms_greedy", k_nms_greedy, A.maps.B, kBlock, 0, st, A)) return e;
   g_err[0] = 0;
   return 0;
 }

@@ -11,23 +11,18 @@
 //   k_det_bwd     : one thread per anchor: every channel's gradient, in the features' element type and layout.
 // No atomics on floating-point sums: every sum has a fixed order, two runs give the same bits.
 #pragma once
-#include "common.cuh"
+#include "detmaps.cuh"
 
 namespace mgacbam {
 
-constexpr int kDetLevelsMax = 4;               // = MGADET_MAX_LEVELS (api_det.hip asserts these)
-constexpr int kDetReg = 16;                    // bins per box side
-constexpr int kDetTopkMax = 16;
+constexpr int kDetTopkMax = 16;                // = MGADET_MAX_TOPK, kDetMMax = MGADET_MAX_GT (api_det.hip asserts these)
 constexpr int kDetMMax = 256;                  // ground truths per image
 constexpr int kDetChunk = 2048;                // cells a k_det_assign workgroup stages in LDS at a time
 
 struct DetArgs {
-  const void* feat[kDetLevelsMax];             // (B, 64 + nc, H_l, W_l)
-  void* gfeat[kDetLevelsMax];
-  int H[kDetLevelsMax], W[kDetLevelsMax];
-  int a0[kDetLevelsMax + 1];                   // anchors [a0[l], a0[l+1]) belong to level l
-  float stride[kDetLevelsMax];
-  int n_levels, B, nc, no, A, topk, n_cap, m_cap;
+  DetMaps maps;                                // the Detect maps (detmaps.cuh)
+  void* gfeat[kMapsLevelsMax];                 // their gradients, in the same layout
+  int topk, n_cap, m_cap;
   float gain[3];
   float img_w, img_h;                          // W_0 * stride_0, H_0 * stride_0
   const float* batch_idx; const float* cls; const float* bboxes; const int* n_ptr;
@@ -42,8 +37,6 @@ struct DetArgs {
   const float* upstream;
 };
 
-struct DetBox { float x1, y1, x2, y2; };
-
 __device__ __forceinline__ int det_n(const DetArgs& A) {
   const int n = A.n_ptr ? *A.n_ptr : A.n_cap;
   return min(max(n, 0), A.n_cap);
@@ -55,14 +48,7 @@ __device__ __forceinline__ DetBox det_gt_box(const DetArgs& A, int r) {
   return DetBox{cx - hw, cy - hh, cx + hw, cy + hh};
 }
 __device__ __forceinline__ bool det_gt_valid(const DetBox& g) { return ((g.x1 + g.y1) + g.x2) + g.y2 > 0.f; }      // loss.py:263
-__device__ __forceinline__ int det_label(const DetArgs& A, int r) { return min(max(static_cast<int>(A.cls[r]), 0), A.nc - 1); }
-__device__ __forceinline__ int det_level(const DetArgs& A, int a) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < kDetLevelsMax; ++i)
-    if (i < A.n_levels && a >= A.a0[i]) l = i;
-  return l;
-}
+__device__ __forceinline__ int det_label(const DetArgs& A, int r) { return min(max(static_cast<int>(A.cls[r]), 0), A.maps.nc - 1); }
 
 // metrics.py:113-141 with xywh=False, CIoU=True: box1's and box2's heights carry the eps
 constexpr float kDetEps = 1e-7f;
@@ -115,41 +101,17 @@ __device__ __forceinline__ float det_ciou_grad(const DetBox& p, const DetBox& q,
   return iou - (rho2 / c2 + v * alpha);
 }
 
-// one side's 16 bins of an anchor: softmax probabilities, their expectation (loss.py:238) and the log of the sum of exponentials
-template <typename T>
-__device__ __forceinline__ void det_side(const T* __restrict__ f, size_t hw, int side, float (&p)[kDetReg], float& d, float& lse) {
-  float m = -FLT_MAX;
-#pragma unroll
-  for (int j = 0; j < kDetReg; ++j) { p[j] = to_f32<T>(f[(side * kDetReg + j) * hw]); m = fmaxf(m, p[j]); }
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < kDetReg; ++j) { p[j] = expf(p[j] - m); sum += p[j]; }
-  const float inv = 1.f / sum;
-  d = 0.f;
-#pragma unroll
-  for (int j = 0; j < kDetReg; ++j) { p[j] *= inv; d += p[j] * static_cast<float>(j); }
-  lse = m + logf(sum);
-}
-// the decoded box of the anchor at (ax, ay), in grid units (tal.py:382-391)
-template <typename T>
-__device__ __forceinline__ DetBox det_decode(const T* __restrict__ f, size_t hw, float ax, float ay) {
-  float p[kDetReg], d[4], lse;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) det_side<T>(f, hw, s, p, d[s], lse);
-  return DetBox{ax - d[0], ay - d[1], ax + d[2], ay + d[3]};
-}
 // tal.py:279-299: the anchor's centre, in pixels, lies inside the box by more than 1e-9
 __device__ __forceinline__ bool det_inside(const DetBox& g, float px, float py) {
   return fminf(fminf(px - g.x1, py - g.y1), fminf(g.x2 - px, g.y2 - py)) > 1e-9f;
 }
 // tal.py:156-188 for one (ground truth, anchor) pair that passed det_inside: overlap = clamp(CIoU, 0), metric = score^0.5 overlap^6
 template <typename T>
-__device__ __forceinline__ void det_pair(const T* __restrict__ f, size_t hw, float ax, float ay, float s, const DetBox& g, int label,
-                                         float& met, float& ov) {
-  const DetBox pg = det_decode<T>(f, hw, ax, ay);
-  const DetBox pb{pg.x1 * s, pg.y1 * s, pg.x2 * s, pg.y2 * s};
+__device__ __forceinline__ void det_pair(const T* __restrict__ f, const MapsAnchor& t, const DetBox& g, int label, float& met, float& ov) {
+  const DetBox pg = maps_decode<T>(f, t.hw, t.ax, t.ay);
+  const DetBox pb{pg.x1 * t.s, pg.y1 * t.s, pg.x2 * t.s, pg.y2 * t.s};
   ov = fmaxf(det_ciou(g, pb), 0.f);
-  const float sc = sigmoidf_(to_f32<T>(f[(4 * kDetReg + label) * hw]));
+  const float sc = sigmoidf_(to_f32<T>(f[(4 * kMapsReg + label) * t.hw]));
   const float o2 = ov * ov;
   met = sqrtf(sc) * (o2 * o2 * o2);
 }
@@ -164,10 +126,10 @@ __global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
   const int b = static_cast<int>(blockIdx.x) / A.m_cap, g = static_cast<int>(blockIdx.x) % A.m_cap;
   const int slot = b * A.m_cap + g;
   {                                                            // this workgroup's share of the image's assignment: background
-    const int per = (A.A + A.m_cap - 1) / A.m_cap, hi = min((g + 1) * per, A.A);
+    const int per = (A.maps.A + A.m_cap - 1) / A.m_cap, hi = min((g + 1) * per, A.maps.A);
     for (int a = g * per + tid; a < hi; a += kBlock) {
-      A.asg_gt[static_cast<size_t>(b) * A.A + a] = -1;
-      A.asg_score[static_cast<size_t>(b) * A.A + a] = 0.f;
+      A.asg_gt[static_cast<size_t>(b) * A.maps.A + a] = -1;
+      A.asg_score[static_cast<size_t>(b) * A.maps.A + a] = 0.f;
     }
   }
   // loss.py:217-232: the g-th row whose batch_idx is b
@@ -198,24 +160,24 @@ __global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
   }
   const int label = det_label(A, row);
   // per level, the rectangle of cells whose centres can lie inside the box (one cell of margin; det_inside decides)
-  int ix0[kDetLevelsMax], iy0[kDetLevelsMax], rw[kDetLevelsMax], tot[kDetLevelsMax + 1];
+  int ix0[kMapsLevelsMax], iy0[kMapsLevelsMax], rw[kMapsLevelsMax], tot[kMapsLevelsMax + 1];
   tot[0] = 0;
 #pragma unroll
-  for (int l = 0; l < kDetLevelsMax; ++l) {
+  for (int l = 0; l < kMapsLevelsMax; ++l) {
     int cells = 0;
     ix0[l] = iy0[l] = 0; rw[l] = 1;
-    if (l < A.n_levels) {
-      const float s = A.stride[l];
-      const int x0 = static_cast<int>(fminf(fmaxf(floorf(gt.x1 / s - 0.5f) - 1.f, 0.f), static_cast<float>(A.W[l] - 1)));
-      const int y0 = static_cast<int>(fminf(fmaxf(floorf(gt.y1 / s - 0.5f) - 1.f, 0.f), static_cast<float>(A.H[l] - 1)));
-      const int x1 = static_cast<int>(fmaxf(fminf(ceilf(gt.x2 / s - 0.5f) + 1.f, static_cast<float>(A.W[l] - 1)), 0.f));
-      const int y1 = static_cast<int>(fmaxf(fminf(ceilf(gt.y2 / s - 0.5f) + 1.f, static_cast<float>(A.H[l] - 1)), 0.f));
+    if (l < A.maps.n_levels) {
+      const float s = A.maps.stride[l];
+      const int x0 = static_cast<int>(fminf(fmaxf(floorf(gt.x1 / s - 0.5f) - 1.f, 0.f), static_cast<float>(A.maps.W[l] - 1)));
+      const int y0 = static_cast<int>(fminf(fmaxf(floorf(gt.y1 / s - 0.5f) - 1.f, 0.f), static_cast<float>(A.maps.H[l] - 1)));
+      const int x1 = static_cast<int>(fmaxf(fminf(ceilf(gt.x2 / s - 0.5f) + 1.f, static_cast<float>(A.maps.W[l] - 1)), 0.f));
+      const int y1 = static_cast<int>(fmaxf(fminf(ceilf(gt.y2 / s - 0.5f) + 1.f, static_cast<float>(A.maps.H[l] - 1)), 0.f));
       ix0[l] = x0; iy0[l] = y0; rw[l] = max(x1 - x0 + 1, 1);
       cells = max(x1 - x0 + 1, 0) * max(y1 - y0 + 1, 0);
     }
     tot[l + 1] = tot[l] + cells;
   }
-  const int T_ = tot[kDetLevelsMax];
+  const int T_ = tot[kMapsLevelsMax];
   int ncarry = 0;
   for (int c0 = 0; c0 < T_; c0 += kDetChunk) {
     const int cn = min(kDetChunk, T_ - c0);
@@ -223,22 +185,17 @@ __global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
       const int idx = c0 + i;
       int l = 0;
 #pragma unroll
-      for (int k = 1; k < kDetLevelsMax; ++k)
+      for (int k = 1; k < kMapsLevelsMax; ++k)
         if (idx >= tot[k]) l = k;                              // levels past n_levels hold no cell: tot[k] = T_ > idx
       int x0 = ix0[0], y0 = iy0[0], w = rw[0], t0 = tot[0];
 #pragma unroll
-      for (int k = 1; k < kDetLevelsMax; ++k)
+      for (int k = 1; k < kMapsLevelsMax; ++k)
         if (l == k) { x0 = ix0[k]; y0 = iy0[k]; w = rw[k]; t0 = tot[k]; }
       const int local = idx - t0, x = x0 + local % w, y = y0 + local / w;
-      const int Wl = A.W[l], Hl = A.H[l];
-      const float s = A.stride[l], ax = static_cast<float>(x) + 0.5f, ay = static_cast<float>(y) + 0.5f;
+      const MapsAnchor t = maps_cell(A.maps, l, y * A.maps.W[l] + x, y, x);
       float met = -1.f, ov = 0.f;
-      if (det_inside(gt, ax * s, ay * s)) {
-        const size_t hw = static_cast<size_t>(Hl) * Wl;
-        const T* f = static_cast<const T*>(A.feat[l]) + static_cast<size_t>(b) * A.no * hw + static_cast<size_t>(y) * Wl + x;
-        det_pair<T>(f, hw, ax, ay, s, gt, label, met, ov);
-      }
-      s_met[i] = met; s_ov[i] = ov; s_anc[i] = A.a0[l] + y * Wl + x;
+      if (det_inside(gt, t.ax * t.s, t.ay * t.s)) det_pair<T>(maps_feat<T>(A.maps, t, b), t, gt, label, met, ov);
+      s_met[i] = met; s_ov[i] = ov; s_anc[i] = A.maps.a0[l] + t.p;
     }
     if (tid < ncarry) { s_met[cn + tid] = sel_met[tid]; s_ov[cn + tid] = sel_ov[tid]; s_anc[cn + tid] = sel_anc[tid]; }
     __syncthreads();
@@ -329,11 +286,8 @@ __global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
     if (act & kDetDrop) { e_anc[e] = -1; continue; }
     if (!(act & kDetLead)) continue;
     // the arg-max over every slot of the overlap, 0 where the anchor is not inside a valid box; the first slot wins a tie
-    const int a = e_anc[e], l = det_level(A, a);
-    const int Wl = A.W[l], p = a - A.a0[l], x = p % Wl, y = p / Wl;
-    const float s = A.stride[l], ax = static_cast<float>(x) + 0.5f, ay = static_cast<float>(y) + 0.5f;
-    const size_t hw = static_cast<size_t>(A.H[l]) * Wl;
-    const T* f = static_cast<const T*>(A.feat[l]) + static_cast<size_t>(b) * A.no * hw + p;
+    const MapsAnchor t = maps_anchor(A.maps, e_anc[e]);
+    const T* f = maps_feat<T>(A.maps, t, b);
     float best_ov = -1.f, best_met = 0.f;
     int best = 0;
     for (int g = 0; g < M; ++g) {
@@ -341,7 +295,7 @@ __global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
       if (row < 0) break;                                      // rows fill the slots from 0: the rest are empty, overlap 0, never first
       float met = 0.f, ov = 0.f;
       const DetBox gt = det_gt_box(A, row);
-      if (det_gt_valid(gt) && det_inside(gt, ax * s, ay * s)) det_pair<T>(f, hw, ax, ay, s, gt, det_label(A, row), met, ov);
+      if (det_gt_valid(gt) && det_inside(gt, t.ax * t.s, t.ay * t.s)) det_pair<T>(f, t, gt, det_label(A, row), met, ov);
       if (ov > best_ov) { best_ov = ov; best_met = met; best = g; }
     }
     e_gt[e] = static_cast<short>(best);
@@ -362,8 +316,8 @@ __global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
     if (a < 0) continue;
     const int g = e_gt[e] & kDetSlotMask;
     const float sc = e_met[e] * __int_as_float(pos_o[g]) / (__int_as_float(pos_m[g]) + 1e-9f);
-    A.asg_gt[static_cast<size_t>(b) * A.A + a] = s_row[g];
-    A.asg_score[static_cast<size_t>(b) * A.A + a] = sc;
+    A.asg_gt[static_cast<size_t>(b) * A.maps.A + a] = s_row[g];
+    A.asg_score[static_cast<size_t>(b) * A.maps.A + a] = sc;
     sum += sc;
   }
   sum = block_sum(sum, tid, red);
@@ -381,19 +335,9 @@ __device__ __forceinline__ float det_side_target(const DetBox& tb, float ax, flo
 }
 
 // what a thread of the two sweeps owns: anchor `idx` of (B, A)
-struct DetAnchor { int b, l, p, gi; size_t hw; float ax, ay, s, sc; };
+struct DetAnchor : MapsAnchor { int b, gi; float sc; };
 __device__ __forceinline__ DetAnchor det_anchor(const DetArgs& A, long long idx) {
-  DetAnchor t;
-  t.b = static_cast<int>(idx / A.A);
-  const int a = static_cast<int>(idx % A.A);
-  t.l = det_level(A, a);
-  t.p = a - A.a0[t.l];
-  const int Wl = A.W[t.l];
-  t.hw = static_cast<size_t>(A.H[t.l]) * Wl;
-  t.ax = static_cast<float>(t.p % Wl) + 0.5f; t.ay = static_cast<float>(t.p / Wl) + 0.5f;
-  t.s = A.stride[t.l];
-  t.gi = A.asg_gt[idx]; t.sc = A.asg_score[idx];
-  return t;
+  return DetAnchor{maps_anchor(A.maps, static_cast<int>(idx % A.maps.A)), static_cast<int>(idx / A.maps.A), A.asg_gt[idx], A.asg_score[idx]};
 }
 
 template <typename T>
@@ -402,12 +346,12 @@ __global__ __launch_bounds__(kBlock) void k_det_loss(const DetArgs A) {
   const int tid = static_cast<int>(threadIdx.x);
   const long long idx = static_cast<long long>(blockIdx.x) * kBlock + tid;
   float lbox = 0.f, lcls = 0.f, ldfl = 0.f;
-  if (idx < static_cast<long long>(A.B) * A.A) {
+  if (idx < static_cast<long long>(A.maps.B) * A.maps.A) {
     const DetAnchor t = det_anchor(A, idx);
-    const T* f = static_cast<const T*>(A.feat[t.l]) + static_cast<size_t>(t.b) * A.no * t.hw + t.p;
+    const T* f = maps_feat<T>(A.maps, t, t.b);
     const int label = t.gi >= 0 ? det_label(A, t.gi) : -1;
-    for (int c = 0; c < A.nc; ++c) {                           // BCEWithLogits against onehot(label) * score (loss.py:284)
-      const float x = to_f32<T>(f[(4 * kDetReg + c) * t.hw]);
+    for (int c = 0; c < A.maps.nc; ++c) {                           // BCEWithLogits against onehot(label) * score (loss.py:284)
+      const float x = to_f32<T>(f[(4 * kMapsReg + c) * t.hw]);
       lcls += fmaxf(x, 0.f) - (c == label ? x * t.sc : 0.f) + log1pf(expf(-fabsf(x)));
     }
     if (t.gi >= 0) {
@@ -416,16 +360,16 @@ __global__ __launch_bounds__(kBlock) void k_det_loss(const DetArgs A) {
       float d[4], dfl = 0.f;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        float p[kDetReg], lse, wl;
+        float p[kMapsReg], lse, wl;
         int tl;
         float vl = 0.f, vr = 0.f;
         det_dfl_target(det_side_target(tb, t.ax, t.ay, s), tl, wl);
 #pragma unroll
-        for (int j = 0; j < kDetReg; ++j) {
-          const float v = to_f32<T>(f[(s * kDetReg + j) * t.hw]);
+        for (int j = 0; j < kMapsReg; ++j) {
+          const float v = to_f32<T>(f[(s * kMapsReg + j) * t.hw]);
           vl = j == tl ? v : vl; vr = j == tl + 1 ? v : vr;
         }
-        det_side<T>(f, t.hw, s, p, d[s], lse);
+        maps_side<T>(f, t.hw, s, p, d[s], lse);
         dfl += (lse - vl) * wl + (lse - vr) * (1.f - wl);
       }
       const DetBox pb{t.ax - d[0], t.ay - d[1], t.ax + d[2], t.ay + d[3]};
@@ -448,7 +392,7 @@ __global__ __launch_bounds__(kBlock) void k_det_final(const DetArgs A) {
   for (int i = tid; i < A.nblk; i += kBlock) {
     s[0] += A.partial[i * 3]; s[1] += A.partial[i * 3 + 1]; s[2] += A.partial[i * 3 + 2];
   }
-  for (int b = tid; b < A.B; b += kBlock) { tss += A.tss_part[b]; bad += A.ovf[b] ? 1.f : 0.f; }
+  for (int b = tid; b < A.maps.B; b += kBlock) { tss += A.tss_part[b]; bad += A.ovf[b] ? 1.f : 0.f; }
 #pragma unroll
   for (int k = 0; k < 3; ++k) s[k] = block_sum(s[k], tid, red);
   tss = block_sum(tss, tid, red);
@@ -460,7 +404,7 @@ __global__ __launch_bounds__(kBlock) void k_det_final(const DetArgs A) {
   for (int k = 0; k < 3; ++k) {
     const float item = bad > 0.f ? nan : s[k] / tss * A.gain[k];
     A.items[k] = item;
-    A.out[k] = item * static_cast<float>(A.B);                 // loss.py:297
+    A.out[k] = item * static_cast<float>(A.maps.B);            // loss.py:297
   }
   A.fin[0] = bad > 0.f ? nan : tss;
   A.fin[1] = bad;
@@ -470,42 +414,42 @@ __global__ __launch_bounds__(kBlock) void k_det_final(const DetArgs A) {
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_det_bwd(const DetArgs A) {
   const long long idx = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
-  if (idx >= static_cast<long long>(A.B) * A.A) return;
-  const float tss = uniform_load(A.fin), Bf = static_cast<float>(A.B);      // tss: divided by, not multiplied with its reciprocal (one rounding less)
+  if (idx >= static_cast<long long>(A.maps.B) * A.maps.A) return;
+  const float tss = uniform_load(A.fin), Bf = static_cast<float>(A.maps.B);      // tss: divided by, not multiplied with its reciprocal (one rounding less)
   const float fbox = uniform_load(A.upstream) * A.gain[0] * Bf / tss, fcls = uniform_load(A.upstream + 1) * A.gain[1] * Bf / tss,
               fdfl = uniform_load(A.upstream + 2) * A.gain[2] * Bf / tss;
   const DetAnchor t = det_anchor(A, idx);
-  const size_t off = static_cast<size_t>(t.b) * A.no * t.hw + t.p;
-  const T* f = static_cast<const T*>(A.feat[t.l]) + off;
+  const size_t off = maps_offset(A.maps, t, t.b);
+  const T* f = static_cast<const T*>(A.maps.feat[t.l]) + off;
   T* g = static_cast<T*>(A.gfeat[t.l]) + off;
   const int label = t.gi >= 0 ? det_label(A, t.gi) : -1;
-  for (int c = 0; c < A.nc; ++c) {
-    const float x = to_f32<T>(f[(4 * kDetReg + c) * t.hw]);
-    g[(4 * kDetReg + c) * t.hw] = from_f32<T>(fcls * (sigmoidf_(x) - (c == label ? t.sc : 0.f)));
+  for (int c = 0; c < A.maps.nc; ++c) {
+    const float x = to_f32<T>(f[(4 * kMapsReg + c) * t.hw]);
+    g[(4 * kMapsReg + c) * t.hw] = from_f32<T>(fcls * (sigmoidf_(x) - (c == label ? t.sc : 0.f)));
   }
   if (t.gi < 0 || !(tss == tss)) {                             // background, or the poisoned call: no box terms (NaN where poisoned)
     const T z = from_f32<T>(t.gi < 0 && tss == tss ? 0.f : tss);
-    for (int c = 0; c < 4 * kDetReg; ++c) g[c * t.hw] = z;
+    for (int c = 0; c < 4 * kMapsReg; ++c) g[c * t.hw] = z;
     return;
   }
   const DetBox gp = det_gt_box(A, t.gi);
   const DetBox tb{gp.x1 / t.s, gp.y1 / t.s, gp.x2 / t.s, gp.y2 / t.s};
-  const DetBox pb = det_decode<T>(f, t.hw, t.ax, t.ay);
+  const DetBox pb = maps_decode<T>(f, t.hw, t.ax, t.ay);
   float gc[4];
   det_ciou_grad(pb, tb, gc);
   // the loss is (1 - CIoU) score: x1 = ax - d_l, y1 = ay - d_t, x2 = ax + d_r, y2 = ay + d_b
   const float wbox = fbox * t.sc, wdfl = fdfl * t.sc * 0.25f;
 #pragma unroll 1
   for (int s = 0; s < 4; ++s) {                                // a side at a time: 16 bins live, not 64
-    float p[kDetReg], d, lse, wl;
+    float p[kMapsReg], d, lse, wl;
     int tl;
     const float gds = s == 0 ? gc[0] : s == 1 ? gc[1] : s == 2 ? -gc[2] : -gc[3];
-    det_side<T>(f, t.hw, s, p, d, lse);
+    maps_side<T>(f, t.hw, s, p, d, lse);
     det_dfl_target(det_side_target(tb, t.ax, t.ay, s), tl, wl);
 #pragma unroll
-    for (int j = 0; j < kDetReg; ++j) {
+    for (int j = 0; j < kMapsReg; ++j) {
       const float hit = j == tl ? wl : (j == tl + 1 ? 1.f - wl : 0.f);
-      g[(s * kDetReg + j) * t.hw] = from_f32<T>(wdfl * (p[j] - hit) + wbox * gds * p[j] * (static_cast<float>(j) - d));
+      g[(s * kMapsReg + j) * t.hw] = from_f32<T>(wdfl * (p[j] - hit) + wbox * gds * p[j] * (static_cast<float>(j) - d));
     }
   }
 }

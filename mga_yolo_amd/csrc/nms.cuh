@@ -10,22 +10,17 @@
 //                  so a kill is read again only by the thread that wrote it.  Lists of up to kNmsLds entries are swept in LDS, longer
 //                  ones in the workspace.  It leaves the image's counter at 0 for the next call.
 #pragma once
-#include "common.cuh"
+#include "detmaps.cuh"
 
 namespace mgacbam {
 
-constexpr int kNmsLevelsMax = 4;               // = MGANMS_MAX_LEVELS (api_nms.hip asserts it)
-constexpr int kNmsReg = 16;                    // bins per box side
 constexpr int kNmsLds = 1024;                  // entries of a list that is swept in LDS (24 bytes each)
 typedef unsigned long long nms_key_t;
 
 struct NmsArgs {
-  const void* feat[kNmsLevelsMax];             // (B, 64 + nc, H_l, W_l), or
+  DetMaps maps;                                // the Detect maps (detmaps.cuh; n_levels = 0: B, nc and A alone), or
   const void* pred;                            // (B, 4 + nc, A)
-  int H[kNmsLevelsMax], W[kNmsLevelsMax];
-  int a0[kNmsLevelsMax + 1];
-  float stride[kNmsLevelsMax];
-  int n_levels, B, nc, no, A, bpi;             // bpi: k_nms_cand's workgroups per image
+  int bpi;                                     // k_nms_cand's workgroups per image
   float conf, iou;
   int max_det, max_nms, multi, agnostic, cand_cap;
   int* cnt;                                    // (B): candidates appended to the image's list (may exceed cand_cap: the overflow)
@@ -39,49 +34,26 @@ __device__ __forceinline__ nms_key_t nms_key(float score, int cand) {
 }
 __device__ __forceinline__ int nms_key_cand(nms_key_t k) { return static_cast<int>(~static_cast<unsigned>(k)); }
 
-// one side's distance: the softmax expectation over its 16 bins (head.py: DFL), as csrc/det.cuh's det_side
-template <typename T>
-__device__ __forceinline__ float nms_side(const T* __restrict__ f, size_t hw, int side) {
-  float p[kNmsReg], m = -FLT_MAX;
-#pragma unroll
-  for (int j = 0; j < kNmsReg; ++j) { p[j] = to_f32<T>(f[(side * kNmsReg + j) * hw]); m = fmaxf(m, p[j]); }
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < kNmsReg; ++j) { p[j] = expf(p[j] - m); sum += p[j]; }
-  const float inv = 1.f / sum;
-  float d = 0.f;
-#pragma unroll
-  for (int j = 0; j < kNmsReg; ++j) d += p[j] * inv * static_cast<float>(j);
-  return d;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_nms_cand(const NmsArgs A) {
   const int tid = static_cast<int>(threadIdx.x), lane = tid & (kWave - 1);
   const int b = static_cast<int>(blockIdx.x) / A.bpi, a = (static_cast<int>(blockIdx.x) % A.bpi) * kBlock + tid;
   if (blockIdx.x == 0 && tid == 0) *A.status = 0;
-  const bool live = a < A.A;
-  const int nc = A.nc;
+  const bool live = a < A.maps.A;
+  const int nc = A.maps.nc;
   // where the anchor's class values start and how far apart its channels lie
   const T* cls = nullptr;
   const T* f = nullptr;
-  size_t hw = 0;
-  float ax = 0.f, ay = 0.f, s = 0.f;
+  MapsAnchor t{};                                              // from pred: t.hw alone, the anchors
   if (live) {
     if (A.pred) {
-      hw = static_cast<size_t>(A.A);
-      f = static_cast<const T*>(A.pred) + static_cast<size_t>(b) * (4 + nc) * hw + a;
-      cls = f + 4 * hw;
+      t.hw = static_cast<size_t>(A.maps.A);
+      f = static_cast<const T*>(A.pred) + static_cast<size_t>(b) * (4 + nc) * t.hw + a;
+      cls = f + 4 * t.hw;
     } else {
-      int l = 0;
-#pragma unroll
-      for (int i = 1; i < kNmsLevelsMax; ++i)
-        if (i < A.n_levels && a >= A.a0[i]) l = i;
-      const int p = a - A.a0[l], Wl = A.W[l];
-      hw = static_cast<size_t>(A.H[l]) * Wl;
-      f = static_cast<const T*>(A.feat[l]) + static_cast<size_t>(b) * A.no * hw + p;
-      cls = f + 4 * kNmsReg * hw;
-      ax = static_cast<float>(p % Wl) + 0.5f; ay = static_cast<float>(p / Wl) + 0.5f; s = A.stride[l];
+      t = maps_anchor(A.maps, a);
+      f = maps_feat<T>(A.maps, t, b);
+      cls = f + 4 * kMapsReg * t.hw;
     }
   }
   const bool from_pred = A.pred != nullptr;
@@ -90,7 +62,7 @@ __global__ __launch_bounds__(kBlock) void k_nms_cand(const NmsArgs A) {
   float best_p = -1.f;
   if (live) {
     for (int c = 0; c < nc; ++c) {
-      const float v = to_f32<T>(cls[c * hw]);
+      const float v = to_f32<T>(cls[c * t.hw]);
       const float p = from_pred ? v : sigmoidf_(v);
       if (A.multi) m += p > A.conf ? 1 : 0;
       else if (p > best_p) { best_p = p; best_c = c; }
@@ -119,11 +91,11 @@ __global__ __launch_bounds__(kBlock) void k_nms_cand(const NmsArgs A) {
   if (m == 0) return;
   float4 box;
   if (from_pred) {                                             // ops.xywh2xyxy
-    const float cx = to_f32<T>(f[0]), cy = to_f32<T>(f[hw]), w2 = to_f32<T>(f[2 * hw]) * 0.5f, h2 = to_f32<T>(f[3 * hw]) * 0.5f;
+    const float cx = to_f32<T>(f[0]), cy = to_f32<T>(f[t.hw]), w2 = to_f32<T>(f[2 * t.hw]) * 0.5f, h2 = to_f32<T>(f[3 * t.hw]) * 0.5f;
     box = make_float4(cx - w2, cy - h2, cx + w2, cy + h2);
   } else {
-    box = make_float4((ax - nms_side<T>(f, hw, 0)) * s, (ay - nms_side<T>(f, hw, 1)) * s, (ax + nms_side<T>(f, hw, 2)) * s,
-                      (ay + nms_side<T>(f, hw, 3)) * s);
+    box = make_float4((t.ax - maps_dist<T>(f, t.hw, 0)) * t.s, (t.ay - maps_dist<T>(f, t.hw, 1)) * t.s, (t.ax + maps_dist<T>(f, t.hw, 2)) * t.s,
+                      (t.ay + maps_dist<T>(f, t.hw, 3)) * t.s);
   }
   const size_t row = static_cast<size_t>(b) * A.cand_cap;
   long long at_ = static_cast<long long>(base) + before;
@@ -132,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_nms_cand(const NmsArgs A) {
     return;
   }
   for (int c = 0; c < nc; ++c) {
-    const float v = to_f32<T>(cls[c * hw]);
+    const float v = to_f32<T>(cls[c * t.hw]);
     const float p = from_pred ? v : sigmoidf_(v);
     if (!(p > A.conf)) continue;
     if (at_ < A.cand_cap) { A.keys[row + at_] = nms_key(p, a * nc + c); A.boxes[row + at_] = box; }
@@ -202,7 +174,7 @@ __device__ __forceinline__ void nms_select(KP keys, int n, int max_nms, int tid,
 // The visit: returns the number of kept rows, written to dets and keep as it goes.
 template <typename KP, typename BP>
 __device__ __forceinline__ int nms_rounds(const NmsArgs& A, int b, int n, KP keys, BP boxes, int tid, NmsShared& S) {
-  const int lane = tid & (kWave - 1), wave = tid / kWave, nc = A.nc;
+  const int lane = tid & (kWave - 1), wave = tid / kWave, nc = A.maps.nc;
   const bool by_class = !A.agnostic && nc > 1;
   float* dets = A.dets + static_cast<size_t>(b) * A.max_det * 6;
   int* keep = A.keep + static_cast<size_t>(b) * A.max_det;

@@ -17,9 +17,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from ._binding import DTYPES, call, fill_det
+from ._binding import call, fill_det
+from .detmaps import REG_MAX, anchor_grid, check_maps, kernel_maps, raise_on_status, zero_maps
 
-REG_MAX = _lib.DET_REG_MAX
 EPS = 1e-7
 
 
@@ -41,16 +41,6 @@ def _ciou(p: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     v = (4 / math.pi ** 2) * (torch.atan(w2 / h2) - torch.atan(w1 / h1)) ** 2
     alpha = (v / (v - iou + (1 + EPS))).detach()
     return iou - (rho2 / c2 + v * alpha)
-
-
-def _anchors(feats, strides, dtype, device):
-    pts, st = [], []
-    for f, s in zip(feats, strides):
-        h, w = f.shape[2:]
-        yy, xx = torch.meshgrid(torch.arange(h, dtype=dtype, device=device) + 0.5, torch.arange(w, dtype=dtype, device=device) + 0.5, indexing="ij")
-        pts.append(torch.stack((xx, yy), -1).view(-1, 2))
-        st.append(torch.full((h * w, 1), float(s), dtype=dtype, device=device))
-    return torch.cat(pts), torch.cat(st)
 
 
 def _ground_truths(batch_idx, cls, bboxes, B: int, img_wh, dtype):
@@ -113,7 +103,7 @@ def _host_loss(feats, batch_idx, cls, bboxes, nc, strides, gains, topk, lowest_f
     x = torch.cat([f.reshape(B, no, -1) for f in feats], 2).permute(0, 2, 1)             # (B, A, no)
     A = x.shape[1]
     dist, scores = x[..., :4 * REG_MAX].reshape(B, A, 4, REG_MAX), x[..., 4 * REG_MAX:]
-    anc, st = _anchors(feats, strides, dtype, x.device)
+    anc, st = anchor_grid(feats, strides, dtype, x.device)
     dev = x.device
     d = dist.softmax(-1) @ torch.arange(REG_MAX, dtype=dtype, device=dev)
     pred = torch.cat((anc - d[..., :2], anc + d[..., 2:]), -1)                           # grid units
@@ -151,16 +141,12 @@ def _host_loss(feats, batch_idx, cls, bboxes, nc, strides, gains, topk, lowest_f
 # ---------------------------------------------------------------------------------------------------------------------------
 # HIP path
 # ---------------------------------------------------------------------------------------------------------------------------
-def _anchor_count(shapes) -> int:
-    return sum(s[-2] * s[-1] for s in shapes)
-
-
 class _DetState:
     """The buffers of one criterion call and its descriptor: outputs of the forward the backward reads again."""
 
     def __init__(self, feats, strides, nc, topk, m_cap, gains, batch_idx, cls, bboxes, n, out=None, g_feats=None, upstream=None):
         dev = feats[0].device
-        B, A = feats[0].shape[0], _anchor_count([f.shape for f in feats])
+        B, A = feats[0].shape[0], sum(f.shape[2] * f.shape[3] for f in feats)
         i32, f32 = torch.int32, torch.float32
         self.assign_gt = torch.empty(B, A, dtype=i32, device=dev)
         self.assign_score = torch.empty(B, A, dtype=f32, device=dev)
@@ -215,10 +201,7 @@ def detection_loss(feats: Sequence[torch.Tensor], batch_idx: torch.Tensor, cls: 
     NaN).  return_assignment adds a dict: fg (B, A), target_gt (B, A: the label row, -1 background), target_scores (B, A, nc),
     target_bboxes (B, A, 4 in pixels), weight (B, A), status (1)."""
     feats = list(feats)
-    if any(f.dim() != 4 or f.shape[1] != 4 * REG_MAX + nc or f.shape[0] != feats[0].shape[0] for f in feats):
-        raise ValueError(f"detection_loss: every feature map must be (B, {4 * REG_MAX + nc}, H, W)")
-    if len(strides) != len(feats):
-        raise ValueError("detection_loss: one stride per feature map")
+    check_maps("detection_loss", feats, nc, strides)
     dev = feats[0].device
     if not feats[0].is_cuda:
         if any(f.is_cuda for f in feats):
@@ -226,9 +209,7 @@ def detection_loss(feats: Sequence[torch.Tensor], batch_idx: torch.Tensor, cls: 
         b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
         loss, items, asg = _host_loss([f.float() for f in feats], b_, c_, x_, nc, strides, gains, topk)
         return (loss, items, asg) if return_assignment else (loss, items)
-    if len({f.dtype for f in feats}) != 1 or feats[0].dtype not in DTYPES:
-        feats = [f.float() for f in feats]
-    feats = [f.contiguous() for f in feats]                      # channels_last included: the kernels read NCHW
+    feats = kernel_maps(feats)
     b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
     if m_cap is None:
         m_cap = int(torch.bincount(b_.long().clamp(0, feats[0].shape[0] - 1)).max()) if b_.numel() else 1
@@ -279,7 +260,7 @@ class DetLossPlan:
         dev = torch.device(device)
         f32 = torch.float32
         self.device, self.nc, self.strides = dev, int(nc), tuple(int(s) for s in strides)
-        self.feats = [torch.zeros(B, 4 * REG_MAX + nc, H, W, dtype=dtype, device=dev) for B, H, W in shapes]
+        self.feats = zero_maps(shapes, nc, dtype, dev)
         self.g_feats = [torch.zeros_like(f) for f in self.feats]
         self.batch_idx = torch.zeros(n_cap, dtype=f32, device=dev)
         self.cls = torch.zeros(n_cap, dtype=f32, device=dev)
@@ -314,10 +295,7 @@ class DetLossPlan:
 
     def check_status(self):
         """Raise if the last forward met an image with more label rows than m_cap (a host read: not inside a capture)."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        if int(self.status.item()) != 0:
-            raise RuntimeError("DetLossPlan: an image has more ground truths than m_cap; the loss of that call is NaN")
+        raise_on_status(self.status, "DetLossPlan: an image has more ground truths than m_cap; the loss of that call is NaN")
 
     def assignment(self):
         return assignment_views(self.assign_gt, self.assign_score, self.status, self.cls, self.bboxes, self.nc,

@@ -20,9 +20,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._binding import DTYPES, call, fill_nms
-
-REG_MAX = 16
+from ._binding import call, fill_nms
+from .detmaps import REG_MAX, anchor_grid, check_maps, kernel_maps, raise_on_status, zero_maps
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -35,12 +34,8 @@ def _decode(feats, strides, nc: int):
     x = torch.cat([f.reshape(B, 4 * REG_MAX + nc, -1) for f in feats], 2)                # (B, no, A)
     A = x.shape[2]
     d = (x[:, :4 * REG_MAX].reshape(B, 4, REG_MAX, A).softmax(2) * torch.arange(REG_MAX, dtype=dtype, device=dev).view(1, 1, -1, 1)).sum(2)
-    ax, ay, st = [], [], []
-    for f, s in zip(feats, strides):
-        h, w = f.shape[2:]
-        yy, xx = torch.meshgrid(torch.arange(h, dtype=dtype, device=dev) + 0.5, torch.arange(w, dtype=dtype, device=dev) + 0.5, indexing="ij")
-        ax.append(xx.reshape(-1)); ay.append(yy.reshape(-1)); st.append(torch.full((h * w,), float(s), dtype=dtype, device=dev))
-    ax, ay, st = torch.cat(ax), torch.cat(ay), torch.cat(st)
+    anc, st = anchor_grid(feats, strides, dtype, dev)
+    ax, ay, st = anc[:, 0], anc[:, 1], st[:, 0]
     boxes = torch.stack(((ax - d[:, 0]) * st, (ay - d[:, 1]) * st, (ax + d[:, 2]) * st, (ay + d[:, 3]) * st), -1)
     return boxes, x[:, 4 * REG_MAX:].sigmoid().permute(0, 2, 1)
 
@@ -165,10 +160,7 @@ def detect_postprocess(feats, *, nc: int, strides: Sequence[int] = (8, 16, 32), 
         tensors = [pred]
     else:
         feats = list(feats)
-        if any(f.dim() != 4 or f.shape[1] != 4 * REG_MAX + nc or f.shape[0] != feats[0].shape[0] for f in feats):
-            raise ValueError(f"detect_postprocess: every feature map must be (B, {4 * REG_MAX + nc}, H, W)")
-        if len(strides) != len(feats):
-            raise ValueError("detect_postprocess: one stride per feature map")
+        check_maps("detect_postprocess", feats, nc, strides)
         tensors = feats
     if not tensors[0].is_cuda:
         if any(t.is_cuda for t in tensors):
@@ -177,9 +169,7 @@ def detect_postprocess(feats, *, nc: int, strides: Sequence[int] = (8, 16, 32), 
         d, c, k = _host_postprocess(None if feats is None else [up(f) for f in feats], None if pred is None else up(pred), nc, strides,
                                     conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic)
         return d.float(), c, k
-    if len({t.dtype for t in tensors}) != 1 or tensors[0].dtype not in DTYPES:
-        tensors = [t.float() for t in tensors]
-    tensors = [t.contiguous() for t in tensors]                  # channels_last included: the kernels read NCHW
+    tensors = kernel_maps(tensors)
     st = _PostState(tensors if feats is not None else None, tensors[0] if pred is not None else None, tuple(int(s) for s in strides),
                     int(nc), conf_thres, iou_thres, int(max_det), int(max_nms), multi_label, agnostic, cand_cap)
     st.run(tensors[0].device)
@@ -237,7 +227,7 @@ class DetPostPlan:
         _check_args(conf_thres, iou_thres, max_det, max_nms)
         dev = torch.device(device)
         if feats is None:
-            feats = [torch.zeros(B, 4 * REG_MAX + nc, H, W, dtype=dtype, device=dev) for B, H, W in shapes]
+            feats = zero_maps(shapes, nc, dtype, dev)
         return cls(list(feats), nc, strides, conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic, cand_cap, dets)
 
     def run(self):
@@ -245,7 +235,4 @@ class DetPostPlan:
 
     def check_status(self):
         """Raise if the last run met an image with more candidates than cand_cap (a host read: not inside a capture)."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        if int(self.status.item()) != 0:
-            raise RuntimeError("DetPostPlan: an image has more candidates than cand_cap; its count is -1 and its rows are NaN")
+        raise_on_status(self.status, "DetPostPlan: an image has more candidates than cand_cap; its count is -1 and its rows are NaN")
