@@ -1,10 +1,11 @@
-"""ctypes binding of libmgacbam.so (C ABI: include/mgacbam.h).  There is NO fallback: if the library is missing
+"""ctypes binding of libmgacbam.so (C ABI: the headers under include/, one record of HEADERS each).  There is NO fallback: if the library is missing
 or an entry point is absent, loading raises -- device tensors never take another path."""
 from __future__ import annotations
 
 import ctypes as C
 import os
 import threading
+from typing import NamedTuple
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGACBAM_LIB") or os.path.join(_PKG, "libmgacbam.so")   # MGACBAM_LIB: A/B builds in tuning sweeps
@@ -72,7 +73,6 @@ class CtxLayout(C.Structure):                    # mgacbam_ctx_layout_t
     _fields_ = [(n, C.c_int64) for n in CTX_FIELDS]
 
 
-# every symbol include/mgacbam.h declares: (restype, argtypes)
 class SegLevel(C.Structure):                     # mgaseg_level_t
     _fields_ = [("logits", C.c_void_p), ("target", C.c_void_p), ("glogits", C.c_void_p),
                 ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ht", C.c_int32), ("Wt", C.c_int32),
@@ -145,64 +145,6 @@ class GateLevel(C.Structure):                    # mgagate_level_t (include/mgag
                 ("tau", C.c_float), ("p_min", C.c_float), ("threshold", C.c_float)]
 
 
-SYMBOLS = {
-    "mgacbam_abi_version": (C.c_int, []),
-    "mgacbam_last_error": (C.c_char_p, []),
-    "mgacbam_build_info": (C.c_char_p, []),
-    "mgacbam_reload_env": (None, []),
-    "mgacbam_ctx_bytes": (C.c_size_t, [C.c_int] * 5),
-    "mgacbam_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 6),
-    "mgacbam_ctx_layout": (C.c_int, [C.c_int] * 5 + [C.POINTER(CtxLayout)]),
-    "mgacbam_fwd_ws_bytes": (C.c_size_t, [C.c_int] * 6),
-    "mgacbam_bwd_scratch_bytes_flags": (C.c_size_t, [C.c_int] * 7),
-    "mgacbam_forward": (C.c_int, [C.POINTER(FwdLevel), C.c_int, C.c_void_p]),
-    "mgacbam_backward": (C.c_int, [C.POINTER(BwdLevel), C.c_int, C.c_void_p]),
-    "mgacbam_forward_stages": (C.c_int, [C.POINTER(FwdLevel), C.c_int, C.c_int, C.c_void_p]),
-    "mgacbam_backward_stages": (C.c_int, [C.POINTER(BwdLevel), C.c_int, C.c_int, C.c_void_p]),
-    "mgacbam_resize_nearest": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
-    "mgacbam_eca_ctx_bytes": (C.c_size_t, [C.c_int] * 4),
-    "mgacbam_eca_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
-    "mgacbam_eca_ctx_bytes_flags": (C.c_size_t, [C.c_int] * 5),
-    "mgacbam_eca_scratch_bytes_flags": (C.c_size_t, [C.c_int] * 5),
-    "mgacbam_eca_forward": (C.c_int, [C.POINTER(EcaFwdLevel), C.c_int, C.c_void_p]),
-    "mgacbam_eca_backward": (C.c_int, [C.POINTER(EcaBwdLevel), C.c_int, C.c_void_p]),
-    "mgaseg_ws_bytes": (C.c_size_t, [C.POINTER(SegLevel), C.c_int]),
-    "mgaseg_forward": (C.c_int, [C.POINTER(SegLevel), C.c_int, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "mgaseg_backward": (C.c_int, [C.POINTER(SegLevel), C.c_int, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "mgahead_ctx_bytes": (C.c_size_t, [C.c_int] * 5),
-    "mgahead_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
-    "mgahead_ctx_bytes_flags": (C.c_size_t, [C.c_int] * 6),
-    "mgahead_bwd_scratch_bytes_flags": (C.c_size_t, [C.c_int] * 6),
-    "mgahead_forward": (C.c_int, [C.POINTER(HeadFwdLevel), C.c_int, C.c_void_p]),
-    "mgahead_backward": (C.c_int, [C.POINTER(HeadBwdLevel), C.c_int, C.c_void_p]),
-    "mgakendall_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgakendall_backward": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
-    "mgaseg_kendall_forward": (C.c_int, [C.POINTER(SegLevel), C.c_int, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgaseg_kendall_backward": (C.c_int, [C.POINTER(SegLevel), C.c_int, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6),
-    "mgapmg_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(PmgCfg), C.c_void_p]),
-    "mgapmg_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(PmgCfg), C.c_void_p]),
-}
-# every symbol include/mgaspade.h declares (MaskSPADE: a header of its own, include/mgacbam.h is unchanged by it)
-SPADE_SYMBOLS = {
-    "mgaspade_ctx_bytes": (C.c_size_t, [C.c_int] * 5),
-    "mgaspade_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
-    "mgaspade_forward": (C.c_int, [C.POINTER(SpadeLevel), C.c_int, C.c_void_p]),
-    "mgaspade_backward": (C.c_int, [C.POINTER(SpadeLevel), C.c_int, C.c_void_p]),
-}
-# every symbol include/mgagate.h declares (the pyramid gate with in-kernel Philox noise: a header of its own as well)
-GATE_SYMBOLS = {
-    "mgagate_forward": (C.c_int, [C.POINTER(GateLevel), C.c_int, C.c_void_p, C.c_void_p]),
-    "mgagate_backward": (C.c_int, [C.POINTER(GateLevel), C.c_int, C.c_void_p]),
-    "mgagate_philox4x32": (None, [C.POINTER(C.c_uint32)] * 3),
-    "mgagate_uniforms": (None, [C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_float)]),
-}
-
-# every symbol include/mgaresample.h declares (the mask resample of the static plans; include/mgaspade.h brings that header in)
-RESAMPLE_SYMBOLS = {
-    "mgaspade_resample_forward": (C.c_int, [C.POINTER(ResampleLevel), C.c_int, C.c_void_p]),
-    "mgaspade_resample_backward": (C.c_int, [C.POINTER(ResampleLevel), C.c_int, C.c_void_p]),
-}
-
 # the fused optimizer step over the plans' gradient bucket (include/mgaopt.h: a header of its own as well)
 OPT_SGD, OPT_ADAMW = 0, 1
 OPT_KINDS = dict(sgd=OPT_SGD, adamw=OPT_ADAMW)
@@ -226,14 +168,6 @@ class OptHyper(C.Structure):                     # mgaopt_hyper_t: device memory
                  ("reserved", C.c_int32 * 8)])
 
 
-# every symbol include/mgaopt.h declares
-OPT_SYMBOLS = {
-    "mgaopt_ws_bytes": (C.c_size_t, [C.POINTER(OptSegment), C.c_int]),
-    "mgaopt_ws_init": (C.c_int, [C.POINTER(OptSegment), C.c_int, C.c_void_p, C.c_size_t]),
-    "mgaopt_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mgaopt_step": (C.c_int, [C.POINTER(OptSegment), C.c_int, C.POINTER(OptCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-}
-
 # the multi-scale segmentation targets from full-resolution masks (include/mgatargets.h: a header of its own as well)
 TGT_AVGPOOL, TGT_MAXPOOL = 0, 1
 TGT_METHODS = dict(avgpool=TGT_AVGPOOL, maxpool=TGT_MAXPOOL)
@@ -248,12 +182,6 @@ class TargetsDesc(C.Structure):                  # mgatgt_desc_t
                 ("src_dtype", C.c_int32), ("method", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
-
-# every symbol include/mgatargets.h declares
-TARGETS_SYMBOLS = {
-    "mgatgt_scratch_bytes": (C.c_size_t, [C.POINTER(TargetsDesc)]),
-    "mgatgt_forward": (C.c_int, [C.POINTER(TargetsDesc), C.c_void_p]),
-}
 
 # the detection criterion -- TAL assignment, CIoU, DFL, BCE -- on the Detect maps (include/mgadet.h: a header of its own as well)
 DET_MAX_LEVELS, DET_MAX_TOPK, DET_MAX_GT, DET_REG_MAX = 4, 16, 256, 16
@@ -270,13 +198,6 @@ class DetDesc(C.Structure):                      # mgadet_desc_t
                 ("upstream", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
-# every symbol include/mgadet.h declares
-DET_SYMBOLS = {
-    "mgadet_ws_bytes": (C.c_size_t, [C.POINTER(DetDesc)]),
-    "mgadet_forward": (C.c_int, [C.POINTER(DetDesc), C.c_void_p]),
-    "mgadet_backward": (C.c_int, [C.POINTER(DetDesc), C.c_void_p]),
-}
-
 # the detection post-process -- Detect decode, candidates, greedy NMS -- (include/mganms.h: a header of its own as well)
 NMS_MAX_LEVELS, NMS_MULTI_LABEL, NMS_AGNOSTIC = 4, 1, 2
 
@@ -291,11 +212,132 @@ class NmsDesc(C.Structure):                      # mganms_desc_t
                 ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
-# every symbol include/mganms.h declares
-NMS_SYMBOLS = {
-    "mganms_ws_bytes": (C.c_size_t, [C.POINTER(NmsDesc)]),
-    "mganms_run": (C.c_int, [C.POINTER(NmsDesc), C.c_void_p]),
+class Header(NamedTuple):
+    """What one file under include/ declares and this module mirrors (tests/test_abi_headers.py holds each record against its header)."""
+    symbols: dict        # function -> (restype, argtypes)
+    structs: dict        # C struct tag -> ctypes mirror
+    constants: dict      # C #define / enumerator -> the Python value that mirrors it
+
+
+_BWD_STAGE_NAMES = dict(reduce1="REDUCE1", convT="CONVT", reduce2="REDUCE2", wsa="WSA", params="PARAMGRAD", apply="APPLY")
+_i = C.c_int
+HEADERS = {
+    "mgacbam.h": Header(
+        symbols={
+            "mgacbam_abi_version": (_i, []),
+            "mgacbam_last_error": (C.c_char_p, []),
+            "mgacbam_build_info": (C.c_char_p, []),
+            "mgacbam_reload_env": (None, []),
+            "mgacbam_ctx_bytes": (C.c_size_t, [_i] * 5),
+            "mgacbam_bwd_scratch_bytes": (C.c_size_t, [_i] * 6),
+            "mgacbam_ctx_layout": (_i, [_i] * 5 + [C.POINTER(CtxLayout)]),
+            "mgacbam_fwd_ws_bytes": (C.c_size_t, [_i] * 6),
+            "mgacbam_bwd_scratch_bytes_flags": (C.c_size_t, [_i] * 7),
+            "mgacbam_forward": (_i, [C.POINTER(FwdLevel), _i, C.c_void_p]),
+            "mgacbam_backward": (_i, [C.POINTER(BwdLevel), _i, C.c_void_p]),
+            "mgacbam_forward_stages": (_i, [C.POINTER(FwdLevel), _i, _i, C.c_void_p]),
+            "mgacbam_backward_stages": (_i, [C.POINTER(BwdLevel), _i, _i, C.c_void_p]),
+            "mgacbam_resize_nearest": (_i, [C.c_void_p, C.c_void_p] + [_i] * 5 + [C.c_void_p]),
+            "mgacbam_eca_ctx_bytes": (C.c_size_t, [_i] * 4),
+            "mgacbam_eca_scratch_bytes": (C.c_size_t, [_i] * 4),
+            "mgacbam_eca_ctx_bytes_flags": (C.c_size_t, [_i] * 5),
+            "mgacbam_eca_scratch_bytes_flags": (C.c_size_t, [_i] * 5),
+            "mgacbam_eca_forward": (_i, [C.POINTER(EcaFwdLevel), _i, C.c_void_p]),
+            "mgacbam_eca_backward": (_i, [C.POINTER(EcaBwdLevel), _i, C.c_void_p]),
+            "mgaseg_ws_bytes": (C.c_size_t, [C.POINTER(SegLevel), _i]),
+            "mgaseg_forward": (_i, [C.POINTER(SegLevel), _i, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+            "mgaseg_backward": (_i, [C.POINTER(SegLevel), _i, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+            "mgahead_ctx_bytes": (C.c_size_t, [_i] * 5),
+            "mgahead_bwd_scratch_bytes": (C.c_size_t, [_i] * 5),
+            "mgahead_ctx_bytes_flags": (C.c_size_t, [_i] * 6),
+            "mgahead_bwd_scratch_bytes_flags": (C.c_size_t, [_i] * 6),
+            "mgahead_forward": (_i, [C.POINTER(HeadFwdLevel), _i, C.c_void_p]),
+            "mgahead_backward": (_i, [C.POINTER(HeadBwdLevel), _i, C.c_void_p]),
+            "mgakendall_forward": (_i, [C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "mgakendall_backward": (_i, [C.c_void_p, _i] + [C.c_void_p] * 7),
+            "mgaseg_kendall_forward": (_i, [C.POINTER(SegLevel), _i, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, _i,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+            "mgaseg_kendall_backward": (_i, [C.POINTER(SegLevel), _i, C.POINTER(SegCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, _i] +
+                                        [C.c_void_p] * 6),
+            "mgapmg_forward": (_i, [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(PmgCfg), C.c_void_p]),
+            "mgapmg_backward": (_i, [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(PmgCfg), C.c_void_p]),
+        },
+        structs=dict(mgacbam_params=Params, mgacbam_fwd_level=FwdLevel, mgacbam_bwd_level=BwdLevel, mgacbam_ctx_layout=CtxLayout,
+                     mgacbam_eca_params=EcaParams, mgacbam_eca_fwd_level=EcaFwdLevel, mgacbam_eca_bwd_level=EcaBwdLevel,
+                     mgaseg_level=SegLevel, mgaseg_cfg=SegCfg, mgahead_params=HeadParams, mgahead_fwd_level=HeadFwdLevel,
+                     mgahead_bwd_level=HeadBwdLevel, mgapmg_cfg=PmgCfg),
+        constants=dict(
+            MGACBAM_ABI_VERSION=ABI_VERSION, MGACBAM_MAX_LEVELS=MAX_LEVELS, MGACBAM_F32=F32, MGACBAM_F16=F16, MGACBAM_BF16=BF16,
+            MGACBAM_PROJ_MAX_HIDDEN=PROJ_MAX_HIDDEN, MGACBAM_FWD_SAVE_PROJ=FWD_SAVE_PROJ, MGACBAM_BWD_HAVE_PROJ=BWD_HAVE_PROJ,
+            MGACBAM_LAYOUT_NHWC=LAYOUT_NHWC, MGACBAM_E_NULL=E_NULL, MGACBAM_E_SHAPE=E_SHAPE, MGACBAM_E_DTYPE=E_DTYPE, MGACBAM_E_ALIGN=E_ALIGN,
+            MGACBAM_E_LEVELS=E_LEVELS, MGACBAM_E_SIZE=E_SIZE,
+            **{"MGACBAM_FWD_" + k.upper(): v for k, v in FWD_STAGES.items()}, MGACBAM_FWD_ALL=FWD_ALL, MGACBAM_FWD_FUSE=FWD_FUSE,
+            **{"MGACBAM_BWD_" + _BWD_STAGE_NAMES[k]: v for k, v in BWD_STAGES.items()}, MGACBAM_BWD_FUSE=BWD_FUSE,
+            MGACBAM_BWD_PARAMS=BWD_PARAMS, MGACBAM_BWD_INPUTS=BWD_INPUTS, MGACBAM_BWD_ALL=BWD_ALL, MGACBAM_BWD_FOLD=BWD_FOLD,
+            MGASEG_MAX_LEVELS=SEG_MAX_LEVELS, MGASEG_NEAREST=SEG_NEAREST, MGASEG_BILINEAR=SEG_BILINEAR,
+            MGAHEAD_BWD_ACCUM_GX=HEAD_BWD_ACCUM_GX, MGAHEAD_LOGITS_F32=HEAD_LOGITS_F32, MGAHEAD_LAYOUT_NHWC=HEAD_LAYOUT_NHWC)),
+    "mgaspade.h": Header(                            # brings mgaresample.h in; each declaration belongs to the file that spells it
+        symbols={
+            "mgaspade_ctx_bytes": (C.c_size_t, [_i] * 5),
+            "mgaspade_scratch_bytes": (C.c_size_t, [_i] * 5),
+            "mgaspade_forward": (_i, [C.POINTER(SpadeLevel), _i, C.c_void_p]),
+            "mgaspade_backward": (_i, [C.POINTER(SpadeLevel), _i, C.c_void_p]),
+        },
+        structs=dict(mgaspade_level=SpadeLevel),
+        constants=dict(MGASPADE_NORM_IN=NORM_IN, MGASPADE_NORM_BN=NORM_BN, MGASPADE_LAYOUT_NHWC=SPADE_LAYOUT_NHWC)),
+    "mgaresample.h": Header(
+        symbols={
+            "mgaspade_resample_forward": (_i, [C.POINTER(ResampleLevel), _i, C.c_void_p]),
+            "mgaspade_resample_backward": (_i, [C.POINTER(ResampleLevel), _i, C.c_void_p]),
+        },
+        structs=dict(mgaspade_resample_level=ResampleLevel),
+        constants={}),
+    "mgagate.h": Header(
+        symbols={
+            "mgagate_forward": (_i, [C.POINTER(GateLevel), _i, C.c_void_p, C.c_void_p]),
+            "mgagate_backward": (_i, [C.POINTER(GateLevel), _i, C.c_void_p]),
+            "mgagate_philox4x32": (None, [C.POINTER(C.c_uint32)] * 3),
+            "mgagate_uniforms": (None, [C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_float)]),
+        },
+        structs=dict(mgagate_level=GateLevel),
+        constants={"MGAGATE_" + k.upper(): v for k, v in GATE_MODES.items()}),
+    "mgaopt.h": Header(
+        symbols={
+            "mgaopt_ws_bytes": (C.c_size_t, [C.POINTER(OptSegment), _i]),
+            "mgaopt_ws_init": (_i, [C.POINTER(OptSegment), _i, C.c_void_p, C.c_size_t]),
+            "mgaopt_accumulate": (_i, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+            "mgaopt_step": (_i, [C.POINTER(OptSegment), _i, C.POINTER(OptCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+        },
+        structs=dict(mgaopt_segment=OptSegment, mgaopt_cfg=OptCfg, mgaopt_hyper=OptHyper),
+        constants=dict({"MGAOPT_" + k.upper(): v for k, v in OPT_KINDS.items()},
+                       MGAOPT_GROUPS=OPT_GROUPS, MGAOPT_MAX_SEGMENTS=OPT_MAX_SEGMENTS, MGAOPT_CHUNK=OPT_CHUNK)),
+    "mgatargets.h": Header(
+        symbols={
+            "mgatgt_scratch_bytes": (C.c_size_t, [C.POINTER(TargetsDesc)]),
+            "mgatgt_forward": (_i, [C.POINTER(TargetsDesc), C.c_void_p]),
+        },
+        structs=dict(mgatgt_desc=TargetsDesc),
+        constants=dict({"MGATGT_" + k.upper(): v for k, v in TGT_METHODS.items()}, MGACBAM_E_ARG=E_ARG, MGATGT_SRC_U8=TGT_SRC_U8,
+                       MGATGT_SRC_F32=TGT_SRC_F32, MGATGT_CLOSE3=TGT_CLOSE3, MGATGT_MAX_LEVELS=TGT_MAX_LEVELS)),
+    "mgadet.h": Header(
+        symbols={
+            "mgadet_ws_bytes": (C.c_size_t, [C.POINTER(DetDesc)]),
+            "mgadet_forward": (_i, [C.POINTER(DetDesc), C.c_void_p]),
+            "mgadet_backward": (_i, [C.POINTER(DetDesc), C.c_void_p]),
+        },
+        structs=dict(mgadet_desc=DetDesc),
+        constants=dict(MGADET_MAX_LEVELS=DET_MAX_LEVELS, MGADET_MAX_TOPK=DET_MAX_TOPK, MGADET_MAX_GT=DET_MAX_GT)),
+    "mganms.h": Header(
+        symbols={
+            "mganms_ws_bytes": (C.c_size_t, [C.POINTER(NmsDesc)]),
+            "mganms_run": (_i, [C.POINTER(NmsDesc), C.c_void_p]),
+        },
+        structs=dict(mganms_desc=NmsDesc),
+        constants=dict(MGANMS_MAX_LEVELS=NMS_MAX_LEVELS, MGANMS_MULTI_LABEL=NMS_MULTI_LABEL, MGANMS_AGNOSTIC=NMS_AGNOSTIC)),
 }
+_bound = [name for h in HEADERS.values() for name in h.symbols]
+if len(_bound) != len(set(_bound)):
+    raise ImportError(f"_lib.HEADERS binds a symbol in two records: {sorted(n for n in set(_bound) if _bound.count(n) > 1)}")
 
 _lib = None
 _lock = threading.Lock()
@@ -319,13 +361,13 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **SPADE_SYMBOLS, **GATE_SYMBOLS, **RESAMPLE_SYMBOLS, **OPT_SYMBOLS, **TARGETS_SYMBOLS,
-                                         **DET_SYMBOLS, **NMS_SYMBOLS}.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise LibraryMissing(f"{LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype, fn.argtypes = res, args
+        for h in HEADERS.values():
+            for name, (res, args) in h.symbols.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError as e:
+                    raise LibraryMissing(f"{LIB_PATH} does not export {name}; rebuild it") from e
+                fn.restype, fn.argtypes = res, args
         v = lib.mgacbam_abi_version()
         if v != ABI_VERSION:
             raise LibraryMissing(f"{LIB_PATH} has ABI version {v}, expected {ABI_VERSION}; rebuild it")
@@ -416,37 +458,34 @@ def spade_scratch_bytes(B, Cc, H, W, hidden) -> int:
     return size("mgaspade_scratch_bytes", B, Cc, H, W, hidden)
 
 
-def seg_ws_bytes(levels, n: int) -> int:
-    """Workspace of a segmentation-loss call.  It depends on the whole level table, not on a few integers, so it is asked every time."""
-    nbytes = load().mgaseg_ws_bytes(levels, n)
-    if nbytes == 0:
-        check(E_SHAPE, "mgaseg_ws_bytes")
+def _table_size(symbol: str, refusal: int, *args, zero_is_an_answer: bool = False) -> int:
+    """A size query that reads a whole level table or descriptor, so it is asked every time: 0 is the library's refusal and raises as
+    `refusal` with its message -- unless 0 can be the answer, which a refusal is told apart from by its message."""
+    lib = load()
+    nbytes = getattr(lib, symbol)(*args)
+    if nbytes == 0 and (not zero_is_an_answer or lib.mgacbam_last_error()):
+        check(refusal, symbol)
     return nbytes
+
+
+def seg_ws_bytes(levels, n: int) -> int:
+    """Workspace of a segmentation-loss call."""
+    return _table_size("mgaseg_ws_bytes", E_SHAPE, levels, n)
 
 
 def targets_scratch_bytes(desc) -> int:
-    """Scratch of a target-pyramid call: 0 without TGT_CLOSE3.  0 is also the library's refusal, told apart by its message."""
-    lib = load()
-    nbytes = lib.mgatgt_scratch_bytes(C.byref(desc))
-    if nbytes == 0 and lib.mgacbam_last_error():
-        check(E_ARG, "mgatgt_scratch_bytes")
-    return nbytes
+    """Scratch of a target-pyramid call: 0 without TGT_CLOSE3."""
+    return _table_size("mgatgt_scratch_bytes", E_ARG, C.byref(desc), zero_is_an_answer=True)
 
 
 def det_ws_bytes(desc) -> int:
-    """Workspace of a detection-criterion call; 0 is the library's refusal and raises with its message."""
-    nbytes = load().mgadet_ws_bytes(C.byref(desc))
-    if nbytes == 0:
-        check(E_ARG, "mgadet_ws_bytes")
-    return nbytes
+    """Workspace of a detection-criterion call."""
+    return _table_size("mgadet_ws_bytes", E_ARG, C.byref(desc))
 
 
 def nms_ws_bytes(desc) -> int:
-    """Workspace of a detection post-process call; 0 is the library's refusal and raises with its message."""
-    nbytes = load().mganms_ws_bytes(C.byref(desc))
-    if nbytes == 0:
-        check(E_ARG, "mganms_ws_bytes")
-    return nbytes
+    """Workspace of a detection post-process call."""
+    return _table_size("mganms_ws_bytes", E_ARG, C.byref(desc))
 
 
 def sync_regions(B, Cc, H, W) -> dict:

@@ -17,6 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:                 # (tests/conftest.py does the same; this keeps `python tests/head_nchw_rows.py` working)
     sys.path.insert(0, ROOT)
+from abi_header import a16  # noqa: E402
 from oracle import maskhead_oracle as HO  # noqa: E402
 
 DT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
@@ -127,10 +128,6 @@ CASES = ([(r[0], dt, True, "flat") for r in HEAD_NCHW_ROWS for dt in r[1]] +
 CASE_IDS = [f"{n}-{dt}-{'train' if tr else 'eval'}-{g}" for n, dt, tr, g in CASES]
 
 
-def _a16(v):
-    return (v + 15) & ~15
-
-
 def _waves(mtiles, mtw, K):
     """api_head.hip: head_waves -> (mw as the kernel uses it, remapped from 3, kw, pw)."""
     mw = min(4, -(-mtiles // mtw))
@@ -158,7 +155,7 @@ def head_out_max(ppt, W):
 def head_geo(B, C, hid, H, W):
     """One NCHW level called alone, no knobs set; restated by hand (see the module's docstring)."""
     HW = H * W
-    g = dict(vec=4 if HW % 4 == 0 else 1, hidp=_a16(hid), cp=_a16(C))
+    g = dict(vec=4 if HW % 4 == 0 else 1, hidp=a16(hid), cp=a16(C))
     vec, hidp, cp = g["vec"], g["hidp"], g["cp"]
     # forward GEMM
     g["fw_mtw"] = 4 if hidp // 16 > 8 else 2
@@ -211,8 +208,8 @@ def head_geo(B, C, hid, H, W):
     # head_ctx_layout / head_scratch_layout: floats, each region rounded up to 16 bytes
     ctx = [B * hid * HW, hidp, hidp, hidp * HEAD_PAR, g["nwg"] * 2 * hidp]
     scr = [B * hid * HW, g["nwg1"] * hidp * HEAD_NSTAT, 5 * hidp, ncb * nshare * hidp * HEAD_CB]
-    g["ctx_bytes"] = sum(_a16(4 * n) for n in ctx)
-    g["scratch_bytes"] = sum(_a16(4 * n) for n in scr)
+    g["ctx_bytes"] = sum(a16(4 * n) for n in ctx)
+    g["scratch_bytes"] = sum(a16(4 * n) for n in scr)
     return g
 
 

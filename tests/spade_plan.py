@@ -8,6 +8,8 @@ ABI: it is mirrored from the source of sp_level alone, and only a change of that
 """
 from collections import namedtuple
 
+from abi_header import a16
+
 PX = 128           # kSpPx: pixels of a tile
 DW_TARGET = 512    # kSpDwTarget
 DH_CC = 32         # kSpDhCC: channels staged per round of k_spade_dh
@@ -17,10 +19,6 @@ MAX_LEVELS = 8     # MGACBAM_MAX_LEVELS
 
 def cdiv(a, b):
     return (a + b - 1) // b
-
-
-def a16(n):
-    return (n + 15) & ~15
 
 
 Tiling = namedtuple("Tiling", "TW TH ltw tiles_x tiles_y tiles")

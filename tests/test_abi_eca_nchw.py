@@ -3,26 +3,23 @@ queries, the forward and the backward alike, and the launch geometry of the rows
 here: every call below must fail its argument checks before anything touches a device."""
 import pytest
 
+from abi_header import fake
 from eca_nchw_rows import ECA_BWD_STATIC_LDS, KNOB_ROWS, LDS_PER_WORKGROUP, NCHW_ROWS, nchw_geo, nchw_max_c, row_case
 
 LIMIT = nchw_max_c()
 
 
-def _fake(addr=0x10000):
-    return addr          # a non-NULL, 16-byte aligned "pointer": the calls below must fail before anything dereferences it
-
-
 def _levels(_lib, lib, B, Cc, H, W, k, dtype):
     """One forward and one backward NCHW level on fake pointers; the capacities are those of a C the queries accept (they grow with C)."""
-    P = _lib.EcaParams(_fake(), _fake(), k, 1, 1e-4, 1e-6)
+    P = _lib.EcaParams(fake(), fake(), k, 1, 1e-4, 1e-6)
     fl = (_lib.EcaFwdLevel * 1)()
     F = fl[0]
-    F.x = F.mask = F.y = F.ctx = _fake()
+    F.x = F.mask = F.y = F.ctx = fake()
     F.p, F.B, F.C, F.H, F.W, F.dtype, F.flags = P, B, Cc, H, W, dtype, 0
     bl = (_lib.EcaBwdLevel * 1)()
     Bw = bl[0]
     for f in ("x", "mask", "gy", "ctx", "scratch", "gx", "gmask", "gw", "gbeta"):
-        setattr(Bw, f, _fake())
+        setattr(Bw, f, fake())
     Bw.p, Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype, Bw.flags = P, B, Cc, H, W, dtype, 0
     return fl, bl
 

@@ -2,71 +2,10 @@
 the rows tests/test_gpu_eca_channels_last.py runs at the corners of the tiling.  No kernel is launched here: every call below must fail
 its argument checks before anything touches a device."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "mgacbam.h")
-# sizeof(mgacbam_eca_fwd_level_t) / sizeof(mgacbam_eca_bwd_level_t) on x86-64 BEFORE the flags field existed (a C program on that header
-# printed 96 and 144, with `dtype` at offsets 88 and 136: 4 bytes of tail padding each, which the new field takes)
-SIZEOF_FWD, SIZEOF_BWD = 96, 144
-
-
-def _header():
-    return open(HEADER).read()
-
-
-def _struct_fields(tag):
-    """[(C type, name)] of `typedef struct <tag> { ... }` in the header, comments stripped, `int32_t B, C, H, W;` expanded."""
-    body = re.search(r"typedef struct " + tag + r" \{(.*?)\} " + tag + r"_t;", _header(), re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    out = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"(.*?[\s\*])(\w+(?:\s*,\s*\w+)*)$", decl)
-        typ, names = m.group(1).strip(), [n.strip() for n in m.group(2).split(",")]
-        out += [(typ, n) for n in names]
-    return out
-
-
-def _ctype(typ, structs):
-    if "*" in typ:
-        return C.c_void_p
-    return {"size_t": C.c_size_t, "int32_t": C.c_int32, "float": C.c_float, "int64_t": C.c_int64, **structs}[typ]
-
-
-def _mirror_of_header(tag, structs):
-    return type(tag, (C.Structure,), {"_fields_": [(n, _ctype(t, structs)) for t, n in _struct_fields(tag)]})
-
-
-def test_abi_version_is_unchanged(built_lib):
-    from mga_yolo_amd import _lib
-    assert int(re.search(r"#define MGACBAM_ABI_VERSION (\d+)", _header()).group(1)) == 15 == _lib.ABI_VERSION
-    assert _lib.load().mgacbam_abi_version() == 15
-    assert int(re.search(r"MGACBAM_LAYOUT_NHWC\s*=\s*(\d+)", _header()).group(1)) == _lib.LAYOUT_NHWC == 2
-
-
-def test_flags_is_the_last_field_and_the_structs_keep_their_size(built_lib):
-    from mga_yolo_amd import _lib
-    P = _mirror_of_header("mgacbam_eca_params", {})
-    assert C.sizeof(P) == C.sizeof(_lib.EcaParams)
-    for tag, mirror, size in (("mgacbam_eca_fwd_level", _lib.EcaFwdLevel, SIZEOF_FWD), ("mgacbam_eca_bwd_level", _lib.EcaBwdLevel, SIZEOF_BWD)):
-        fields = _struct_fields(tag)
-        assert fields[-1] == ("int32_t", "flags") and fields[-2] == ("int32_t", "dtype"), tag
-        assert [n for _, n in fields] == [f[0] for f in mirror._fields_], tag
-        assert mirror._fields_[-1][0] == "flags" and mirror._fields_[-1][1] is C.c_int32
-        H = _mirror_of_header(tag, {"mgacbam_eca_params_t": P})
-        assert C.sizeof(H) == C.sizeof(mirror) == size, tag
-        for name, _ in mirror._fields_:
-            assert getattr(H, name).offset == getattr(mirror, name).offset, (tag, name)
-        assert getattr(mirror, "flags").offset == size - 4 and getattr(mirror, "dtype").offset == size - 8
-        assert mirror().flags == 0                                  # a zero-filled level is an NCHW level
-
+from abi_header import a16, fake, read
 
 SHAPES = [(1, 1, 1, 1), (2, 64, 16, 16), (32, 64, 80, 80), (32, 128, 40, 40), (32, 256, 20, 20), (1, 48, 17, 17), (3, 5, 7, 9),
           (2, 1024, 10, 10), (2, 130, 48, 47), (1, 72, 140, 120), (11, 7, 30, 31), (5, 12, 700, 3), (2, 4096, 4, 4)]
@@ -76,7 +15,7 @@ def test_size_queries_are_declared_bound_and_layout_aware(built_lib):
     from mga_yolo_amd import _lib
     lib = _lib.load()
     for name in ("mgacbam_eca_ctx_bytes_flags", "mgacbam_eca_scratch_bytes_flags"):
-        assert name in _lib.SYMBOLS and re.search(r"\b" + name + r"\s*\(", _header()) and hasattr(lib, name)
+        assert name in _lib.HEADERS["mgacbam.h"].symbols and name in read("mgacbam.h").functions and hasattr(lib, name)
     N = _lib.LAYOUT_NHWC
     for B, Cc, H, W in SHAPES:
         ctx0, scr0 = lib.mgacbam_eca_ctx_bytes(B, Cc, H, W), lib.mgacbam_eca_scratch_bytes(B, Cc, H, W)
@@ -97,21 +36,17 @@ def test_size_queries_are_declared_bound_and_layout_aware(built_lib):
     assert lib.mgacbam_eca_scratch_bytes_flags(2, 64, 8, 8, 4) == 0
 
 
-def _fake(addr=0x10000):
-    return addr          # a non-NULL, 16-byte aligned "pointer": the calls below must fail before anything dereferences it
-
-
 def _levels(_lib, B, Cc, H, W, k, dtype, flags):
-    P = _lib.EcaParams(_fake(), _fake(), k, 1, 1e-4, 1e-6)
+    P = _lib.EcaParams(fake(), fake(), k, 1, 1e-4, 1e-6)
     fl = (_lib.EcaFwdLevel * 1)()
     F = fl[0]
-    F.x = F.mask = F.y = F.ctx = _fake()
+    F.x = F.mask = F.y = F.ctx = fake()
     F.p, F.B, F.C, F.H, F.W, F.dtype, F.flags = P, B, Cc, H, W, dtype, flags
     F.ctx_bytes = _lib.eca_ctx_bytes(B, Cc, H, W, flags)
     bl = (_lib.EcaBwdLevel * 1)()
     Bw = bl[0]
     for f in ("x", "mask", "gy", "ctx", "scratch", "gx", "gmask", "gw", "gbeta"):
-        setattr(Bw, f, _fake())
+        setattr(Bw, f, fake())
     Bw.p, Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype, Bw.flags = P, B, Cc, H, W, dtype, flags
     Bw.ctx_bytes = _lib.eca_ctx_bytes(B, Cc, H, W, flags)
     Bw.scratch_bytes = _lib.eca_scratch_bytes(B, Cc, H, W, flags)
@@ -161,23 +96,23 @@ def test_misaligned_nhwc_features_and_unknown_flags_are_refused(built_lib):
     from mga_yolo_amd import _lib
     lib = _lib.load()
     fl, bl = _levels(_lib, 2, 64, 16, 16, 5, _lib.F32, _lib.LAYOUT_NHWC)
-    fl[0].x = _fake() + 4                                          # fp32 with C % 4 == 0: 16-byte lanes
+    fl[0].x = fake() + 4                                          # fp32 with C % 4 == 0: 16-byte lanes
     assert lib.mgacbam_eca_forward(fl, 1, None) == _lib.E_ALIGN
-    fl[0].x = _fake()
-    fl[0].y = _fake() + 8
+    fl[0].x = fake()
+    fl[0].y = fake() + 8
     assert lib.mgacbam_eca_forward(fl, 1, None) == _lib.E_ALIGN
     for f in ("x", "gy", "gx"):
-        setattr(bl[0], f, _fake() + 4)
+        setattr(bl[0], f, fake() + 4)
         assert lib.mgacbam_eca_backward(bl, 1, None) == _lib.E_ALIGN, f
-        setattr(bl[0], f, _fake())
+        setattr(bl[0], f, fake())
     fl2, _ = _levels(_lib, 2, 64, 16, 16, 5, _lib.BF16, _lib.LAYOUT_NHWC)     # bf16 with C % 8 == 0: 16-byte lanes as well
-    fl2[0].x = _fake() + 8
+    fl2[0].x = fake() + 8
     assert lib.mgacbam_eca_forward(fl2, 1, None) == _lib.E_ALIGN
     fl3, bl3 = _levels(_lib, 2, 6, 16, 16, 3, _lib.F16, _lib.LAYOUT_NHWC)     # C = 6: scalar lanes, 2-byte alignment is enough ...
-    fl3[0].x = _fake() + 2
+    fl3[0].x = fake() + 2
     fl3[0].ctx_bytes = 0                                                      # ... so the call gets past it, to the capacity check
     assert lib.mgacbam_eca_forward(fl3, 1, None) == _lib.E_SIZE
-    fl3[0].x = _fake() + 1
+    fl3[0].x = fake() + 1
     assert lib.mgacbam_eca_forward(fl3, 1, None) == _lib.E_ALIGN
     for bad in (1, 4, _lib.LAYOUT_NHWC | 8, 1 << 30):
         fl, bl = _levels(_lib, 2, 64, 16, 16, 5, _lib.F32, _lib.LAYOUT_NHWC)
@@ -217,10 +152,6 @@ def _nhwc_geo(Cc, H, W, vec):
                 ncb=-(-Cc // 64), fold_partial=Cc > 64 and Cc % 64 != 0)
 
 
-def _a16(n):
-    return (n + 15) & ~15
-
-
 def test_eca_edge_rows_reach_every_tiling_branch(built_lib):
     from mga_yolo_amd import _lib
     from test_gpu_channels_last_edges import EDGE_ROWS
@@ -232,8 +163,8 @@ def test_eca_edge_rows_reach_every_tiling_branch(built_lib):
     for name, dt, B, Cc, H, W, k, kind, mask3d, mask_grad in ECA_EDGE_ROWS:
         assert cbam[(dt, B, Cc, H, W)] == (kind, mask3d, mask_grad), name       # shapes and mask kinds are the MaskCBAM rows'
         nchunk = max(_nhwc_geo(Cc, H, W, _nhwc_vec(Cc, d))["nchunk"] for d in ("f32", "f16"))
-        assert lib.mgacbam_eca_ctx_bytes_flags(B, Cc, H, W, N) - lib.mgacbam_eca_ctx_bytes(B, Cc, H, W) == _a16(B * nchunk * (2 * Cc + 4) * 4), name
-        assert lib.mgacbam_eca_scratch_bytes_flags(B, Cc, H, W, N) - lib.mgacbam_eca_scratch_bytes(B, Cc, H, W) == _a16(B * nchunk * Cc * 4), name
+        assert lib.mgacbam_eca_ctx_bytes_flags(B, Cc, H, W, N) - lib.mgacbam_eca_ctx_bytes(B, Cc, H, W) == a16(B * nchunk * (2 * Cc + 4) * 4), name
+        assert lib.mgacbam_eca_scratch_bytes_flags(B, Cc, H, W, N) - lib.mgacbam_eca_scratch_bytes(B, Cc, H, W) == a16(B * nchunk * Cc * 4), name
         rows.append(dict(_nhwc_geo(Cc, H, W, _nhwc_vec(Cc, dt)), name=name, dt=dt, B=B, C=Cc, H=H, W=W, k=k, kind=kind, mask3d=mask3d,
                          mask_grad=mask_grad))
     want = [("f32", 130, 23, 17), ("f32", 130, 48, 47), ("f32", 16, 190, 190), ("f32", 256, 40, 52), ("f16", 260, 20, 13), ("bf16", 520, 12, 12),

@@ -5,6 +5,7 @@ kernel is launched here: every call below must fail its argument checks before a
 import pytest
 import torch
 
+from abi_header import fake
 from conftest import rel_err
 from head_nchw_rows import (CASES, HEAD_NCHW_ROWS, HO, OUTPUTS, TOL, U_BAR, U_ORACLE32, head_geo, measure_oracle_u, oracle32, row_case)
 
@@ -107,24 +108,20 @@ def test_restated_layouts_equal_the_library_s_size_queries(built_lib):
 # ---------------------------------------------------------------------------------------------------------------------------
 # (c) argument validation of an NCHW level
 # ---------------------------------------------------------------------------------------------------------------------------
-def _fake(addr=0x10000):
-    return addr          # a non-NULL, 16-byte aligned "pointer": the calls below must fail before anything dereferences it
-
-
 BWD_PTRS = ("x", "g_logits", "ctx", "scratch", "gx", "gw1", "gbn_weight", "gbn_bias", "gwh", "gbh")
 
 
 def _levels(_lib, lib, B, Cc, hid, H, W, dtype, eps=1e-3, momentum=0.03):
-    HP = _lib.HeadParams(*([_fake()] * 8), hid, eps, momentum, 1)
+    HP = _lib.HeadParams(*([fake()] * 8), hid, eps, momentum, 1)
     fl = (_lib.HeadFwdLevel * 1)()
     F = fl[0]
-    F.x = F.logits = F.ctx = _fake()
+    F.x = F.logits = F.ctx = fake()
     F.p, F.B, F.C, F.H, F.W, F.dtype, F.flags = HP, B, Cc, H, W, dtype, 0
     F.ctx_bytes = lib.mgahead_ctx_bytes(B, Cc, H, W, hid)
     bl = (_lib.HeadBwdLevel * 1)()
     Bw = bl[0]
     for f in BWD_PTRS:
-        setattr(Bw, f, _fake())
+        setattr(Bw, f, fake())
     Bw.p, Bw.B, Bw.C, Bw.H, Bw.W, Bw.dtype, Bw.flags = HP, B, Cc, H, W, dtype, 0
     Bw.ctx_bytes, Bw.scratch_bytes = F.ctx_bytes, lib.mgahead_bwd_scratch_bytes(B, Cc, H, W, hid)
     return fl, bl
@@ -139,12 +136,12 @@ def test_misaligned_features_are_refused(built_lib, hw, dt, need):
     (H, W), dtype = hw, getattr(_lib, dt)
     for off in {need // 2, 1}:
         fl, bl = _levels(_lib, lib, 2, 20, 8, H, W, dtype)
-        fl[0].x = _fake() + off
+        fl[0].x = fake() + off
         assert lib.mgahead_forward(fl, 1, None) == _lib.E_ALIGN
         assert f"x must be {need}-byte aligned".encode() in lib.mgacbam_last_error(), lib.mgacbam_last_error()
         for f in ("x", "gx"):
             fl, bl = _levels(_lib, lib, 2, 20, 8, H, W, dtype)
-            setattr(bl[0], f, _fake() + off)
+            setattr(bl[0], f, fake() + off)
             assert lib.mgahead_backward(bl, 1, None) == _lib.E_ALIGN, f
             assert f"x/gx must be {need}-byte aligned".encode() in lib.mgacbam_last_error(), lib.mgacbam_last_error()
 
@@ -154,11 +151,11 @@ def test_misaligned_work_buffers_are_refused(built_lib):
     lib = _lib.load()
     for off in (4, 8):
         fl, bl = _levels(_lib, lib, 2, 20, 8, 7, 5, _lib.F32)
-        fl[0].ctx = _fake() + off
+        fl[0].ctx = fake() + off
         assert lib.mgahead_forward(fl, 1, None) == _lib.E_ALIGN and b"ctx 16-byte" in lib.mgacbam_last_error()
         for f in ("ctx", "scratch"):
             fl, bl = _levels(_lib, lib, 2, 20, 8, 7, 5, _lib.F32)
-            setattr(bl[0], f, _fake() + off)
+            setattr(bl[0], f, fake() + off)
             assert lib.mgahead_backward(bl, 1, None) == _lib.E_ALIGN and b"ctx/scratch 16-byte" in lib.mgacbam_last_error(), f
 
 

@@ -1,18 +1,12 @@
-"""CPU-side checks of the MaskSPADE layout flag (MGASPADE_LAYOUT_NHWC in mgaspade_level_t.flags) on the built library: its value in the
-header and the mirror, that a flagged level gets past the flags check and meets every later check, that every other bit is still
+"""CPU-side checks of the MaskSPADE layout flag (MGASPADE_LAYOUT_NHWC in mgaspade_level_t.flags) on the built library: that it is
+MGACBAM_LAYOUT_NHWC's value, that a flagged level gets past the flags check and meets every later check, that every other bit is still
 refused, and that the binding writes the field.  Levels are built over fake pointers as tests/test_abi_spade.py builds them: every
 call here returns before anything is launched (there is no GPU here: a call that got past its checks would crash on the pointers)."""
-import os
-import re
-import sys
-
 import pytest
 import torch
 
-from conftest import ROOT
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_abi_spade import _level  # noqa: E402
+from abi_header import read
+from test_abi_spade import _level
 
 NHWC = 2
 E_SHAPE, E_ALIGN, E_SIZE = -2, -4, -6
@@ -34,9 +28,7 @@ def test_a_flagged_level_passes_the_flags_check_and_meets_the_capacity_check(bui
 
 def test_layout_constant():
     from mga_yolo_amd import _lib
-    strip = lambda path: re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    spade = int(re.search(r"MGASPADE_LAYOUT_NHWC = (\d+)", strip(os.path.join(ROOT, "include", "mgaspade.h"))).group(1))
-    cbam = int(re.search(r"MGACBAM_LAYOUT_NHWC = (\d+)", strip(os.path.join(ROOT, "include", "mgacbam.h"))).group(1))
+    spade, cbam = read("mgaspade.h").constants["MGASPADE_LAYOUT_NHWC"], read("mgacbam.h").constants["MGACBAM_LAYOUT_NHWC"]
     assert spade == _lib.SPADE_LAYOUT_NHWC == NHWC == cbam == _lib.LAYOUT_NHWC
 
 

@@ -1,81 +1,11 @@
-"""CPU-side checks of the target-pyramid entry points (include/mgatargets.h) on the built library: symbols, the descriptor's layout against
-the C compiler's, the scratch query, and every refusal -- each returned, with its message, before anything is launched (there is no GPU
-here: a call that got past its checks would fail differently).  include/mgacbam.h and its ABI version are unchanged."""
+"""CPU-side checks of the target-pyramid entry points (include/mgatargets.h) on the built library: the scratch query, and every refusal --
+each returned, with its message, before anything is launched (there is no GPU here: a call that got past its checks would fail
+differently).  The header against the binding is tests/test_abi_headers.py's."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "mgatargets.h")
-MAIN_HEADER = os.path.join(ROOT, "include", "mgacbam.h")
-P = 0x10000                                                # non-NULL, 16-byte aligned; every call below fails before it is dereferenced
-
-
-def _src():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _fields():
-    body = re.search(r"typedef struct mgatgt_desc \{(.*?)\}", _src(), re.S).group(1)
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            names = decl.split(",")
-            out.append(re.sub(r"\[.*?\]", "", names[0].split()[-1]).lstrip("*"))
-            out += [re.sub(r"\[.*?\]", "", n).strip().lstrip("*") for n in names[1:]]
-    return out
-
-
-def test_symbols_exist_and_the_main_abi_is_unchanged(built_lib):
-    from mga_yolo_amd import _lib
-    declared = sorted(set(re.findall(r"\b(mgatgt_\w+)\s*\(", _src())))
-    assert declared == sorted(_lib.TARGETS_SYMBOLS) == ["mgatgt_forward", "mgatgt_scratch_bytes"]
-    raw = C.CDLL(built_lib)
-    for name in declared:
-        assert hasattr(raw, name)
-    lib = _lib.load()
-    assert lib.mgacbam_abi_version() == 15 == _lib.ABI_VERSION
-    main = re.sub(r"/\*.*?\*/", "", open(MAIN_HEADER).read(), flags=re.S)
-    assert int(re.search(r"#define MGACBAM_ABI_VERSION (\d+)", main).group(1)) == 15
-    assert "mgatgt" not in main and "MGACBAM_E_ARG" not in main                          # additive: a header of its own
-    enum = {k: int(v) for k, v in re.findall(r"(MGA\w+) = (-?\d+)", _src())}
-    assert enum == dict(MGACBAM_E_ARG=_lib.E_ARG, MGATGT_AVGPOOL=_lib.TGT_AVGPOOL, MGATGT_MAXPOOL=_lib.TGT_MAXPOOL, MGATGT_SRC_U8=_lib.TGT_SRC_U8,
-                        MGATGT_SRC_F32=_lib.TGT_SRC_F32)
-    assert _lib.E_ARG == -7 and _lib.E_ARG not in (_lib.E_NULL, _lib.E_SHAPE, _lib.E_DTYPE, _lib.E_ALIGN, _lib.E_LEVELS, _lib.E_SIZE)
-    define = {k: int(v) for k, v in re.findall(r"#define (MGATGT_\w+) (\d+)", _src())}
-    assert define == dict(MGATGT_CLOSE3=_lib.TGT_CLOSE3, MGATGT_MAX_LEVELS=_lib.TGT_MAX_LEVELS)
-
-
-def test_struct_mirror_matches_the_header_and_the_compiler(tmp_path):
-    from mga_yolo_amd import _lib
-    D = _lib.TargetsDesc
-    fields = _fields()
-    assert fields == [f[0] for f in D._fields_]
-    # by hand (LP64): src, dst[4] -- five pointers; stride[4] and eight more int32; scratch, scratch_bytes
-    want = dict(src=0, dst=8, stride=40, n_levels=56, B=60, H=64, W=68, src_dtype=72, method=76, flags=80, reserved=84, scratch=88,
-                scratch_bytes=96)
-    assert {name: getattr(D, name).offset for name in fields} == want and C.sizeof(D) == 104
-    assert D.dst.size == 32 and D.stride.size == 16
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        return                                               # the hand-computed layout above stands alone
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mgatargets.h"', "int main(void) {",
-             '  printf("size %zu\\n", sizeof(mgatgt_desc_t));']
-    lines += [f'  printf("{f} %zu\\n", offsetof(mgatgt_desc_t, {f}));' for f in fields]
-    lines += ["  return 0;", "}"]
-    (tmp_path / "layout.c").write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.run([cc, "-I", os.path.dirname(HEADER), str(tmp_path / "layout.c"), "-o", exe], check=True)
-    got = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["size"]) == C.sizeof(D)
-    for name, _ in D._fields_:
-        assert int(got[name]) == getattr(D, name).offset, name
+from abi_header import FAKE as P, a16
 
 
 def _desc(_lib, strides=(8, 16, 32), **over):
@@ -91,10 +21,6 @@ def _desc(_lib, strides=(8, 16, 32), **over):
         else:
             setattr(D, k, v)
     return D
-
-
-def a16(n):
-    return (n + 15) & ~15
 
 
 # the closing's scratch at (2, 100, 76), strides 8 / 16 / 32: levels of 13x10, 7x5 and 4x3 cells, fp32, each 16-byte aligned

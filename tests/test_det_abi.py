@@ -1,85 +1,17 @@
-"""CPU-side checks of the detection criterion (include/mgadet.h): symbols, the descriptor's layout against the C compiler's, the size
+"""CPU-side checks of the detection criterion (include/mgadet.h; the header against the binding is tests/test_abi_headers.py's): the size
 query, every refusal -- each returned, with its message, before anything is launched (there is no GPU here) -- and the host path of
 mga_yolo_amd.detloss against the reference's stored results and the fp64 oracle, under both tie orders."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import det_oracle as O
-from conftest import ROOT
+from abi_header import FAKE as P, a16
 
-HEADER = os.path.join(ROOT, "include", "mgadet.h")
-MAIN_HEADER = os.path.join(ROOT, "include", "mgacbam.h")
-P = 0x10000                                                # non-NULL, 16-byte aligned; every call below fails before it is dereferenced
 EPS32 = float(np.finfo(np.float32).eps)
-
-
-def _src():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _fields():
-    body = re.search(r"typedef struct mgadet_desc \{(.*?)\}", _src(), re.S).group(1)
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            names = decl.split(",")
-            out.append(re.sub(r"\[.*?\]", "", names[0].split()[-1]).lstrip("*"))
-            out += [re.sub(r"\[.*?\]", "", n).strip().lstrip("*") for n in names[1:]]
-    return out
-
-
-def test_symbols_exist_and_the_main_abi_is_unchanged(built_lib):
-    from mga_yolo_amd import _lib
-    declared = sorted(set(re.findall(r"\b(mgadet_\w+)\s*\(", _src())))
-    assert declared == sorted(_lib.DET_SYMBOLS) == ["mgadet_backward", "mgadet_forward", "mgadet_ws_bytes"]
-    raw = C.CDLL(built_lib)
-    for name in declared:
-        assert hasattr(raw, name)
-    assert _lib.load().mgacbam_abi_version() == 15 == _lib.ABI_VERSION
-    main = re.sub(r"/\*.*?\*/", "", open(MAIN_HEADER).read(), flags=re.S)
-    assert "mgadet" not in main
-    assert '#include "mgatargets.h"' in _src() and "MGACBAM_E_ARG =" not in _src()       # the code is reused, not redefined
-    define = {k: int(v) for k, v in re.findall(r"#define (MGADET_\w+) (\d+)", _src())}
-    assert define == dict(MGADET_MAX_LEVELS=_lib.DET_MAX_LEVELS, MGADET_MAX_TOPK=_lib.DET_MAX_TOPK, MGADET_MAX_GT=_lib.DET_MAX_GT)
-
-
-def test_struct_mirror_matches_the_header_and_the_compiler(tmp_path):
-    from mga_yolo_amd import _lib
-    D = _lib.DetDesc
-    fields = _fields()
-    assert fields == [f[0] for f in D._fields_]
-    # by hand (LP64): 2 x 4 pointers; 3 x 4 int32; 8 int32; 3 floats + 1 int32; 10 pointers; ws, ws_bytes
-    want = dict(feats=0, g_feats=32, H=64, W=80, stride=96, n_levels=112, B=116, nc=120, reg_max=124, dtype=128, topk=132, n_cap=136,
-                m_cap=140, gains=144, reserved=156, batch_idx=160, cls=168, bboxes=176, n=184, assign_gt=192, assign_score=200, out=208,
-                items=216, status=224, upstream=232, ws=240, ws_bytes=248)
-    assert {name: getattr(D, name).offset for name in fields} == want and C.sizeof(D) == 256
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        return                                               # the hand-computed layout above stands alone
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mgadet.h"', "int main(void) {",
-             '  printf("size %zu\\n", sizeof(mgadet_desc_t));']
-    lines += [f'  printf("{f} %zu\\n", offsetof(mgadet_desc_t, {f}));' for f in fields]
-    lines += ["  return 0;", "}"]
-    (tmp_path / "layout.c").write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.run([cc, "-I", os.path.dirname(HEADER), str(tmp_path / "layout.c"), "-o", exe], check=True)
-    got = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["size"]) == C.sizeof(D)
-    for name, _ in D._fields_:
-        assert int(got[name]) == getattr(D, name).offset, name
-
-
-def a16(n):
-    return (n + 15) & ~15
-
 
 # B = 2, 64 x 64 image, m_cap = 4: 84 anchors, 8 slots, one workgroup of partials
 WS_BYTES = 2 * a16(8 * 4) + 3 * a16(8 * 16 * 4) + 2 * a16(2 * 4) + a16(3 * 4) + a16(4 * 4)

@@ -1,81 +1,13 @@
-"""include/mganms.h without a GPU: the symbols, the struct mirror against the header and the compiler, every refusal before a launch, the size
-query, and install(nms=True) / uninstall() on a stub of the reference's ultralytics.utils.ops."""
+"""include/mganms.h without a GPU: every refusal before a launch, the size query, and install(nms=True) / uninstall() on a stub of the
+reference's ultralytics.utils.ops.  The header against the binding is tests/test_abi_headers.py's."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 import sys
 import types
 
 import pytest
 
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "mganms.h")
-MAIN_HEADER = os.path.join(ROOT, "include", "mgacbam.h")
-P = 0x10000                                                # non-NULL, 16-byte aligned; every call below fails before it is dereferenced
-
-
-def _src():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _fields():
-    body = re.search(r"typedef struct mganms_desc \{(.*?)\}", _src(), re.S).group(1)
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            names = decl.split(",")
-            out.append(re.sub(r"\[.*?\]", "", names[0].split()[-1]).lstrip("*"))
-            out += [re.sub(r"\[.*?\]", "", n).strip().lstrip("*") for n in names[1:]]
-    return out
-
-
-def test_symbols_exist_and_the_main_abi_is_unchanged(built_lib):
-    from mga_yolo_amd import _lib
-    declared = sorted(set(re.findall(r"\b(mganms_\w+)\s*\(", _src())))
-    assert declared == sorted(_lib.NMS_SYMBOLS) == ["mganms_run", "mganms_ws_bytes"]
-    raw = C.CDLL(built_lib)
-    for name in declared:
-        assert hasattr(raw, name)
-    assert _lib.load().mgacbam_abi_version() == 15 == _lib.ABI_VERSION
-    main = re.sub(r"/\*.*?\*/", "", open(MAIN_HEADER).read(), flags=re.S)
-    assert "mganms" not in main
-    assert '#include "mgatargets.h"' in _src() and "MGACBAM_E_ARG =" not in _src()
-    define = {k: int(v) for k, v in re.findall(r"#define (MGANMS_\w+) (\d+)", _src())}
-    assert define == dict(MGANMS_MAX_LEVELS=_lib.NMS_MAX_LEVELS, MGANMS_MULTI_LABEL=_lib.NMS_MULTI_LABEL, MGANMS_AGNOSTIC=_lib.NMS_AGNOSTIC)
-
-
-def test_struct_mirror_matches_the_header_and_the_compiler(tmp_path):
-    from mga_yolo_amd import _lib
-    D = _lib.NmsDesc
-    fields = _fields()
-    assert fields == [f[0] for f in D._fields_]
-    # by hand (LP64): 4 + 1 pointers; 3 x 4 int32; 8 int32; 2 floats; 2 int32; 4 pointers; ws, ws_bytes
-    want = dict(feats=0, pred=32, H=40, W=56, stride=72, n_levels=88, A=92, B=96, nc=100, dtype=104, max_det=108, max_nms=112, flags=116,
-                conf_thres=120, iou_thres=124, cand_cap=128, reserved=132, dets=136, count=144, keep=152, status=160, ws=168, ws_bytes=176)
-    assert {name: getattr(D, name).offset for name in fields} == want and C.sizeof(D) == 184
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        return                                               # the hand-computed layout above stands alone
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mganms.h"', "int main(void) {",
-             '  printf("size %zu\\n", sizeof(mganms_desc_t));']
-    lines += [f'  printf("{f} %zu\\n", offsetof(mganms_desc_t, {f}));' for f in fields]
-    lines += ["  return 0;", "}"]
-    (tmp_path / "layout.c").write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.run([cc, "-I", os.path.dirname(HEADER), str(tmp_path / "layout.c"), "-o", exe], check=True)
-    got = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["size"]) == C.sizeof(D)
-    for name, _ in D._fields_:
-        assert int(got[name]) == getattr(D, name).offset, name
-
-
-def a16(n):
-    return (n + 15) & ~15
-
+from abi_header import FAKE as P, a16
 
 # B = 2, 64 x 64 image: 84 anchors, cand_cap = 84: the counters, the keys, the boxes
 WS_BYTES = a16(2 * 4) + a16(2 * 84 * 8) + a16(2 * 84 * 16)

@@ -1,20 +1,13 @@
 """The static plans of every block in both feature layouts (mga_yolo_amd/plan.py, slice.py), built on the host: the size queries are host
 code and nothing is launched, so bucket layouts, level tables, flags, buffer sizes and refusals are all checked without a GPU.  And the
-mask resample's ABI (include/mgaresample.h): the struct mirror against the C compiler's layout and every argument error, each returned
-before a launch.  PyramidPlan, EcaPyramidPlan and SlicePlan take the new options through ``create`` -- their constructors' argument lists
+mask resample's entry points (include/mgaresample.h): every argument error, each returned before a launch (the header against the binding
+is tests/test_abi_headers.py's).  PyramidPlan, EcaPyramidPlan and SlicePlan take the new options through ``create`` -- their constructors' argument lists
 are pinned by tests/test_gate_abi.py and tests/test_abi_eca_nhwc.py and stay as they are."""
-import ctypes as C
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 import torch
 
-from conftest import ROOT
+from abi_header import FAKE as P
 
-HEADER = os.path.join(ROOT, "include", "mgaresample.h")
 SHAPES = [(4, 64, 16, 16), (4, 128, 8, 8), (4, 256, 4, 4)]
 HIDDEN = [16, 32, 64]
 CL = torch.channels_last
@@ -294,49 +287,6 @@ def test_exports():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the resample ABI
-def _src():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def test_resample_symbols_and_struct_mirror(built_lib, tmp_path):
-    from mga_yolo_amd import _lib
-    declared = sorted(set(re.findall(r"\b(mgaspade_resample_\w+)\s*\(", _src())))
-    assert declared == sorted(_lib.RESAMPLE_SYMBOLS) == ["mgaspade_resample_backward", "mgaspade_resample_forward"]
-    raw = C.CDLL(built_lib)
-    for name in declared:
-        assert hasattr(raw, name)
-    assert not set(_lib.RESAMPLE_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.SPADE_SYMBOLS) | set(_lib.GATE_SYMBOLS))
-    assert '#include "mgaresample.h"' in open(os.path.join(ROOT, "include", "mgaspade.h")).read()       # one include serves MaskSPADE's callers
-    assert _lib.load().mgacbam_abi_version() == 15 == _lib.ABI_VERSION
-    body = re.search(r"typedef struct mgaspade_resample_level \{(.*?)\}", _src(), re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            names = decl.split(",")
-            fields.append(names[0].split()[-1].lstrip("*"))
-            fields += [n.strip().lstrip("*") for n in names[1:]]
-    assert fields == [f[0] for f in _lib.ResampleLevel._fields_] == ["src", "dst", "B", "in_h", "in_w", "out_h", "out_w"]
-    # by hand (LP64): two pointers, five four-byte members, padded to 8
-    want = {name: 8 * i if i < 2 else 16 + 4 * (i - 2) for i, name in enumerate(fields)}
-    assert C.sizeof(_lib.ResampleLevel) == 40
-    assert {name: getattr(_lib.ResampleLevel, name).offset for name in fields} == want
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        return                                               # the hand-computed layout above stands alone
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mgaspade.h"', "int main(void) {",
-             '  printf("size %zu\\n", sizeof(mgaspade_resample_level_t));']
-    lines += [f'  printf("{f} %zu\\n", offsetof(mgaspade_resample_level_t, {f}));' for f in fields]
-    lines += ["  return 0;", "}"]
-    (tmp_path / "layout.c").write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.run([cc, "-I", os.path.dirname(HEADER), str(tmp_path / "layout.c"), "-o", exe], check=True)
-    got = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["size"]) == C.sizeof(_lib.ResampleLevel)
-    for name, _ in _lib.ResampleLevel._fields_:
-        assert int(got[name]) == getattr(_lib.ResampleLevel, name).offset, name
-
-
 def test_fill_resample_sets_every_field(built_lib):
     from mga_yolo_amd import _binding, _lib
     small, big = torch.zeros(3, 1, 7, 5), torch.zeros(3, 1, 16, 12)
@@ -348,7 +298,6 @@ def test_fill_resample_sets_every_field(built_lib):
 
 
 def _rs_level(_lib, **over):
-    P = 0x10000                                            # non-NULL, aligned; every call below fails before it is dereferenced
     L = _lib.ResampleLevel()
     L.src, L.dst, L.B, L.in_h, L.in_w, L.out_h, L.out_w = P, P + 0x1000, 3, 7, 5, 16, 12
     for k, v in over.items():
