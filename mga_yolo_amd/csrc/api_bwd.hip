@@ -6,9 +6,17 @@
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
-// One level of either layout: validated (NULL, parameters, shape, dtype, alignment, capacity), then its kernel arguments.  N.a is the
-// whole result for an NCHW level; a channels-last level (sig.nhwc) also gets its chunk geometry and has no in-launch hand-off.
-static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig) {
+// What the backward groups by (host.cuh: the signature of a family).  gmask: dL/dmask is wanted; vec: along H*W, or along C for a
+// channels-last level.  Whether a level has W1-projection planes is NOT here: the levels of a pyramid stay one launch group whichever qualify.
+struct BwdSig {
+  int dtype, vec, has_mask, k, gmask, nhwc, weight;
+  bool operator==(const BwdSig& o) const {
+    return dtype == o.dtype && vec == o.vec && has_mask == o.has_mask && k == o.k && gmask == o.gmask && nhwc == o.nhwc;
+  }
+};
+// One level of either layout: validated (NULL, parameters, shape, dtype, alignment, capacity), then its kernel arguments; a channels-last
+// level (sig.nhwc) also gets its chunk geometry and has no in-launch hand-off.
+static int backward_args(const mgacbam_bwd_level_t& L, BwdArgs& A, BwdSig& sig) {
   const bool nhwc = (L.flags & MGACBAM_LAYOUT_NHWC) != 0;
   if (!L.x || !L.gy || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "backward: x / gy / ctx / scratch / gx is NULL");
   if (!L.gw1 || !L.gb1 || !L.gw2 || !L.gb2 || !L.gwsa || !L.gbeta) return fail(MGACBAM_E_NULL, "backward: NULL parameter-gradient pointer");
@@ -22,7 +30,6 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
   const ScratchLayout SL = scratch_layout(L.B, L.C, L.H, L.W, L.p.hidden, L.p.k, nhwc, VEC);
   if (int e = check_ctx_capacity("backward", L)) return e;
   if (int e = check_capacity("backward", "scratch", SL.total, L.scratch_bytes)) return e;
-  BwdArgs& A = N.a;
   A.x = L.x; A.mask = L.mask; A.gy = L.gy; A.gx = L.gx; A.gmask = L.gmask;
   A.gw1 = L.gw1; A.gb1 = L.gb1; A.gw2 = L.gw2; A.gb2 = L.gb2; A.gwsa = L.gwsa; A.gbeta = L.gbeta;
   level_setup(L, A);
@@ -33,14 +40,15 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
   A.merged = 0;
   A.make_proj = 0;
   A.vec = VEC;
-  sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, L.gmask != nullptr, 0};
-  if (nhwc) {
-    N.n = nhwc_geo(L.C, L.H, L.W, VEC);
-    N.ncb = (L.C + kNhwcFoldC - 1) / kNhwcFoldC;
-    A.nt = N.n.nchunk;
-    A.ncg = N.ncb;
+  A.n = NhwcGeo{}; A.ncb = 0;
+  sig = BwdSig{};
+  sig.dtype = L.dtype; sig.vec = VEC; sig.has_mask = L.mask != nullptr; sig.k = L.p.k; sig.gmask = L.gmask != nullptr; sig.nhwc = nhwc;
+  if (nhwc) {                                                     // (no projection planes, HAVE_PROJ is ignored: the NHWC apply reads x for dL/dmask)
+    A.n = nhwc_geo(L.C, L.H, L.W, VEC);
+    A.ncb = (L.C + kNhwcFoldC - 1) / kNhwcFoldC;
+    A.nt = A.n.nchunk;
+    A.ncg = A.ncb;
     A.bflag0 = A.cflag0 = A.mbflag0 = A.mcflag0 = A.wflag0 = A.sflag0 = 0;   // (no in-launch hand-off on this path)
-    sig.nhwc = 1;                                                 // (no projection planes, HAVE_PROJ is ignored: the NHWC apply reads x for dL/dmask)
     sig.weight = L.C;
     return 0;
   }
@@ -57,10 +65,9 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
   // other levels share either call.  fp32 only: at config 2 with bf16 / fp16 features the tiles lose more than k_bwd_apply gains
   // (step 0.1382 -> 0.1396 ms and 0.1519 -> 0.1547 ms, three interleaved pairs each), so those levels keep reading x.
   // (W1^T of the level must fit beside the tiles' combine buffer in the LDS every launch may ask for: C up to ~1,700.)
-  // sig.proj follows "gmask wanted" only: the levels of a pyramid stay ONE launch group whichever of them qualify.
+  // The signature follows "gmask wanted" only: the levels of a pyramid stay ONE launch group whichever of them qualify.
   const bool have = (L.flags & MGACBAM_BWD_HAVE_PROJ) != 0;
   const bool make = !have && L.dtype == MGACBAM_F32 && reduce1_smem(A.g, VEC, true) <= 64 * 1024;
-  sig.proj = L.gmask != nullptr;
   A.g.proj_h = (L.gmask && L.p.hidden <= MGACBAM_PROJ_MAX_HIDDEN && (have || make)) ? L.p.hidden : 0;
   A.make_proj = A.g.proj_h > 0 && make;
   // kProjMax < hidden <= kProjWide: the tiles form the planes on the matrix cores (bwd.cuh) into the SCRATCH buffer -- made and used inside
@@ -74,7 +81,7 @@ static int backward_args(const mgacbam_bwd_level_t& L, NhwcBwdArgs& N, Sig& sig)
   return 0;
 }
 
-// The layout-free kernels take the plain level arguments: each launch computes its own grid and LDS size from the group
+// The layout-free kernels: each launch computes its own grid and LDS size from the group
 static size_t reduce2_smem(const Tune& t) { return (64 + static_cast<size_t>(std::max(kPghLds, kBlock / t.pool_tx))) * sizeof(float); }
 static int launch_convT(Group<BwdArgs>& G, int k, hipStream_t st) {
   auto kernel = with_k(k, [](auto kk) { return k_bwd_convT<kk.value>; });
@@ -88,7 +95,9 @@ static int launch_params(Group<BwdArgs>& G, hipStream_t st) {
   return launch_group("k_bwd_params", k_bwd_params, G, [](const BwdArgs& a) { return a.npg; }, [](const BwdArgs& a) { return params_smem(a.g); }, st);
 }
 
-static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
+static int backward_group_nhwc(BwdArgs* lv, int n, const BwdSig& sig, int stages, hipStream_t st);
+static int backward_group(BwdArgs* lv, int n, const BwdSig& sig, int stages, hipStream_t st) {
+  if (sig.nhwc) return backward_group_nhwc(lv, n, sig, stages, st);
   // k_bwd_reduce2 re-reads three planes (g_planes x 2, cidx) per channel group: 4 channels per row halve that share of its loads
   // (config 4: 88 -> 80 us) whenever the grid still fills the chip; k_pool (one mask plane per group) measured slower with 4
   constexpr int kReduce2MaxCpt = 4;
@@ -171,7 +180,7 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
     if (int e = launch_params(G, st)) return e;
   if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask) [+ parameter gradients as role workgroups]
     // A group whose fp32 levels ALL have planes runs the instantiation that cannot read x (fewer registers, one more workgroup per CU);
-    // a level's results are the same bits under either, so this is a property of the launch, not of the level (it is not in Sig: a
+    // a level's results are the same bits under either, so this is a property of the launch, not of the level (it is not in BwdSig: a
     // mixed pyramid stays one launch).  Half-precision groups keep the one instantiation they had.
     bool nox = sig.gmask && sig.dtype == MGACBAM_F32 && sig.vec == 4;
     for (int l = 0; l < n; ++l) nox = nox && lv[l].g.proj_h > 0;
@@ -193,42 +202,38 @@ static int backward_group(BwdArgs* lv, int n, const Sig& sig, int stages, hipStr
 // backward of channels-last levels (nhwc.cuh): k_bwd_reduce1_nhwc, k_bwd_convT, k_bwd_reduce2_nhwc + k_bwd_fold_nhwc, k_bwd_wsa,
 // k_bwd_params, k_bwd_apply_nhwc -- the layout-free kernels are the NCHW path's own
 // ------------------------------------------------------------------------------------------------
-static int backward_group_nhwc(NhwcBwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
-  Group<NhwcBwdArgs> G = make_group(lv, n);
-  Group<BwdArgs> GB;                                            // the layout-free kernels take the plain level arguments
-  GB.n = n;
-  for (int l = 0; l < n; ++l) GB.lv[l] = lv[l].a;
-  auto chunks = [](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); };
+static int backward_group_nhwc(BwdArgs* lv, int n, const BwdSig& sig, int stages, hipStream_t st) {
+  Group<BwdArgs> G = make_group(lv, n);
+  auto chunks = [](const BwdArgs& a) { return xcd_grid(a.g.B, a.n.nchunk); };
   if (stages & MGACBAM_BWD_REDUCE1) {  // 1. chunk partials of A and D, g_pre
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_bwd_reduce1_nhwc<elem_t<decltype(t)>, v.value>; });
     if (int e = launch_group("k_bwd_reduce1_nhwc", kernel, G, chunks,
-                             [&](const NhwcBwdArgs& a) { return nhwc_reduce1_smem(a.a.g, sig.vec); }, st)) return e;
+                             [&](const BwdArgs& a) { return nhwc_reduce1_smem(a.g, sig.vec); }, st)) return e;
   }
   if (stages & MGACBAM_BWD_CONVT)  // 2. transposed conv
-    if (int e = launch_convT(GB, sig.k, st)) return e;
+    if (int e = launch_convT(G, sig.k, st)) return e;
   if (stages & MGACBAM_BWD_REDUCE2) {  // 3. chunk partials of the g_planes term, then their fold: g_z, D, hidden-gradient partials
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_bwd_reduce2_nhwc<elem_t<decltype(t)>, v.value>; });
-    if (int e = launch_group("k_bwd_reduce2_nhwc", kernel, G, chunks, [](const NhwcBwdArgs& a) { return nhwc_reduce2_smem(a.a.g); }, st)) return e;
-    if (int e = launch_group("k_bwd_fold_nhwc", k_bwd_fold_nhwc, G, [](const NhwcBwdArgs& a) { return a.a.g.B * a.ncb; }, 0, st)) return e;
+    if (int e = launch_group("k_bwd_reduce2_nhwc", kernel, G, chunks, [](const BwdArgs& a) { return nhwc_reduce2_smem(a.g); }, st)) return e;
+    if (int e = launch_group("k_bwd_fold_nhwc", k_bwd_fold_nhwc, G, [](const BwdArgs& a) { return a.g.B * a.ncb; }, 0, st)) return e;
   }
   if (stages & MGACBAM_BWD_WSA)  // 4. dWsa tile partials
-    if (int e = launch_wsa(GB, sig.k, st)) return e;
+    if (int e = launch_wsa(G, sig.k, st)) return e;
   if (stages & MGACBAM_BWD_PARAMGRAD)  // 5. every parameter gradient
-    if (int e = launch_params(GB, st)) return e;
+    if (int e = launch_params(G, st)) return e;
   if (stages & MGACBAM_BWD_APPLY) {  // 6. gx (+ gmask)
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_bool(sig.gmask, [&](auto gm) { return k_bwd_apply_nhwc<elem_t<decltype(t)>, v.value, gm.value>; }); });
-    if (int e = launch_group("k_bwd_apply_nhwc", kernel, G, [](const NhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); },
-                             [](const NhwcBwdArgs& a) { return nhwc_bwd_apply_smem(a.a.g); }, st)) return e;
+    if (int e = launch_group("k_bwd_apply_nhwc", kernel, G, [](const BwdArgs& a) { return xcd_grid(a.g.B, a.n.ntile); },
+                             [](const BwdArgs& a) { return nhwc_bwd_apply_smem(a.g); }, st)) return e;
   }
   return 0;
 }
 
 extern "C" int mgacbam_backward_stages(const mgacbam_bwd_level_t* levels, int n_levels, int stages, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return run_levels<BwdArgs, NhwcBwdArgs>(levels, n_levels, backward_args,
-      [&](BwdArgs* g, int m, const Sig& s) { return backward_group(g, m, s, stages, st); },
-      [&](NhwcBwdArgs* g, int m, const Sig& s) { return backward_group_nhwc(g, m, s, stages, st); });
+  return run_levels<BwdArgs, BwdSig>(levels, n_levels, true, backward_args,
+      [&](BwdArgs* g, int m, const BwdSig& s) { return backward_group(g, m, s, stages, st); });
 }
 extern "C" int mgacbam_backward(const mgacbam_bwd_level_t* levels, int n_levels, void* stream) {
   return mgacbam_backward_stages(levels, n_levels, MGACBAM_BWD_ALL, stream);

@@ -88,12 +88,18 @@ static int eca_check_params(const mgacbam_eca_params_t& p) {
   if (p.k < 1 || p.k > 15 || (p.k & 1) == 0) return fail(MGACBAM_E_SHAPE, "eca: conv1d kernel k=%d must be odd and in 1..15", p.k);
   return 0;
 }
-// One level of either direction (Level: mgacbam_eca_fwd_level_t / mgacbam_eca_bwd_level_t, N: EcaNhwcFwdArgs / EcaNhwcBwdArgs) and
-// layout: validated (NULL, parameters, shape, dtype, flags, alignment, capacity), then its kernel arguments.  N.a is the whole
-// result for an NCHW level; a channels-last level (sig.nhwc) also gets its chunk geometry and the partials' tail of ctx / scratch.
-template <typename Level, typename N>
-static int eca_level(const char* what, const Level& L, N& out, Sig& sig) {
-  constexpr bool bwd = std::is_same_v<N, EcaNhwcBwdArgs>;
+// What MaskECA groups by (host.cuh: the signature of a family).  gmask: dL/dmask is wanted (the backward; 0 in the forward); vec: along
+// H*W, or along C for a channels-last level
+struct EcaSig {
+  int dtype, vec, has_mask, gmask, nhwc, weight;
+  bool operator==(const EcaSig& o) const { return dtype == o.dtype && vec == o.vec && has_mask == o.has_mask && gmask == o.gmask && nhwc == o.nhwc; }
+};
+// One level of either direction (Level: mgacbam_eca_fwd_level_t / mgacbam_eca_bwd_level_t, Args: EcaFwdArgs / EcaBwdArgs) and layout:
+// validated (NULL, parameters, shape, dtype, flags, alignment, capacity), then its kernel arguments; a channels-last level (sig.nhwc)
+// also gets its chunk geometry and the partials' tail of ctx / scratch.
+template <typename Level, typename Args>
+static int eca_level(const char* what, const Level& L, Args& A, EcaSig& sig) {
+  constexpr bool bwd = std::is_same_v<Args, EcaBwdArgs>;
   if constexpr (bwd) {
     if (!L.x || !L.gy || !L.ctx || !L.scratch || !L.gx || !L.gw || !L.gbeta) return fail(MGACBAM_E_NULL, "%s: NULL pointer", what);
     if (L.gmask && !L.mask) return fail(MGACBAM_E_NULL, "%s: gmask requested but mask is NULL", what);
@@ -107,7 +113,6 @@ static int eca_level(const char* what, const Level& L, N& out, Sig& sig) {
   const bool nhwc = (L.flags & MGACBAM_LAYOUT_NHWC) != 0;
   const int VEC = level_vec(nhwc, L.C, L.H, L.W, L.dtype);
   const size_t need = VEC * elem_size(L.dtype);
-  auto& A = out.a;
   if constexpr (bwd) {
     if (!aligned_to(L.x, need) || !aligned_to(L.gy, need) || !aligned_to(L.gx, need) || !aligned_to(L.ctx, 16) ||
         !aligned_to(L.scratch, 16) || (L.gmask && !aligned_to(L.gmask, 16)))
@@ -126,14 +131,15 @@ static int eca_level(const char* what, const Level& L, N& out, Sig& sig) {
   A.w1d = L.p.w; A.beta = L.p.beta;
   A.g = eca_geo(L.B, L.C, L.H, L.W, L.p);
   A.t = choose_tune(L.B, L.C, L.H, L.W, 7);
-  sig = Sig{L.dtype, VEC, L.mask != nullptr, 0, 0, 0};
+  A.n = NhwcGeo{}; A.part = nullptr;
+  sig = EcaSig{};
+  sig.dtype = L.dtype; sig.vec = VEC; sig.has_mask = L.mask != nullptr; sig.nhwc = nhwc;
   if constexpr (bwd) { sig.gmask = L.gmask != nullptr; A.nt = nhwc ? 0 : chan_tiles(A.t, L.H, L.W, VEC); }
-  sig.nhwc = nhwc;
   sig.weight = nhwc ? L.C : L.C * A.t.chan_tx;
   if (nhwc) {
-    out.n = nhwc_geo(L.C, L.H, L.W, VEC);
-    if constexpr (bwd) out.part = at(L.scratch, eca_gg_bytes(L.B, L.C));
-    else out.part = at(L.ctx, eca_ctx_layout(L.B, L.C, L.H, L.W).total);
+    A.n = nhwc_geo(L.C, L.H, L.W, VEC);
+    if constexpr (bwd) A.part = at(L.scratch, eca_gg_bytes(L.B, L.C));
+    else A.part = at(L.ctx, eca_ctx_layout(L.B, L.C, L.H, L.W).total);
   }
   return 0;
 }
@@ -143,7 +149,9 @@ static size_t eca_bwd_nhwc_smem(const Geo& g) {
   return (((static_cast<size_t>(g.C) + 1) & ~static_cast<size_t>(1)) + 2 * static_cast<size_t>(g.C)) * sizeof(float);
 }
 
-static int eca_forward_group(EcaFwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
+static int eca_forward_group_nhwc(EcaFwdArgs* lv, int n, const EcaSig& sig, hipStream_t st);
+static int eca_forward_group(EcaFwdArgs* lv, int n, const EcaSig& sig, hipStream_t st) {
+  if (sig.nhwc) return eca_forward_group_nhwc(lv, n, sig, st);
   const int cpt = group_cpt(lv, n);
   for (int l = 0; l < n; ++l) lv[l].t.pool_cpt = cpt;
   Group<EcaFwdArgs> G = make_group(lv, n);
@@ -157,27 +165,28 @@ static int eca_forward_group(EcaFwdArgs* lv, int n, const Sig& sig, hipStream_t 
 }
 
 // channels-last levels: k_eca_pool_nhwc, k_eca_fin, k_eca_apply_nhwc
-static int eca_forward_group_nhwc(EcaNhwcFwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<EcaNhwcFwdArgs> G = make_group(lv, n);
+static int eca_forward_group_nhwc(EcaFwdArgs* lv, int n, const EcaSig& sig, hipStream_t st) {
+  Group<EcaFwdArgs> G = make_group(lv, n);
   auto pool = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
     return with_bool(sig.has_mask, [&](auto m) { return k_eca_pool_nhwc<elem_t<decltype(t)>, v.value, m.value>; }); });
-  if (int e = launch_group("k_eca_pool_nhwc", pool, G, [](const EcaNhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }, 0, st)) return e;
+  if (int e = launch_group("k_eca_pool_nhwc", pool, G, [](const EcaFwdArgs& a) { return xcd_grid(a.g.B, a.n.nchunk); }, 0, st)) return e;
   auto fin = with_bool(sig.has_mask, [](auto m) { return k_eca_fin<m.value>; });
-  if (int e = launch_group("k_eca_fin", fin, G, [](const EcaNhwcFwdArgs& a) { return nhwc_fold_blocks(a.a.g); }, 0, st)) return e;
+  if (int e = launch_group("k_eca_fin", fin, G, [](const EcaFwdArgs& a) { return nhwc_fold_blocks(a.g); }, 0, st)) return e;
   auto apply = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_eca_apply_nhwc<elem_t<decltype(t)>, v.value>; });
-  return launch_group("k_eca_apply_nhwc", apply, G, [](const EcaNhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); },
-                      [](const EcaNhwcFwdArgs& a) { return eca_apply_nhwc_smem(a.a.g); }, st);
+  return launch_group("k_eca_apply_nhwc", apply, G, [](const EcaFwdArgs& a) { return xcd_grid(a.g.B, a.n.ntile); },
+                      [](const EcaFwdArgs& a) { return eca_apply_nhwc_smem(a.g); }, st);
 }
 
 extern "C" int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_levels, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return run_levels<EcaFwdArgs, EcaNhwcFwdArgs>(levels, n_levels,
-      [](const mgacbam_eca_fwd_level_t& L, EcaNhwcFwdArgs& N, Sig& s) { return eca_level("eca forward", L, N, s); },
-      [&](EcaFwdArgs* g, int m, const Sig& s) { return eca_forward_group(g, m, s, st); },
-      [&](EcaNhwcFwdArgs* g, int m, const Sig& s) { return eca_forward_group_nhwc(g, m, s, st); });
+  return run_levels<EcaFwdArgs, EcaSig>(levels, n_levels, true,
+      [](const mgacbam_eca_fwd_level_t& L, EcaFwdArgs& A, EcaSig& s) { return eca_level("eca forward", L, A, s); },
+      [&](EcaFwdArgs* g, int m, const EcaSig& s) { return eca_forward_group(g, m, s, st); });
 }
 
-static int eca_backward_group(EcaBwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
+static int eca_backward_group_nhwc(EcaBwdArgs* lv, int n, const EcaSig& sig, hipStream_t st);
+static int eca_backward_group(EcaBwdArgs* lv, int n, const EcaSig& sig, hipStream_t st) {
+  if (sig.nhwc) return eca_backward_group_nhwc(lv, n, sig, st);
   const int cpt = group_cpt(lv, n);
   for (int l = 0; l < n; ++l) lv[l].t.pool_cpt = cpt;
   Group<EcaBwdArgs> G = make_group(lv, n);
@@ -191,23 +200,22 @@ static int eca_backward_group(EcaBwdArgs* lv, int n, const Sig& sig, hipStream_t
 }
 
 // channels-last levels: k_eca_reduce_nhwc, k_eca_fold, k_eca_bwd_nhwc (+ the layout-free role workgroups)
-static int eca_backward_group_nhwc(EcaNhwcBwdArgs* lv, int n, const Sig& sig, hipStream_t st) {
-  Group<EcaNhwcBwdArgs> G = make_group(lv, n);
+static int eca_backward_group_nhwc(EcaBwdArgs* lv, int n, const EcaSig& sig, hipStream_t st) {
+  Group<EcaBwdArgs> G = make_group(lv, n);
   auto reduce = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_eca_reduce_nhwc<elem_t<decltype(t)>, v.value>; });
-  if (int e = launch_group("k_eca_reduce_nhwc", reduce, G, [](const EcaNhwcBwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); }, 0, st)) return e;
-  if (int e = launch_group("k_eca_fold", k_eca_fold, G, [](const EcaNhwcBwdArgs& a) { return nhwc_fold_blocks(a.a.g); }, 0, st)) return e;
+  if (int e = launch_group("k_eca_reduce_nhwc", reduce, G, [](const EcaBwdArgs& a) { return xcd_grid(a.g.B, a.n.nchunk); }, 0, st)) return e;
+  if (int e = launch_group("k_eca_fold", k_eca_fold, G, [](const EcaBwdArgs& a) { return nhwc_fold_blocks(a.g); }, 0, st)) return e;
   auto bwd = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
     return with_bool(sig.gmask, [&](auto gm) { return k_eca_bwd_nhwc<elem_t<decltype(t)>, v.value, gm.value>; }); });
-  return launch_group("k_eca_bwd_nhwc", bwd, G, [](const EcaNhwcBwdArgs& a) { return kEcaRoles + xcd_grid(a.a.g.B, a.n.ntile); },
-                      [](const EcaNhwcBwdArgs& a) { return eca_bwd_nhwc_smem(a.a.g); }, st);
+  return launch_group("k_eca_bwd_nhwc", bwd, G, [](const EcaBwdArgs& a) { return kEcaRoles + xcd_grid(a.g.B, a.n.ntile); },
+                      [](const EcaBwdArgs& a) { return eca_bwd_nhwc_smem(a.g); }, st);
 }
 
 extern "C" int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n_levels, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return run_levels<EcaBwdArgs, EcaNhwcBwdArgs>(levels, n_levels,
-      [](const mgacbam_eca_bwd_level_t& L, EcaNhwcBwdArgs& N, Sig& s) { return eca_level("eca backward", L, N, s); },
-      [&](EcaBwdArgs* g, int m, const Sig& s) { return eca_backward_group(g, m, s, st); },
-      [&](EcaNhwcBwdArgs* g, int m, const Sig& s) { return eca_backward_group_nhwc(g, m, s, st); });
+  return run_levels<EcaBwdArgs, EcaSig>(levels, n_levels, true,
+      [](const mgacbam_eca_bwd_level_t& L, EcaBwdArgs& A, EcaSig& s) { return eca_level("eca backward", L, A, s); },
+      [&](EcaBwdArgs* g, int m, const EcaSig& s) { return eca_backward_group(g, m, s, st); });
 }
 
 // ------------------------------------------------------------------------------------------------

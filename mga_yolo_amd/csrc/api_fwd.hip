@@ -6,9 +6,19 @@
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-// One level of either layout: validated (NULL, parameters, shape, dtype, alignment, capacity), then its kernel arguments.  N.a is the
-// whole result for an NCHW level; a channels-last level (sig.nhwc) also gets its chunk geometry and the ws buffer.
-static int forward_args(const mgacbam_fwd_level_t& L, NhwcFwdArgs& N, Sig& sig) {
+// What the forward groups by (host.cuh: the signature of a family).  gvec: elements per lane of k_gate for this level -- a function of
+// the LEVEL alone (dtype, shape, k, knobs), never of the levels it happens to be called with: the hand-off flags in ctx.sync count calls per
+// TILE, so a ctx must see the same tiling in every call whatever the group composition (levels of different gvec go to different launches).
+// proj: W1-projection planes are saved (NCHW levels); vec: along H*W, or along C for a channels-last level
+struct FwdSig {
+  int dtype, vec, has_mask, k, proj, gvec, nhwc, weight;
+  bool operator==(const FwdSig& o) const {
+    return dtype == o.dtype && vec == o.vec && has_mask == o.has_mask && k == o.k && proj == o.proj && gvec == o.gvec && nhwc == o.nhwc;
+  }
+};
+// One level of either layout: validated (NULL, parameters, shape, dtype, alignment, capacity), then its kernel arguments; a channels-last
+// level (sig.nhwc) also gets its chunk geometry and the ws buffer.
+static int forward_args(const mgacbam_fwd_level_t& L, FwdArgs& A, FwdSig& sig) {
   const bool nhwc = (L.flags & MGACBAM_LAYOUT_NHWC) != 0;
   if (!L.x || !L.y || !L.ctx || (nhwc && !L.ws))
     return fail(MGACBAM_E_NULL, nhwc ? "forward (NHWC): x / y / ctx / ws is NULL" : "forward: x / y / ctx is NULL");
@@ -21,17 +31,17 @@ static int forward_args(const mgacbam_fwd_level_t& L, NhwcFwdArgs& N, Sig& sig) 
                 nhwc ? " / ws" : "", nhwc ? 4 : VEC * 4);
   if (int e = check_ctx_capacity("forward", L)) return e;
   if (nhwc) if (int e = check_capacity("forward", "ws", nhwc_ws_bytes(L.B, L.C, L.H, L.W, VEC), L.ws_bytes)) return e;
-  FwdArgs& A = N.a;
   A.x = L.x; A.mask = L.mask; A.y = L.y; A.fused = 0;
   level_setup(L, A);
   A.fault = knobs().fault;
-  sig = Sig{L.dtype, VEC, L.mask != nullptr, L.p.k, 0, 0};
+  A.n = NhwcGeo{}; A.ws = nullptr;
+  sig = FwdSig{};
+  sig.dtype = L.dtype; sig.vec = VEC; sig.has_mask = L.mask != nullptr; sig.k = L.p.k; sig.nhwc = nhwc;
   if (nhwc) {
-    N.n = nhwc_geo(L.C, L.H, L.W, VEC);
-    N.ws = static_cast<float*>(L.ws);
-    const int rows = std::min((N.n.ch - 1) / L.W + 2, L.H);     // image rows a chunk of ch pixels touches
+    A.n = nhwc_geo(L.C, L.H, L.W, VEC);
+    A.ws = static_cast<float*>(L.ws);
+    const int rows = std::min((A.n.ch - 1) / L.W + 2, L.H);     // image rows a chunk of ch pixels touches
     A.t.apply_rows = rows + L.p.k - 1;
-    sig.nhwc = 1;
     sig.weight = L.C;
     return 0;
   }
@@ -49,12 +59,14 @@ static int forward_args(const mgacbam_fwd_level_t& L, NhwcFwdArgs& N, Sig& sig) 
   return 0;
 }
 
-// k_mlp is layout-free: one workgroup per sample, the plain level arguments
+// k_mlp is layout-free: one workgroup per sample
 static int launch_mlp(Group<FwdArgs>& G, hipStream_t st) {
   return launch_group("k_mlp", k_mlp, G, [](const FwdArgs& a) { return a.g.B; }, [](const FwdArgs& a) { return mlp_smem(a.g); }, st);
 }
 
-static int forward_group(FwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
+static int forward_group_nhwc(FwdArgs* lv, int n, const FwdSig& sig, int stages, hipStream_t st);
+static int forward_group(FwdArgs* lv, int n, const FwdSig& sig, int stages, hipStream_t st) {
+  if (sig.nhwc) return forward_group_nhwc(lv, n, sig, stages, st);
   const int pool_cpt = group_cpt(lv, n);
   for (int l = 0; l < n; ++l) lv[l].t.pool_cpt = pool_cpt;
   Group<FwdArgs> G = make_group(lv, n);
@@ -113,39 +125,35 @@ static int forward_group(FwdArgs* lv, int n, const Sig& sig, int stages, hipStre
 // ------------------------------------------------------------------------------------------------
 // forward of channels-last levels (nhwc.cuh): k_pool_nhwc, k_pool_fin (+ shared MLP), k_chan_nhwc, k_apply_nhwc
 // ------------------------------------------------------------------------------------------------
-static int forward_group_nhwc(NhwcFwdArgs* lv, int n, const Sig& sig, int stages, hipStream_t st) {
-  Group<NhwcFwdArgs> G = make_group(lv, n);
+static int forward_group_nhwc(FwdArgs* lv, int n, const FwdSig& sig, int stages, hipStream_t st) {
+  Group<FwdArgs> G = make_group(lv, n);
   if (stages & MGACBAM_FWD_POOL) {  // 1. chunk partials of the pooling, 2. their fold, 3. the shared MLP -> ca
     auto pool = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_bool(sig.has_mask, [&](auto m) { return k_pool_nhwc<elem_t<decltype(t)>, v.value, m.value>; }); });
-    if (int e = launch_group("k_pool_nhwc", pool, G, [](const NhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.nchunk); },
-                             [](const NhwcFwdArgs& a) { return nhwc_pool_smem(a.a.g); }, st)) return e;
+    if (int e = launch_group("k_pool_nhwc", pool, G, [](const FwdArgs& a) { return xcd_grid(a.g.B, a.n.nchunk); },
+                             [](const FwdArgs& a) { return nhwc_pool_smem(a.g); }, st)) return e;
     auto fin = with_bool(sig.has_mask, [](auto m) { return k_pool_fin<m.value>; });
-    if (int e = launch_group("k_pool_fin", fin, G, [](const NhwcFwdArgs& a) { return nhwc_fold_blocks(a.a.g); }, 0, st)) return e;
-    Group<FwdArgs> GM;
-    GM.n = n;
-    for (int l = 0; l < n; ++l) GM.lv[l] = lv[l].a;
-    if (int e = launch_mlp(GM, st)) return e;
+    if (int e = launch_group("k_pool_fin", fin, G, [](const FwdArgs& a) { return nhwc_fold_blocks(a.g); }, 0, st)) return e;
+    if (int e = launch_mlp(G, st)) return e;
   }
-  auto tiles = [](const NhwcFwdArgs& a) { return xcd_grid(a.a.g.B, a.n.ntile); };
+  auto tiles = [](const FwdArgs& a) { return xcd_grid(a.g.B, a.n.ntile); };
   if (stages & MGACBAM_FWD_CHAN) {  // 3. channel max / mean planes
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_bool(sig.has_mask, [&](auto m) { return k_chan_nhwc<elem_t<decltype(t)>, v.value, m.value>; }); });
-    if (int e = launch_group("k_chan_nhwc", kernel, G, tiles, [](const NhwcFwdArgs& a) { return nhwc_chan_smem(a.a.g); }, st)) return e;
+    if (int e = launch_group("k_chan_nhwc", kernel, G, tiles, [](const FwdArgs& a) { return nhwc_chan_smem(a.g); }, st)) return e;
   }
   if (stages & MGACBAM_FWD_APPLY) {  // 4. k x k conv + spatial gate (prologue), y
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_k(sig.k, [&](auto k) { return k_apply_nhwc<elem_t<decltype(t)>, v.value, k.value>; }); });
-    if (int e = launch_group("k_apply_nhwc", kernel, G, tiles, [](const NhwcFwdArgs& a) { return nhwc_apply_smem(a.a.g, a.a.t, a.n); }, st)) return e;
+    if (int e = launch_group("k_apply_nhwc", kernel, G, tiles, [](const FwdArgs& a) { return nhwc_apply_smem(a.g, a.t, a.n); }, st)) return e;
   }
   return 0;
 }
 
 extern "C" int mgacbam_forward_stages(const mgacbam_fwd_level_t* levels, int n_levels, int stages, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return run_levels<FwdArgs, NhwcFwdArgs>(levels, n_levels, forward_args,
-      [&](FwdArgs* g, int m, const Sig& s) { return forward_group(g, m, s, stages, st); },
-      [&](NhwcFwdArgs* g, int m, const Sig& s) { return forward_group_nhwc(g, m, s, stages, st); });
+  return run_levels<FwdArgs, FwdSig>(levels, n_levels, true, forward_args,
+      [&](FwdArgs* g, int m, const FwdSig& s) { return forward_group(g, m, s, stages, st); });
 }
 extern "C" int mgacbam_forward(const mgacbam_fwd_level_t* levels, int n_levels, void* stream) {
   return mgacbam_forward_stages(levels, n_levels, MGACBAM_FWD_ALL, stream);

@@ -29,6 +29,16 @@ static void head_waves(int mtiles, int mtw, int K, int& pw, int& kw) {
   kw = K >= 128 ? rest : 1;
   pw = rest / kw;
 }
+// pixel shares of the LDS-staged dW1 forms (k_head_bwd_gw2, k_head_gw_nhwc): a share = every nshare-th 64-pixel chunk.
+// kHeadGwDiv: 64-pixel chunks per workgroup (pixel shares = chunks / this).  5: the YOLOv8n pyramid's 1,008 workgroups are one resident round
+// at the kernel's 108 VGPRs (4 per CU): slice 0.3886 -> 0.3852 ms; 3, 6, 8 and config 3: no difference
+// (measured: 2-4 chunks per workgroup and 512-2048 shares all within 1 %; 6+ chunks, one resident round: +12 %)
+constexpr int kHeadGwDiv = 5;
+static int head_staged_nshare(int B, int HW, long long per_share) {
+  const long long chunks64 = static_cast<long long>(B) * ((HW + kHeadGwPx - 1) / kHeadGwPx);
+  const long long cap = std::max(1ll, std::min(512ll, (4ll << 20) / per_share));
+  return static_cast<int>(std::max(1ll, std::min(cap, chunks64 / kHeadGwDiv)));
+}
 static HeadTiling head_tiling(int B, int C, int H, int W, int hidden, bool nhwc = false) {
   HeadTiling t;
   const int HW = H * W;
@@ -57,14 +67,7 @@ static HeadTiling head_tiling(int B, int C, int H, int W, int hidden, bool nhwc 
   ns = std::min(ns, (chunks + 7) / 8);
   t.nshare = static_cast<int>(std::max(32ll, std::min(256ll, ns)));
   t.gw2 = (t.vec == 4 && t.hidp <= 64) ? 1 : 0;                     // k_head_bwd_gw2 (operands through LDS): a share = every nshare-th 64-pixel chunk
-  if (t.gw2) {
-    // 64-pixel chunks per workgroup (pixel shares = chunks / this).  5: the YOLOv8n pyramid's 1,008 workgroups are one resident round
-    // at the kernel's 108 VGPRs (4 per CU): slice 0.3886 -> 0.3852 ms; 3, 6, 8 and config 3: no difference
-    constexpr int kHeadGwDiv = 5;
-    const long long chunks64 = static_cast<long long>(B) * ((HW + kHeadGwPx - 1) / kHeadGwPx);
-    const long long cap = std::max(1ll, std::min(512ll, (4ll << 20) / per_share));
-    t.nshare = static_cast<int>(std::max(1ll, std::min(cap, chunks64 / kHeadGwDiv)));   // (measured: 2-4 chunks per workgroup and 512-2048 shares all within 1 %; 6+ chunks, one resident round: +12 %)
-  }
+  if (t.gw2) t.nshare = head_staged_nshare(B, HW, per_share);
   if (nhwc) {
     // MGAHEAD_LAYOUT_NHWC (head_nhwc.cuh): 64 pixels per wave along N, no K split; dW1 always takes the LDS-staged form, shares as k_head_bwd_gw2's
     auto waves_px = [](int mtiles, int mtw) { int mw = std::min(4, (mtiles + mtw - 1) / mtw); if (mw == 3) mw = 4; return 4 / mw; };
@@ -74,10 +77,7 @@ static HeadTiling head_tiling(int B, int C, int H, int W, int hidden, bool nhwc 
     t.nwg = B * t.tps;
     t.gx_tile_px = waves_px(t.cp / 16, t.gx_mtw) * kHeadNhwcPx;
     t.gx_tps = (HW + t.gx_tile_px - 1) / t.gx_tile_px;
-    constexpr int kHeadGwDiv = 5;
-    const long long chunks64 = static_cast<long long>(B) * ((HW + kHeadGwPx - 1) / kHeadGwPx);
-    const long long cap = std::max(1ll, std::min(512ll, (4ll << 20) / per_share));
-    t.nshare = static_cast<int>(std::max(1ll, std::min(cap, chunks64 / kHeadGwDiv)));
+    t.nshare = head_staged_nshare(B, HW, per_share);
     t.gw2 = 0;
   }
   return t;
@@ -86,26 +86,24 @@ struct HeadCtxLayout { size_t z, mean, rstd, par, part, total; };
 static HeadCtxLayout head_ctx_layout(int B, int C, int H, int W, int hidden, bool nhwc = false) {
   const HeadTiling t = head_tiling(B, C, H, W, hidden, nhwc);
   HeadCtxLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
-  L.z = take(static_cast<size_t>(B) * hidden * H * W);
-  L.mean = take(t.hidp); L.rstd = take(t.hidp);
-  L.par = take(static_cast<size_t>(t.hidp) * kHeadPar);
-  L.part = take(static_cast<size_t>(t.nwg) * 2 * t.hidp);
-  L.total = o;
+  Carver cv;
+  L.z = cv.take(static_cast<size_t>(B) * hidden * H * W);
+  L.mean = cv.take(t.hidp); L.rstd = cv.take(t.hidp);
+  L.par = cv.take(static_cast<size_t>(t.hidp) * kHeadPar);
+  L.part = cv.take(static_cast<size_t>(t.nwg) * 2 * t.hidp);
+  L.total = cv.total;
   return L;
 }
 struct HeadScratchLayout { size_t ga, part1, kst, gwpart, total; };
 static HeadScratchLayout head_scratch_layout(int B, int C, int H, int W, int hidden, bool nhwc = false) {
   const HeadTiling t = head_tiling(B, C, H, W, hidden, nhwc);
   HeadScratchLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o = align16(o + n * 4); return at; };
-  L.ga = take(static_cast<size_t>(B) * hidden * H * W);
-  L.part1 = take(static_cast<size_t>(t.nwg1) * t.hidp * kHeadNStat);
-  L.kst = take(5 * static_cast<size_t>(t.hidp));
-  L.gwpart = take(static_cast<size_t>(t.ncb) * t.nshare * t.hidp * kHeadCB);
-  L.total = o;
+  Carver cv;
+  L.ga = cv.take(static_cast<size_t>(B) * hidden * H * W);
+  L.part1 = cv.take(static_cast<size_t>(t.nwg1) * t.hidp * kHeadNStat);
+  L.kst = cv.take(5 * static_cast<size_t>(t.hidp));
+  L.gwpart = cv.take(static_cast<size_t>(t.ncb) * t.nshare * t.hidp * kHeadCB);
+  L.total = cv.total;
   return L;
 }
 extern "C" size_t mgahead_ctx_bytes(int B, int C, int H, int W, int hidden) {
@@ -124,7 +122,14 @@ extern "C" size_t mgahead_bwd_scratch_bytes_flags(int B, int C, int H, int W, in
   if (head_check_shape(B, C, H, W, hidden)) return 0;
   return head_scratch_layout(B, C, H, W, hidden, (flags & MGAHEAD_LAYOUT_NHWC) != 0).total;
 }
-static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, int dtype, bool nhwc, void* ctx, HeadArgs& A, Sig& sig) {
+// What the mask head groups by (host.cuh: the signature of a family).  vec: along H*W in either layout; lf32: logits / g_logits are fp32
+// whatever dtype is (MGAHEAD_LOGITS_F32); nhwc: MGAHEAD_LAYOUT_NHWC level, kernels of head_nhwc.cuh; cvec: their channels per lane access
+// (4 when C % 4 == 0, else 1; 0 for an NCHW level)
+struct HeadSig {
+  int dtype, vec, lf32, nhwc, cvec, weight;
+  bool operator==(const HeadSig& o) const { return dtype == o.dtype && vec == o.vec && lf32 == o.lf32 && nhwc == o.nhwc && cvec == o.cvec; }
+};
+static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, int dtype, bool nhwc, void* ctx, HeadArgs& A, HeadSig& sig) {
   if (!P.w1 || !P.bn_weight || !P.bn_bias || !P.running_mean || !P.running_var || !P.wh || !P.bh)
     return fail(MGACBAM_E_NULL, "mask head: NULL parameter pointer");
   if (int e = head_check_shape(B, C, H, W, P.hidden)) return e;
@@ -141,8 +146,8 @@ static int head_common(const mgahead_params_t& P, int B, int C, int H, int W, in
   A.gx_tile_px = t.gx_tile_px; A.gx_tiles_per_sample = t.gx_tps; A.fw_kw = t.fw_kw; A.gx_kw = t.gx_kw; A.fw_mtw = t.fw_mtw; A.gx_mtw = t.gx_mtw;
   A.trace = knobs().trace; A.trace_base = 0;
   A.nwg_out = t.nwg_out; A.out_ppt = t.out_ppt; A.out_px = t.out_px; A.out_per = t.out_per; A.nwg1 = t.nwg1; A.act_ppt = t.act_ppt; A.act_hl_max = t.act_hl; A.ncb = t.ncb; A.nshare = t.nshare; A.gw2 = t.gw2;
-  sig = Sig{dtype, t.vec, 0, 0, 0, 0};
-  if (nhwc) { sig.nhwc = 1; sig.cvec = C % 4 == 0 ? 4 : 1; }
+  sig = HeadSig{};
+  sig.dtype = dtype; sig.vec = t.vec; sig.nhwc = nhwc; sig.cvec = !nhwc ? 0 : C % 4 == 0 ? 4 : 1;
   sig.weight = C;
   return 0;
 }
@@ -152,7 +157,7 @@ static int max_hidp(const HeadArgs* lv, int n) {
   for (int l = 0; l < n; ++l) m = std::max(m, lv[l].g.hidp);
   return m;
 }
-static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t st) {
+static int head_forward_group(HeadArgs* lv, int n, const HeadSig& sig, hipStream_t st) {
   Group<HeadArgs> G = make_group(lv, n);
   {
     // one launch per accumulator template (two tiles per wave: hidden <= 128, i.e. every level of the n/s models; four beyond): each level
@@ -193,7 +198,7 @@ static int head_forward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t s
     return with_int<4, 1>(sig.vec, [&](auto v) { return k_head_out<elem_t<decltype(t)>, v.value>; }); });
   return launch_group("k_head_out", out, G, [](const HeadArgs& a) { return a.nwg_out; }, 0, st);
 }
-static int head_forward_level(const mgahead_fwd_level_t& L, HeadArgs& A, Sig& sig) {
+static int head_forward_level(const mgahead_fwd_level_t& L, HeadArgs& A, HeadSig& sig) {
   if (!L.x || !L.logits || !L.ctx) return fail(MGACBAM_E_NULL, "mask head forward: x / logits / ctx is NULL");
   const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
   if (int e = head_common(L.p, L.B, L.C, L.H, L.W, L.dtype, nhwc, L.ctx, A, sig)) return e;
@@ -206,10 +211,10 @@ static int head_forward_level(const mgahead_fwd_level_t& L, HeadArgs& A, Sig& si
 }
 extern "C" int mgahead_forward(const mgahead_fwd_level_t* levels, int n_levels, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return run_levels<HeadArgs>(levels, n_levels, head_forward_level,
-                              [&](HeadArgs* g, int m, const Sig& s) { return head_forward_group(g, m, s, st); });
+  return run_levels<HeadArgs, HeadSig>(levels, n_levels, false, head_forward_level,
+                              [&](HeadArgs* g, int m, const HeadSig& s) { return head_forward_group(g, m, s, st); });
 }
-static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t st) {
+static int head_backward_group(HeadArgs* lv, int n, const HeadSig& sig, hipStream_t st) {
   int hl = 0;
   for (int l = 0; l < n; ++l) hl = std::max(hl, lv[l].act_hl_max);
   for (int l = 0; l < n; ++l) lv[l].act_hl_max = hl;            // the reduction scratch sits behind the launch's longest run
@@ -257,7 +262,7 @@ static int head_backward_group(HeadArgs* lv, int n, const Sig& sig, hipStream_t 
   return launch_group("k_head_bwd_gwf", k_head_bwd_gwf, G,
                       [](const HeadArgs& a) { return (a.g.hid * a.g.C + kHeadGwfOut - 1) / kHeadGwfOut; }, 0, st);
 }
-static int head_backward_level(const mgahead_bwd_level_t& L, HeadArgs& A, Sig& sig) {
+static int head_backward_level(const mgahead_bwd_level_t& L, HeadArgs& A, HeadSig& sig) {
   if (!L.x || !L.g_logits || !L.ctx || !L.scratch || !L.gx) return fail(MGACBAM_E_NULL, "mask head backward: x / g_logits / ctx / scratch / gx is NULL");
   if (!L.gw1 || !L.gbn_weight || !L.gbn_bias || !L.gwh || !L.gbh) return fail(MGACBAM_E_NULL, "mask head backward: NULL parameter-gradient pointer");
   const bool nhwc = (L.flags & MGAHEAD_LAYOUT_NHWC) != 0;
@@ -278,6 +283,6 @@ static int head_backward_level(const mgahead_bwd_level_t& L, HeadArgs& A, Sig& s
 }
 extern "C" int mgahead_backward(const mgahead_bwd_level_t* levels, int n_levels, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return run_levels<HeadArgs>(levels, n_levels, head_backward_level,
-                              [&](HeadArgs* g, int m, const Sig& s) { return head_backward_group(g, m, s, st); });
+  return run_levels<HeadArgs, HeadSig>(levels, n_levels, false, head_backward_level,
+                              [&](HeadArgs* g, int m, const HeadSig& s) { return head_backward_group(g, m, s, st); });
 }

@@ -87,8 +87,14 @@ static void sp_allow_lds(K kernel, size_t smem) {
   if (hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) == hipSuccess) have = smem;
 }
 
+// What MaskSPADE groups by (host.cuh: the signature of a family).  keep: the forward keeps gamma in the ctx (0 in the backward);
+// gmask: dL/dmask is wanted (the backward; 0 in the forward)
+struct SpadeSig {
+  int dtype, has_mask, nhwc, keep, gmask, weight;
+  bool operator==(const SpadeSig& o) const { return dtype == o.dtype && has_mask == o.has_mask && nhwc == o.nhwc && keep == o.keep && gmask == o.gmask; }
+};
 // everything a level is checked for before the first launch, and its kernel arguments
-static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, SpadeArgs& A, Sig& sig) {
+static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, SpadeArgs& A, SpadeSig& sig) {
   if (!L.x || !L.ctx) return fail(MGACBAM_E_NULL, "%s: x / ctx is NULL", what);
   if (!bwd && !L.y) return fail(MGACBAM_E_NULL, "%s: y is NULL", what);
   if (bwd && (!L.gy || !L.gx || !L.scratch)) return fail(MGACBAM_E_NULL, "%s: gy / gx / scratch is NULL", what);
@@ -134,9 +140,10 @@ static int sp_level(const char* what, const mgaspade_level_t& L, bool bwd, Spade
   while (cblk > 64 && static_cast<long long>(L.B) * t.tiles * ((L.C + cblk - 1) / cblk) < 512) cblk = (cblk / 2 + 15) & ~15;
   A.cblk = cblk; A.ncb = (L.C + cblk - 1) / cblk;
   A.nchunk = SL.nchunk; A.tpc = SL.tpc;
-  sig = Sig{L.dtype, 0, L.mask != nullptr, 0, bwd ? (L.gmask != nullptr) : (gamma_kept ? 1 : 0), 0};
+  sig = SpadeSig{};
+  sig.dtype = L.dtype; sig.has_mask = L.mask != nullptr; sig.nhwc = L.flags == MGASPADE_LAYOUT_NHWC;
+  if (bwd) sig.gmask = L.gmask != nullptr; else sig.keep = gamma_kept;
   sig.weight = L.C;
-  sig.nhwc = L.flags == MGASPADE_LAYOUT_NHWC;
   return 0;
 }
 static int sp_ew_blocks(const SpadeArgs& a) {
@@ -147,12 +154,12 @@ static int sp_plane_blocks(const SpadeArgs& a) { return (a.B * a.C + 3) / 4; }
 
 static int sp_pack_blocks(const SpadeArgs& a) { return (2 * a.C * a.hid * 9 + kBlock - 1) / kBlock; }
 
-// Channels-last levels (Sig::nhwc: launch groups of their own) run the same launches with the kernels' NHWC instantiations; tiling, grids
+// Channels-last levels (SpadeSig::nhwc: launch groups of their own) run the same launches with the kernels' NHWC instantiations; tiling, grids
 // of the tile kernels, ctx and scratch are the NCHW ones.  Their reductions (spade_nhwc.cuh) take 16 channels of a sample per workgroup.
 static int sp_nhwc_plane_blocks(const SpadeArgs& a) { return a.B * (a.C / kSpNhCB); }
 static int sp_nhwc_bn_blocks(const SpadeArgs& a) { return a.bn && a.train ? (a.C / kSpNhCB) * (kBlock / kWave) : 0; }
 static int sp_nhwc_bn_fin_blocks(const SpadeArgs& a) { return a.bn && a.train ? (a.C + kBlock - 1) / kBlock : 0; }
-static int sp_stats_nhwc(Group<SpadeArgs>& G, const Sig& sig, hipStream_t st) {
+static int sp_stats_nhwc(Group<SpadeArgs>& G, const SpadeSig& sig, hipStream_t st) {
   auto stats = with_elem(sig.dtype, [](auto t) { return k_spade_stats_nhwc<elem_t<decltype(t)>>; });
   auto stat_blocks = [](const SpadeArgs& a) { return !a.bn ? sp_nhwc_plane_blocks(a) : a.train ? sp_nhwc_bn_blocks(a) : (a.B * a.C + kBlock - 1) / kBlock; };
   if (int e = launch_group("k_spade_stats_nhwc", stats, G, stat_blocks, 0, st)) return e;
@@ -168,11 +175,11 @@ static int sp_stats_nhwc(Group<SpadeArgs>& G, const Sig& sig, hipStream_t st) {
 }
 // T x layout: f(Ty<T>, std::bool_constant<NHWC>)
 template <typename F>
-static auto with_elem_layout(const Sig& sig, F f) {
+static auto with_elem_layout(const SpadeSig& sig, F f) {
   return with_elem(sig.dtype, [&](auto t) { return with_bool(sig.nhwc, [&](auto n) { return f(t, n); }); });
 }
 
-static int sp_forward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
+static int sp_forward_group(SpadeArgs* lv, int n, const SpadeSig& sig, hipStream_t st) {
   Group<SpadeArgs> G = make_group(lv, n);
   if (sig.nhwc) {
     if (int e = sp_stats_nhwc(G, sig, st)) return e;
@@ -187,12 +194,12 @@ static int sp_forward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st
   }
   if (int e = launch_group("k_spade_pack", k_spade_pack, G, sp_pack_blocks, 0, st)) return e;
   auto fwd = with_elem_layout(sig, [&](auto t, auto l) {
-    return with_bool(sig.gmask, [](auto keep) { return k_spade_fwd<elem_t<decltype(t)>, keep.value, decltype(l)::value>; }); });
+    return with_bool(sig.keep, [](auto keep) { return k_spade_fwd<elem_t<decltype(t)>, keep.value, decltype(l)::value>; }); });
   sp_allow_lds(fwd, group_smem(G, sp_fwd_smem));
   return launch_group("k_spade_fwd", fwd, G, [](const SpadeArgs& a) { return a.B * a.tiles * a.ncb; }, sp_fwd_smem, st);
 }
 
-static int sp_backward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t st) {
+static int sp_backward_group(SpadeArgs* lv, int n, const SpadeSig& sig, hipStream_t st) {
   Group<SpadeArgs> G = make_group(lv, n);
   if (sig.nhwc) {
     auto reduce = with_elem(sig.dtype, [](auto t) { return k_spade_bwd_reduce_nhwc<elem_t<decltype(t)>>; });
@@ -221,8 +228,8 @@ static int sp_backward_group(SpadeArgs* lv, int n, const Sig& sig, hipStream_t s
 
 static int sp_run(const char* what, const mgaspade_level_t* levels, int n_levels, void* stream, bool bwd) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return run_levels<SpadeArgs>(levels, n_levels, [&](const mgaspade_level_t& L, SpadeArgs& A, Sig& s) { return sp_level(what, L, bwd, A, s); },
-      [&](SpadeArgs* g, int m, const Sig& s) { return bwd ? sp_backward_group(g, m, s, st) : sp_forward_group(g, m, s, st); });
+  return run_levels<SpadeArgs, SpadeSig>(levels, n_levels, false, [&](const mgaspade_level_t& L, SpadeArgs& A, SpadeSig& s) { return sp_level(what, L, bwd, A, s); },
+      [&](SpadeArgs* g, int m, const SpadeSig& s) { return bwd ? sp_backward_group(g, m, s, st) : sp_forward_group(g, m, s, st); });
 }
 extern "C" int mgaspade_forward(const mgaspade_level_t* levels, int n_levels, void* stream) {
   return sp_run("mgaspade_forward", levels, n_levels, stream, false);

@@ -46,6 +46,19 @@ struct Tune {
   int gate_span;   // k_gate: tiles a k x k window reaches on either side (a tile waits for workgroups up to 8*span ids away)
 };
 
+// channels-last levels (nhwc.cuh): chunk geometry, a function of the level alone (host: nhwc_geo)
+struct NhwcGeo {
+  int cs, lcs;     // lanes per pixel (power of two <= 64) and its log2
+  int ng;          // channel groups of VEC channels: ceil(C / VEC)
+  int ch;          // pixels per TILE = (256 / cs) * pixels per thread (8; 4 with 8-element lanes)
+  int ntile;       // tiles per sample: the per-pixel kernels (k_chan_nhwc, k_apply_nhwc, k_bwd_apply_nhwc) take one tile per workgroup
+  int rp;          // tiles per CHUNK: the per-channel kernels (k_pool_nhwc, k_bwd_reduce1_nhwc, k_bwd_reduce2_nhwc) sweep rp tiles per
+                   // workgroup and write one partial per chunk, so a sample has at most kNhwcMaxChunks partials to fold
+  int nchunk;      // chunks per sample = ceil(ntile / rp)
+};
+constexpr int kNhwcMaxChunks = 64;
+constexpr int kNhwcFoldC = 64;   // channels per workgroup of the NHWC fold kernels (x 4 chunk groups = 256 threads)
+
 struct FwdArgs {
   const void* x; const float* mask; void* y;
   CtxPtrs c; ParamPtrs p; Geo g; Tune t;
@@ -54,6 +67,9 @@ struct FwdArgs {
   unsigned spin_limit;   // bound of every hand-off spin (knob MGACBAM_SPIN_LIMIT, default 2^20 ~ 1 s)
   int fault;       // fault injection for tests (knob MGACBAM_FAULT=1): sample 0's role workgroup never publishes ca
   long long* trace;   // MGACBAM_TRACE builds only: per-workgroup phase timestamps (tools/trace_gate.py), else nullptr
+  // channels-last levels (MGACBAM_LAYOUT_NHWC: the kernels of nhwc_fwd.cuh) only
+  NhwcGeo n;
+  float* ws;       // (B, nchunk, 4*C + 4) pool partials: [sum x*s][sum x][max][arg-max pixel (int)][sum s, 3 pad]
 };
 
 // transient backward buffers (device pointers into the caller's scratch buffer)
@@ -92,20 +108,10 @@ struct BwdArgs {
   unsigned spin_limit;
   int vec;      // elements per lane of the tile kernels (TP = chan_tx * vec pixels per tile)
   long long* trace;   // MGACBAM_TRACE builds only (tools/trace_gate.py), else nullptr
+  // channels-last levels (MGACBAM_LAYOUT_NHWC: the kernels of nhwc_bwd.cuh) only; their A_part is (B, nchunk, 3, C) = [A][D][sum x*wgt]
+  NhwcGeo n;
+  int ncb;         // channel blocks of kNhwcFoldC (k_bwd_fold_nhwc): s.pgh is (B, ncb, hidden)
 };
-
-// channels-last levels (nhwc.cuh): chunk geometry, a function of the level alone (host: nhwc_geo)
-struct NhwcGeo {
-  int cs, lcs;     // lanes per pixel (power of two <= 64) and its log2
-  int ng;          // channel groups of VEC channels: ceil(C / VEC)
-  int ch;          // pixels per TILE = (256 / cs) * pixels per thread (8; 4 with 8-element lanes)
-  int ntile;       // tiles per sample: the per-pixel kernels (k_chan_nhwc, k_apply_nhwc, k_bwd_apply_nhwc) take one tile per workgroup
-  int rp;          // tiles per CHUNK: the per-channel kernels (k_pool_nhwc, k_bwd_reduce1_nhwc, k_bwd_reduce2_nhwc) sweep rp tiles per
-                   // workgroup and write one partial per chunk, so a sample has at most kNhwcMaxChunks partials to fold
-  int nchunk;      // chunks per sample = ceil(ntile / rp)
-};
-constexpr int kNhwcMaxChunks = 64;
-constexpr int kNhwcFoldC = 64;   // channels per workgroup of the NHWC fold kernels (x 4 chunk groups = 256 threads)
 
 static inline size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
 
@@ -121,5 +127,8 @@ struct Group {
   int start[kGroupMax + 1];
   Args lv[kGroupMax];
 };
+// a launch's arguments may take this many bytes; every group, and every struct that holds one, is checked where it is defined
+constexpr size_t kKernargMax = 4096;
+static_assert(sizeof(Group<FwdArgs>) <= kKernargMax && sizeof(Group<BwdArgs>) <= kKernargMax, "a group is one launch's arguments");
 
 }  // namespace mgacbam

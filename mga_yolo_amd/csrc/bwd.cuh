@@ -684,6 +684,7 @@ struct R12Group {
   Group<BwdArgs> g;
   int seg[4][kGroupMax + 1];     // seg[p][l]: first workgroup id of level l in phase p; seg[p][n]: end of phase p
 };
+static_assert(sizeof(R12Group) <= kKernargMax, "a group is one launch's arguments");
 template <typename T, int VEC, int CPT, bool PROJ>   // PROJ: some level's tiles make the W1-projection planes (bwd_reduce1_body)
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PROJ ? 2 : 1))) void k_bwd_r12(const R12Group R) {
   extern __shared__ __align__(16) float smem[];

@@ -25,13 +25,20 @@ struct EcaScratch { float* gg; };     // (B,C) sum_hw gy*x
 struct EcaFwdArgs {
   const void* x; const float* mask; void* y;
   EcaCtx c; const float* w1d; const float* beta; Geo g; Tune t;
+  // channels-last levels (MGACBAM_LAYOUT_NHWC: the kernels of eca_nhwc.cuh) only
+  NhwcGeo n;
+  float* part;     // (B, nchunk, 2*C + 4) pool partials: [sum x][sum x*s][sum s, 3 pad] -- the tail of the level's ctx
 };
 struct EcaBwdArgs {
   const void* x; const float* mask; const void* gy; void* gx; float* gmask;
   float* gw; float* gbeta;
   EcaCtx c; const float* w1d; const float* beta; EcaScratch s; Geo g; Tune t;
   int nt;
+  // channels-last levels only
+  NhwcGeo n;
+  float* part;     // (B, nchunk, C) partials of gg -- the tail of the level's scratch
 };
+static_assert(sizeof(Group<EcaFwdArgs>) <= kKernargMax && sizeof(Group<EcaBwdArgs>) <= kKernargMax, "a group is one launch's arguments");
 
 // ---------------------------------------------------------------------------------------------
 // k_eca_pool: masked average pooling with GAP fallback                             masked_eca.py:139-165

@@ -19,16 +19,6 @@
 
 namespace mgacbam {
 
-struct EcaNhwcFwdArgs {
-  EcaFwdArgs a;
-  NhwcGeo n;
-  float* part;     // (B, nchunk, 2*C + 4) pool partials: [sum x][sum x*s][sum s, 3 pad] -- the tail of the level's ctx
-};
-struct EcaNhwcBwdArgs {
-  EcaBwdArgs a;
-  NhwcGeo n;
-  float* part;     // (B, nchunk, C) partials of gg -- the tail of the level's scratch
-};
 __host__ __device__ inline size_t eca_nhwc_part_stride(int C) { return 2 * static_cast<size_t>(C) + 4; }
 
 // rows of one pass -> channel sums: thread t < CS*VEC owns channel j*CS*VEC + t and adds the PR rows in row order
@@ -55,36 +45,35 @@ __device__ __forceinline__ void eca_rows_to_channels(float (&acc)[N][VEC], float
 //   LDS: [2 x 256*VEC row sums]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, bool HAS_MASK>
-__global__ __launch_bounds__(kBlock) void k_eca_pool_nhwc(const Group<EcaNhwcFwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_eca_pool_nhwc(const Group<EcaFwdArgs> G) {
   constexpr int NS = HAS_MASK ? 2 : 1;                                    // [sum x][sum x*s]
   __shared__ __align__(16) float red[NS * kBlock * VEC];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const EcaNhwcFwdArgs& N = G.lv[l];
-  const EcaFwdArgs& A = N.a;
+  const EcaFwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.nchunk, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.nchunk, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
   const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
   const float* mb = HAS_MASK ? A.mask + static_cast<size_t>(b) * g.HW : nullptr;
   float* splane = A.c.splane + static_cast<size_t>(b) * g.HW;
-  float* part = N.part + (static_cast<size_t>(b) * N.n.nchunk + chunk) * eca_nhwc_part_stride(g.C);
-  const int nj = (N.n.ng + CS - 1) / CS;
-  const int t0 = chunk * N.n.rp, t_end = min(t0 + N.n.rp, N.n.ntile);
+  float* part = A.part + (static_cast<size_t>(b) * A.n.nchunk + chunk) * eca_nhwc_part_stride(g.C);
+  const int nj = (A.n.ng + CS - 1) / CS;
+  const int t0 = chunk * A.n.rp, t_end = min(t0 + A.n.rp, A.n.ntile);
   float ssum = 0.f;
   for (int j = 0; j < nj; ++j) {
     const int cgi = lane + j * CS;
-    const bool okc = cgi < N.n.ng;
-    const int c0 = min(cgi, N.n.ng - 1) * VEC;
+    const bool okc = cgi < A.n.ng;
+    const int c0 = min(cgi, A.n.ng - 1) * VEC;
     float acc[NS][VEC];
 #pragma unroll
     for (int q = 0; q < NS; ++q)
 #pragma unroll
       for (int e = 0; e < VEC; ++e) acc[q][e] = 0.f;
     for (int tile = t0; tile < t_end; ++tile) {
-      const int p0 = tile * N.n.ch;
+      const int p0 = tile * A.n.ch;
       float s[kNhwcNpx];
       bool live[kNhwcNpx];
       float xv[kNhwcNpx][VEC];
@@ -128,18 +117,17 @@ __global__ __launch_bounds__(kBlock) void k_eca_pool_nhwc(const Group<EcaNhwcFwd
 // chunks, the 4 results are added in wave order.  Writes the statistics exactly as k_eca_pool defines them.
 // ---------------------------------------------------------------------------------------------
 template <bool HAS_MASK>
-__global__ __launch_bounds__(kBlock) void k_eca_fin(const Group<EcaNhwcFwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_eca_fin(const Group<EcaFwdArgs> G) {
   __shared__ float s_part[2][kBlock];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const EcaNhwcFwdArgs& N = G.lv[l];
-  const EcaFwdArgs& A = N.a;
+  const EcaFwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   const int ncb = (g.C + kNhwcFoldC - 1) / kNhwcFoldC;
   const int b = local / ncb, cb = local - b * ncb;
-  const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, nch = N.n.nchunk;
+  const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, nch = A.n.nchunk;
   const size_t stride = eca_nhwc_part_stride(g.C);
-  const float* wb = N.part + static_cast<size_t>(b) * nch * stride;
+  const float* wb = A.part + static_cast<size_t>(b) * nch * stride;
   float S = 0.f;                                                          // every workgroup of the sample forms S the same way
   if (HAS_MASK) {
     for (int q = lane; q < nch; q += 64) S += wb[q * stride + 2 * g.C];
@@ -178,18 +166,17 @@ __global__ __launch_bounds__(kBlock) void k_eca_fin(const Group<EcaNhwcFwdArgs> 
 //   LDS: [C gate]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_eca_apply_nhwc(const Group<EcaNhwcFwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_eca_apply_nhwc(const Group<EcaFwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const EcaNhwcFwdArgs& N = G.lv[l];
-  const EcaFwdArgs& A = N.a;
+  const EcaFwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, tile;
-  if (!xcd_sample_part(local, g.B, N.n.ntile, b, tile)) return;
+  if (!xcd_sample_part(local, g.B, A.n.ntile, b, tile)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
-  const int p0 = tile * N.n.ch;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
+  const int p0 = tile * A.n.ch;
   const size_t sb = static_cast<size_t>(b) * g.HW * g.C;
   const T* xb = static_cast<const T*>(A.x) + sb;
   T* yb = static_cast<T*>(A.y) + sb;
@@ -209,10 +196,10 @@ __global__ __launch_bounds__(kBlock) void k_eca_apply_nhwc(const Group<EcaNhwcFw
     okp[k] = p < g.HW;
     pix[k] = okp[k] ? p : 0;
   }
-  const int nj = (N.n.ng + CS - 1) / CS;
+  const int nj = (A.n.ng + CS - 1) / CS;
   for (int j = 0; j < nj; ++j) {
     const int cgi = lane + j * CS;
-    if (cgi >= N.n.ng) break;
+    if (cgi >= A.n.ng) break;
     const int c0 = cgi * VEC;
     float gv[VEC];
 #pragma unroll
@@ -235,32 +222,31 @@ __global__ __launch_bounds__(kBlock) void k_eca_apply_nhwc(const Group<EcaNhwcFw
 //   LDS: [256*VEC row sums]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_eca_reduce_nhwc(const Group<EcaNhwcBwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_eca_reduce_nhwc(const Group<EcaBwdArgs> G) {
   __shared__ __align__(16) float red[kBlock * VEC];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const EcaNhwcBwdArgs& N = G.lv[l];
-  const EcaBwdArgs& A = N.a;
+  const EcaBwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.nchunk, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.nchunk, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
   const size_t sb = static_cast<size_t>(b) * g.HW * g.C;
   const T* xb = static_cast<const T*>(A.x) + sb;
   const T* gb = static_cast<const T*>(A.gy) + sb;
-  float* part = N.part + (static_cast<size_t>(b) * N.n.nchunk + chunk) * g.C;
-  const int nj = (N.n.ng + CS - 1) / CS;
-  const int t0 = chunk * N.n.rp, t_end = min(t0 + N.n.rp, N.n.ntile);
+  float* part = A.part + (static_cast<size_t>(b) * A.n.nchunk + chunk) * g.C;
+  const int nj = (A.n.ng + CS - 1) / CS;
+  const int t0 = chunk * A.n.rp, t_end = min(t0 + A.n.rp, A.n.ntile);
   for (int j = 0; j < nj; ++j) {
     const int cgi = lane + j * CS;
-    const bool okc = cgi < N.n.ng;
-    const int c0 = min(cgi, N.n.ng - 1) * VEC;
+    const bool okc = cgi < A.n.ng;
+    const int c0 = min(cgi, A.n.ng - 1) * VEC;
     float acc[1][VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[0][e] = 0.f;
     for (int tile = t0; tile < t_end; ++tile) {
-      const int p0 = tile * N.n.ch;
+      const int p0 = tile * A.n.ch;
       float xv[kNhwcNpx][VEC], gv[kNhwcNpx][VEC];
       bool live[kNhwcNpx];
 #pragma unroll
@@ -284,21 +270,20 @@ __global__ __launch_bounds__(kBlock) void k_eca_reduce_nhwc(const Group<EcaNhwcB
 // ---------------------------------------------------------------------------------------------
 // k_eca_fold: workgroup = (sample, block of kNhwcFoldC channels): gg[b,c] = chunk partials folded as k_eca_fin folds its own
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_eca_fold(const Group<EcaNhwcBwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_eca_fold(const Group<EcaBwdArgs> G) {
   __shared__ float s_part[kBlock];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const EcaNhwcBwdArgs& N = G.lv[l];
-  const EcaBwdArgs& A = N.a;
+  const EcaBwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   const int ncb = (g.C + kNhwcFoldC - 1) / kNhwcFoldC;
   const int b = local / ncb, cb = local - b * ncb;
   const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6;
   const int c = cb * kNhwcFoldC + lane, cc = min(c, g.C - 1);
-  const float* pb = N.part + static_cast<size_t>(b) * N.n.nchunk * g.C + cc;
+  const float* pb = A.part + static_cast<size_t>(b) * A.n.nchunk * g.C + cc;
   float s = 0.f;
 #pragma unroll 4
-  for (int q = grp; q < N.n.nchunk; q += 4) s += pb[static_cast<size_t>(q) * g.C];
+  for (int q = grp; q < A.n.nchunk; q += 4) s += pb[static_cast<size_t>(q) * g.C];
   s_part[tid] = s;
   __syncthreads();
   if (grp != 0 || c >= g.C) return;
@@ -313,21 +298,20 @@ __global__ __launch_bounds__(kBlock) void k_eca_fold(const Group<EcaNhwcBwdArgs>
 //   LDS: [C gy1][2C q]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, bool GMASK>
-__global__ __launch_bounds__(kBlock) void k_eca_bwd_nhwc(const Group<EcaNhwcBwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_eca_bwd_nhwc(const Group<EcaBwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   __shared__ float red[8];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const EcaNhwcBwdArgs& N = G.lv[l];
-  const EcaBwdArgs& A = N.a;
+  const EcaBwdArgs& A = G.lv[l];
   if (local < kEcaRoles) { eca_params_body(A, local, red); return; }     // 16 role ids keep the streaming ids XCD-aligned
   local -= kEcaRoles;
   const Geo& g = A.g;
   int b, tile;
-  if (!xcd_sample_part(local, g.B, N.n.ntile, b, tile)) return;
+  if (!xcd_sample_part(local, g.B, A.n.ntile, b, tile)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
-  const int p0 = tile * N.n.ch;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
+  const int p0 = tile * A.n.ch;
   const float a = softplusf_(*A.beta);
   const float Nf = static_cast<float>(g.HW);
   const bool has_mask = A.mask != nullptr;
@@ -375,10 +359,10 @@ __global__ __launch_bounds__(kBlock) void k_eca_bwd_nhwc(const Group<EcaNhwcBwdA
     wA[kk] = has_mask ? (use * sv[kk] / den + (1.f - use) / Nf) : 1.f / Nf;
     accp[kk] = 0.f;
   }
-  const int nj = (N.n.ng + CS - 1) / CS;
+  const int nj = (A.n.ng + CS - 1) / CS;
   for (int j = 0; j < nj; ++j) {
     const int cgi = lane + j * CS;
-    if (cgi >= N.n.ng) break;
+    if (cgi >= A.n.ng) break;
     const int c0 = cgi * VEC;
     float2 q[VEC];
 #pragma unroll

@@ -880,6 +880,7 @@ struct GateGroup {
   int nrole;                     // role workgroups = sum of the levels' batch sizes; tile workgroup ids follow
   int rstart[kGroupMax + 1];     // level l owns role ids [rstart[l], rstart[l+1])
 };
+static_assert(sizeof(GateGroup) <= kKernargMax, "a group is one launch's arguments");
 
 
 template <typename T, int VEC, int K>

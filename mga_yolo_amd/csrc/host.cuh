@@ -406,7 +406,7 @@ template <typename F>
 static auto with_elem_vec(int dtype, int vec, F f) {
   return with_elem(dtype, [&](auto t) { return with_int<4, 1>(vec, [&](auto v) { return f(t, v); }); });
 }
-// T x VEC of k_gate (Sig::gvec) and of the NHWC kernels (nhwc_vec): fp16 / bf16 also 8 (float x 8 is never formed)
+// T x VEC of k_gate (FwdSig::gvec) and of the NHWC kernels (nhwc_vec): fp16 / bf16 also 8 (float x 8 is never formed)
 template <typename F>
 static auto with_elem_vec8(int dtype, int vec, F f) {
   return with_elem(dtype, [&](auto t) {
@@ -459,22 +459,14 @@ static void level_setup(const Level& L, Args& A) {
   A.trace = kn.trace; A.spin_limit = kn.spin_limit;
 }
 
-// Levels that share every compile-time property of the kernels (element type, vector width, mask / no mask,
-// conv size, dL/dmask wanted) are launched together: one grid per stage, the levels' grids concatenated.
-struct Sig {
-  int dtype, vec, has_mask, k, gmask, proj;
-  int lf32 = 0;   // mask head only: logits / g_logits are fp32 whatever dtype is (MGAHEAD_LOGITS_F32)
-  int nhwc = 0;   // MGACBAM_LAYOUT_NHWC level: kernels of nhwc.cuh (vec = its lanes' width along C); MGAHEAD_LAYOUT_NHWC level: head_nhwc.cuh
-  int cvec = 0;   // mask head NHWC levels only: channels per lane access of head_nhwc.cuh (4 when C % 4 == 0, else 1); vec stays the H*W one
-  int gvec = 0;   // forward only: elements per lane of k_gate for this level -- a function of the LEVEL alone (dtype, shape, k, knobs), never of
-                  // the levels it happens to be called with: the hand-off flags in ctx.sync count calls per TILE, so a ctx must see the same
-                  // tiling in every call whatever the group composition (levels of different gvec go to different launches)
-  int weight = 0; // not part of the signature: ~ how long a workgroup of the level runs (C x channels per thread of the tile kernels where the
-                  // family has them, else C), set by the *_args functions; for_each_group launches the levels of a group longest first
-  bool operator==(const Sig& o) const {
-    return dtype == o.dtype && vec == o.vec && has_mask == o.has_mask && k == o.k && gmask == o.gmask && proj == o.proj && gvec == o.gvec && lf32 == o.lf32 && nhwc == o.nhwc && cvec == o.cvec;
-  }
-};
+// Levels that share every compile-time property of the kernels (element type, vector width, mask / no mask, conv size, dL/dmask wanted,
+// layout) are launched together: one grid per stage, the levels' grids concatenated.  Each family defines the signature it groups by next to
+// its level function -- only the fields its kernel selection reads, set by name -- and the frame below asks three things of it:
+//   operator==   over every field but weight.  The hand-off counters in ctx.sync count launches per TILE, so which levels share a launch is
+//                part of correctness: a field belongs here only if it is a function of the LEVEL alone, never of the call's other levels
+//   int weight   not compared: ~ how long a workgroup of the level runs (C x channels per thread of the tile kernels where the family has
+//                them, else C); for_each_group launches the levels of a group longest first
+//   int nhwc     the level is channels-last: a launch group is single-layout, and its group function picks the layout's kernels
 
 // channels per thread for the row-sweep kernels, uniform over a group: 2 when that still gives the chip >= 6 workgroups
 // per CU, else 1 (4 is instantiated and reachable through MGACBAM_POOL_CPT, but measured slower at every benchmark shape:
@@ -581,10 +573,12 @@ static int launch_group(const char* what, void (*kernel)(Group<Args>), Group<Arg
   return launch(what, kernel, grid, kBlock, group_smem(G, smem_of), st, G);
 }
 
-// partition the levels into launch groups (same signature, at most kGroupMax levels) and run `run` on each
-template <typename Args, typename Run>
-static int for_each_group(Args* args, const Sig* sigs, int n, Run run) {
-  bool done[MGACBAM_MAX_LEVELS] = {false};
+// partition the levels into launch groups (same signature, at most kGroupMax levels) and run `run` on each, in order of first
+// appearance; layout 0 / 1: only the NCHW / channels-last levels, -1: all
+template <typename Args, typename Sig, typename Run>
+static int for_each_group(Args* args, const Sig* sigs, int n, int layout, Run run) {
+  bool done[MGACBAM_MAX_LEVELS];
+  for (int l = 0; l < n; ++l) done[l] = layout >= 0 && sigs[l].nhwc != layout;
   for (int l = 0; l < n; ++l) {
     if (done[l]) continue;
     int idx[kGroupMax], m = 0;
@@ -598,32 +592,20 @@ static int for_each_group(Args* args, const Sig* sigs, int n, Run run) {
   return 0;
 }
 
-// The frame of every grouped entry point: `level` checks one level and builds its arguments and signature
-// (int level(const Level&, NArgs&, Sig&)); EVERY level is checked before anything is launched; then the NCHW levels' groups run
-// (`run`), then the channels-last ones' (`nrun`), each in for_each_group's order.  With two runners the NCHW kernels take the `.a` member
-// of the channels-last argument block (Args); a family with one runner (nrun = nullptr) sends every level to it as it is.
-template <typename Args, typename NArgs = Args, typename Level, typename LevelFn, typename Run, typename NRun = std::nullptr_t>
-static int run_levels(const Level* levels, int n_levels, LevelFn level, Run run, NRun nrun = nullptr) {
-  constexpr bool two = !std::is_same_v<NRun, std::nullptr_t>;
+// The frame of every grouped entry point: `level` checks one level and builds its argument block and signature
+// (int level(const Level&, Args&, Sig&)); EVERY level is checked before anything is launched; then `run(Args*, n, const Sig&)` gets each
+// launch group, in for_each_group's order -- nchw_first: the groups of the NCHW levels, then those of the channels-last ones (MaskCBAM,
+// MaskECA), else all in order of first appearance (mask head, MaskSPADE).
+template <typename Args, typename Sig, typename Level, typename LevelFn, typename Run>
+static int run_levels(const Level* levels, int n_levels, bool nchw_first, LevelFn level, Run run) {
   if (!levels) return fail(MGACBAM_E_NULL, "levels is NULL");
   if (n_levels < 1 || n_levels > MGACBAM_MAX_LEVELS) return fail(MGACBAM_E_LEVELS, "n_levels=%d", n_levels);
   Args args[MGACBAM_MAX_LEVELS];
-  NArgs nargs[two ? MGACBAM_MAX_LEVELS : 1];
-  Sig sigs[MGACBAM_MAX_LEVELS], nsigs[MGACBAM_MAX_LEVELS];
-  int nc = 0, nn = 0;                                             // NCHW levels, NHWC levels
-  for (int l = 0; l < n_levels; ++l) {
-    if constexpr (two) {
-      NArgs N;
-      Sig s;
-      if (int e = level(levels[l], N, s)) return e;
-      if (s.nhwc) { nargs[nn] = N; nsigs[nn++] = s; } else { args[nc] = N.a; sigs[nc++] = s; }
-    } else {
-      if (int e = level(levels[l], args[nc], sigs[nc])) return e;
-      ++nc;
-    }
-  }
-  if (nc) if (int e = for_each_group(args, sigs, nc, run)) return e;
-  if constexpr (two) if (nn) if (int e = for_each_group(nargs, nsigs, nn, nrun)) return e;
+  Sig sigs[MGACBAM_MAX_LEVELS];
+  for (int l = 0; l < n_levels; ++l)
+    if (int e = level(levels[l], args[l], sigs[l])) return e;
+  for (int layout = nchw_first ? 0 : -1; layout <= (nchw_first ? 1 : -1); ++layout)
+    if (int e = for_each_group(args, sigs, n_levels, layout, run)) return e;
   g_err[0] = 0;
   return 0;
 }

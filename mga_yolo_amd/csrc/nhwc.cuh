@@ -1,5 +1,5 @@
-// Channels-last (NHWC) forms of the MaskCBAM kernels that stream x, gy, y or gx (MGACBAM_LAYOUT_NHWC levels): the shared argument
-// blocks and helpers; the kernels are in nhwc_fwd.cuh and nhwc_bwd.cuh.
+// Channels-last (NHWC) forms of the MaskCBAM kernels that stream x, gy, y or gx (MGACBAM_LAYOUT_NHWC levels): the shared
+// helpers (the argument blocks are FwdArgs / BwdArgs, args.cuh); the kernels are in nhwc_fwd.cuh and nhwc_bwd.cuh.
 //
 // In NHWC the two reductions of the block swap roles: the per-pixel reductions over C (max_c / mean_c of u, sum_c ca*gy*x, the
 // dL/dmask sum) run along contiguous memory, and the per-(b,c) reductions over H*W become sums across pixels.  Every kernel below uses
@@ -30,18 +30,6 @@ namespace mgacbam {
 // pixels per thread per tile: 8, or 4 with 8-element (16 B fp16 / bf16) lanes, so a thread's loads of one channel group stay at
 // 32 elements in flight
 template <int VEC> struct NhwcNpx { static constexpr int value = VEC == 8 ? 4 : 8; };
-
-struct NhwcFwdArgs {
-  FwdArgs a;
-  NhwcGeo n;
-  float* ws;       // (B, nchunk, 4*C + 4) pool partials: [sum x*s][sum x][max][arg-max pixel (int)][sum s, 3 pad]
-};
-struct NhwcBwdArgs {
-  BwdArgs a;
-  NhwcGeo n;
-  int ncb;         // channel blocks of kNhwcFoldC (k_pool_fin, k_bwd_fold_nhwc): a.s.pgh is (B, ncb, hidden)
-};
-// A_part of an NHWC level: (B, nchunk, 3, C) = [A][D][sum x*wgt]
 
 // per-channel partials of a chunk: each thread holds N sums for the VEC channels of its group; rows are combined in row order
 // through LDS and threads t < CS*VEC write channel j*CS*VEC + t.  red: N * 256 * VEC floats.

@@ -12,17 +12,16 @@ namespace mgacbam {
 //   LDS: [C ca][C A][C D][2 * 256 * VEC row partials]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_bwd_reduce1_nhwc(const Group<NhwcBwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_bwd_reduce1_nhwc(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcBwdArgs& N = G.lv[l];
-  const BwdArgs& A = N.a;
+  const BwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.nchunk, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.nchunk, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
   const size_t sb = static_cast<size_t>(b) * g.HW * g.C;
   const T* xb = static_cast<const T*>(A.x) + sb;
   const T* gb = static_cast<const T*>(A.gy) + sb;
@@ -32,12 +31,12 @@ __global__ __launch_bounds__(kBlock) void k_bwd_reduce1_nhwc(const Group<NhwcBwd
   float* s_acc = smem + C4;                                              // [C A][C D]
   float* red = s_acc + 2 * C4;
   for (int c = tid; c < g.C; c += kBlock) { s_ca[c] = A.c.ca[static_cast<size_t>(b) * g.C + c]; s_acc[c] = 0.f; s_acc[C4 + c] = 0.f; }
-  float* part = A.s.A_part + (static_cast<size_t>(b) * N.n.nchunk + chunk) * 3 * g.C;
+  float* part = A.s.A_part + (static_cast<size_t>(b) * A.n.nchunk + chunk) * 3 * g.C;
   __syncthreads();
-  const int nj = (N.n.ng + CS - 1) / CS, CV = CS * VEC;
-  const int t_end = min((chunk + 1) * N.n.rp, N.n.ntile);
-  for (int tile = chunk * N.n.rp; tile < t_end; ++tile) {
-    const int p0 = tile * N.n.ch;
+  const int nj = (A.n.ng + CS - 1) / CS, CV = CS * VEC;
+  const int t_end = min((chunk + 1) * A.n.rp, A.n.ntile);
+  for (int tile = chunk * A.n.rp; tile < t_end; ++tile) {
+    const int p0 = tile * A.n.ch;
     bool okp[kNhwcNpx];
     float sav[kNhwcNpx], accp[kNhwcNpx];
 #pragma unroll
@@ -49,8 +48,8 @@ __global__ __launch_bounds__(kBlock) void k_bwd_reduce1_nhwc(const Group<NhwcBwd
     }
     for (int j = 0; j < nj; ++j) {
       const int cgi = lane + j * CS;
-      const bool okc = cgi < N.n.ng;
-      const int c0 = min(cgi, N.n.ng - 1) * VEC;
+      const bool okc = cgi < A.n.ng;
+      const int c0 = min(cgi, A.n.ng - 1) * VEC;
       float cav[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) cav[e] = (okc && c0 + e < g.C) ? s_ca[c0 + e] : 0.f;
@@ -100,27 +99,26 @@ __global__ __launch_bounds__(kBlock) void k_bwd_reduce1_nhwc(const Group<NhwcBwd
 //   LDS: [256 * VEC row partials] static ; [C running sums] dynamic
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_bwd_reduce2_nhwc(const Group<NhwcBwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_bwd_reduce2_nhwc(const Group<BwdArgs> G) {
   __shared__ __align__(16) float red[kBlock * VEC];
   extern __shared__ __align__(16) float s_acc[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcBwdArgs& N = G.lv[l];
-  const BwdArgs& A = N.a;
+  const BwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.nchunk, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.nchunk, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
   const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
   const float invC = 1.f / static_cast<float>(g.C);
   const float* gp0 = A.s.gplanes + static_cast<size_t>(b) * 3 * g.HW;
   for (int c = tid; c < g.C; c += kBlock) s_acc[c] = 0.f;
-  float* part = A.s.A_part + (static_cast<size_t>(b) * N.n.nchunk + chunk) * 3 * g.C + 2 * g.C;
-  const int nj = (N.n.ng + CS - 1) / CS, CV = CS * VEC;
-  const int t_end = min((chunk + 1) * N.n.rp, N.n.ntile);
-  for (int tile = chunk * N.n.rp; tile < t_end; ++tile) {
-    const int p0 = tile * N.n.ch;
+  float* part = A.s.A_part + (static_cast<size_t>(b) * A.n.nchunk + chunk) * 3 * g.C + 2 * g.C;
+  const int nj = (A.n.ng + CS - 1) / CS, CV = CS * VEC;
+  const int t_end = min((chunk + 1) * A.n.rp, A.n.ntile);
+  for (int tile = chunk * A.n.rp; tile < t_end; ++tile) {
+    const int p0 = tile * A.n.ch;
     bool okp[kNhwcNpx];
     float g0[kNhwcNpx], g1[kNhwcNpx];
     int ci[kNhwcNpx];
@@ -135,8 +133,8 @@ __global__ __launch_bounds__(kBlock) void k_bwd_reduce2_nhwc(const Group<NhwcBwd
     }
     for (int j = 0; j < nj; ++j) {
       const int cgi = lane + j * CS;
-      const bool okc = cgi < N.n.ng;
-      const int c0 = min(cgi, N.n.ng - 1) * VEC;
+      const bool okc = cgi < A.n.ng;
+      const int c0 = min(cgi, A.n.ng - 1) * VEC;
       float xv[kNhwcNpx][VEC];
 #pragma unroll
       for (int k = 0; k < kNhwcNpx; ++k) {
@@ -179,23 +177,22 @@ __global__ __launch_bounds__(kBlock) void k_bwd_reduce2_nhwc(const Group<NhwcBwd
 //   pgh[b,cb,j] = sum_{c in block} W2[c,j] g_z[b,c] (channel order)
 //   LDS: [3 x 256 wave partials][kNhwcFoldC g_z]
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_bwd_fold_nhwc(const Group<NhwcBwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_bwd_fold_nhwc(const Group<BwdArgs> G) {
   __shared__ float s_part[3][kBlock];
   __shared__ float s_gz[kNhwcFoldC];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcBwdArgs& N = G.lv[l];
-  const BwdArgs& A = N.a;
+  const BwdArgs& A = G.lv[l];
   const Geo& g = A.g;
-  const int b = local / N.ncb, cb = local - b * N.ncb;
+  const int b = local / A.ncb, cb = local - b * A.ncb;
   const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6;
   const int c = cb * kNhwcFoldC + lane, cc = min(c, g.C - 1);
   const float a = softplusf_(*A.p.beta);
   {
-    const float* pb = A.s.A_part + static_cast<size_t>(b) * N.n.nchunk * 3 * g.C + cc;
+    const float* pb = A.s.A_part + static_cast<size_t>(b) * A.n.nchunk * 3 * g.C + cc;
     float As = 0.f, Ds = 0.f, Rs = 0.f;
 #pragma unroll 4
-    for (int q = grp; q < N.n.nchunk; q += 4) {
+    for (int q = grp; q < A.n.nchunk; q += 4) {
       const float* pq = pb + static_cast<size_t>(q) * 3 * g.C;
       As += pq[0]; Ds += pq[g.C]; Rs += pq[2 * g.C];
     }
@@ -220,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_fold_nhwc(const Group<NhwcBwdArg
   for (int j = tid; j < h; j += kBlock) {
     float p = 0.f;
     for (int k2 = 0; k2 < nc; ++k2) p += A.p.w2[static_cast<size_t>(cb * kNhwcFoldC + k2) * h + j] * s_gz[k2];
-    A.s.pgh[(static_cast<size_t>(b) * N.ncb + cb) * h + j] = p;
+    A.s.pgh[(static_cast<size_t>(b) * A.ncb + cb) * h + j] = p;
   }
 }
 
@@ -231,19 +228,18 @@ __global__ __launch_bounds__(kBlock) void k_bwd_fold_nhwc(const Group<NhwcBwdArg
 //   LDS: [C float4 q][C arg-max][2*hidden][256 scratch]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, bool GMASK>
-__global__ __launch_bounds__(kBlock) void k_bwd_apply_nhwc(const Group<NhwcBwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_bwd_apply_nhwc(const Group<BwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   __shared__ float red[8];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcBwdArgs& N = G.lv[l];
-  const BwdArgs& A = N.a;
+  const BwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.ntile, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.ntile, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
-  const int p0 = chunk * N.n.ch;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
+  const int p0 = chunk * A.n.ch;
   const float a = softplusf_(*A.p.beta);
   const float Nf = static_cast<float>(g.HW);
   const bool has_mask = A.mask != nullptr;
@@ -254,10 +250,10 @@ __global__ __launch_bounds__(kBlock) void k_bwd_apply_nhwc(const Group<NhwcBwdAr
 
   // ---- prologue: hidden gradient (channel-block partials in order), q[c], K_b ------------------------------------------------
   {
-    const float* pg = A.s.pgh + static_cast<size_t>(b) * N.ncb * h;
+    const float* pg = A.s.pgh + static_cast<size_t>(b) * A.ncb * h;
     for (int j = tid; j < h; j += kBlock) {
       float p = 0.f;
-      for (int q = 0; q < N.ncb; ++q) p += pg[q * h + j];
+      for (int q = 0; q < A.ncb; ++q) p += pg[q * h + j];
       s_gh[j] = A.c.h_avg[static_cast<size_t>(b) * h + j] > 0.f ? p : 0.f;
       s_gh[h + j] = A.c.h_mx[static_cast<size_t>(b) * h + j] > 0.f ? p : 0.f;
     }
@@ -308,10 +304,10 @@ __global__ __launch_bounds__(kBlock) void k_bwd_apply_nhwc(const Group<NhwcBwdAr
     ci[k] = A.c.cidx[po];
     accp[k] = 0.f;
   }
-  const int nj = (N.n.ng + CS - 1) / CS;
+  const int nj = (A.n.ng + CS - 1) / CS;
   for (int j = 0; j < nj; ++j) {
     const int cgi = lane + j * CS;
-    if (cgi >= N.n.ng) break;
+    if (cgi >= A.n.ng) break;
     const int c0 = cgi * VEC;
     float4 q[VEC];
     int am[VEC];

@@ -12,28 +12,27 @@ namespace mgacbam {
 //   LDS: [256*VEC x 3 row sums][256*VEC row arg-max (int)] static ; [C sum x*s][C sum x][C max][C arg-max (int)] dynamic
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, bool HAS_MASK>
-__global__ __launch_bounds__(kBlock) void k_pool_nhwc(const Group<NhwcFwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_pool_nhwc(const Group<FwdArgs> G) {
   __shared__ __align__(16) float red[3 * kBlock * VEC];
   __shared__ __align__(16) int redi[kBlock * VEC];
   extern __shared__ __align__(16) float s_acc[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcFwdArgs& N = G.lv[l];
-  const FwdArgs& A = N.a;
+  const FwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.nchunk, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.nchunk, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
   const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
-  float* part = N.ws + (static_cast<size_t>(b) * N.n.nchunk + chunk) * (4 * static_cast<size_t>(g.C) + 4);
+  float* part = A.ws + (static_cast<size_t>(b) * A.n.nchunk + chunk) * (4 * static_cast<size_t>(g.C) + 4);
   int* s_idx = reinterpret_cast<int*>(s_acc + 3 * g.C);
   for (int c = tid; c < g.C; c += kBlock) { s_acc[c] = 0.f; s_acc[g.C + c] = 0.f; s_acc[2 * g.C + c] = -FLT_MAX; s_idx[c] = INT_MAX; }
   float ssum = 0.f;
-  const int nj = (N.n.ng + CS - 1) / CS, CV = CS * VEC;
-  const int t_end = min((chunk + 1) * N.n.rp, N.n.ntile);
-  for (int tile = chunk * N.n.rp; tile < t_end; ++tile) {
-    const int p0 = tile * N.n.ch;
+  const int nj = (A.n.ng + CS - 1) / CS, CV = CS * VEC;
+  const int t_end = min((chunk + 1) * A.n.rp, A.n.ntile);
+  for (int tile = chunk * A.n.rp; tile < t_end; ++tile) {
+    const int p0 = tile * A.n.ch;
     float s[kNhwcNpx];
     bool sel[kNhwcNpx], okp[kNhwcNpx];
 #pragma unroll
@@ -50,8 +49,8 @@ __global__ __launch_bounds__(kBlock) void k_pool_nhwc(const Group<NhwcFwdArgs> G
     }
     for (int j = 0; j < nj; ++j) {
       const int cgi = lane + j * CS;
-      const bool okc = cgi < N.n.ng;
-      const int c0 = min(cgi, N.n.ng - 1) * VEC;
+      const bool okc = cgi < A.n.ng;
+      const int c0 = min(cgi, A.n.ng - 1) * VEC;
       float acc[3][VEC];                                                  // [sum x*s][sum x][max]
       int im[VEC];
 #pragma unroll
@@ -119,19 +118,18 @@ __global__ __launch_bounds__(kBlock) void k_pool_nhwc(const Group<NhwcFwdArgs> G
 // pooled statistics exactly as k_pool defines them; the shared MLP follows as k_mlp.
 // ---------------------------------------------------------------------------------------------
 template <bool HAS_MASK>
-__global__ __launch_bounds__(kBlock) void k_pool_fin(const Group<NhwcFwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_pool_fin(const Group<FwdArgs> G) {
   __shared__ float s_part[3][kBlock];
   __shared__ int s_pidx[kBlock];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcFwdArgs& N = G.lv[l];
-  const FwdArgs& A = N.a;
+  const FwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   const int ncb = (g.C + kNhwcFoldC - 1) / kNhwcFoldC;
   const int b = local / ncb, cb = local - b * ncb;
-  const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, nch = N.n.nchunk;
+  const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, nch = A.n.nchunk;
   const size_t stride = 4 * static_cast<size_t>(g.C) + 4;
-  const float* wb = N.ws + static_cast<size_t>(b) * nch * stride;
+  const float* wb = A.ws + static_cast<size_t>(b) * nch * stride;
   float S = 0.f;                                                        // every workgroup of the sample forms S the same way
   if (HAS_MASK) {
     for (int q = lane; q < nch; q += 64) S += wb[q * stride + 4 * g.C];
@@ -184,18 +182,17 @@ __global__ __launch_bounds__(kBlock) void k_pool_fin(const Group<NhwcFwdArgs> G)
 //   LDS: [C ca]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, bool HAS_MASK>
-__global__ __launch_bounds__(kBlock) void k_chan_nhwc(const Group<NhwcFwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_chan_nhwc(const Group<FwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcFwdArgs& N = G.lv[l];
-  const FwdArgs& A = N.a;
+  const FwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.ntile, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.ntile, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
-  const int p0 = chunk * N.n.ch;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
+  const int p0 = chunk * A.n.ch;
   const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
   float* s_ca = smem;
   for (int c = tid; c < g.C; c += kBlock) s_ca[c] = A.c.ca[static_cast<size_t>(b) * g.C + c];
@@ -208,10 +205,10 @@ __global__ __launch_bounds__(kBlock) void k_chan_nhwc(const Group<NhwcFwdArgs> G
     okp[k] = row < PR && p0 + k * PR + row < g.HW;
     vmax[k] = -INFINITY; vsum[k] = 0.f; vidx[k] = lane * VEC;
   }
-  const int nj = (N.n.ng + CS - 1) / CS;
+  const int nj = (A.n.ng + CS - 1) / CS;
   for (int j = 0; j < nj; ++j) {
     const int cgi = lane + j * CS;
-    if (cgi >= N.n.ng) break;
+    if (cgi >= A.n.ng) break;
     const int c0 = cgi * VEC;
     float xv[kNhwcNpx][VEC];
 #pragma unroll
@@ -254,18 +251,17 @@ __global__ __launch_bounds__(kBlock) void k_chan_nhwc(const Group<NhwcFwdArgs> G
 //   LDS: [3*k*k weights][3 * rows * (W+k-1) planes][CH sa][C ca]
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, int K>
-__global__ __launch_bounds__(kBlock) void k_apply_nhwc(const Group<NhwcFwdArgs> G) {
+__global__ __launch_bounds__(kBlock) void k_apply_nhwc(const Group<FwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  const NhwcFwdArgs& N = G.lv[l];
-  const FwdArgs& A = N.a;
+  const FwdArgs& A = G.lv[l];
   const Geo& g = A.g;
   int b, chunk;
-  if (!xcd_sample_part(local, g.B, N.n.ntile, b, chunk)) return;
+  if (!xcd_sample_part(local, g.B, A.n.ntile, b, chunk)) return;
   constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = N.n.cs, lane = tid & (CS - 1), row = tid >> N.n.lcs, PR = kBlock >> N.n.lcs;
-  const int CH = N.n.ch;
+  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
+  const int CH = A.n.ch;
   const int p0 = chunk * CH, p1 = min(p0 + CH, g.HW) - 1;
   const int k = K ? K : g.k, pad = k / 2;
   const int r0 = p0 / g.W, r1 = p1 / g.W;
@@ -321,10 +317,10 @@ __global__ __launch_bounds__(kBlock) void k_apply_nhwc(const Group<NhwcFwdArgs> 
     okp[k2] = row < PR && p0 + tp < g.HW;
     sav[k2] = okp[k2] ? s_sa[tp] : 0.f;
   }
-  const int nj = (N.n.ng + CS - 1) / CS;
+  const int nj = (A.n.ng + CS - 1) / CS;
   for (int j = 0; j < nj; ++j) {
     const int cgi = lane + j * CS;
-    if (cgi >= N.n.ng) break;
+    if (cgi >= A.n.ng) break;
     const int c0 = cgi * VEC;
     float cav[VEC];
 #pragma unroll

@@ -188,6 +188,64 @@ static void spade() {
     rc(F("spade bwd pyramid mixed layouts dt=%d n=%d", dt, n), mgaspade_backward(P, n, ST));
   }
 }
+// ---- calls of three and five small levels for the four level families: what decides the launch groups, mixed within one call
+// pattern 0 / 1: layouts alternate (NCHW first / channels-last first), mask, dL/dmask (gamma kept) and element type vary from level to level;
+// pattern 2 / 3: a block of one layout, then the other (channels-last first / NCHW first), fp32, two shapes of one vector width, so groups hold
+// several levels and their order inside a group shows; pattern 4 / 5: ONE signature throughout (NCHW / channels-last): five levels exceed a group
+struct Mix { Shape s; int dt, nhwc, mask, gmask, keep; };
+static Mix mix_level(int pattern, int l, int n, bool spade) {
+  static const Shape any[] = {{2, 64, 16, 16}, {2, 20, 10, 10}, {1, 6, 5, 7}, {1, 260, 7, 9}};
+  static const Shape sp[] = {{2, 64, 16, 16}, {2, 32, 10, 10}, {1, 16, 5, 7}, {1, 256, 7, 9}};   // MaskSPADE takes C % 16 == 0
+  const Shape* S = spade ? sp : any;
+  Mix m;
+  if (pattern < 2) {
+    m.s = S[l % 4]; m.dt = (l / 2) % 2 ? MGACBAM_F16 : MGACBAM_F32; m.nhwc = (l + pattern) & 1; m.mask = l % 3 != 1; m.gmask = m.mask && l != 3;
+    m.keep = l % 2 == 0;
+  } else if (pattern < 4) {
+    m.s = S[l % 2]; m.dt = MGACBAM_F32; m.nhwc = (pattern == 2) == (l < n / 2); m.mask = 1; m.gmask = l != 1; m.keep = l != 2;
+  } else {
+    m.s = S[l % 2]; m.dt = MGACBAM_F32; m.nhwc = pattern - 4; m.mask = 1; m.gmask = 1; m.keep = 1;
+  }
+  return m;
+}
+static void mixed() {
+  for (int pattern = 0; pattern < 6; ++pattern) for (int n : {3, 5}) {
+    mgacbam_fwd_level_t CF[5]; mgacbam_bwd_level_t CB[5];
+    mgacbam_eca_fwd_level_t EF[5]; mgacbam_eca_bwd_level_t EB[5];
+    mgahead_fwd_level_t HF[5]; mgahead_bwd_level_t HB[5];
+    mgaspade_level_t SF[5], SB[5];
+    for (int l = 0; l < n; ++l) {
+      const Mix m = mix_level(pattern, l, n, false);
+      const Shape s = m.s;
+      const int fl = m.nhwc ? MGACBAM_LAYOUT_NHWC : 0;
+      CF[l] = cbam_fwd(m.dt, s, 4, 7, m.mask, fl);
+      CB[l] = cbam_bwd(m.dt, s, 4, 7, m.mask, m.gmask, fl);
+      mgacbam_eca_fwd_level_t& L = EF[l];
+      L = mgacbam_eca_fwd_level_t{};
+      L.x = dev(); L.y = dev(); L.mask = m.mask ? devf() : nullptr; L.ctx = dev(); L.ctx_bytes = mgacbam_eca_ctx_bytes_flags(s.B, s.C, s.H, s.W, fl);
+      L.p = {devf(), devf(), 3, 1, 1e-4f, 1e-6f}; L.B = s.B; L.C = s.C; L.H = s.H; L.W = s.W; L.dtype = m.dt; L.flags = fl;
+      mgacbam_eca_bwd_level_t& Lb = EB[l];
+      Lb = mgacbam_eca_bwd_level_t{};
+      Lb.x = dev(); Lb.gy = dev(); Lb.gx = dev(); Lb.mask = L.mask; Lb.gmask = m.gmask ? devf() : nullptr; Lb.ctx = L.ctx; Lb.ctx_bytes = L.ctx_bytes;
+      Lb.scratch = dev(); Lb.scratch_bytes = mgacbam_eca_scratch_bytes_flags(s.B, s.C, s.H, s.W, fl); Lb.gw = devf(); Lb.gbeta = devf();
+      Lb.p = L.p; Lb.B = s.B; Lb.C = s.C; Lb.H = s.H; Lb.W = s.W; Lb.dtype = m.dt; Lb.flags = fl;
+      HB[l] = head_level(m.dt, s, 16, (m.nhwc ? MGAHEAD_LAYOUT_NHWC : 0) | (m.keep ? 0 : MGAHEAD_LOGITS_F32), HF[l]);
+      const Mix ms = mix_level(pattern, l, n, true);
+      SF[l] = spade_level(ms.dt, ms.s, 16, l % 2, 1, ms.mask, false, ms.mask && ms.keep, ms.nhwc ? kSpadeNhwc : 0);
+      SB[l] = spade_level(ms.dt, ms.s, 16, l % 2, 1, ms.mask, ms.gmask, 1, ms.nhwc ? kSpadeNhwc : 0);
+    }
+    rc(F("mixed cbam fwd pattern=%d n=%d", pattern, n), mgacbam_forward(CF, n, ST));
+    rc(F("mixed cbam fwd fused pattern=%d n=%d", pattern, n), mgacbam_forward_stages(CF, n, MGACBAM_FWD_ALL | MGACBAM_FWD_FUSE, ST));
+    rc(F("mixed cbam bwd pattern=%d n=%d", pattern, n), mgacbam_backward(CB, n, ST));
+    rc(F("mixed cbam bwd folded pattern=%d n=%d", pattern, n), mgacbam_backward_stages(CB, n, MGACBAM_BWD_ALL | MGACBAM_BWD_FOLD, ST));
+    rc(F("mixed eca fwd pattern=%d n=%d", pattern, n), mgacbam_eca_forward(EF, n, ST));
+    rc(F("mixed eca bwd pattern=%d n=%d", pattern, n), mgacbam_eca_backward(EB, n, ST));
+    rc(F("mixed head fwd pattern=%d n=%d", pattern, n), mgahead_forward(HF, n, ST));
+    rc(F("mixed head bwd pattern=%d n=%d", pattern, n), mgahead_backward(HB, n, ST));
+    rc(F("mixed spade fwd pattern=%d n=%d", pattern, n), mgaspade_forward(SF, n, ST));
+    rc(F("mixed spade bwd pattern=%d n=%d", pattern, n), mgaspade_backward(SB, n, ST));
+  }
+}
 // ---- segmentation loss, Kendall combine, gater, resize
 static void loss_side() {
   const mgaseg_cfg_t cfg{1.f, 1.f, 1.f, 0.5f, 0, 0.5f, 0.6f, 0.5f};
@@ -344,7 +402,7 @@ static void knob(const char* name, const char* value) {
 int main(int argc, char** argv) {
   stub_set_occupancy(argc > 1 ? atoi(argv[1]) : 4);
   printf("abi %d occupancy %s\n", mgacbam_abi_version(), argc > 1 ? argv[1] : "4");
-  cbam(true); eca(true); head(); spade(); loss_side(); invalid();
+  cbam(true); eca(true); head(); spade(); mixed(); loss_side(); invalid();
   const char* knobs[][2] = {{"MGACBAM_BWD_MERGE", "0"}, {"MGACBAM_GATE_NARROW", "1"}, {"MGACBAM_POOL_TX", "32"}, {"MGACBAM_POOL_CPT", "1"},
                             {"MGACBAM_POOL_CPT", "2"}, {"MGACBAM_POOL_CPT", "4"}, {"MGACBAM_CHAN_TX", "16"}, {"MGACBAM_RESIDENT_WGS", "64"},
                             {"MGACBAM_RESIDENT_WGS", "100000"}};

@@ -5,7 +5,8 @@ levels, each launch printed as kernel / grid / block / LDS / stream.  Two revisi
 
   launch_plan.py run TREE OUT [--sanitize] [--resource-log LOG] [--objdir DIR]
                                      build TREE's csrc/api_*.hip (its own build.py flags; objects already in DIR are reused), write the plan
-  launch_plan.py diff A B                                         compare two plans: launches and return codes, then messages
+  launch_plan.py diff A B                                         compare two plans: launches (kernels by demangled name and template
+                                                                  arguments, whatever their parameter types) and return codes, then messages
 """
 import importlib.util
 import os
@@ -57,9 +58,19 @@ def run(tree, out, sanitize=False, resource_log=None, objdir=None):
         print("\n".join("  " + n for n in names.split("\n") if n))
 
 
+def demangled(path):
+    """The plan's lines with every kernel as its demangled name and template arguments, without the parameter list: a kernel whose
+    argument block changed its type between two revisions is still the same kernel."""
+    text = open(path).read()
+    names = sorted(set(re.findall(r"^  (?:launch|attribute) (\S+)", text, re.M)))
+    plain = subprocess.run(["c++filt", "-p"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    table = dict(zip(names, plain))
+    return re.sub(r"^(  (?:launch|attribute) )(\S+)", lambda m: m.group(1) + table[m.group(2)], text, flags=re.M).splitlines()
+
+
 def diff(a, b):
     split = lambda line: re.match(r"(.* -> -?\d+) ?(.*)$", line).groups() if " -> " in line and not line.startswith("  ") else (line, "")
-    A, Bl = [split(l.rstrip("\n")) for l in open(a)], [split(l.rstrip("\n")) for l in open(b)]
+    A, Bl = [split(l) for l in demangled(a)], [split(l) for l in demangled(b)]
     plan = sum(x[0] != y[0] for x, y in zip(A, Bl)) + abs(len(A) - len(Bl))
     msgs = sorted({(x[1], y[1]) for x, y in zip(A, Bl) if x[0] == y[0] and x[1] != y[1]})
     print(f"{len(A)} / {len(Bl)} lines; {plan} differ in kernel, grid, block, LDS, stream or return code; {len(msgs)} distinct message differences")
