@@ -253,3 +253,28 @@ def fill_nms(D: _lib.NmsDesc, feats, pred, strides, nc: int, conf_thres: float, 
     D.conf_thres, D.iou_thres, D.cand_cap, D.reserved = float(conf_thres), float(iou_thres), int(cand_cap), 0
     D.dets, D.count, D.keep, D.status = (t.data_ptr() for t in (dets, count, keep, status))
     D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+
+
+# ---- detections matched to labels (include/ext/mgamatch.h)
+def fill_match(D: _lib.MatchDesc, dets, count, batch_idx, cls, bboxes, n, m_cap: int, img_w: float, img_h: float, iouv, flags: int,
+               tp, best_iou, best_gt, status, acc=None, ws=None) -> None:
+    """dets fp32 (B, max_det, 6) and count int32 (B) as mganms_run writes them; batch_idx / cls (n_cap) and bboxes (n_cap, 4) fp32; n: the
+    int32 device word of live label rows or None (= n_cap); iouv: the thresholds as Python floats; flags: _lib.MATCH_SINGLE_CLS; tp uint8
+    (B, max_det, niou), best_iou fp32 and best_gt int32 (B, max_det) and status int32 (1) are written.  acc: None, or the accumulation
+    buffers (rows_tp uint8 (rows_cap, niou), rows_conf, rows_cls fp32 and rows_img int32 (rows_cap), tgt_cls fp32 and tgt_img int32
+    (tgt_cap), state int32 (4)); ws: uint8, _lib.match_ws_bytes of the filled struct (fill once without it to ask, then again with it)."""
+    D.dets, D.count = dets.data_ptr(), count.data_ptr()
+    has = batch_idx.shape[0] > 0
+    D.batch_idx, D.cls, D.bboxes = (batch_idx.data_ptr(), cls.data_ptr(), bboxes.data_ptr()) if has else (None, None, None)
+    D.n = _ptr(n)
+    D.B, D.max_det, D.n_cap, D.m_cap = dets.shape[0], dets.shape[1], batch_idx.shape[0], int(m_cap)
+    D.img_w, D.img_h, D.niou, D.flags = float(img_w), float(img_h), len(iouv), int(flags)
+    for t in range(_lib.MATCH_MAX_IOU):
+        D.iouv[t] = float(iouv[t]) if t < len(iouv) else 0.0
+    D.tp, D.best_iou, D.best_gt, D.status = (t.data_ptr() for t in (tp, best_iou, best_gt, status))
+    rows_tp, rows_conf, rows_cls, rows_img, tgt_cls, tgt_img, state = acc if acc is not None else (None,) * 7
+    D.rows_cap, D.tgt_cap = (rows_conf.shape[0], tgt_cls.shape[0]) if acc is not None else (0, 0)
+    D.rows_tp, D.rows_conf, D.rows_cls, D.rows_img = _ptr(rows_tp), _ptr(rows_conf), _ptr(rows_cls), _ptr(rows_img)
+    D.tgt_cls, D.tgt_img, D.state = _ptr(tgt_cls), _ptr(tgt_img), _ptr(state)
+    D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+    D.reserved = 0

@@ -212,6 +212,21 @@ class NmsDesc(C.Structure):                      # mganms_desc_t
                 ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+# detections matched to labels for the validation metrics (include/ext/mgamatch.h: a header in a directory of its own, EXT_HEADERS below)
+MATCH_MAX_IOU, MATCH_SINGLE_CLS = 16, 1
+
+
+class MatchDesc(C.Structure):                    # mgamatch_desc_t
+    _fields_ = [("dets", C.c_void_p), ("count", C.c_void_p), ("batch_idx", C.c_void_p), ("cls", C.c_void_p), ("bboxes", C.c_void_p),
+                ("n", C.c_void_p), ("B", C.c_int32), ("max_det", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32),
+                ("img_w", C.c_float), ("img_h", C.c_float), ("niou", C.c_int32), ("flags", C.c_int32), ("iouv", C.c_float * MATCH_MAX_IOU),
+                ("rows_cap", C.c_int32), ("tgt_cap", C.c_int32),
+                ("tp", C.c_void_p), ("best_iou", C.c_void_p), ("best_gt", C.c_void_p),
+                ("rows_tp", C.c_void_p), ("rows_conf", C.c_void_p), ("rows_cls", C.c_void_p), ("rows_img", C.c_void_p),
+                ("tgt_cls", C.c_void_p), ("tgt_img", C.c_void_p), ("state", C.c_void_p), ("status", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("reserved", C.c_int32)]
+
+
 class Header(NamedTuple):
     """What one file under include/ declares and this module mirrors (tests/test_abi_headers.py holds each record against its header)."""
     symbols: dict        # function -> (restype, argtypes)
@@ -335,9 +350,23 @@ HEADERS = {
         structs=dict(mganms_desc=NmsDesc),
         constants=dict(MGANMS_MAX_LEVELS=NMS_MAX_LEVELS, MGANMS_MULTI_LABEL=NMS_MULTI_LABEL, MGANMS_AGNOSTIC=NMS_AGNOSTIC)),
 }
-_bound = [name for h in HEADERS.values() for name in h.symbols]
+# the headers in directories below include/, keyed by their path from it: bound exactly as HEADERS, held to their files by their own tests
+# (tests/test_abi_match.py)
+EXT_HEADERS = {
+    "ext/mgamatch.h": Header(
+        symbols={
+            "mgamatch_ws_bytes": (C.c_size_t, [C.POINTER(MatchDesc)]),
+            "mgamatch_run": (_i, [C.POINTER(MatchDesc), C.c_void_p]),
+        },
+        structs=dict(mgamatch_desc=MatchDesc),
+        constants=dict(MGAMATCH_MAX_IOU=MATCH_MAX_IOU, MGAMATCH_SINGLE_CLS=MATCH_SINGLE_CLS)),
+}
+ALL_HEADERS = {**HEADERS, **EXT_HEADERS}
+_bound = [name for h in ALL_HEADERS.values() for name in h.symbols]
+if set(HEADERS) & set(EXT_HEADERS):
+    raise ImportError(f"_lib.HEADERS and _lib.EXT_HEADERS both hold a record for {sorted(set(HEADERS) & set(EXT_HEADERS))}")
 if len(_bound) != len(set(_bound)):
-    raise ImportError(f"_lib.HEADERS binds a symbol in two records: {sorted(n for n in set(_bound) if _bound.count(n) > 1)}")
+    raise ImportError(f"_lib.HEADERS and _lib.EXT_HEADERS bind a symbol in two records: {sorted(n for n in set(_bound) if _bound.count(n) > 1)}")
 
 _lib = None
 _lock = threading.Lock()
@@ -361,7 +390,7 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for h in HEADERS.values():
+        for h in ALL_HEADERS.values():
             for name, (res, args) in h.symbols.items():
                 try:
                     fn = getattr(lib, name)
@@ -486,6 +515,11 @@ def det_ws_bytes(desc) -> int:
 def nms_ws_bytes(desc) -> int:
     """Workspace of a detection post-process call."""
     return _table_size("mganms_ws_bytes", E_ARG, C.byref(desc))
+
+
+def match_ws_bytes(desc) -> int:
+    """Workspace of a detection-matching call."""
+    return _table_size("mgamatch_ws_bytes", E_ARG, C.byref(desc))
 
 
 def sync_regions(B, Cc, H, W) -> dict:

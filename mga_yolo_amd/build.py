@@ -30,7 +30,10 @@ _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 # mask-head and loss kernels lose what -O3's extra unrolling / hoisting cost them in registers.  (Measured and not adopted: the scheduler
 # strategies max-ilp (k_gate +3 us), iterative-minreg (+6 %), max-memory-clause (same); -fno-vectorize (same).)
 BASE_FLAGS = ["-O2", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wno-pass-failed", "-fno-slp-vectorize"]
-UNIT_FLAGS: dict = {}          # extra flags per translation unit (none at present)
+INCLUDE = os.path.join(ROOT, "include")
+# extra flags per translation unit.  api_match.hip: include/ext/mgamatch.h names "mgatargets.h", which lies one directory above it; its IoU
+# is the reference's fp32 expression operation by operation, so no product may be contracted into a fused multiply-add
+UNIT_FLAGS: dict = {"api_match.hip": ["-I", INCLUDE, "-ffp-contract=off"]}
 
 
 def sources():
@@ -38,12 +41,13 @@ def sources():
 
 
 def _includes(path: str, seen: set) -> set:
-    """Files `path` includes with quotes, transitively (relative to the including file)."""
+    """Files `path` includes with quotes, transitively (relative to the including file, else to include/)."""
     if path in seen or not os.path.exists(path):
         return seen
     seen.add(path)
     for inc in _INC.findall(open(path).read()):
-        _includes(os.path.normpath(os.path.join(os.path.dirname(path), inc)), seen)
+        near = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+        _includes(near if os.path.exists(near) else os.path.join(INCLUDE, inc), seen)      # (-I include: UNIT_FLAGS)
     return seen
 
 

@@ -11,7 +11,9 @@ that binds one of the class names to a class of that name is rebound.  The train
 ``MGAModel.init_criterion`` imports the loss classes at call time (model/model.py:103-117): covered by the same rule.
 Nothing else in the reference changes.  ``install(nms=True)`` -- opt-in -- also rebinds ``non_max_suppression`` in the reference's
 ``ultralytics.utils.ops`` modules: the validator and the predictor look it up through ``ops.`` at call time (U/models/yolo/detect/val.py,
-predict.py), so the unchanged ``postprocess`` then runs ``detpost.non_max_suppression``.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
+predict.py), so the unchanged ``postprocess`` then runs ``detpost.non_max_suppression``.  ``install(match=True)`` -- opt-in as well -- rebinds
+``DetectionValidator.update_metrics`` in the reference's ``ultralytics.models.yolo.detect.val`` modules to ``detmatch.update_metrics``: one matching call
+and one read-back per batch; subclasses (``MGAValidator``) reach it through ``super()``.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
 """
 from __future__ import annotations
 
@@ -42,12 +44,13 @@ def _is_reference_module(name: str) -> bool:
     return any(name == p or name.startswith(p + ".") for p in _PREFIXES) and not name.startswith("mga_yolo_amd")
 
 
-def install(strict: bool = False, nms: bool = False) -> List[str]:
+def install(strict: bool = False, nms: bool = False, match: bool = False) -> List[str]:
     """Rebind the block classes in every loaded reference module that exports them.  Returns the module names patched.
     ``strict=True`` raises unless the module whose ``parse_model`` builds ``MGAModel`` (the one providing
     ``mga_yolo.model.model.DetectionModel``; ``ultralytics.nn.tasks`` when mga_yolo is absent) was patched.
-    ``nms=True`` also rebinds ``non_max_suppression`` in the reference's ``ultralytics.utils.ops`` modules (see ``_install_nms``)."""
-    for name in _PRELOAD + (_OPS_PRELOAD if nms else ()):
+    ``nms=True`` also rebinds ``non_max_suppression`` in the reference's ``ultralytics.utils.ops`` modules (see ``_install_nms``),
+    ``match=True`` ``DetectionValidator.update_metrics`` in its ``ultralytics.models.yolo.detect.val`` modules (see ``_install_match``)."""
+    for name in _PRELOAD + (_OPS_PRELOAD if nms else ()) + (_VAL_PRELOAD if match else ()):
         if name not in sys.modules:
             try:
                 importlib.import_module(name)
@@ -73,6 +76,8 @@ def install(strict: bool = False, nms: bool = False) -> List[str]:
             patched.append(name)
     if nms:
         patched += _install_nms()
+    if match:
+        patched += _install_match()
     if strict:
         need = _factory_module_name()
         if need not in patched:
@@ -102,6 +107,34 @@ def _install_nms() -> List[str]:
     return done
 
 
+_VAL_PRELOAD = ("ultralytics.models.yolo.detect.val", "mga_yolo.external.ultralytics.ultralytics.models.yolo.detect.val")
+_VAL_SUFFIX = "ultralytics.models.yolo.detect.val"
+
+
+def _install_match() -> List[str]:
+    """Rebind ``DetectionValidator.update_metrics`` in every loaded ``ultralytics.models.yolo.detect.val`` module of the reference (two module
+    objects of that file, as of ops.py).  The class keeps its identity, so subclasses reach the replacement through ``super()``; the method it
+    replaces is kept in ``detmatch._ORIGINALS``, where the replacement finds it for what it does not cover (a subclass with a
+    ``_process_batch`` of its own: masks, keypoints, rotated boxes).  uninstall() restores it: the undo record names the class,
+    ``<module>:DetectionValidator``."""
+    from .detmatch import _ORIGINALS, update_metrics
+    done = []
+    for name, mod in list(sys.modules.items()):
+        if mod is None or not _is_reference_module(name) or not name.endswith(_VAL_SUFFIX):
+            continue
+        cls = mod.__dict__.get("DetectionValidator", _MISSING)
+        if not isinstance(cls, type):
+            continue
+        cur = cls.__dict__.get("update_metrics", _MISSING)
+        if cur is _MISSING or cur is update_metrics:
+            continue
+        _UNDO.append((name + ":DetectionValidator", "update_metrics", cur))
+        _ORIGINALS[cls] = cur
+        cls.update_metrics = update_metrics
+        done.append(name)
+    return done
+
+
 _MISSING = object()
 _UNDO: list = []          # (module name, attribute, previous value) of every rebinding install() made
 
@@ -111,9 +144,12 @@ def uninstall() -> int:
     n = 0
     while _UNDO:
         name, attr, old = _UNDO.pop()
-        mod = sys.modules.get(name)
-        if mod is not None:
-            setattr(mod, attr, old)
+        name, _, member = name.partition(":")                    # "<module>:<class>": an attribute of a class of the module
+        owner = sys.modules.get(name)
+        if owner is not None and member:
+            owner = getattr(owner, member, None)
+        if owner is not None:
+            setattr(owner, attr, old)
             n += 1
     return n
 
