@@ -522,23 +522,28 @@ def match_ws_bytes(desc) -> int:
     return _table_size("mgamatch_ws_bytes", E_ARG, C.byref(desc))
 
 
+ARRIVE_STRIDE = 64     # int32 words between the arrival words of two samples (csrc/args.cuh: kArriveStride)
+
+
 def sync_regions(B, Cc, H, W) -> dict:
     """The hand-off state at ctx_layout()["sync"], in int32 words from its start: name -> (offset, length).  Every word is a generation
     counter the caller zero-fills once.  This is the one Python copy of csrc/host.cuh's sync_layout (tests/test_abi.py pins the two
     against each other): gate = (B, nflag) k_gate tile flags, status = [time-out, 3 spare], ca = (B) per-sample flags, tiles / conv_tiles =
     (B, nflag) flags of the folded backward launch, merged_* / wsa_tiles = the same and the dWsa-tile flags of the merged launch
-    (k_bwd_r12), sweeps = its (B, C) per-channel flags."""
+    (k_bwd_r12), sweeps = its (B, C) per-channel flags, arrive = (B, ARRIVE_STRIDE), column 0 = the arrival word of
+    k_pool's workgroups of a sample at the levels where its last arriver forms ca (the one region that does not count calls: every launch
+    leaves it at 0)."""
     nf = B * ((H * W + 15) // 16 + 1)              # nflag per sample: one per 16 pixels (kSyncPx) + 1
     out, o = {}, 0
     for name, n in (("gate", nf), ("status", 4), ("ca", B), ("tiles", nf), ("conv_tiles", nf), ("merged_tiles", nf),
-                    ("merged_conv_tiles", nf), ("wsa_tiles", nf), ("sweeps", B * Cc)):
+                    ("merged_conv_tiles", nf), ("wsa_tiles", nf), ("sweeps", B * Cc), ("arrive", B * ARRIVE_STRIDE)):
         out[name] = (o, n)
         o += n
     return out
 
 
 def sync_len(B, Cc, H, W) -> int:
-    o, n = sync_regions(B, Cc, H, W)["sweeps"]
+    o, n = sync_regions(B, Cc, H, W)["arrive"]
     return o + n
 
 

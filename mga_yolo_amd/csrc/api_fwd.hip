@@ -34,6 +34,8 @@ static int forward_args(const mgacbam_fwd_level_t& L, FwdArgs& A, FwdSig& sig) {
   A.x = L.x; A.mask = L.mask; A.y = L.y; A.fused = 0;
   level_setup(L, A);
   A.fault = knobs().fault;
+  A.pool_mlp = 0;
+  A.arrive0 = static_cast<int>(sync_layout(L.B, L.C, static_cast<size_t>(L.H) * L.W).arrive);
   A.n = NhwcGeo{}; A.ws = nullptr;
   sig = FwdSig{};
   sig.dtype = L.dtype; sig.vec = VEC; sig.has_mask = L.mask != nullptr; sig.k = L.p.k; sig.nhwc = nhwc;
@@ -56,6 +58,7 @@ static int forward_args(const mgacbam_fwd_level_t& L, FwdArgs& A, FwdSig& sig) {
     gate_geometry(L.C, L.H, L.W, L.p.k, 8, t8);
     if (t8.gate_tx > 0) { sig.gvec = 8; A.t = t8; }
   }
+  A.pool_mlp = pool_forms_ca(A.g, A.t, false, L.dtype);
   return 0;
 }
 
@@ -89,17 +92,23 @@ static int forward_group(FwdArgs* lv, int n, const FwdSig& sig, int stages, hipS
   }
   if (gate) for (int l = 0; l < n; ++l) { lv[l].fused = 1; G.lv[l].fused = 1; }
 
+  // levels whose ca k_pool forms (pool_forms_ca, a rule of the level alone): a group with one takes k_pool's instantiation with the tail
+  bool any_pool_mlp = false, all_pool_mlp = true;
+  for (int l = 0; l < n; ++l) { any_pool_mlp |= lv[l].pool_mlp != 0; all_pool_mlp &= lv[l].pool_mlp != 0; }
+
   if (stages & MGACBAM_FWD_POOL) {  // 1. pooling
     auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_cpt(pool_cpt, [&](auto c) {
-      return with_bool(sig.has_mask, [&](auto m) { return k_pool<elem_t<decltype(t)>, v.value, c.value, m.value>; }); }); });
-    if (int e = launch_group("k_pool", kernel, G, [&](const FwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, pool_cpt); }, 0, st)) return e;
+      return with_bool(sig.has_mask, [&](auto m) { return with_bool(any_pool_mlp, [&](auto ml) {
+        return k_pool<elem_t<decltype(t)>, v.value, c.value, m.value, ml.value>; }); }); }); });
+    if (int e = launch_group("k_pool", kernel, G, [&](const FwdArgs& a) { return sweep_blocks(a, a.t.pool_tx, pool_cpt); },
+                             [](const FwdArgs& a) { return a.pool_mlp ? pool_mlp_smem(a.g) : size_t(0); }, st)) return e;
   }
   if (gate) {
     GateGroup GG;
     const int tiles = fill_starts(G, lv, n, [&](const FwdArgs& a) { return xcd_grid(a.g.B, gate_tiles(a.t, a.g.H, a.g.W, gvec)); });
     GG.g = G;
     GG.nrole = 0;
-    for (int l = 0; l < n; ++l) { GG.rstart[l] = GG.nrole; GG.nrole += lv[l].g.B; }
+    for (int l = 0; l < n; ++l) { GG.rstart[l] = GG.nrole; GG.nrole += lv[l].pool_mlp ? 0 : lv[l].g.B; }
     GG.rstart[n] = GG.nrole;
     return launch("k_gate", gate_kernel, GG.nrole + tiles, kBlock, gsmem, st, GG);
   }
@@ -108,8 +117,9 @@ static int forward_group(FwdArgs* lv, int n, const FwdSig& sig, int stages, hipS
     bool split_mlp = false;
     for (int l = 0; l < n; ++l) split_mlp |= static_cast<long long>(lv[l].g.C) * lv[l].g.hidden >= 8192;
     if (split_mlp) if (int e = launch_mlp(G, st)) return e;
+    const bool have_ca = split_mlp || all_pool_mlp;            // from k_mlp, or every level's from k_pool: no prologue (mixed groups keep it)
     auto kernel = with_elem_vec(sig.dtype, sig.vec, [&](auto t, auto v) { return with_bool(sig.proj, [&](auto pj) {
-      return with_bool(split_mlp, [&](auto sp) { return k_chan<elem_t<decltype(t)>, v.value, pj.value, sp.value>; }); }); });
+      return with_bool(have_ca, [&](auto sp) { return k_chan<elem_t<decltype(t)>, v.value, pj.value, sp.value>; }); }); });
     if (int e = launch_group("k_chan", kernel, G, [&](const FwdArgs& a) { return xcd_grid(a.g.B, chan_tiles(a.t, a.g.H, a.g.W, sig.vec)); },
                              [&](const FwdArgs& a) { return chan_smem(a.g, sig.vec, sig.proj); }, st)) return e;
   }

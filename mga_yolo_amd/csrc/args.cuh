@@ -17,6 +17,8 @@ constexpr int kProjMax = 4;   // MGACBAM_PROJ_MAX_HIDDEN
 constexpr int kProjWide = 16; // widest hidden layer the backward makes planes for: the 16 output rows of one v_mfma_f32_16x16x4_f32
 constexpr int kGateR = 16;   // channels a thread of the x-resident kernels keeps in registers (x VEC pixels each)
 constexpr int kSyncPx = 16;   // a hand-off tile is at least this many pixels: ctx.sync holds ceil(HW/kSyncPx)+1 flags per sample
+constexpr int kArriveStride = 64;   // ints between the arrival words of two samples (256 B): returning device-scope adds on ONE line
+                                    // serialise at ~90 per us whichever word they hit -- 1,024 of them on one line cost k_pool 7 us
 
 // saved statistics (device pointers into the caller's ctx buffer) -- see mgacbam_ctx_layout_t
 struct CtxPtrs {
@@ -27,7 +29,9 @@ struct CtxPtrs {
   float* planes; int* cidx; float* sa;
   float* proj;     // (B, hidden, HW) when hidden <= kProjMax (a backward level with wider planes: ScratchPtrs::proj, put here by the host)
   int* sync;       // in-launch hand-off state, all generation counters (zero-filled once by the caller, never reset): [B][nflag] k_gate tile flags,
-                   // 4 status words ([0] = time-out), [B] per-sample ca flags, [B][nflag] k_bwd_reduce1 tile flags, [B][nflag] folded conv-tile flags
+                   // 4 status words ([0] = time-out), [B] per-sample ca flags, [B][nflag] k_bwd_reduce1 tile flags, [B][nflag] folded conv-tile flags,
+                   // ... (host: sync_layout); last, k_pool's arrival words, one per sample, kArriveStride apart (not generation counters: a
+                   // launch counts them up and puts them back to 0)
 };
 
 struct ParamPtrs { const float* w1; const float* b1; const float* w2; const float* b2; const float* wsa; const float* beta; };
@@ -67,6 +71,9 @@ struct FwdArgs {
   unsigned spin_limit;   // bound of every hand-off spin (knob MGACBAM_SPIN_LIMIT, default 2^20 ~ 1 s)
   int fault;       // fault injection for tests (knob MGACBAM_FAULT=1): sample 0's role workgroup never publishes ca
   long long* trace;   // MGACBAM_TRACE builds only: per-workgroup phase timestamps (tools/trace_gate.py), else nullptr
+  int pool_mlp;    // ca, h_avg, h_mx of this level are formed by k_pool's last arriver of each sample (host: pool_forms_ca, a rule of the
+                   // level alone): k_gate gives it no role workgroups and its tiles do not wait for ca
+  int arrive0;     // the level's arrival words of k_pool in c.sync (ints), sample b's at arrive0 + b * kArriveStride: 0 between launches
   // channels-last levels (MGACBAM_LAYOUT_NHWC: the kernels of nhwc_fwd.cuh) only
   NhwcGeo n;
   float* ws;       // (B, nchunk, 4*C + 4) pool partials: [sum x*s][sum x][max][arg-max pixel (int)][sum s, 3 pad]

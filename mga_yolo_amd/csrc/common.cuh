@@ -235,6 +235,9 @@ __device__ __forceinline__ float block_sum(float v, int tid, float* red) {
 
 __device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
 
+// shapes the streamed form of the shared MLP takes (fwd.cuh: mlp_stream); asked by the kernels and by the host's rules
+__host__ __device__ __forceinline__ bool mlp_stream_ok(const Geo& g) { return (g.C & 3) == 0 && (g.hidden & 3) == 0 && g.C <= 8 * 4 * kWave; }
+
 // One axis of F.interpolate(mode="bilinear", align_corners=False), torch's fp32 coordinate rule (scale = n / destination length, in fp32):
 // source coordinate max(scale * (d + 0.5) - 0.5, 0), taps i0 <= i1 (equal at the last index), weights 1 - lam and lam.  The ONE statement
 // of the rule: the loss's bilinear targets (segloss.cuh), the mask resample and its adjoint (resample.cuh) all call it.

@@ -1,7 +1,8 @@
 // Forward kernels of the mask-guided CBAM block (reference mga_yolo/nn/modules/masked_cbam.py:87-171).
 //
 //   k_pool   x (1 read)         -> avg, mx (+ arg-max), S/use/den, sigma(mask) plane                     [HBM-bound]
-//   k_gate   x (1 read, the tile stays in registers) -> role workgroups: shared MLP -> ca ; tiles: planes[max_c, mean_c], cidx,
+//                                  levels with FwdArgs::pool_mlp: the last workgroup of a sample to arrive also runs the shared MLP -> ca
+//   k_gate   x (1 read, the tile stays in registers) -> role workgroups: shared MLP -> ca (levels without pool_mlp) ; tiles: planes[max_c, mean_c], cidx,
 //                                  in-launch hand-off of the plane rows, k x k conv -> sa, y (1 write)      [MGACBAM_FWD_FUSE]
 //   fallback (shapes k_gate does not take, or without the flag):
 //   k_chan   x (1 read)         -> prologue: shared MLP -> ca ; body: planes[max_c, mean_c], cidx         [HBM-bound]
@@ -37,8 +38,17 @@ namespace mgacbam {
 // Comparing the LOGIT keeps valid / amax bit-exact where a fast sigmoid (v_exp + v_rcp, ~1e-6) could flip a pixel within ~1e-6 of 0.
 constexpr float kSelLogit = 0x1.8p-24f;
 
-template <typename T, int VEC, int CPT, bool HAS_MASK>
-__device__ __forceinline__ void pool_body(const FwdArgs& A, const int bid, float* red) {
+// the streamed shared MLP (defined below, with gate_role): LDA = avg / mx are read with agent-scope loads, NW1 / NW2 = 16-byte vectors
+// of W1 / W2 a thread holds per pass
+constexpr int kMlpW1 = 8;       // 16-byte vectors of W1 a lane holds per pass
+constexpr int kMlpW2 = 8;       // 16-byte vectors of W2 a thread holds per pass
+constexpr int kPoolMlpW = 2;    // both, in k_pool's tail: C*hidden is small there, and the instantiation keeps k_pool's 8 waves per SIMD
+template <bool AGENT, bool LDA = false, int NW1 = kMlpW1, int NW2 = kMlpW2>
+__device__ __forceinline__ void mlp_stream(const FwdArgs& A, const int b, float* smem);
+
+// MLP: the instantiation for launch groups with a pool_mlp level; `smem` = its dynamic LDS, [last?, 3 pad][2C avg|mx][2h] (host: pool_mlp_smem)
+template <typename T, int VEC, int CPT, bool HAS_MASK, bool MLP>
+__device__ __forceinline__ void pool_body(const FwdArgs& A, const int bid, float* red, float* smem) {
   const Geo& g = A.g;
   const int tid = threadIdx.x;
   const int TX = A.t.pool_tx, lt = ilog2(TX);
@@ -61,6 +71,7 @@ __device__ __forceinline__ void pool_body(const FwdArgs& A, const int bid, float
   const float* mb = HAS_MASK ? A.mask + static_cast<size_t>(b) * g.HW : nullptr;
   float* splane = A.c.planes + (static_cast<size_t>(b) * 3 + 2) * g.HW;
   const bool writes_plane = (cg == 0 && ty == 0);
+  const bool tail = MLP && A.pool_mlp;                       // (uniform over the level)
 
   float sx[CPT], sxs[CPT], vmax[CPT];
   int imax[CPT];
@@ -145,7 +156,9 @@ __device__ __forceinline__ void pool_body(const FwdArgs& A, const int bid, float
         } else {
           mavg = gap; avg = gap; valid = 1; mxo = vmax[j];   // masked_cbam.py:90-91, 107-108
         }
-        A.c.avg[o] = avg; A.c.mavg[o] = mavg; A.c.mx[o] = mxo;
+        if (tail) { st_agent(A.c.avg + o, avg); st_agent(A.c.mx + o, mxo); }   // read by another workgroup of THIS launch
+        else { A.c.avg[o] = avg; A.c.mx[o] = mxo; }
+        A.c.mavg[o] = mavg;
         A.c.valid[o] = valid; A.c.amax[o] = imax[j];
       }
     }
@@ -161,14 +174,35 @@ __device__ __forceinline__ void pool_body(const FwdArgs& A, const int bid, float
   __syncthreads();
   TRACE_MARK(A.trace, blockIdx.x, 10);
 #endif
+  if constexpr (MLP) {
+    if (!tail) return;
+    // The ncg workgroups of a sample count their arrivals (hand-off rules of common.cuh: agent-scope stores, every wave drains them,
+    // barrier, one lane adds); the one whose add comes last -- told by the value the add RETURNED, so there is no wait anywhere -- finds
+    // every avg / mx of the sample written through, and runs the sample's MLP.  It puts the word back to 0 first: the count is per
+    // launch, so a call with another channel grouping (MGACBAM_POOL_TX / _POOL_CPT, another group composition) starts clean.
+    int* arrive = A.c.sync + A.arrive0 + static_cast<size_t>(b) * kArriveStride;
+    int* s_last = reinterpret_cast<int*>(smem);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      const int before = __hip_atomic_fetch_add(arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (before == ncg - 1) st_agent(arrive, 0);
+      *s_last = before == ncg - 1;
+    }
+    __syncthreads();
+    if (!*s_last) return;
+    mlp_stream<false, true, kPoolMlpW, kPoolMlpW>(A, b, smem + 4);   // ca, h_avg, h_mx plainly: the next launch reads them
+    TRACE_MARK(A.trace, blockIdx.x, 11);                       // the sample's MLP is done
+  }
 }
 
-template <typename T, int VEC, int CPT, bool HAS_MASK>
+template <typename T, int VEC, int CPT, bool HAS_MASK, bool MLP = false>
 __global__ __launch_bounds__(kBlock) void k_pool(const Group<FwdArgs> G) {
   __shared__ float red[64];
+  extern __shared__ __align__(16) float pool_smem[];
   int local;
   const int l = find_level(G, blockIdx.x, local);
-  pool_body<T, VEC, CPT, HAS_MASK>(G.lv[l], local, red);
+  pool_body<T, VEC, CPT, HAS_MASK, MLP>(G.lv[l], local, red, pool_smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -496,7 +530,8 @@ __global__ __launch_bounds__(kBlock) void k_apply(const Group<FwdArgs> G) {
 // k_gate: k_chan + k_apply in ONE pass over x with the tile RESIDENT IN REGISTERS (MGACBAM_FWD_FUSE).
 //   workgroup = (sample b, tile of TX vectors = TP contiguous pixels) x ALL channels: thread (tx, ty) keeps channels
 //   ty, ty+TY, ... (kGateR of them) of its VEC pixels in registers -- 64 KB of x per workgroup, read from HBM once.
-//     1. issue the loads; meanwhile wait for ca of the sample from its role workgroup (gate_role: the shared MLP, once per sample)
+//     1. issue the loads; meanwhile wait for ca of the sample from its role workgroup (gate_role: the shared MLP, once per sample) --
+//        a level whose ca k_pool has formed (FwdArgs::pool_mlp) has no role workgroups and reads ca plainly
 //     2. per pixel max_c / mean_c of x*ca (LDS combine over the TY slices) -> planes, cidx to ctx (backward needs them anyway)
 //     3. publish the tile's plane rows; wait for the tiles whose rows the k x k window of this tile touches (in-launch
 //        hand-off, common.cuh).  Consumers only ever wait on tiles at most `span` tile-ids away and workgroups are
@@ -536,13 +571,21 @@ __device__ __forceinline__ void gate_body(const FwdArgs& A, const int bid, float
 
   float* s_ca = smem;
   float* work = s_ca + ((g.C + 3) & ~3);
-  bool bad;                                                    // a hand-off timed out: this tile's sa (hence y) is poisoned with NaN
-  {                                                            // ca of this sample: from its role workgroup (gate_role)
-    int* caflag = A.c.sync + static_cast<size_t>(g.B) * A.nflag + 4;
-    bad = handoff_wait(caflag, b, b, gen, caflag - 4, A.spin_limit);
+  bool bad = false;                                            // a hand-off timed out: this tile's sa (hence y) is poisoned with NaN
+  {
     const float* cab = A.c.ca + static_cast<size_t>(b) * g.C;
-    TRACE_MARK(A.trace, gid, 1);                               // ca flag seen
-    for (int c = tid; c < g.C; c += kBlock) s_ca[c] = ld_agent(cab + c);
+    if (A.pool_mlp) {                                          // ca of this sample: from k_pool, the previous launch -- nothing to wait for
+      TRACE_MARK(A.trace, gid, 1);
+      for (int c = tid; c < g.C; c += kBlock) s_ca[c] = cab[c];
+      // the sample's ca flag still counts the call (tile 0 stands in for the role workgroup): calls of either form alternate on one ctx
+      if (tile == 0 && tid == 0)
+        __hip_atomic_fetch_add(A.c.sync + static_cast<size_t>(g.B) * A.nflag + 4 + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {                                                   // ... or from its role workgroup (gate_role)
+      int* caflag = A.c.sync + static_cast<size_t>(g.B) * A.nflag + 4;
+      bad = handoff_wait(caflag, b, b, gen, caflag - 4, A.spin_limit);
+      TRACE_MARK(A.trace, gid, 1);                             // ca flag seen
+      for (int c = tid; c < g.C; c += kBlock) s_ca[c] = ld_agent(cab + c);
+    }
     __syncthreads();
   }
   TRACE_MARK(A.trace, gid, 2);                                 // ca in LDS
@@ -725,14 +768,14 @@ __device__ __forceinline__ void gate_body(const FwdArgs& A, const int bid, float
 // consumed, so the chain costs two memory latencies plus arithmetic.  Needs C % 4 == 0 and hidden % 4 == 0 (16-byte rows);
 // other shapes use the staged form (mlp_gate_to_lds).
 //   smem: [2C avg|mx][2h hidden]        ca is written with st_agent when `agent` (consumed inside the same launch), else plainly
-constexpr int kMlpW1 = 8;       // 16-byte vectors of W1 a lane holds per pass
-constexpr int kMlpW2 = 8;       // 16-byte vectors of W2 a thread holds per pass
-__device__ __forceinline__ bool mlp_stream_ok(const Geo& g) { return (g.C & 3) == 0 && (g.hidden & 3) == 0 && g.C <= 8 * 4 * kWave; }
+// (kMlpW1, kMlpW2 and the declaration with the default arguments: above pool_body, its other caller)
 
-// hidden layer: wave w owns hidden units w, w+4, ...; a lane holds CVL vectors of each of UP rows per pass
-template <int CVL>
+// hidden layer: wave w owns hidden units w, w+4, ...; a lane holds CVL vectors of each of UP rows per pass.  (UP only sets how many rows
+// are in flight together: every unit is summed on its own, in the same order whatever UP.)
+template <int CVL, bool LDA, int NW1>
 __device__ __forceinline__ void mlp_hidden(const FwdArgs& A, const int b, float* s_avg, float* s_mx, float* s_h) {
-  constexpr int UP = kMlpW1 / CVL;
+  constexpr int UP = NW1 > CVL ? NW1 / CVL : 1;
+  constexpr int CH = NW1 < CVL ? NW1 : CVL;                     // vectors of a row in flight together: the whole row, or NW1 of it at a time
   const Geo& g = A.g;
   const int tid = threadIdx.x, C = g.C, h = g.hidden, CV = C >> 2;
   const int wave = tid >> 6, lane = tid & 63;
@@ -740,44 +783,55 @@ __device__ __forceinline__ void mlp_hidden(const FwdArgs& A, const int b, float*
   const int nunit = h > wave ? (h - wave + 3) >> 2 : 0;        // units of this wave
   const int npass = (((h + 3) >> 2) + UP - 1) / UP;            // uniform over the workgroup
   for (int p = 0; p < npass; ++p) {
-    float4 wr[UP][CVL];
+    float da[UP], dm[UP];
 #pragma unroll
-    for (int uu = 0; uu < UP; ++uu) {
-      const int u = p * UP + uu, j = wave + 4 * u;
+    for (int uu = 0; uu < UP; ++uu) { da[uu] = 0.f; dm[uu] = 0.f; }
+#pragma unroll 1
+    for (int i0 = 0; i0 < CVL; i0 += CH) {                      // (one round unless NW1 < CVL; a unit's sum runs over i ascending either way)
+      float4 wr[UP][CH];
 #pragma unroll
-      for (int i = 0; i < CVL; ++i) {
-        const int cv = lane + kWave * i;
-        wr[uu][i] = (u < nunit && cv < CV) ? w1v[static_cast<size_t>(j) * CV + cv] : float4{0.f, 0.f, 0.f, 0.f};
+      for (int uu = 0; uu < UP; ++uu) {
+        const int u = p * UP + uu, j = wave + 4 * u;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+          const int cv = lane + kWave * (i0 + i);
+          wr[uu][i] = (u < nunit && cv < CV) ? w1v[static_cast<size_t>(j) * CV + cv] : float4{0.f, 0.f, 0.f, 0.f};
+        }
       }
-    }
-    if (p == 0) {                                               // the pooled descriptors, requested right behind the first W1 rows
-      for (int c = tid; c < C; c += kBlock) {
-        s_avg[c] = A.c.avg[static_cast<size_t>(b) * C + c];
-        s_mx[c] = A.c.mx[static_cast<size_t>(b) * C + c];
+      if (p == 0 && i0 == 0) {                                  // the pooled descriptors, requested right behind the first W1 rows
+        for (int c = tid; c < C; c += kBlock) {                 // LDA: written in THIS launch by other workgroups (pool_body's tail)
+          const float* pa = A.c.avg + static_cast<size_t>(b) * C + c;
+          const float* pm = A.c.mx + static_cast<size_t>(b) * C + c;
+          s_avg[c] = LDA ? ld_agent(pa) : *pa;
+          s_mx[c] = LDA ? ld_agent(pm) : *pm;
+        }
+        __syncthreads();
       }
-      __syncthreads();
+#pragma unroll
+      for (int uu = 0; uu < UP; ++uu) {
+        if (p * UP + uu < nunit) {                              // (uniform per wave)
+#pragma unroll
+          for (int i = 0; i < CH; ++i) {
+            const int cv = lane + kWave * (i0 + i);
+            if (cv < CV) {
+              const float4 w = wr[uu][i];
+              const float4 a4 = *reinterpret_cast<const float4*>(s_avg + 4 * cv), m4 = *reinterpret_cast<const float4*>(s_mx + 4 * cv);
+              da[uu] += w.x * a4.x + w.y * a4.y + w.z * a4.z + w.w * a4.w;
+              dm[uu] += w.x * m4.x + w.y * m4.y + w.z * m4.z + w.w * m4.w;
+            }
+          }
+        }
+      }
     }
 #pragma unroll
     for (int uu = 0; uu < UP; ++uu) {
       const int u = p * UP + uu;
-      if (u < nunit) {                                          // (uniform per wave)
-        float da = 0.f, dm = 0.f;
-#pragma unroll
-        for (int i = 0; i < CVL; ++i) {
-          const int cv = lane + kWave * i;
-          if (cv < CV) {
-            const float4 w = wr[uu][i];
-            const float4 a4 = *reinterpret_cast<const float4*>(s_avg + 4 * cv), m4 = *reinterpret_cast<const float4*>(s_mx + 4 * cv);
-            da += w.x * a4.x + w.y * a4.y + w.z * a4.z + w.w * a4.w;
-            dm += w.x * m4.x + w.y * m4.y + w.z * m4.z + w.w * m4.w;
-          }
-        }
-        da = wave_group_sum(da, kWave);
-        dm = wave_group_sum(dm, kWave);
+      if (u < nunit) {
+        const float sa = wave_group_sum(da[uu], kWave), sm = wave_group_sum(dm[uu], kWave);
         if (lane == 0) {
           const int j = wave + 4 * u;
           const float bj = A.p.b1[j];
-          const float ha = fmaxf(da + bj, 0.f), hm = fmaxf(dm + bj, 0.f);
+          const float ha = fmaxf(sa + bj, 0.f), hm = fmaxf(sm + bj, 0.f);
           s_h[j] = ha; s_h[h + j] = hm;
           A.c.h_avg[static_cast<size_t>(b) * h + j] = ha;
           A.c.h_mx[static_cast<size_t>(b) * h + j] = hm;
@@ -787,7 +841,7 @@ __device__ __forceinline__ void mlp_hidden(const FwdArgs& A, const int b, float*
   }
 }
 
-template <bool AGENT>
+template <bool AGENT, bool LDA, int NW1, int NW2>
 __device__ __forceinline__ void mlp_stream(const FwdArgs& A, const int b, float* smem) {
   const Geo& g = A.g;
   const int tid = threadIdx.x, C = g.C, h = g.hidden;
@@ -795,29 +849,29 @@ __device__ __forceinline__ void mlp_stream(const FwdArgs& A, const int b, float*
   float* s_mx = smem + C;
   float* s_h = smem + 2 * C;
   const int cvl = ((C >> 2) + kWave - 1) / kWave;              // vectors of a W1 row per lane: 1 (C <= 256), 2, 4, 8 (C <= 2048)
-  if (cvl <= 1) mlp_hidden<1>(A, b, s_avg, s_mx, s_h);
-  else if (cvl <= 2) mlp_hidden<2>(A, b, s_avg, s_mx, s_h);
-  else if (cvl <= 4) mlp_hidden<4>(A, b, s_avg, s_mx, s_h);
-  else mlp_hidden<8>(A, b, s_avg, s_mx, s_h);
+  if (cvl <= 1) mlp_hidden<1, LDA, NW1>(A, b, s_avg, s_mx, s_h);
+  else if (cvl <= 2) mlp_hidden<2, LDA, NW1>(A, b, s_avg, s_mx, s_h);
+  else if (cvl <= 4) mlp_hidden<4, LDA, NW1>(A, b, s_avg, s_mx, s_h);
+  else mlp_hidden<8, LDA, NW1>(A, b, s_avg, s_mx, s_h);
   // ---- output layer: thread = channel; its first W2 row is requested BEFORE the barrier that publishes the hidden activations -------
   const int HV = h >> 2;
   const float4* w2v = reinterpret_cast<const float4*>(A.p.w2);
-  float4 wr[kMlpW2];
+  float4 wr[NW2];
   {
     const int c = min(tid, C - 1);
 #pragma unroll
-    for (int q = 0; q < kMlpW2; ++q) wr[q] = q < HV ? w2v[static_cast<size_t>(c) * HV + q] : float4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < NW2; ++q) wr[q] = q < HV ? w2v[static_cast<size_t>(c) * HV + q] : float4{0.f, 0.f, 0.f, 0.f};
   }
   __syncthreads();
   for (int c = tid; c < C; c += kBlock) {
     float za = 0.f, zm = 0.f;
-    for (int v0 = 0; v0 < HV; v0 += kMlpW2) {
+    for (int v0 = 0; v0 < HV; v0 += NW2) {
       if (c != tid || v0 != 0) {
 #pragma unroll
-        for (int q = 0; q < kMlpW2; ++q) wr[q] = v0 + q < HV ? w2v[static_cast<size_t>(c) * HV + v0 + q] : float4{0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < NW2; ++q) wr[q] = v0 + q < HV ? w2v[static_cast<size_t>(c) * HV + v0 + q] : float4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
-      for (int q = 0; q < kMlpW2; ++q) {
+      for (int q = 0; q < NW2; ++q) {
         if (v0 + q < HV) {
           const float* ha = s_h + 4 * (v0 + q);
           const float* hm = ha + h;
@@ -877,8 +931,8 @@ __global__ __launch_bounds__(kBlock) void k_mlp(const Group<FwdArgs> G) {
 
 struct GateGroup {
   Group<FwdArgs> g;
-  int nrole;                     // role workgroups = sum of the levels' batch sizes; tile workgroup ids follow
-  int rstart[kGroupMax + 1];     // level l owns role ids [rstart[l], rstart[l+1])
+  int nrole;                     // role workgroups = sum of the batch sizes of the levels without pool_mlp; tile workgroup ids follow
+  int rstart[kGroupMax + 1];     // level l owns role ids [rstart[l], rstart[l+1]): none when k_pool formed its ca
 };
 static_assert(sizeof(GateGroup) <= kKernargMax, "a group is one launch's arguments");
 

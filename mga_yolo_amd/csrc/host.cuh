@@ -72,6 +72,7 @@ struct SyncLayout {
   size_t bflag, cflag;       // [B][nflag] k_bwd_reduce1 tile flags, [B][nflag] folded conv-tile flags
   size_t mbflag, mcflag;     // the same two of the merged launch
   size_t wflag, sflag;       // the merged launch's [B][nflag] dWsa-tile flags and [B][C] per-channel sweep flags
+  size_t arrive;             // [B][kArriveStride], word 0 of each: k_pool's arrival count of the sample (FwdArgs::pool_mlp), 0 between launches
   size_t len;
 };
 static SyncLayout sync_layout(int B, int C, size_t HW) {
@@ -80,7 +81,8 @@ static SyncLayout sync_layout(int B, int C, size_t HW) {
   const size_t per = static_cast<size_t>(B) * S.nflag;
   S.gate = 0; S.status = per; S.ca = S.status + 4; S.bflag = S.ca + B;
   S.cflag = S.bflag + per; S.mbflag = S.cflag + per; S.mcflag = S.mbflag + per; S.wflag = S.mcflag + per; S.sflag = S.wflag + per;
-  S.len = S.sflag + static_cast<size_t>(B) * C;
+  S.arrive = S.sflag + static_cast<size_t>(B) * C;           // appended: every older offset is where it was
+  S.len = S.arrive + static_cast<size_t>(B) * kArriveStride;
   return S;
 }
 
@@ -135,6 +137,8 @@ struct Knobs {
   int pool_tx, pool_cpt, chan_tx;   // MGACBAM_POOL_TX / _POOL_CPT / _CHAN_TX: launch-geometry overrides (choose_tune, group_cpt)
   int resident_wgs;        // MGACBAM_RESIDENT_WGS: override of the co-resident workgroup budget the hand-off eligibility is sized from
   int fault;               // MGACBAM_FAULT: fault injection for tests (args.cuh)
+  int pool_mlp;            // MGACBAM_POOL_MLP: 0 = k_pool never forms ca, unset = by the rule (pool_forms_ca), 2 = at every level whose shape
+                           // the tail takes, however small (tests)
   unsigned spin_limit;     // MGACBAM_SPIN_LIMIT
   long long* trace;        // MGACBAM_TRACE_PTR (-DMGACBAM_TRACE builds, tools/trace_gate.py)
 };
@@ -144,6 +148,7 @@ static Knobs read_knobs() {
   k.gate_narrow = env_int("MGACBAM_GATE_NARROW", 0);
   k.pool_tx = env_int("MGACBAM_POOL_TX", 0); k.pool_cpt = env_int("MGACBAM_POOL_CPT", 0); k.chan_tx = env_int("MGACBAM_CHAN_TX", 0);
   k.resident_wgs = env_int("MGACBAM_RESIDENT_WGS", 0); k.fault = env_int("MGACBAM_FAULT", 0);
+  k.pool_mlp = env_int("MGACBAM_POOL_MLP", 1);
   const int sl = env_int("MGACBAM_SPIN_LIMIT", 0);
   k.spin_limit = sl > 0 ? static_cast<unsigned>(sl) : (1u << 20);
   const char* tp = getenv("MGACBAM_TRACE_PTR");
@@ -228,6 +233,21 @@ static void gate_geometry(int C, int H, int W, int k, int VEC, Tune& t) {
   // takes 20 us for the first round; 60 % of the resident workgroups are in the chain at any time and HBM runs at 3 TB/s
   // (whether the 8*span + 1 workgroups a tile's wait spans are co-resident on THIS device is checked at dispatch: forward_group)
   if (TP >= kSyncPx && (TP >= W || knobs().gate_narrow) && lds <= 48 * 1024) { t.gate_tx = gtx; t.gate_rows = grows; t.gate_span = span; }
+}
+
+// k_pool forms ca itself -- the last workgroup of a sample to arrive runs the shared MLP (fwd.cuh: pool_body) -- at NCHW levels where
+// k_gate's first resident round would otherwise sit on the sample's ca flag: the streamed MLP takes the shape, C*hidden is small enough
+// that the forward never splits the MLP off (forward_group: k_mlp), the level can run k_gate, and x of one sample is >= 1 MiB.  The last
+// condition keeps the small levels of a pyramid out: a tail costs k_pool ~2.5 us (every level streams to the end of the launch, so the
+// tails run behind it), and the tiles of the small levels become resident in k_gate's second round, when ca is long there -- only the
+// level of the first round repays it (k_gate -6 us at config 2).  A rule of the LEVEL alone:
+// a ctx meets the level in calls of any composition, and the pool and the chan|apply stage calls must agree.  Fault injection keeps the
+// role workgroup it silences.
+static bool pool_forms_ca(const Geo& g, const Tune& t, bool nhwc, int dtype) {
+  const Knobs kn = knobs();
+  if (nhwc || kn.fault || kn.pool_mlp == 0) return false;
+  if (!mlp_stream_ok(g) || static_cast<long long>(g.C) * g.hidden >= 8192 || t.gate_tx <= 0) return false;
+  return kn.pool_mlp == 2 || static_cast<size_t>(g.C) * g.HW * (dtype == MGACBAM_F32 ? 4 : 2) >= (size_t(1) << 20);
 }
 
 static Tune choose_tune(int B, int C, int H, int W, int k) {
@@ -526,6 +546,7 @@ static size_t reduce1_smem(const Geo& g, int vec, int proj) {
   if (proj == 2) return (((3 * static_cast<size_t>(g.C) + 3) & ~static_cast<size_t>(3)) + 3 * 16 * kWave) * sizeof(float);
   return (((3 * static_cast<size_t>(g.C) + 3) & ~static_cast<size_t>(3)) + static_cast<size_t>(g.C) * kProjMax + 4 * kBlock * vec) * sizeof(float);
 }
+static size_t pool_mlp_smem(const Geo& g) { return (4 + 2 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }   // k_pool's tail: [last?, 3 pad][2C avg|mx][2h]
 static size_t mlp_smem(const Geo& g) { return (3 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }
 // their NHWC siblings (n: nhwc_geo of the level)
 static size_t nhwc_pool_smem(const Geo& g) { return 4 * static_cast<size_t>(g.C) * sizeof(float); }
