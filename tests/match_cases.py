@@ -8,7 +8,16 @@ Two kinds, both numpy.random.RandomState (a frozen stream) and arithmetic only, 
   by construction  coordinates on a 1/64 grid of a 64 x 64 image: the boxes, their IoUs and the answer are exact in fp32 and known: ANSWERS.
 
 tests/golden/match_<name>.npz (tools/gen_golden_match.py) holds the inputs, the seed the generator accepted, and what the reference's own
-validator gave on exactly these values; load() rebuilds the case from the seed and refuses inputs that differ from the stored ones."""
+validator gave on exactly these values; load() rebuilds the case from the seed and refuses inputs that differ from the stored ones.
+
+Which path of csrc/match.cuh runs where:
+  k_match's staging loop, a second chunk of 1024 rows   chunks (1082 rows, every image's on both sides of row 1024, best labels behind it: the carry
+                                                        of the rows met so far), dup_far (a label's twin at row 1030: the lower row wins across chunks)
+  k_match's detection loop, a second trip of 512        dets600 (counts 600, 513, 512, 257: a second trip of 88 rows with none in its upper half, of one
+                                                        row, none, and a first trip with one row in its upper half; owners decided between a
+                                                        detection below 512 and one at or above it)
+  k_match_append with five label workgroups             chunks through a plan (the GPU tests: the n word at 1024, 1025 and 1030)
+  status 1 from rows counted in the second chunk        chunks with m_cap one below an image's rows (the GPU tests)"""
 import os
 
 import numpy as np
@@ -34,9 +43,20 @@ CASES = {
     "iou1": dict(D=12, nc=2, counts=(12, 8), labels=(3, 4), hw=(64, 64), iouv=IOUV10[:1]),
     "iou16": dict(D=12, nc=2, counts=(12, 8), labels=(3, 4), hw=(64, 64), iouv=IOUV16),
     "wrongcls": dict(construct=True),
+    # 1082 label rows in two staging chunks; the images that do not exist hold 32 of them
+    "chunks": dict(D=48, nc=4, counts=(48, 33, 20, 7, 0, 48), labels=(200, 190, 180, 170, 160, 150), hw=(640, 640), grid=16,
+                   extra=[6, 9, 6, 7] * 8, shuffle=True),
+    # `wide` with up to 600 detections an image: two trips of the detection loop
+    "dets600": dict(D=600, nc=4, counts=(600, 513, 512, 257), labels=(40, 30, 12, 3), hw=(640, 640), grid=8, shuffle=True),
+    # `dup` with its twin labels in two staging chunks (parity=False as for `dup`: the reference's order of equal IoUs is an unstable sort's)
+    "dup_far": dict(construct=True, parity=False),
 }
 NAMES = list(CASES)
 PARITY = [n for n in NAMES if CASES[n].get("parity", True)]        # held to the reference's own answer
+TWINS = ("dup", "dup_far")                                         # a detection's two largest IoUs are equal by construction
+STAGE = 1024                                                       # label rows per staging chunk: kMatchStage * kBlock of csrc/match.cuh
+N_WORDS = (STAGE, STAGE + 1, STAGE + 6)                            # `chunks` under an n word on and inside its second chunk
+TRIP = 512                                                         # detections per trip of k_match's detection loop: 2 * kBlock
 
 
 def _px(boxes, size=64.0):
@@ -57,6 +77,10 @@ _CONSTRUCT = {
     # 928 / 1024 = 0.90625 with the label of class 0, 736 / 1280 = 0.575 with the label of its own class
     "wrongcls": dict(labels=[(0, 8, 8, 40, 40), (1, 8, 14, 40, 48)], dets=[(8, 8, 40, 37, 0.9, 1)]),
 }
+# dup's detection; the matched label at flat rows 3 and 1030, every other row a small box of an image that does not exist
+_FAR = (3, STAGE + 6)
+_CONSTRUCT["dup_far"] = dict(labels=[(0, 8, 8, 40, 40) if r in _FAR else (0, 1, 1, 9, 9) for r in range(_FAR[1] + 1)],
+                             batch_idx=[0 if r in _FAR else 7 for r in range(_FAR[1] + 1)], dets=_CONSTRUCT["dup"]["dets"])
 _T = lambda n: [i < n for i in range(10)]
 # tp rows and best_gt by construction (thresholds 0.5, 0.55, ..., 0.95)
 ANSWERS = {
@@ -64,6 +88,7 @@ ANSWERS = {
     "owned": dict(tp=[_T(9), _T(0)], best_gt=[0, 0]),
     "dup": dict(tp=[_T(4)], best_gt=[1]),
     "wrongcls": dict(tp=[_T(2)], best_gt=[1]),
+    "dup_far": dict(tp=[_T(4)], best_gt=[_FAR[0]]),
 }
 # the wrong rule each by-construction case fails (match_oracle.WRONG)
 BUILT_AGAINST = {"steal": "highest_iou_owns", "owned": "second_best_allowed", "wrongcls": "class_ignored"}
@@ -159,6 +184,21 @@ def built_for(name, c, o):
         best = o["best_iou"][..., None] >= c["iouv"][None, None, :].astype(np.float64)
         if not np.any(best & ~tp):
             why.append("no detection is refused because its label is owned")
+    if name in ("chunks", "dets600"):
+        best = o["best_iou"][..., None] >= c["iouv"][None, None, :].astype(np.float64)
+    if name == "chunks":
+        bi = c["batch_idx"]
+        if len(bi) <= STAGE or not all(np.any(bi[:STAGE] == b) and np.any(bi[STAGE:] == b) for b in range(len(c["count"]))):
+            why.append(f"an image without label rows on both sides of row {STAGE}")
+        if not np.any(o["best_gt"] >= STAGE):
+            why.append(f"no detection's best label lies at or behind row {STAGE}")
+        if not np.any(best & ~tp):
+            why.append("no detection is refused because its label is owned")
+    if name == "dets600":
+        if not tp[:, TRIP:].any():
+            why.append(f"no detection at or above {TRIP} is true")
+        if not np.any((best & ~tp)[:, TRIP:]):
+            why.append(f"no detection at or above {TRIP} is refused because a lower one owns its label")
     if name == "nword" and c["n"] is None:
         why.append("no n word")
     if name in ("iou1", "iou16") and not (tp.any() and not tp.all()):

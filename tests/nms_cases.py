@@ -10,7 +10,19 @@ Two kinds of features, both numpy.random.RandomState (a frozen stream) and arith
 
 tests/golden/nms_<name>.npz (tools/gen_golden_nms.py) holds the features of a small case whole; a larger one records the seed the generator
 accepted and the SHA-256 of the features, and load() refuses rebuilt features whose digest differs.  Either way it holds what the reference's
-own Detect._inference and non_max_suppression gave on exactly these values, from an fp32 and an fp64 run."""
+own Detect._inference and non_max_suppression gave on exactly these values, from an fp32 and an fp64 run -- for the cases of PARITY.  A case
+with parity=False (cut_ties, cut_ties_wide) is held to its construction and the oracle alone, and its record holds no reference lists.
+
+Which path of csrc/nms.cuh runs where:
+  nms_select in LDS            maxnms (distinct scores: the score word decides), cut_ties (the cut inside 86 equal scores: the four low passes)
+  nms_select in the workspace  cut_ties_wide (1280 candidates, their indices over two bytes of the low word), and the stored `wide` features at
+                               max_nms 1, 1023, 1024, 1025, 1100, 1343 (SELECT_CUTS; 1344 = n: no select)
+  nms_rounds in the workspace  wide (nc 1: by_class false), ml_wide (nc 80: by_class true, some 4500 candidates an image)
+  multi-label append           classes_ml (4 anchors, nc 3), ml_wide (a full wave and one of 20 lanes, 44 to 64 classes an anchor, unequal counts;
+                               cand_cap crossed inside an anchor's classes: the GPU tests' overflow run)
+  `pred` in fp16 / bf16        basic, classes, wide (PRED_HALF_CASES): in `wide` scores tie by the hundreds and the tie order decides the answer;
+                               wide cut at max_nms 700: in some images the 700th and 701st scores are equal, the select's low passes decide
+A plan replayed across the paths (long list, empty list, long list) is the GPU tests' own."""
 import hashlib
 import os
 
@@ -30,6 +42,11 @@ _OBJ2 = [(0, 1, 6.3, 9.1, 41.7, 50.2), (0, 0, 50.5, 20.2, 90.9, 45.1), (1, 0, 10
 _CLS = [(0, 0, 2, 2, (2, 2, 2, 2), {0: 3.0}), (0, 0, 2, 3, (3, 2, 1, 2), {1: 2.0}), (0, 0, 3, 2, (2, 3, 2, 1), {2: 1.0}),
         (0, 0, 5, 5, (1.5, 1.5, 1.5, 1.5), {0: 2.5, 2: 0.5})]
 _CHAIN = [(0, 0, 3, 2, (2.5,) * 4, {0: 3.0}), (0, 0, 3, 3, (2.5,) * 4, {0: 2.0}), (0, 0, 3, 4, (2.5,) * 4, {0: 1.0})]
+_TIE3 = (2.0, 1.0, 0.0)
+_CELL = (0.5,) * 4                             # a box that is exactly its anchor's cell
+_CUT = [(0, 0, y, x, _CELL, {0: _TIE3[(y + x) % 3]}) for y in range(16) for x in range(16)]
+_CUT_WIDE = [(0, 0, y, x, _CELL, {0: _TIE3[(y + x) % 3]}) for y in range(32) for x in range(32)] + \
+            [(1, 0, y, x, _CELL, {0: _TIE3[(y + 2 * x) % 3]}) for y in range(16) for x in range(16)]
 # trained-like: rows = (image, class, x1, y1, x2, y2[, dict(lg=, lsd=)]); by construction: puts = (level, image, y, x, (l, t, r, b) in cells, {class: logit})
 CASES = {
     "basic": dict(B=2, hw=(64, 64), nc=1, strides=S3, rows=_OBJ),
@@ -57,11 +74,32 @@ CASES = {
     # pairs the visit compares have an IoU of 0, or of some 0.2 across levels, and the guard on near-threshold pairs can hold at all
     "wide": dict(B=17, hw=(256, 256), nc=1, strides=S3, kw=dict(conf_thres=0.001), tight=True,
                  rows=[(0, 0, 12.3, 20.4, 44.6, 50.7), (5, 0, 170.2, 8.3, 220.7, 40.9), (16, 0, 140.6, 130.3, 170.2, 160.8), (16, 0, 8.9, 180.4, 40.3, 220.6)]),
+    # every level-0 anchor placed with its own cell as its box (every IoU 0), three scores in a diagonal pattern: the max_nms cut falls inside
+    # the second group of equal scores, so the select's four low passes, over the inverted candidate index, decide it -- in LDS.
+    # parity=False: the reference cuts behind an unstable argsort, so which of the equal scores it keeps is not defined; the case is held to
+    # its construction (ANSWERS) and the oracle, and its record holds no reference lists
+    "cut_ties": dict(B=1, hw=(128, 128), nc=1, strides=S3, puts=_CUT, kw=dict(max_nms=120, max_det=2000), parity=False),
+    # the same in the workspace: 1024 level-0 anchors and the 256 of level 1 (a level-1 cell holds four level-0 cells: IoU 0.25, nothing is
+    # suppressed), 1280 candidates whose indices spread over two bytes of the key's low word.  parity=False for the same reason
+    "cut_ties_wide": dict(B=1, hw=(256, 256), nc=1, strides=S3, puts=_CUT_WIDE, kw=dict(max_nms=700, max_det=2000), parity=False),
+    # multi-label at a trained-like class count: 84 anchors (a full wave and one of 20 lanes), 44 to 64 candidate classes each, some 4500
+    # candidates an image: the wave scan over unequal counts, the per-class append, by_class in the workspace, max_det reached
+    "ml_wide": dict(B=2, hw=(64, 64), nc=80, strides=S3, kw=dict(conf_thres=0.01, multi_label=True), tight=True,
+                    rows=[(0, 3, 6.3, 9.1, 41.7, 50.2), (0, 17, 30.5, 20.2, 60.9, 45.1), (1, 79, 10.4, 5.7, 52.6, 58.3), (1, 0, 40.3, 2.2, 62.1, 20.7)]),
     "lv1": dict(B=2, hw=(64, 96), nc=2, strides=(8,), rows=_OBJ2),
     "lv2": dict(B=2, hw=(64, 96), nc=2, strides=(8, 16), rows=_OBJ2),
     "lv4": dict(B=2, hw=(64, 96), nc=2, strides=(4, 8, 16, 32), rows=_OBJ2),
 }
-HALF_CASES = ("basic", "classes", "wide")
+NAMES = list(CASES)
+PARITY = [n for n in NAMES if CASES[n].get("parity", True)]        # held to the reference's own lists
+HALF_CASES = ("basic", "classes", "wide", "ml_wide")
+# the `pred` front end on an fp16 / bf16 prediction: (case, arguments that replace the case's).  The last: `wide` cut at max_nms 700 with
+# max_det out of reach, so that the select in the workspace cuts inside equal scores of trained-like values and every survivor is a kept row
+PRED_HALF_CASES = (("basic", {}), ("classes", {}), ("wide", {}), ("wide", dict(max_nms=700, max_det=1400)))
+PRED_HALF_IDS = ["basic", "classes", "wide", "wide_cut"]
+# the select on the stored `wide` features: its images 0 and 1 (1344 candidates each) at these max_nms, max_det above every count
+SELECT_CUTS = (1, 1023, 1024, 1025, 1100, 1343, 1344)
+SELECT_KW = dict(max_det=1400)
 # the kept anchors and their classes, by construction (anchor = y * 8 + x on level 0 of a 64^2 image)
 ANSWERS = {
     "chain": ([[26, 28]], [[0, 0]]),
@@ -75,7 +113,9 @@ ANSWERS = {
     "ties": ([[9, 51, 41, 45]], [[0] * 4]),
 }
 # what each deliberately wrong rule must get wrong (tests/test_nms_oracle.py; the same four mistakes were put into local builds of the kernels)
-MUTATIONS = {"chain": dict(kept_only=False), "classes": dict(compare_classes=False), "maxnms": dict(max_nms=1 << 30), "ties": dict(lowest_first=False)}
+MUTATIONS = {"chain": dict(kept_only=False), "classes": dict(compare_classes=False), "maxnms": dict(max_nms=1 << 30), "ties": dict(lowest_first=False),
+             "cut_ties": dict(lowest_first=False), "cut_ties_wide": dict(lowest_first=False)}
+TIE_ORDER = tuple(n for n, m in MUTATIONS.items() if m == dict(lowest_first=False))      # the cases whose answer the tie order decides
 
 
 def kw(name):
@@ -95,6 +135,20 @@ def anchors(name):
 def elements(name):
     c = CASES[name]
     return c["B"] * (64 + c["nc"]) * anchors(name)
+
+
+def _cut_answer(name):
+    """cut_ties, cut_ties_wide: nothing is suppressed and max_det is out of reach, so the kept rows are the first max_nms of the placed
+    anchors by (logit descending, anchor ascending), from the puts."""
+    a0 = np.cumsum([0] + [h * w for h, w in shapes(name)])
+    width = [w for _, w in shapes(name)]
+    rows = sorted((-lg[0], int(a0[l]) + y * width[l] + x) for l, _, y, x, _, lg in CASES[name]["puts"])
+    n = kw(name)["max_nms"]
+    assert n < len(rows) and rows[n - 1][0] == rows[n][0], "the cut does not fall inside a group of equal scores"
+    return [[a for _, a in rows[:n]]], [[0] * n]
+
+
+ANSWERS.update({n: _cut_answer(n) for n in ("cut_ties", "cut_ties_wide")})
 
 
 def build_feats(name, seed):
@@ -182,10 +236,13 @@ def load(name):
     for key in DEFAULTS:
         assert float(c[key]) == float(k[key]), f"{name}: {key} differs from the record"
     B = CASES[name]["B"]
+    c.update(name=name, B=B, feats=feats, kw=k)
+    if name not in PARITY:
+        assert "ref_count" not in c, f"{name}: a case without parity holds no reference lists"
+        return c
     cnt = c["ref_count"]
     off = np.concatenate(([0], np.cumsum(cnt)))
-    c.update(name=name, B=B, feats=feats, kw=k,
-             ref32=[c["ref_dets_f32"][off[b]:off[b + 1]] for b in range(B)], ref64=[c["ref_dets_f64"][off[b]:off[b + 1]] for b in range(B)],
+    c.update(ref32=[c["ref_dets_f32"][off[b]:off[b + 1]] for b in range(B)], ref64=[c["ref_dets_f64"][off[b]:off[b + 1]] for b in range(B)],
              ref_keep=[c["ref_keep_all"][off[b]:off[b + 1]] for b in range(B)])
     return c
 
@@ -210,6 +267,29 @@ def oracle(name, dtype=None, front="maps"):
     return _CACHE[key]
 
 
+def select_case(max_nms):
+    """The select on stored features: images 0 and 1 of `wide`, max_det above every count, the given max_nms -> (feats, arguments, the
+    oracle's answer under them), computed once and shared."""
+    key = ("select", max_nms)
+    if key not in _CACHE:
+        feats = [f[:2].contiguous() for f in load("wide")["feats"]]
+        k = dict(kw("wide"), max_nms=max_nms, **SELECT_KW)
+        _CACHE[key] = (feats, k, O.oracle(feats=[f.numpy() for f in feats], **k))
+    return _CACHE[key]
+
+
+def pred_half(name, dtype, lowest_first=True, **over):
+    """The reference-style decoded prediction of the case's fp32 features rounded to fp16 / bf16 -> (the rounded prediction, the arguments
+    without strides, the oracle's answer on its upcast values), computed once and shared.  over: arguments that replace the case's."""
+    key = ("pred_half", name, dtype, lowest_first, tuple(sorted(over.items())))
+    if key not in _CACHE:
+        k = dict(kw(name), **over)
+        strides = k.pop("strides")
+        pred = ref_decode(load(name)["feats"], strides, k["nc"]).to(dtype)
+        _CACHE[key] = (pred, k, O.oracle(pred=pred.float().numpy(), lowest_first=lowest_first, **k))
+    return _CACHE[key]
+
+
 def built_for(name, feats):
     """What the case was built to hold, beyond its ANSWERS; returns the reasons it does not (empty: it does)."""
     why = []
@@ -229,6 +309,24 @@ def built_for(name, feats):
             why.append("not every anchor is a candidate")
         if not (o["count"] >= 2).all():
             why.append(f"counts {o['count'].tolist()}")
+    if name in ("cut_ties", "cut_ties_wide"):
+        free = O.oracle(feats=np_feats, **dict(k, max_nms=1 << 30))
+        placed = len(CASES[name]["puts"])
+        if o["n_cand"] != [placed] or (placed > LDS) != (name == "cut_ties_wide"):
+            why.append(f"{o['n_cand']} candidates of {placed} placed anchors")
+        if o["count"].tolist() != [k["max_nms"]] or free["count"].tolist() != [placed]:
+            why.append(f"counts {o['count'].tolist()} with max_nms, {free['count'].tolist()} without")
+    if name == "ml_wide":
+        _, prob, _ = O.decode(np_feats, k["strides"], k["nc"])
+        per = (prob > k["conf_thres"]).sum(2)                       # (B, A): an anchor's candidates, a lane's count in k_nms_cand's scan
+        if not all(n > LDS for n in o["n_cand"]):
+            why.append(f"{o['n_cand']} candidates: not past {LDS} in every image")
+        if anchors(name) % 64 == 0 or not all(len(set(per[b, w:w + 64].tolist())) >= 2 for b in range(per.shape[0]) for w in range(0, per.shape[1], 64)):
+            why.append("a wave whose lanes all have the same count, or no partly live wave")
+        if not (o["count"] == k["max_det"]).all():
+            why.append(f"counts {o['count'].tolist()}: max_det is not reached")
+        if not all(len(set(o["dets"][b, :o["count"][b], 5].tolist())) >= 2 for b in range(per.shape[0])):
+            why.append("kept rows of one class only")
     if name in ("lv1", "lv2", "lv4"):
         a0 = np.cumsum([0] + [h * w for h, w in shapes(name)])
         kept = o["keep"][o["keep"] >= 0]

@@ -2,7 +2,7 @@
 tests/match_cases.py.  tp and best_gt are exactly the oracle's (which, on the cases of MC.PARITY, is the reference validator's own stored
 answer); best_iou lies within K eps_fp32 term of the fp64 oracle, K = twice the largest ratio of the reference's own fp32 box_iou over the cases
 (tests/golden/match_ratios.json: 0.61, so K = 1.22), not below 1.  Then the plan: fed by a DetPostPlan inside one captured graph, its status
-words, and its accumulation."""
+words, and its accumulation.  tests/match_cases.py says which case runs which path of the kernels."""
 import json
 import os
 
@@ -162,6 +162,50 @@ def test_status_1_an_image_over_m_cap():
             assert np.array_equal(tp[b] != 0, o["tp"][b]) and np.array_equal(gt[b], o["best_gt"][b])
 
 
+def test_the_n_word_inside_the_second_staging_chunk():
+    """`chunks` through a plan of five label workgroups with the word on the chunk boundary, one behind it and six behind it: the answer and
+    the accumulated rows are those of the rows before the word"""
+    from mga_yolo_amd.detmatch import host_stats
+    c, _, _ = _case("chunks")
+    assert len(c["batch_idx"]) > 4 * 256 and c["n"] is None
+    plan, total, _ = _plan(c)
+    B = len(c["count"])
+    for n in MC.N_WORDS:
+        cut = dict(c, n=n)
+        plan.reset()
+        plan.n.fill_(n)
+        plan.run()
+        plan.check_status()
+        _check(f"chunks, n = {n}", plan.tp, plan.best_iou, plan.best_gt, MC.oracle("chunks", cut))
+        n_live = int((c["batch_idx"][:n] < B).sum())
+        assert plan.state.tolist() == [total, n_live, B, 0]
+        got, want = plan.stats(), host_stats([MC.tensors(MC.live(cut))], imgsz=c["hw"], iouv=c["iouv"])
+        assert got["seen"] == want["seen"] == B and got["target_cls"].shape == (n_live,)
+        for k in ("tp", "conf", "pred_cls", "target_cls", "target_img"):
+            assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), (n, k)
+
+
+def test_status_1_decided_by_rows_of_the_second_staging_chunk():
+    c, _, o = _case("chunks")
+    B = len(c["count"])
+    per = np.bincount(c["batch_idx"][c["batch_idx"] < B].astype(int), minlength=B)
+    b = int(np.argmax(per))
+    m_cap = int(per[b]) - 1
+    assert (np.delete(per, b) <= m_cap).all() and int((c["batch_idx"][:MC.STAGE] == b).sum()) <= m_cap    # the first chunk alone fits
+    plan, _, _ = _plan(c, m_cap=m_cap)
+    plan.run()
+    assert plan.status.item() == 1 and plan.state.tolist() == [0, 0, 0, 0]
+    with pytest.raises(RuntimeError, match="m_cap"):
+        plan.check_status()
+    tp, iou, gt = plan.tp.cpu().numpy(), plan.best_iou.cpu().numpy(), plan.best_gt.cpu().numpy()
+    for i in range(B):
+        if i == b:
+            assert not tp[i].any() and np.isnan(iou[i]).all() and (gt[i] == -1).all()
+        else:
+            assert np.array_equal(tp[i] != 0, o["tp"][i]) and np.array_equal(gt[i], o["best_gt"][i])
+            assert O.ratio(iou[i], o["best_iou"][i], o["term"][i]) <= K
+
+
 def test_status_2_rows_cap_one_short_appends_nothing():
     c, _, o = _case("basic")
     _, total, n_live = _plan(c, acc=False)
@@ -184,7 +228,7 @@ def test_status_2_rows_cap_one_short_appends_nothing():
     assert s["tp"].shape == (2 * total, 10) and np.array_equal(s["tp"][:total], s["tp"][total:]) and s["target_cls"].shape == (2 * n_live,)
 
 
-@pytest.mark.parametrize("name", ["basic", "wide", "labels256"])
+@pytest.mark.parametrize("name", ["basic", "wide", "labels256", "chunks", "dets600"])
 def test_two_runs_give_the_same_bytes(name):
     c, _, _ = _case(name)
     outs = []

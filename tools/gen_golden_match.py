@@ -11,9 +11,10 @@ the rows before its n word.  With single_cls the labels' classes are zeroed for 
 
 A seed is accepted only if
   - for every class-matched pair the fp64 IoU is farther than 1e-4 from every threshold;
-  - except in the `dup` case, a detection's two largest class-matched IoUs differ by more than 1e-4 (match_oracle.oracle's guards);
+  - except in the cases of match_cases.TWINS (`dup`, `dup_far`), a detection's two largest class-matched IoUs differ by more than 1e-4 (match_oracle.oracle's guards);
   - the case holds what it was built for (match_cases.built_for, ANSWERS);
-  - the reference's answer equals the oracle's, under the rule and under the literal procedure (`dup` apart: construction only).
+  - the reference's answer equals the oracle's, under the rule and under the literal procedure (the cases with parity=False apart:
+    construction only).
 match_ratios.json: per case the largest |reference fp32 box_iou of a detection's best pair - fp64 oracle| / (eps_fp32 * term), the term from
 the oracle -- the measurement behind the GPU tests' bar."""
 import argparse
@@ -82,7 +83,7 @@ def main():
         for seed in range(100, 140):
             c = MC.build(name, seed)
             o = MC.oracle(name, c)
-            why = [g for g in o["guards"] if not (name == "dup" and "two largest" in g)]
+            why = [g for g in o["guards"] if not (name in MC.TWINS and "two largest" in g)]
             why += MC.built_for(name, c, o)
             B, D = c["dets"].shape[:2]
             T = len(c["iouv"])

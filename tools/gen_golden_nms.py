@@ -14,7 +14,9 @@ tests/nms_oracle.py and by the cases whose answer is known by construction (test
 
 A seed is accepted only if
   - the reference's fp32 run, its fp64 run and the oracle give the same kept anchors and classes in the same order, under both of the
-    oracle's tie orders (the `ties` case apart, where the other order must differ);
+    oracle's tie orders (the `ties` case apart, where the other order must differ).  A case with parity=False (nms_cases.CASES: the cut of
+    max_nms falls inside a group of equal scores, which the reference orders with an unstable argsort) is held to its construction and the
+    oracle instead: the reference decodes it, nothing of its lists is compared or stored, and it has no entry in nms_ratios.json;
   - no candidate probability lies within 1e-5 relative of conf_thres, no compared pair's IoU within 1e-4 of iou_thres, with the class
     offset and without it (nms_oracle.guards), on the fp32 features and on their fp16- and bf16-rounded values;
   - the case holds what it was built for (nms_cases.built_for, ANSWERS).
@@ -109,6 +111,7 @@ def main():
         if args.only and name not in args.only:
             continue
         k = NC.kw(name)
+        parity = name in NC.PARITY
         for seed in range(100, 140):
             feats = NC.build_feats(name, seed)
             np_feats = [f.numpy() for f in feats]
@@ -119,9 +122,9 @@ def main():
             if not why:
                 pred32, r32, i32 = run_reference(torch, Detect, ref_nms, feats, k, torch.float32)
                 pred64, r64, i64 = run_reference(torch, Detect, ref_nms, feats, k, torch.float64)
-                if not (same_set(lo, r32, i32) and same_set(lo, r64, i64)):
+                if parity and not (same_set(lo, r32, i32) and same_set(lo, r64, i64)):
                     why.append("the reference's runs and the oracle keep different rows")
-                if (name == "ties") == same_set(hi, r64, i64):
+                if parity and (name == "ties") == same_set(hi, r64, i64):
                     why.append("the other tie order: " + ("the same rows" if name == "ties" else "different rows"))
                 if not torch.allclose(NC.ref_decode(feats, k["strides"], k["nc"]), pred32, rtol=1e-5, atol=1e-4):
                     why.append("nms_cases.ref_decode is not the reference's decode")      # (the same ops but for the DFL's sum, a conv there)
@@ -130,8 +133,11 @@ def main():
                 why = NC.built_for(name, feats)
             if not why and name in NC.ANSWERS:
                 ka, kc = NC.ANSWERS[name]
-                if [a.tolist() for a in i64] != ka or [r[:, 5].astype(int).tolist() for r in r64] != kc:
+                if parity and ([a.tolist() for a in i64] != ka or [r[:, 5].astype(int).tolist() for r in r64] != kc):
                     why.append(f"the answer by construction is {ka}, the reference kept {[a.tolist() for a in i64]}")
+                got = [lo["keep"][b, :lo["count"][b]].tolist() for b in range(spec["B"])]
+                if got != ka or [lo["dets"][b, :lo["count"][b], 5].astype(int).tolist() for b in range(spec["B"])] != kc:
+                    why.append(f"the answer by construction is {ka}, the oracle kept {got}")
             if not why:
                 break
             print(f"{name}: seed {seed} rejected: {'; '.join(why)}")
@@ -139,6 +145,17 @@ def main():
                 raise SystemExit(f"{name}: a case by construction does not depend on the seed")
         else:
             raise SystemExit(f"{name}: no seed passed the guards")
+        rec = dict(k, strides=np.array(k["strides"]), seed=seed)
+        if NC.elements(name) <= NC.STORE_WHOLE:
+            for l, f in enumerate(np_feats):
+                rec[f"feat{l}"] = f
+        else:
+            rec["sha256"] = NC.digest(feats)
+        if not parity:
+            np.savez_compressed(NC.path(name), **rec)
+            ratios.pop(name, None)
+            print(f"{name}: no parity, {os.path.getsize(NC.path(name)) / 1024:.0f} KB, counts {lo['count'].tolist()}, candidates {lo['n_cand']}")
+            continue
         B = spec["B"]
         r = 0.0
         for b in range(B):
@@ -152,13 +169,8 @@ def main():
             if n:
                 assert O.ratio(lo["dets"][b, :n, 4], r64[b][:, 4], lo["terms"][b, :n, 4]) < 1e-6, f"{name}: the oracle is not the reference"
                 assert O.ratio(lo["dets"][b, :n, :4], r64[b][:, :4], lo["terms"][b, :n, :4]) <= 0.5, f"{name}: the oracle is not the reference"
-        rec = dict(k, strides=np.array(k["strides"]), seed=seed, ratio=r, ref_count=np.array([x.shape[0] for x in r64], dtype=np.int64),
+        rec.update(ratio=r, ref_count=np.array([x.shape[0] for x in r64], dtype=np.int64),
                    ref_dets_f32=np.concatenate(r32).astype(np.float32), ref_dets_f64=np.concatenate(r64), ref_keep_all=np.concatenate(i64))
-        if NC.elements(name) <= NC.STORE_WHOLE:
-            for l, f in enumerate(np_feats):
-                rec[f"feat{l}"] = f
-        else:
-            rec["sha256"] = NC.digest(feats)
         np.savez_compressed(NC.path(name), **rec)
         ratios[name] = r
         print(f"{name}: seed {seed}, {os.path.getsize(NC.path(name)) / 1024:.0f} KB, counts {rec['ref_count'].tolist()}, candidates {lo['n_cand']}, ratio {r:.3f}")
