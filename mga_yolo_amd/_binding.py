@@ -278,3 +278,21 @@ def fill_match(D: _lib.MatchDesc, dets, count, batch_idx, cls, bboxes, n, m_cap:
     D.tgt_cls, D.tgt_img, D.state = _ptr(tgt_cls), _ptr(tgt_img), _ptr(state)
     D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
     D.reserved = 0
+
+
+# ---- the validator's confusion matrix (include/ext/mgaconfusion.h)
+def fill_confusion(D: _lib.ConfusionDesc, dets, count, batch_idx, cls, bboxes, n, m_cap: int, nc: int, flags: int, img_w: float, img_h: float,
+                   conf_thres: float, iou_thres: float, det_out, lab_out, cm, acc, status, ws=None) -> None:
+    """dets, count and the labels as fill_match takes them; n: the int32 device word of live label rows or None (= n_cap); flags:
+    _lib.CM_SINGLE_CLS; conf_thres: what a counted detection's confidence exceeds (after detconfusion.reference_conf); det_out int32
+    (B, max_det), lab_out int32 (n_cap), cm int32 (nc + 1, nc + 1) and status int32 (1) are written; acc: the run-long int64
+    (nc + 1, nc + 1) matrix or None; ws: uint8, _lib.confusion_ws_bytes of the filled struct (fill once without it to ask, then again with it)."""
+    D.dets, D.count = dets.data_ptr(), count.data_ptr()
+    has = batch_idx.shape[0] > 0
+    D.batch_idx, D.cls, D.bboxes, D.lab_out = (batch_idx.data_ptr(), cls.data_ptr(), bboxes.data_ptr(), lab_out.data_ptr()) if has else (None,) * 4
+    D.n = _ptr(n)
+    D.B, D.max_det, D.n_cap, D.m_cap, D.nc, D.flags = dets.shape[0], dets.shape[1], batch_idx.shape[0], int(m_cap), int(nc), int(flags)
+    D.img_w, D.img_h, D.conf_thres, D.iou_thres = float(img_w), float(img_h), float(conf_thres), float(iou_thres)
+    D.det_out, D.cm, D.acc, D.status = det_out.data_ptr(), cm.data_ptr(), _ptr(acc), status.data_ptr()
+    D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+    D.reserved = 0

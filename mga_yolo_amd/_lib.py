@@ -227,6 +227,19 @@ class MatchDesc(C.Structure):                    # mgamatch_desc_t
                 ("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("reserved", C.c_int32)]
 
 
+# the validator's confusion matrix (include/ext/mgaconfusion.h: the third stage behind the post-process and the matching, METRIC_HEADERS below)
+CM_MAX_NC, CM_SINGLE_CLS = 119, 1
+
+
+class ConfusionDesc(C.Structure):                # mgacm_desc_t
+    _fields_ = [("dets", C.c_void_p), ("count", C.c_void_p), ("batch_idx", C.c_void_p), ("cls", C.c_void_p), ("bboxes", C.c_void_p),
+                ("n", C.c_void_p), ("B", C.c_int32), ("max_det", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32),
+                ("nc", C.c_int32), ("flags", C.c_int32),
+                ("img_w", C.c_float), ("img_h", C.c_float), ("conf_thres", C.c_float), ("iou_thres", C.c_float),
+                ("det_out", C.c_void_p), ("lab_out", C.c_void_p), ("cm", C.c_void_p), ("acc", C.c_void_p), ("status", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("reserved", C.c_int32)]
+
+
 class Header(NamedTuple):
     """What one file under include/ declares and this module mirrors (tests/test_abi_headers.py holds each record against its header)."""
     symbols: dict        # function -> (restype, argtypes)
@@ -361,12 +374,24 @@ EXT_HEADERS = {
         structs=dict(mgamatch_desc=MatchDesc),
         constants=dict(MGAMATCH_MAX_IOU=MATCH_MAX_IOU, MGAMATCH_SINGLE_CLS=MATCH_SINGLE_CLS)),
 }
-ALL_HEADERS = {**HEADERS, **EXT_HEADERS}
+# the headers of the validation metrics behind the matching, keyed and bound the same way (tests/test_abi_confusion.py)
+METRIC_HEADERS = {
+    "ext/mgaconfusion.h": Header(
+        symbols={
+            "mgacm_ws_bytes": (C.c_size_t, [C.POINTER(ConfusionDesc)]),
+            "mgacm_run": (_i, [C.POINTER(ConfusionDesc), C.c_void_p]),
+        },
+        structs=dict(mgacm_desc=ConfusionDesc),
+        constants=dict(MGACM_MAX_NC=CM_MAX_NC, MGACM_SINGLE_CLS=CM_SINGLE_CLS)),
+}
+_TABLES = dict(HEADERS=HEADERS, EXT_HEADERS=EXT_HEADERS, METRIC_HEADERS=METRIC_HEADERS)
+ALL_HEADERS = {**HEADERS, **EXT_HEADERS, **METRIC_HEADERS}
 _bound = [name for h in ALL_HEADERS.values() for name in h.symbols]
-if set(HEADERS) & set(EXT_HEADERS):
-    raise ImportError(f"_lib.HEADERS and _lib.EXT_HEADERS both hold a record for {sorted(set(HEADERS) & set(EXT_HEADERS))}")
+if len(ALL_HEADERS) != sum(len(t) for t in _TABLES.values()):
+    _keys = [k for t in _TABLES.values() for k in t]
+    raise ImportError(f"_lib.{', _lib.'.join(_TABLES)}: two tables hold a record for {sorted(k for k in set(_keys) if _keys.count(k) > 1)}")
 if len(_bound) != len(set(_bound)):
-    raise ImportError(f"_lib.HEADERS and _lib.EXT_HEADERS bind a symbol in two records: {sorted(n for n in set(_bound) if _bound.count(n) > 1)}")
+    raise ImportError(f"_lib.{', _lib.'.join(_TABLES)} bind a symbol in two records: {sorted(n for n in set(_bound) if _bound.count(n) > 1)}")
 
 _lib = None
 _lock = threading.Lock()
@@ -520,6 +545,11 @@ def nms_ws_bytes(desc) -> int:
 def match_ws_bytes(desc) -> int:
     """Workspace of a detection-matching call."""
     return _table_size("mgamatch_ws_bytes", E_ARG, C.byref(desc))
+
+
+def confusion_ws_bytes(desc) -> int:
+    """Workspace of a confusion-matrix call."""
+    return _table_size("mgacm_ws_bytes", E_ARG, C.byref(desc))
 
 
 ARRIVE_STRIDE = 64     # int32 words between the arrival words of two samples (csrc/args.cuh: kArriveStride)

@@ -33,7 +33,8 @@ BASE_FLAGS = ["-O2", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wno-pass
 INCLUDE = os.path.join(ROOT, "include")
 # extra flags per translation unit.  api_match.hip: include/ext/mgamatch.h names "mgatargets.h", which lies one directory above it; its IoU
 # is the reference's fp32 expression operation by operation, so no product may be contracted into a fused multiply-add
-UNIT_FLAGS: dict = {"api_match.hip": ["-I", INCLUDE, "-ffp-contract=off"]}
+# api_confusion.hip: the same for include/ext/mgaconfusion.h, which shares that IoU (csrc/match_common.cuh)
+UNIT_FLAGS: dict = {"api_match.hip": ["-I", INCLUDE, "-ffp-contract=off"], "api_confusion.hip": ["-I", INCLUDE, "-ffp-contract=off"]}
 
 
 def sources():

@@ -11,7 +11,9 @@ Device tensors go through `mgamatch_run`: two launches, fixed-size outputs, no h
 sit inside a captured graph behind the post-process (`DetMatchPlan` fed by a `DetPostPlan`).  Host tensors take `_host_match`, the same rule
 stated in torch ops.
 
-Not built: the confusion matrix on the device, `ap_per_class`, the scipy assignment branch of `match_predictions`, rotated boxes, and the
+The confusion matrix is the third stage, in a module of its own (detconfusion.py, include/ext/mgaconfusion.h).
+
+Not built: `ap_per_class`, the scipy assignment branch of `match_predictions`, rotated boxes, and the
 mask and pose matrices `tp_m` / `tp_p`.
 """
 from __future__ import annotations
@@ -305,6 +307,7 @@ def host_stats(batches, *, imgsz, iouv=None, single_cls: bool = False) -> Dict[s
 # ---------------------------------------------------------------------------------------------------------------------------
 _ORIGINALS: dict = {}          # DetectionValidator class -> the update_metrics install(match=True) replaced on it (install._install_match)
 _REPLACED = ("_process_batch", "_prepare_batch", "match_predictions")      # what the replacement stands in for and never calls
+_CONFUSION_ON = False          # install(match=True, confusion=True): update_metrics also forms the batch's confusion matrix on the device
 
 
 def _reference_s(self):
@@ -320,7 +323,11 @@ def update_metrics(self, preds, batch) -> None:
     and ONE read-back: the prediction list is padded on the device, the matching runs once with m_cap at its limit (nothing is read to size
     it), tp / conf / cls, the labels and the status word come back in one copy, and the images are walked on the host, feeding
     `self.metrics.update_stats` the per-image dicts the reference builds.  The confusion matrix, pred_to_json and save_one_txt still run per
-    image under the reference's conditions.  `_prepare_pred` runs first, so with args.single_cls the predictions' classes are zeroed and
+    image under the reference's conditions -- but the confusion matrix where install(match=True, confusion=True) set the switch, args.plots
+    is set, the detections are on the GPU and the validator's ConfusionMatrix is the detection task's, saves no matches (visualize) and has at
+    most 119 classes: then one confusion call runs on the same padded batch, its matrix rides in the same read-back and is added to
+    `self.confusion_matrix.matrix`, and no per-image process_batch runs (a non-zero status of that call -- a class outside 0 .. nc - 1 --
+    leaves the batch to the per-image calls).  `_prepare_pred` runs first, so with args.single_cls the predictions' classes are zeroed and
     compared with the labels' as the reference compares them.
     What it does not cover goes to the reference's own method, the one install() replaced: a validator whose class overrides
     `_process_batch`, `_prepare_batch` or `match_predictions` (the segmentation, pose, OBB and YOLOE validators: masks, keypoints, rotated
@@ -348,6 +355,10 @@ def update_metrics(self, preds, batch) -> None:
     bi, lc, lx = _labels(batch["batch_idx"], batch["cls"], batch["bboxes"], dev)
     niou = int(self.iouv.numel())
     imgsz = tuple(batch["img"].shape[2:])
+    cmx = getattr(self, "confusion_matrix", None) if _CONFUSION_ON and self.args.plots and dets.is_cuda else None
+    if cmx is not None and not (getattr(cmx, "task", None) == "detect" and cmx.matches is None and 1 <= cmx.nc <= _lib.CM_MAX_NC):
+        cmx = None
+    extra = []
     if dets.is_cuda:
         img_w, img_h = _img_wh(imgsz)
         thr = getattr(self, "_mga_iouv", None)                     # the validator's thresholds are read from the device once, not per batch
@@ -356,15 +367,26 @@ def update_metrics(self, preds, batch) -> None:
         st = _MatchState(dets, count, bi, lc, lx, None, _lib.DET_MAX_GT, img_w, img_h, thr, False)
         st.run(dev)
         tp, status = st.tp, st.status.float()
+        if cmx is not None:
+            from .detconfusion import _ConfusionState, reference_conf
+            ct = _ConfusionState(dets, count, bi, lc, lx, None, _lib.DET_MAX_GT, cmx.nc, img_w, img_h, reference_conf(self.args.conf), 0.45, False)
+            ct.run(dev)
+            extra = [ct.status.float(), ct.cm.reshape(-1).float()]             # a batch's counts are far below 2^24: exact in fp32
     else:
         tp, _, _ = match_detections(dets, count, bi, lc, lx, imgsz=imgsz, iouv=self.iouv)
         status = torch.zeros(1)
-    packed = torch.cat((status, tp.reshape(-1).float(), dets[..., 4:6].reshape(-1), bi, lc)).cpu().numpy()     # the one read-back
+    packed = torch.cat((status, tp.reshape(-1).float(), dets[..., 4:6].reshape(-1), bi, lc, *extra)).cpu().numpy()     # the one read-back
     if packed[0] != 0:                                             # an image over the limit: nothing was counted yet, and _prepare_pred is idempotent
         if original is None:
             raise NotImplementedError(f"update_metrics: an image has more than {_lib.DET_MAX_GT} label rows")
         return original(self, preds, batch)
     packed = packed[1:]
+    cm_h = None
+    if extra:
+        cells = (cmx.nc + 1) ** 2
+        if packed[-cells - 1] == 0:                                # its status; otherwise the per-image calls below take the batch
+            cm_h = packed[-cells:].reshape(cmx.nc + 1, cmx.nc + 1)
+        packed = packed[:-cells - 1]
     n_tp = B * D * niou
     tp_h = packed[:n_tp].reshape(B, D, niou) != 0
     cc_h = packed[n_tp:n_tp + 2 * B * D].reshape(B, D, 2)
@@ -384,7 +406,7 @@ def update_metrics(self, preds, batch) -> None:
             "pred_cls": np.zeros(0) if no_pred else cc_h[si, :k, 1].copy(),
         })
         pbatch = self._prepare_batch(si, batch) if need_batch else None
-        if self.args.plots:
+        if self.args.plots and cm_h is None:
             self.confusion_matrix.process_batch(predn, pbatch, conf=self.args.conf)
             if self.args.visualize:
                 self.confusion_matrix.plot_matches(batch["img"][si], pbatch["im_file"], self.save_dir)
@@ -394,3 +416,5 @@ def update_metrics(self, preds, batch) -> None:
             self.pred_to_json(predn, pbatch)
         if self.args.save_txt:
             self.save_one_txt(predn, self.args.save_conf, pbatch["ori_shape"], self.save_dir / "labels" / f"{Path(pbatch['im_file']).stem}.txt")
+    if cm_h is not None:
+        self.confusion_matrix.matrix += cm_h

@@ -44,12 +44,16 @@ def _is_reference_module(name: str) -> bool:
     return any(name == p or name.startswith(p + ".") for p in _PREFIXES) and not name.startswith("mga_yolo_amd")
 
 
-def install(strict: bool = False, nms: bool = False, match: bool = False) -> List[str]:
+def install(strict: bool = False, nms: bool = False, match: bool = False, confusion: bool = False) -> List[str]:
     """Rebind the block classes in every loaded reference module that exports them.  Returns the module names patched.
     ``strict=True`` raises unless the module whose ``parse_model`` builds ``MGAModel`` (the one providing
     ``mga_yolo.model.model.DetectionModel``; ``ultralytics.nn.tasks`` when mga_yolo is absent) was patched.
     ``nms=True`` also rebinds ``non_max_suppression`` in the reference's ``ultralytics.utils.ops`` modules (see ``_install_nms``),
-    ``match=True`` ``DetectionValidator.update_metrics`` in its ``ultralytics.models.yolo.detect.val`` modules (see ``_install_match``)."""
+    ``match=True`` ``DetectionValidator.update_metrics`` in its ``ultralytics.models.yolo.detect.val`` modules (see ``_install_match``).
+    ``confusion=True`` -- with ``match=True`` only, else ValueError -- sets the switch under which that ``update_metrics`` forms a plotted
+    validation's confusion matrix on the device, one call per batch (``detmatch._CONFUSION_ON``; uninstall() clears it)."""
+    if confusion and not match:
+        raise ValueError("install(confusion=True) needs match=True: the confusion matrix is formed by the replacement update_metrics")
     for name in _PRELOAD + (_OPS_PRELOAD if nms else ()) + (_VAL_PRELOAD if match else ()):
         if name not in sys.modules:
             try:
@@ -78,6 +82,11 @@ def install(strict: bool = False, nms: bool = False, match: bool = False) -> Lis
         patched += _install_nms()
     if match:
         patched += _install_match()
+    if confusion:
+        from . import detmatch
+        if not detmatch._CONFUSION_ON:
+            _UNDO.append((detmatch.__name__, "_CONFUSION_ON", False))
+            detmatch._CONFUSION_ON = True
     if strict:
         need = _factory_module_name()
         if need not in patched:
