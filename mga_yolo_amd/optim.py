@@ -187,11 +187,11 @@ class BucketOptimizer:
             f[_word("lr") + j] = float(lr)
         if momentum is not None:
             m = float(momentum)
-            if not 0.0 <= m < 1.0 or (self.adamw and m <= 0.0):
-                raise ValueError(f"momentum {m}")
+            if not 0.0 < m < 1.0:                                             # SGD too: at 0 torch leaves momentum_buffer alone, the kernel
+                raise ValueError(f"momentum {m}")                             # stores buf = g, and the two part when momentum returns
             f[_word("momentum") + j] = m
             f[_word("one_minus_momentum") + j] = 1.0 - m                      # in double, as torch's Python side forms it
-            f[_word("ln_momentum") + j] = math.log(m) if m > 0.0 else 0.0
+            f[_word("ln_momentum") + j] = math.log(m)
         if weight_decay is not None:
             f[_word("weight_decay") + j] = float(weight_decay)
 
@@ -199,7 +199,8 @@ class BucketOptimizer:
         self.hyper[:_HOST_WORDS].copy_(self._host)
 
     def set_group(self, j: int, lr: Optional[float] = None, momentum: Optional[float] = None, weight_decay: Optional[float] = None) -> None:
-        """Group j's lr / momentum (AdamW: beta1) / weight decay from now on: what warm-up and the scheduler change every iteration."""
+        """Group j's lr / momentum (AdamW: beta1; either in (0, 1)) / weight decay from now on: what warm-up and the scheduler change every
+        iteration."""
         self._set_group(j, lr, momentum, weight_decay)
         self._upload()
 

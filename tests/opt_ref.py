@@ -45,8 +45,22 @@ class TorchTail:
         self.ema = {n: p.detach().clone() for n, p in {**self.params, **self.buffers}.items()}
         self.updates = 0
 
-    def step(self, grads, lr, momentum, ext_sumsq=0.0, buffers=None):
-        """grads: {name: tensor}; lr / momentum: per group; buffers: the EMA-only tensors' current values -> (total norm, clip coefficient)"""
+    def start_at(self, u0, t0, state0, state1, ema):
+        """A mid-run state: ModelEMA.updates = u0, t0 applied steps (AdamW's state["step"]), the given momentum_buffer | exp_avg (state0),
+        exp_avg_sq (state1, AdamW) and averages, each {name: flat fp32 tensor on the host}"""
+        self.updates = u0
+        for n, p in self.params.items():
+            put = lambda t: t.to(self.device, self.dtype).reshape(p.shape).clone()
+            if self.kind == "sgd":
+                self.opt.state[p]["momentum_buffer"] = put(state0[n])
+            else:                                                      # what _init_group would have made, t0 steps later
+                self.opt.state[p].update(step=torch.tensor(float(t0), dtype=torch.float32), exp_avg=put(state0[n]), exp_avg_sq=put(state1[n]))
+        for n, v in self.ema.items():
+            v.copy_(ema[n].to(self.device, self.dtype).reshape(v.shape))
+
+    def step(self, grads, lr, momentum, ext_sumsq=0.0, buffers=None, skip=False):
+        """grads: {name: tensor}; lr / momentum: per group; buffers: the EMA-only tensors' current values -> (total norm, clip coefficient).
+        skip: GradScaler.step on found_inf -- no optimizer.step(); ModelEMA.update runs all the same (trainer.py:717-718)"""
         for j, pg in enumerate(self.opt.param_groups):                 # trainer.py:463-474
             pg["lr"] = lr[j]
             if "momentum" in pg:
@@ -61,7 +75,8 @@ class TorchTail:
                     p.grad = torch.zeros_like(p)
         self.ext.grad = torch.full_like(self.ext, math.sqrt(ext_sumsq))
         total = torch.nn.utils.clip_grad_norm_(list(self.params.values()) + [self.ext], max_norm=self.max_norm)
-        self.opt.step()
+        if not skip:
+            self.opt.step()
         for n, b in (buffers or {}).items():
             self.buffers[n] = b.detach().to(self.device, self.dtype).clone()
         self.updates += 1                                              # torch_utils.py:767-774
@@ -73,10 +88,17 @@ class TorchTail:
         total = float(total)
         return total, min(1.0, self.max_norm / (total + 1e-6))
 
-    def tensors(self):
-        """{name: tensor}: parameters as 'param.<name>', averages as 'ema.<name>'"""
+    def tensors(self, state=False):
+        """{name: tensor}: parameters as 'param.<name>', averages as 'ema.<name>'; state: also momentum_buffer | exp_avg as 'state0.<name>'
+        and exp_avg_sq as 'state1.<name>'"""
         out = {f"param.{n}": p.detach() for n, p in self.params.items()}
         out.update({f"ema.{n}": v for n, v in self.ema.items()})
+        if state:
+            for n, p in self.params.items():
+                st = self.opt.state[p]
+                out[f"state0.{n}"] = st["momentum_buffer" if self.kind == "sgd" else "exp_avg"]
+                if self.kind != "sgd":
+                    out[f"state1.{n}"] = st["exp_avg_sq"]
         return out
 
 
@@ -201,4 +223,328 @@ def run_against_torch(kind, device, figures=None):
         for name in ours:
             misses += bar_check(f"{kind} step {t} {name}", ours[name], a32[name], a64[name], figures)
     assert opt.updates == K and opt.t == K
+    return misses
+
+
+# ---- a run's horizon: a late start, a warm-up schedule, wrong settings ---------------------------------------------------------------
+# The four steps above never evaluate -expm1f(t ln m), sqrt(-expm1f(t ln beta2)) or (1 - decay) + decay exp(-u / tau) past t = u = 4, nor at
+# the reference's tau = 2000; and one EMA step at decay 0.9999 moves an element by 1e-4 |p - e|, so an error of a few per cent in 1 - d is
+# below bar_check's floor until a trajectory has carried the average a hundred bars away.  These rows start mid-run and go that far.
+LATE_STARTS = ((0, 0), (1000, 990), (20000, 19990))      # (ModelEMA.updates, applied steps) a run starts from
+LATE_STEPS, LATE_CHECKPOINTS, WARMUP = 256, (1, 16, 64, 256), 100
+LATE = dict(ema_decay=0.9999, ema_tau=2000.0, beta2=0.999)                # the reference's
+EMA_OFFSET, DRIFT, MIN_DISPLACEMENT = 0.05, 0.01, 100.0
+# settings that BucketOptimizer's side alone may be given wrong, and the rows built to notice each
+WRONG = ("tau", "ema_decay", "beta2", "t_plus_1")
+BUILT_AGAINST = {("sgd", 1000): ("tau",), ("adamw", 1000): ("tau", "t_plus_1", "beta2"),
+                 ("sgd", 20000): ("tau", "ema_decay"), ("adamw", 20000): ("tau", "ema_decay", "beta2")}
+
+
+def wrong_settings(wrong=None):
+    """-> (OptConfig's ema_decay / ema_tau / beta2, what is added to the applied-step counter) with one of WRONG, or None: the tails' own"""
+    assert wrong is None or wrong in WRONG, wrong
+    kw = dict(LATE)
+    if wrong == "tau":
+        kw["ema_tau"] *= 1.01
+    elif wrong == "ema_decay":
+        kw["ema_decay"] = 0.99989
+    elif wrong == "beta2":
+        kw["beta2"] = 0.9989
+    return kw, int(wrong == "t_plus_1")
+
+
+def warmup(kind, i):
+    """Step i of the reference's warm-up (trainer.py:463-474), WARMUP steps long -> (lr per group, momentum per group): the bias group's lr
+    comes down from warmup_bias_lr, the others' up from 0, momentum up from warmup_momentum"""
+    f = min(i, WARMUP) / WARMUP
+    if kind == "sgd":
+        return [0.1 + f * (0.01 - 0.1), f * 0.01, f * 0.01], [0.8 + f * (0.937 - 0.8)] * 3
+    return [f * 0.002] * 3, [0.8 + f * (0.9 - 0.8)] * 3
+
+
+def horizon_ext(i):
+    return 200.0 if i % 4 == 0 else 0.0                   # the clip is active every fourth step (EXT_SUMSQ's reasoning)
+
+
+_HORIZON_GRADS = {}
+
+
+def horizon_grads(i):
+    """Step i's flat gradient on the host: the sixteen of step_grads in turn plus a constant drift, so that the parameters travel"""
+    if i % 16 not in _HORIZON_GRADS:
+        _HORIZON_GRADS[i % 16] = step_grads(i % 16, "cpu") + DRIFT
+    return _HORIZON_GRADS[i % 16]
+
+
+def split(flat):
+    """{segment name: its part of a flat tensor laid out as make_case's bucket}"""
+    out, off = {}, 0
+    for n in LENGTHS:
+        out[f"seg{n}"] = flat[off:off + n]
+        off += n
+    return out
+
+
+def start_state(kind, segs, seed=7):
+    """The state of a run under way, on the host -> ({name: momentum_buffer | exp_avg}, {name: exp_avg_sq} (AdamW), {name: average}): no
+    state is zero, exp_avg_sq is positive, and every average lies EMA_OFFSET from its parameter with a random sign, so no tensor -- the
+    1-element segment included -- starts with e == p"""
+    g = torch.Generator().manual_seed(seed)
+    s0, s1, ema = {}, {}, {}
+    for s in segs:
+        n = s.param.numel()
+        if s.grad is not None:
+            s0[s.name] = torch.randn(n, generator=g) * (0.1 if kind == "sgd" else 0.02)
+            if kind == "adamw":
+                s1[s.name] = (torch.rand(n, generator=g) + 0.5) * 0.0025
+        sign = torch.randint(0, 2, (n,), generator=g).float() * 2.0 - 1.0
+        ema[s.name] = s.param.detach().cpu().reshape(-1) + EMA_OFFSET * sign
+    return s0, s1, ema
+
+
+def start_optimizer(opt, u0, t0, state0, state1, ema):
+    """TorchTail.start_at for a BucketOptimizer: `updates` = u0 and t0 in the slot the next step reads, slot u0 & 1"""
+    for n, v in state0.items():
+        opt._state0[n].copy_(v)
+    for n, v in state1.items():
+        opt._state1[n].copy_(v)
+    for n, v in ema.items():
+        opt.ema[n].copy_(v)
+    c = [u0, 0, 0]
+    c[1 + (u0 & 1)] = t0
+    opt.counters.copy_(torch.tensor(c, dtype=torch.int32))
+    assert opt.updates == u0 and opt.t == t0
+
+
+def model_state(opt):
+    """parameters and optimizer state: what a skipped step must leave alone"""
+    return [s.param for s in opt.segments if s.grad is not None] + list(opt._state0.values()) + list(opt._state1.values())
+
+
+def same(a, b):
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def _ours(opt, state=False):
+    out = {f"param.{s.name}": s.param for s in opt.segments if s.grad is not None}
+    out.update({f"ema.{n}": v for n, v in opt.ema.items()})
+    if state:
+        out.update({f"state0.{n}": v for n, v in opt._state0.items()})
+        out.update({f"state1.{n}": v for n, v in opt._state1.items()})
+    return out
+
+
+def _tails(kind, device, u0, t0):
+    """make_case's segments, and both tails put into start_state at (u0, t0) -> (segs, grads, bucket, buffers, state, fp32 tail, fp64 tail)"""
+    segs, grads, bucket, init, groups, bufs = make_case(device)
+    state = start_state(kind, segs)
+    kw = dict(decay=5e-4, buffers=bufs, **LATE)
+    t32 = TorchTail(kind, init, groups, dtype=torch.float32, device=device, **kw)
+    t64 = TorchTail(kind, init, groups, dtype=torch.float64, device="cpu", **kw)
+    for t in (t32, t64):
+        t.start_at(u0, t0, *state)
+    return segs, grads, bucket, bufs, state, t32, t64
+
+
+_LATE_REFERENCE = {}
+
+
+def late_reference(kind, u0, t0, device):
+    """Both tails over LATE_STEPS steps from (u0, t0), run once per row and device and left unchanged -> (the fp64 tensors at the start,
+    {checkpoint: (fp32 tensors, fp64 tensors, fp32 norm, fp64 norm, fp64 clip coefficient)})"""
+    key = (kind, u0, t0, str(device))
+    if key not in _LATE_REFERENCE:
+        _, _, _, bufs, _, t32, t64 = _tails(kind, device, u0, t0)
+        start = {n: v.clone() for n, v in t64.tensors().items()}
+        ref = {}
+        for i in range(LATE_STEPS):
+            gs = split(horizon_grads(i))
+            lr, mom = warmup(kind, i)
+            n32, _ = t32.step(gs, lr, mom, ext_sumsq=horizon_ext(i), buffers=bufs)
+            n64, c64 = t64.step(gs, lr, mom, ext_sumsq=horizon_ext(i), buffers=bufs)
+            if i + 1 in LATE_CHECKPOINTS:
+                ref[i + 1] = ({n: v.clone() for n, v in t32.tensors().items()}, {n: v.clone() for n, v in t64.tensors().items()}, n32, n64, c64)
+        assert t64.updates == u0 + LATE_STEPS
+        _LATE_REFERENCE[key] = (start, ref)
+    return _LATE_REFERENCE[key]
+
+
+def run_late(kind, u0, t0, device, wrong=None, figures=None):
+    """LATE_STEPS steps of BucketOptimizer on `device` from the mid-run state (u0, t0) under the warm-up schedule, compared with the fp64 tail
+    at LATE_CHECKPOINTS -> (misses, {tensor: max|oracle - start| / its bar at the last step}).  wrong: one of WRONG, given to BucketOptimizer
+    alone (the counters are then not asserted)."""
+    from mga_yolo_amd.optim import BucketOptimizer, OptConfig
+    start, ref = late_reference(kind, u0, t0, device)
+    segs, _, bucket, _, _, _ = make_case(device)
+    cfg_kw, dt = wrong_settings(wrong)
+    lr, mom = warmup(kind, 0)
+    opt = BucketOptimizer(segs, OptConfig(kind, lr=lr, momentum=mom, weight_decay=5e-4, **cfg_kw), device)
+    start_optimizer(opt, u0, t0 + dt, *start_state(kind, segs))
+    misses, moved = [], {}
+    for i in range(LATE_STEPS):
+        bucket.copy_(horizon_grads(i))
+        lr, mom = warmup(kind, i)
+        for j in range(3):
+            opt.set_group(j, lr=lr[j], momentum=mom[j])
+        opt.set_external(sumsq=horizon_ext(i))
+        opt.step()
+        k = i + 1
+        if k not in ref:
+            continue
+        a32, a64, n32, n64, c64 = ref[k]
+        if wrong is None:
+            assert opt.updates == u0 + k and opt.t == t0 + k, (k, opt.updates, opt.t)
+            assert abs(float(opt.grad_norm) - n64) <= max(1e-6 * n64, 4 * abs(n32 - n64)), (k, float(opt.grad_norm), n32, n64)
+            assert abs(float(opt.clip_coef) - c64) <= 1e-6 and (c64 < 1.0) == bool(horizon_ext(i)) and int(opt.found_inf) == 0
+        ours, fig = _ours(opt), []
+        assert sorted(ours) == sorted(a64)
+        for name in ours:
+            misses += bar_check(f"{kind} from {u0} step {k} {name}", ours[name], a32[name], a64[name], fig)
+        if figures is not None:
+            figures += fig
+        if k == LATE_STEPS:
+            for name, f in zip(ours, fig):
+                moved[name] = float((a64[name] - start[name]).abs().max()) / f[4]
+    return misses, moved
+
+
+def check_late_row(kind, u0, t0, device):
+    """The row as the host and the device test run it: no miss at any checkpoint, and at the last one every compared tensor has travelled
+    at least MIN_DISPLACEMENT bars from where it started -- short of that the bar could not tell a wrong 1 - d from a right one.
+    -> (figures, the least displacement / bar)"""
+    figures = []
+    misses, moved = run_late(kind, u0, t0, device, figures=figures)
+    least = min(moved, key=moved.get)
+    print(f"{kind} from {u0}: least displacement / bar {moved[least]:.1f} ({least})")
+    assert len(moved) == 2 * len(LENGTHS) + 1
+    assert not misses, misses
+    assert moved[least] >= MIN_DISPLACEMENT, (least, moved[least])
+    return figures, moved[least]
+
+
+# ---- a scaled, accumulating run with skipped steps ------------------------------------------------------------------------------------------
+ACC_STEPS, ACC_MICRO, ACC_GROWTH, ACC_SCALE0, ACC_CHECKPOINTS, ACC_START = 40, 4, 6, 1024.0, (1, 8, 40), (1000, 990)
+# step -> (micro-step, segment, element, value).  `updates` after step i is 1001 + i: a skip at an even one (5, 33), at an odd one (12), and
+# two in a row (20, 21); the last element of seg1025 is alone in its chunk, the first of seg1 is the bucket's first word
+ACC_INJECT = {5: (2, "seg1025", -1, float("inf")), 12: (0, "seg1", 0, float("nan")), 20: (3, "seg1025", -1, float("-inf")),
+              21: (1, "seg1", 0, float("inf")), 33: (1, "seg4099", 2048, float("nan"))}
+
+
+def _inject(flat, seg, element, value):
+    off = dict(zip((f"seg{n}" for n in LENGTHS), np.cumsum((0,) + LENGTHS[:-1]).tolist()))[seg]
+    n = int(seg[3:])
+    flat = flat.clone()
+    flat[off + element % n] = value
+    return flat
+
+
+def run_scaled_accumulation(kind, device, figures=None):
+    """ACC_STEPS optimizer steps of ACC_MICRO accumulate() calls each, the bucket holding scale x g with the scale driven as GradScaler.update
+    drives it (halved on found_inf, doubled after ACC_GROWTH clean steps), a non-finite value injected per ACC_INJECT.  The fp64 tail is fed
+    the fp64 sum of the unscaled micro-gradients, the fp32 tail their fp32 sum in call order, both with skip= at the injected steps.
+    Asserted after every step: acc is zero, found_inf is as injected, updates and t, and that a skipped step -- and no other -- leaves
+    parameters and state as they were.  -> the misses at ACC_CHECKPOINTS"""
+    from mga_yolo_amd.optim import BucketOptimizer, OptConfig
+    u0, t0 = ACC_START
+    after = sorted(u0 + 1 + i for i in ACC_INJECT)
+    assert {u & 1 for u in after} == {0, 1} and any(b - a == 1 for a, b in zip(after, after[1:]))
+    segs, _, bucket, bufs, state, t32, t64 = _tails(kind, device, u0, t0)
+    lr, mom = warmup(kind, 0)
+    opt = BucketOptimizer(segs, OptConfig(kind, lr=lr, momentum=mom, weight_decay=5e-4, **LATE), device, accumulate=True, bucket=bucket)
+    start_optimizer(opt, u0, t0, *state)
+    scale, clean, applied, misses, scales = ACC_SCALE0, 0, 0, [], set()
+    for i in range(ACC_STEPS):
+        inject = ACC_INJECT.get(i)
+        skip = inject is not None
+        lr, mom = warmup(kind, i)
+        for j in range(3):
+            opt.set_group(j, lr=lr[j], momentum=mom[j])
+        opt.set_external(sumsq=horizon_ext(i + 1))
+        opt.set_scale(scale)
+        scales.add(scale)
+        sum32, sum64 = torch.zeros(sum(LENGTHS)), torch.zeros(sum(LENGTHS), dtype=torch.float64)
+        for k in range(ACC_MICRO):
+            g = step_grads(ACC_MICRO * i + k, "cpu")
+            if skip and inject[0] == k:
+                g = _inject(g, *inject[1:])
+            bucket.copy_(g * scale)                                    # a power of two: exact, and inf and NaN stay what they are
+            opt.accumulate()
+            sum32 += g
+            sum64 += g.double()
+        if not skip:
+            assert torch.equal(opt.acc.cpu(), sum32 * scale), i
+        before = [t.clone() for t in model_state(opt)]
+        opt.step()
+        applied += not skip
+        assert int(torch.count_nonzero(opt.acc)) == 0, i               # a NaN counts as non-zero: the skipped step zeroed it too
+        assert int(opt.found_inf) == int(skip) and math.isfinite(float(opt.grad_norm)) != skip, (i, float(opt.grad_norm))
+        assert opt.updates == u0 + i + 1 and opt.t == t0 + applied, (i, opt.updates, opt.t)
+        assert same(model_state(opt), before) == skip, i
+        t32.step(split(sum32), lr, mom, ext_sumsq=horizon_ext(i + 1), buffers=bufs, skip=skip)
+        t64.step(split(sum64), lr, mom, ext_sumsq=horizon_ext(i + 1), buffers=bufs, skip=skip)
+        if i + 1 in ACC_CHECKPOINTS:
+            ours, a32, a64 = _ours(opt), t32.tensors(), t64.tensors()
+            assert sorted(ours) == sorted(a64)
+            for name in ours:
+                misses += bar_check(f"{kind} scaled step {i + 1} {name}", ours[name], a32[name], a64[name], figures)
+        if skip:                                                       # GradScaler.update
+            scale, clean = scale / 2.0, 0
+        else:
+            clean += 1
+            if clean == ACC_GROWTH:
+                scale, clean = scale * 2.0, 0
+    assert applied == ACC_STEPS - len(ACC_INJECT) and len(scales) >= 3, scales
+    return misses
+
+
+# ---- check_finite=False: a non-finite gradient is applied, as torch applies it ------------------------------------------------------------
+def finite_bar_check(what, got, f32, oracle, figures=None):
+    """bar_check on the elements that are finite in the oracle; a NaN or an infinity anywhere else than the oracle's is a miss"""
+    g, f, o = (t.detach().cpu().reshape(-1) for t in (got, f32, oracle))
+    misses = []
+    for who, t in (("result", g), ("torch fp32", f)):
+        if not (torch.equal(torch.isnan(t), torch.isnan(o)) and torch.equal(torch.isfinite(t), torch.isfinite(o))):
+            misses.append((f"{what}: NaN positions of the {who}", int(torch.isnan(t).sum()), int(torch.isnan(o).sum())))
+    ok = torch.isfinite(o)
+    if not misses and bool(ok.any()):
+        misses += bar_check(what, g[ok], f[ok], o[ok], figures)
+    return misses
+
+
+def run_unchecked(kind, device, value, figures=None):
+    """check_finite=False, four steps from ACC_START, `value` (an infinity or a NaN) in the last element of seg1025 at the third; parameters,
+    state and averages are compared with the tails after the third and the fourth -> misses"""
+    from mga_yolo_amd.optim import BucketOptimizer, OptConfig
+    u0, t0 = ACC_START
+    segs, _, bucket, bufs, state, t32, t64 = _tails(kind, device, u0, t0)
+    lr, mom = warmup(kind, 50)
+    opt = BucketOptimizer(segs, OptConfig(kind, lr=lr, momentum=mom, weight_decay=5e-4, check_finite=False, **LATE), device)
+    start_optimizer(opt, u0, t0, *state)
+    misses = []
+    for i in range(4):
+        g = horizon_grads(i)
+        if i == 2:
+            g = _inject(g, "seg1025", -1, value)
+        lr, mom = warmup(kind, 50 + i)
+        for j in range(3):
+            opt.set_group(j, lr=lr[j], momentum=mom[j])
+        bucket.copy_(g)
+        opt.step()
+        t32.step(split(g), lr, mom, buffers=bufs)
+        n64, c64 = t64.step(split(g), lr, mom, buffers=bufs)
+        assert opt.updates == u0 + i + 1 and opt.t == t0 + i + 1 and int(opt.found_inf) == int(i == 2)      # applied all the same
+        if i < 2:
+            continue
+        ours, a32, a64 = _ours(opt, True), t32.tensors(True), t64.tensors(True)
+        assert sorted(ours) == sorted(a64)
+        trained = [n for n in a64 if n != "ema.buffer"]
+        if math.isinf(value):                                          # coef = 0: that one element is NaN wherever it is kept, nothing else
+            assert i > 2 or (math.isinf(n64) and c64 == 0.0 and float(opt.clip_coef) == 0.0)
+            assert all(int(torch.isnan(a64[n]).sum()) == int(n.endswith(".seg1025")) for n in a64)
+            assert all(bool(torch.isnan(a64[n].reshape(-1)[-1])) for n in a64 if n.endswith(".seg1025"))
+        else:                                                          # a NaN norm, a NaN coefficient: every trained tensor is NaN throughout
+            assert i > 2 or (math.isnan(n64) and math.isnan(float(opt.clip_coef)))
+            assert all(bool(torch.isnan(a64[n]).all()) for n in trained) and bool(torch.isfinite(a64["ema.buffer"]).all())
+        for name in ours:
+            misses += finite_bar_check(f"{kind} {value} step {i} {name}", ours[name], a32[name], a64[name], figures)
     return misses

@@ -5,6 +5,9 @@ misaligned to 16 bytes and a chunk ends inside a segment --, all three parameter
 Every comparison with torch uses the rule of tests/opt_ref.bar_check: the oracle is an fp64 run of the same torch sequence on the host, and the
 device result may differ from it by at most max(1e-6 max|p|, 4 x the error of torch's own fp32 device run against that oracle).
 
+Sections 6 and 7 run the same segments where a run spends its time: 256 steps from `updates` = 0, 1000 and 20000 at the reference's tau = 2000
+under the warm-up schedule, a GradScaler's run of scaled, accumulated and skipped steps, and check_finite=False against torch element for element.
+
 The measured figures are in DESIGN 7h."""
 import pytest
 import torch
@@ -146,7 +149,58 @@ def test_two_runs_give_the_same_bits(built_lib, kind):
         assert _same(a.state_tensors(), b.state_tensors()), t
 
 
-# ---- 6. in the graph ---------------------------------------------------------------------------------------------------------------------
+# ---- 6. over a run's horizon (opt_ref: "a run's horizon"; tests/test_opt_host.py runs the same rows through the host path) -----------------
+def _worst_by_kind(figures):
+    return " | ".join(f"worst {k}: " + "{1:.1e} / {2:.1e} / {4:.1e} ({0})".format(*max((f for f in figures if f" {k}." in f[0]), key=lambda f: f[1] / f[4]))
+                      for k in ("param", "ema"))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("u0,t0", R.LATE_STARTS)
+def test_steps_agree_with_torch_from_a_late_start(built_lib, kind, u0, t0):
+    """256 steps from `updates` = u0 with t0 applied steps, tau = 2000, decay 0.9999, the warm-up schedule, every fourth step clipped:
+    expm1f(t ln m), expm1f(t ln beta2) and expf(-u / tau) at the arguments of a run under way.  Compared at steps 1, 16, 64 and 256, and at
+    256 every tensor has moved at least 100 bars (both inside check_late_row).  That the rows miss a tau, ema_decay, beta2 or t that is
+    slightly wrong is shown on the host path (tests/test_opt_host.py)."""
+    figures, least = R.check_late_row(kind, u0, t0, DEV)
+    print(kind, u0, _worst_by_kind(figures), "| least displacement / bar", f"{least:.0f}")
+
+
+# ---- 7. the GradScaler's run: scaled, accumulated, skipped ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_scaled_accumulation_with_skips(built_lib, kind):
+    """40 steps of 4 accumulate() calls on scale x g, the scale halved and doubled as GradScaler.update does, an inf or a NaN in one micro-step
+    of five steps: skips at an even and an odd `updates` and two in a row.  After every step acc is all zero -- a skipped step that left it
+    alone would keep the inf and skip every step after --, found_inf, updates and t are as injected, and a skipped step leaves parameters
+    and state bit for bit (all inside run_scaled_accumulation); at steps 1, 8 and 40 everything is within the bar of the fp64 tail."""
+    figures = []
+    misses = R.run_scaled_accumulation(kind, DEV, figures)
+    print(kind, _worst_by_kind(figures))
+    assert not misses, misses
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("value", [float("inf"), float("nan")], ids=["inf", "nan"])
+def test_check_finite_off_is_torch_without_a_scaler(built_lib, kind, value):
+    """What torch does with a non-finite gradient and no GradScaler, element for element.  An infinity: the norm is inf, coef = 10 / inf = 0,
+    inf * 0 = NaN in that element of the parameter, its state and its average, and every other element takes a step on a zero gradient
+    (weight decay and the momentum it already had).  A NaN: a NaN norm, a NaN coefficient, and every trained tensor is NaN throughout; only
+    the EMA-only buffer's average stays finite.  NaN positions equal the fp64 tail's in parameters, state and averages; the finite elements
+    are within the bar."""
+    figures = []
+    misses = R.run_unchecked(kind, DEV, value, figures)
+    print(kind, value, _worst(figures) if figures else "nothing finite")
+    assert not misses, misses
+
+
+def test_sgd_refuses_momentum_zero(built_lib):
+    """k_opt_step stores buf = g at momentum 0 where torch leaves the buffer alone (tests/test_opt_host.py shows the trajectories part)"""
+    opt, _, _ = _opt("sgd")
+    with pytest.raises(ValueError, match="momentum"):
+        opt.set_group(0, momentum=0.0)
+
+
+# ---- 8. in the graph ---------------------------------------------------------------------------------------------------------------------
 SHAPES = [(4, 64, 16, 16), (4, 128, 8, 8), (4, 256, 4, 4)]
 GRAPH_ROWS = [("cbam", False), ("spade", True)]                         # (block, channels_last); MaskSPADE's middle level is a batch-norm level
 GRAPH_LR = dict(sgd=[[0.1, 0.002, 0.002], [0.08, 0.004, 0.004], [0.05, 0.007, 0.007], [0.01, 0.01, 0.01]],
