@@ -130,3 +130,99 @@ def test_slice_plan_target_argument_errors(shapes, kw):
 def test_unknown_keyword_is_still_a_type_error():
     with pytest.raises(TypeError):
         _create(target_sauce=(128, 128))
+
+
+# ---- the edge fixtures and the helpers the device tests lean on (tests/targets_cases.py; tests/test_gpu_targets_edges.py)
+@pytest.mark.parametrize("shape", T.EDGE_SHAPES, ids=T.shape_id)
+def test_cpu_path_and_compose_are_bit_equal_to_every_edge_golden(shape):
+    from mga_yolo_amd import mask_pyramid
+    meta, z = T.load(shape)
+    assert tuple(meta["shape"]) == shape and tuple(meta["patterns"]) == T.EDGE_PATTERNS and tuple(meta["strides"]) == T.ALL_STRIDES
+    B, H, W = shape
+    n = 0
+    for p in T.EDGE_PATTERNS:
+        mask = z[f"mask.{p}"]
+        assert mask.shape == shape and mask.dtype == (torch.float32 if p in T.F32_PATTERNS else torch.uint8)
+        for method in T.METHODS:
+            for sl in [T.MODEL_STRIDES, (2, 4, 8, 16)] + [(s,) for s in T.ALL_STRIDES]:
+                got = mask_pyramid(mask, sl, method)
+                for s, g, c in zip(sl, got, T.compose(mask, sl, method)):
+                    want = z[f"{method}.{p}.{s}"]
+                    assert g.dtype == torch.float32 and g.shape == want.shape == (B, 1, -(-H // s), -(-W // s))
+                    assert torch.equal(g, want), (p, method, s)
+                    assert torch.equal(c, want), (p, method, s)
+                    n += 1
+    assert n == len(T.EDGE_PATTERNS) * 2 * (3 + 4 + 6)
+
+
+def test_the_edge_patterns_hold_what_they_are_for():
+    tiny = float(torch.finfo(torch.float32).tiny)
+    for shape in T.EDGE_SHAPES:
+        B, H, W = shape
+        _, z = T.load(shape)
+        # u8all: every byte value; each key byte at each position of an aligned 8-byte word, once among 0x00 and once among 0xff
+        u8 = z["mask.u8all"]
+        assert W % 8 == 0 and len(u8.unique()) == 256
+        words = {tuple(w) for w in u8.reshape(-1, 8).tolist()}
+        for k in T.KEY_BYTES:
+            for j in range(8):
+                for other in (0x00, 0xFF):
+                    assert tuple(k if i == j else other for i in range(8)) in words, (shape, k, j, other)
+        # f32special: all twelve values, and a plain > 0 on the host flushes none of them
+        f = z["mask.f32special"]
+        fg = f > 0
+        bits = f.view(torch.int32)
+        assert len(bits.unique()) == 12 and bool(torch.isnan(f).any())                # twelve bit patterns: +0.0 and -0.0 are two
+        assert sorted(f[fg].unique().tolist()) == sorted(torch.tensor([1e-45, 1e-38, tiny, 0.3, 1.0, float("inf")]).tolist())
+        assert sorted(f[~fg & ~torch.isnan(f)].unique().tolist()) == sorted(torch.tensor([float("-inf"), -tiny, -1e-45, 0.0]).tolist())
+        assert int(((f > 0) & (f < tiny)).sum()) > 0                                  # subnormals, and they are foreground
+        assert torch.equal(z["maxpool.f32special.2"], T.compose(fg.to(torch.uint8), (2,), "maxpool")[0])
+        # ramp: the 8-counts are the formula, cut where a cell leaves the image (rows only: W % 8 == 0)
+        cy, cx = torch.meshgrid(torch.arange(-(-H // 8)), torch.arange(W // 8), indexing="ij")
+        want = torch.minimum((cy * 9 + cx * 5) % 65, 8 * (H - 8 * cy).clamp(max=8))
+        assert torch.equal(z["avgpool.ramp.8"] * 64, want.float().expand(B, 1, -1, -1))
+        quad = want[: 2 * (want.shape[0] // 2), : 2 * (want.shape[1] // 2)].unfold(0, 2, 2).unfold(1, 2, 2).reshape(-1, 4)
+        assert all(len(set(q)) == 4 for q in quad.tolist()[:4])                      # the first quads: four different counts
+        # lastrow: nothing but the last row and column
+        m = z["mask.lastrow"]
+        assert int(m.sum()) == B * (H + W - 1) and bool(m[:, H - 1, :].all()) and bool(m[:, :, W - 1].all())
+
+
+def _seam_levels():
+    """every (shape, stride) the device tests close: the levels of (2, 70, 136), one 1 x 1 level and one 1 x 17 level"""
+    return [((2, 70, 136), s) for s in (2, 4, 8, 16, 32)] + [((1, 7, 5), 8), ((2, 5, 133), 8)]
+
+
+def test_seam_masks_closed_forms_agree_with_the_loops_and_the_composition():
+    names = set()
+    for shape, s in _seam_levels():
+        for name, mask, closed, seam in T.seam_masks(shape, s):
+            names.add(name)
+            unclosed = T.compose(mask, (s,), "maxpool")[0]
+            assert torch.equal(T.close3_loops(unclosed), closed), (shape, s, name)
+            assert torch.equal(T.compose(mask, (s,), "maxpool", bridge=True)[0], closed), (shape, s, name)
+            assert int(mask.sum()) == int(unclosed.sum())                                  # one pixel per chosen cell
+            if seam is not None:                                                           # a filled gap: the closing changed the seam cell itself
+                assert float(unclosed[0, 0, seam[0], seam[1]]) == 0.0 and float(closed[0, 0, seam[0], seam[1]]) == 1.0, (shape, s, name)
+            elif name[0] in "hvd":                                                         # a gap of three, a diagonal: the seam cell stays empty
+                k, oh, ow = int(name[1:3]), closed.shape[2], closed.shape[3]
+                cell = {"h": (oh // 2, k), "v": (k, ow // 2), "d": (k, k)}[name[0]]
+                assert float(closed[0, 0, cell[0], cell[1]]) == 0.0, (shape, s, name)
+            elif name == "corners" and min(closed.shape[2:]) >= 5:
+                assert torch.equal(unclosed, closed), (shape, s, name)                     # each stays single: three cells or more between two
+    # the 35 x 68 level has every case; gaps of one and two are filled, a gap of three is not
+    want = {f"{d}{s}gap{g}" for d in "hv" for s in (16, 32) for g in (1, 2, 3)} | {"d16", "q16", "d32", "q32", "corners", "ones", "hole"}
+    assert names == want and {c[0] for c in T.seam_masks((2, 70, 136), 2)} == want
+    assert [c[0] for c in T.seam_masks((1, 7, 5), 8)] == ["corners", "ones"]
+
+
+def test_close3_loops_agrees_with_the_composition_and_the_cpu_path_on_random_masks():
+    from mga_yolo_amd import mask_pyramid
+    for shape in T.EDGE_SHAPES:
+        m = T.random_mask(shape)
+        strides = (2, 4, 8, 16)
+        unclosed = T.compose(m, strides, "maxpool")
+        closed = T.compose(m, strides, "maxpool", bridge=True)
+        for u, c, g in zip(unclosed, closed, mask_pyramid(m, strides, "maxpool", bridge=True)):
+            assert torch.equal(T.close3_loops(u), c) and torch.equal(g, c)
+        assert not torch.equal(unclosed[0], closed[0])
