@@ -62,7 +62,9 @@ extern "C" {
  * strides not positive and strictly ascending, reserved != 0: MGACBAM_E_ARG; a NULL buffer: MGACBAM_E_NULL; features not aligned to
  * their element, an fp32 / int32 buffer not 4-byte aligned, ws not 16-byte aligned: MGACBAM_E_ALIGN; ws smaller than mgadet_ws_bytes:
  * MGACBAM_E_SIZE.
- * Not built: channels_last features, reg_max != 16, the rotated and the segmentation criteria.
+ * Not built: reg_max != 16, the rotated and the segmentation criteria.  Channels_last maps, (B, H_l, W_l, 64 + nc) in memory, are read
+ * and their gradients written in place by mgamaps_det_forward / mgamaps_det_backward (include/ext/mgamaps.h): this header's own entry
+ * points take NCHW maps only.
  * ------------------------------------------------------------------------------------------------ */
 #define MGADET_MAX_LEVELS 4
 #define MGADET_MAX_TOPK 16

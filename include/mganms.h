@@ -55,7 +55,8 @@ extern "C" {
  * their element, an fp32 / int32 buffer not 4-byte aligned, ws not 16-byte aligned: MGACBAM_E_ALIGN; ws smaller than mganms_ws_bytes:
  * MGACBAM_E_SIZE.
  * Not built: the classes= filter and labels= (autolabelling); rotated boxes, end2end heads and extra mask channels (nc is C - 4);
- * reg_max != 16; channels_last features.
+ * reg_max != 16.  Channels_last maps, (B, H_l, W_l, 64 + nc) in memory, are read in place by mgamaps_nms_run (include/ext/mgamaps.h):
+ * this header's own entry point takes NCHW maps only.
  * ------------------------------------------------------------------------------------------------ */
 #define MGANMS_MAX_LEVELS 4
 #define MGANMS_MULTI_LABEL 1

@@ -384,10 +384,24 @@ METRIC_HEADERS = {
         structs=dict(mgacm_desc=ConfusionDesc),
         constants=dict(MGACM_MAX_NC=CM_MAX_NC, MGACM_SINGLE_CLS=CM_SINGLE_CLS)),
 }
-_TABLES = dict(HEADERS=HEADERS, EXT_HEADERS=EXT_HEADERS, METRIC_HEADERS=METRIC_HEADERS)
-ALL_HEADERS = {**HEADERS, **EXT_HEADERS, **METRIC_HEADERS}
-_bound = [name for h in ALL_HEADERS.values() for name in h.symbols]
-if len(ALL_HEADERS) != sum(len(t) for t in _TABLES.values()):
+# the Detect maps in either memory layout (include/ext/mgamaps.h: the descriptors of mgadet.h and mganms.h with a flags argument; a table of
+# its own, bound by load() as the others; tests/test_abi_maps.py)
+MAPS_LAYOUT_NHWC = 1
+LAYOUT_HEADERS = {
+    "ext/mgamaps.h": Header(
+        symbols={
+            "mgamaps_det_forward": (_i, [C.POINTER(DetDesc), C.c_int32, C.c_void_p]),
+            "mgamaps_det_backward": (_i, [C.POINTER(DetDesc), C.c_int32, C.c_void_p]),
+            "mgamaps_nms_run": (_i, [C.POINTER(NmsDesc), C.c_int32, C.c_void_p]),
+        },
+        structs={},
+        constants=dict(MGAMAPS_LAYOUT_NHWC=MAPS_LAYOUT_NHWC)),
+}
+_TABLES = dict(HEADERS=HEADERS, EXT_HEADERS=EXT_HEADERS, METRIC_HEADERS=METRIC_HEADERS, LAYOUT_HEADERS=LAYOUT_HEADERS)
+ALL_HEADERS = {**HEADERS, **EXT_HEADERS, **METRIC_HEADERS}       # the three tables of the descriptors' headers
+_EVERY_HEADER = {**ALL_HEADERS, **LAYOUT_HEADERS}
+_bound = [name for h in _EVERY_HEADER.values() for name in h.symbols]
+if len(_EVERY_HEADER) != sum(len(t) for t in _TABLES.values()):
     _keys = [k for t in _TABLES.values() for k in t]
     raise ImportError(f"_lib.{', _lib.'.join(_TABLES)}: two tables hold a record for {sorted(k for k in set(_keys) if _keys.count(k) > 1)}")
 if len(_bound) != len(set(_bound)):
@@ -415,7 +429,7 @@ def load():
                 "Build it with `python -m mga_yolo_amd.build` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         import torch  # noqa: F401  -- loads torch's libamdhip64.so.7 first so the library binds to the same HIP runtime
         lib = C.CDLL(LIB_PATH)
-        for h in ALL_HEADERS.values():
+        for h in _EVERY_HEADER.values():
             for name, (res, args) in h.symbols.items():
                 try:
                     fn = getattr(lib, name)

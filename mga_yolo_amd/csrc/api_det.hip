@@ -2,7 +2,7 @@
 #include "detmaps_host.cuh"
 #include "det.cuh"
 
-#include "../../include/mgadet.h"
+#include "../../include/ext/mgamaps.h"        // mgadet.h, and the entry points that take the maps' layout
 
 static_assert(kMapsLevelsMax == MGADET_MAX_LEVELS && kDetTopkMax == MGADET_MAX_TOPK && kDetMMax == MGADET_MAX_GT, "DetArgs against the ABI");
 static_assert(kDetMMax <= kDetSlotMask, "a slot fits under the resolve's action bits");
@@ -65,28 +65,41 @@ static int det_bind(const char* what, const mgadet_desc_t* D, DetArgs& A, const 
   return 0;
 }
 
-template <typename T>
+template <typename T, MapsLayout L>
 static int det_forward(const DetArgs& A, hipStream_t st) {
   const size_t E = static_cast<size_t>(A.m_cap) * kDetTopkMax;
   const size_t smem = E * 14 + static_cast<size_t>(A.m_cap) * 12;       // k_det_resolve: e_anc, e_met, e_ov, e_gt; pos_m, pos_o, s_row
-  if (int e = launch("k_det_assign", k_det_assign<T>, static_cast<long long>(A.maps.B) * A.m_cap, kBlock, 0, st, A)) return e;
-  if (int e = launch("k_det_resolve", k_det_resolve<T>, A.maps.B, kBlock, smem, st, A)) return e;
-  if (int e = launch("k_det_loss", k_det_loss<T>, A.nblk, kBlock, 0, st, A)) return e;
+  if (int e = launch("k_det_assign", k_det_assign<T, L>, static_cast<long long>(A.maps.B) * A.m_cap, kBlock, 0, st, A)) return e;
+  if (int e = launch("k_det_resolve", k_det_resolve<T, L>, A.maps.B, kBlock, smem, st, A)) return e;
+  if (int e = launch("k_det_loss", k_det_loss<T, L>, A.nblk, kBlock, 0, st, A)) return e;
   return launch("k_det_final", k_det_final, 1, kBlock, 0, st, A);
 }
 
-// either direction: check, bind, launch in the maps' element type
-static int det_run(const char* what, const mgadet_desc_t* D, void* stream, bool bwd) {
+// the maps' layout as a tag for the kernels' template parameter (host.cuh: with_elem's way)
+template <MapsLayout L> using LayoutTag = std::integral_constant<MapsLayout, L>;
+template <typename F>
+static auto with_layout(bool nhwc, F f) { return nhwc ? f(LayoutTag<MapsLayout::kNHWC>{}) : f(LayoutTag<MapsLayout::kNCHW>{}); }
+
+// either direction: check, bind, launch in the maps' element type and layout.  flags: 0 (mgadet_*) or MGAMAPS_LAYOUT_NHWC.  The layout changes
+// no check and no size: the maps hold the same elements, aligned to the element, in either.
+static int det_run(const char* what, const mgadet_desc_t* D, int32_t flags, void* stream, bool bwd) {
+  if (flags & ~MGAMAPS_LAYOUT_NHWC) return fail(MGACBAM_E_ARG, "%s: flags=0x%x (0 or MGAMAPS_LAYOUT_NHWC)", what, flags);
   DetArgs A;
   DetLayout L;
   if (int e = det_check(what, D, A, L)) return e;
   if (int e = det_bind(what, D, A, L, bwd)) return e;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const int e = with_elem(D->dtype, [&](auto t) {
-    return bwd ? launch("k_det_bwd", k_det_bwd<elem_t<decltype(t)>>, A.nblk, kBlock, 0, st, A) : det_forward<elem_t<decltype(t)>>(A, st);
+    return with_layout(flags & MGAMAPS_LAYOUT_NHWC, [&](auto l) {
+      using T = elem_t<decltype(t)>;
+      constexpr MapsLayout kL = decltype(l)::value;
+      return bwd ? launch("k_det_bwd", k_det_bwd<T, kL>, A.nblk, kBlock, 0, st, A) : det_forward<T, kL>(A, st);
+    });
   });
   if (!e) g_err[0] = 0;
   return e;
 }
-extern "C" int mgadet_forward(const mgadet_desc_t* D, void* stream) { return det_run("mgadet_forward", D, stream, false); }
-extern "C" int mgadet_backward(const mgadet_desc_t* D, void* stream) { return det_run("mgadet_backward", D, stream, true); }
+extern "C" int mgadet_forward(const mgadet_desc_t* D, void* stream) { return det_run("mgadet_forward", D, 0, stream, false); }
+extern "C" int mgadet_backward(const mgadet_desc_t* D, void* stream) { return det_run("mgadet_backward", D, 0, stream, true); }
+extern "C" int mgamaps_det_forward(const mgadet_desc_t* D, int32_t flags, void* stream) { return det_run("mgamaps_det_forward", D, flags, stream, false); }
+extern "C" int mgamaps_det_backward(const mgadet_desc_t* D, int32_t flags, void* stream) { return det_run("mgamaps_det_backward", D, flags, stream, true); }

@@ -2,7 +2,7 @@
 #include "detmaps_host.cuh"
 #include "nms.cuh"
 
-#include "../../include/mganms.h"
+#include "../../include/ext/mgamaps.h"        // mganms.h, and the entry point that takes the maps' layout
 
 static_assert(kMapsLevelsMax == MGANMS_MAX_LEVELS, "NmsArgs against the ABI");
 static_assert(kBlock == 256, "k_nms_greedy's radix select has one bin per thread");
@@ -67,16 +67,25 @@ static int nms_bind(const char* what, const mganms_desc_t* D, NmsArgs& A, const 
   return 0;
 }
 
-extern "C" int mganms_run(const mganms_desc_t* D, void* stream) {
-  const char* what = "mganms_run";
+// flags: 0 (mganms_run) or MGAMAPS_LAYOUT_NHWC.  The layout changes no other check and no size; a decoded prediction has no NHWC form, which is
+// refused last, so a descriptor with another fault is refused for that fault under either flags.
+static int nms_run(const char* what, const mganms_desc_t* D, int32_t flags, void* stream) {
+  if (flags & ~MGAMAPS_LAYOUT_NHWC) return fail(MGACBAM_E_ARG, "%s: flags=0x%x (0 or MGAMAPS_LAYOUT_NHWC)", what, flags);
   NmsArgs A;
   NmsLayout L;
   if (int e = nms_check(what, D, A, L)) return e;
   if (int e = nms_bind(what, D, A, L)) return e;
+  const bool nhwc = flags & MGAMAPS_LAYOUT_NHWC;
+  if (nhwc && D->pred) return fail(MGACBAM_E_ARG, "%s: MGAMAPS_LAYOUT_NHWC with pred: a decoded prediction is (B, 4 + nc, A)", what);
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  auto cand = with_elem(D->dtype, [](auto t) { return k_nms_cand<elem_t<decltype(t)>>; });
+  auto cand = with_elem(D->dtype, [&](auto t) {
+    using T = elem_t<decltype(t)>;
+    return nhwc ? k_nms_cand<T, MapsLayout::kNHWC> : k_nms_cand<T, MapsLayout::kNCHW>;
+  });
   if (int e = launch("k_nms_cand", cand, static_cast<long long>(A.maps.B) * A.bpi, kBlock, 0, st, A)) return e;
   if (int e = launch("k_nms_greedy", k_nms_greedy, A.maps.B, kBlock, 0, st, A)) return e;
   g_err[0] = 0;
   return 0;
 }
+extern "C" int mganms_run(const mganms_desc_t* D, void* stream) { return nms_run("mganms_run", D, 0, stream); }
+extern "C" int mgamaps_nms_run(const mganms_desc_t* D, int32_t flags, void* stream) { return nms_run("mgamaps_nms_run", D, flags, stream); }

@@ -9,6 +9,8 @@
 //   k_det_loss    : one thread per anchor: BCE over the classes; box and DFL terms for assigned anchors; per-workgroup partials.
 //   k_det_final   : one workgroup: the partials in a fixed order, max(sum of target scores, 1), gains, the status word.
 //   k_det_bwd     : one thread per anchor: every channel's gradient, in the features' element type and layout.
+// Every kernel that reads the maps has the layout as a compile-time parameter (detmaps.cuh: MapsLayout).  In NHWC the two gathers read an
+// anchor's row with 16-byte loads, the two sweeps move their workgroup's anchors through LDS; the arithmetic is the NCHW kernels', to the bit.
 // No atomics on floating-point sums: every sum has a fixed order, two runs give the same bits.
 #pragma once
 #include "detmaps.cuh"
@@ -106,17 +108,17 @@ __device__ __forceinline__ bool det_inside(const DetBox& g, float px, float py) 
   return fminf(fminf(px - g.x1, py - g.y1), fminf(g.x2 - px, g.y2 - py)) > 1e-9f;
 }
 // tal.py:156-188 for one (ground truth, anchor) pair that passed det_inside: overlap = clamp(CIoU, 0), metric = score^0.5 overlap^6
-template <typename T>
-__device__ __forceinline__ void det_pair(const T* __restrict__ f, const MapsAnchor& t, const DetBox& g, int label, float& met, float& ov) {
-  const DetBox pg = maps_decode<T>(f, t.hw, t.ax, t.ay);
+template <typename R>
+__device__ __forceinline__ void det_pair(const R& f, const MapsAnchor& t, const DetBox& g, int label, float& met, float& ov) {
+  const DetBox pg = maps_decode(f, t.ax, t.ay);
   const DetBox pb{pg.x1 * t.s, pg.y1 * t.s, pg.x2 * t.s, pg.y2 * t.s};
   ov = fmaxf(det_ciou(g, pb), 0.f);
-  const float sc = sigmoidf_(to_f32<T>(f[(4 * kMapsReg + label) * t.hw]));
+  const float sc = sigmoidf_(f.at(4 * kMapsReg + label));
   const float o2 = ov * ov;
   met = sqrtf(sc) * (o2 * o2 * o2);
 }
 
-template <typename T>
+template <typename T, MapsLayout L = MapsLayout::kNCHW>
 __global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
   __shared__ float s_met[kDetChunk + kDetTopkMax], s_ov[kDetChunk + kDetTopkMax];
   __shared__ int s_anc[kDetChunk + kDetTopkMax];
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
       const int local = idx - t0, x = x0 + local % w, y = y0 + local / w;
       const MapsAnchor t = maps_cell(A.maps, l, y * A.maps.W[l] + x, y, x);
       float met = -1.f, ov = 0.f;
-      if (det_inside(gt, t.ax * t.s, t.ay * t.s)) det_pair<T>(maps_feat<T>(A.maps, t, b), t, gt, label, met, ov);
+      if (det_inside(gt, t.ax * t.s, t.ay * t.s)) det_pair(maps_feat<T, L>(A.maps, t, b), t, gt, label, met, ov);
       s_met[i] = met; s_ov[i] = ov; s_anc[i] = A.maps.a0[l] + t.p;
     }
     if (tid < ncarry) { s_met[cn + tid] = sel_met[tid]; s_ov[cn + tid] = sel_ov[tid]; s_anc[cn + tid] = sel_anc[tid]; }
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
 // entry e of an image: slot e / kDetTopkMax's candidate e % kDetTopkMax.  e_gt: the slot the entry belongs to after the resolve, plus
 // an action in the bits above kDetSlotMask while it runs.
 constexpr int kDetSlotMask = 0x1ff, kDetDrop = 0x200, kDetLead = 0x400;
-template <typename T>
+template <typename T, MapsLayout L = MapsLayout::kNCHW>
 __global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
   extern __shared__ int det_smem[];
   const int M = A.m_cap, E = M * kDetTopkMax;
@@ -287,7 +289,7 @@ __global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
     if (!(act & kDetLead)) continue;
     // the arg-max over every slot of the overlap, 0 where the anchor is not inside a valid box; the first slot wins a tie
     const MapsAnchor t = maps_anchor(A.maps, e_anc[e]);
-    const T* f = maps_feat<T>(A.maps, t, b);
+    const auto f = maps_feat<T, L>(A.maps, t, b);
     float best_ov = -1.f, best_met = 0.f;
     int best = 0;
     for (int g = 0; g < M; ++g) {
@@ -295,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
       if (row < 0) break;                                      // rows fill the slots from 0: the rest are empty, overlap 0, never first
       float met = 0.f, ov = 0.f;
       const DetBox gt = det_gt_box(A, row);
-      if (det_gt_valid(gt) && det_inside(gt, t.ax * t.s, t.ay * t.s)) det_pair<T>(f, t, gt, det_label(A, row), met, ov);
+      if (det_gt_valid(gt) && det_inside(gt, t.ax * t.s, t.ay * t.s)) det_pair(f, t, gt, det_label(A, row), met, ov);
       if (ov > best_ov) { best_ov = ov; best_met = met; best = g; }
     }
     e_gt[e] = static_cast<short>(best);
@@ -340,41 +342,71 @@ __device__ __forceinline__ DetAnchor det_anchor(const DetArgs& A, long long idx)
   return DetAnchor{maps_anchor(A.maps, static_cast<int>(idx % A.maps.A)), static_cast<int>(idx / A.maps.A), A.asg_gt[idx], A.asg_score[idx]};
 }
 
-template <typename T>
+// k_det_loss's terms of one anchor, its channels read through `f`
+template <typename R>
+__device__ __forceinline__ void det_loss_anchor(const DetArgs& A, const DetAnchor& t, const R& f, float& lbox, float& lcls, float& ldfl) {
+  const int label = t.gi >= 0 ? det_label(A, t.gi) : -1;
+  for (int c = 0; c < A.maps.nc; ++c) {                             // BCEWithLogits against onehot(label) * score (loss.py:284)
+    const float x = f.at(4 * kMapsReg + c);
+    lcls += fmaxf(x, 0.f) - (c == label ? x * t.sc : 0.f) + log1pf(expf(-fabsf(x)));
+  }
+  if (t.gi >= 0) {
+    const DetBox gp = det_gt_box(A, t.gi);
+    const DetBox tb{gp.x1 / t.s, gp.y1 / t.s, gp.x2 / t.s, gp.y2 / t.s};            // loss.py:288
+    float d[4], dfl = 0.f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      float p[kMapsReg], lse, wl;
+      int tl;
+      float vl = 0.f, vr = 0.f;
+      det_dfl_target(det_side_target(tb, t.ax, t.ay, s), tl, wl);
+#pragma unroll
+      for (int j = 0; j < kMapsReg; ++j) {
+        const float v = f.at(s * kMapsReg + j);
+        vl = j == tl ? v : vl; vr = j == tl + 1 ? v : vr;
+      }
+      maps_side(f, s, p, d[s], lse);
+      dfl += (lse - vl) * wl + (lse - vr) * (1.f - wl);
+    }
+    const DetBox pb{t.ax - d[0], t.ay - d[1], t.ax + d[2], t.ay + d[3]};
+    lbox = (1.f - det_ciou(pb, tb)) * t.sc;                  // loss.py:127-129
+    ldfl = dfl * 0.25f * t.sc;                               // loss.py:134: the mean over the four sides
+  }
+}
+
+// NHWC sweeps: the workgroup's kBlock anchors go through LDS (detmaps.cuh: maps_stage_in) kDetStageWords of fp32 at a time -- whole rows, so a
+// round holds det_stage_rows(no) anchors: all 256 up to no = 65 (nc = 1), 114 at nc = 80 -- and a thread does its anchor in the round that
+// holds it: thread = anchor and block_sum's tree are the NCHW sweep's, so are the partials' bits.  66560 bytes: two workgroups fit a CU's 160 KiB.
+constexpr int kDetStageWords = kBlock * (4 * kMapsReg + 1);
+__device__ __forceinline__ int det_stage_rows(int no) { return min(kBlock, kDetStageWords / maps_stage_pitch(no)); }
+
+template <typename T, MapsLayout L = MapsLayout::kNCHW>
 __global__ __launch_bounds__(kBlock) void k_det_loss(const DetArgs A) {
   __shared__ float red[kBlock / kWave];
   const int tid = static_cast<int>(threadIdx.x);
-  const long long idx = static_cast<long long>(blockIdx.x) * kBlock + tid;
+  const long long idx = static_cast<long long>(blockIdx.x) * kBlock + tid, total = static_cast<long long>(A.maps.B) * A.maps.A;
   float lbox = 0.f, lcls = 0.f, ldfl = 0.f;
-  if (idx < static_cast<long long>(A.maps.B) * A.maps.A) {
-    const DetAnchor t = det_anchor(A, idx);
-    const T* f = maps_feat<T>(A.maps, t, t.b);
-    const int label = t.gi >= 0 ? det_label(A, t.gi) : -1;
-    for (int c = 0; c < A.maps.nc; ++c) {                           // BCEWithLogits against onehot(label) * score (loss.py:284)
-      const float x = to_f32<T>(f[(4 * kMapsReg + c) * t.hw]);
-      lcls += fmaxf(x, 0.f) - (c == label ? x * t.sc : 0.f) + log1pf(expf(-fabsf(x)));
+  if constexpr (L == MapsLayout::kNHWC) {
+    __shared__ float stage[kDetStageWords];
+    const long long i0 = static_cast<long long>(blockIdx.x) * kBlock, i1 = min(i0 + kBlock, total);
+    const int rows = det_stage_rows(A.maps.no), pitch = maps_stage_pitch(A.maps.no);
+    if (rows == 0 && idx < total) {                                 // a row longer than the stage (nc > 16575): read in place
+      const DetAnchor t = det_anchor(A, idx);
+      det_loss_anchor(A, t, maps_feat<T, L>(A.maps, t, t.b), lbox, lcls, ldfl);
     }
-    if (t.gi >= 0) {
-      const DetBox gp = det_gt_box(A, t.gi);
-      const DetBox tb{gp.x1 / t.s, gp.y1 / t.s, gp.x2 / t.s, gp.y2 / t.s};            // loss.py:288
-      float d[4], dfl = 0.f;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float p[kMapsReg], lse, wl;
-        int tl;
-        float vl = 0.f, vr = 0.f;
-        det_dfl_target(det_side_target(tb, t.ax, t.ay, s), tl, wl);
-#pragma unroll
-        for (int j = 0; j < kMapsReg; ++j) {
-          const float v = to_f32<T>(f[(s * kMapsReg + j) * t.hw]);
-          vl = j == tl ? v : vl; vr = j == tl + 1 ? v : vr;
-        }
-        maps_side<T>(f, t.hw, s, p, d[s], lse);
-        dfl += (lse - vl) * wl + (lse - vr) * (1.f - wl);
-      }
-      const DetBox pb{t.ax - d[0], t.ay - d[1], t.ax + d[2], t.ay + d[3]};
-      lbox = (1.f - det_ciou(pb, tb)) * t.sc;                  // loss.py:127-129
-      ldfl = dfl * 0.25f * t.sc;                               // loss.py:134: the mean over the four sides
+    for (long long r0 = i0; rows > 0 && r0 < i1; r0 += rows) {      // uniform over the workgroup
+      const long long r1 = min(r0 + rows, i1);
+      maps_segments(A.maps, r0, r1, [&](int l, size_t off, unsigned n, int row0) {
+        maps_stage_in<T>(static_cast<const T*>(A.maps.feat[l]) + off, n, row0, A.maps.no, stage, tid);
+      });
+      __syncthreads();
+      if (idx >= r0 && idx < r1) det_loss_anchor(A, det_anchor(A, idx), MapsStaged{stage + static_cast<int>(idx - r0) * pitch}, lbox, lcls, ldfl);
+      __syncthreads();                                              // the next round overwrites the rows
+    }
+  } else {
+    if (idx < total) {
+      const DetAnchor t = det_anchor(A, idx);
+      det_loss_anchor(A, t, maps_feat<T>(A.maps, t, t.b), lbox, lcls, ldfl);
     }
   }
   lbox = block_sum(lbox, tid, red);
@@ -411,30 +443,40 @@ __global__ __launch_bounds__(kBlock) void k_det_final(const DetArgs A) {
   *A.status = bad > 0.f ? 1 : 0;
 }
 
+// where k_det_bwd's gradients of one anchor go: the planes of an NCHW map, rounded to T, or the anchor's row in LDS
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_det_bwd(const DetArgs A) {
-  const long long idx = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
-  if (idx >= static_cast<long long>(A.maps.B) * A.maps.A) return;
-  const float tss = uniform_load(A.fin), Bf = static_cast<float>(A.maps.B);      // tss: divided by, not multiplied with its reciprocal (one rounding less)
-  const float fbox = uniform_load(A.upstream) * A.gain[0] * Bf / tss, fcls = uniform_load(A.upstream + 1) * A.gain[1] * Bf / tss,
-              fdfl = uniform_load(A.upstream + 2) * A.gain[2] * Bf / tss;
-  const DetAnchor t = det_anchor(A, idx);
-  const size_t off = maps_offset(A.maps, t, t.b);
-  const T* f = static_cast<const T*>(A.maps.feat[t.l]) + off;
-  T* g = static_cast<T*>(A.gfeat[t.l]) + off;
+struct DetGradPlanes {
+  T* __restrict__ g; size_t hw;
+  __device__ __forceinline__ void put(int c, float v) const { g[c * hw] = from_f32<T>(v); }
+};
+// (stored as a value of T, as DetGradPlanes stores it: detmaps.cuh, maps_stage_put)
+template <typename T>
+struct DetGradStaged {
+  float* g;
+  __device__ __forceinline__ void put(int c, float v) const { maps_stage_put<T>(g + c, v); }
+};
+template <typename T>
+struct DetGradRow {                                            // an NHWC anchor's row in global memory
+  T* g;
+  __device__ __forceinline__ void put(int c, float v) const { g[c] = from_f32<T>(v); }
+};
+// every channel's gradient of one anchor.  tss, fbox, fcls, fdfl: the call's factors (k_det_bwd).  With f and g on the same LDS row a channel is
+// written after its last read: the class channels one by one, a side's bins after maps_decode and the side's own maps_side.
+template <typename R, typename G>
+__device__ __forceinline__ void det_bwd_anchor(const DetArgs& A, const DetAnchor& t, const R& f, const G& g, float tss, float fbox, float fcls, float fdfl) {
   const int label = t.gi >= 0 ? det_label(A, t.gi) : -1;
   for (int c = 0; c < A.maps.nc; ++c) {
-    const float x = to_f32<T>(f[(4 * kMapsReg + c) * t.hw]);
-    g[(4 * kMapsReg + c) * t.hw] = from_f32<T>(fcls * (sigmoidf_(x) - (c == label ? t.sc : 0.f)));
+    const float x = f.at(4 * kMapsReg + c);
+    g.put(4 * kMapsReg + c, fcls * (sigmoidf_(x) - (c == label ? t.sc : 0.f)));
   }
   if (t.gi < 0 || !(tss == tss)) {                             // background, or the poisoned call: no box terms (NaN where poisoned)
-    const T z = from_f32<T>(t.gi < 0 && tss == tss ? 0.f : tss);
-    for (int c = 0; c < 4 * kMapsReg; ++c) g[c * t.hw] = z;
+    const float z = t.gi < 0 && tss == tss ? 0.f : tss;
+    for (int c = 0; c < 4 * kMapsReg; ++c) g.put(c, z);
     return;
   }
   const DetBox gp = det_gt_box(A, t.gi);
   const DetBox tb{gp.x1 / t.s, gp.y1 / t.s, gp.x2 / t.s, gp.y2 / t.s};
-  const DetBox pb = maps_decode<T>(f, t.hw, t.ax, t.ay);
+  const DetBox pb = maps_decode(f, t.ax, t.ay);
   float gc[4];
   det_ciou_grad(pb, tb, gc);
   // the loss is (1 - CIoU) score: x1 = ax - d_l, y1 = ay - d_t, x2 = ax + d_r, y2 = ay + d_b
@@ -444,13 +486,55 @@ __global__ __launch_bounds__(kBlock) void k_det_bwd(const DetArgs A) {
     float p[kMapsReg], d, lse, wl;
     int tl;
     const float gds = s == 0 ? gc[0] : s == 1 ? gc[1] : s == 2 ? -gc[2] : -gc[3];
-    maps_side<T>(f, t.hw, s, p, d, lse);
+    maps_side(f, s, p, d, lse);
     det_dfl_target(det_side_target(tb, t.ax, t.ay, s), tl, wl);
 #pragma unroll
     for (int j = 0; j < kMapsReg; ++j) {
       const float hit = j == tl ? wl : (j == tl + 1 ? 1.f - wl : 0.f);
-      g[(s * kMapsReg + j) * t.hw] = from_f32<T>(wdfl * (p[j] - hit) + wbox * gds * p[j] * (static_cast<float>(j) - d));
+      g.put(s * kMapsReg + j, wdfl * (p[j] - hit) + wbox * gds * p[j] * (static_cast<float>(j) - d));
     }
+  }
+}
+
+template <typename T, MapsLayout L = MapsLayout::kNCHW>
+__global__ __launch_bounds__(kBlock) void k_det_bwd(const DetArgs A) {
+  const long long idx = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x, total = static_cast<long long>(A.maps.B) * A.maps.A;
+  if constexpr (L == MapsLayout::kNCHW) {
+    if (idx >= total) return;
+  }
+  const float tss = uniform_load(A.fin), Bf = static_cast<float>(A.maps.B);      // tss: divided by, not multiplied with its reciprocal (one rounding less)
+  const float fbox = uniform_load(A.upstream) * A.gain[0] * Bf / tss, fcls = uniform_load(A.upstream + 1) * A.gain[1] * Bf / tss,
+              fdfl = uniform_load(A.upstream + 2) * A.gain[2] * Bf / tss;
+  if constexpr (L == MapsLayout::kNHWC) {                      // through LDS in rounds of whole rows, as k_det_loss; the gradients leave from the same rows
+    __shared__ float stage[kDetStageWords];
+    const int tid = static_cast<int>(threadIdx.x);
+    const long long i0 = static_cast<long long>(blockIdx.x) * kBlock, i1 = min(i0 + kBlock, total);
+    const int rows = det_stage_rows(A.maps.no), pitch = maps_stage_pitch(A.maps.no);
+    if (rows == 0 && idx < total) {                                 // a row longer than the stage (nc > 16575): read and written in place
+      const DetAnchor t = det_anchor(A, idx);
+      det_bwd_anchor(A, t, maps_feat<T, L>(A.maps, t, t.b), DetGradRow<T>{static_cast<T*>(A.gfeat[t.l]) + maps_offset<L>(A.maps, t, t.b)}, tss, fbox, fcls, fdfl);
+    }
+    for (long long r0 = i0; rows > 0 && r0 < i1; r0 += rows) {      // uniform over the workgroup
+      const long long r1 = min(r0 + rows, i1);
+      maps_segments(A.maps, r0, r1, [&](int l, size_t off, unsigned n, int row0) {
+        maps_stage_in<T>(static_cast<const T*>(A.maps.feat[l]) + off, n, row0, A.maps.no, stage, tid);
+      });
+      __syncthreads();
+      if (idx >= r0 && idx < r1) {
+        float* row = stage + static_cast<int>(idx - r0) * pitch;
+        det_bwd_anchor(A, det_anchor(A, idx), MapsStaged{row}, DetGradStaged<T>{row}, tss, fbox, fcls, fdfl);
+      }
+      __syncthreads();
+      maps_segments(A.maps, r0, r1, [&](int l, size_t off, unsigned n, int row0) {
+        maps_stage_out<T>(static_cast<T*>(A.gfeat[l]) + off, n, row0, A.maps.no, stage, tid);
+      });
+      __syncthreads();                                              // the next round overwrites the rows
+    }
+  } else {
+    const DetAnchor t = det_anchor(A, idx);
+    const size_t off = maps_offset(A.maps, t, t.b);
+    det_bwd_anchor(A, t, MapsPlanes<T>{static_cast<const T*>(A.maps.feat[t.l]) + off, t.hw}, DetGradPlanes<T>{static_cast<T*>(A.gfeat[t.l]) + off, t.hw},
+                      tss, fbox, fcls, fdfl);
   }
 }
 

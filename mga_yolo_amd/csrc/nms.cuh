@@ -4,6 +4,8 @@
 //                  image's list -- box 4 x fp32 and a 64-bit key -- at a wave prefix behind ONE atomic per wave.  The key is the score's
 //                  bits above the inverted candidate index (anchor * nc + class): keys are distinct, the largest is the next candidate
 //                  to visit, and the order the hardware appends in cannot change any result.  It also clears the status word.
+//                  The maps' layout is a compile-time parameter (detmaps.cuh: MapsLayout): in NHWC an anchor's channels are one row, read with
+//                  16-byte loads where the row's own address allows; the class order, the append and the key are the NCHW kernel's.
 //   k_nms_greedy : one workgroup per image.  max_nms: a radix select over the keys (eight 8-bit passes) finds the max_nms-th largest,
 //                  what lies below it is dead.  Then one sweep per kept row: it kills what the last kept box suppresses and finds the
 //                  largest live key (a DPP arg-max per wave, a few words through LDS).  A thread sweeps the same entries in every round,
@@ -34,39 +36,55 @@ __device__ __forceinline__ nms_key_t nms_key(float score, int cand) {
 }
 __device__ __forceinline__ int nms_key_cand(nms_key_t k) { return static_cast<int>(~static_cast<unsigned>(k)); }
 
-template <typename T>
+// the anchor's class values (probabilities from `pred`, logits from the maps) in ascending class order: fn(c, value)
+template <typename T, typename F>
+__device__ __forceinline__ void nms_classes(const MapsPlanes<T>& cls, int nc, F fn) {
+  for (int c = 0; c < nc; ++c) fn(c, cls.at(c));
+}
+template <typename T, typename F>
+__device__ __forceinline__ void nms_classes(const MapsRow<T>& cls, int nc, F fn) { cls.scan(0, nc, fn); }   // the row's own 16-byte pieces
+
+// L: the maps' layout.  NHWC: an anchor's channels are one row, read with 16-byte loads (the class logits of consecutive anchors lie `no` elements
+// apart, so the class scan touches every line of the map whatever the threshold); a decoded prediction has no such layout (api_nms.hip refuses it).
+template <typename T, MapsLayout L = MapsLayout::kNCHW>
 __global__ __launch_bounds__(kBlock) void k_nms_cand(const NmsArgs A) {
+  constexpr bool kRows = L == MapsLayout::kNHWC;
+  using Reader = typename MapsReaderOf<T, L>::type;
   const int tid = static_cast<int>(threadIdx.x), lane = tid & (kWave - 1);
   const int b = static_cast<int>(blockIdx.x) / A.bpi, a = (static_cast<int>(blockIdx.x) % A.bpi) * kBlock + tid;
   if (blockIdx.x == 0 && tid == 0) *A.status = 0;
   const bool live = a < A.maps.A;
   const int nc = A.maps.nc;
   // where the anchor's class values start and how far apart its channels lie
-  const T* cls = nullptr;
-  const T* f = nullptr;
+  Reader cls{}, f{};
   MapsAnchor t{};                                              // from pred: t.hw alone, the anchors
   if (live) {
-    if (A.pred) {
-      t.hw = static_cast<size_t>(A.maps.A);
-      f = static_cast<const T*>(A.pred) + static_cast<size_t>(b) * (4 + nc) * t.hw + a;
-      cls = f + 4 * t.hw;
-    } else {
+    if constexpr (kRows) {
       t = maps_anchor(A.maps, a);
-      f = maps_feat<T>(A.maps, t, b);
-      cls = f + 4 * kMapsReg * t.hw;
+      f = maps_feat<T, L>(A.maps, t, b);
+      cls = Reader{f.f + 4 * kMapsReg};
+    } else {
+      if (A.pred) {
+        t.hw = static_cast<size_t>(A.maps.A);
+        f = Reader{static_cast<const T*>(A.pred) + static_cast<size_t>(b) * (4 + nc) * t.hw + a, t.hw};
+        cls = Reader{f.f + 4 * t.hw, t.hw};
+      } else {
+        t = maps_anchor(A.maps, a);
+        f = maps_feat<T>(A.maps, t, b);
+        cls = Reader{f.f + 4 * kMapsReg * t.hw, t.hw};
+      }
     }
   }
-  const bool from_pred = A.pred != nullptr;
+  const bool from_pred = !kRows && A.pred != nullptr;
   // the anchor's candidates: every class over the threshold, or the best one (the lowest index among equal probabilities)
   int m = 0, best_c = 0;
   float best_p = -1.f;
   if (live) {
-    for (int c = 0; c < nc; ++c) {
-      const float v = to_f32<T>(cls[c * t.hw]);
+    nms_classes(cls, nc, [&](int c, float v) {
       const float p = from_pred ? v : sigmoidf_(v);
       if (A.multi) m += p > A.conf ? 1 : 0;
       else if (p > best_p) { best_p = p; best_c = c; }
-    }
+    });
     if (!A.multi) m = best_p > A.conf ? 1 : 0;
   }
   // the wave's place in the list: a prefix over the lanes' counts and one atomic
@@ -91,11 +109,10 @@ __global__ __launch_bounds__(kBlock) void k_nms_cand(const NmsArgs A) {
   if (m == 0) return;
   float4 box;
   if (from_pred) {                                             // ops.xywh2xyxy
-    const float cx = to_f32<T>(f[0]), cy = to_f32<T>(f[t.hw]), w2 = to_f32<T>(f[2 * t.hw]) * 0.5f, h2 = to_f32<T>(f[3 * t.hw]) * 0.5f;
+    const float cx = f.at(0), cy = f.at(1), w2 = f.at(2) * 0.5f, h2 = f.at(3) * 0.5f;
     box = make_float4(cx - w2, cy - h2, cx + w2, cy + h2);
   } else {
-    box = make_float4((t.ax - maps_dist<T>(f, t.hw, 0)) * t.s, (t.ay - maps_dist<T>(f, t.hw, 1)) * t.s, (t.ax + maps_dist<T>(f, t.hw, 2)) * t.s,
-                      (t.ay + maps_dist<T>(f, t.hw, 3)) * t.s);
+    box = make_float4((t.ax - maps_dist(f, 0)) * t.s, (t.ay - maps_dist(f, 1)) * t.s, (t.ax + maps_dist(f, 2)) * t.s, (t.ay + maps_dist(f, 3)) * t.s);
   }
   const size_t row = static_cast<size_t>(b) * A.cand_cap;
   long long at_ = static_cast<long long>(base) + before;
@@ -103,13 +120,12 @@ __global__ __launch_bounds__(kBlock) void k_nms_cand(const NmsArgs A) {
     if (at_ < A.cand_cap) { A.keys[row + at_] = nms_key(best_p, a * nc + best_c); A.boxes[row + at_] = box; }
     return;
   }
-  for (int c = 0; c < nc; ++c) {
-    const float v = to_f32<T>(cls[c * t.hw]);
+  nms_classes(cls, nc, [&](int c, float v) {
     const float p = from_pred ? v : sigmoidf_(v);
-    if (!(p > A.conf)) continue;
+    if (!(p > A.conf)) return;
     if (at_ < A.cand_cap) { A.keys[row + at_] = nms_key(p, a * nc + c); A.boxes[row + at_] = box; }
     ++at_;
-  }
+  });
 }
 
 // (key, position) arg-max over a wave: the DPP steps of wave_group_argmax on a 64-bit key in two words.  Live keys are distinct; dead

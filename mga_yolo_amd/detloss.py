@@ -1,10 +1,13 @@
 """The detection criterion of the training step (include/mgadet.h): task-aligned assignment, CIoU, DFL and BCE on the Detect head's three
 feature maps, behind the interface of the reference's `v8DetectionLoss` (ultralytics/utils/loss.py:194-297).
 
-Device tensors go through `mgadet_forward` / `mgadet_backward`: four launches forward, one backward, no host synchronisation, so the
-criterion can sit inside a captured graph (`DetLossPlan`).  Host tensors take `_host_loss`, the same semantics stated in torch ops.
+Device tensors go through `mgamaps_det_forward` / `mgamaps_det_backward` (include/ext/mgamaps.h: `mgadet_forward` / `mgadet_backward` with the
+maps' layout as a flag): four launches forward, one backward, no host synchronisation, so the criterion can sit inside a captured graph
+(`DetLossPlan`).  Maps that are torch.channels_last on every level are read in place and their gradients come back channels_last, bit for bit
+what NCHW maps of the same values give; NCHW contiguous maps likewise; anything else is made NCHW contiguous first (detmaps.maps_layout).
+Host tensors take `_host_loss`, the same semantics stated in torch ops.
 
-Not built: channels_last features (they are made contiguous here), reg_max other than 16, the rotated and the segmentation criteria, and
+Not built: levels of different layouts in one call (they are made contiguous here), reg_max other than 16, the rotated and the segmentation criteria, and
 the reference's own half-precision arithmetic under autocast: half features are read, and everything is accumulated, in fp32.
 """
 from __future__ import annotations
@@ -18,7 +21,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._binding import call, fill_det
-from .detmaps import REG_MAX, anchor_grid, check_maps, kernel_maps, raise_on_status, zero_maps
+from .detmaps import REG_MAX, anchor_grid, check_maps, device_maps, plan_maps, raise_on_status, zero_maps
 
 EPS = 1e-7
 
@@ -144,8 +147,9 @@ def _host_loss(feats, batch_idx, cls, bboxes, nc, strides, gains, topk, lowest_f
 class _DetState:
     """The buffers of one criterion call and its descriptor: outputs of the forward the backward reads again."""
 
-    def __init__(self, feats, strides, nc, topk, m_cap, gains, batch_idx, cls, bboxes, n, out=None, g_feats=None, upstream=None):
+    def __init__(self, feats, strides, nc, topk, m_cap, gains, batch_idx, cls, bboxes, n, out=None, g_feats=None, upstream=None, flags=0):
         dev = feats[0].device
+        self.flags = int(flags)                                  # 0 or _lib.MAPS_LAYOUT_NHWC: how feats and g_feats lie in memory
         B, A = feats[0].shape[0], sum(f.shape[2] * f.shape[3] for f in feats)
         i32, f32 = torch.int32, torch.float32
         self.assign_gt = torch.empty(B, A, dtype=i32, device=dev)
@@ -163,13 +167,19 @@ class _DetState:
     def bind(self, g_feats, upstream):
         fill_det(self.desc, *self.args, ws=self.ws, g_feats=g_feats, upstream=upstream)
 
+    def forward(self, dev):
+        call("mgamaps_det_forward", dev, C.byref(self.desc), self.flags)
+
+    def backward(self, dev):
+        call("mgamaps_det_backward", dev, C.byref(self.desc), self.flags)
+
 
 class _DetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, batch_idx, cls, bboxes, *feats):
-        nc, strides, gains, topk, m_cap = cfg
-        st = _DetState(feats, strides, nc, topk, m_cap, gains, batch_idx, cls, bboxes, None)
-        call("mgadet_forward", feats[0].device, C.byref(st.desc))
+        nc, strides, gains, topk, m_cap, flags = cfg
+        st = _DetState(feats, strides, nc, topk, m_cap, gains, batch_idx, cls, bboxes, None, flags=flags)
+        st.forward(feats[0].device)
         ctx.st = st
         ctx.mark_non_differentiable(st.items, st.assign_gt, st.assign_score, st.status)
         return st.out, st.items, st.assign_gt, st.assign_score, st.status
@@ -178,10 +188,11 @@ class _DetFn(torch.autograd.Function):
     def backward(ctx, g_out, *_):
         st = ctx.st
         feats = st.args[0]
-        g_feats = [torch.empty_like(f) for f in feats]
+        fmt = torch.channels_last if st.flags & _lib.MAPS_LAYOUT_NHWC else torch.contiguous_format
+        g_feats = [torch.empty_like(f, memory_format=fmt) for f in feats]           # the maps' own layout (a 1 x 1 level is both: said outright)
         up = g_out.to(torch.float32).contiguous()
         st.bind(g_feats, up)
-        call("mgadet_backward", feats[0].device, C.byref(st.desc))
+        st.backward(feats[0].device)
         return (None, None, None, None, *g_feats)
 
 
@@ -209,13 +220,13 @@ def detection_loss(feats: Sequence[torch.Tensor], batch_idx: torch.Tensor, cls: 
         b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
         loss, items, asg = _host_loss([f.float() for f in feats], b_, c_, x_, nc, strides, gains, topk)
         return (loss, items, asg) if return_assignment else (loss, items)
-    feats = kernel_maps(feats)
+    feats, flags = device_maps(feats)
     b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
     if m_cap is None:
         m_cap = int(torch.bincount(b_.long().clamp(0, feats[0].shape[0] - 1)).max()) if b_.numel() else 1
         m_cap = max(m_cap, 1)
     out, items, gt, score, status = _DetFn.apply((int(nc), tuple(int(s) for s in strides), tuple(float(g) for g in gains), int(topk),
-                                                  int(m_cap)), b_, c_, x_, *feats)
+                                                  int(m_cap), flags), b_, c_, x_, *feats)
     if not return_assignment:
         return out, items
     return out, items, assignment_views(gt, score, status, c_, x_, nc, feats[0].shape[3] * strides[0], feats[0].shape[2] * strides[0])
@@ -256,28 +267,29 @@ class DetLossPlan:
     upstream gradient in `g_out` (3, device memory).  With out=plan.det_loss and g_out=plan.g_det of a slice.SlicePlan the order is
     criterion forward -> SlicePlan.forward -> SlicePlan.backward -> criterion backward, all four in one capture."""
 
-    def __init__(self, shapes, nc, n_cap, m_cap, dtype, out, g_out, strides, gains, topk, device):
+    def __init__(self, shapes, nc, n_cap, m_cap, dtype, out, g_out, strides, gains, topk, device, channels_last=False):
         dev = torch.device(device)
         f32 = torch.float32
-        self.device, self.nc, self.strides = dev, int(nc), tuple(int(s) for s in strides)
-        self.feats = zero_maps(shapes, nc, dtype, dev)
-        self.g_feats = [torch.zeros_like(f) for f in self.feats]
+        self.device, self.nc, self.strides, self.channels_last = dev, int(nc), tuple(int(s) for s in strides), bool(channels_last)
+        self.feats = zero_maps(shapes, nc, dtype, dev, channels_last)
+        self.g_feats = zero_maps(shapes, nc, dtype, dev, channels_last)
         self.batch_idx = torch.zeros(n_cap, dtype=f32, device=dev)
         self.cls = torch.zeros(n_cap, dtype=f32, device=dev)
         self.bboxes = torch.zeros(n_cap, 4, dtype=f32, device=dev)
         self.n = torch.zeros(1, dtype=torch.int32, device=dev)
         self.g_out = g_out if g_out is not None else torch.ones(3, dtype=f32, device=dev)
         self._st = _DetState(self.feats, self.strides, nc, topk, m_cap, gains, self.batch_idx, self.cls, self.bboxes, self.n, out=out,
-                             g_feats=self.g_feats, upstream=self.g_out)
+                             g_feats=self.g_feats, upstream=self.g_out, flags=plan_maps("DetLossPlan", self.feats, channels_last))
         self.out, self.items, self.status = self._st.out, self._st.items, self._st.status
         self.assign_gt, self.assign_score = self._st.assign_gt, self._st.assign_score
 
     @classmethod
     def create(cls, shapes, nc: int, *, n_cap: int, m_cap: int, dtype=torch.float32, out=None, g_out=None, strides=(8, 16, 32),
-               gains=(7.5, 0.5, 1.5), topk: int = 10, device="cuda"):
-        """shapes: per level (B, H, W).  out / g_out: fp32 (3) device tensors to write the loss vector to / read its gradient from."""
+               gains=(7.5, 0.5, 1.5), topk: int = 10, device="cuda", channels_last: bool = False):
+        """shapes: per level (B, H, W).  out / g_out: fp32 (3) device tensors to write the loss vector to / read its gradient from.
+        channels_last: the plan's `feats` and `g_feats` are torch.channels_last (the layout a channels_last model leaves its Detect maps in)."""
         _lib.load()
-        return cls(list(shapes), nc, int(n_cap), int(m_cap), dtype, out, g_out, strides, gains, topk, device)
+        return cls(list(shapes), nc, int(n_cap), int(m_cap), dtype, out, g_out, strides, gains, topk, device, channels_last)
 
     def set_labels(self, batch_idx, cls, bboxes):
         """Copy a batch's labels into the static buffers and write their count (outside a capture)."""
@@ -288,10 +300,10 @@ class DetLossPlan:
         self.n.fill_(n)
 
     def forward(self):
-        call("mgadet_forward", self.device, C.byref(self._st.desc))
+        self._st.forward(self.device)
 
     def backward(self):
-        call("mgadet_backward", self.device, C.byref(self._st.desc))
+        self._st.backward(self.device)
 
     def check_status(self):
         """Raise if the last forward met an image with more label rows than m_cap (a host read: not inside a capture)."""

@@ -1,5 +1,6 @@
 """The Detect head's maps as the criterion (detloss.py) and the post-process (detpost.py) take them: level l is (B, 4 * REG_MAX + nc, H_l, W_l),
 the anchors are the cells' centres, level after level.  What both say about that input is said here once (csrc/detmaps.cuh: the kernels' side).
+The kernels read the maps in place in either memory layout: NCHW contiguous, or torch.channels_last on every level (`maps_layout`).
 The two host paths keep their own arithmetic on the bins: they round differently and each is pinned by its stored results."""
 import torch
 
@@ -32,8 +33,52 @@ def kernel_maps(tensors):
     return [t.contiguous() for t in tensors]
 
 
-def zero_maps(shapes, nc: int, dtype, device):                # a static plan's own maps; shapes: per level (B, H, W)
-    return [torch.zeros(B, 4 * REG_MAX + nc, H, W, dtype=dtype, device=device) for B, H, W in shapes]
+def _nchw(t) -> bool:
+    return t.is_contiguous()
+
+
+def _nhwc(t) -> bool:
+    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
+
+
+def maps_layout(tensors) -> str:
+    """How the kernels can read the maps in place: "nhwc" when every level is dense channels_last and not every one is NCHW contiguous as
+    well (a 1 x 1 level is both at once: it goes with whatever the other levels are), "nchw" when every level is NCHW contiguous, else
+    "copy": levels of different layouts, strided views and mixed or unknown element types take `kernel_maps`."""
+    tensors = list(tensors)
+    if len({t.dtype for t in tensors}) != 1 or tensors[0].dtype not in DTYPES:
+        return "copy"
+    if all(_nchw(t) for t in tensors):
+        return "nchw"
+    if all(_nhwc(t) for t in tensors):
+        return "nhwc"
+    return "copy"
+
+
+def device_maps(tensors):
+    """The maps as a device call takes them, and that call's layout flag: channels_last maps as they are with MAPS_LAYOUT_NHWC, everything
+    else through kernel_maps with 0."""
+    from ._lib import MAPS_LAYOUT_NHWC
+    if maps_layout(tensors) == "nhwc":
+        return list(tensors), MAPS_LAYOUT_NHWC
+    return kernel_maps(tensors), 0
+
+
+def plan_maps(who: str, feats, channels_last: bool):
+    """A static plan's external maps: they are read in place on every replay, so they must have the plan's layout.  Returns the flag."""
+    from ._lib import MAPS_LAYOUT_NHWC
+    want = "nhwc" if channels_last else "nchw"
+    for l, f in enumerate(feats):
+        ok = f.dtype in DTYPES and f.dtype == feats[0].dtype and (_nhwc(f) if channels_last else _nchw(f))
+        if not ok:
+            raise ValueError(f"{who}: feats[{l}] (shape {tuple(f.shape)}, strides {f.stride()}, {f.dtype}) is not a dense "
+                             f"{'channels_last' if channels_last else 'NCHW contiguous'} map of one element type (channels_last={channels_last})")
+    return MAPS_LAYOUT_NHWC if want == "nhwc" else 0
+
+
+def zero_maps(shapes, nc: int, dtype, device, channels_last: bool = False):      # a static plan's own maps; shapes: per level (B, H, W)
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    return [torch.empty(B, 4 * REG_MAX + nc, H, W, dtype=dtype, device=device, memory_format=fmt).zero_() for B, H, W in shapes]
 
 
 def raise_on_status(status: torch.Tensor, message: str) -> None:      # a plan's status word is set (a host read: not inside a capture)

@@ -2,7 +2,8 @@
 suppression on the Detect head's feature maps or on an already decoded prediction, behind the call form of the reference's
 `non_max_suppression` (ultralytics/utils/ops.py:192-338) after `Detect._inference` (ultralytics/nn/modules/head.py:150-185).
 
-Device tensors go through `mganms_run`: two launches, fixed-size outputs, no host synchronisation and no allocation, so the post-process can
+Device tensors go through `mgamaps_nms_run` (include/ext/mgamaps.h: `mganms_run` with the maps' layout as a flag; maps that are
+torch.channels_last on every level are read in place, bit for bit what NCHW maps of the same values give): two launches, fixed-size outputs, no host synchronisation and no allocation, so the post-process can
 sit inside a captured graph behind the forward (`DetPostPlan`).  Host tensors take `_host_postprocess`, the same semantics stated in torch
 ops.
 
@@ -10,7 +11,7 @@ Two departures from the reference: classes are compared instead of being moved a
 lets very wide boxes meet across classes), and half features are read and everything is computed in fp32.
 
 Not built: the `classes=` filter and `labels=` (autolabelling); `rotated`, `end2end` and extra mask channels (`nc` is taken as `C - 4`);
-reg_max other than 16; channels_last features (they are made contiguous here).
+reg_max other than 16; levels of different layouts in one call (they are made contiguous here).
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ import torch
 
 from . import _lib
 from ._binding import call, fill_nms
-from .detmaps import REG_MAX, anchor_grid, check_maps, kernel_maps, raise_on_status, zero_maps
+from .detmaps import REG_MAX, anchor_grid, check_maps, device_maps, kernel_maps, plan_maps, raise_on_status, zero_maps
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -114,8 +115,9 @@ def _flags(multi_label: bool, agnostic: bool) -> int:
 class _PostState:
     """The buffers of one post-process call and its descriptor."""
 
-    def __init__(self, feats, pred, strides, nc, conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic, cand_cap, dets=None):
+    def __init__(self, feats, pred, strides, nc, conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic, cand_cap, dets=None, layout=0):
         src = feats[0] if feats is not None else pred
+        self.layout = int(layout)                                # 0 or _lib.MAPS_LAYOUT_NHWC: how feats lie in memory
         dev, B = src.device, src.shape[0]
         A = sum(f.shape[2] * f.shape[3] for f in feats) if feats is not None else pred.shape[2]
         if cand_cap is None:
@@ -133,7 +135,7 @@ class _PostState:
         fill_nms(self.desc, *self.args, ws=self.ws)
 
     def run(self, dev):
-        call("mganms_run", dev, C.byref(self.desc))
+        call("mgamaps_nms_run", dev, C.byref(self.desc), self.layout)
 
 
 def _check_args(conf_thres, iou_thres, max_det, max_nms):
@@ -169,9 +171,9 @@ def detect_postprocess(feats, *, nc: int, strides: Sequence[int] = (8, 16, 32), 
         d, c, k = _host_postprocess(None if feats is None else [up(f) for f in feats], None if pred is None else up(pred), nc, strides,
                                     conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic)
         return d.float(), c, k
-    tensors = kernel_maps(tensors)
+    tensors, layout = device_maps(tensors) if feats is not None else (kernel_maps(tensors), 0)
     st = _PostState(tensors if feats is not None else None, tensors[0] if pred is not None else None, tuple(int(s) for s in strides),
-                    int(nc), conf_thres, iou_thres, int(max_det), int(max_nms), multi_label, agnostic, cand_cap)
+                    int(nc), conf_thres, iou_thres, int(max_det), int(max_nms), multi_label, agnostic, cand_cap, layout=layout)
     st.run(tensors[0].device)
     return st.dets, st.count, st.keep
 
@@ -210,25 +212,26 @@ class DetPostPlan:
     run() -- `dets` (B, max_det, 6), `count` (B) and `keep` (B, max_det) are written -- and read `status` outside the capture
     (check_status).  Nothing is allocated or read back by run(), and no buffer has to be cleared between replays."""
 
-    def __init__(self, feats, nc, strides, conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic, cand_cap, dets):
-        self.device, self.nc, self.strides = feats[0].device, int(nc), tuple(int(s) for s in strides)
+    def __init__(self, feats, nc, strides, conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic, cand_cap, dets, channels_last=False):
+        self.device, self.nc, self.strides, self.channels_last = feats[0].device, int(nc), tuple(int(s) for s in strides), bool(channels_last)
         self.feats = feats
         self._st = _PostState(feats, None, self.strides, self.nc, conf_thres, iou_thres, int(max_det), int(max_nms), multi_label, agnostic,
-                              cand_cap, dets=dets)
+                              cand_cap, dets=dets, layout=plan_maps("DetPostPlan", feats, channels_last))
         self.dets, self.count, self.keep, self.status = self._st.dets, self._st.count, self._st.keep, self._st.status
 
     @classmethod
     def create(cls, shapes, nc: int, *, dtype=torch.float32, strides=(8, 16, 32), conf_thres: float = 0.25, iou_thres: float = 0.45,
                max_det: int = 300, max_nms: int = 30000, multi_label: bool = False, agnostic: bool = False, cand_cap: Optional[int] = None,
-               dets=None, feats=None, device="cuda"):
+               dets=None, feats=None, device="cuda", channels_last: bool = False):
         """shapes: per level (B, H, W).  dets: an fp32 (B, max_det, 6) device tensor to write the rows to; feats: the tensors to read (the
-        forward's static outputs) instead of buffers of the plan's own."""
+        forward's static outputs) instead of buffers of the plan's own.  channels_last: the maps -- the plan's own or `feats` -- are
+        torch.channels_last; `feats` of the other layout raise ValueError (they are read in place on every replay, never copied)."""
         _lib.load()
         _check_args(conf_thres, iou_thres, max_det, max_nms)
         dev = torch.device(device)
         if feats is None:
-            feats = zero_maps(shapes, nc, dtype, dev)
-        return cls(list(feats), nc, strides, conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic, cand_cap, dets)
+            feats = zero_maps(shapes, nc, dtype, dev, channels_last)
+        return cls(list(feats), nc, strides, conf_thres, iou_thres, max_det, max_nms, multi_label, agnostic, cand_cap, dets, channels_last)
 
     def run(self):
         self._st.run(self.device)

@@ -16,7 +16,16 @@ Per row, the timed things:
 Protocol: everything is built, compared and warmed first -- the graph replay and the eager call bit for bit, the torch composition by the
 rows it keeps (reported, not asserted: random features are not guarded against near-ties) -- then timed in alternating rounds of `steps`
 calls each, the clock read after a device synchronise; a row reports each side's median over the rounds and its spread (max - min over the
-rounds).  No figure is fixed in advance."""
+rounds).  No figure is fixed in advance.
+
+    python tools/bench_nms.py --channels-last [--dtype fp32 fp16] [--out profiles/det_nhwc/bench_nms_channels_last.json]
+
+The maps' layout instead, at B = 32, 640 x 640 with nc = 1 and nc = 80 and both thresholds, three graph replays in alternating rounds:
+  nchw          NCHW maps through DetPostPlan
+  copy          channels_last maps the way they went before the kernels read them in place: a copy of every level into NCHW maps, then the
+                NCHW plan
+  native        channels_last maps through DetPostPlan(channels_last=True): no copy
+The three are compared bit for bit before anything is timed."""
 import argparse
 import json
 import os
@@ -110,6 +119,73 @@ def timed(fn, steps, dev):
     return (time.perf_counter() - t0) * 1e3 / steps
 
 
+def capture(step, dev):
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        step()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize(dev)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    return graph
+
+
+def layouts(a):
+    """--channels-last: the three arms of the module docstring"""
+    from mga_yolo_amd import DetPostPlan
+    dev = torch.device("cuda", 0)
+    rows = []
+    for cfg, (B, size, nc) in list(CONFIGS.items())[:2]:
+        if a.only and cfg not in a.only:
+            continue
+        made = make(B, size, nc)
+        for name in a.dtype:
+            dtype = dict(fp32=torch.float32, fp16=torch.float16, bf16=torch.bfloat16)[name]
+            feats = [f.to(dev, dtype) for f in made]
+            src = [f.contiguous(memory_format=torch.channels_last) for f in feats]
+            shapes = [(B, f.shape[2], f.shape[3]) for f in feats]
+            for conf in CONFS:
+                kw = dict(nc=nc, strides=STRIDES, conf_thres=conf, iou_thres=IOU, max_det=MAX_DET, max_nms=MAX_NMS)
+                nchw = DetPostPlan.create(shapes, feats=feats, **kw)
+                staged = DetPostPlan.create(shapes, dtype=dtype, **kw)           # the copy's destination: NCHW maps of the plan's own
+                native = DetPostPlan.create(shapes, feats=src, channels_last=True, **kw)
+
+                def step_copy():
+                    for dst, f in zip(staged.feats, src):
+                        dst.copy_(f)
+                    staged.run()
+                graphs = dict(nchw=capture(nchw.run, dev), copy=capture(step_copy, dev), native=capture(native.run, dev))
+                for g in graphs.values():
+                    g.replay()
+                torch.cuda.synchronize(dev)
+                native.check_status()
+                for other in (nchw, staged):
+                    assert torch.equal(native.dets, other.dets) and torch.equal(native.count, other.count) and torch.equal(native.keep, other.keep)
+                for g in graphs.values():
+                    timed(g.replay, a.warmup, dev)
+                ms = {k: [] for k in graphs}
+                for _ in range(a.rounds):                            # alternate the arms
+                    for k, g in graphs.items():
+                        ms[k].append(timed(g.replay, a.steps, dev))
+                med = {k: statistics.median(v) for k, v in ms.items()}
+                row = dict(config=cfg, dtype=name, B=B, size=size, nc=nc, conf_thres=conf, kept_rows=int(native.count.sum()),
+                           map_bytes=sum(f.numel() for f in feats) * feats[0].element_size())
+                for k in ms:
+                    row[k + "_ms"], row[k + "_spread_ms"], row[k + "_rounds_ms"] = round(med[k], 5), round(max(ms[k]) - min(ms[k]), 5), [round(v, 5) for v in ms[k]]
+                pair = [c - n for c, n in zip(ms["copy"], ms["native"])]      # the interleaved pairs' own differences
+                row["copy_minus_native_ms"], row["copy_minus_native_spread_ms"] = round(statistics.median(pair), 5), round(max(pair) - min(pair), 5)
+                row["native_vs_nchw"] = round(med["native"] / med["nchw"], 3)
+                row["native_is_the_faster"] = bool(statistics.median(pair) > max(pair) - min(pair))
+                rows.append(row)
+                print(json.dumps({k: v for k, v in row.items() if not k.endswith("_rounds_ms")}), flush=True)
+                del graphs, nchw, staged, native
+            del feats, src
+            torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -117,14 +193,17 @@ def main():
     ap.add_argument("--torch-steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", nargs="*")
-    ap.add_argument("--out", default=os.path.join("profiles", "nms", "bench_nms.json"))
+    ap.add_argument("--channels-last", action="store_true", help="time the maps' layouts instead: NCHW, channels_last by copy, channels_last native")
+    ap.add_argument("--dtype", nargs="*", default=["fp32", "fp16"], choices=["fp32", "fp16", "bf16"], help="with --channels-last")
+    ap.add_argument("--out")
     a = ap.parse_args()
+    a.out = a.out or (os.path.join("profiles", "det_nhwc", "bench_nms_channels_last.json") if a.channels_last else os.path.join("profiles", "nms", "bench_nms.json"))
     assert a.rounds >= 5, "at least 5 rounds"
     assert torch.cuda.is_available(), "this benchmark needs the GPU: there is no other path"
     from mga_yolo_amd import DetPostPlan, detect_postprocess
     dev = torch.device("cuda", 0)
-    rows = []
-    for cfg, (B, size, nc) in CONFIGS.items():
+    rows = layouts(a) if a.channels_last else []
+    for cfg, (B, size, nc) in ({} if a.channels_last else CONFIGS).items():
         if a.only and cfg not in a.only:
             continue
         feats = [f.to(dev) for f in make(B, size, nc)]
