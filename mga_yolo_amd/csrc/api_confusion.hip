@@ -2,10 +2,7 @@
 #include "detmaps_host.cuh"
 #include "confusion.cuh"
 
-#include "../../include/mgadet.h"
 #include "../../include/ext/mgaconfusion.h"
-
-#include <math.h>
 
 static_assert(kMatchMaxGt == MGADET_MAX_GT && kCmMaxNc == MGACM_MAX_NC, "CmArgs against the ABI");
 static_assert(kCmCells * sizeof(int) + kMatchWaves * sizeof(long long) <= 65536, "k_cm_count's cells fit a workgroup's static LDS");
@@ -14,18 +11,12 @@ static_assert(sizeof(mgacm_desc_t) == 152, "the descriptor's layout (mirrored by
 // Everything a descriptor is checked for that does not involve a pointer's value; fills the kernel arguments' geometry and the ws size.
 static int cm_check(const char* what, const mgacm_desc_t* D, CmArgs& A, size_t& ws_total) {
   if (!D) return fail(MGACBAM_E_NULL, "%s: desc is NULL", what);
-  if (D->B < 1 || D->max_det < 1 || D->n_cap < 0) return fail(MGACBAM_E_SHAPE, "%s: B=%d max_det=%d n_cap=%d", what, D->B, D->max_det, D->n_cap);
-  if (static_cast<long long>(D->B) * D->max_det >= (1ll << 31)) return fail(MGACBAM_E_SHAPE, "%s: B * max_det must stay below 2^31", what);
-  if (D->n_cap >= (1 << 29)) return fail(MGACBAM_E_SHAPE, "%s: n_cap=%d must stay below 2^29 (the kernels index bboxes, 4 words a row, with int)", what, D->n_cap);
+  if (int e = labels_check(what, D->B, D->max_det, D->n_cap, D->m_cap, D->reserved, D->img_w, D->img_h)) return e;
   if (D->nc < 1 || D->nc > MGACM_MAX_NC) return fail(MGACBAM_E_ARG, "%s: nc=%d (1 .. %d: (nc + 1)^2 cells of LDS)", what, D->nc, MGACM_MAX_NC);
-  if (D->m_cap < 1 || D->m_cap > MGADET_MAX_GT) return fail(MGACBAM_E_ARG, "%s: m_cap=%d (1 .. %d)", what, D->m_cap, MGADET_MAX_GT);
   if (D->flags & ~MGACM_SINGLE_CLS) return fail(MGACBAM_E_ARG, "%s: flags=0x%x", what, D->flags);
-  if (D->reserved != 0) return fail(MGACBAM_E_ARG, "%s: reserved=%d (0)", what, D->reserved);
-  if (!(D->img_w > 0.f && D->img_h > 0.f) || !isfinite(D->img_w) || !isfinite(D->img_h))
-    return fail(MGACBAM_E_ARG, "%s: img_w=%g img_h=%g (positive and finite)", what, D->img_w, D->img_h);
   if (!isfinite(D->conf_thres)) return fail(MGACBAM_E_ARG, "%s: conf_thres=%g (finite)", what, D->conf_thres);
   if (!(D->iou_thres >= 0.f && D->iou_thres < 1.f)) return fail(MGACBAM_E_ARG, "%s: iou_thres=%g (in [0, 1))", what, D->iou_thres);
-  A.B = D->B; A.max_det = D->max_det; A.n_cap = D->n_cap; A.m_cap = D->m_cap; A.nc = D->nc;
+  A.B = D->B; A.max_det = D->max_det; A.m_cap = D->m_cap; A.nc = D->nc;
   A.single_cls = D->flags & MGACM_SINGLE_CLS ? 1 : 0;
   A.img_w = D->img_w; A.img_h = D->img_h; A.conf_thres = D->conf_thres; A.iou_thres = D->iou_thres;
   Carver cv;
@@ -45,12 +36,11 @@ extern "C" size_t mgacm_ws_bytes(const mgacm_desc_t* desc) {
 static int cm_bind(const char* what, const mgacm_desc_t* D, CmArgs& A, size_t ws_total) {
   if (!D->dets || !D->count || !D->det_out || !D->cm || !D->status || !D->ws)
     return fail(MGACBAM_E_NULL, "%s: dets, count, det_out, cm, status, ws must not be NULL", what);
-  if (D->n_cap > 0 && (!D->batch_idx || !D->cls || !D->bboxes || !D->lab_out))
-    return fail(MGACBAM_E_NULL, "%s: batch_idx, cls, bboxes, lab_out must not be NULL with n_cap=%d", what, D->n_cap);
+  if (int e = labels_bind(what, D, A.labels, ", lab_out", !D->lab_out)) return e;
   if (!aligned_to(D->acc, 8)) return fail(MGACBAM_E_ALIGN, "%s: acc (int64) must be 8-byte aligned", what);
   const void* words[] = {D->dets, D->count, D->batch_idx, D->cls, D->bboxes, D->n, D->det_out, D->lab_out, D->cm, D->status};
   if (int e = check_words_and_ws(what, words, D->ws, ws_total, D->ws_bytes)) return e;
-  A.dets = D->dets; A.count = D->count; A.batch_idx = D->batch_idx; A.cls = D->cls; A.bboxes = D->bboxes; A.n_ptr = D->n;
+  A.dets = D->dets; A.count = D->count;
   A.det_out = D->det_out; A.lab_out = D->lab_out; A.cm = D->cm; A.acc = reinterpret_cast<long long*>(D->acc); A.status = D->status;
   A.over = at<int>(D->ws, 0); A.bad = A.over + D->B;
   return 0;

@@ -18,13 +18,12 @@ static int det_check(const char* what, const mgadet_desc_t* D, DetArgs& A, DetLa
   if (int e = check_dtype(what, D->dtype)) return e;
   if (D->reg_max != kMapsReg) return fail(MGACBAM_E_ARG, "%s: reg_max=%d (16 is the one built)", what, D->reg_max);
   if (D->topk < 1 || D->topk > MGADET_MAX_TOPK) return fail(MGACBAM_E_ARG, "%s: topk=%d (1 .. %d)", what, D->topk, MGADET_MAX_TOPK);
-  if (D->m_cap < 1 || D->m_cap > MGADET_MAX_GT) return fail(MGACBAM_E_ARG, "%s: m_cap=%d (1 .. %d)", what, D->m_cap, MGADET_MAX_GT);
-  if (D->reserved != 0) return fail(MGACBAM_E_ARG, "%s: reserved=%d (0)", what, D->reserved);
+  if (int e = labels_caps(what, D->m_cap, D->reserved)) return e;
   if (D->n_cap < 0) return fail(MGACBAM_E_SHAPE, "%s: n_cap=%d", what, D->n_cap);
   if (int e = maps_check(what, D->n_levels, D->H, D->W, D->stride, D->B, D->nc, true, A.maps)) return e;
   if (static_cast<long long>(D->W[0]) * D->stride[0] > (1 << 24) || static_cast<long long>(D->H[0]) * D->stride[0] > (1 << 24))
     return fail(MGACBAM_E_SHAPE, "%s: an image side above 2^24 pixels", what);
-  A.topk = D->topk; A.n_cap = D->n_cap; A.m_cap = D->m_cap;
+  A.topk = D->topk; A.m_cap = D->m_cap;
   for (int k = 0; k < 3; ++k) A.gain[k] = D->gains[k];
   A.img_w = static_cast<float>(D->W[0] * D->stride[0]); A.img_h = static_cast<float>(D->H[0] * D->stride[0]);
   A.nblk = static_cast<int>((static_cast<long long>(D->B) * A.maps.A + kBlock - 1) / kBlock);
@@ -56,7 +55,7 @@ static int det_bind(const char* what, const mgadet_desc_t* D, DetArgs& A, const 
     return fail(MGACBAM_E_NULL, "%s: assign_gt, assign_score, out, items, status, ws%s must not be NULL", what, bwd ? ", upstream" : "");
   const void* words[] = {D->batch_idx, D->cls, D->bboxes, D->n, D->assign_gt, D->assign_score, D->out, D->items, D->status, D->upstream};
   if (int e = check_words_and_ws(what, words, D->ws, L.total, D->ws_bytes)) return e;
-  A.batch_idx = D->batch_idx; A.cls = D->cls; A.bboxes = D->bboxes; A.n_ptr = D->n;
+  A.labels = LabelBatch{D->batch_idx, D->cls, D->bboxes, D->n, D->n_cap};
   A.asg_gt = D->assign_gt; A.asg_score = D->assign_score;
   A.cand_n = at<int>(D->ws, L.cand_n); A.cand_row = at<int>(D->ws, L.cand_row); A.cand_anchor = at<int>(D->ws, L.cand_anchor);
   A.cand_metric = at(D->ws, L.cand_metric); A.cand_overlap = at(D->ws, L.cand_overlap);

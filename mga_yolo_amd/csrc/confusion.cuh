@@ -1,6 +1,6 @@
 // The validator's confusion matrix (include/ext/mgaconfusion.h), without a host read-back: the third stage behind the post-process and the matching.
-//   k_cm_match : one workgroup per image.  The image's label rows are staged in LDS exactly as k_match stages them (match_common.cuh: flat order,
-//                chunks of kMatchStage kBlock rows, prefix sums, no atomics).  Every thread strides over the image's detections; a counted one
+//   k_cm_match : one workgroup per image.  The image's label rows are staged in LDS as k_match stages them (labels.cuh: labels_stage -- flat order,
+//                prefix sums, no atomics).  Every thread strides over the image's detections; a counted one
 //                (conf > conf_thres) keeps the largest IoU above iou_thres over ALL the labels, whatever their classes -- a strict `>` over
 //                ascending slots that starts at the threshold, so equal IoUs go to the lower label row and a NaN never wins.  One 64-bit
 //                atomicMax in LDS per label on (IoU bits << 32 | ~d) finds w(l): the largest IoU, among equals the lowest detection -- the
@@ -10,7 +10,7 @@
 //                (nc + 1)^2 LDS cells with LDS integer atomics (integer sums: the order of arrival does not show), stores the per-call
 //                matrix with plain stores and adds it to the run-long int64 matrix -- no global atomics, no zeroing launch.
 #pragma once
-#include "match_common.cuh"
+#include "labels.cuh"
 
 namespace mgacbam {
 
@@ -19,8 +19,8 @@ constexpr int kCmCells = (kCmMaxNc + 1) * (kCmMaxNc + 1);
 
 struct CmArgs {
   const float* dets; const int* count;
-  const float* batch_idx; const float* cls; const float* bboxes; const int* n_ptr;
-  int B, max_det, n_cap, m_cap, nc, single_cls;
+  LabelBatch labels;
+  int B, max_det, m_cap, nc, single_cls;
   float img_w, img_h, conf_thres, iou_thres;
   int* det_out; int* lab_out; int* cm; long long* acc; int* status;
   int* over;                                                   // ws, (B): 1 for an image with more than m_cap label rows
@@ -44,41 +44,24 @@ __global__ __launch_bounds__(kBlock) void k_cm_match(const CmArgs A) {
   __shared__ int s_wave[kMatchWaves];
   __shared__ int s_bad;
   const int tid = static_cast<int>(threadIdx.x), b = static_cast<int>(blockIdx.x);
-  const int n = match_live_labels(A), cnt = match_live_rows(A, b), nc = A.nc;
-  const float fb = static_cast<float>(b), fB = static_cast<float>(A.B);
+  const int n = labels_live(A.labels), cnt = match_live_rows(A, b), nc = A.nc;
+  const float fB = static_cast<float>(A.B);
   if (tid == 0) s_bad = 0;
   __syncthreads();
   if (b == 0)                                                  // the rows behind the n word and the rows of no image
-    for (int r = tid; r < A.n_cap; r += kBlock)
-      if (r >= n || !match_has_image(A.batch_idx[r], fB)) A.lab_out[r] = -1;
-  // the image's label rows, in flat order
-  int m = 0;                                                   // rows met so far (uniform)
+    for (int r = tid; r < A.labels.n_cap; r += kBlock)
+      if (r >= n || !labels_has_image(A.labels.batch_idx[r], fB)) A.lab_out[r] = -1;
   bool bad = false;
-  for (int base = 0; base < n; base += kMatchStage * kBlock) {
-    const int r0 = base + tid * kMatchStage;
-    bool mine[kMatchStage];
-    int c = 0;
-#pragma unroll
-    for (int u = 0; u < kMatchStage; ++u) { mine[u] = r0 + u < n && A.batch_idx[r0 + u] == fb; c += mine[u] ? 1 : 0; }
-    int total;
-    int slot = m + match_block_offset(c, tid, s_wave, total);
-#pragma unroll
-    for (int u = 0; u < kMatchStage; ++u) {
-      if (!mine[u]) continue;
-      const int r = r0 + u;
-      int lc;
-      if (!cm_class(A.cls[r], nc, A.single_cls, lc)) bad = true;
-      if (slot < A.m_cap) {
-        const float cx = A.bboxes[4 * r], cy = A.bboxes[4 * r + 1], w2 = A.bboxes[4 * r + 2] / 2.f, h2 = A.bboxes[4 * r + 3] / 2.f;
-        const float4 q = make_float4((cx - w2) * A.img_w, (cy - h2) * A.img_h, (cx + w2) * A.img_w, (cy + h2) * A.img_h);
-        s_box[slot] = q; s_area[slot] = match_area(q); s_cls[slot] = lc; s_row[slot] = r;
-      } else {
-        A.lab_out[r] = -1;                                     // past m_cap: the image cannot be answered
-      }
-      ++slot;
+  const int m = labels_stage(A.labels, n, b, tid, s_wave, [&](int slot, int r) {
+    int lc;
+    if (!cm_class(A.labels.cls[r], A.nc, A.single_cls, lc)) bad = true;
+    if (slot < A.m_cap) {
+      const float4 q = labels_box_val(A.labels, r, A.img_w, A.img_h);
+      s_box[slot] = q; s_area[slot] = match_area(q); s_cls[slot] = lc; s_row[slot] = r;
+    } else {
+      A.lab_out[r] = -1;                                       // past m_cap: the image cannot be answered
     }
-    m += total;
-  }
+  });
   const bool over = m > A.m_cap;
   const size_t row0 = static_cast<size_t>(b) * A.max_det;
   int* det_out = A.det_out + row0;
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_cm_count(const CmArgs A) {
   }
   for (int i = tid; i < cells; i += kBlock) s_cm[i] = 0;
   __syncthreads();
-  const int n = match_live_labels(A);
+  const int n = labels_live(A.labels);
   const int rows = A.B * A.max_det;
   for (int i = tid; i < rows; i += kBlock) {                   // a counted detection that is nobody's winner: [cls(d), nc]
     if (A.det_out[i] != nc) continue;
@@ -179,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void k_cm_count(const CmArgs A) {
     const int v = A.lab_out[r];
     if (v < 0 || v > nc) continue;
     int c;
-    if (cm_class(A.cls[r], nc, A.single_cls, c)) atomicAdd(&s_cm[v * side + c], 1);
+    if (cm_class(A.labels.cls[r], nc, A.single_cls, c)) atomicAdd(&s_cm[v * side + c], 1);
   }
   __syncthreads();
   for (int i = tid; i < cells; i += kBlock) {

@@ -14,6 +14,7 @@
 // No atomics on floating-point sums: every sum has a fixed order, two runs give the same bits.
 #pragma once
 #include "detmaps.cuh"
+#include "labels.cuh"
 
 namespace mgacbam {
 
@@ -24,10 +25,10 @@ constexpr int kDetChunk = 2048;                // cells a k_det_assign workgroup
 struct DetArgs {
   DetMaps maps;                                // the Detect maps (detmaps.cuh)
   void* gfeat[kMapsLevelsMax];                 // their gradients, in the same layout
-  int topk, n_cap, m_cap;
+  int topk, m_cap;
   float gain[3];
   float img_w, img_h;                          // W_0 * stride_0, H_0 * stride_0
-  const float* batch_idx; const float* cls; const float* bboxes; const int* n_ptr;
+  LabelBatch labels;                           // the batch's labels (labels.cuh)
   int* asg_gt; float* asg_score;               // (B, A): the label row an anchor is assigned to (-1: background), its target score
   int* cand_n; int* cand_row;                  // (B, m_cap): candidates kept, the slot's label row (-1: the image has fewer rows)
   int* cand_anchor; float* cand_metric; float* cand_overlap;   // (B, m_cap, kDetTopkMax)
@@ -39,18 +40,9 @@ struct DetArgs {
   const float* upstream;
 };
 
-__device__ __forceinline__ int det_n(const DetArgs& A) {
-  const int n = A.n_ptr ? *A.n_ptr : A.n_cap;
-  return min(max(n, 0), A.n_cap);
-}
-// loss.py:231 and ops.xywh2xyxy: the row scaled by (W, H, W, H), then centre -+ half the size
-__device__ __forceinline__ DetBox det_gt_box(const DetArgs& A, int r) {
-  const float cx = A.bboxes[4 * r] * A.img_w, cy = A.bboxes[4 * r + 1] * A.img_h;
-  const float hw = A.bboxes[4 * r + 2] * A.img_w * 0.5f, hh = A.bboxes[4 * r + 3] * A.img_h * 0.5f;
-  return DetBox{cx - hw, cy - hh, cx + hw, cy + hh};
-}
+__device__ __forceinline__ DetBox det_gt_box(const DetArgs& A, int r) { return labels_box_loss<DetBox>(A.labels, r, A.img_w, A.img_h); }
 __device__ __forceinline__ bool det_gt_valid(const DetBox& g) { return ((g.x1 + g.y1) + g.x2) + g.y2 > 0.f; }      // loss.py:263
-__device__ __forceinline__ int det_label(const DetArgs& A, int r) { return min(max(static_cast<int>(A.cls[r]), 0), A.maps.nc - 1); }
+__device__ __forceinline__ int det_label(const DetArgs& A, int r) { return min(max(static_cast<int>(A.labels.cls[r]), 0), A.maps.nc - 1); }
 
 // metrics.py:113-141 with xywh=False, CIoU=True: box1's and box2's heights carry the eps
 constexpr float kDetEps = 1e-7f;
@@ -135,12 +127,12 @@ __global__ __launch_bounds__(kBlock) void k_det_assign(const DetArgs A) {
     }
   }
   // loss.py:217-232: the g-th row whose batch_idx is b
-  const int n = det_n(A);
+  const int n = labels_live(A.labels);
   if (tid == 0) s_row = -1;
   int base = 0;
   for (int r0 = 0; r0 < n; r0 += kBlock) {
     const int r = r0 + tid;
-    const bool mine = r < n && A.batch_idx[r] == static_cast<float>(b);
+    const bool mine = r < n && A.labels.batch_idx[r] == static_cast<float>(b);
     const unsigned long long mask = __ballot(mine);
     __syncthreads();
     if (lane == 0) s_cnt[wave] = __popcll(mask);
@@ -265,9 +257,9 @@ __global__ __launch_bounds__(kBlock) void k_det_resolve(const DetArgs A) {
     e_gt[e] = static_cast<short>(g);
   }
   {                                                            // an image with more rows than slots: the call's status
-    const int n = det_n(A);
+    const int n = labels_live(A.labels);
     float cnt = 0.f;
-    for (int r = tid; r < n; r += kBlock) cnt += A.batch_idx[r] == static_cast<float>(b) ? 1.f : 0.f;
+    for (int r = tid; r < n; r += kBlock) cnt += A.labels.batch_idx[r] == static_cast<float>(b) ? 1.f : 0.f;
     cnt = block_sum(cnt, tid, red);
     if (tid == 0) A.ovf[b] = cnt > static_cast<float>(M) ? 1 : 0;
   }

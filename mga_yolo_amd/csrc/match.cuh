@@ -1,6 +1,6 @@
 // Matching detections to labels for the validation metrics (include/ext/mgamatch.h), without a host read-back.
-//   k_match        : one workgroup per image.  The image's rows of the flat label list are staged in LDS in flat order (a prefix over the
-//                    threads' counts per chunk of 4 kBlock rows: no atomics, so a slot is the row's rank within its image).  Every thread strides over the
+//   k_match        : one workgroup per image.  The image's rows of the flat label list are staged in LDS in flat order (labels.cuh:
+//                    labels_stage, so a slot is the row's rank within its image).  Every thread strides over the
 //                    image's detections and keeps the largest class-matched IoU and its slot -- a strict `>` over ascending slots, so equal
 //                    IoUs go to the lower label row.  Per threshold an integer atomicMin in LDS over owner[t][slot] finds the lowest
 //                    detection that qualifies: the minimum of a set, whatever order its members arrive in.  tp[d, t] = owner[t][slot] == d.
@@ -12,7 +12,7 @@
 //                    rank within it -- prefix sums, no atomics, so the place of a row does not depend on arrival.  Workgroup 0 alone advances
 //                    state and writes the status word; the others read only the snapshot.
 #pragma once
-#include "match_common.cuh"
+#include "labels.cuh"
 
 namespace mgacbam {
 
@@ -20,8 +20,8 @@ constexpr int kMatchMaxIou = 16;               // MGAMATCH_MAX_IOU
 
 struct MatchArgs {
   const float* dets; const int* count;
-  const float* batch_idx; const float* cls; const float* bboxes; const int* n_ptr;
-  int B, max_det, n_cap, m_cap, niou, single_cls;
+  LabelBatch labels;
+  int B, max_det, m_cap, niou, single_cls;
   float img_w, img_h;
   float iouv[kMatchMaxIou];
   int rows_cap, tgt_cap;
@@ -41,31 +41,13 @@ __global__ __launch_bounds__(kBlock) void k_match(const MatchArgs A) {
   __shared__ int s_owner[kMatchMaxIou][kMatchMaxGt];
   __shared__ int s_wave[kMatchWaves];
   const int tid = static_cast<int>(threadIdx.x), b = static_cast<int>(blockIdx.x);
-  const int n = match_live_labels(A), cnt = match_live_rows(A, b), niou = A.niou;
-  const float fb = static_cast<float>(b);
-  // the image's label rows, in flat order
-  int m = 0;                                                   // rows met so far (uniform)
-  for (int base = 0; base < n; base += kMatchStage * kBlock) {   // kMatchStage consecutive rows per thread: a quarter of the barriers
-    const int r0 = base + tid * kMatchStage;
-    bool mine[kMatchStage];
-    int c = 0;
-#pragma unroll
-    for (int u = 0; u < kMatchStage; ++u) { mine[u] = r0 + u < n && A.batch_idx[r0 + u] == fb; c += mine[u] ? 1 : 0; }
-    int total;
-    int slot = m + match_block_offset(c, tid, s_wave, total);
-#pragma unroll
-    for (int u = 0; u < kMatchStage; ++u) {
-      if (!mine[u]) continue;
-      if (slot < A.m_cap) {
-        const int r = r0 + u;
-        const float cx = A.bboxes[4 * r], cy = A.bboxes[4 * r + 1], w2 = A.bboxes[4 * r + 2] / 2.f, h2 = A.bboxes[4 * r + 3] / 2.f;
-        const float4 q = make_float4((cx - w2) * A.img_w, (cy - h2) * A.img_h, (cx + w2) * A.img_w, (cy + h2) * A.img_h);
-        s_box[slot] = q; s_area[slot] = match_area(q); s_cls[slot] = A.cls[r]; s_row[slot] = r;
-      }
-      ++slot;
+  const int n = labels_live(A.labels), cnt = match_live_rows(A, b), niou = A.niou;
+  const int m = labels_stage(A.labels, n, b, tid, s_wave, [&](int slot, int r) {
+    if (slot < A.m_cap) {
+      const float4 q = labels_box_val(A.labels, r, A.img_w, A.img_h);
+      s_box[slot] = q; s_area[slot] = match_area(q); s_cls[slot] = A.labels.cls[r]; s_row[slot] = r;
     }
-    m += total;
-  }
+  });
   const bool over = m > A.m_cap;
   if (tid == 0) A.over[b] = over ? 1 : 0;
   if (b == 0 && tid < 3 && A.state) A.snap[tid] = A.state[tid];  // k_match_append's workgroups read the counters here while one advances them
@@ -138,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void k_match_append(const MatchArgs A) {
   __shared__ long long s_sum[kMatchWaves];
   __shared__ int s_wave[kMatchWaves];
   const int tid = static_cast<int>(threadIdx.x), wg = static_cast<int>(blockIdx.x);
-  const int n = match_live_labels(A), niou = A.niou;
+  const int n = labels_live(A.labels), niou = A.niou;
   const float fB = static_cast<float>(A.B);
   const bool accumulate = A.state != nullptr;
   const int r0 = (wg - A.B) * kBlock;                          // a label workgroup's first row
@@ -150,7 +132,7 @@ __global__ __launch_bounds__(kBlock) void k_match_append(const MatchArgs A) {
   }
   if (accumulate)
     for (int r = tid; r < n; r += kBlock) {
-      const int mine = match_has_image(A.batch_idx[r], fB) ? 1 : 0;
+      const int mine = labels_has_image(A.labels.batch_idx[r], fB) ? 1 : 0;
       tgts += mine;
       if (wg >= A.B && r < r0) before += mine;
     }
@@ -194,11 +176,11 @@ __global__ __launch_bounds__(kBlock) void k_match_append(const MatchArgs A) {
   }
   // the label rows that belong to an image, in flat order
   const int r = r0 + tid;
-  const float bi = r < n ? A.batch_idx[r] : -1.f;
-  const bool mine = match_has_image(bi, fB);
+  const float bi = r < n ? A.labels.batch_idx[r] : -1.f;
+  const bool mine = labels_has_image(bi, fB);
   int total;
   const int k = n_tgts + static_cast<int>(before) + match_block_offset(mine ? 1 : 0, tid, s_wave, total);
-  if (mine) { A.tgt_cls[k] = A.cls[r]; A.tgt_img[k] = seen + static_cast<int>(bi); }
+  if (mine) { A.tgt_cls[k] = A.labels.cls[r]; A.tgt_img[k] = seen + static_cast<int>(bi); }
 }
 
 }  // namespace mgacbam

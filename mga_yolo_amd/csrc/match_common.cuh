@@ -1,6 +1,6 @@
-// What the kernels of csrc/match.cuh and csrc/confusion.cuh share: the staging geometry of an image's label rows, the live-row clamps, the
-// workgroup prefix and sum, and the reference's fp32 box_iou on one pair.  Units that include it are compiled with -ffp-contract=off
-// (build.UNIT_FLAGS).
+// What the kernels of csrc/match.cuh and csrc/confusion.cuh share about (label, detection) pairs: the staging geometry, an image's live
+// detection rows, the workgroup prefix and sum, and the reference's fp32 box_iou on one pair.  The labels themselves are csrc/labels.cuh's.
+// Units that call match_iou are compiled with -ffp-contract=off (build.UNIT_FLAGS).
 #pragma once
 #include "common.cuh"
 
@@ -10,12 +10,7 @@ constexpr int kMatchMaxGt = 256;               // MGADET_MAX_GT
 constexpr int kMatchWaves = kBlock / kWave;
 constexpr int kMatchStage = 4;                 // label rows a thread looks at per staging chunk
 
-// the live label rows and an image's live detection rows (Args: MatchArgs or CmArgs, which name the same fields)
-template <typename Args>
-__device__ __forceinline__ int match_live_labels(const Args& A) {
-  const int n = A.n_ptr ? *A.n_ptr : A.n_cap;
-  return n < 0 ? 0 : (n > A.n_cap ? A.n_cap : n);
-}
+// an image's live detection rows (Args: MatchArgs or CmArgs)
 template <typename Args>
 __device__ __forceinline__ int match_live_rows(const Args& A, int b) {
   const int c = A.count[b];
@@ -72,6 +67,5 @@ __device__ __forceinline__ long long match_block_sum(long long v, int tid, long 
   for (int w = 0; w < kMatchWaves; ++w) tot += s_sum[w];
   return tot;
 }
-__device__ __forceinline__ bool match_has_image(float bi, float fB) { return bi >= 0.f && bi < fB && bi == floorf(bi); }
 
 }  // namespace mgacbam

@@ -28,7 +28,9 @@ import torch
 
 from . import _lib
 from ._binding import call, fill_confusion
-from .detmatch import IOU_EPS, DetMatchPlan, _img_wh, _label_boxes, _labels
+from .detlabels import LabelBuffers, as_labels, img_wh, label_boxes, pair_iou, plan_dets, rows_per_image, size_m_cap, sized_ws
+from .detmaps import raise_on_status
+from .detmatch import DetMatchPlan
 
 
 def reference_conf(conf) -> float:
@@ -57,8 +59,7 @@ def _host_confusion(dets, count, batch_idx, cls, bboxes, img_w: float, img_h: fl
     B, D = dets.shape[:2]
     dt, dev = dets.dtype, dets.device
     N = batch_idx.numel()
-    idx = batch_idx.to(torch.int64)
-    belongs = (batch_idx >= 0) & (batch_idx < B) & (batch_idx == idx)
+    rows, has, belongs = rows_per_image(batch_idx, B)
     live = torch.arange(D, device=dev)[None] < count.to(torch.int64).clamp(0, D)[:, None]
     counted = live & (dets[..., 4] > torch.tensor(conf_thres, dtype=torch.float32).to(dt))
     cm = torch.zeros(nc + 1, nc + 1, dtype=torch.int64, device=dev)
@@ -73,24 +74,10 @@ def _host_confusion(dets, count, batch_idx, cls, bboxes, img_w: float, img_h: fl
         dc = torch.where(counted, dets[..., 5], torch.zeros((), dtype=dt, device=dev)).to(torch.int64)
         lc_flat = torch.where(belongs, cls.to(dt), torch.zeros((), dtype=dt, device=dev)).to(torch.int64)
     det_out[counted] = nc
-    per = torch.bincount(idx[belongs], minlength=B) if bool(belongs.any()) else torch.zeros(B, dtype=torch.int64, device=dev)
-    M = int(per.max())
+    M = rows.shape[1]
     if M:
-        rows = torch.full((B, M), -1, dtype=torch.int64, device=dev)                 # per image its label rows in flat order
-        for b in range(B):
-            r = torch.nonzero(belongs & (idx == b)).flatten()
-            rows[b, :r.numel()] = r
-        has = rows >= 0
         safe = rows.clamp(min=0)
-        lb = _label_boxes(bboxes.to(dt), img_w, img_h)[safe]                         # (B, M, 4)
-        db = dets[..., :4]
-        # ultralytics/utils/metrics.py:53-74, label x detection -> here (B, D, M)
-        iw = (torch.minimum(lb[:, None, :, 2], db[:, :, None, 2]) - torch.maximum(lb[:, None, :, 0], db[:, :, None, 0])).clamp(min=0)
-        ih = (torch.minimum(lb[:, None, :, 3], db[:, :, None, 3]) - torch.maximum(lb[:, None, :, 1], db[:, :, None, 1])).clamp(min=0)
-        inter = iw * ih
-        area_l = (lb[..., 2] - lb[..., 0]) * (lb[..., 3] - lb[..., 1])
-        area_d = (db[..., 2] - db[..., 0]) * (db[..., 3] - db[..., 1])
-        iou = inter / (area_l[:, None, :] + area_d[:, :, None] - inter + IOU_EPS)
+        iou = pair_iou(label_boxes(bboxes.to(dt), img_w, img_h)[safe], dets[..., :4])                       # (B, D, M)
         qual = has[:, None, :] & counted[:, :, None] & (iou > torch.tensor(iou_thres, dtype=torch.float32).to(dt))
         none = torch.full((), -1, dtype=dt, device=dev)
         iou = torch.where(qual, iou, none)
@@ -130,10 +117,7 @@ class _ConfusionState:
         self.acc = acc
         self.args = (dets, count, batch_idx, cls, bboxes, n, m_cap, nc, _lib.CM_SINGLE_CLS if single_cls else 0, img_w, img_h, conf_thres,
                      iou_thres, self.det_out, self.lab_out, self.cm, acc, self.status)
-        self.desc = _lib.ConfusionDesc()
-        fill_confusion(self.desc, *self.args)
-        self.ws = torch.empty(_lib.confusion_ws_bytes(self.desc), dtype=torch.uint8, device=dev)
-        fill_confusion(self.desc, *self.args, ws=self.ws)
+        self.desc, self.ws = sized_ws(_lib.ConfusionDesc(), fill_confusion, _lib.confusion_ws_bytes, self.args, dev)
 
     def run(self, dev):
         call("mgacm_run", dev, C.byref(self.desc))
@@ -155,21 +139,16 @@ def confusion_matrix(dets: torch.Tensor, count: torch.Tensor, batch_idx: torch.T
     if nc < 1:
         raise ValueError(f"confusion_matrix: nc={nc}")
     conf_thres, iou_thres = _thresholds(conf, iou_thres)
-    img_w, img_h = _img_wh(imgsz)
+    img_w, img_h = img_wh(imgsz)
     dev = dets.device
+    b_, c_, x_ = as_labels(batch_idx, cls, bboxes, dev)
     if not dets.is_cuda:
         if any(t.is_cuda for t in (count, batch_idx, cls, bboxes)):
             raise RuntimeError("confusion_matrix: the tensors must all live on the GPU or all on the host")
-        b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
         d_ = dets if dets.dtype == torch.float64 else dets.float()
         return _host_confusion(d_, count, b_, c_, x_, img_w, img_h, int(nc), conf_thres, iou_thres, single_cls)
-    b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
-    B = dets.shape[0]
-    if m_cap is None:
-        inside = b_[(b_ >= 0) & (b_ < B)].long()
-        m_cap = max(int(torch.bincount(inside).max()) if inside.numel() else 1, 1)
-    st = _ConfusionState(dets.to(torch.float32).contiguous(), count.to(dev, torch.int32).contiguous(), b_, c_, x_, None, int(m_cap), int(nc),
-                         img_w, img_h, conf_thres, iou_thres, single_cls)
+    st = _ConfusionState(dets.to(torch.float32).contiguous(), count.to(dev, torch.int32).contiguous(), b_, c_, x_, None,
+                         size_m_cap(b_, dets.shape[0]) if m_cap is None else int(m_cap), int(nc), img_w, img_h, conf_thres, iou_thres, single_cls)
     st.run(dev)
     return st.cm.long(), st.det_out, st.lab_out
 
@@ -182,17 +161,11 @@ class ConfusionPlan:
 
     def __init__(self, dets, count, labels, n_cap, m_cap, nc, img_w, img_h, conf_thres, iou_thres, single_cls, accumulate):
         dev = dets.device
-        f32, i32 = torch.float32, torch.int32
         self.device, self.nc = dev, nc
         self.dets, self.count = dets, count
-        self._labels = labels
-        if labels is not None:
-            self.batch_idx, self.cls, self.bboxes, self.n = labels.batch_idx, labels.cls, labels.bboxes, labels.n
-        else:
-            self.batch_idx = torch.zeros(n_cap, dtype=f32, device=dev)
-            self.cls = torch.zeros(n_cap, dtype=f32, device=dev)
-            self.bboxes = torch.zeros(n_cap, 4, dtype=f32, device=dev)
-            self.n = torch.zeros(1, dtype=i32, device=dev)
+        self.labels = lab = labels.labels if labels is not None else LabelBuffers(n_cap, dev)      # the DetMatchPlan's own object, or this plan's
+        self.batch_idx, self.cls, self.bboxes, self.n = lab.batch_idx, lab.cls, lab.bboxes, lab.n
+        self._who = "ConfusionPlan" if labels is None else "DetMatchPlan"                           # whose buffers set_labels() fills
         self.acc = torch.zeros(nc + 1, nc + 1, dtype=torch.int64, device=dev) if accumulate else None
         self._st = _ConfusionState(dets, count, self.batch_idx, self.cls, self.bboxes, self.n, m_cap, nc, img_w, img_h, conf_thres, iou_thres,
                                    single_cls, acc=self.acc)
@@ -211,28 +184,17 @@ class ConfusionPlan:
             if n_cap is not None and int(n_cap) != labels.batch_idx.numel():
                 raise ValueError(f"ConfusionPlan: n_cap={n_cap}, the DetMatchPlan holds {labels.batch_idx.numel()} label rows")
             n_cap = labels.batch_idx.numel()
+            dets, count = labels.dets if dets is None else dets, labels.count if count is None else count
         elif n_cap is None:
             raise ValueError("ConfusionPlan: n_cap or labels must be given")
-        if dets is None:
-            dets = labels.dets if labels is not None else torch.zeros(B, max_det, 6, dtype=torch.float32, device=dev)
-        if count is None:
-            count = labels.count if labels is not None else torch.zeros(B, dtype=torch.int32, device=dev)
-        if tuple(dets.shape) != (B, max_det, 6) or dets.dtype != torch.float32 or not dets.is_contiguous() or tuple(count.shape) != (B,) \
-                or count.dtype != torch.int32:
-            raise ValueError(f"ConfusionPlan: dets must be a contiguous fp32 ({B}, {max_det}, 6) tensor and count int32 ({B})")
+        dets, count = plan_dets("ConfusionPlan", dets, count, B, max_det, dev)
         conf_thres, iou_thres = _thresholds(conf, iou_thres)
-        img_w, img_h = _img_wh(imgsz)
+        img_w, img_h = img_wh(imgsz)
         return cls(dets, count, labels, int(n_cap), int(m_cap), int(nc), img_w, img_h, conf_thres, iou_thres, bool(single_cls), bool(accumulate))
 
     def set_labels(self, batch_idx, cls, bboxes):
         """Copy a batch's labels into the static buffers and write their count (outside a capture); with labels= it is the DetMatchPlan's."""
-        if self._labels is not None:
-            return self._labels.set_labels(batch_idx, cls, bboxes)
-        n = batch_idx.numel()
-        if n > self.batch_idx.numel():
-            raise ValueError(f"ConfusionPlan: {n} label rows, the plan holds {self.batch_idx.numel()}")
-        self.batch_idx[:n].copy_(batch_idx.reshape(-1)); self.cls[:n].copy_(cls.reshape(-1)); self.bboxes[:n].copy_(bboxes.reshape(-1, 4))
-        self.n.fill_(n)
+        self.labels.set(batch_idx, cls, bboxes, self._who)
 
     def run(self):
         self._st.run(self.device)
@@ -246,14 +208,9 @@ class ConfusionPlan:
     def check_status(self):
         """Raise if the last run counted nothing: an image with more label rows than m_cap, or a class outside 0 .. nc - 1 (a host
         read: not inside a capture)."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        s = int(self.status.item())
-        if s == 1:
-            raise RuntimeError("ConfusionPlan: an image has more label rows than m_cap; cm is zeros and nothing was accumulated")
-        if s == 3:
-            raise RuntimeError(f"ConfusionPlan: a counted detection or a label has a class outside 0 .. {self.nc - 1}; cm is zeros and "
-                               "nothing was accumulated")
+        raise_on_status(self.status, {1: "ConfusionPlan: an image has more label rows than m_cap; cm is zeros and nothing was accumulated",
+                                      3: f"ConfusionPlan: a counted detection or a label has a class outside 0 .. {self.nc - 1}; cm is zeros "
+                                         "and nothing was accumulated"})
 
     def matrix(self) -> torch.Tensor:
         """The run's accumulated matrix, (nc + 1, nc + 1) int64 on the host.  One read-back."""

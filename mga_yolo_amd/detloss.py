@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._binding import call, fill_det
+from .detlabels import LabelBuffers, as_labels, loss_boxes, rows_per_image, sized_ws
 from .detmaps import REG_MAX, anchor_grid, check_maps, device_maps, plan_maps, raise_on_status, zero_maps
 
 EPS = 1e-7
@@ -48,24 +49,11 @@ def _ciou(p: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
 
 def _ground_truths(batch_idx, cls, bboxes, B: int, img_wh, dtype):
     """Per image its label rows in order: boxes (B, M, 4) xyxy in pixels, labels (B, M) int64, valid (B, M), rows (B, M) (-1: none)."""
-    dev = bboxes.device
-    idx = batch_idx.to(torch.int64)
-    counts = torch.bincount(idx.clamp(0, B - 1), minlength=B) if idx.numel() else torch.zeros(B, dtype=torch.int64)
-    M = int(counts.max()) if idx.numel() else 0
-    rows = torch.full((B, M), -1, dtype=torch.int64, device=dev)
-    for b in range(B):
-        r = torch.nonzero(idx == b).flatten()
-        rows[b, :r.numel()] = r
-    has = rows >= 0
+    rows, has, _ = rows_per_image(batch_idx, B, integral=False)
     safe = rows.clamp(min=0)
-    scale = torch.tensor([img_wh[0], img_wh[1], img_wh[0], img_wh[1]], dtype=dtype, device=dev)
-    zero = torch.zeros((), dtype=dtype, device=dev)
-    xywh = torch.where(has[..., None], bboxes.to(dtype)[safe] * scale, zero) if M else torch.zeros(B, 0, 4, dtype=dtype, device=dev)
-    half = xywh[..., 2:] / 2
-    boxes = torch.cat((xywh[..., :2] - half, xywh[..., :2] + half), -1)
-    labels = torch.where(has, cls.to(torch.int64)[safe], torch.zeros_like(safe)) if M else torch.zeros(B, 0, dtype=torch.int64, device=dev)
-    valid = boxes.sum(-1) > 0
-    return boxes, labels, valid, rows
+    boxes = torch.where(has[..., None], loss_boxes(bboxes.to(dtype), *img_wh)[safe], torch.zeros((), dtype=dtype, device=bboxes.device))
+    labels = cls.to(torch.int64)[safe] * has
+    return boxes, labels, boxes.sum(-1) > 0, rows
 
 
 def _assign(scores, pred_px, anc_px, boxes, labels, valid, nc: int, topk: int, lowest_first: bool = True):
@@ -159,10 +147,7 @@ class _DetState:
         self.status = torch.empty(1, dtype=i32, device=dev)
         self.args = (feats, strides, nc, topk, m_cap, gains, batch_idx, cls, bboxes, n, self.assign_gt, self.assign_score, self.out,
                      self.items, self.status)
-        self.desc = _lib.DetDesc()
-        fill_det(self.desc, *self.args)
-        self.ws = torch.empty(_lib.det_ws_bytes(self.desc), dtype=torch.uint8, device=dev)
-        self.bind(g_feats, upstream)
+        self.desc, self.ws = sized_ws(_lib.DetDesc(), fill_det, _lib.det_ws_bytes, self.args, dev, g_feats=g_feats, upstream=upstream)
 
     def bind(self, g_feats, upstream):
         fill_det(self.desc, *self.args, ws=self.ws, g_feats=g_feats, upstream=upstream)
@@ -196,12 +181,6 @@ class _DetFn(torch.autograd.Function):
         return (None, None, None, None, *g_feats)
 
 
-def _labels(batch_idx, cls, bboxes, device):
-    f32 = torch.float32
-    return (batch_idx.reshape(-1).to(device, f32).contiguous(), cls.reshape(-1).to(device, f32).contiguous(),
-            bboxes.reshape(-1, 4).to(device, f32).contiguous())
-
-
 def detection_loss(feats: Sequence[torch.Tensor], batch_idx: torch.Tensor, cls: torch.Tensor, bboxes: torch.Tensor, *, nc: int,
                    strides: Sequence[int] = (8, 16, 32), gains: Sequence[float] = (7.5, 0.5, 1.5), topk: int = 10,
                    m_cap: Optional[int] = None, return_assignment: bool = False):
@@ -214,15 +193,14 @@ def detection_loss(feats: Sequence[torch.Tensor], batch_idx: torch.Tensor, cls: 
     feats = list(feats)
     check_maps("detection_loss", feats, nc, strides)
     dev = feats[0].device
+    b_, c_, x_ = as_labels(batch_idx, cls, bboxes, dev)
     if not feats[0].is_cuda:
         if any(f.is_cuda for f in feats):
             raise RuntimeError("detection_loss: the feature maps must all live on the GPU or all on the host")
-        b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
         loss, items, asg = _host_loss([f.float() for f in feats], b_, c_, x_, nc, strides, gains, topk)
         return (loss, items, asg) if return_assignment else (loss, items)
     feats, flags = device_maps(feats)
-    b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
-    if m_cap is None:
+    if m_cap is None:                                        # the criterion's own sizing (detlabels.py: not detlabels.size_m_cap's rule)
         m_cap = int(torch.bincount(b_.long().clamp(0, feats[0].shape[0] - 1)).max()) if b_.numel() else 1
         m_cap = max(m_cap, 1)
     out, items, gt, score, status = _DetFn.apply((int(nc), tuple(int(s) for s in strides), tuple(float(g) for g in gains), int(topk),
@@ -238,9 +216,7 @@ def assignment_views(gt, score, status, cls, bboxes, nc: int, img_w: float, img_
     if cls.numel():
         row = gt.clamp(min=0).long()
         lab = cls.long().clamp(0, nc - 1)[row]
-        xywh = bboxes[row] * torch.tensor([img_w, img_h, img_w, img_h], dtype=torch.float32, device=gt.device)
-        half = xywh[..., 2:] / 2
-        boxes = torch.cat((xywh[..., :2] - half, xywh[..., :2] + half), -1) * fg[..., None]
+        boxes = loss_boxes(bboxes, img_w, img_h)[row] * fg[..., None]
     else:
         lab, boxes = torch.zeros_like(gt, dtype=torch.int64), torch.zeros(*gt.shape, 4, device=gt.device)
     t_scores = F.one_hot(lab, nc).float() * (score * fg)[..., None]
@@ -273,10 +249,8 @@ class DetLossPlan:
         self.device, self.nc, self.strides, self.channels_last = dev, int(nc), tuple(int(s) for s in strides), bool(channels_last)
         self.feats = zero_maps(shapes, nc, dtype, dev, channels_last)
         self.g_feats = zero_maps(shapes, nc, dtype, dev, channels_last)
-        self.batch_idx = torch.zeros(n_cap, dtype=f32, device=dev)
-        self.cls = torch.zeros(n_cap, dtype=f32, device=dev)
-        self.bboxes = torch.zeros(n_cap, 4, dtype=f32, device=dev)
-        self.n = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.labels = lab = LabelBuffers(n_cap, dev)
+        self.batch_idx, self.cls, self.bboxes, self.n = lab.batch_idx, lab.cls, lab.bboxes, lab.n
         self.g_out = g_out if g_out is not None else torch.ones(3, dtype=f32, device=dev)
         self._st = _DetState(self.feats, self.strides, nc, topk, m_cap, gains, self.batch_idx, self.cls, self.bboxes, self.n, out=out,
                              g_feats=self.g_feats, upstream=self.g_out, flags=plan_maps("DetLossPlan", self.feats, channels_last))
@@ -293,11 +267,7 @@ class DetLossPlan:
 
     def set_labels(self, batch_idx, cls, bboxes):
         """Copy a batch's labels into the static buffers and write their count (outside a capture)."""
-        n = batch_idx.numel()
-        if n > self.batch_idx.numel():
-            raise ValueError(f"DetLossPlan: {n} label rows, the plan holds {self.batch_idx.numel()}")
-        self.batch_idx[:n].copy_(batch_idx.reshape(-1)); self.cls[:n].copy_(cls.reshape(-1)); self.bboxes[:n].copy_(bboxes.reshape(-1, 4))
-        self.n.fill_(n)
+        self.labels.set(batch_idx, cls, bboxes, "DetLossPlan")
 
     def forward(self):
         self._st.forward(self.device)

@@ -81,6 +81,10 @@ def zero_maps(shapes, nc: int, dtype, device, channels_last: bool = False):     
     return [torch.empty(B, 4 * REG_MAX + nc, H, W, dtype=dtype, device=device, memory_format=fmt).zero_() for B, H, W in shapes]
 
 
-def raise_on_status(status: torch.Tensor, message: str) -> None:      # a plan's status word is set (a host read: not inside a capture)
-    if not torch.cuda.is_current_stream_capturing() and int(status.item()) != 0:
-        raise RuntimeError(message)
+def raise_on_status(status: torch.Tensor, message) -> None:
+    """A plan's status word is set (a host read: not inside a capture).  message: the text for any non-zero status, or {code: text} where
+    the codes mean different things (a code it does not name passes)."""
+    s = 0 if torch.cuda.is_current_stream_capturing() else int(status.item())
+    text = message.get(s) if isinstance(message, dict) else message
+    if s != 0 and text:
+        raise RuntimeError(text)

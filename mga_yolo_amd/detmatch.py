@@ -27,8 +27,8 @@ import torch
 
 from . import _lib
 from ._binding import call, fill_match
-
-IOU_EPS = 1e-7
+from .detlabels import LabelBuffers, as_labels, img_wh, label_boxes, pair_iou, plan_dets, rows_per_image, size_m_cap, sized_ws
+from .detmaps import raise_on_status
 
 
 def default_iouv() -> torch.Tensor:
@@ -46,61 +46,28 @@ def _iouv_list(iouv) -> list:
     return v
 
 
-def _img_wh(imgsz) -> Tuple[float, float]:
-    if isinstance(imgsz, (int, float)):
-        return float(imgsz), float(imgsz)
-    h, w = imgsz
-    return float(w), float(h)
-
-
-def _labels(batch_idx, cls, bboxes, device):
-    f32 = torch.float32
-    return (batch_idx.reshape(-1).to(device, f32).contiguous(), cls.reshape(-1).to(device, f32).contiguous(),
-            bboxes.reshape(-1, 4).to(device, f32).contiguous())
-
-
 # ---------------------------------------------------------------------------------------------------------------------------
 # torch ops (host tensors): the project's own statement of the rule, batched
 # ---------------------------------------------------------------------------------------------------------------------------
-def _label_boxes(bboxes, img_w: float, img_h: float):
-    """xywh normalised -> xyxy in pixels as the reference forms it: (c -+ s / 2) * size (ops.xywh2xyxy, then the scale)."""
-    half = bboxes[:, 2:] / 2
-    size = torch.tensor([img_w, img_h, img_w, img_h], dtype=bboxes.dtype, device=bboxes.device)
-    return torch.cat((bboxes[:, :2] - half, bboxes[:, :2] + half), 1) * size
-
-
 def _host_match(dets, count, batch_idx, cls, bboxes, img_w: float, img_h: float, iouv, single_cls: bool):
     """The rule in torch ops on the whole batch, in the element type of `dets`.  Returns tp (B, max_det, niou) bool, best_iou (B, max_det),
     best_gt (B, max_det) int32."""
     B, D = dets.shape[:2]
     dt, dev = dets.dtype, dets.device
     T = len(iouv)
-    idx = batch_idx.to(torch.int64)
-    belongs = (batch_idx >= 0) & (batch_idx < B) & (batch_idx == idx)
-    per = torch.bincount(idx[belongs], minlength=B) if bool(belongs.any()) else torch.zeros(B, dtype=torch.int64, device=dev)
-    M = int(per.max())
+    rows, has, _ = rows_per_image(batch_idx, B)
+    M = rows.shape[1]
     tp = torch.zeros(B, D, T, dtype=torch.bool, device=dev)
     best_iou = torch.zeros(B, D, dtype=dt, device=dev)
     best_gt = torch.full((B, D), -1, dtype=torch.int32, device=dev)
     if M == 0:
         return tp, best_iou, best_gt
-    rows = torch.full((B, M), -1, dtype=torch.int64, device=dev)                     # per image its label rows in flat order
-    for b in range(B):
-        r = torch.nonzero(belongs & (idx == b)).flatten()
-        rows[b, :r.numel()] = r
-    has = rows >= 0
     safe = rows.clamp(min=0)
-    lb = _label_boxes(bboxes.to(dt), img_w, img_h)[safe]                             # (B, M, 4)
+    lb = label_boxes(bboxes.to(dt), img_w, img_h)[safe]                              # (B, M, 4)
     lc = cls.to(dt)[safe]
     live = torch.arange(D, device=dev)[None] < count.to(torch.int64).clamp(0, D)[:, None]
-    db, dc = dets[..., :4], dets[..., 5]
-    # ultralytics/utils/metrics.py:53-74, label x detection -> here (B, D, M)
-    iw = (torch.minimum(lb[:, None, :, 2], db[:, :, None, 2]) - torch.maximum(lb[:, None, :, 0], db[:, :, None, 0])).clamp(min=0)
-    ih = (torch.minimum(lb[:, None, :, 3], db[:, :, None, 3]) - torch.maximum(lb[:, None, :, 1], db[:, :, None, 1])).clamp(min=0)
-    inter = iw * ih
-    area_l = (lb[..., 2] - lb[..., 0]) * (lb[..., 3] - lb[..., 1])
-    area_d = (db[..., 2] - db[..., 0]) * (db[..., 3] - db[..., 1])
-    iou = inter / (area_l[:, None, :] + area_d[:, :, None] - inter + IOU_EPS)
+    dc = dets[..., 5]
+    iou = pair_iou(lb, dets[..., :4])                                                # (B, D, M)
     pair = has[:, None, :] & live[:, :, None]
     if not single_cls:
         pair = pair & (lc[:, None, :] == dc[:, :, None])
@@ -134,10 +101,7 @@ class _MatchState:
         self.status = torch.empty(1, dtype=torch.int32, device=dev)
         self.args = (dets, count, batch_idx, cls, bboxes, n, m_cap, img_w, img_h, iouv, _lib.MATCH_SINGLE_CLS if single_cls else 0,
                      self.tp, self.best_iou, self.best_gt, self.status)
-        self.desc = _lib.MatchDesc()
-        fill_match(self.desc, *self.args, acc=acc)
-        self.ws = torch.empty(_lib.match_ws_bytes(self.desc), dtype=torch.uint8, device=dev)
-        fill_match(self.desc, *self.args, acc=acc, ws=self.ws)
+        self.desc, self.ws = sized_ws(_lib.MatchDesc(), fill_match, _lib.match_ws_bytes, self.args, dev, acc=acc)
 
     def run(self, dev):
         call("mgamatch_run", dev, C.byref(self.desc))
@@ -155,22 +119,17 @@ def match_detections(dets: torch.Tensor, count: torch.Tensor, batch_idx: torch.T
     if dets.dim() != 3 or dets.shape[2] != 6 or count.shape != dets.shape[:1]:
         raise ValueError("match_detections: dets must be (B, max_det, 6) and count (B)")
     thr = _iouv_list(iouv)
-    img_w, img_h = _img_wh(imgsz)
+    img_w, img_h = img_wh(imgsz)
     dev = dets.device
+    b_, c_, x_ = as_labels(batch_idx, cls, bboxes, dev)
     if not dets.is_cuda:
         if any(t.is_cuda for t in (count, batch_idx, cls, bboxes)):
             raise RuntimeError("match_detections: the tensors must all live on the GPU or all on the host")
-        b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
         d_ = dets if dets.dtype == torch.float64 else dets.float()
         tp, best_iou, best_gt = _host_match(d_, count, b_, c_, x_, img_w, img_h, thr, single_cls)
         return tp, best_iou.float(), best_gt
-    b_, c_, x_ = _labels(batch_idx, cls, bboxes, dev)
-    B = dets.shape[0]
-    if m_cap is None:
-        inside = b_[(b_ >= 0) & (b_ < B)].long()
-        m_cap = max(int(torch.bincount(inside).max()) if inside.numel() else 1, 1)
-    st = _MatchState(dets.to(torch.float32).contiguous(), count.to(dev, torch.int32).contiguous(), b_, c_, x_, None, int(m_cap), img_w, img_h,
-                     thr, single_cls)
+    st = _MatchState(dets.to(torch.float32).contiguous(), count.to(dev, torch.int32).contiguous(), b_, c_, x_, None,
+                     size_m_cap(b_, dets.shape[0]) if m_cap is None else int(m_cap), img_w, img_h, thr, single_cls)
     st.run(dev)
     return st.tp.bool(), st.best_iou, st.best_gt
 
@@ -186,10 +145,8 @@ class DetMatchPlan:
         f32, i32 = torch.float32, torch.int32
         self.device, self.niou = dev, len(iouv)
         self.dets, self.count = dets, count
-        self.batch_idx = torch.zeros(n_cap, dtype=f32, device=dev)
-        self.cls = torch.zeros(n_cap, dtype=f32, device=dev)
-        self.bboxes = torch.zeros(n_cap, 4, dtype=f32, device=dev)
-        self.n = torch.zeros(1, dtype=i32, device=dev)
+        self.labels = lab = LabelBuffers(n_cap, dev)                  # a ConfusionPlan(labels=this plan) holds the same object
+        self.batch_idx, self.cls, self.bboxes, self.n = lab.batch_idx, lab.cls, lab.bboxes, lab.n
         acc = None
         self._arena = None
         if rows_cap is not None:
@@ -215,24 +172,14 @@ class DetMatchPlan:
         if (rows_cap is None) != (tgt_cap is None):
             raise ValueError("DetMatchPlan: rows_cap and tgt_cap are given together or not at all")
         dev = torch.device(device)
-        if dets is None:
-            dets = torch.zeros(B, max_det, 6, dtype=torch.float32, device=dev)
-        if count is None:
-            count = torch.zeros(B, dtype=torch.int32, device=dev)
-        if tuple(dets.shape) != (B, max_det, 6) or dets.dtype != torch.float32 or not dets.is_contiguous() or tuple(count.shape) != (B,) \
-                or count.dtype != torch.int32:
-            raise ValueError(f"DetMatchPlan: dets must be a contiguous fp32 ({B}, {max_det}, 6) tensor and count int32 ({B})")
-        img_w, img_h = _img_wh(imgsz)
+        dets, count = plan_dets("DetMatchPlan", dets, count, B, max_det, dev)
+        img_w, img_h = img_wh(imgsz)
         return cls(dets, count, int(n_cap), int(m_cap), img_w, img_h, _iouv_list(iouv), bool(single_cls),
                    None if rows_cap is None else int(rows_cap), None if tgt_cap is None else int(tgt_cap))
 
     def set_labels(self, batch_idx, cls, bboxes):
         """Copy a batch's labels into the static buffers and write their count (outside a capture)."""
-        n = batch_idx.numel()
-        if n > self.batch_idx.numel():
-            raise ValueError(f"DetMatchPlan: {n} label rows, the plan holds {self.batch_idx.numel()}")
-        self.batch_idx[:n].copy_(batch_idx.reshape(-1)); self.cls[:n].copy_(cls.reshape(-1)); self.bboxes[:n].copy_(bboxes.reshape(-1, 4))
-        self.n.fill_(n)
+        self.labels.set(batch_idx, cls, bboxes, "DetMatchPlan")
 
     def run(self):
         self._st.run(self.device)
@@ -246,13 +193,8 @@ class DetMatchPlan:
     def check_status(self):
         """Raise if the last run met an image with more label rows than m_cap, or an append past rows_cap / tgt_cap (a host read: not
         inside a capture)."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        s = int(self.status.item())
-        if s == 1:
-            raise RuntimeError("DetMatchPlan: an image has more label rows than m_cap; its tp rows are 0 and nothing was appended")
-        if s == 2:
-            raise RuntimeError("DetMatchPlan: the batch's rows do not fit behind rows_cap / tgt_cap; nothing was appended")
+        raise_on_status(self.status, {1: "DetMatchPlan: an image has more label rows than m_cap; its tp rows are 0 and nothing was appended",
+                                      2: "DetMatchPlan: the batch's rows do not fit behind rows_cap / tgt_cap; nothing was appended"})
 
     @property
     def seen(self) -> int:
@@ -289,7 +231,7 @@ def host_stats(batches, *, imgsz, iouv=None, single_cls: bool = False) -> Dict[s
     seen = 0
     for dets, count, batch_idx, cls, bboxes in batches:
         dets, count = dets.cpu().float(), count.cpu()
-        b_, c_, _ = _labels(batch_idx, cls, bboxes, "cpu")
+        b_, c_, _ = as_labels(batch_idx, cls, bboxes, "cpu")
         tp, _, _ = match_detections(dets, count, batch_idx.cpu(), cls.cpu(), bboxes.cpu(), imgsz=imgsz, iouv=iouv, single_cls=single_cls)
         B, D = dets.shape[:2]
         for b in range(B):
@@ -352,7 +294,7 @@ def update_metrics(self, preds, batch) -> None:
         if k:
             dets[b, :k, :4], dets[b, :k, 4], dets[b, :k, 5] = p["bboxes"][:, :4].float(), p["conf"].float(), p["cls"].float()
     count = torch.tensor(counts, dtype=torch.int32, device=dev)
-    bi, lc, lx = _labels(batch["batch_idx"], batch["cls"], batch["bboxes"], dev)
+    bi, lc, lx = as_labels(batch["batch_idx"], batch["cls"], batch["bboxes"], dev)
     niou = int(self.iouv.numel())
     imgsz = tuple(batch["img"].shape[2:])
     cmx = getattr(self, "confusion_matrix", None) if _CONFUSION_ON and self.args.plots and dets.is_cuda else None
@@ -360,7 +302,7 @@ def update_metrics(self, preds, batch) -> None:
         cmx = None
     extra = []
     if dets.is_cuda:
-        img_w, img_h = _img_wh(imgsz)
+        img_w, img_h = img_wh(imgsz)
         thr = getattr(self, "_mga_iouv", None)                     # the validator's thresholds are read from the device once, not per batch
         if thr is None:
             thr = self._mga_iouv = _iouv_list(self.iouv)

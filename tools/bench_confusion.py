@@ -42,12 +42,12 @@ CONF, IOU_THRES = 0.001, 0.45
 
 def torch_loop(dets, batch_idx, cls, bboxes, nc):
     """process_batch's steps per image on device tensors, restated: the batch's matrix"""
-    from mga_yolo_amd.detmatch import _label_boxes
+    from mga_yolo_amd.detlabels import label_boxes
     matrix = np.zeros((nc + 1, nc + 1))
     conf = 0.25 if CONF in {None, 0.001} else CONF
     for b in range(dets.shape[0]):
         rows = batch_idx == b
-        gt_cls, gt_boxes = cls[rows].squeeze(-1), _label_boxes(bboxes[rows], SIZE, SIZE)
+        gt_cls, gt_boxes = cls[rows].squeeze(-1), label_boxes(bboxes[rows], SIZE, SIZE)
         p = dets[b]
         p = p[p[:, 4] > conf]
         gt_classes = gt_cls.int().tolist()                                                     # read-back 1

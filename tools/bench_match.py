@@ -75,11 +75,11 @@ def match_numpy(iou, thrs):
 
 def torch_loop(dets, count, batch_idx, cls, bboxes, thrs):
     """The validator's loop on device tensors: per image the tp matrix and the three arrays its stats take."""
-    from mga_yolo_amd.detmatch import _label_boxes
+    from mga_yolo_amd.detlabels import label_boxes
     out = []
     for b in range(dets.shape[0]):
         rows = batch_idx == b
-        lc, lb = cls[rows].squeeze(-1), _label_boxes(bboxes[rows], SIZE, SIZE)
+        lc, lb = cls[rows].squeeze(-1), label_boxes(bboxes[rows], SIZE, SIZE)
         p = dets[b, :int(D)]
         iw = (torch.minimum(lb[:, None, 2], p[None, :, 2]) - torch.maximum(lb[:, None, 0], p[None, :, 0])).clamp(min=0)
         ih = (torch.minimum(lb[:, None, 3], p[None, :, 3]) - torch.maximum(lb[:, None, 1], p[None, :, 1])).clamp(min=0)
