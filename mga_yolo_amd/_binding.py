@@ -1,10 +1,12 @@
 """The torch side of the binding: the one place where tensors become C-ABI level structs (include/mgacbam.h, include/mgaspade.h) and
 where a library entry point is called on torch's current stream.  One fill function per struct sets EVERY field of it; the autograd
 Functions (functional.py, segloss.py) and the static plans (plan.py, slice.py) all build their level tables here and differ only in the
-arguments they pass.  Sizes are asked in _lib.py (`_lib.size`)."""
+arguments they pass.  Sizes are asked in _lib.py (`_lib.size`).  The four feature blocks are described once more, as a `Family` each
+(CBAM, ECA, HEAD, SPADE at the end of this file): structs, layout flag, byte counts, fills, entry points and parameter names, which the eager
+frame and the plans read instead of restating them."""
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -151,6 +153,8 @@ def fill_spade(L: _lib.SpadeLevel, x, mask, params, cfg, running, ctx, y=None, s
     _lib.SPADE_LAYOUT_NHWC when x / y / gy / gx are channels_last (x.shape stays (B,C,H,W)); a backward carries its forward's flag."""
     B, Cc, H, W = x.shape
     L.x, L.mask, L.y, L.gy, L.gx, L.gmask = x.data_ptr(), _ptr(mask), _ptr(y), _ptr(gy), _ptr(gx), _ptr(gmask)
+    if mask is None:                                     # a level without a mask reads no parameter and writes no parameter gradient
+        params = pgrads = (None,) * 6
     for name, p, g in zip(_SPADE_P, params, pgrads or (None,) * 6):
         setattr(L, name, _ptr(p))
         setattr(L, "g" + name, _ptr(g))
@@ -296,3 +300,60 @@ def fill_confusion(D: _lib.ConfusionDesc, dets, count, batch_idx, cls, bboxes, n
     D.det_out, D.cm, D.acc, D.status = det_out.data_ptr(), cm.data_ptr(), _ptr(acc), status.data_ptr()
     D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
     D.reserved = 0
+
+
+# ---- the feature-block families: what the eager frame (functional.py) and the static plans (plan.py, slice.py) both need of one
+class Family(NamedTuple):
+    """One block family.  ``shape`` = (B,C,H,W); ``cfg`` = the block's config dataclass, for the mask head the tuple (hidden, eps, momentum,
+    training); ``flags`` = the level flags, of which the byte counts read the layout bit only.  The fills take a level's buffers BY NAME and
+    use the ones their struct has: x, mask, y (the head's logits), ctx, ws, params, running, save_gamma forward; x, mask, gy (the head's
+    dL/dlogits), gy2 (its second one, fill_head_bwd), ctx, scratch, gx, gmask, grads, params, running backward."""
+    kind: str                                   # "cbam" | "eca" | "head" | "spade"
+    fwd_level: type                             # the ctypes structs of the two level tables
+    bwd_level: type
+    layout_nhwc: int                            # the level flag of torch.channels_last features
+    param_names: Tuple[str, ...]                # a level's parameters, in the order of the bucket (and of the state_dict's keys where dotted)
+    fwd_entry: str                              # the two entry points: (levels, n[, stages], stream)
+    bwd_entry: str
+    ctx_bytes: Callable[[tuple, object, int], int]
+    scratch_bytes: Callable[[tuple, object, int], int]
+    ws_bytes: Callable[[tuple, object, int], int]      # the forward's workspace: 0 = none
+    fill_fwd: Callable[..., None]               # (L, cfg, flags, **buffers)
+    fill_bwd: Callable[..., None]
+
+
+def spade_eager_ctx_bytes(shape, cfg, gamma_elem: int) -> int:
+    """MaskSPADE's ctx on the eager path: the full mgaspade_ctx_bytes (SPADE.ctx_bytes, what a static plan allocates) keeps gamma as fp32;
+    an eager forward keeps it at the feature's own element size ``gamma_elem``, or not at all (0: no backward will come, or no mask)."""
+    B, Cc, H, W = shape
+    a16 = lambda v: (v + 15) & ~15
+    base = _lib.spade_ctx_bytes(B, Cc, H, W, cfg.hidden) - a16(B * Cc * H * W * 4)
+    return base + (a16(B * Cc * H * W * gamma_elem) if gamma_elem else 0)
+
+
+# (s, c, f = shape, cfg, flags; b = the level's buffers by name.  The fill_* signatures above are pinned: these lines only hand the names over)
+CBAM = Family(
+    "cbam", _lib.FwdLevel, _lib.BwdLevel, _lib.LAYOUT_NHWC, ("w1", "b1", "w2", "b2", "wsa", "beta"), "mgacbam_forward_stages", "mgacbam_backward_stages",
+    lambda s, c, f: _lib.ctx_bytes(*s, c.hidden), lambda s, c, f: _lib.scratch_bytes(*s, c.hidden, c.k, f), lambda s, c, f: _lib.fwd_ws_bytes(*s, c.hidden, f),
+    lambda L, c, f, **b: fill_cbam_fwd(L, b["x"], b["mask"], b["y"], b["ctx"], b["params"], c, f, b.get("ws")),
+    lambda L, c, f, **b: fill_cbam_bwd(L, b["x"], b["mask"], b["gy"], b["ctx"], b["scratch"], b["gx"], b["gmask"], b["grads"], b["params"], c, f))
+ECA = Family(
+    "eca", _lib.EcaFwdLevel, _lib.EcaBwdLevel, _lib.LAYOUT_NHWC, ("conv1d.weight", "beta"), "mgacbam_eca_forward", "mgacbam_eca_backward",
+    lambda s, c, f: _lib.eca_ctx_bytes(*s, f), lambda s, c, f: _lib.eca_scratch_bytes(*s, f), lambda s, c, f: 0,
+    lambda L, c, f, **b: fill_eca_fwd(L, b["x"], b["mask"], b["y"], b["ctx"], *b["params"], c, f),
+    lambda L, c, f, **b: fill_eca_bwd(L, b["x"], b["mask"], b["gy"], b["ctx"], b["scratch"], b["gx"], b["gmask"], *b["grads"], *b["params"], c, f))
+HEAD = Family(
+    "head", _lib.HeadFwdLevel, _lib.HeadBwdLevel, _lib.HEAD_LAYOUT_NHWC, ("proj.0.weight", "proj.1.weight", "proj.1.bias", "head.weight", "head.bias"),
+    "mgahead_forward", "mgahead_backward",
+    lambda s, c, f: _lib.head_ctx_bytes(*s, c[0], f), lambda s, c, f: _lib.head_scratch_bytes(*s, c[0], f), lambda s, c, f: 0,
+    lambda L, c, f, **b: fill_head_fwd(L, b["x"], b["y"], b["ctx"], b["params"], b["running"], *c, f),
+    lambda L, c, f, **b: fill_head_bwd(L, b["x"], b["gy"], b.get("gy2"), b["ctx"], b["scratch"], b["gx"], b["grads"], b["params"], b["running"], *c, f))
+SPADE = Family(
+    "spade", _lib.SpadeLevel, _lib.SpadeLevel, _lib.SPADE_LAYOUT_NHWC,
+    ("shared.0.weight", "shared.0.bias", "conv_gamma.weight", "conv_gamma.bias", "conv_beta.weight", "conv_beta.bias"), "mgaspade_forward", "mgaspade_backward",
+    lambda s, c, f: _lib.spade_ctx_bytes(*s, c.hidden), lambda s, c, f: _lib.spade_scratch_bytes(*s, c.hidden), lambda s, c, f: 0,
+    lambda L, c, f, **b: fill_spade(L, b["x"], b["mask"], b["params"], c, b["running"], b["ctx"], y=b["y"], save_gamma=b["save_gamma"], flags=f),
+    lambda L, c, f, **b: fill_spade(L, b["x"], b["mask"], b["params"], c, b["running"], b["ctx"], gy=b["gy"], gx=b["gx"], gmask=b["gmask"],
+                                    pgrads=b["grads"], scratch=b["scratch"], flags=f))
+
+

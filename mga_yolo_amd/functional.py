@@ -18,9 +18,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._binding import DTYPES as _DTYPES, call as _call, raw_stream as _raw_stream
-from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_gate, fill_head_bwd, fill_head_fwd, fill_spade, fill_targets
-from ._binding import head_params as _head_params  # noqa: F401  (tests fill head levels by hand with it)
+from ._binding import CBAM, DTYPES as _DTYPES, ECA, HEAD, SPADE, Family, call as _call, raw_stream as _raw_stream
+from ._binding import fill_gate, fill_targets, spade_eager_ctx_bytes, head_params as _head_params  # noqa: F401  (tests fill head levels by hand with it)
 
 
 @dataclass(frozen=True)
@@ -33,16 +32,18 @@ class BlockConfig:
     eps: float = 1e-6
 
 
-# k_chan + k_apply as ONE x-resident launch (k_gate, MGACBAM_FWD_FUSE); MGACBAM_FUSE_FWD=0 restores the three-launch forward
-_FUSE_FWD = bool(int(os.environ.get("MGACBAM_FUSE_FWD", "1")))
-# transposed conv folded into the k_bwd_reduce1 launch (MGACBAM_BWD_FOLD); needs the zero-filled ctx tail the fused forward sets up
-_FOLD_BWD = _FUSE_FWD and bool(int(os.environ.get("MGACBAM_FOLD_BWD", "1")))
+def stage_switches() -> Tuple[bool, bool]:
+    """(MGACBAM_FUSE_FWD, MGACBAM_FOLD_BWD) as the environment has them NOW, both on by default (the eager path asks at import, a plan when it is
+    built).  FUSE_FWD: k_chan + k_apply as ONE x-resident launch, k_gate; FOLD_BWD: the transposed conv folded into the k_bwd_reduce1 launch."""
+    return bool(int(os.environ.get("MGACBAM_FUSE_FWD", "1"))), bool(int(os.environ.get("MGACBAM_FOLD_BWD", "1")))
+
+
+_FUSE_FWD, _FOLD_BWD = stage_switches()
+_FOLD_BWD = _FUSE_FWD and _FOLD_BWD       # the folded launch needs the zero-filled ctx tail the fused forward sets up
 # MGACBAM_CHECK_HANDOFF=1: synchronise after every library call and raise if an in-launch hand-off timed out (debugging switch;
 # without it a time-out is still loud -- the tile is poisoned with NaN -- and handoff_report() reads every status word at once)
 _CHECK_HANDOFF = bool(int(os.environ.get("MGACBAM_CHECK_HANDOFF", "0")))
-SLOTS = 8  # tensors per level in the flat argument list: x, mask, w1, b1, w2, b2, wsa, beta
-_FWD_STAGES = _lib.FWD_ALL | (_lib.FWD_FUSE if _FUSE_FWD else 0)
-_BWD_STAGES = _lib.BWD_ALL | (_lib.BWD_FOLD if _FOLD_BWD else 0)
+_LEAD = ("blk", "cfgs")      # what the eager frame's Function (_BlockFn.forward) takes in front of the levels' tensors: no gradient
 
 
 class HandoffTimeout(RuntimeError):
@@ -106,27 +107,36 @@ def status_words(bufs_and_shapes) -> List[int]:
     return torch.cat(words).cpu().tolist()
 
 
+def handoff_check(bufs_and_shapes, where, what: Optional[str] = None) -> int:
+    """The one status-word check: read the word of every (ctx buffer, (B,C,H,W,hidden)) given (status_words: it synchronises) and raise
+    HandoffTimeout if any is set -> the number of buffers checked.  where(the (B,C,H,W) whose word is set) words them in the message;
+    what: a call's name, for the per-call form (MGACBAM_CHECK_HANDOFF), which carries no advice."""
+    entries = list(bufs_and_shapes)
+    bad = [s[:4] for (_, s), w in zip(entries, status_words(entries)) if w != 0]
+    if bad:
+        advice = ": affected tiles were poisoned with NaN (is the GPU shared with other work?  MGACBAM_FUSE_FWD=0 runs without hand-offs)"
+        raise HandoffTimeout(f"in-launch hand-off timed out for {where(bad)}{advice}" if what is None else
+                             f"{what}: in-launch hand-off timed out for {where(bad)}")
+    return len(entries)
+
+
 def handoff_report(clear_pool: bool = False):
     """Synchronise and read the hand-off status word of every ctx buffer the eager path has handed out and that is still alive.
     Returns the number of buffers checked; raises HandoffTimeout if any word is set.  Call it where the training loop synchronises
     anyway (end of an epoch / validation)."""
     live = [(r(), k) for r, k in _POOL.all]
-    live = [(b, k) for b, k in live if b is not None]
+    live = [(b, k[2:7]) for b, k in live if b is not None]
     if not live:
         return 0
-    bad = [k for (b, k), w in zip(live, status_words((b, k[2:7]) for b, k in live)) if w != 0]
-    if clear_pool:
-        _POOL.clear()
-    if bad:
-        raise HandoffTimeout(f"in-launch hand-off timed out for shapes {sorted(set(k[2:6] for k in bad))}: affected tiles were "
-                             "poisoned with NaN (is the GPU shared with other work?  MGACBAM_FUSE_FWD=0 runs without hand-offs)")
-    return len(live)
+    try:
+        return handoff_check(live, lambda bad: f"shapes {sorted(set(bad))}")
+    finally:
+        if clear_pool:
+            _POOL.clear()
 
 
-def _check_status(bufs_and_shapes, what: str):
-    for (_, (B, Cc, H, W, _)), w in zip(bufs_and_shapes, status_words(bufs_and_shapes)):     # (the read synchronises)
-        if w != 0:
-            raise HandoffTimeout(f"{what}: in-launch hand-off timed out for level (B,C,H,W)=({B},{Cc},{H},{W})")
+def _check_status(leases, what: str):
+    handoff_check([(ls.buf, ls.key[2:7]) for ls in leases], lambda bad: "level (B,C,H,W)=({},{},{},{})".format(*bad[0]), what)
 
 
 def _aligned(t: torch.Tensor) -> torch.Tensor:
@@ -188,12 +198,14 @@ def _grad_in(gy: Optional[torch.Tensor], like: torch.Tensor, nhwc: bool) -> torc
     return _ready_nhwc(gy) if nhwc else _aligned(gy)
 
 
-def _gmask_out(grads: list, slots: int, metas: Sequence[Optional[tuple]]) -> None:
-    """Give dL/dmask (slot 1 of each level's `slots` gradients, after the leading None) back in the mask's own shape / element type.
+def _gmask_out(grads: list, blk: "_Block", kept: Sequence[tuple]) -> None:
+    """Give dL/dmask (the gradient of each level's input "mask") back in the mask's own shape / element type.
     This runs AFTER the launch that writes it: a cast enqueued before it would read unwritten memory (that was the case for
     half-precision masks until the AMP test of round 3)."""
-    for l, meta in enumerate(metas):
-        i = 2 + l * slots
+    if blk.mask_at is None:
+        return
+    for l, (_, _, meta, _, _) in enumerate(kept):
+        i = len(_LEAD) + l * blk.slots + blk.mask_at
         if grads[i] is not None:
             grads[i] = grads[i].reshape(meta[1]).to(meta[0])
 
@@ -213,109 +225,187 @@ def _check_params(x: torch.Tensor, params: Sequence[torch.Tensor], cfg: BlockCon
             raise ValueError(f"parameter {name}: expected fp32 {want[name]} on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
-def _cbam_inputs(x, mask, params, cfg: BlockConfig):
-    """Checks (the AssertionError / TypeError / RuntimeError / ValueError split mirrors the reference, in its order) and the tensors a
-    MaskCBAM level reads -> (x, fp32 mask | None, params, level flags, mask meta).  The layout decides the kernels, per level; y keeps it."""
-    _check_feature(x, "MaskCBAM expects a (B,C,H,W) feature")                 # masked_cbam.py:160
-    B, _, H, W = x.shape
-    m32, mmeta = _mask_in(mask, B, H, W)
-    _check_params(x, params, cfg)
-    xc, nhwc = _feature_in(x)
-    return xc, m32, [_ready(p) for p in params], (_lib.LAYOUT_NHWC if nhwc else 0), mmeta
+# ---------------------------------------------------------------------------------------------------------
+# The eager frame: n independent levels of ONE block family (_binding.Family) through autograd, one library call each way.  _BlockFn and
+# the two table builders under it hold the only level loops; a family adds a _Block: its checks, its inputs, what it saves, what it returns
+# ---------------------------------------------------------------------------------------------------------
+class _Block:
+    """What one family's eager call adds to the frame.  ``inputs`` names a level's tensors in the order they are passed, ``saved`` the ones
+    its backward gets back, in the order they are saved; "params" stands for the family's parameters (``family.param_names``), every other
+    name for one tensor.  The frame derives every position from the two: the slice of a level, where a gradient goes in the returned
+    tuple, whether dL/dmask is wanted.  An input that is none of "x", "mask", "params" is a buffer: its gradient is None."""
+    family: Family
+    name: str                                   # what the refusals call the function
+    device_only = True                          # host tensors are refused by that name (False: by the same-GPU refusal, as ever)
+    same_gpu = True                             # the same-GPU refusal (False: the family's own argument check covers the device)
+    pooled = False                              # ctx comes from _POOL, keyed by the stream
+    inputs: Tuple[str, ...]
+    saved: Tuple[str, ...]
+    fwd_args = bwd_args = ()                    # what the entry points take after (levels, n)
+
+    def __init__(self):
+        expand = lambda declared: tuple(n for d in declared for n in (self.family.param_names if d == "params" else (d,)))
+        self.input_names, self.saved_names = expand(self.inputs), expand(self.saved)         # ("params" written out)
+        self.slots, self.n_saved = len(self.input_names), len(self.saved_names)
+        self.x_at = self.input_names.index("x")
+        self.mask_at = self.input_names.index("mask") if "mask" in self.inputs else None
+
+    def level(self, cfg, inp, dev):
+        """The family's argument checks, in their order, and the tensors a level's kernels read, from `inp`, the level's inputs in the
+        order of ``inputs`` -> (the cfg its fills take, channels_last?, the mask's (dtype, shape) | None, its running buffers | None,
+        {x, mask, params and whatever else ``saved`` names})"""
+        raise NotImplementedError
+
+    def out(self, x):
+        return torch.empty_like(x)              # (preserve_format: channels_last for a channels_last level)
+
+    def ctx_buffer(self, cfg, flags, x, stream, save_gamma):
+        """-> (a level's ctx, the _Lease it came with | None)"""
+        return torch.empty(self.family.ctx_bytes(x.shape, cfg, flags), dtype=torch.uint8, device=x.device), None
+
+    def grad_in(self, gy, x, nhwc):
+        return _grad_in(gy, x, nhwc)
+
+    def pack(self, b: dict) -> list:
+        """a level's tensors for save_for_backward, in the order of ``saved_names``"""
+        return [t for k in self.saved for t in (b[k] if k == "params" else (b[k],))]
+
+    def unpack(self, run) -> dict:
+        """pack's inverse: {name in ``saved``: tensor, "params": list} from a level's run of saved tensors; "mask": None unless saved"""
+        it = iter(run)
+        return {"mask": None, **{k: [next(it) for _ in self.family.param_names] if k == "params" else next(it) for k in self.saved}}
 
 
-class _PyramidFn(torch.autograd.Function):
-    """n independent levels; flat inputs = n x (x, mask|None, w1, b1, w2, b2, wsa, beta)."""
+def _refuse_host(blk: _Block, xs: Sequence[torch.Tensor]) -> None:
+    """The frame runs device tensors of ONE GPU; these refusals stand in front of the table builders, which take host tensors too."""
+    if blk.device_only and not xs[0].is_cuda:
+        raise RuntimeError(f"{blk.name}: device tensors only (host tensors take the module's host path)")
+    if blk.same_gpu and not all(x.is_cuda and x.device == xs[0].device for x in xs):
+        raise RuntimeError(f"{blk.name}: all features must live on the same GPU")
+
+
+def _forward_tables(blk: _Block, cfgs, flat, want_grad: bool, stream=None):
+    """The table-building half of a forward, on tensors of any device, nothing launched -> (the filled level table, the outputs, the
+    tensors to save, per level what the backward needs besides: (cfg, flags, mask meta, running, lease), the tensors to hold until the call
+    is enqueued).  want_grad: a backward may come (MaskSPADE keeps gamma for it); stream: the pool's key (``blk.pooled``)."""
+    fam, k, n = blk.family, blk.slots, len(cfgs)
+    levels = (fam.fwd_level * n)()
+    dev = flat[blk.x_at].device
+    outs, keep, kept, hold = [], [], [], []
+    for l in range(n):
+        cfg, nhwc, mmeta, running, b = blk.level(cfgs[l], flat[l * k:(l + 1) * k], dev)
+        x = b["x"]
+        flags = fam.layout_nhwc if nhwc else 0
+        save_gamma = want_grad and b["mask"] is not None
+        y = blk.out(x)
+        b["ctx"], lease = blk.ctx_buffer(cfg, flags, x, stream, save_gamma)
+        nws = fam.ws_bytes(x.shape, cfg, flags)     # MaskCBAM, channels_last: per-chunk pooling partials, consumed inside this call
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+        fam.fill_fwd(levels[l], cfg, flags, y=y, ws=ws, running=running, save_gamma=save_gamma, **b)
+        hold.append(ws)
+        keep += blk.pack(b)
+        outs.append(y)
+        kept.append((cfg, flags, mmeta, running, lease))
+    return levels, outs, keep, kept, hold
+
+
+def _backward_tables(blk: _Block, kept, saved, gys, needs):
+    """The table-building half of a backward -> (the filled level table, what _BlockFn.backward returns: None per _LEAD, then the gradients
+    of the levels' inputs in the order of ``blk.input_names``, level after level; the tensors to hold until the call is enqueued).  kept,
+    saved: what _forward_tables gave; needs: ctx.needs_input_grad (dL/dmask is written only where it is wanted)."""
+    fam, k, ns = blk.family, blk.slots, blk.n_saved
+    levels = (fam.bwd_level * len(kept))()
+    grads, hold, lead = [None] * len(_LEAD), [], len(_LEAD)
+    for l, (cfg, flags, _, running, lease) in enumerate(kept):
+        b = blk.unpack(saved[l * ns:(l + 1) * ns])
+        if lease is not None:
+            b["ctx"] = lease.buf
+        x, mask = b["x"], b["mask"]
+        gy = blk.grad_in(gys[l], x, flags)
+        gx = torch.empty_like(x)                                   # (channels_last for NHWC levels, as x)
+        gmask = torch.empty_like(mask) if mask is not None and needs[lead + l * k + blk.mask_at] else None
+        pg = [None if p is None else torch.empty_like(p) for p in b["params"]]
+        scratch = torch.empty(fam.scratch_bytes(x.shape, cfg, flags), dtype=torch.uint8, device=x.device)
+        fam.fill_bwd(levels[l], cfg, flags, gy=gy, scratch=scratch, gx=gx, gmask=gmask, grads=pg, running=running, **b)
+        hold += [gy, scratch]
+        own = {"x": (gx,), "mask": (gmask,), "params": pg}
+        for name in blk.inputs:
+            grads += own.get(name, (None,))                      # (any other input is a buffer)
+    return levels, grads, hold
+
+
+class _BlockFn(torch.autograd.Function):
+    """n levels of the family ``blk``; cfgs: per level its config (the mask head: its BatchNorm state); flat: n x ``blk.input_names``."""
 
     @staticmethod
-    def forward(ctx, cfgs: Tuple[BlockConfig, ...], *flat):
+    def forward(ctx, blk: _Block, cfgs: tuple, *flat):
         n = len(cfgs)
-        assert len(flat) == n * SLOTS and 1 <= n <= _lib.MAX_LEVELS
+        assert len(flat) == n * blk.slots and 1 <= n <= _lib.MAX_LEVELS
         _lib.load()                                             # a missing library is the first thing a call reports
-        levels = (_lib.FwdLevel * n)()
-        keep: List[Optional[torch.Tensor]] = []
-        outs, meta, leases, layouts, hold = [], [], [], [], []
-        dev = flat[0].device
-        if not flat[0].is_cuda:
-            raise RuntimeError("mask_cbam: device tensors only (host tensors take the module's host path)")
-        stream = _raw_stream(dev)
-        for l in range(n):
-            x, mask, *params = flat[l * SLOTS:(l + 1) * SLOTS]
-            cfg = cfgs[l]
-            if not x.is_cuda or x.device != dev:
-                raise RuntimeError("mask_cbam: all features must live on the same GPU")
-            xc, m32, pc, flags, mmeta = _cbam_inputs(x, mask, params, cfg)
-            B, Cc, H, W = x.shape
-            y = torch.empty_like(xc)
-            # FWD_FUSE / BWD_FOLD contract: the hand-off flags at the end of ctx were zero-filled once (by the pool, at creation)
-            # (the flags count calls PER TILE, so a buffer is only reused under the tiling it was used with.  The library derives every
-            #  flagged tiling from the level alone -- shape, element type, conv size k, knobs; never from the other levels of the call --
-            #  and exactly those are in the key.  The merged backward's sweeps, whose channel groups do depend on the call, count per
-            #  channel instead: tests/test_gpu_composition.py)
-            key = (dev.index, stream, B, Cc, H, W, cfg.hidden, x.dtype, _lib.ENV_EPOCH, cfg.k) + ((flags,) if flags else ())
-            lease = _Lease(key, _POOL.take(key, _lib.ctx_bytes(B, Cc, H, W, cfg.hidden), _lib.ctx_layout(B, Cc, H, W, cfg.hidden)["sync"], dev))
-            leases.append(lease)
-            ws = None
-            if flags:                                           # per-chunk pooling partials, consumed inside this call
-                ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, flags), dtype=torch.uint8, device=dev)
-                hold.append(ws)
-            # (no SAVE_PROJ in flags: the backward makes the W1-projection planes itself where they pay (include/mgacbam.h), and the
-            #  forward keeps k_gate; PyramidPlan(use_proj=True) and forward_with_ctx still drive the forward producer, k_chan)
-            fill_cbam_fwd(levels[l], xc, m32, y, lease.buf, pc, cfg, flags, ws)
-            keep += [xc, m32, *pc]
-            outs.append(y)
-            layouts.append(flags)
-            meta.append(mmeta)
-        _call("mgacbam_forward_stages", dev, levels, n, _FWD_STAGES)
+        dev = flat[blk.x_at].device
+        _refuse_host(blk, flat[blk.x_at::blk.slots])
+        levels, outs, keep, kept, hold = _forward_tables(blk, cfgs, flat, any(ctx.needs_input_grad), _raw_stream(dev) if blk.pooled else None)
+        _call(blk.family.fwd_entry, dev, levels, n, *blk.fwd_args)
         del hold
-        if _CHECK_HANDOFF:
-            _check_status([(ls.buf, ls.key[2:7]) for ls in leases], "mask_cbam forward")
+        if _CHECK_HANDOFF and blk.pooled:
+            _check_status([lease for *_, lease in kept], f"{blk.name} forward")
         ctx.save_for_backward(*keep)
-        ctx.cfgs, ctx.meta, ctx.leases, ctx.layouts = cfgs, meta, leases, layouts
+        ctx.blk, ctx.kept, ctx.dev = blk, kept, dev
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *gys):
-        cfgs, n = ctx.cfgs, len(ctx.cfgs)
-        saved = ctx.saved_tensors
-        levels = (_lib.BwdLevel * n)()
-        grads: List[Optional[torch.Tensor]] = [None]
-        hold = []
-        dev = saved[0].device
-        for l in range(n):
-            xc, m32, *pc = saved[l * SLOTS:(l + 1) * SLOTS]
-            cfg = cfgs[l]
-            B, Cc, H, W = xc.shape
-            flags = ctx.layouts[l]
-            gy = _grad_in(gys[l], xc, flags & _lib.LAYOUT_NHWC)
-            want_gmask = m32 is not None and ctx.needs_input_grad[1 + l * SLOTS + 1]
-            gx = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
-            gmask = torch.empty_like(m32) if want_gmask else None
-            pg = [torch.empty_like(p) for p in pc]
-            scratch = torch.empty(_lib.scratch_bytes(B, Cc, H, W, cfg.hidden, cfg.k, flags), dtype=torch.uint8, device=dev)
-            fill_cbam_bwd(levels[l], xc, m32, gy, ctx.leases[l].buf, scratch, gx, gmask, pg, pc, cfg, flags)
-            hold += [gy, scratch]
-            grads += [gx, gmask, *pg]
-        _call("mgacbam_backward_stages", dev, levels, n, _BWD_STAGES)
+        blk, kept = ctx.blk, ctx.kept
+        levels, grads, hold = _backward_tables(blk, kept, ctx.saved_tensors, gys, ctx.needs_input_grad)
+        _call(blk.family.bwd_entry, ctx.dev, levels, len(kept), *blk.bwd_args)
         del hold
-        _gmask_out(grads, SLOTS, ctx.meta)
-        if _CHECK_HANDOFF:
-            _check_status([(ls.buf, ls.key[2:7]) for ls in ctx.leases], "mask_cbam backward")
+        _gmask_out(grads, blk, kept)
+        if _CHECK_HANDOFF and blk.pooled:
+            _check_status([lease for *_, lease in kept], f"{blk.name} backward")
         return tuple(grads)
+
+
+class _CbamBlock(_Block):
+    family, name, pooled = CBAM, "mask_cbam", True
+    inputs = saved = ("x", "mask", "params")                    # (ctx is not saved: it is the pool's, held by the level's lease)
+    fwd_args = (_lib.FWD_ALL | (_lib.FWD_FUSE if _FUSE_FWD else 0),)
+    bwd_args = (_lib.BWD_ALL | (_lib.BWD_FOLD if _FOLD_BWD else 0),)
+
+    def level(self, cfg, inp, dev):         # (the AssertionError / TypeError / RuntimeError / ValueError split mirrors the reference, in its order)
+        x, mask, *params = inp
+        _check_feature(x, "MaskCBAM expects a (B,C,H,W) feature")                 # masked_cbam.py:160
+        B, _, H, W = x.shape
+        m32, mmeta = _mask_in(mask, B, H, W)
+        _check_params(x, params, cfg)
+        xc, nhwc = _feature_in(x)
+        return cfg, nhwc, mmeta, None, dict(x=xc, mask=m32, params=[_ready(p) for p in params])
+
+    def ctx_buffer(self, cfg, flags, x, stream, save_gamma):
+        # FWD_FUSE / BWD_FOLD contract: the hand-off flags at the end of ctx were zero-filled once (by the pool, at creation)
+        # (the flags count calls PER TILE, so a buffer is only reused under the tiling it was used with.  The library derives every
+        #  flagged tiling from the level alone -- shape, element type, conv size k, knobs; never from the other levels of the call --
+        #  and exactly those are in the key.  The merged backward's sweeps, whose channel groups do depend on the call, count per
+        #  channel instead: tests/test_gpu_composition.py)
+        # (no SAVE_PROJ in flags: the backward makes the W1-projection planes itself where they pay (include/mgacbam.h), and the
+        #  forward keeps k_gate; PyramidPlan(use_proj=True) and forward_with_ctx still drive the forward producer, k_chan)
+        (B, Cc, H, W), dev = x.shape, x.device
+        key = (dev.index, stream, B, Cc, H, W, cfg.hidden, x.dtype, _lib.ENV_EPOCH, cfg.k) + ((flags,) if flags else ())
+        lease = _Lease(key, _POOL.take(key, _lib.ctx_bytes(B, Cc, H, W, cfg.hidden), _lib.ctx_layout(B, Cc, H, W, cfg.hidden)["sync"], dev))
+        return lease.buf, lease
+
+
+_CBAM = _CbamBlock()
+SLOTS = _CBAM.slots     # tensors per level in the flat argument list: x, mask, w1, b1, w2, b2, wsa, beta
 
 
 def mask_cbam_pyramid(levels: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], Sequence[torch.Tensor], BlockConfig]]):
     """levels: [(x, mask|None, (w1,b1,w2,b2,wsa,beta), BlockConfig), ...] -> tuple of outputs (one library call)."""
-    cfgs, flat = [], []
-    for x, mask, params, cfg in levels:
-        cfgs.append(cfg)
-        flat += [x, mask, *params]
-    return _PyramidFn.apply(tuple(cfgs), *flat)
+    return _BlockFn.apply(_CBAM, tuple(cfg for *_, cfg in levels), *(t for x, mask, params, _ in levels for t in (x, mask, *params)))
 
 
 def mask_cbam(x: torch.Tensor, mask: Optional[torch.Tensor], w1, b1, w2, b2, wsa, beta, cfg: BlockConfig) -> torch.Tensor:
     """y = x + softplus(beta) * (SAM(CAM(x, mask), mask) - x) for a device tensor x (B,C,H,W)."""
-    return _PyramidFn.apply((cfg,), x, mask, w1, b1, w2, b2, wsa, beta)[0]
+    return _BlockFn.apply(_CBAM, (cfg,), x, mask, w1, b1, w2, b2, wsa, beta)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -324,13 +414,13 @@ def mask_cbam(x: torch.Tensor, mask: Optional[torch.Tensor], w1, b1, w2, b2, wsa
 def forward_with_ctx(x, mask, params, cfg: BlockConfig, save_proj: bool = True):
     """-> (y, {name: tensor view into ctx}) without autograd; names follow mgacbam_ctx_layout_t.  A channels_last x runs the
     channels-last kernels (y comes back channels_last); the ctx views are the same for both layouts."""
-    xc, m32, pc, flags, _ = _cbam_inputs(x.detach(), None if mask is None else mask.detach(), [p.detach() for p in params], cfg)
+    _, nhwc, _, _, b = _CBAM.level(cfg, (x.detach(), None if mask is None else mask.detach(), *(p.detach() for p in params)), x.device)
     B, Cc, H, W = x.shape
-    y = torch.empty_like(xc)
+    y, flags = torch.empty_like(b["x"]), (_lib.LAYOUT_NHWC if nhwc else 0)
     cbuf = torch.zeros(_lib.ctx_bytes(B, Cc, H, W, cfg.hidden), dtype=torch.uint8, device=x.device)
     ws = torch.empty(_lib.fwd_ws_bytes(B, Cc, H, W, cfg.hidden, flags), dtype=torch.uint8, device=x.device) if flags else None
     lv = (_lib.FwdLevel * 1)()
-    fill_cbam_fwd(lv[0], xc, m32, y, cbuf, pc, cfg, flags | (_lib.FWD_SAVE_PROJ if (save_proj and mask is not None) else 0), ws)
+    CBAM.fill_fwd(lv[0], cfg, flags | (_lib.FWD_SAVE_PROJ if (save_proj and mask is not None) else 0), y=y, ctx=cbuf, ws=ws, **b)
     _call("mgacbam_forward", x.device, lv, 1)
     return y, ctx_views(cbuf, B, Cc, H, W, cfg.hidden)
 
@@ -371,68 +461,24 @@ class EcaConfig:
 _ECA_NHWC_MAX_C = 4096
 
 
-class _EcaFn(torch.autograd.Function):
-    """n independent levels; flat inputs = n x (x, mask|None, conv1d.weight, beta).  The layout decides the kernels, per level (MaskCBAM's
-    rule, _is_nhwc): a channels_last x runs the channels-last kernels without a copy and y / gx come back channels_last."""
+class _EcaBlock(_Block):
+    """The layout decides the kernels, per level (MaskCBAM's rule, _is_nhwc): a channels_last x runs the channels-last kernels without a
+    copy and y / gx come back channels_last."""
+    family, name, device_only = ECA, "mask_eca", False
+    inputs, saved = ("x", "mask", "params"), ("x", "mask", "ctx", "params")
 
-    @staticmethod
-    def forward(ctx, cfgs: Tuple[EcaConfig, ...], *flat):
-        n = len(cfgs)
-        assert len(flat) == 4 * n and 1 <= n <= _lib.MAX_LEVELS
-        _lib.load()                                             # a missing library is the first thing a call reports
-        levels = (_lib.EcaFwdLevel * n)()
-        keep, outs, meta, layouts = [], [], [], []
-        dev = flat[0].device
-        for l in range(n):
-            x, mask, w, beta = flat[4 * l:4 * l + 4]
-            cfg = cfgs[l]
-            if not x.is_cuda or x.device != dev:
-                raise RuntimeError("mask_eca: all features must live on the same GPU")
-            _check_feature(x, "feature must be (B,C,H,W)")                            # masked_eca.py:174
-            B, Cc, H, W = x.shape
-            m32, mmeta = _mask_in(mask, B, H, W)
-            if tuple(w.shape) != (1, 1, cfg.k) or beta.dim() != 0:
-                raise ValueError(f"MaskECA parameters: expected conv1d.weight (1,1,{cfg.k}) and scalar beta")
-            xc, nhwc = _feature_in(x, Cc <= _ECA_NHWC_MAX_C)
-            flags = _lib.LAYOUT_NHWC if nhwc else 0
-            wc, bc = _param32(w), _param32(beta)
-            y = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
-            cbuf = torch.empty(_lib.eca_ctx_bytes(B, Cc, H, W, flags), dtype=torch.uint8, device=dev)
-            fill_eca_fwd(levels[l], xc, m32, y, cbuf, wc, bc, cfg, flags)
-            keep += [xc, m32, cbuf, wc, bc]
-            outs.append(y)
-            layouts.append(flags)
-            meta.append(mmeta)
-        _call("mgacbam_eca_forward", dev, levels, n)
-        ctx.save_for_backward(*keep)
-        ctx.cfgs, ctx.meta, ctx.layouts = cfgs, meta, layouts
-        return tuple(outs)
+    def level(self, cfg, inp, dev):
+        x, mask, w, beta = inp
+        _check_feature(x, "feature must be (B,C,H,W)")                            # masked_eca.py:174
+        B, Cc, H, W = x.shape
+        m32, mmeta = _mask_in(mask, B, H, W)
+        if tuple(w.shape) != (1, 1, cfg.k) or beta.dim() != 0:
+            raise ValueError(f"MaskECA parameters: expected conv1d.weight (1,1,{cfg.k}) and scalar beta")
+        xc, nhwc = _feature_in(x, Cc <= _ECA_NHWC_MAX_C)
+        return cfg, nhwc, mmeta, None, dict(x=xc, mask=m32, params=[_param32(w), _param32(beta)])
 
-    @staticmethod
-    def backward(ctx, *gys):
-        cfgs, n = ctx.cfgs, len(ctx.cfgs)
-        saved = ctx.saved_tensors
-        levels = (_lib.EcaBwdLevel * n)()
-        grads: List[Optional[torch.Tensor]] = [None]
-        hold = []
-        dev = saved[0].device
-        for l in range(n):
-            xc, m32, cbuf, wc, bc = saved[5 * l:5 * l + 5]
-            B, Cc, H, W = xc.shape
-            flags = ctx.layouts[l]
-            gy = _grad_in(gys[l], xc, flags & _lib.LAYOUT_NHWC)
-            want_gmask = m32 is not None and ctx.needs_input_grad[1 + 4 * l + 1]
-            gx = torch.empty_like(xc)                              # (channels_last for NHWC levels, as xc)
-            gmask = torch.empty_like(m32) if want_gmask else None
-            gw, gb = torch.empty_like(wc), torch.empty_like(bc)
-            scratch = torch.empty(_lib.eca_scratch_bytes(B, Cc, H, W, flags), dtype=torch.uint8, device=dev)
-            fill_eca_bwd(levels[l], xc, m32, gy, cbuf, scratch, gx, gmask, gw, gb, wc, bc, cfgs[l], flags)
-            hold += [gy, scratch]
-            grads += [gx, gmask, gw, gb]
-        _call("mgacbam_eca_backward", dev, levels, n)
-        del hold
-        _gmask_out(grads, 4, ctx.meta)
-        return tuple(grads)
+
+_ECA = _EcaBlock()
 
 
 def mask_eca(x: torch.Tensor, mask: Optional[torch.Tensor], w: torch.Tensor, beta: torch.Tensor, cfg: EcaConfig) -> torch.Tensor:
@@ -440,17 +486,13 @@ def mask_eca(x: torch.Tensor, mask: Optional[torch.Tensor], w: torch.Tensor, bet
     A channels_last x with C <= 4096 is taken as it is (no layout copy); y and dL/dx are then channels_last too.  Any other layout, and a
     wider channels_last feature, is copied to NCHW once and runs the NCHW kernels, as before.  The NCHW kernels take C <= 5117 (the
     backward's LDS, csrc/api_eca.hip: kEcaNchwMaxC); a wider feature raises here, at the forward, with the library's message."""
-    return _EcaFn.apply((cfg,), x, mask, w, beta)[0]
+    return _BlockFn.apply(_ECA, (cfg,), x, mask, w, beta)[0]
 
 
 def mask_eca_pyramid(levels: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, torch.Tensor, EcaConfig]]):
     """levels: [(x, mask|None, conv1d.weight, beta, EcaConfig), ...] -> tuple of outputs (one library call each way).  Levels may mix
     layouts: each channels_last feature runs the channels-last kernels, the others the NCHW ones."""
-    cfgs, flat = [], []
-    for x, mask, w, beta, cfg in levels:
-        cfgs.append(cfg)
-        flat += [x, mask, w, beta]
-    return _EcaFn.apply(tuple(cfgs), *flat)
+    return _BlockFn.apply(_ECA, tuple(cfg for *_, cfg in levels), *(t for *tensors, _ in levels for t in tensors))
 
 
 def resize_nearest(src: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
@@ -707,79 +749,49 @@ def prob_mask_gate_pyramid(masks: Sequence[torch.Tensor], state: torch.Tensor, c
 # MGAMaskHead: Conv1x1 -> BatchNorm2d -> SiLU -> Conv3x3 as 3 launches forward, 5 backward (csrc/head.cuh); a channels_last
 # feature takes the NHWC forms of the GEMM kernels (csrc/head_nhwc.cuh) without a copy, and its gx comes back channels_last
 # ---------------------------------------------------------------------------------------------------------
-class _HeadFn(torch.autograd.Function):
-    """n independent levels; flat inputs = n x (x, proj.0.weight, proj.1.weight, proj.1.bias, head.weight, head.bias);
-    ``state`` = per level (running_mean, running_var, num_batches_tracked | None, eps, momentum, training): buffers updated in place."""
+class _HeadBlock(_Block):
+    """A level's "cfg" is its BatchNorm state (running_mean, running_var, num_batches_tracked | None, eps, momentum, training): buffers
+    updated in place.  running_mean / running_var are saved as tensors although the backward's table gets them with the state: autograd
+    then refuses a backward after an in-place change of either."""
+    family, name, same_gpu = HEAD, "mask_head", False
+    inputs, saved = ("x", "params"), ("x", "ctx", "params", "running_mean", "running_var")
 
-    @staticmethod
-    def forward(ctx, state: tuple, *flat):
-        n = len(state)
-        assert len(flat) == 6 * n and 1 <= n <= _lib.MAX_LEVELS
-        _lib.load()                                             # a missing library is the first thing a call reports
-        levels = (_lib.HeadFwdLevel * n)()
-        keep, outs, meta = [], [], []
-        dev = flat[0].device
-        if not flat[0].is_cuda:
-            raise RuntimeError("mask_head: device tensors only (host tensors take the module's host path)")
-        for l in range(n):
-            x, w1, gamma, beta, wh, bh = flat[6 * l:6 * l + 6]
-            rmean, rvar, nbt, eps, momentum, training = state[l]
-            if x.dim() != 4 or x.dtype not in _DTYPES or x.device != dev:
-                raise RuntimeError("mask_head: x must be a (B,C,H,W) fp32 / fp16 / bf16 tensor on one GPU")
-            B, Cc, H, W = x.shape
-            hid = w1.shape[0]
-            if tuple(w1.shape[:2]) != (hid, Cc) or tuple(wh.shape) != (1, hid, 3, 3) or bh.numel() != 1 or gamma.numel() != hid:
-                raise ValueError(f"mask_head: parameter shapes do not match C={Cc}, hidden={hid} (out_channels must be 1)")
-            if training and B * H * W == 1:                     # torch.nn.functional.batch_norm refuses this too (no variance from one value)
-                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
-            xc, nhwc = _feature_in(x)                           # the layout decides the GEMM kernels, per level (MaskCBAM's rule)
-            fl = _lib.HEAD_LAYOUT_NHWC if nhwc else 0
-            pc = [_param32(t) for t in (w1, gamma, beta, wh, bh)]
-            for t in (rmean, rvar):
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                    raise ValueError("mask_head: running statistics must be contiguous fp32 tensors on the feature's device")
-            logits = torch.empty(B, 1, H, W, dtype=x.dtype, device=dev)
-            cbuf = torch.empty(_lib.head_ctx_bytes(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
-            fill_head_fwd(levels[l], xc, logits, cbuf, pc, (rmean, rvar, nbt), hid, float(eps), float(momentum), training, fl)
-            keep += [xc, cbuf, *pc, rmean, rvar]
-            outs.append(logits)
-            meta.append((hid, float(eps), float(momentum), bool(training), tuple(w1.shape), fl))
-        _call("mgahead_forward", dev, levels, n)
-        ctx.save_for_backward(*keep)
-        ctx.meta = meta
-        return tuple(outs)
+    def level(self, state, inp, dev):
+        x, w1, gamma, beta, wh, bh = inp
+        rmean, rvar, nbt, eps, momentum, training = state
+        if x.dim() != 4 or x.dtype not in _DTYPES or x.device != dev:
+            raise RuntimeError("mask_head: x must be a (B,C,H,W) fp32 / fp16 / bf16 tensor on one GPU")
+        B, Cc, H, W = x.shape
+        hid = w1.shape[0]
+        if tuple(w1.shape[:2]) != (hid, Cc) or tuple(wh.shape) != (1, hid, 3, 3) or bh.numel() != 1 or gamma.numel() != hid:
+            raise ValueError(f"mask_head: parameter shapes do not match C={Cc}, hidden={hid} (out_channels must be 1)")
+        if training and B * H * W == 1:                     # torch.nn.functional.batch_norm refuses this too (no variance from one value)
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        xc, nhwc = _feature_in(x)                           # the layout decides the GEMM kernels, per level (MaskCBAM's rule)
+        pc = [_param32(t) for t in (w1, gamma, beta, wh, bh)]     # (dL/dw1 comes back in w1's shape: _param32 keeps it)
+        for t in (rmean, rvar):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError("mask_head: running statistics must be contiguous fp32 tensors on the feature's device")
+        return ((hid, float(eps), float(momentum), bool(training)), nhwc, None, (rmean, rvar, nbt),
+                dict(x=xc, mask=None, params=pc, running_mean=rmean, running_var=rvar))
 
-    @staticmethod
-    def backward(ctx, *gls):
-        n = len(ctx.meta)
-        saved = ctx.saved_tensors
-        levels = (_lib.HeadBwdLevel * n)()
-        grads: List[Optional[torch.Tensor]] = [None]
-        hold = []
-        dev = saved[0].device
-        for l in range(n):
-            xc, cbuf, *pc, rmean, rvar = saved[9 * l:9 * l + 9]
-            hid, eps, momentum, training, w1_shape, fl = ctx.meta[l]
-            B, Cc, H, W = xc.shape
-            gl = gls[l]
-            gl = torch.zeros(B, 1, H, W, dtype=xc.dtype, device=dev) if gl is None else _aligned(gl.to(xc.dtype))
-            gx = torch.empty_like(xc, memory_format=torch.channels_last if fl else torch.contiguous_format)
-            pg = [torch.empty_like(t) for t in pc]
-            scratch = torch.empty(_lib.head_scratch_bytes(B, Cc, H, W, hid, fl), dtype=torch.uint8, device=dev)
-            fill_head_bwd(levels[l], xc, gl, None, cbuf, scratch, gx, pg, pc, (rmean, rvar), hid, eps, momentum, training, fl)
-            hold += [gl, scratch]
-            pg[0] = pg[0].view(w1_shape)
-            grads += [gx, *pg]
-        _call("mgahead_backward", dev, levels, n)
-        del hold
-        return tuple(grads)
+    def out(self, x):
+        B, _, H, W = x.shape
+        return torch.empty(B, 1, H, W, dtype=x.dtype, device=x.device)
+
+    def grad_in(self, gl, x, nhwc):
+        B, _, H, W = x.shape
+        return torch.zeros(B, 1, H, W, dtype=x.dtype, device=x.device) if gl is None else _aligned(gl.to(x.dtype))
+
+
+_HEAD = _HeadBlock()
 
 
 def mask_head(x: torch.Tensor, w1, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, wh, bh,
               eps: float = 1e-5, momentum: float = 0.1, training: bool = True) -> torch.Tensor:
     """Mask logits (B,1,H,W) = Conv3x3(SiLU(BatchNorm2d(Conv1x1(x)))) for a device tensor x; in training the running statistics
     (and num_batches_tracked) are updated in place exactly as torch's BatchNorm2d does (mga_yolo/nn/modules/segmentation.py:56-110)."""
-    return _HeadFn.apply(((running_mean, running_var, num_batches_tracked, eps, momentum, training),), x, w1, bn_weight, bn_bias, wh, bh)[0]
+    return _BlockFn.apply(_HEAD, ((running_mean, running_var, num_batches_tracked, eps, momentum, training),), x, w1, bn_weight, bn_bias, wh, bh)[0]
 
 
 def mask_head_pyramid(levels):
@@ -790,7 +802,7 @@ def mask_head_pyramid(levels):
     for x, w1, g_, b_, rm, rv, nbt, wh, bh, eps, mom, tr in levels:
         state.append((rm, rv, nbt, eps, mom, tr))
         flat += [x, w1, g_, b_, wh, bh]
-    return _HeadFn.apply(tuple(state), *flat)
+    return _BlockFn.apply(_HEAD, tuple(state), *flat)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -813,7 +825,6 @@ class SpadeConfig:
 
 
 SPADE_MAX_C, SPADE_MAX_HIDDEN = 1024, 64
-_SPADE_SLOTS = 11    # x, mask, w0, b0, wg, bg, wb, bb, running_mean, running_var, num_batches_tracked
 _spade_warned = set()
 
 
@@ -868,76 +879,27 @@ def spade_compose(x, mask, params, cfg: SpadeConfig, running=None) -> torch.Tens
     return gamma * x_hat + beta
 
 
-class _SpadeFn(torch.autograd.Function):
-    """n independent levels; flat inputs = n x (x, mask|None, w0, b0, wg, bg, wb, bb, running_mean|None, running_var|None, nbt|None).
-    Forward: statistics, weight pack and ONE fused launch (MFMA convs + FiLM); backward: plain launches (csrc/spade.cuh).  The layout
+class _SpadeBlock(_Block):
+    """Forward: statistics, weight pack and ONE fused launch (MFMA convs + FiLM); backward: plain launches (csrc/spade.cuh).  The layout
     decides the kernels, per level (_is_nhwc): a channels_last x runs the channels-last kernels (csrc/spade_nhwc.cuh) without a copy, y and
-    gx come back channels_last, and the results are the NCHW kernels' bit for bit."""
+    gx come back channels_last, and the results are the NCHW kernels' bit for bit.  A level without a mask reads no parameter: None each."""
+    family, name, device_only = SPADE, "mask_spade", False
+    inputs = ("x", "mask", "params", "running_mean", "running_var", "num_batches_tracked")
+    saved = ("x", "mask", "ctx", "params")
 
-    @staticmethod
-    def forward(ctx, cfgs: Tuple[SpadeConfig, ...], *flat):
-        n = len(cfgs)
-        assert len(flat) == _SPADE_SLOTS * n and 1 <= n <= _lib.MAX_LEVELS
-        _lib.load()                                             # a missing library is the first thing a call reports
-        levels = (_lib.SpadeLevel * n)()
-        dev = flat[0].device
-        want_grad = any(ctx.needs_input_grad)
-        keep, outs, meta, running = [], [], [], []
-        for l in range(n):
-            x, mask, w0, b0, wg, bg, wb, bb, rm, rv, nbt = flat[_SPADE_SLOTS * l:_SPADE_SLOTS * (l + 1)]
-            cfg = cfgs[l]
-            if not x.is_cuda or x.device != dev:
-                raise RuntimeError("mask_spade: all features must live on the same GPU")
-            B, Cc, H, W = x.shape
-            xc, nhwc = _feature_in(x)
-            m32, mmeta = _mask_in(mask, B, H, W)
-            ps = [None] * 6 if mask is None else [_param32(t) for t in (w0, b0, wg, bg, wb, bb)]
-            y = torch.empty_like(xc)                                # (preserve_format: channels_last for a channels_last level)
-            elem = xc.element_size()
-            full = _lib.spade_ctx_bytes(B, Cc, H, W, cfg.hidden)
-            a16 = lambda v: (v + 15) & ~15
-            base = full - a16(xc.numel() * 4)
-            save = want_grad and m32 is not None
-            cbuf = torch.empty(base + (a16(xc.numel() * elem) if save else 0), dtype=torch.uint8, device=dev)
-            fill_spade(levels[l], xc, m32, ps, cfg, (rm, rv, nbt), cbuf, y=y, save_gamma=save,
-                       flags=_lib.SPADE_LAYOUT_NHWC if nhwc else 0)
-            keep += [xc, m32, cbuf] + ps
-            outs.append(y)
-            meta.append(mmeta)
-            running.append((rm, rv, nbt))
-        _call("mgaspade_forward", dev, levels, n)
-        ctx.save_for_backward(*keep)
-        ctx.cfgs, ctx.meta, ctx.running = cfgs, meta, running
-        return tuple(outs)
+    def level(self, cfg, inp, dev):
+        x, mask, *params, rm, rv, nbt = inp
+        B, _, H, W = x.shape
+        xc, nhwc = _feature_in(x)
+        m32, mmeta = _mask_in(mask, B, H, W)
+        ps = [None] * len(params) if mask is None else [_param32(t) for t in params]
+        return cfg, nhwc, mmeta, (rm, rv, nbt), dict(x=xc, mask=m32, params=ps)
 
-    @staticmethod
-    def backward(ctx, *gys):
-        cfgs, n = ctx.cfgs, len(ctx.cfgs)
-        saved = ctx.saved_tensors
-        levels = (_lib.SpadeLevel * n)()
-        grads: List[Optional[torch.Tensor]] = [None]
-        hold = []
-        dev = saved[0].device
-        for l in range(n):
-            xc, m32, cbuf = saved[9 * l:9 * l + 3]
-            ps = list(saved[9 * l + 3:9 * l + 9])
-            cfg = cfgs[l]
-            B, Cc, H, W = xc.shape
-            nhwc = _is_nhwc(xc)                                     # xc is dense in one of the two layouts: the forward's answer
-            gy = _grad_in(gys[l], xc, nhwc)
-            gx = torch.empty_like(xc)
-            want_gmask = m32 is not None and ctx.needs_input_grad[1 + _SPADE_SLOTS * l + 1]
-            gmask = torch.empty_like(m32) if want_gmask else None
-            gps = [None] * 6 if m32 is None else [torch.empty_like(p) for p in ps]
-            scratch = torch.empty(_lib.spade_scratch_bytes(B, Cc, H, W, cfg.hidden), dtype=torch.uint8, device=dev)
-            fill_spade(levels[l], xc, m32, ps, cfg, ctx.running[l], cbuf, gy=gy, gx=gx, gmask=gmask, pgrads=gps, scratch=scratch,
-                       flags=_lib.SPADE_LAYOUT_NHWC if nhwc else 0)
-            hold += [gy, scratch]
-            grads += [gx, gmask] + gps + [None, None, None]
-        _call("mgaspade_backward", dev, levels, n)
-        del hold
-        _gmask_out(grads, _SPADE_SLOTS, ctx.meta)
-        return tuple(grads)
+    def ctx_buffer(self, cfg, flags, x, stream, save_gamma):
+        return torch.empty(spade_eager_ctx_bytes(x.shape, cfg, x.element_size() if save_gamma else 0), dtype=torch.uint8, device=x.device), None
+
+
+_SPADE = _SpadeBlock()
 
 
 def _spade_apply(cfgs, flat):
@@ -945,7 +907,7 @@ def _spade_apply(cfgs, flat):
     parameter that requires grad as needing one whatever the grad mode, and the forward would keep gamma for a backward that cannot come."""
     if not torch.is_grad_enabled():
         flat = [t.detach() if isinstance(t, torch.Tensor) else t for t in flat]
-    return _SpadeFn.apply(tuple(cfgs), *flat)
+    return _BlockFn.apply(_SPADE, tuple(cfgs), *flat)
 
 
 def _spade_prepare(x, mask, params, cfg: SpadeConfig, running):
@@ -985,10 +947,7 @@ def mask_spade(x: torch.Tensor, mask: Optional[torch.Tensor], params: Sequence[t
     """y = gamma(mask) * norm(x) + beta(mask) for a device tensor.  params = (shared.0.weight, shared.0.bias, conv_gamma.weight,
     conv_gamma.bias, conv_beta.weight, conv_beta.bias); running = (running_mean, running_var, num_batches_tracked) for norm_type 'bn'
     (updated in place by a training call).  Gradients reach x, the mask and the six parameters."""
-    flat = _spade_prepare(x, mask, params, cfg, running)
-    if flat is None:
-        return spade_compose(x, mask, params, cfg, running)
-    return _spade_apply((cfg,), flat)[0]
+    return mask_spade_pyramid([(x, mask, params, cfg, running)])[0]
 
 
 def mask_spade_pyramid(levels):

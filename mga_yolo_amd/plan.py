@@ -5,8 +5,8 @@ step are recorded once and replayed, instead of being issued from Python every s
 
 ``PyramidPlan`` (MaskCBAM), ``EcaPyramidPlan`` and ``SpadePyramidPlan`` are one executor, ``_BlockPlan``: it owns, per level, x, mask, y,
 gy, gx, gmask, ctx, scratch, the level tables, and ONE flat fp32 bucket holding the parameter gradients of all levels (what data-parallel
-training all-reduces, see ``dp.py``), on NCHW or on ``torch.channels_last`` features.  A subclass states its level structs, layout flag,
-parameter names and ``kind``, the byte counts of a level's ctx and scratch and the ``fill_*`` calls of its tables, and adds what only it has.
+training all-reduces, see ``dp.py``), on NCHW or on ``torch.channels_last`` features.  A subclass states its ``family`` (_binding.Family:
+level structs, layout flag, byte counts, fills, entry points, parameter names) and adds what only it has.
 
 ``PyramidPlan.forward`` / ``backward`` each make ONE library call on the current stream (5 kernel launches per step in total).
 ``backward_params`` + ``backward_inputs`` is the split form for callers that want the parameter gradients early (see ``dp.py``).
@@ -21,18 +21,14 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
-import os
-
 import torch
 
 from . import _lib
-from ._binding import fill_cbam_bwd, fill_cbam_fwd, fill_eca_bwd, fill_eca_fwd, fill_gate, fill_resample, fill_spade
-from .functional import (BlockConfig, GateConfig, HandoffTimeout, SpadeConfig, ctx_views, gate_state, spade_check_norm, spade_kernel_reason,
-                         status_words)
+from ._binding import CBAM, ECA, SPADE, Family, fill_gate, fill_resample
+from .functional import (BlockConfig, GateConfig, SpadeConfig, ctx_views, gate_state, handoff_check, spade_check_norm, spade_kernel_reason,
+                         stage_switches)
 
-PARAM_NAMES = ("w1", "b1", "w2", "b2", "wsa", "beta")
-ECA_PARAM_NAMES = ("conv1d.weight", "beta")
-SPADE_PARAM_NAMES = ("shared.0.weight", "shared.0.bias", "conv_gamma.weight", "conv_gamma.bias", "conv_beta.weight", "conv_beta.bias")
+PARAM_NAMES, ECA_PARAM_NAMES, SPADE_PARAM_NAMES = CBAM.param_names, ECA.param_names, SPADE.param_names
 GROUP_MAX = 4      # levels of one signature per launch (csrc/args.cuh: kGroupMax)
 
 
@@ -83,20 +79,24 @@ class _BlockPlan(_Executor):
     clones of the parameters, their gradients as views into ONE flat fp32 ``grad_bucket`` -- the plan's own, or a caller's slice of a larger
     one -- and the two C-ABI level tables ``_fwd`` / ``_bwd``.
 
-    A subclass states the class attributes below and two hooks, ``_level_bytes`` and ``_fill_level``; whatever else is its own (MaskCBAM's
-    gate, MaskSPADE's running statistics and mask sources) it builds in a ``_setup`` of its own around this one.
+    A subclass states its ``family``, from which the struct types, the layout flag, the byte counts, the fills and the parameter names
+    come; whatever else is its own (MaskCBAM's gate, workspace and projection flags, MaskSPADE's running statistics and mask sources) it
+    builds in a ``_setup`` of its own around this one and in ``_level_own``.
 
     ``__init__`` and ``create`` of a subclass only name its arguments and hand them to ``_setup``.  There are two because the argument lists
     of the constructors are public and pinned (tests/test_gate_abi.py, test_opt_abi.py, test_abi_eca_nhwc.py): an option added later
     (PyramidPlan's ``channels_last``, EcaPyramidPlan's ``grad_bucket``) is a keyword of ``create``, which takes every argument of
     ``_setup``."""
-    kind: str                                   # "cbam" | "eca" | "spade": what optim.plan_segments classifies the parameters by
-    param_names: Tuple[str, ...]                # a level's parameters, in the order of ``params[l]`` and of the bucket
-    grad_names: Tuple[str, ...]                 # the keys of named_param_grads
-    fwd_level = bwd_level = None                # the ctypes structs of the two level tables
-    layout_nhwc: int                            # the level flag of torch.channels_last features
+    family: Family
+    kind: str                                   # family.kind: what optim.plan_segments classifies the parameters by
+    param_names: Tuple[str, ...]                # family.param_names: a level's parameters, in the order of ``params[l]`` and of the bucket
+    grad_names: Tuple[str, ...]                 # the keys of named_param_grads: param_names unless the subclass says otherwise
     _defaults = dict(dtype=torch.float32, device="cuda", with_mask=True, want_gmask=True, channels_last=False, grad_bucket=None)
     running: Sequence[tuple] = ()               # what _setup fills per level; optim.plan_segments finds none on a plan that was not set up
+
+    def __init_subclass__(cls):
+        cls.kind, cls.param_names = cls.family.kind, cls.family.param_names
+        cls.grad_names = cls.__dict__.get("grad_names", cls.param_names)
 
     @classmethod
     def _create(cls, shapes, params, cfgs, kw):
@@ -120,7 +120,8 @@ class _BlockPlan(_Executor):
         self.device = dev = torch.device(device)
         self.n, self.shapes, self.cfgs, self.dtype = len(shapes), list(shapes), list(cfgs), dtype
         self.with_mask, self.channels_last = bool(with_mask), bool(channels_last)
-        flags = self.layout_nhwc if self.channels_last else 0
+        fam = self.family
+        flags = fam.layout_nhwc if self.channels_last else 0
         fmt = torch.channels_last if self.channels_last else torch.contiguous_format
         self.params = [[p.detach().to(dev, torch.float32).contiguous() for p in ps] for ps in params]
         n_grad = sum(p.numel() for ps in self.params for p in ps)
@@ -129,24 +130,24 @@ class _BlockPlan(_Executor):
         assert grad_bucket.numel() == n_grad and grad_bucket.dtype == torch.float32 and grad_bucket.is_contiguous()
         self.grad_bucket, (self.param_grads, _) = grad_bucket, _carve(grad_bucket, self.params)
         self.x, self.mask, self.y, self.gy, self.gx, self.gmask, self.ctx, self.scratch = ([] for _ in range(8))
-        self._fwd, self._bwd = (self.fwd_level * self.n)(), (self.bwd_level * self.n)()
+        self._fwd, self._bwd = (fam.fwd_level * self.n)(), (fam.bwd_level * self.n)()
         for l, ((B, C, H, W), cfg) in enumerate(zip(shapes, cfgs)):
             mk = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
             mkf = lambda: torch.zeros(B, C, H, W, dtype=dtype, device=dev).contiguous(memory_format=fmt)
             self.x.append(mkf()); self.y.append(mkf()); self.gy.append(mkf()); self.gx.append(mkf())
             self.mask.append(mk(B, 1, H, W) if with_mask else None)
             self.gmask.append(mk(B, 1, H, W) if (with_mask and want_gmask) else None)
-            ctx_bytes, scratch_bytes = self._level_bytes((B, C, H, W), cfg, flags)
-            self.ctx.append(mk(ctx_bytes, dt=torch.uint8)); self.scratch.append(mk(scratch_bytes, dt=torch.uint8))
-            self._fill_level(l, self.params[l], self.param_grads[l], cfg, flags)
+            self.ctx.append(mk(fam.ctx_bytes((B, C, H, W), cfg, flags), dt=torch.uint8))
+            self.scratch.append(mk(fam.scratch_bytes((B, C, H, W), cfg, flags), dt=torch.uint8))
+            b = dict(x=self.x[l], mask=self.mask[l], y=self.y[l], gy=self.gy[l], gx=self.gx[l], gmask=self.gmask[l], ctx=self.ctx[l],
+                     scratch=self.scratch[l], params=self.params[l], grads=self.param_grads[l], running=self.running[l],
+                     save_gamma=self.with_mask)                 # (MaskSPADE: a plan's forward always keeps gamma for its backward)
+            fwd_flags, bwd_flags = self._level_own(l, cfg, flags, b)
+            fam.fill_fwd(self._fwd[l], cfg, fwd_flags, **b)
+            fam.fill_bwd(self._bwd[l], cfg, bwd_flags, **b)
 
-    def _level_bytes(self, shape, cfg, flags) -> Tuple[int, int]:
-        """(ctx bytes, scratch bytes) of a level"""
-        raise NotImplementedError
-
-    def _fill_level(self, l, ps, grads, cfg, flags) -> None:
-        """``_fwd[l]`` and ``_bwd[l]`` from the level's buffers (the fill_* calls of _binding.py)"""
-        raise NotImplementedError
+    def _level_own(self, l, cfg, flags, b: dict) -> Tuple[int, int]:
+        return flags, flags     # what a subclass adds to level l before its tables are filled: buffers into `b` -> (forward's, backward's flags)
 
     def elements(self) -> int:
         """E = sum over levels of B*C*H*W."""
@@ -157,8 +158,7 @@ class _BlockPlan(_Executor):
 
 
 class PyramidPlan(_BlockPlan):
-    kind, param_names, grad_names = "cbam", PARAM_NAMES, tuple("g" + n for n in PARAM_NAMES)
-    fwd_level, bwd_level, layout_nhwc = _lib.FwdLevel, _lib.BwdLevel, _lib.LAYOUT_NHWC
+    family, grad_names = CBAM, tuple("g" + n for n in CBAM.param_names)
     _defaults = dict(_BlockPlan._defaults, use_proj=False, fuse_forward=None, gate=None, seed=0)
 
     def __init__(self, shapes: Sequence[Tuple[int, int, int, int]], params: Sequence[Sequence[torch.Tensor]],
@@ -181,25 +181,21 @@ class PyramidPlan(_BlockPlan):
             raise ValueError("PyramidPlan: use_proj with channels_last (the channels-last backward ignores the projection planes)")
         self._use_proj = bool(use_proj)
         # fuse_forward: k_chan + k_apply as ONE x-resident launch, k_gate (MGACBAM_FWD_FUSE); None = env MGACBAM_FUSE_FWD (on)
-        self.fuse_forward = bool(int(os.environ.get("MGACBAM_FUSE_FWD", "1"))) if fuse_forward is None else bool(fuse_forward)
-        # transposed conv folded into the k_bwd_reduce1 launch (MGACBAM_BWD_FOLD) whenever the whole backward is one call
-        self.fold_backward = bool(int(os.environ.get("MGACBAM_FOLD_BWD", "1")))
+        # fold_backward: transposed conv folded into the k_bwd_reduce1 launch (MGACBAM_BWD_FOLD) whenever the whole backward is one call
+        env_fuse, self.fold_backward = stage_switches()
+        self.fuse_forward = env_fuse if fuse_forward is None else bool(fuse_forward)
         self.ws: List[Optional[torch.Tensor]] = []          # channels_last: the forward's per-chunk pooling partials
         super()._setup(shapes, params, cfgs, channels_last=channels_last, **common)
         self.gate = None if gate is None else list(gate)
         if self.gate is not None:
             self._init_gate(seed)
 
-    def _level_bytes(self, shape, cfg, flags):
-        return _lib.ctx_bytes(*shape, cfg.hidden), _lib.scratch_bytes(*shape, cfg.hidden, cfg.k, flags)
-
-    def _fill_level(self, l, ps, grads, cfg, flags):
-        ws = torch.zeros(_lib.fwd_ws_bytes(*self.shapes[l], cfg.hidden, flags), dtype=torch.uint8, device=self.device) if flags else None
-        self.ws.append(ws)
+    def _level_own(self, l, cfg, flags, b):
+        nws = CBAM.ws_bytes(self.shapes[l], cfg, flags)
+        b["ws"] = torch.zeros(nws, dtype=torch.uint8, device=self.device) if nws else None
+        self.ws.append(b["ws"])
         proj = self.gmask[l] is not None and self._use_proj      # the forward saves the W1-projection planes, the backward reads them
-        fill_cbam_fwd(self._fwd[l], self.x[l], self.mask[l], self.y[l], self.ctx[l], ps, cfg, flags | (_lib.FWD_SAVE_PROJ if proj else 0), ws)
-        fill_cbam_bwd(self._bwd[l], self.x[l], self.mask[l], self.gy[l], self.ctx[l], self.scratch[l], self.gx[l], self.gmask[l],
-                      grads, ps, cfg, flags | (_lib.BWD_HAVE_PROJ if proj else 0))
+        return flags | (_lib.FWD_SAVE_PROJ if proj else 0), flags | (_lib.BWD_HAVE_PROJ if proj else 0)
 
     def _init_gate(self, seed: int) -> None:
         """logits -> [gate] -> mask, gmask -> [gate backward] -> glogits: the buffers and the two level tables (include/mgagate.h)"""
@@ -222,18 +218,14 @@ class PyramidPlan(_BlockPlan):
         both = _lib.FWD_STAGES["chan"] | _lib.FWD_STAGES["apply"]
         if self.fuse_forward and (stages & both) == both:
             stages |= _lib.FWD_FUSE     # ctx is zero-filled at allocation, as the flag's contract asks
-        self._call("mgacbam_forward_stages", self._fwd, self.n, stages)
+        self._call(CBAM.fwd_entry, self._fwd, self.n, stages)
 
     def check_handoff(self) -> None:
         """Synchronise and raise HandoffTimeout if any in-launch hand-off of any call on this plan timed out (status word of each
         level's ctx, include/mgacbam.h).  Callers invoke it where they synchronise anyway: bench.py after the timed region,
         training loops after a batch of graph replays."""
         torch.cuda.synchronize(self.device)
-        words = status_words((self.ctx[l], (*shp, self.cfgs[l].hidden)) for l, shp in enumerate(self.shapes))
-        bad = [shp for shp, w in zip(self.shapes, words) if w != 0]
-        if bad:
-            raise HandoffTimeout(f"in-launch hand-off timed out for levels {bad}: affected tiles were poisoned with NaN "
-                                 "(is the GPU shared with other work?  MGACBAM_FUSE_FWD=0 runs without hand-offs)")
+        handoff_check(((self.ctx[l], (*shp, self.cfgs[l].hidden)) for l, shp in enumerate(self.shapes)), lambda bad: f"levels {bad}")
 
     def gate_active(self) -> bool:
         """True when the last fused forward really ran k_gate (the library falls back to k_chan + k_apply for groups with a
@@ -267,7 +259,7 @@ class PyramidPlan(_BlockPlan):
     def backward(self, stages: int = _lib.BWD_ALL):
         if stages == _lib.BWD_ALL and self.fold_backward:
             stages |= _lib.BWD_FOLD     # ctx is zero-filled at allocation, as the flag's contract asks
-        self._call("mgacbam_backward_stages", self._bwd, self.n, stages)
+        self._call(CBAM.bwd_entry, self._bwd, self.n, stages)
         if self.gate is not None and stages & _lib.BWD_STAGES["apply"] and self.glogits[0] is not None:   # k_bwd_apply has written gmask
             self._call("mgagate_backward", self._gate_bwd, self.n)
 
@@ -297,8 +289,7 @@ class EcaPyramidPlan(_BlockPlan):
     ``backward`` = one library call each (2 kernel launches each for all levels together).  ``channels_last=True`` runs the channels-last
     kernels (MGACBAM_LAYOUT_NHWC; 3 launches each way); masks and parameter gradients are the same in both layouts.  ``create`` takes
     ``grad_bucket=`` as well: a slice of a larger bucket owned by the caller (slice.SlicePlan)."""
-    kind, param_names, grad_names = "eca", ECA_PARAM_NAMES, ECA_PARAM_NAMES
-    fwd_level, bwd_level, layout_nhwc = _lib.EcaFwdLevel, _lib.EcaBwdLevel, _lib.LAYOUT_NHWC
+    family = ECA
 
     def __init__(self, shapes, params, cfgs, dtype=torch.float32, device="cuda", with_mask=True, want_gmask=True,
                  channels_last: bool = False):
@@ -310,19 +301,11 @@ class EcaPyramidPlan(_BlockPlan):
         """The constructor with the gradient bucket as an argument.  **kw: the constructor's keyword arguments."""
         return cls._create(shapes, params, cfgs, dict(kw, grad_bucket=grad_bucket))
 
-    def _level_bytes(self, shape, cfg, flags):
-        return _lib.eca_ctx_bytes(*shape, flags), _lib.eca_scratch_bytes(*shape, flags)
-
-    def _fill_level(self, l, ps, grads, cfg, flags):
-        fill_eca_fwd(self._fwd[l], self.x[l], self.mask[l], self.y[l], self.ctx[l], *ps, cfg, flags)
-        fill_eca_bwd(self._bwd[l], self.x[l], self.mask[l], self.gy[l], self.ctx[l], self.scratch[l], self.gx[l], self.gmask[l],
-                     *grads, *ps, cfg, flags)
-
     def forward(self):
-        self._call("mgacbam_eca_forward", self._fwd, self.n)
+        self._call(ECA.fwd_entry, self._fwd, self.n)
 
     def backward(self):
-        self._call("mgacbam_eca_backward", self._bwd, self.n)
+        self._call(ECA.bwd_entry, self._bwd, self.n)
 
     def launch_counts(self) -> Tuple[int, int]:
         """Kernel launches of forward() and of backward() (csrc/api_eca.hip, per group of levels of one signature)."""
@@ -341,8 +324,7 @@ class SpadePyramidPlan(_BlockPlan):
     ``mask_hw`` = per level (h, w) or None: such a level gets its mask at that resolution (masked_spade.py:102-110).  The plan then owns
     ``mask_src[l]`` (B,1,h,w) fp32, which the caller fills instead of ``mask[l]``, and ``gmask_src[l]``; ``forward`` first resamples
     mask_src -> mask and ``backward`` last resamples gmask -> gmask_src (include/mgaresample.h), one launch each for all such levels."""
-    kind, param_names, grad_names = "spade", SPADE_PARAM_NAMES, SPADE_PARAM_NAMES
-    fwd_level, bwd_level, layout_nhwc = _lib.SpadeLevel, _lib.SpadeLevel, _lib.SPADE_LAYOUT_NHWC
+    family = SPADE
 
     def __init__(self, shapes, params, cfgs: Sequence[SpadeConfig], dtype=torch.float32, device="cuda", with_mask=True, want_gmask=True,
                  channels_last: bool = False, grad_bucket: Optional[torch.Tensor] = None, running=None, mask_hw=None):
@@ -391,24 +373,13 @@ class SpadePyramidPlan(_BlockPlan):
                 fill_resample(self._rs_bwd[j], self.gmask[l], self.gmask_src[l], mask_hw[l], (H, W))
                 j += 1
 
-    def _level_bytes(self, shape, cfg, flags):
-        return _lib.spade_ctx_bytes(*shape, cfg.hidden), _lib.spade_scratch_bytes(*shape, cfg.hidden)
-
-    def _fill_level(self, l, ps, grads, cfg, flags):
-        if not self.with_mask:
-            ps, grads = [None] * 6, [None] * 6      # a level without a mask reads no parameter
-        run = self.running[l]
-        fill_spade(self._fwd[l], self.x[l], self.mask[l], ps, cfg, run, self.ctx[l], y=self.y[l], save_gamma=self.with_mask, flags=flags)
-        fill_spade(self._bwd[l], self.x[l], self.mask[l], ps, cfg, run, self.ctx[l], gy=self.gy[l], gx=self.gx[l], gmask=self.gmask[l],
-                   pgrads=grads, scratch=self.scratch[l], flags=flags)
-
     def forward(self):
         if self._n_rs:
             self._call("mgaspade_resample_forward", self._rs_fwd, self._n_rs)
-        self._call("mgaspade_forward", self._fwd, self.n)
+        self._call(SPADE.fwd_entry, self._fwd, self.n)
 
     def backward(self):
-        self._call("mgaspade_backward", self._bwd, self.n)
+        self._call(SPADE.bwd_entry, self._bwd, self.n)
         if self._n_rs_bwd:
             self._call("mgaspade_resample_backward", self._rs_bwd, self._n_rs_bwd)
 

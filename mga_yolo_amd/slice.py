@@ -35,13 +35,13 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._binding import fill_head_bwd, fill_head_fwd, fill_seg
+from ._binding import HEAD, fill_seg
 from .functional import BlockConfig, GateConfig, TargetPyramidCall, target_pyramid_check, target_pyramid_shapes
 from .plan import EcaPyramidPlan, PyramidPlan, SpadePyramidPlan, _carve, _Executor
 
 BLOCKS = ("cbam", "eca", "spade")
 TARGET_RESIZE = {"nearest": _lib.SEG_NEAREST, "bilinear": _lib.SEG_BILINEAR}
-HEAD_PARAM_NAMES = ("proj.0.weight", "proj.1.weight", "proj.1.bias", "head.weight", "head.bias")
+HEAD_PARAM_NAMES = HEAD.param_names
 
 
 def target_strides(shapes, target_source) -> Tuple[int, ...]:
@@ -188,26 +188,25 @@ class SlicePlan(_Executor):
         self._seg_cfg = _lib.SegCfg(1.0, 1.0, 1.0, 1.0, 0, 0.5, 0.6, 0.5)      # SegLossConfig defaults (losses/segmentation.py:9-21)
         self.seg_ws = torch.zeros(_lib.seg_ws_bytes(self._seg, self.n), dtype=torch.uint8, device=dev)
         # ---- mask heads -------------------------------------------------------------------------------------------------------------
-        self._hf, self._hb = (_lib.HeadFwdLevel * self.n)(), (_lib.HeadBwdLevel * self.n)()
+        self._hf, self._hb = (HEAD.fwd_level * self.n)(), (HEAD.bwd_level * self.n)()
         self.head_ctx, self.head_scratch = [], []
-        hfl = _lib.HEAD_LAYOUT_NHWC if self.channels_last else 0        # x, gx channels_last: the NHWC forms of the heads' GEMM kernels
-        for l, (B, Cc, H, W) in enumerate(shapes):
+        hfl = HEAD.layout_nhwc if self.channels_last else 0             # x, gx channels_last: the NHWC forms of the heads' GEMM kernels
+        for l, shp in enumerate(shapes):
             bn = (self.hidden[l], bn_eps, bn_momentum, training)
-            self.head_ctx.append(torch.zeros(_lib.head_ctx_bytes(B, Cc, H, W, self.hidden[l], hfl), dtype=torch.uint8, device=dev))
-            self.head_scratch.append(torch.zeros(_lib.head_scratch_bytes(B, Cc, H, W, self.hidden[l], hfl), dtype=torch.uint8, device=dev))
-            fill_head_fwd(self._hf[l], self.x[l], self.logits[l], self.head_ctx[l], self.head_params[l], self.head_buffers[l], *bn,
-                          hfl | _lib.HEAD_LOGITS_F32)
+            self.head_ctx.append(torch.zeros(HEAD.ctx_bytes(shp, bn, hfl), dtype=torch.uint8, device=dev))
+            self.head_scratch.append(torch.zeros(HEAD.scratch_bytes(shp, bn, hfl), dtype=torch.uint8, device=dev))
             # dL/dlogits = the loss's part (seg_glogits) + the block's dL/dmask, through the gate's backward when there is one (g_logits2):
             # summed while the head's backward loads them
-            fill_head_bwd(self._hb[l], self.x[l], self.seg_glogits[l], g_logits2[l], self.head_ctx[l], self.head_scratch[l], self.gx[l],
-                          self.head_grads[l], self.head_params[l], self.head_buffers[l], *bn,
-                          hfl | _lib.HEAD_BWD_ACCUM_GX | _lib.HEAD_LOGITS_F32)
+            b = dict(x=self.x[l], y=self.logits[l], gy=self.seg_glogits[l], gy2=g_logits2[l], gx=self.gx[l], ctx=self.head_ctx[l],
+                     scratch=self.head_scratch[l], params=self.head_params[l], grads=self.head_grads[l], running=self.head_buffers[l])
+            HEAD.fill_fwd(self._hf[l], bn, hfl | _lib.HEAD_LOGITS_F32, **b)
+            HEAD.fill_bwd(self._hb[l], bn, hfl | _lib.HEAD_BWD_ACCUM_GX | _lib.HEAD_LOGITS_F32, **b)
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def forward(self):
         if self._tgt is not None:
             self._tgt.run()                                                                            # mask_full -> targets
-        self._call("mgahead_forward", self._hf, self.n)                                                # features -> mask logits
+        self._call(HEAD.fwd_entry, self._hf, self.n)                                                # features -> mask logits
         self.block.forward()                                                                           # [feature, logits] -> refined (a gate first: logits -> mask)
         # logits, targets -> seg_total (+ log entries) -> Kendall total, the combine riding in the loss's last launch
         self._call("mgaseg_kendall_forward", self._seg, self.n, C.byref(self._seg_cfg), self.seg_ws.data_ptr(), self.seg_ws.numel(), self.seg_out.data_ptr(),
@@ -218,7 +217,7 @@ class SlicePlan(_Executor):
                    self.det_loss.data_ptr(), 3, self.log_vars.data_ptr(), self.g_total.data_ptr(),
                    self.g_det.data_ptr(), self.g_seg.data_ptr(), self.g_log_vars.data_ptr())          # -> seg_glogits, g_det, g_log_vars
         self.block.backward()                                                                          # gy -> gx (MaskCBAM's part), dL/dmask (its part of dL/dlogits; a gate's backward last)
-        self._call("mgahead_backward", self._hb, self.n)                                               # gx += head's part; head parameter gradients
+        self._call(HEAD.bwd_entry, self._hb, self.n)                                               # gx += head's part; head parameter gradients
 
     def step(self):
         self.forward()

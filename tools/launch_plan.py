@@ -36,7 +36,7 @@ def run(tree, out, sanitize=False, resource_log=None, objdir=None):
             if os.path.exists(obj):
                 return obj
             extra = [f for s in SAN for f in ("-Xarch_host", s)] if sanitize else []
-            subprocess.run([hipcc] + B.BASE_FLAGS + extra + ["-c", os.path.join(B.CSRC, src), "-o", obj], check=True)
+            subprocess.run([hipcc] + B.BASE_FLAGS + B.UNIT_FLAGS.get(src, []) + extra + ["-c", os.path.join(B.CSRC, src), "-o", obj], check=True)
             return obj
         with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
             objs = list(ex.map(unit, B.sources()))
