@@ -208,13 +208,13 @@ static int backward_group_nhwc(BwdArgs* lv, int n, const BwdSig& sig, int stages
   if (stages & MGACBAM_BWD_REDUCE1) {  // 1. chunk partials of A and D, g_pre
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_bwd_reduce1_nhwc<elem_t<decltype(t)>, v.value>; });
     if (int e = launch_group("k_bwd_reduce1_nhwc", kernel, G, chunks,
-                             [&](const BwdArgs& a) { return nhwc_reduce1_smem(a.g, sig.vec); }, st)) return e;
+                             [&](const BwdArgs& a) { return lds_bytes(Reduce1NhwcLds(a.g, sig.vec)); }, st)) return e;
   }
   if (stages & MGACBAM_BWD_CONVT)  // 2. transposed conv
     if (int e = launch_convT(G, sig.k, st)) return e;
   if (stages & MGACBAM_BWD_REDUCE2) {  // 3. chunk partials of the g_planes term, then their fold: g_z, D, hidden-gradient partials
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_bwd_reduce2_nhwc<elem_t<decltype(t)>, v.value>; });
-    if (int e = launch_group("k_bwd_reduce2_nhwc", kernel, G, chunks, [](const BwdArgs& a) { return nhwc_reduce2_smem(a.g); }, st)) return e;
+    if (int e = launch_group("k_bwd_reduce2_nhwc", kernel, G, chunks, [](const BwdArgs& a) { return lds_bytes(Reduce2NhwcLds(a.g)); }, st)) return e;
     if (int e = launch_group("k_bwd_fold_nhwc", k_bwd_fold_nhwc, G, [](const BwdArgs& a) { return a.g.B * a.ncb; }, 0, st)) return e;
   }
   if (stages & MGACBAM_BWD_WSA)  // 4. dWsa tile partials
@@ -225,7 +225,7 @@ static int backward_group_nhwc(BwdArgs* lv, int n, const BwdSig& sig, int stages
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_bool(sig.gmask, [&](auto gm) { return k_bwd_apply_nhwc<elem_t<decltype(t)>, v.value, gm.value>; }); });
     if (int e = launch_group("k_bwd_apply_nhwc", kernel, G, [](const BwdArgs& a) { return xcd_grid(a.g.B, a.n.ntile); },
-                             [](const BwdArgs& a) { return nhwc_bwd_apply_smem(a.g); }, st)) return e;
+                             [](const BwdArgs& a) { return lds_bytes(BwdApplyNhwcLds(a.g)); }, st)) return e;
   }
   return 0;
 }

@@ -144,11 +144,6 @@ static int eca_level(const char* what, const Level& L, Args& A, EcaSig& sig) {
   return 0;
 }
 
-static size_t eca_apply_nhwc_smem(const Geo& g) { return static_cast<size_t>(g.C) * sizeof(float); }
-static size_t eca_bwd_nhwc_smem(const Geo& g) {
-  return (((static_cast<size_t>(g.C) + 1) & ~static_cast<size_t>(1)) + 2 * static_cast<size_t>(g.C)) * sizeof(float);
-}
-
 static int eca_forward_group_nhwc(EcaFwdArgs* lv, int n, const EcaSig& sig, hipStream_t st);
 static int eca_forward_group(EcaFwdArgs* lv, int n, const EcaSig& sig, hipStream_t st) {
   if (sig.nhwc) return eca_forward_group_nhwc(lv, n, sig, st);
@@ -174,7 +169,7 @@ static int eca_forward_group_nhwc(EcaFwdArgs* lv, int n, const EcaSig& sig, hipS
   if (int e = launch_group("k_eca_fin", fin, G, [](const EcaFwdArgs& a) { return nhwc_fold_blocks(a.g); }, 0, st)) return e;
   auto apply = with_elem_vec8(sig.dtype, sig.vec, [](auto t, auto v) { return k_eca_apply_nhwc<elem_t<decltype(t)>, v.value>; });
   return launch_group("k_eca_apply_nhwc", apply, G, [](const EcaFwdArgs& a) { return xcd_grid(a.g.B, a.n.ntile); },
-                      [](const EcaFwdArgs& a) { return eca_apply_nhwc_smem(a.g); }, st);
+                      [](const EcaFwdArgs& a) { return lds_bytes(EcaApplyNhwcLds(a.g)); }, st);
 }
 
 extern "C" int mgacbam_eca_forward(const mgacbam_eca_fwd_level_t* levels, int n_levels, void* stream) {
@@ -208,7 +203,7 @@ static int eca_backward_group_nhwc(EcaBwdArgs* lv, int n, const EcaSig& sig, hip
   auto bwd = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
     return with_bool(sig.gmask, [&](auto gm) { return k_eca_bwd_nhwc<elem_t<decltype(t)>, v.value, gm.value>; }); });
   return launch_group("k_eca_bwd_nhwc", bwd, G, [](const EcaBwdArgs& a) { return kEcaRoles + xcd_grid(a.g.B, a.n.ntile); },
-                      [](const EcaBwdArgs& a) { return eca_bwd_nhwc_smem(a.g); }, st);
+                      [](const EcaBwdArgs& a) { return lds_bytes(EcaBwdNhwcLds(a.g)); }, st);
 }
 
 extern "C" int mgacbam_eca_backward(const mgacbam_eca_bwd_level_t* levels, int n_levels, void* stream) {

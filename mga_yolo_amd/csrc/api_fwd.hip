@@ -141,7 +141,7 @@ static int forward_group_nhwc(FwdArgs* lv, int n, const FwdSig& sig, int stages,
     auto pool = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_bool(sig.has_mask, [&](auto m) { return k_pool_nhwc<elem_t<decltype(t)>, v.value, m.value>; }); });
     if (int e = launch_group("k_pool_nhwc", pool, G, [](const FwdArgs& a) { return xcd_grid(a.g.B, a.n.nchunk); },
-                             [](const FwdArgs& a) { return nhwc_pool_smem(a.g); }, st)) return e;
+                             [](const FwdArgs& a) { return lds_bytes(PoolNhwcLds(a.g)); }, st)) return e;
     auto fin = with_bool(sig.has_mask, [](auto m) { return k_pool_fin<m.value>; });
     if (int e = launch_group("k_pool_fin", fin, G, [](const FwdArgs& a) { return nhwc_fold_blocks(a.g); }, 0, st)) return e;
     if (int e = launch_mlp(G, st)) return e;
@@ -150,12 +150,12 @@ static int forward_group_nhwc(FwdArgs* lv, int n, const FwdSig& sig, int stages,
   if (stages & MGACBAM_FWD_CHAN) {  // 3. channel max / mean planes
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_bool(sig.has_mask, [&](auto m) { return k_chan_nhwc<elem_t<decltype(t)>, v.value, m.value>; }); });
-    if (int e = launch_group("k_chan_nhwc", kernel, G, tiles, [](const FwdArgs& a) { return nhwc_chan_smem(a.g); }, st)) return e;
+    if (int e = launch_group("k_chan_nhwc", kernel, G, tiles, [](const FwdArgs& a) { return lds_bytes(ChanNhwcLds(a.g)); }, st)) return e;
   }
   if (stages & MGACBAM_FWD_APPLY) {  // 4. k x k conv + spatial gate (prologue), y
     auto kernel = with_elem_vec8(sig.dtype, sig.vec, [&](auto t, auto v) {
       return with_k(sig.k, [&](auto k) { return k_apply_nhwc<elem_t<decltype(t)>, v.value, k.value>; }); });
-    if (int e = launch_group("k_apply_nhwc", kernel, G, tiles, [](const FwdArgs& a) { return nhwc_apply_smem(a.g, a.t, a.n); }, st)) return e;
+    if (int e = launch_group("k_apply_nhwc", kernel, G, tiles, [](const FwdArgs& a) { return lds_bytes(ApplyNhwcLds(a.g, a.t, a.n, a.g.k)); }, st)) return e;
   }
   return 0;
 }

@@ -40,6 +40,25 @@ struct EcaBwdArgs {
 };
 static_assert(sizeof(Group<EcaFwdArgs>) <= kKernargMax && sizeof(Group<EcaBwdArgs>) <= kKernargMax, "a group is one launch's arguments");
 
+// pooled statistics of (b, c) from its sums over H*W (S = sum s of the sample, sx = sum x, sxs = sum x*s): the masked average with
+// the GAP fallback; channel 0's thread also writes the sample's S / use / den.  Shared by k_eca_pool and k_eca_fin (eca_nhwc.cuh).
+template <bool HAS_MASK>
+__device__ __forceinline__ void eca_pooled_stats(const EcaCtx& ctx, const Geo& g, int b, int c, float S, float sx, float sxs) {
+  const float N = static_cast<float>(g.HW);
+  const float use = (S / N >= g.thr) ? 1.f : 0.f;              // masked_eca.py:152-153, 159
+  const float den = fmaxf(S, g.eps);                           // :156, 164
+  const size_t o = static_cast<size_t>(b) * g.C + c;
+  const float gap = sx / N;
+  const float mavg = HAS_MASK ? sxs / den : gap;               // :157, 165
+  ctx.mavg[o] = mavg;
+  ctx.avg[o] = HAS_MASK ? mavg * use + gap * (1.f - use) : gap;   // :161
+  if (c == 0) {
+    ctx.S[b] = HAS_MASK ? S : 0.f;
+    ctx.use[b] = HAS_MASK ? use : 0.f;
+    ctx.den[b] = HAS_MASK ? den : 1.f;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_eca_pool: masked average pooling with GAP fallback                             masked_eca.py:139-165
 // ---------------------------------------------------------------------------------------------
@@ -96,26 +115,9 @@ __global__ __launch_bounds__(kBlock) void k_eca_pool(const Group<EcaFwdArgs> G) 
   sums[2 * CPT] = ssum;
   row_sum<2 * CPT + 1>(sums, TX, tid, red);
   if (tx == 0) {
-    const float N = static_cast<float>(g.HW);
-    const float S = sums[2 * CPT];
-    const float use = (S / N >= g.thr) ? 1.f : 0.f;            // masked_eca.py:152-153, 159
-    const float den = fmaxf(S, g.eps);                         // :156, 164
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-      const int c = c0 + j;
-      if (c < g.C) {
-        const size_t o = static_cast<size_t>(b) * g.C + c;
-        const float gap = sums[j] / N;
-        const float mavg = HAS_MASK ? sums[CPT + j] / den : gap;                 // :157, 165
-        A.c.mavg[o] = mavg;
-        A.c.avg[o] = HAS_MASK ? mavg * use + gap * (1.f - use) : gap;            // :161
-      }
-    }
-    if (cg == 0 && ty == 0) {
-      A.c.S[b] = HAS_MASK ? S : 0.f;
-      A.c.use[b] = HAS_MASK ? use : 0.f;
-      A.c.den[b] = HAS_MASK ? den : 1.f;
-    }
+    for (int j = 0; j < CPT; ++j)
+      if (c0 + j < g.C) eca_pooled_stats<HAS_MASK>(A.c, g, b, c0 + j, sums[2 * CPT], sums[j], sums[CPT + j]);
   }
 }
 
@@ -253,9 +255,44 @@ __device__ __forceinline__ void eca_params_body(const EcaBwdArgs& A, const int r
   if (tid == 0) { if (r == kEcaRoles - 1) *A.gbeta = sigmoidf_(*A.beta) * acc; else A.gw[r] = acc; }
 }
 
+// The per-sample prologue of the backward's streaming workgroups, layout-free (k_eca_bwd, k_eca_bwd_nhwc): gy1 = a*gg*w(1-w) -> s_gy1[C];
+// g_avg = conv1d^T(gy1); s_q[c] = {g, g_avg}; returns K_b = sum_c g_avg*mavg (0 without a mask or when den was clamped) to every thread.
+// red: the kernel's kEcaBwdRed static floats.  Its barriers publish s_q.
+__device__ __forceinline__ float eca_bwd_prologue(const EcaBwdArgs& A, int b, float a, float* s_gy1, float2* s_q, float* red) {
+  const Geo& g = A.g;
+  const int tid = threadIdx.x, k = g.k, pad = k / 2;
+  for (int c = tid; c < g.C; c += kBlock) {
+    const size_t o = static_cast<size_t>(b) * g.C + c;
+    const float w = A.c.w[o];
+    s_gy1[c] = a * A.s.gg[o] * w * (1.f - w);
+  }
+  __syncthreads();
+  const float live = (A.mask != nullptr && A.c.S[b] >= g.eps) ? 1.f : 0.f;   // clamp_min passes grad only when not clamped
+  float kpart = 0.f;
+  for (int c = tid; c < g.C; c += kBlock) {
+    float ga = 0.f;
+    for (int t = 0; t < k; ++t) {                              // conv1d backward w.r.t. its input
+      const int cc = c - t + pad;
+      if (cc >= 0 && cc < g.C) ga += A.w1d[t] * s_gy1[cc];
+    }
+    const size_t o = static_cast<size_t>(b) * g.C + c;
+    s_q[c] = make_float2(1.f + a * (A.c.w[o] - 0.5f), ga);
+    kpart += ga * A.c.mavg[o] * live;
+  }
+  kpart = block_sum(kpart, tid, red);
+  if (tid == 0) red[kEcaBwdRed - 1] = kpart;
+  __syncthreads();
+  return red[kEcaBwdRed - 1];
+}
+// dL/dmask of a pixel from dot = sum_c g_avg*x over its channels and its s = sigma(mask)
+__device__ __forceinline__ float eca_gmask(const Geo& g, float use, float den, float dot, float kb, float s) {
+  const float gs = (use / den) * (dot - kb);
+  return g.use_sigmoid ? gs * s * (1.f - s) : gs;
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_eca_bwd: gx = gy*g + g_avg*wA ; gmask = (use/den) * (sum_c g_avg*x - K_b) * s(1-s)          (tile layout of k_bwd_apply)
-//   prologue per workgroup (its sample): gy1 = a*gg*w(1-w) -> LDS; g_avg = conv1d^T(gy1) ; q[c] = {g, g_avg} ; K_b
+//   prologue per workgroup (its sample): eca_bwd_prologue
 //   the level's first 16 workgroups are the parameter-gradient roles (dW1d taps, dbeta)
 //   LDS: [C gy1][2C q][256*VEC combine]
 // ---------------------------------------------------------------------------------------------
@@ -286,7 +323,6 @@ __global__ __launch_bounds__(kBlock) void k_eca_bwd(const Group<EcaBwdArgs> G) {
   const float a = softplusf_(*A.beta);
   const float N = static_cast<float>(g.HW);
   const bool has_mask = A.mask != nullptr;
-  const int k = g.k, pad = k / 2;
 
   constexpr int UN = 2;                                        // first feature vectors are requested before the prologue
   float g0v[UN][VEC], x0v[UN][VEC];
@@ -299,28 +335,7 @@ __global__ __launch_bounds__(kBlock) void k_eca_bwd(const Group<EcaBwdArgs> G) {
   float* s_gy1 = smem;
   float2* s_q = reinterpret_cast<float2*>(smem + g.C);
   float* sm = smem + 3 * g.C;
-  for (int c = tid; c < g.C; c += kBlock) {
-    const size_t o = static_cast<size_t>(b) * g.C + c;
-    const float w = A.c.w[o];
-    s_gy1[c] = a * A.s.gg[o] * w * (1.f - w);
-  }
-  __syncthreads();
-  const float live = (has_mask && A.c.S[b] >= g.eps) ? 1.f : 0.f;
-  float kpart = 0.f;
-  for (int c = tid; c < g.C; c += kBlock) {
-    float ga = 0.f;
-    for (int t = 0; t < k; ++t) {                              // conv1d backward w.r.t. its input
-      const int cc = c - t + pad;
-      if (cc >= 0 && cc < g.C) ga += A.w1d[t] * s_gy1[cc];
-    }
-    const size_t o = static_cast<size_t>(b) * g.C + c;
-    s_q[c] = make_float2(1.f + a * (A.c.w[o] - 0.5f), ga);
-    kpart += ga * A.c.mavg[o] * live;
-  }
-  kpart = block_sum(kpart, tid, red);
-  if (tid == 0) red[7] = kpart;
-  __syncthreads();
-  const float kb = red[7];
+  const float kb = eca_bwd_prologue(A, b, a, s_gy1, s_q, red);
 
   float sv[VEC], wA[VEC], accp[VEC];
   load_vec<float, VEC>(A.c.splane + static_cast<size_t>(b) * g.HW + static_cast<size_t>(ii) * VEC, sv);
@@ -359,10 +374,7 @@ __global__ __launch_bounds__(kBlock) void k_eca_bwd(const Group<EcaBwdArgs> G) {
         for (int e = 0; e < VEC; ++e) accp[e] += sm[(r * TX + tx) * VEC + e];
       float gm[VEC];
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        const float gs = (use / den) * (accp[e] - kb);
-        gm[e] = g.use_sigmoid ? gs * sv[e] * (1.f - sv[e]) : gs;
-      }
+      for (int e = 0; e < VEC; ++e) gm[e] = eca_gmask(g, use, den, accp[e], kb, sv[e]);
       store_vec<float, VEC>(A.gmask + static_cast<size_t>(b) * g.HW + static_cast<size_t>(i) * VEC, gm);
     }
   }

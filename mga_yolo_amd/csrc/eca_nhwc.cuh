@@ -1,6 +1,5 @@
-// Channels-last (MGACBAM_LAYOUT_NHWC) forms of the MaskECA kernels: the thread layout of nhwc.cuh (a workgroup owns a TILE of CH
-// consecutive pixels of one sample, CS lanes split a pixel's channels VEC at a time, per-pixel sums are wave shuffles, per-channel sums
-// go through LDS in row order), the algebra of eca.cuh.
+// Channels-last (MGACBAM_LAYOUT_NHWC) forms of the MaskECA kernels: the thread layout of nhwc.cuh (NhwcPos, NhwcPix, NhwcGroup, the
+// folds), the algebra of eca.cuh (eca_pooled_stats, eca_gate_w, eca_bwd_prologue, eca_gmask, eca_params_body).
 //
 //   forward   k_eca_pool_nhwc    x (1 read)        -> per-chunk partials of sum x*s and sum x per channel, sum s ; sigma(mask) plane
 //             k_eca_fin          partials          -> S/use/den, mavg, avg (fixed-order fold, as k_pool_fin)
@@ -21,28 +20,9 @@ namespace mgacbam {
 
 __host__ __device__ inline size_t eca_nhwc_part_stride(int C) { return 2 * static_cast<size_t>(C) + 4; }
 
-// rows of one pass -> channel sums: thread t < CS*VEC owns channel j*CS*VEC + t and adds the PR rows in row order
-template <int N, int VEC>
-__device__ __forceinline__ void eca_rows_to_channels(float (&acc)[N][VEC], float* red, int tid, int j, int CS, int PR, int C, float* out,
-                                                     size_t out_stride) {
-  nhwc_rows_sum<N, VEC>(acc, red, tid);
-  const int CV = CS * VEC;
-  for (int t = tid; t < CV; t += kBlock) {                                // (CV = 512 with 8-element lanes)
-    const int c = j * CV + t;
-    if (c < C) {
-#pragma unroll
-      for (int q = 0; q < N; ++q) {
-        float s = 0.f;
-        for (int r = 0; r < PR; ++r) s += red[q * kBlock * VEC + r * CV + t];
-        out[q * out_stride + c] = s;
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // k_eca_pool_nhwc: workgroup = (sample, chunk of rp tiles).  The workgroup owns its pixels' sigma(mask) and their sum.
-//   LDS: [2 x 256*VEC row sums]
+//   static LDS: red = NS x 256*VEC row sums of a pass
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC, bool HAS_MASK>
 __global__ __launch_bounds__(kBlock) void k_eca_pool_nhwc(const Group<EcaFwdArgs> G) {
@@ -54,67 +34,62 @@ __global__ __launch_bounds__(kBlock) void k_eca_pool_nhwc(const Group<EcaFwdArgs
   const Geo& g = A.g;
   int b, chunk;
   if (!xcd_sample_part(local, g.B, A.n.nchunk, b, chunk)) return;
-  constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
+  constexpr int NPX = NhwcNpx<VEC>::value;
+  const NhwcPos t = nhwc_pos<VEC>(A.n);
   const T* xb = static_cast<const T*>(A.x) + static_cast<size_t>(b) * g.HW * g.C;
   const float* mb = HAS_MASK ? A.mask + static_cast<size_t>(b) * g.HW : nullptr;
   float* splane = A.c.splane + static_cast<size_t>(b) * g.HW;
   float* part = A.part + (static_cast<size_t>(b) * A.n.nchunk + chunk) * eca_nhwc_part_stride(g.C);
-  const int nj = (A.n.ng + CS - 1) / CS;
   const int t0 = chunk * A.n.rp, t_end = min(t0 + A.n.rp, A.n.ntile);
   float ssum = 0.f;
-  for (int j = 0; j < nj; ++j) {
-    const int cgi = lane + j * CS;
-    const bool okc = cgi < A.n.ng;
-    const int c0 = min(cgi, A.n.ng - 1) * VEC;
+  for (int j = 0; j < t.nj; ++j) {
+    const NhwcGroup cg = nhwc_group_clamped<VEC>(t, A.n, j);
     float acc[NS][VEC];
 #pragma unroll
     for (int q = 0; q < NS; ++q)
 #pragma unroll
       for (int e = 0; e < VEC; ++e) acc[q][e] = 0.f;
     for (int tile = t0; tile < t_end; ++tile) {
-      const int p0 = tile * A.n.ch;
-      float s[kNhwcNpx];
-      bool live[kNhwcNpx];
-      float xv[kNhwcNpx][VEC];
+      const NhwcPix<NPX> P = nhwc_pixels<NPX>(t, tile * A.n.ch, g.HW);
+      float s[NPX];
+      float xv[NPX][VEC];
 #pragma unroll
-      for (int k = 0; k < kNhwcNpx; ++k) {
-        const int p = p0 + k * PR + row;
-        const bool okp = p < g.HW;
-        live[k] = okp && okc;
-        load_vec<T, VEC>(xb + static_cast<size_t>(okp ? p : 0) * g.C + c0, xv[k]);
+      for (int k = 0; k < NPX; ++k) {
+        load_vec<T, VEC>(xb + static_cast<size_t>(P.pix[k]) * g.C + cg.c0, xv[k]);
         s[k] = 0.f;
-        if (HAS_MASK && okp) {
-          const float m = mb[p];
+        if (HAS_MASK && P.ok[k]) {
+          const float m = mb[P.pix[k]];
           s[k] = g.use_sigmoid ? sigmoid_fast(m) : m;                     // masked_eca.py:146-147
         }
-        if (j == 0 && okp) {
+        if (j == 0 && P.ok[k]) {
           ssum += s[k];
-          if (lane == 0) splane[p] = s[k];                                // (zeros when there is no mask)
+          if (t.lane == 0) splane[P.live(k)] = s[k];                       // (zeros when there is no mask)
         }
       }
 #pragma unroll
-      for (int k = 0; k < kNhwcNpx; ++k)
+      for (int k = 0; k < NPX; ++k)
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-          const float v = live[k] ? xv[k][e] : 0.f;
+          const float v = (P.ok[k] && cg.okc) ? xv[k][e] : 0.f;
           acc[0][e] += v;
           if (HAS_MASK) acc[NS - 1][e] += v * s[k];
         }
     }
     // without a mask only sum x is formed (k_eca_fin reads nothing else)
-    eca_rows_to_channels<NS, VEC>(acc, red, tid, j, CS, PR, g.C, part, g.C);
+    nhwc_rows_to_channels<NS, VEC>(acc, red, t, j, g.C, [&](int c, const float (&sum)[NS]) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) part[static_cast<size_t>(q) * g.C + c] = sum[q];
+    });
   }
-  // sum of s over the chunk: rows in order (every lane of a row holds the row's sum)
+  // sum of s over the chunk (every lane of a row holds the row's sum)
   __syncthreads();
-  if (lane == 0) red[row] = ssum;
-  __syncthreads();
-  if (tid == 0) { float t = 0.f; for (int r = 0; r < PR; ++r) t += red[r]; part[2 * g.C] = t; }
+  const float S = nhwc_chunk_row_total(ssum, red, t);
+  if (t.tid == 0) part[2 * g.C] = S;
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_eca_fin: workgroup = (sample, block of kNhwcFoldC channels); its 4 waves fold the chunk partials of a channel with a stride of 4
-// chunks, the 4 results are added in wave order.  Writes the statistics exactly as k_eca_pool defines them.
+// k_eca_fin: workgroup = (sample, block of kNhwcFoldC channels): nhwc_chunk_fold over the chunk partials, then the statistics
+// exactly as k_eca_pool defines them (eca_pooled_stats).
 // ---------------------------------------------------------------------------------------------
 template <bool HAS_MASK>
 __global__ __launch_bounds__(kBlock) void k_eca_fin(const Group<EcaFwdArgs> G) {
@@ -135,36 +110,24 @@ __global__ __launch_bounds__(kBlock) void k_eca_fin(const Group<EcaFwdArgs> G) {
   }
   const int c = cb * kNhwcFoldC + lane;
   const int cc = min(c, g.C - 1);
-  float sxs = 0.f, sx = 0.f;
-#pragma unroll 4
-  for (int q = grp; q < nch; q += 4) {
+  float sum[2];                                                           // [sum x*s][sum x]
+  nhwc_chunk_fold<2>(sum, s_part, nch, [&](int q, float (&s)[2]) {
     const float* pq = wb + q * stride;
-    sx += pq[cc];
-    if (HAS_MASK) sxs += pq[g.C + cc];
-  }
-  s_part[0][tid] = sxs; s_part[1][tid] = sx;
-  __syncthreads();
+    s[1] += pq[cc];
+    if (HAS_MASK) s[0] += pq[g.C + cc];
+  });
   if (grp != 0 || c >= g.C) return;
-  for (int r = 1; r < 4; ++r) { sxs += s_part[0][r * 64 + lane]; sx += s_part[1][r * 64 + lane]; }
-  const float Nf = static_cast<float>(g.HW);
-  const float use = (S / Nf >= g.thr) ? 1.f : 0.f;                        // masked_eca.py:152-153, 159
-  const float den = fmaxf(S, g.eps);                                      // :156, 164
-  const size_t o = static_cast<size_t>(b) * g.C + c;
-  const float gap = sx / Nf;
-  const float mavg = HAS_MASK ? sxs / den : gap;                          // :157, 165
-  A.c.mavg[o] = mavg;
-  A.c.avg[o] = HAS_MASK ? mavg * use + gap * (1.f - use) : gap;           // :161
-  if (cb == 0 && lane == 0) {
-    A.c.S[b] = HAS_MASK ? S : 0.f;
-    A.c.use[b] = HAS_MASK ? use : 0.f;
-    A.c.den[b] = HAS_MASK ? den : 1.f;
-  }
+  eca_pooled_stats<HAS_MASK>(A.c, g, b, c, S, sum[1], sum[0]);
 }
 
 // ---------------------------------------------------------------------------------------------
 // k_eca_apply_nhwc: workgroup = (sample, tile).  Prologue: the sample's C gates into LDS (tile 0 also saves w); body: y = x * gate[c]
-//   LDS: [C gate]
 // ---------------------------------------------------------------------------------------------
+struct EcaApplyNhwcLds {
+  size_t gate;                 // [C] 1 + a*(w - 0.5)
+  size_t total;
+  __host__ __device__ explicit EcaApplyNhwcLds(const Geo& g) : gate(0), total(g.C) {}
+};
 template <typename T, int VEC>
 __global__ __launch_bounds__(kBlock) void k_eca_apply_nhwc(const Group<EcaFwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
@@ -174,52 +137,42 @@ __global__ __launch_bounds__(kBlock) void k_eca_apply_nhwc(const Group<EcaFwdArg
   const Geo& g = A.g;
   int b, tile;
   if (!xcd_sample_part(local, g.B, A.n.ntile, b, tile)) return;
-  constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
-  const int p0 = tile * A.n.ch;
+  constexpr int NPX = NhwcNpx<VEC>::value;
+  const NhwcPos t = nhwc_pos<VEC>(A.n);
   const size_t sb = static_cast<size_t>(b) * g.HW * g.C;
   const T* xb = static_cast<const T*>(A.x) + sb;
   T* yb = static_cast<T*>(A.y) + sb;
   const float a = softplusf_(*A.beta);
-  float* s_gate = smem;
-  for (int c = tid; c < g.C; c += kBlock) {
+  float* s_gate = smem + EcaApplyNhwcLds(g).gate;
+  for (int c = t.tid; c < g.C; c += kBlock) {
     const float w = eca_gate_w(A.c.avg + static_cast<size_t>(b) * g.C, A.w1d, g.k, g.C, c);
     s_gate[c] = 1.f + a * (w - 0.5f);                                     // masked_eca.py:190
     if (tile == 0) A.c.w[static_cast<size_t>(b) * g.C + c] = w;
   }
   __syncthreads();
-  int pix[kNhwcNpx];
-  bool okp[kNhwcNpx];
-#pragma unroll
-  for (int k = 0; k < kNhwcNpx; ++k) {
-    const int p = p0 + k * PR + row;
-    okp[k] = p < g.HW;
-    pix[k] = okp[k] ? p : 0;
-  }
-  const int nj = (A.n.ng + CS - 1) / CS;
-  for (int j = 0; j < nj; ++j) {
-    const int cgi = lane + j * CS;
-    if (cgi >= A.n.ng) break;
-    const int c0 = cgi * VEC;
+  const NhwcPix<NPX> P = nhwc_pixels<NPX>(t, tile * A.n.ch, g.HW);
+  for (int j = 0; j < t.nj; ++j) {
+    NhwcGroup cg;
+    if (!nhwc_group_live<VEC>(t, A.n, j, cg)) break;
     float gv[VEC];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) gv[e] = s_gate[min(c0 + e, g.C - 1)];
-    float xv[kNhwcNpx][VEC];
+    for (int e = 0; e < VEC; ++e) gv[e] = s_gate[min(cg.c0 + e, g.C - 1)];
+    float xv[NPX][VEC];
 #pragma unroll
-    for (int k = 0; k < kNhwcNpx; ++k) load_vec<T, VEC>(xb + static_cast<size_t>(pix[k]) * g.C + c0, xv[k]);
+    for (int k = 0; k < NPX; ++k) load_vec<T, VEC>(xb + static_cast<size_t>(P.pix[k]) * g.C + cg.c0, xv[k]);
 #pragma unroll
-    for (int k = 0; k < kNhwcNpx; ++k) {
+    for (int k = 0; k < NPX; ++k) {
       float yv[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) yv[e] = xv[k][e] * gv[e];
-      if (okp[k]) store_vec<T, VEC>(yb + static_cast<size_t>(pix[k]) * g.C + c0, yv);
+      if (P.ok[k]) store_vec<T, VEC>(yb + static_cast<size_t>(P.pix[k]) * g.C + cg.c0, yv);
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------
 // k_eca_reduce_nhwc: per-chunk partials of gg[b,c] = sum_hw gy*x   (chunks as k_eca_pool_nhwc)
-//   LDS: [256*VEC row sums]
+//   static LDS: red = 256*VEC row sums of a pass
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC>
 __global__ __launch_bounds__(kBlock) void k_eca_reduce_nhwc(const Group<EcaBwdArgs> G) {
@@ -230,45 +183,38 @@ __global__ __launch_bounds__(kBlock) void k_eca_reduce_nhwc(const Group<EcaBwdAr
   const Geo& g = A.g;
   int b, chunk;
   if (!xcd_sample_part(local, g.B, A.n.nchunk, b, chunk)) return;
-  constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
+  constexpr int NPX = NhwcNpx<VEC>::value;
+  const NhwcPos t = nhwc_pos<VEC>(A.n);
   const size_t sb = static_cast<size_t>(b) * g.HW * g.C;
   const T* xb = static_cast<const T*>(A.x) + sb;
   const T* gb = static_cast<const T*>(A.gy) + sb;
   float* part = A.part + (static_cast<size_t>(b) * A.n.nchunk + chunk) * g.C;
-  const int nj = (A.n.ng + CS - 1) / CS;
   const int t0 = chunk * A.n.rp, t_end = min(t0 + A.n.rp, A.n.ntile);
-  for (int j = 0; j < nj; ++j) {
-    const int cgi = lane + j * CS;
-    const bool okc = cgi < A.n.ng;
-    const int c0 = min(cgi, A.n.ng - 1) * VEC;
+  for (int j = 0; j < t.nj; ++j) {
+    const NhwcGroup cg = nhwc_group_clamped<VEC>(t, A.n, j);
     float acc[1][VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[0][e] = 0.f;
     for (int tile = t0; tile < t_end; ++tile) {
-      const int p0 = tile * A.n.ch;
-      float xv[kNhwcNpx][VEC], gv[kNhwcNpx][VEC];
-      bool live[kNhwcNpx];
+      const NhwcPix<NPX> P = nhwc_pixels<NPX>(t, tile * A.n.ch, g.HW);
+      float xv[NPX][VEC], gv[NPX][VEC];
 #pragma unroll
-      for (int k = 0; k < kNhwcNpx; ++k) {
-        const int p = p0 + k * PR + row;
-        const bool okp = p < g.HW;
-        live[k] = okp && okc;
-        const size_t o = static_cast<size_t>(okp ? p : 0) * g.C + c0;
+      for (int k = 0; k < NPX; ++k) {
+        const size_t o = static_cast<size_t>(P.pix[k]) * g.C + cg.c0;
         load_vec<T, VEC>(xb + o, xv[k]);
         load_vec<T, VEC>(gb + o, gv[k]);
       }
 #pragma unroll
-      for (int k = 0; k < kNhwcNpx; ++k)
+      for (int k = 0; k < NPX; ++k)
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) acc[0][e] += live[k] ? xv[k][e] * gv[k][e] : 0.f;
+        for (int e = 0; e < VEC; ++e) acc[0][e] += (P.ok[k] && cg.okc) ? xv[k][e] * gv[k][e] : 0.f;
     }
-    eca_rows_to_channels<1, VEC>(acc, red, tid, j, CS, PR, g.C, part, 0);
+    nhwc_rows_to_channels<1, VEC>(acc, red, t, j, g.C, [&](int c, const float (&sum)[1]) { part[c] = sum[0]; });
   }
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_eca_fold: workgroup = (sample, block of kNhwcFoldC channels): gg[b,c] = chunk partials folded as k_eca_fin folds its own
+// k_eca_fold: workgroup = (sample, block of kNhwcFoldC channels): gg[b,c] = nhwc_chunk_fold over its chunk partials
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_eca_fold(const Group<EcaBwdArgs> G) {
   __shared__ float s_part[kBlock];
@@ -281,26 +227,28 @@ __global__ __launch_bounds__(kBlock) void k_eca_fold(const Group<EcaBwdArgs> G) 
   const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6;
   const int c = cb * kNhwcFoldC + lane, cc = min(c, g.C - 1);
   const float* pb = A.part + static_cast<size_t>(b) * A.n.nchunk * g.C + cc;
-  float s = 0.f;
-#pragma unroll 4
-  for (int q = grp; q < A.n.nchunk; q += 4) s += pb[static_cast<size_t>(q) * g.C];
-  s_part[tid] = s;
-  __syncthreads();
+  float sum[1];
+  nhwc_chunk_fold<1>(sum, &s_part, A.n.nchunk, [&](int q, float (&s)[1]) { s[0] += pb[static_cast<size_t>(q) * g.C]; });
   if (grp != 0 || c >= g.C) return;
-  for (int r = 1; r < 4; ++r) s += s_part[r * 64 + lane];
-  A.s.gg[static_cast<size_t>(b) * g.C + c] = s;
+  A.s.gg[static_cast<size_t>(b) * g.C + c] = sum[0];
 }
 
 // ---------------------------------------------------------------------------------------------
 // k_eca_bwd_nhwc: gx = gy*g + g_avg*wA ; gmask = (use/den) * (sum_c g_avg*x - K_b) * s(1-s)      (eca.cuh k_eca_bwd, NHWC)
-//   prologue per workgroup (its sample): gy1 = a*gg*w(1-w) -> LDS; g_avg = conv1d^T(gy1) ; q[c] = {g, g_avg} ; K_b
+//   prologue per workgroup (its sample): eca_bwd_prologue
 //   the level's first 16 workgroups are the parameter-gradient roles (eca_params_body: layout-free)
-//   LDS: [C gy1][2C q]
 // ---------------------------------------------------------------------------------------------
+struct EcaBwdNhwcLds {
+  size_t gy1;                  // [C] a*gg*w(1-w), padded to 2 floats: q is float2, keep it 8-byte aligned
+  size_t q;                    // [C] float2 {g, g_avg}
+  size_t total;
+  __host__ __device__ explicit EcaBwdNhwcLds(const Geo& g)
+      : gy1(0), q(gy1 + ((static_cast<size_t>(g.C) + 1) & ~static_cast<size_t>(1))), total(q + 2 * static_cast<size_t>(g.C)) {}
+};
 template <typename T, int VEC, bool GMASK>
 __global__ __launch_bounds__(kBlock) void k_eca_bwd_nhwc(const Group<EcaBwdArgs> G) {
   extern __shared__ __align__(16) float smem[];
-  __shared__ float red[8];
+  __shared__ float red[kEcaBwdRed];
   int local;
   const int l = find_level(G, blockIdx.x, local);
   const EcaBwdArgs& A = G.lv[l];
@@ -309,90 +257,57 @@ __global__ __launch_bounds__(kBlock) void k_eca_bwd_nhwc(const Group<EcaBwdArgs>
   const Geo& g = A.g;
   int b, tile;
   if (!xcd_sample_part(local, g.B, A.n.ntile, b, tile)) return;
-  constexpr int kNhwcNpx = NhwcNpx<VEC>::value;
-  const int tid = threadIdx.x, CS = A.n.cs, lane = tid & (CS - 1), row = tid >> A.n.lcs, PR = kBlock >> A.n.lcs;
-  const int p0 = tile * A.n.ch;
+  constexpr int NPX = NhwcNpx<VEC>::value;
+  const NhwcPos t = nhwc_pos<VEC>(A.n);
   const float a = softplusf_(*A.beta);
   const float Nf = static_cast<float>(g.HW);
   const bool has_mask = A.mask != nullptr;
-  const int k = g.k, pad = k / 2;
-  const int C2 = (g.C + 1) & ~1;                                         // q is float2: keep it 8-byte aligned
-  float* s_gy1 = smem;
-  float2* s_q = reinterpret_cast<float2*>(smem + C2);
-  for (int c = tid; c < g.C; c += kBlock) {
-    const size_t o = static_cast<size_t>(b) * g.C + c;
-    const float w = A.c.w[o];
-    s_gy1[c] = a * A.s.gg[o] * w * (1.f - w);
-  }
-  __syncthreads();
-  const float live = (has_mask && A.c.S[b] >= g.eps) ? 1.f : 0.f;
-  float kpart = 0.f;
-  for (int c = tid; c < g.C; c += kBlock) {
-    float ga = 0.f;
-    for (int t = 0; t < k; ++t) {                                        // conv1d backward w.r.t. its input
-      const int cc = c - t + pad;
-      if (cc >= 0 && cc < g.C) ga += A.w1d[t] * s_gy1[cc];
-    }
-    const size_t o = static_cast<size_t>(b) * g.C + c;
-    s_q[c] = make_float2(1.f + a * (A.c.w[o] - 0.5f), ga);
-    kpart += ga * A.c.mavg[o] * live;
-  }
-  kpart = block_sum(kpart, tid, red);                                    // (its barriers publish s_q)
-  if (tid == 0) red[7] = kpart;
-  __syncthreads();
-  const float kb = red[7];
+  const EcaBwdNhwcLds L(g);
+  float2* s_q = reinterpret_cast<float2*>(smem + L.q);
+  const float kb = eca_bwd_prologue(A, b, a, smem + L.gy1, s_q, red);
 
   const size_t sb = static_cast<size_t>(b) * g.HW * g.C;
   const T* xb = static_cast<const T*>(A.x) + sb;
   const T* gb = static_cast<const T*>(A.gy) + sb;
   T* ob = static_cast<T*>(A.gx) + sb;
   const float use = A.c.use[b], den = A.c.den[b];
-  bool okp[kNhwcNpx];
-  int pix[kNhwcNpx];
-  float sv[kNhwcNpx], wA[kNhwcNpx], accp[kNhwcNpx];
+  const NhwcPix<NPX> P = nhwc_pixels<NPX>(t, tile * A.n.ch, g.HW);
+  float sv[NPX], wA[NPX], accp[NPX];
 #pragma unroll
-  for (int kk = 0; kk < kNhwcNpx; ++kk) {
-    const int p = p0 + kk * PR + row;
-    okp[kk] = p < g.HW;
-    pix[kk] = okp[kk] ? p : 0;
-    sv[kk] = A.c.splane[static_cast<size_t>(b) * g.HW + pix[kk]];
-    wA[kk] = has_mask ? (use * sv[kk] / den + (1.f - use) / Nf) : 1.f / Nf;
-    accp[kk] = 0.f;
+  for (int k = 0; k < NPX; ++k) {
+    sv[k] = A.c.splane[static_cast<size_t>(b) * g.HW + P.pix[k]];
+    wA[k] = has_mask ? (use * sv[k] / den + (1.f - use) / Nf) : 1.f / Nf;
+    accp[k] = 0.f;
   }
-  const int nj = (A.n.ng + CS - 1) / CS;
-  for (int j = 0; j < nj; ++j) {
-    const int cgi = lane + j * CS;
-    if (cgi >= A.n.ng) break;
-    const int c0 = cgi * VEC;
+  for (int j = 0; j < t.nj; ++j) {
+    NhwcGroup cg;
+    if (!nhwc_group_live<VEC>(t, A.n, j, cg)) break;
     float2 q[VEC];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) q[e] = s_q[min(c0 + e, g.C - 1)];
-    float gv[kNhwcNpx][VEC], xv[kNhwcNpx][VEC];
+    for (int e = 0; e < VEC; ++e) q[e] = s_q[min(cg.c0 + e, g.C - 1)];
+    float gv[NPX][VEC], xv[NPX][VEC];
 #pragma unroll
-    for (int kk = 0; kk < kNhwcNpx; ++kk) {
-      const size_t o = static_cast<size_t>(pix[kk]) * g.C + c0;
-      load_vec<T, VEC>(gb + o, gv[kk]);
-      if (GMASK) load_vec<T, VEC>(xb + o, xv[kk]);
+    for (int k = 0; k < NPX; ++k) {
+      const size_t o = static_cast<size_t>(P.pix[k]) * g.C + cg.c0;
+      load_vec<T, VEC>(gb + o, gv[k]);
+      if (GMASK) load_vec<T, VEC>(xb + o, xv[k]);
     }
 #pragma unroll
-    for (int kk = 0; kk < kNhwcNpx; ++kk) {
+    for (int k = 0; k < NPX; ++k) {
       float ov[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
-        ov[e] = gv[kk][e] * q[e].x + q[e].y * wA[kk];
-        if (GMASK) accp[kk] += q[e].y * xv[kk][e];
+        ov[e] = gv[k][e] * q[e].x + q[e].y * wA[k];
+        if (GMASK) accp[k] += q[e].y * xv[k][e];
       }
-      if (okp[kk]) store_vec<T, VEC>(ob + static_cast<size_t>(pix[kk]) * g.C + c0, ov);
+      if (P.ok[k]) store_vec<T, VEC>(ob + static_cast<size_t>(P.pix[k]) * g.C + cg.c0, ov);
     }
   }
   if (GMASK) {
 #pragma unroll
-    for (int kk = 0; kk < kNhwcNpx; ++kk) {
-      const float t = wave_group_sum(accp[kk], CS);                      // a pixel's lanes sit in one wave
-      if (lane == 0 && okp[kk]) {
-        const float gs = (use / den) * (t - kb);
-        A.gmask[static_cast<size_t>(b) * g.HW + pix[kk]] = g.use_sigmoid ? gs * sv[kk] * (1.f - sv[kk]) : gs;
-      }
+    for (int k = 0; k < NPX; ++k) {
+      const float dot = wave_group_sum(accp[k], t.CS);                   // a pixel's lanes sit in one wave
+      if (t.lane == 0 && P.ok[k]) A.gmask[static_cast<size_t>(b) * g.HW + P.pix[k]] = eca_gmask(g, use, den, dot, kb, sv[k]);
     }
   }
 }

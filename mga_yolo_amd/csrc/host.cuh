@@ -548,17 +548,7 @@ static size_t reduce1_smem(const Geo& g, int vec, int proj) {
 }
 static size_t pool_mlp_smem(const Geo& g) { return (4 + 2 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }   // k_pool's tail: [last?, 3 pad][2C avg|mx][2h]
 static size_t mlp_smem(const Geo& g) { return (3 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }
-// their NHWC siblings (n: nhwc_geo of the level)
-static size_t nhwc_pool_smem(const Geo& g) { return 4 * static_cast<size_t>(g.C) * sizeof(float); }
-static size_t nhwc_chan_smem(const Geo& g) { return static_cast<size_t>(g.C) * sizeof(float); }
-static size_t nhwc_apply_smem(const Geo& g, const Tune& t, const NhwcGeo& n) {
-  return (((3 * g.k * g.k + 3) & ~3) + 3 * static_cast<size_t>(t.apply_rows) * (g.W + g.k - 1) + n.ch + g.C) * sizeof(float);
-}
-static size_t nhwc_reduce1_smem(const Geo& g, int vec) {
-  return (3 * ((static_cast<size_t>(g.C) + 3) & ~static_cast<size_t>(3)) + 2 * kBlock * vec) * sizeof(float);
-}
-static size_t nhwc_reduce2_smem(const Geo& g) { return static_cast<size_t>(g.C) * sizeof(float); }
-static size_t nhwc_bwd_apply_smem(const Geo& g) { return (5 * static_cast<size_t>(g.C) + 2 * g.hidden) * sizeof(float); }
+// (their NHWC siblings: the *NhwcLds layout structs beside the kernels, nhwc.cuh lds_bytes)
 
 // concatenate the levels' grids: workgroup ids [start[l], start[l+1]) of the launch belong to level l; returns the grid
 template <typename Args, typename Fn>
