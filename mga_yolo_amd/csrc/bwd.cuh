@@ -742,7 +742,7 @@ __device__ __forceinline__ void bwd_params_body(const BwdArgs& A, const int loca
       d = wave_group_sum(d, kWave);
       if (lane == 0) {
         const float ha = A.c.h_avg[b * h + j], hm = A.c.h_mx[b * h + j];
-        const float ga = ha > 0.f ? d : 0.f, gm = hm > 0.f ? d : 0.f;          // relu backward
+        const float ga = relu_passes(ha) ? d : 0.f, gm = relu_passes(hm) ? d : 0.f;   // relu backward
         s_ga[b] = ga; s_gm[b] = gm; s_hs[b] = ha + hm;
         A.s.gh_avg[b * h + j] = ga;
         A.s.gh_mx[b * h + j] = gm;
@@ -932,8 +932,8 @@ __device__ __forceinline__ void bwd_apply_body(const BwdArgs& A, const int bid, 
       __syncthreads();
       if (k0 == 0 && j < h) {
         for (int q = 1; q < G_; ++q) p += sm[q * hh + j0];
-        s_gh[j] = A.c.h_avg[static_cast<size_t>(b) * h + j] > 0.f ? p : 0.f;
-        s_gh[h + j] = A.c.h_mx[static_cast<size_t>(b) * h + j] > 0.f ? p : 0.f;
+        s_gh[j] = relu_passes(A.c.h_avg[static_cast<size_t>(b) * h + j]) ? p : 0.f;
+        s_gh[h + j] = relu_passes(A.c.h_mx[static_cast<size_t>(b) * h + j]) ? p : 0.f;
       }
       __syncthreads();
     }

@@ -89,6 +89,12 @@ __device__ __forceinline__ float sigmoid_fast(float v) {
 }
 // torch.nn.functional.softplus(beta=1, threshold=20)  (masked_cbam.py:150-152)
 __device__ __forceinline__ float softplusf_(float v) { return v > 20.0f ? v : log1pf(expf(v)); }
+// Non-finite values go where torch's operators carry them ("Non-finite values"); finite inputs give the bits of fmaxf / `> 0`.
+// torch.relu(NaN) is NaN (fmaxf(NaN, 0) is 0); threshold_backward zeroes the gradient where h <= 0 and so passes it where h is NaN;
+// clamp_min(NaN, m) is NaN (fmaxf(NaN, m) is m)
+__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
+__device__ __forceinline__ bool relu_passes(float h) { return !(h <= 0.f); }
+__device__ __forceinline__ float clamp_min_nan(float v, float m) { return v < m ? m : v; }
 // torch.isclose(a, b) with the default rtol=1e-5, atol=1e-8 (masked_cbam.py:120)
 __device__ __forceinline__ bool isclosef_(float a, float b) { return fabsf(a - b) <= 1e-8f + 1e-5f * fabsf(b); }
 

@@ -46,7 +46,7 @@ template <bool HAS_MASK>
 __device__ __forceinline__ void eca_pooled_stats(const EcaCtx& ctx, const Geo& g, int b, int c, float S, float sx, float sxs) {
   const float N = static_cast<float>(g.HW);
   const float use = (S / N >= g.thr) ? 1.f : 0.f;              // masked_eca.py:152-153, 159
-  const float den = fmaxf(S, g.eps);                           // :156, 164
+  const float den = clamp_min_nan(S, g.eps);                   // :156, 164
   const size_t o = static_cast<size_t>(b) * g.C + c;
   const float gap = sx / N;
   const float mavg = HAS_MASK ? sxs / den : gap;               // :157, 165
@@ -121,6 +121,17 @@ __global__ __launch_bounds__(kBlock) void k_eca_pool(const Group<EcaFwdArgs> G) 
   }
 }
 
+// The pooled descriptor the conv1d reads.  The reference forms the blend with the GAP (masked_eca.py:152-161) only in a BATCH that holds a
+// tiny sample; in any other batch the descriptor is the masked average itself (:163-165).  On finite values the two are the same numbers
+// (mavg * 1 + gap * 0); an infinite x makes gap * 0 a NaN in the one and leaves an infinity in the other, which the sigmoid saturates
+// ("Non-finite values").  Read in the launches after the pooling one: every sample's S is in ctx.
+__device__ __forceinline__ const float* eca_descriptor(const EcaCtx& c, const Geo& g, bool has_mask) {
+  if (!has_mask) return c.avg;
+  bool tiny = false;                                           // S / N < thr: use = [S / N >= thr] is 0 and S is no NaN
+  for (int b = 0; b < g.B; ++b) tiny = tiny || (c.use[b] == 0.f && c.S[b] == c.S[b]);
+  return tiny ? c.avg : c.mavg;
+}
+
 // sigmoid(conv1d(avg))[b,c] with zero padding over the channel axis                masked_eca.py:181-187
 __device__ __forceinline__ float eca_gate_w(const float* __restrict__ avg_b, const float* __restrict__ w1d, int k, int C, int c) {
   const int pad = k / 2;
@@ -151,6 +162,7 @@ __global__ __launch_bounds__(kBlock) void k_eca_apply(const Group<EcaFwdArgs> G)
   const int c0 = cg * CPB + ty * CPT;
   const int nv = g.HW / VEC;
   const float a = softplusf_(*A.beta);
+  const float* desc = eca_descriptor(A.c, g, A.mask != nullptr);
   const T* xr[CPT];
   T* yr[CPT];
   float gate[CPT];
@@ -162,7 +174,7 @@ __global__ __launch_bounds__(kBlock) void k_eca_apply(const Group<EcaFwdArgs> G)
     const size_t o = static_cast<size_t>(b) * g.C + c;
     xr[j] = static_cast<const T*>(A.x) + o * g.HW;
     yr[j] = static_cast<T*>(A.y) + o * g.HW;
-    const float w = eca_gate_w(A.c.avg + static_cast<size_t>(b) * g.C, A.w1d, g.k, g.C, c);
+    const float w = eca_gate_w(desc + static_cast<size_t>(b) * g.C, A.w1d, g.k, g.C, c);
     gate[j] = 1.f + a * (w - 0.5f);                            // masked_eca.py:190
     if (tx == 0 && live[j]) A.c.w[o] = w;
   }
@@ -240,6 +252,9 @@ __device__ __forceinline__ void eca_params_body(const EcaBwdArgs& A, const int r
   const int tid = threadIdx.x, k = g.k, pad = k / 2, BC = g.B * g.C;
   if (r >= k && r != kEcaRoles - 1) return;
   const float a = softplusf_(*A.beta);
+  // (ctx.avg, not eca_descriptor: the two differ only where one holds an infinity and the other a NaN, and either makes every tap it
+  //  reaches non-finite; choosing between two pointers here cost k_eca_bwd<float, 4, true> 12 VGPRs and a wave per SIMD)
+  const float* desc = A.c.avg;
   float acc = 0.f;
 #pragma unroll 4
   for (int o = tid; o < BC; o += kBlock) {
@@ -248,7 +263,10 @@ __device__ __forceinline__ void eca_params_body(const EcaBwdArgs& A, const int r
       acc += gg * (w - 0.5f);
     } else {
       const int b = o / g.C, c = o - b * g.C, cc = c + r - pad;
-      if (cc >= 0 && cc < g.C) acc += a * gg * w * (1.f - w) * A.c.avg[static_cast<size_t>(b) * g.C + cc];
+      // a tap outside the channel axis reads the convolution's zero padding: the product is formed, so a non-finite gy1 reaches every tap
+      // as it does in torch's conv1d backward (finite values: + 0, the same bits)
+      const float av = (cc >= 0 && cc < g.C) ? desc[static_cast<size_t>(b) * g.C + cc] : 0.f;
+      acc += a * gg * w * (1.f - w) * av;
     }
   }
   acc = block_sum(acc, tid, red);

@@ -144,8 +144,9 @@ __global__ __launch_bounds__(kBlock) void k_eca_apply_nhwc(const Group<EcaFwdArg
   T* yb = static_cast<T*>(A.y) + sb;
   const float a = softplusf_(*A.beta);
   float* s_gate = smem + EcaApplyNhwcLds(g).gate;
+  const float* desc = eca_descriptor(A.c, g, A.mask != nullptr);
   for (int c = t.tid; c < g.C; c += kBlock) {
-    const float w = eca_gate_w(A.c.avg + static_cast<size_t>(b) * g.C, A.w1d, g.k, g.C, c);
+    const float w = eca_gate_w(desc + static_cast<size_t>(b) * g.C, A.w1d, g.k, g.C, c);
     s_gate[c] = 1.f + a * (w - 0.5f);                                     // masked_eca.py:190
     if (tile == 0) A.c.w[static_cast<size_t>(b) * g.C + c] = w;
   }

@@ -139,7 +139,7 @@ __device__ __forceinline__ void pool_body(const FwdArgs& A, const int bid, float
     const float N = static_cast<float>(g.HW);
     const float S = sums[2 * CPT];
     const float use = (S / N >= g.thr) ? 1.f : 0.f;          // masked_cbam.py:97-98
-    const float den = fmaxf(S, g.eps);                       // masked_cbam.py:99
+    const float den = clamp_min_nan(S, g.eps);               // masked_cbam.py:99
 #pragma unroll
     for (int j = 0; j < CPT; ++j) {
       const int c = c0 + j;
@@ -232,7 +232,7 @@ __device__ __forceinline__ void mlp_gate_to_lds(const FwdArgs& A, const int b, c
     dm = wave_group_sum(dm, kWave);
     if (lane == 0) {
       const float bj = A.p.b1[j];
-      const float ha = fmaxf(da + bj, 0.f), hm = fmaxf(dm + bj, 0.f);
+      const float ha = relu_nan(da + bj), hm = relu_nan(dm + bj);
       s_h[j] = ha; s_h[h + j] = hm;
       if (publish) {
         A.c.h_avg[static_cast<size_t>(b) * h + j] = ha;
@@ -831,7 +831,7 @@ __device__ __forceinline__ void mlp_hidden(const FwdArgs& A, const int b, float*
         if (lane == 0) {
           const int j = wave + 4 * u;
           const float bj = A.p.b1[j];
-          const float ha = fmaxf(sa + bj, 0.f), hm = fmaxf(sm + bj, 0.f);
+          const float ha = relu_nan(sa + bj), hm = relu_nan(sm + bj);
           s_h[j] = ha; s_h[h + j] = hm;
           A.c.h_avg[static_cast<size_t>(b) * h + j] = ha;
           A.c.h_mx[static_cast<size_t>(b) * h + j] = hm;

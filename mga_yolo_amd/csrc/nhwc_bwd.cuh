@@ -240,8 +240,8 @@ __global__ __launch_bounds__(kBlock) void k_bwd_apply_nhwc(const Group<BwdArgs> 
     for (int j = tid; j < h; j += kBlock) {
       float p = 0.f;
       for (int q = 0; q < A.ncb; ++q) p += pg[q * h + j];
-      s_gh[j] = A.c.h_avg[static_cast<size_t>(b) * h + j] > 0.f ? p : 0.f;
-      s_gh[h + j] = A.c.h_mx[static_cast<size_t>(b) * h + j] > 0.f ? p : 0.f;
+      s_gh[j] = relu_passes(A.c.h_avg[static_cast<size_t>(b) * h + j]) ? p : 0.f;
+      s_gh[h + j] = relu_passes(A.c.h_mx[static_cast<size_t>(b) * h + j]) ? p : 0.f;
     }
   }
   __syncthreads();

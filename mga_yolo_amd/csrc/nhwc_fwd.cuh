@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kBlock) void k_pool_fin(const Group<FwdArgs> G) {
   const float sxs = sum[0], sx = sum[1];
   const float Nf = static_cast<float>(g.HW);
   const float use = (S / Nf >= g.thr) ? 1.f : 0.f;                      // masked_cbam.py:97-98
-  const float den = fmaxf(S, g.eps);                                    // masked_cbam.py:99
+  const float den = clamp_min_nan(S, g.eps);                            // masked_cbam.py:99
   const size_t o = static_cast<size_t>(b) * g.C + c;
   const float gap = sx / Nf;                                            // masked_cbam.py:101
   float avg, mavg, mxo;

@@ -147,7 +147,7 @@ __device__ __forceinline__ void sp_form_h(const SpadeArgs& A, const SpTile& t, c
       v = b0s[j];
 #pragma unroll
       for (int k = 0; k < 9; ++k) v = fmaf(w0s[j * 9 + k], ss[(r + k / 3) * SW + c + k % 3], v);
-      v = fmaxf(v, 0.f);
+      v = relu_nan(v);
     }
     hs[ph * HS + j] = v;
   }
@@ -676,7 +676,7 @@ __global__ __launch_bounds__(kBlock) void k_spade_dh(const Group<SpadeArgs> G) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) pre = fmaf(w0s[j * 9 + k], ss[(r + 1 + k / 3) * SW + cx + 1 + k % 3], pre);
         const bool in = t.y0 + r < A.H && t.x0 + cx < A.W;
-        dp[j * kSpAStride + p] = (in && pre > 0.f) ? acc[nt][v] : 0.f;
+        dp[j * kSpAStride + p] = (in && relu_passes(pre)) ? acc[nt][v] : 0.f;
       }
     }
   }

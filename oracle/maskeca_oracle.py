@@ -114,9 +114,15 @@ def reference_form(x, mask, p: EcaParams, cfg: EcaConfig = EcaConfig()):
         m = mask.unsqueeze(1) if mask.dim() == 3 else mask
         s = m.sigmoid() if cfg.use_sigmoid_mask else m
         se = s.expand(B, C, H, W)
-        valid = (se.mean(dim=(2, 3)).mean(dim=1) >= cfg.tiny_thr).to(x.dtype).unsqueeze(1)
+        mean_mask = se.mean(dim=(2, 3)).mean(dim=1)
         masked = (x * se).sum(dim=(2, 3)) / se.sum(dim=(2, 3)).clamp_min(cfg.eps)
-        v = masked * valid + F.adaptive_avg_pool2d(x, 1).view(B, C) * (1.0 - valid)
+        # masked_eca.py:152-165: the blend with the GAP is formed only in a batch that holds a tiny sample.  On finite values the two
+        # branches are the same numbers (masked * 1 + gap * 0); an infinite x makes gap * 0 a NaN in the one and leaves masked = inf in the other
+        if bool((mean_mask < cfg.tiny_thr).any()):
+            valid = (mean_mask >= cfg.tiny_thr).to(x.dtype).unsqueeze(1)
+            v = masked * valid + F.adaptive_avg_pool2d(x, 1).view(B, C) * (1.0 - valid)
+        else:
+            v = masked
     k = p.w.shape[-1]
     w = F.conv1d(v.unsqueeze(1), p.w, padding=k // 2).squeeze(1).sigmoid().view(B, C, 1, 1)
     return x * (1.0 + F.softplus(p.beta) * (w - 0.5))

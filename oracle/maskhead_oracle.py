@@ -191,6 +191,13 @@ def elem_u(got: torch.Tensor, want: torch.Tensor, mag: torch.Tensor, floor: floa
 
 def reference_form_step(x, p: HeadParams, g, training: bool = True):
     """The same computation issued as the reference issues it (three nn modules' ATen ops through autograd): the CPU baseline."""
+    y, out = reference_form_all(x, p, g, training)
+    return y, out["gx"]
+
+
+def reference_form_all(x, p: HeadParams, g, training: bool = True):
+    """reference_form_step with every result: -> (logits, dict(gx, gw1 (hid, C), ggamma, gbeta, gwh, gbh, running_mean, running_var)),
+    in the dtype of x and p (the tests of non-finite propagation call it in fp64)."""
     hid, C = p.w1.shape
     xl = x.clone().requires_grad_(True)
     ws = [t.clone().requires_grad_(True) for t in (p.w1.reshape(hid, C, 1, 1), p.gamma, p.beta, p.wh, p.bh)]
@@ -199,4 +206,5 @@ def reference_form_step(x, p: HeadParams, g, training: bool = True):
     a = F.batch_norm(z, rm, rv, ws[1], ws[2], training, p.momentum, p.eps)
     y = F.conv2d(F.silu(a), ws[3], ws[4], padding=1)
     y.backward(g)
-    return y.detach(), xl.grad
+    return y.detach(), dict(gx=xl.grad, gw1=ws[0].grad.reshape(hid, C), ggamma=ws[1].grad, gbeta=ws[2].grad, gwh=ws[3].grad, gbh=ws[4].grad,
+                            running_mean=rm, running_var=rv)

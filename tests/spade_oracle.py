@@ -109,6 +109,46 @@ def backward(gy, ctx):
     return out
 
 
+def reference_form(x, mask, params, norm_type="in", training=True, use_sigmoid=True, eps=1e-6, running=None, momentum=0.1):
+    """The block as the differentiable eager-op sequence the reference executes, one op per line of masked_spade.py, in the dtype of x.
+    running: (mean, var) of a batch norm, updated in place as F.batch_norm does.  Unlike forward / backward above it goes through autograd,
+    so it says what torch's own operators do with a non-finite value."""
+    if norm_type.lower() == "bn":                                                            # masked_spade.py:73, 122
+        x_hat = F.batch_norm(x, running[0], running[1], None, None, training, momentum, eps)
+    else:                                                                                    # masked_spade.py:75, 122
+        x_hat = F.instance_norm(x, None, None, None, None, True, 0.1, eps)
+    if mask is None:                                                                         # masked_spade.py:124-126
+        return x_hat
+    if mask.dim() == 3:                                                                      # masked_spade.py:103-104
+        mask = mask.unsqueeze(1)
+    if tuple(mask.shape[-2:]) != tuple(x.shape[-2:]):                                        # masked_spade.py:107-108
+        mask = F.interpolate(mask, size=tuple(x.shape[-2:]), mode="bilinear", align_corners=False)
+    if use_sigmoid:                                                                          # masked_spade.py:109-110
+        mask = mask.sigmoid()
+    h = F.relu(F.conv2d(mask, params["shared.0.weight"], params["shared.0.bias"], padding=1))      # masked_spade.py:131
+    gamma = F.conv2d(h, params["conv_gamma.weight"], params["conv_gamma.bias"], padding=1)         # masked_spade.py:132
+    beta = F.conv2d(h, params["conv_beta.weight"], params["conv_beta.bias"], padding=1)            # masked_spade.py:133
+    return gamma * x_hat + beta                                                                     # masked_spade.py:138
+
+
+def reference_form_step(x, mask, params, gy, norm_type="in", training=True, use_sigmoid=True, eps=1e-6, running=None, momentum=0.1):
+    """One forward + backward of the eager form through autograd -> (y, dict(gx, [gmask, g<param key>...], [running_mean, running_var]))
+    with backward()'s keys.  Nothing given is written to: the running statistics are cloned first."""
+    xr = x.detach().clone().requires_grad_(True)
+    mr = None if mask is None else mask.detach().clone().requires_grad_(True)
+    leaves = {k: params[k].detach().clone().requires_grad_(True) for k in PARAM_KEYS}
+    run = None if running is None else tuple(t.detach().clone() for t in running[:2])
+    y = reference_form(xr, mr, leaves, norm_type, training, use_sigmoid, eps, run, momentum)
+    y.backward(gy)
+    out = {"gx": xr.grad}
+    if mr is not None:
+        out["gmask"] = mr.grad
+        out.update({k: v.grad for k, v in leaves.items()})
+    if run is not None:
+        out["running_mean"], out["running_var"] = run
+    return y.detach(), out
+
+
 def min_abs_pre(ctx) -> float:
     return float(ctx["pre"].abs().min())
 
