@@ -57,7 +57,8 @@ extern "C" {
  * img_h not positive and finite, conf_thres not finite, iou_thres not finite or outside [0, 1): MGACBAM_E_ARG; a NULL dets, count, det_out,
  * cm, status or ws, NULL labels or lab_out with n_cap > 0: MGACBAM_E_NULL; an fp32 / int32 buffer not 4-byte aligned, acc not 8-byte
  * aligned, ws not 16-byte aligned: MGACBAM_E_ALIGN; ws smaller than mgacm_ws_bytes: MGACBAM_E_SIZE.
- * Not built: ap_per_class, plot_matches / visualize (the TP / FP / FN index lists), rotated boxes (batch_probiou), the classification
+ * ap_per_class is the stage behind this one (include/ext/mgaap.h).
+ * Not built: plot_matches / visualize (the TP / FP / FN index lists), rotated boxes (batch_probiou), the classification
  * task's process_cls_preds, nc above MGACM_MAX_NC.
  * ------------------------------------------------------------------------------------------------ */
 #define MGACM_MAX_NC 119

@@ -54,8 +54,8 @@ extern "C" {
  * and finite, rows_cap or tgt_cap < 1 with the accumulation on: MGACBAM_E_ARG; a NULL dets, count, tp, best_iou, best_gt, status or ws, NULL
  * labels with n_cap > 0, a partial set of the accumulation buffers: MGACBAM_E_NULL; an fp32 / int32 buffer not 4-byte aligned, ws not 16-byte
  * aligned: MGACBAM_E_ALIGN; ws smaller than mgamatch_ws_bytes: MGACBAM_E_SIZE.
- * Not built: the confusion matrix, ap_per_class, the scipy assignment branch of match_predictions, rotated boxes, the mask and pose
- * matrices tp_m / tp_p.
+ * Behind it: the confusion matrix (include/ext/mgaconfusion.h) and ap_per_class on this accumulation (include/ext/mgaap.h).
+ * Not built: the scipy assignment branch of match_predictions, rotated boxes, the mask and pose matrices tp_m / tp_p.
  * ------------------------------------------------------------------------------------------------ */
 #define MGAMATCH_MAX_IOU 16
 #define MGAMATCH_SINGLE_CLS 1

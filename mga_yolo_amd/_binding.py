@@ -302,6 +302,21 @@ def fill_confusion(D: _lib.ConfusionDesc, dets, count, batch_idx, cls, bboxes, n
     D.reserved = 0
 
 
+# ---- average precision per class from the accumulated rows (include/ext/mgaap.h)
+def fill_ap(D: _lib.ApDesc, rows_tp, rows_conf, rows_cls, rows_img, tgt_cls, tgt_img, state, nc: int, grid_ap, grid_curve, result, status,
+            ws=None) -> None:
+    """The accumulation as fill_match's acc holds it: rows_tp uint8 (rows_cap, niou), rows_conf, rows_cls fp32 (rows_cap), tgt_cls fp32
+    (tgt_cap), state int32 (4); rows_img and tgt_img int32 or None (they are not read); grid_ap fp64 (101) and grid_curve fp64 (1000): the
+    two linspaces; result uint8, _lib.ap_result_layout(nc, niou)["total"] bytes, and status int32 (1) are written; ws: uint8,
+    _lib.ap_ws_bytes of the filled struct (fill once without it to ask, then again with it)."""
+    D.rows_tp, D.rows_conf, D.rows_cls, D.rows_img = rows_tp.data_ptr(), rows_conf.data_ptr(), rows_cls.data_ptr(), _ptr(rows_img)
+    D.tgt_cls, D.tgt_img, D.state = tgt_cls.data_ptr(), _ptr(tgt_img), state.data_ptr()
+    D.rows_cap, D.tgt_cap, D.niou, D.nc = rows_conf.shape[0], tgt_cls.shape[0], rows_tp.shape[1], int(nc)
+    D.grid_ap, D.grid_curve, D.result, D.status = grid_ap.data_ptr(), grid_curve.data_ptr(), result.data_ptr(), status.data_ptr()
+    D.ws, D.ws_bytes = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+    D.reserved = 0
+
+
 # ---- the feature-block families: what the eager frame (functional.py) and the static plans (plan.py, slice.py) both need of one
 class Family(NamedTuple):
     """One block family.  ``shape`` = (B,C,H,W); ``cfg`` = the block's config dataclass, for the mask head the tuple (hidden, eps, momentum,

@@ -240,6 +240,29 @@ class ConfusionDesc(C.Structure):                # mgacm_desc_t
                 ("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("reserved", C.c_int32)]
 
 
+# average precision per class from the accumulated rows (include/ext/mgaap.h: the fourth stage, CURVE_HEADERS below)
+AP_MAX_NC, AP_TILE, AP_POINTS, AP_CURVE_POINTS = 1024, 2048, 101, 1000
+
+
+class ApDesc(C.Structure):                       # mgaap_desc_t
+    _fields_ = [("rows_tp", C.c_void_p), ("rows_conf", C.c_void_p), ("rows_cls", C.c_void_p), ("rows_img", C.c_void_p),
+                ("tgt_cls", C.c_void_p), ("tgt_img", C.c_void_p), ("state", C.c_void_p),
+                ("rows_cap", C.c_int32), ("tgt_cap", C.c_int32), ("niou", C.c_int32), ("nc", C.c_int32),
+                ("grid_ap", C.c_void_p), ("grid_curve", C.c_void_p), ("result", C.c_void_p), ("status", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("reserved", C.c_int32)]
+
+
+def ap_result_layout(nc: int, niou: int) -> dict:
+    """The result block of mgaap_run in bytes: name -> (offset, shape, numpy dtype string); "total": its size."""
+    out, o = {}, 0
+    for name, shape, dt in (("ap", (nc, niou), "f8"), ("p_curve", (nc, AP_CURVE_POINTS), "f8"), ("r_curve", (nc, AP_CURVE_POINTS), "f8"),
+                            ("prec_values", (nc, AP_CURVE_POINTS), "f8"), ("nt", (nc,), "i4"), ("n_det", (nc,), "i4")):
+        out[name] = (o, shape, dt)
+        o += shape[0] * (shape[1] if len(shape) > 1 else 1) * int(dt[1])
+    out["total"] = o
+    return out
+
+
 class Header(NamedTuple):
     """What one file under include/ declares and this module mirrors (tests/test_abi_headers.py holds each record against its header)."""
     symbols: dict        # function -> (restype, argtypes)
@@ -397,9 +420,20 @@ LAYOUT_HEADERS = {
         structs={},
         constants=dict(MGAMAPS_LAYOUT_NHWC=MAPS_LAYOUT_NHWC)),
 }
-_TABLES = dict(HEADERS=HEADERS, EXT_HEADERS=EXT_HEADERS, METRIC_HEADERS=METRIC_HEADERS, LAYOUT_HEADERS=LAYOUT_HEADERS)
+# average precision per class behind the matching's accumulation (include/ext/mgaap.h; a table of its own as well; tests/test_abi_ap.py)
+CURVE_HEADERS = {
+    "ext/mgaap.h": Header(
+        symbols={
+            "mgaap_ws_bytes": (C.c_size_t, [C.POINTER(ApDesc)]),
+            "mgaap_run": (_i, [C.POINTER(ApDesc), C.c_void_p]),
+        },
+        structs=dict(mgaap_desc=ApDesc),
+        constants=dict(MGAAP_MAX_NC=AP_MAX_NC, MGAAP_TILE=AP_TILE, MGAAP_AP_POINTS=AP_POINTS, MGAAP_CURVE_POINTS=AP_CURVE_POINTS)),
+}
+_TABLES = dict(HEADERS=HEADERS, EXT_HEADERS=EXT_HEADERS, METRIC_HEADERS=METRIC_HEADERS, LAYOUT_HEADERS=LAYOUT_HEADERS,
+               CURVE_HEADERS=CURVE_HEADERS)
 ALL_HEADERS = {**HEADERS, **EXT_HEADERS, **METRIC_HEADERS}       # the three tables of the descriptors' headers
-_EVERY_HEADER = {**ALL_HEADERS, **LAYOUT_HEADERS}
+_EVERY_HEADER = {**ALL_HEADERS, **LAYOUT_HEADERS, **CURVE_HEADERS}
 _bound = [name for h in _EVERY_HEADER.values() for name in h.symbols]
 if len(_EVERY_HEADER) != sum(len(t) for t in _TABLES.values()):
     _keys = [k for t in _TABLES.values() for k in t]
@@ -564,6 +598,11 @@ def match_ws_bytes(desc) -> int:
 def confusion_ws_bytes(desc) -> int:
     """Workspace of a confusion-matrix call."""
     return _table_size("mgacm_ws_bytes", E_ARG, C.byref(desc))
+
+
+def ap_ws_bytes(desc) -> int:
+    """Workspace of an average-precision call."""
+    return _table_size("mgaap_ws_bytes", E_ARG, C.byref(desc))
 
 
 ARRIVE_STRIDE = 64     # int32 words between the arrival words of two samples (csrc/args.cuh: kArriveStride)

@@ -16,7 +16,9 @@ Device tensors go through `mgacm_run`: two launches, fixed-size outputs, no host
 `post.run(); match.run(); cm.run()` is one captured chain (`ConfusionPlan(labels=match)`).  Host tensors take `_host_confusion`, the same
 rule stated in torch ops.
 
-Not built: `ap_per_class`, `plot_matches` / `visualize`, rotated boxes (`batch_probiou`), the classification task's `process_cls_preds`,
+`ap_per_class` is the stage behind this one (detap.py, include/ext/mgaap.h).
+
+Not built: `plot_matches` / `visualize`, rotated boxes (`batch_probiou`), the classification task's `process_cls_preds`,
 more than 119 classes (`_lib.CM_MAX_NC`: the matrix is histogrammed in one workgroup's LDS).
 """
 from __future__ import annotations

@@ -11,9 +11,10 @@ Device tensors go through `mgamatch_run`: two launches, fixed-size outputs, no h
 sit inside a captured graph behind the post-process (`DetMatchPlan` fed by a `DetPostPlan`).  Host tensors take `_host_match`, the same rule
 stated in torch ops.
 
-The confusion matrix is the third stage, in a module of its own (detconfusion.py, include/ext/mgaconfusion.h).
+The confusion matrix is the third stage, in a module of its own (detconfusion.py, include/ext/mgaconfusion.h); `ap_per_class` on the
+accumulation is the fourth (detap.py, include/ext/mgaap.h).
 
-Not built: `ap_per_class`, the scipy assignment branch of `match_predictions`, rotated boxes, and the
+Not built: the scipy assignment branch of `match_predictions`, rotated boxes, and the
 mask and pose matrices `tp_m` / `tp_p`.
 """
 from __future__ import annotations

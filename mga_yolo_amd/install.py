@@ -13,7 +13,8 @@ Nothing else in the reference changes.  ``install(nms=True)`` -- opt-in -- also 
 ``ultralytics.utils.ops`` modules: the validator and the predictor look it up through ``ops.`` at call time (U/models/yolo/detect/val.py,
 predict.py), so the unchanged ``postprocess`` then runs ``detpost.non_max_suppression``.  ``install(match=True)`` -- opt-in as well -- rebinds
 ``DetectionValidator.update_metrics`` in the reference's ``ultralytics.models.yolo.detect.val`` modules to ``detmatch.update_metrics``: one matching call
-and one read-back per batch; subclasses (``MGAValidator``) reach it through ``super()``.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
+and one read-back per batch; subclasses (``MGAValidator``) reach it through ``super()``.  ``install(ap=True)`` -- opt-in too -- rebinds ``ap_per_class`` in
+the reference's ``ultralytics.utils.metrics`` modules (``DetMetrics.process`` finds it as a module global at call time) to ``detap``'s.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
 """
 from __future__ import annotations
 
@@ -44,17 +45,18 @@ def _is_reference_module(name: str) -> bool:
     return any(name == p or name.startswith(p + ".") for p in _PREFIXES) and not name.startswith("mga_yolo_amd")
 
 
-def install(strict: bool = False, nms: bool = False, match: bool = False, confusion: bool = False) -> List[str]:
+def install(strict: bool = False, nms: bool = False, match: bool = False, confusion: bool = False, ap: bool = False) -> List[str]:
     """Rebind the block classes in every loaded reference module that exports them.  Returns the module names patched.
     ``strict=True`` raises unless the module whose ``parse_model`` builds ``MGAModel`` (the one providing
     ``mga_yolo.model.model.DetectionModel``; ``ultralytics.nn.tasks`` when mga_yolo is absent) was patched.
     ``nms=True`` also rebinds ``non_max_suppression`` in the reference's ``ultralytics.utils.ops`` modules (see ``_install_nms``),
     ``match=True`` ``DetectionValidator.update_metrics`` in its ``ultralytics.models.yolo.detect.val`` modules (see ``_install_match``).
     ``confusion=True`` -- with ``match=True`` only, else ValueError -- sets the switch under which that ``update_metrics`` forms a plotted
-    validation's confusion matrix on the device, one call per batch (``detmatch._CONFUSION_ON``; uninstall() clears it)."""
+    validation's confusion matrix on the device, one call per batch (``detmatch._CONFUSION_ON``; uninstall() clears it).
+    ``ap=True`` also rebinds ``ap_per_class`` in the reference's ``ultralytics.utils.metrics`` modules (see ``_install_ap``)."""
     if confusion and not match:
         raise ValueError("install(confusion=True) needs match=True: the confusion matrix is formed by the replacement update_metrics")
-    for name in _PRELOAD + (_OPS_PRELOAD if nms else ()) + (_VAL_PRELOAD if match else ()):
+    for name in _PRELOAD + (_OPS_PRELOAD if nms else ()) + (_VAL_PRELOAD if match else ()) + (_METRICS_PRELOAD if ap else ()):
         if name not in sys.modules:
             try:
                 importlib.import_module(name)
@@ -87,6 +89,8 @@ def install(strict: bool = False, nms: bool = False, match: bool = False, confus
         if not detmatch._CONFUSION_ON:
             _UNDO.append((detmatch.__name__, "_CONFUSION_ON", False))
             detmatch._CONFUSION_ON = True
+    if ap:
+        patched += _install_ap()
     if strict:
         need = _factory_module_name()
         if need not in patched:
@@ -140,6 +144,28 @@ def _install_match() -> List[str]:
         _UNDO.append((name + ":DetectionValidator", "update_metrics", cur))
         _ORIGINALS[cls] = cur
         cls.update_metrics = update_metrics
+        done.append(name)
+    return done
+
+
+_METRICS_PRELOAD = ("ultralytics.utils.metrics", "mga_yolo.external.ultralytics.ultralytics.utils.metrics")
+_METRICS_SUFFIX = "ultralytics.utils.metrics"
+
+
+def _install_ap() -> List[str]:
+    """Rebind ``ap_per_class`` in every loaded ``ultralytics.utils.metrics`` module of the reference (two module objects of that file, as of
+    ops.py).  Each module gets a function of its own, so that ``plot=True`` reaches that module's ``plot_pr_curve`` / ``plot_mc_curve``.
+    uninstall() restores them."""
+    from .detap import reference_replacement
+    done = []
+    for name, mod in list(sys.modules.items()):
+        if mod is None or not _is_reference_module(name) or not name.endswith(_METRICS_SUFFIX):
+            continue
+        cur = mod.__dict__.get("ap_per_class", _MISSING)
+        if cur is _MISSING or getattr(cur, "_mga_replacement", False):
+            continue
+        _UNDO.append((name, "ap_per_class", cur))
+        mod.ap_per_class = reference_replacement(mod)
         done.append(name)
     return done
 
