@@ -22,6 +22,7 @@ from .detpost import DetPostPlan, detect_postprocess, non_max_suppression  # noq
 from .detmatch import DetMatchPlan, match_detections  # noqa: F401
 from .detconfusion import ConfusionPlan, confusion_matrix, reference_conf  # noqa: F401
 from .detap import DetApPlan, ap_per_class  # noqa: F401
+from .image import ImagePlan, image_batch, multi_scale_size  # noqa: F401
 
 __all__ = ["MaskCBAM", "MaskECA", "MaskSPADE", "MaskSPADEConfig", "SpadeConfig", "mask_spade", "mask_spade_pyramid", "MGAMaskHead", "mask_head", "mask_head_pyramid", "ProbMaskGater", "BlockConfig", "EcaConfig", "mask_cbam", "mask_cbam_pyramid", "mask_eca",
            "mask_eca_pyramid", "prob_mask_gate", "prob_mask_gate_pyramid", "GateConfig", "gate_state", "resize_nearest", "mask_pyramid", "install", "uninstall", "SegLossConfig", "SegmentationLoss", "kendall_combine", "HandoffTimeout", "handoff_report",
@@ -29,5 +30,6 @@ __all__ = ["MaskCBAM", "MaskECA", "MaskSPADE", "MaskSPADEConfig", "SpadeConfig",
            "detection_loss", "V8DetectionLoss", "DetLossPlan", "detect_postprocess", "non_max_suppression", "DetPostPlan",
            "match_detections", "DetMatchPlan",
            "confusion_matrix", "ConfusionPlan", "reference_conf",
-           "ap_per_class", "DetApPlan"]
+           "ap_per_class", "DetApPlan",
+           "image_batch", "multi_scale_size", "ImagePlan"]
 __version__ = "0.1.0"

@@ -317,6 +317,20 @@ def fill_ap(D: _lib.ApDesc, rows_tp, rows_conf, rows_cls, rows_img, tgt_cls, tgt
     D.reserved = 0
 
 
+# ---- a batch of uint8 images prepared in one launch (include/ext/mgaimage.h)
+def fill_image(D: _lib.ImageDesc, src, dst, src_nhwc: bool = False, reverse_channels: bool = False) -> None:
+    """src: uint8, contiguous, (B,C,H,W) or with src_nhwc (B,H,W,C); dst: (B,C,H',W') fp32 / fp16 / bf16, contiguous or channels_last (its
+    strides say which: a destination that is both -- C = 1, or H' = W' = 1 -- is written as contiguous, the same bytes).  H', W' other than
+    H, W: the bilinear resize."""
+    B, Cc, oh, ow = dst.shape
+    ih, iw = (src.shape[1], src.shape[2]) if src_nhwc else (src.shape[2], src.shape[3])
+    D.src, D.dst = src.data_ptr(), dst.data_ptr()
+    D.B, D.C, D.in_h, D.in_w, D.out_h, D.out_w = B, Cc, ih, iw, oh, ow
+    D.dtype = DTYPES[dst.dtype]
+    D.flags = (_lib.IMG_SRC_NHWC if src_nhwc else 0) | (0 if dst.is_contiguous() else _lib.IMG_DST_NHWC) | (_lib.IMG_REVERSE_C if reverse_channels else 0)
+    D.reserved = 0
+
+
 # ---- the feature-block families: what the eager frame (functional.py) and the static plans (plan.py, slice.py) both need of one
 class Family(NamedTuple):
     """One block family.  ``shape`` = (B,C,H,W); ``cfg`` = the block's config dataclass, for the mask head the tuple (hidden, eps, momentum,

@@ -263,6 +263,17 @@ def ap_result_layout(nc: int, niou: int) -> dict:
     return out
 
 
+# a batch of uint8 images prepared in one launch (include/ext/mgaimage.h: /255, element type, layout, channel order, resize; IMAGE_HEADERS below)
+IMG_SRC_NHWC, IMG_DST_NHWC, IMG_REVERSE_C = 1, 2, 4
+IMG_MAX_C, IMG_TILE_PX, IMG_TILE_W, IMG_TILE_H = 4, 1024, 1024, 64
+
+
+class ImageDesc(C.Structure):                    # mgaimg_desc_t
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p),
+                ("B", C.c_int32), ("C", C.c_int32), ("in_h", C.c_int32), ("in_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("dtype", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Header(NamedTuple):
     """What one file under include/ declares and this module mirrors (tests/test_abi_headers.py holds each record against its header)."""
     symbols: dict        # function -> (restype, argtypes)
@@ -430,10 +441,18 @@ CURVE_HEADERS = {
         structs=dict(mgaap_desc=ApDesc),
         constants=dict(MGAAP_MAX_NC=AP_MAX_NC, MGAAP_TILE=AP_TILE, MGAAP_AP_POINTS=AP_POINTS, MGAAP_CURVE_POINTS=AP_CURVE_POINTS)),
 }
+# the image batch in front of the network (include/ext/mgaimage.h; a table of its own as well; tests/test_abi_image.py)
+IMAGE_HEADERS = {
+    "ext/mgaimage.h": Header(
+        symbols={"mgaimg_run": (_i, [C.POINTER(ImageDesc), C.c_void_p])},
+        structs=dict(mgaimg_desc=ImageDesc),
+        constants=dict(MGAIMG_SRC_NHWC=IMG_SRC_NHWC, MGAIMG_DST_NHWC=IMG_DST_NHWC, MGAIMG_REVERSE_C=IMG_REVERSE_C, MGAIMG_MAX_C=IMG_MAX_C,
+                       MGAIMG_TILE_PX=IMG_TILE_PX, MGAIMG_TILE_W=IMG_TILE_W, MGAIMG_TILE_H=IMG_TILE_H)),
+}
 _TABLES = dict(HEADERS=HEADERS, EXT_HEADERS=EXT_HEADERS, METRIC_HEADERS=METRIC_HEADERS, LAYOUT_HEADERS=LAYOUT_HEADERS,
-               CURVE_HEADERS=CURVE_HEADERS)
+               CURVE_HEADERS=CURVE_HEADERS, IMAGE_HEADERS=IMAGE_HEADERS)
 ALL_HEADERS = {**HEADERS, **EXT_HEADERS, **METRIC_HEADERS}       # the three tables of the descriptors' headers
-_EVERY_HEADER = {**ALL_HEADERS, **LAYOUT_HEADERS, **CURVE_HEADERS}
+_EVERY_HEADER = {**ALL_HEADERS, **LAYOUT_HEADERS, **CURVE_HEADERS, **IMAGE_HEADERS}
 _bound = [name for h in _EVERY_HEADER.values() for name in h.symbols]
 if len(_EVERY_HEADER) != sum(len(t) for t in _TABLES.values()):
     _keys = [k for t in _TABLES.values() for k in t]

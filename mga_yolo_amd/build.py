@@ -35,9 +35,11 @@ INCLUDE = os.path.join(ROOT, "include")
 # is the reference's fp32 expression operation by operation, so no product may be contracted into a fused multiply-add
 # api_confusion.hip: the same for include/ext/mgaconfusion.h, which shares that IoU (csrc/match_common.cuh)
 # api_ap.hip: the same for include/ext/mgaap.h; its fp64 divisions, products and sums are numpy's operation by operation
+# api_image.hip: the same for include/ext/mgaimage.h; the bilinear blend of the image resize is spelled operation by operation, so that both
+# destination layouts give the same bits
 # api_det.hip, api_nms.hip: include/ext/mgamaps.h names "mgadet.h" and "mganms.h" the same way
 UNIT_FLAGS: dict = {"api_match.hip": ["-I", INCLUDE, "-ffp-contract=off"], "api_confusion.hip": ["-I", INCLUDE, "-ffp-contract=off"],
-                    "api_ap.hip": ["-I", INCLUDE, "-ffp-contract=off"],
+                    "api_ap.hip": ["-I", INCLUDE, "-ffp-contract=off"], "api_image.hip": ["-I", INCLUDE, "-ffp-contract=off"],
                     "api_det.hip": ["-I", INCLUDE], "api_nms.hip": ["-I", INCLUDE]}
 
 

@@ -14,7 +14,9 @@ Nothing else in the reference changes.  ``install(nms=True)`` -- opt-in -- also 
 predict.py), so the unchanged ``postprocess`` then runs ``detpost.non_max_suppression``.  ``install(match=True)`` -- opt-in as well -- rebinds
 ``DetectionValidator.update_metrics`` in the reference's ``ultralytics.models.yolo.detect.val`` modules to ``detmatch.update_metrics``: one matching call
 and one read-back per batch; subclasses (``MGAValidator``) reach it through ``super()``.  ``install(ap=True)`` -- opt-in too -- rebinds ``ap_per_class`` in
-the reference's ``ultralytics.utils.metrics`` modules (``DetMetrics.process`` finds it as a module global at call time) to ``detap``'s.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
+the reference's ``ultralytics.utils.metrics`` modules (``DetMetrics.process`` finds it as a module global at call time) to ``detap``'s.
+``install(preprocess=True)`` -- opt-in too -- rebinds ``DetectionTrainer.preprocess_batch`` and ``DetectionValidator.preprocess`` on the reference's classes to
+``image.preprocess_batch`` / ``image.preprocess``: the batch's bytes become the network's input in one launch.  See INTEGRATION.md; ``oracle/check_dropin.py`` runs this against the real factory.
 """
 from __future__ import annotations
 
@@ -45,7 +47,8 @@ def _is_reference_module(name: str) -> bool:
     return any(name == p or name.startswith(p + ".") for p in _PREFIXES) and not name.startswith("mga_yolo_amd")
 
 
-def install(strict: bool = False, nms: bool = False, match: bool = False, confusion: bool = False, ap: bool = False) -> List[str]:
+def install(strict: bool = False, nms: bool = False, match: bool = False, confusion: bool = False, ap: bool = False,
+            preprocess: bool = False) -> List[str]:
     """Rebind the block classes in every loaded reference module that exports them.  Returns the module names patched.
     ``strict=True`` raises unless the module whose ``parse_model`` builds ``MGAModel`` (the one providing
     ``mga_yolo.model.model.DetectionModel``; ``ultralytics.nn.tasks`` when mga_yolo is absent) was patched.
@@ -53,10 +56,14 @@ def install(strict: bool = False, nms: bool = False, match: bool = False, confus
     ``match=True`` ``DetectionValidator.update_metrics`` in its ``ultralytics.models.yolo.detect.val`` modules (see ``_install_match``).
     ``confusion=True`` -- with ``match=True`` only, else ValueError -- sets the switch under which that ``update_metrics`` forms a plotted
     validation's confusion matrix on the device, one call per batch (``detmatch._CONFUSION_ON``; uninstall() clears it).
-    ``ap=True`` also rebinds ``ap_per_class`` in the reference's ``ultralytics.utils.metrics`` modules (see ``_install_ap``)."""
+    ``ap=True`` also rebinds ``ap_per_class`` in the reference's ``ultralytics.utils.metrics`` modules (see ``_install_ap``).
+    ``preprocess=True`` also rebinds ``DetectionTrainer.preprocess_batch`` and ``DetectionValidator.preprocess`` in the reference's
+    ``ultralytics.models.yolo.detect.train`` / ``.val`` modules to ``image``'s: one launch for /255, element type and resize (see
+    ``_install_preprocess``)."""
     if confusion and not match:
         raise ValueError("install(confusion=True) needs match=True: the confusion matrix is formed by the replacement update_metrics")
-    for name in _PRELOAD + (_OPS_PRELOAD if nms else ()) + (_VAL_PRELOAD if match else ()) + (_METRICS_PRELOAD if ap else ()):
+    for name in (_PRELOAD + (_OPS_PRELOAD if nms else ()) + (_VAL_PRELOAD if match else ()) + (_METRICS_PRELOAD if ap else ())
+                 + (_TRAIN_PRELOAD + _VAL_PRELOAD if preprocess else ())):
         if name not in sys.modules:
             try:
                 importlib.import_module(name)
@@ -91,6 +98,8 @@ def install(strict: bool = False, nms: bool = False, match: bool = False, confus
             detmatch._CONFUSION_ON = True
     if ap:
         patched += _install_ap()
+    if preprocess:
+        patched += _install_preprocess()
     if strict:
         need = _factory_module_name()
         if need not in patched:
@@ -167,6 +176,35 @@ def _install_ap() -> List[str]:
         _UNDO.append((name, "ap_per_class", cur))
         mod.ap_per_class = reference_replacement(mod)
         done.append(name)
+    return done
+
+
+_TRAIN_PRELOAD = ("ultralytics.models.yolo.detect.train", "mga_yolo.external.ultralytics.ultralytics.models.yolo.detect.train")
+_TRAIN_SUFFIX = "ultralytics.models.yolo.detect.train"
+
+
+def _install_preprocess() -> List[str]:
+    """Rebind ``DetectionTrainer.preprocess_batch`` in every loaded ``ultralytics.models.yolo.detect.train`` module of the reference and
+    ``DetectionValidator.preprocess`` in every loaded ``...detect.val`` module (two module objects of each file, as of ops.py).  The classes
+    keep their identity, so ``MGATrainer`` and ``MGAValidator`` reach the replacements through ``super()``; the methods they replace are kept
+    in ``image._ORIGINALS``, where the replacements find them for a batch whose ``img`` is not uint8.  uninstall() restores them."""
+    from . import image
+    done = []
+    for suffix, cls_name, attr, new in ((_TRAIN_SUFFIX, "DetectionTrainer", "preprocess_batch", image.preprocess_batch),
+                                        (_VAL_SUFFIX, "DetectionValidator", "preprocess", image.preprocess)):
+        for name, mod in list(sys.modules.items()):
+            if mod is None or not _is_reference_module(name) or not name.endswith(suffix):
+                continue
+            cls = mod.__dict__.get(cls_name, _MISSING)
+            if not isinstance(cls, type):
+                continue
+            cur = cls.__dict__.get(attr, _MISSING)
+            if cur is _MISSING or cur is new:
+                continue
+            _UNDO.append((name + ":" + cls_name, attr, cur))
+            image._ORIGINALS[(cls, attr)] = cur
+            setattr(cls, attr, new)
+            done.append(name)
     return done
 
 
